@@ -13,9 +13,15 @@ in-kernel (Philox).  Data parallel: every rank holds the (replicated) parameters
 4096 rows (weak scaling); the forward has no collective.
 
 Headline arithmetic since round 3: the row-scaled fp16 hi + lo operand format with 3 mean + 1 variance MFMA products
-(--precision fp16x3f; 1.4-1.8e-5 of max|out| against fp64, contract 1e-4); the strict 3 + 3 form (fp16x3, 3e-8), the exact
-fp32 MFMA path and the reduced single-product bf16 mode are timed in the same process as labelled secondary legs.
+(--precision fp16x3f; 1.4-1.8e-5 of max|out| against fp64, contract 1e-4); with --full the strict 3 + 3 form (fp16x3, 3e-8),
+the exact fp32 MFMA path and the reduced single-product bf16 mode are timed in the same process as labelled secondary legs.
 `python bench.py --gpus N` with no launcher starts its own N ranks (spawn_ranks) and reports them ("ranks").
+
+A plain run (no --full) does stages 1 and 2 below for the headline precision and prints the line: no per-step event pass,
+no roofline pass, no secondary, strong-scaling or training legs (unless --train is given), no CPU baseline.  --full adds all
+of them.  --dump-outputs DIR writes what the last timed step of the headline leg returned (the log-probabilities and the
+KL) as DIR/<name>.npy in float32; every timed pass starts from the same Philox offset, so the same arguments give the same
+inputs, the same noise and the same outputs from run to run, however long the settle phase ran.
 
 How the number is taken (round 2; the round-1 line did not reproduce under the driver's command):
   1. W untimed warm-up steps (--warmup, honoured and reported), then warm-up CONTINUES to steady
@@ -43,10 +49,12 @@ How the number is taken (round 2; the round-1 line did not reproduce under the d
   4. the same three stages again with the exact-fp32 MFMA GEMM ("secondary": reference precision) and with the strict
      3 + 3 product fp16 form ("secondary_strict_fp16x3").
   4b. at N > 1: the strong-scaling form (the same 4096 rows split N ways) as "secondary_strong".
-  5. with --train (default at N > 1): the full data-parallel training step (forward, backward,
+  5. with --train (default with --full at N > 1): the full data-parallel training step (forward, backward,
      flat-bucket gradient all-reduce over RCCL, Adam) as "secondary_train".
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with the extra objects
+The per-step distribution of stage 2 and stages 3, 4, 4b and 5 run with --full only (stage 5 also with --train).
+
+Prints ONE JSON line on rank 0 (contract in the task statement); with --full it carries the extra objects
   roofline      dominant kernel (the 80x128-tile dual-moment GEMM) vs the MFMA peak of its dtype; frac_rocprof = the same
                 fraction from the committed rocprofv3 summary of this command (profiles/r03_kernel_stats_bench_default.csv);
   cpu_baseline  the CPU oracle (port of the reference op sequence, as-written B-row z flow) timed
@@ -81,6 +89,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=BATCH, help="rows per GPU (headline: 4096)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the per-step event pass, the roofline pass, the "
+                         "secondary precisions, strong scaling and training (N > 1) legs, the CPU baseline (the --no-* "
+                         "options below switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the headline leg's last step returned as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU-baseline sample")
     ap.add_argument("--no-kernel-events", action="store_true", help="skip the per-kernel roofline pass")
@@ -89,7 +103,7 @@ def parse():
     ap.add_argument("--no-reduced", action="store_true",
                     help="skip the reduced-precision leg (one bf16 product per moment: OUTSIDE the 1e-4 contract)")
     ap.add_argument("--train", dest="train", action="store_true", default=None,
-                    help="also time the data-parallel training step (default: only when N > 1)")
+                    help="also time the data-parallel training step (default: with --full when N > 1)")
     ap.add_argument("--train-timeout", type=int, default=240,
                     help="seconds after which a training leg that has not finished is abandoned (the line is printed without it)")
     ap.add_argument("--no-train", dest="train", action="store_false")
@@ -289,7 +303,7 @@ MAX_ATTEMPTS = 3
 STALL_REGION = 2.0      # a timed region whose mean step is this many times the settled step contains an external stall
 
 
-def timed_region(run_step, steps, sync, step_events, attempts=None, world=1, steady_ms=None):
+def timed_region(run_step, steps, sync, step_events, attempts=None, world=1, steady_ms=None, reset=None):
     """The timed region: barrier + synchronize, EXACTLY `steps` steps enqueued back to back with NOTHING between them,
     barrier + synchronize.  (Until late in round 3 one HIP event marked every step boundary inside the region: an event
     record is a barrier packet on this stack, and the ~3 us bubble behind each of them was 2-3 % of a 0.125 ms step.  The
@@ -299,14 +313,15 @@ def timed_region(run_step, steps, sync, step_events, attempts=None, world=1, ste
     single ~40 ms stall hits a run now and then (round 1's driver line: 37 ms inside one GEMM launch's bracket; a round-2 run
     of the fp32 leg: 48 ms for 20 steps that take 7.7), unrelated to the step being timed.  Every attempt is listed in the
     JSON line ("timed_attempts"); the reported value is the first attempt without a stall (the last one if all have one).
-    With N > 1 all ranks must agree on repeating: the decision is all-reduced (MAX)."""
+    With N > 1 all ranks must agree on repeating: the decision is all-reduced (MAX).
+    ``reset`` (if given) is called ahead of every pass, outside the timed part."""
     while True:
-        elapsed, _ = _timed_region_once(run_step, steps, sync, False)
+        elapsed, _ = _timed_region_once(run_step, steps, sync, False, reset)
         rec = {"ms_per_step": elapsed / steps * 1e3}
         stalled = bool(steady_ms and rec["ms_per_step"] > STALL_REGION * steady_ms)
         per_step = None
         if step_events:
-            _, per_step = _timed_region_once(run_step, steps, sync, True)         # the separate, instrumented pass
+            _, per_step = _timed_region_once(run_step, steps, sync, True, reset)  # the separate, instrumented pass
             srt = sorted(per_step)
             rec["max_step_ms"], rec["median_step_ms"] = srt[-1], srt[len(srt) // 2]
             rec["step_stats_from"] = "a separate pass of the same %d steps with one event per step boundary" % steps
@@ -322,8 +337,10 @@ def timed_region(run_step, steps, sync, step_events, attempts=None, world=1, ste
             return elapsed, per_step
 
 
-def _timed_region_once(run_step, steps, sync, step_events):
+def _timed_region_once(run_step, steps, sync, step_events, reset=None):
     """barrier + synchronize, EXACTLY ``steps`` steps, barrier + synchronize.  Returns (elapsed seconds, per-step ms)."""
+    if reset is not None:
+        reset()
     # Nothing slow may sit between the end of the settle phase and the timed steps: a GPU left idle for milliseconds drops its
     # clocks and 20 steps (2.5 ms) are over before it has them back (measured: a gc.collect() placed here cost the line 10 %).
     # The events are made once, ahead of the first timed region of the process; the collector is off inside the region.
@@ -353,6 +370,23 @@ def step_stats(res, per_step):
         res["ms_per_step_median"] = s[len(s) // 2]
         res["ms_per_step_min"] = s[0]
         res["ms_per_step_max"] = s[-1]
+
+
+DUMP_MAX_BYTES = 64 * 10**6
+
+
+def dump_outputs(path, arrays, max_bytes=DUMP_MAX_BYTES):
+    """Write every array as ``path/<name>.npy`` in float32.  If together they exceed max_bytes, every array with more
+    than one row keeps the same share of its rows, picked by a fixed seed (the same rows on every run)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > max_bytes and a.ndim > 0 and a.shape[0] > 1:
+            keep = max(1, a.shape[0] * max_bytes // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def roofline_pass(ops, run_step, sync, n_steps, launches_per_step):
@@ -432,13 +466,15 @@ def roofline_object(events, precision, ms_per_step, sampled_in):
     return roof, None
 
 
-def forward_leg(args, bnn_amd, ops, net, x, sync, precision, world):
-    """warm-up -> settle -> timed region -> roofline pass for one GEMM precision.  Returns a dict of raw results."""
+def forward_leg(args, bnn_amd, ops, net, x, sync, precision, world, keep_outputs=False):
+    """warm-up -> settle -> timed region -> roofline pass for one GEMM precision.  Returns a dict of raw results; with
+    keep_outputs, "outputs" holds host copies of what the last timed step returned."""
     net.set_precision(precision)
+    last = {}
 
     def step():
-        out = net(x, sample=True)
-        return out, net.kl()
+        last["out"], last["kl"] = net(x, sample=True), net.kl()
+        return last["out"], last["kl"]
 
     leg = {}
     with torch.no_grad():
@@ -467,14 +503,21 @@ def forward_leg(args, bnn_amd, ops, net, x, sync, precision, world):
             leg["launch_fallback_reason"] = "%s: %s" % (type(exc).__name__, str(exc)[:200])
         if not args.no_step_events:
             _event_pool(args.steps + 1)                      # (made before the settle phase, not between it and the timed region)
+        # the Philox offset (on the device) as it stands after the warm-up: every timed pass starts from it, so the last
+        # step's outputs do not depend on how many steps the settle phase took
+        rng = ops.RngState.get(x.device).t
+        rng0 = rng[:2].clone()
         leg["settle"] = settle(run, world)
         leg["attempts"] = []
         elapsed, per_step = timed_region(run, args.steps, sync, not args.no_step_events, leg["attempts"], world,
-                                         steady_ms=leg["settle"]["last_blocks_ms_per_step"][-1])
+                                         steady_ms=leg["settle"]["last_blocks_ms_per_step"][-1],
+                                         reset=lambda: rng[:2].copy_(rng0))
         if leg["launch"] == "eager":
-            out, kl = step()
+            out, kl = last["out"], last["kl"]
         sync()
         assert torch.isfinite(out).all() and torch.isfinite(kl)
+        if keep_outputs:
+            leg["outputs"] = {"log_probs": out.float().cpu().numpy(), "kl": kl.float().cpu().numpy()}
         t = torch.tensor([elapsed], device=x.device, dtype=torch.float64)
         if world > 1:
             import torch.distributed as dist
@@ -680,6 +723,9 @@ def pick_backend(world, ndev):
 
 def main():
     args = parse()
+    if not args.full:
+        # a plain run measures the headline figure and nothing else
+        args.no_step_events = args.no_kernel_events = args.no_secondary = args.no_reduced = args.no_cpu_baseline = True
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher: start the ranks ourselves (before anything in this process touches the GPU)
         raise SystemExit(spawn_ranks(args.gpus))
@@ -695,7 +741,7 @@ def main():
     dev_index = local_rank if (backend == "nccl" or local_rank < ndev) else local_rank % max(ndev, 1)
     torch.cuda.set_device(dev_index)
     dev = torch.device("cuda", dev_index)
-    want_train = args.train if args.train is not None else world > 1
+    want_train = args.train if args.train is not None else (args.full and world > 1)
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         if backend == "nccl":
@@ -725,7 +771,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    legs = {args.precision: forward_leg(args, bnn_amd, ops, net, x, sync, args.precision, world)}
+    legs = {args.precision: forward_leg(args, bnn_amd, ops, net, x, sync, args.precision, world,
+                                        keep_outputs=bool(args.dump_outputs))}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, legs[args.precision].pop("outputs"))
     if args.precision != "fp32" and not args.no_secondary:
         legs["fp32"] = forward_leg(args, bnn_amd, ops, net, x, sync, "fp32", world)
         if args.precision != "fp16x3" and world == 1:

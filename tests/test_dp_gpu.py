@@ -168,7 +168,7 @@ def test_bench_gpus2_self_spawned_ranks_report_themselves():
     control flow and the "ranks" record -- not a rate."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                        "--no-secondary", "--no-kernel-events"],
+                        "--full", "--no-secondary", "--no-kernel-events"],
                        capture_output=True, text=True, timeout=900, env=env)
     _keep("bench_gpus2_selfspawn", r)
     assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
@@ -192,7 +192,7 @@ def test_bench_training_leg_watchdog_keeps_the_headline():
     watchdog ends it)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                        "--no-secondary", "--no-kernel-events", "--train-timeout", "0"],
+                        "--full", "--no-secondary", "--no-kernel-events", "--train-timeout", "0"],
                        capture_output=True, text=True, timeout=900, env=env)
     _keep("bench_train_watchdog", r)
     assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-3000:])

@@ -1991,7 +1991,7 @@ def test_propagate_flow_standalone_autograd_1d(bnn, dev, kind):
 
 @pytest.mark.gpu
 def test_bench_contract_json_line():
-    """bench.py, run exactly as the driver runs it (--gpus 1 --steps 20 --warmup 5; only the CPU-baseline budget is cut):
+    """bench.py --full, run as the driver runs it (--gpus 1 --steps 20 --warmup 5; only the CPU-baseline budget is cut):
     ONE JSON line with the contract keys, a roofline that is consistent with the timed region, an fp32 secondary leg,
     and a headline within 25 % of the committed reference run of the same command (profiles/r03_bench_driver_cmd.json: round
     3's row-scaled fp16 format, 27.9 M samples/s; round 2's bf16x3 line read 24.7-24.9 M) -- round 1's driver line (2.05 ms/step
@@ -2000,7 +2000,7 @@ def test_bench_contract_json_line():
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                        "--cpu-seconds", "2"], capture_output=True, text=True, timeout=600, cwd=root)
+                        "--full", "--cpu-seconds", "2"], capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1
@@ -2039,6 +2039,40 @@ def test_bench_contract_json_line():
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in cb, k
     assert cb["kind"] == "port" and cb["value"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_the_same_outputs(tmp_path):
+    """bench.py without --full times the headline and nothing else: the line has the contract keys and none of the extra
+    legs, --steps is the number of timed steps.  --dump-outputs writes the last timed step's log-probabilities and KL in
+    float32, and two runs with the same arguments write the same bits (every timed pass starts from the same Philox
+    offset, however many steps the settle phase took)."""
+    import json, os, subprocess, sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "3",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
+        assert len(lines) == 1
+        res = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "settle"):
+            assert k in res, k
+        assert res["steps"] == 12 and res["warmup"] == 3 and res["higher_is_better"] is True
+        assert abs(res["value"] - 4096 / (res["ms_per_step"] * 1e-3)) / res["value"] < 1e-6
+        for k in ("roofline", "secondary", "secondary_strict_fp16x3", "secondary_reduced_bf16", "secondary_train",
+                  "cpu_baseline", "ms_per_step_median"):
+            assert k not in res, k
+        assert sorted(os.listdir(d)) == ["kl.npy", "log_probs.npy"]
+        lp, kl = np.load(d / "log_probs.npy"), np.load(d / "kl.npy")
+        assert lp.dtype == np.float32 and lp.shape == (4096, 10) and kl.dtype == np.float32 and kl.size == 1
+        assert np.isfinite(lp).all() and np.isfinite(kl).all()
+        assert np.abs(np.log(np.exp(lp.astype(np.float64)).sum(axis=1))).max() < 1e-4      # rows are log-softmax
+        dumps.append((lp, kl))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])
 
 
 @pytest.mark.gpu
