@@ -139,6 +139,17 @@ class GateBwdArgs(ctypes.Structure):
                [("O", c_i), ("I", c_i), ("exact", c_i), ("layer_id", c_u32)]
 
 
+class GateDrawArgs(ctypes.Structure):
+    """lbbnn_gate_draw_args_t"""
+    _fields_ = [("g", GateArgs), ("lambdal", c_p), ("gammas", c_p), ("alpha", c_p), ("tau_w", c_p), ("tau_b", c_p),
+                ("temperature", ctypes.c_float)]
+
+
+class GateBwdDrawArgs(ctypes.Structure):
+    """lbbnn_gate_bwd_draw_args_t"""
+    _fields_ = [("g", GateBwdArgs), ("lambdal", c_p), ("d_lambdal", c_p), ("temperature", ctypes.c_float)]
+
+
 class OutGradArgs(ctypes.Structure):
     """lbbnn_outgrad_args_t"""
     _fields_ = [(n, c_p) for n in ("g_out", "out", "std", "eps", "rng", "gm", "gv", "gmT", "gvT", "g_sum", "gv_sum", "work")] + \
@@ -262,6 +273,11 @@ SIGNATURES = {
     "lbbnn_weight_operands_t": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     "lbbnn_rng_advance": (c_i, [c_p, c_u64, c_p]),
     "lbbnn_philox_normal": (c_i, [c_p, c_u32, c_i64, c_i64, c_i64, c_p, c_p]),
+    "lbbnn_gate_sample_draw": (c_i, [ctypes.POINTER(GateDrawArgs), c_p, c_p]),
+    "lbbnn_gate_backward_draw": (c_i, [ctypes.POINTER(GateBwdDrawArgs), c_p, c_p]),
+    "lbbnn_philox_uniform": (c_i, [c_p, c_u32, c_i64, c_i64, c_i64, c_p, c_p]),
+    "lbbnn_philox_std_gamma": (c_i, [c_p, c_u32, c_p, c_p, c_i64, c_p, c_p]),
+    "lbbnn_gamma_grad": (c_i, [c_p, c_p, c_i64, c_p, c_p]),
     "lbbnn_elbo_loss": (c_i, [c_p, c_i, c_p, c_i, c_i, c_p, ctypes.c_float, c_p, c_p]),
     "lbbnn_elbo_loss_backward": (c_i, [c_p, c_p, c_i, c_i, ctypes.c_float, c_p, c_p, c_p]),
     "lbbnn_elbo_loss_backward_logits": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, ctypes.c_float, c_p, c_p, c_p, c_p]),

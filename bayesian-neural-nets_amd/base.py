@@ -137,6 +137,85 @@ class _BaseFn(torch.autograd.Function):
                 outs["d_alpha"], None, *[grads[n] for n in layer._names])
 
 
+class _BaseDrawFn(torch.autograd.Function):
+    """``sample_elbo(draws="hip")``: one node per layer, parameters in, (out, log_prior, log_q) out.  Forward:
+    lbbnn_gate_sample_draw (gates, tau_w, tau_b and eps from the Philox snapshot ``rng``; W and the four log-probability sums)
+    + the mean-only GEMM with the layer's activation in its epilogue (ReLU, or the head's log_softmax).  Backward: the
+    log_softmax / ReLU mask + G^T + column sums (lbbnn_output_grad, or the loss's own logits gradient) -> dW = G^T x ->
+    lbbnn_gate_backward_draw (every parameter gradient, d lambdal through the gate and through alpha, the Gamma
+    reparameterisation terms) -> dX = G W.  No torch distribution and no sigmoid autograd on the path."""
+
+    @staticmethod
+    def forward(ctx, layer, x, rng, act, *params):
+        out, lp, lq, keep = layer._forward_hip_draws(x, rng, act)
+        ctx.layer, ctx.act, ctx.rng, ctx.keep = layer, act, rng, keep
+        from . import graphs
+        graphs.mark_autograd_node(ctx, layer)          # capture guard: graphs.assert_no_live_graph
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, out, keep["tau_w"], keep["tau_b"], *params)
+        return out, lp, lq
+
+    @staticmethod
+    def backward(ctx, g_out, g_lp, g_lq):
+        from .layers import _hip_matmul_nt
+        layer, act, keep = ctx.layer, ctx.act, ctx.keep
+        x, out, tau_w, tau_b, *params = ctx.saved_tensors
+        P = dict(zip(layer._names, params))
+        O, I, dev = layer.out_features, layer.in_features, x.device
+        f = dict(dtype=torch.float32, device=dev)
+        if g_out is None:
+            g_out = torch.zeros_like(out)
+        if act == "log_softmax":
+            from . import losses
+            ent = losses._LOGITS_GRAD.pop(out.data_ptr(), None)
+            if ent is not None and ent[0] == g_out.data_ptr():
+                g_out = ent[1]                                 # formed by the loss's own backward launch
+            else:
+                g_out = ops.log_softmax_backward(g_out, out)
+        relu = act == "relu"
+        want_gx = bool(ctx.needs_input_grad[1])
+        gm, _, gmT, _, g_sum, _ = ops.output_grad(g_out.contiguous(), out=out if relu else None, relu=relu, want_g=want_gx)
+        dW = _hip_matmul_nt(gmT, ops.transpose_operand, x)                       # (O,I) = G^T x
+        a = _lib.GateBwdDrawArgs()
+        b = a.g
+        kept = []
+
+        def dptr(t):
+            if t is None:
+                return None
+            u = t.detach()
+            if u.dtype != torch.float32 or not u.is_contiguous():
+                u = u.float().contiguous()
+            kept.append(u)
+            return ops._ptr(u, "tensor")
+        b.mu, b.rho = dptr(P["weight_mu"]), dptr(P["weight_rho"])
+        b.bias_mu, b.bias_rho, b.bias_a, b.bias_b = dptr(P["bias_mu"]), dptr(P["bias_rho"]), dptr(P["bias_a"]), dptr(P["bias_b"])
+        b.tau_b, b.tau_w = dptr(tau_b), dptr(tau_w)
+        b.weight_a, b.weight_b, b.pa, b.pb = dptr(P["weight_a"]), dptr(P["weight_b"]), dptr(P["pa"]), dptr(P["pb"])
+        b.dW, b.g_sum = dW.data_ptr(), g_sum.data_ptr()
+        b.g_lp = dptr(g_lp.reshape(1)) if g_lp is not None else None
+        b.g_lq = dptr(g_lq.reshape(1)) if g_lq is not None else None
+        d_mu, d_rho, d_lam = (torch.empty((O, I), **f) for _ in range(3))
+        w_out = torch.empty((O, I), **f) if want_gx else None
+        vecs = {n: torch.empty(O, **f) for n in ("d_bias_mu", "d_bias_rho", "d_bias_a", "d_bias_b")}
+        scal, rows = torch.empty(5, **f), torch.empty(3 * O, **f)
+        b.d_mu, b.d_rho = d_mu.data_ptr(), d_rho.data_ptr()
+        b.w_out = w_out.data_ptr() if w_out is not None else None
+        for n, t in vecs.items():
+            setattr(b, n, t.data_ptr())
+        b.d_scalars, b.rows = scal.data_ptr(), rows.data_ptr()
+        b.O, b.I, b.exact, b.layer_id = O, I, keep["exact"], layer._layer_id
+        a.lambdal, a.d_lambdal, a.temperature = dptr(P["lambdal"]), d_lam.data_ptr(), keep["T"]
+        _lib.check(_lib.lib().lbbnn_gate_backward_draw(ctypes.byref(a), ctx.rng.data_ptr(), ops._stream()),
+                   "lbbnn_gate_backward_draw")
+        del kept
+        gx = _hip_matmul_nt(gm, ops.transpose_operand, w_out) if want_gx else None   # G W
+        grads = {"weight_mu": d_mu, "weight_rho": d_rho, "weight_a": scal[0:1], "weight_b": scal[1:2], "lambdal": d_lam,
+                 "pa": scal[3:4], "pb": scal[4:5], "bias_mu": vecs["d_bias_mu"], "bias_rho": vecs["d_bias_rho"],
+                 "bias_a": vecs["d_bias_a"], "bias_b": vecs["d_bias_b"]}
+        return (None, gx, None, None, *[grads[n] for n in layer._names])
+
+
 class BayesianLinear(nn.Module):
     _names = ("weight_mu", "weight_rho", "weight_a", "weight_b", "lambdal", "pa", "pb",
               "bias_mu", "bias_rho", "bias_a", "bias_b")
@@ -224,6 +303,69 @@ class BayesianLinear(nn.Module):
             st.advance(1)
         saved["cg"] = cg
         return out, lp, lq, saved
+
+    def _forward_hip_draws(self, x, rng, act):
+        """lbbnn_gate_sample_draw + the mean-only GEMM (act: None, "relu" or "log_softmax" in its epilogue).  Returns out,
+        lp, lq and the kernel-written buffers; every draw comes from the Philox state ``rng`` (2 int64 words on the device)."""
+        from . import distributions
+        ws = self._workspace()
+        dev = x.device
+        O, I = self.out_features, self.in_features
+        split = (ops.split_precision() and ops.split_eligible(I, O)
+                 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0)
+        f = dict(dtype=torch.float32, device=dev)
+        P = lambda t: ops._ptr(t.detach(), "tensor")
+        keep = {"gammas": torch.empty((O, I), **f), "alpha": torch.empty((O, I), **f), "tau_w": torch.empty(1, **f),
+                "tau_b": torch.empty(O, **f), "T": float(distributions.TEMPER_PRIOR), "exact": self._exact_bits()}
+        bias = torch.empty(O, **f)
+        lp, lq = torch.empty((), **f), torch.empty((), **f)
+        a = _lib.GateDrawArgs()
+        g = a.g
+        g.mu, g.rho, g.bias_mu, g.bias_rho = P(self.weight_mu), P(self.weight_rho), P(self.bias_mu), P(self.bias_rho)
+        g.bias_a, g.bias_b = P(self.bias_a), P(self.bias_b)
+        g.weight_a, g.weight_b, g.pa, g.pb = P(self.weight_a), P(self.weight_b), P(self.pa), P(self.pb)
+        g.w_out, g.bias_out, g.rows = ws["w"].data_ptr(), bias.data_ptr(), ws["rows"].data_ptr()
+        g.log_prior, g.log_q = lp.data_ptr(), lq.data_ptr()
+        g.O, g.I, g.ld, g.mode, g.exact, g.want_lp = O, I, ops.operand_ld(I), 0, keep["exact"], 1
+        g.flags, g.layer_id = (ops.F_SPLIT16 if split else 0), self._layer_id
+        a.lambdal = P(self.lambdal)
+        a.gammas, a.alpha = keep["gammas"].data_ptr(), keep["alpha"].data_ptr()
+        a.tau_w, a.tau_b, a.temperature = keep["tau_w"].data_ptr(), keep["tau_b"].data_ptr(), keep["T"]
+        _lib.check(_lib.lib().lbbnn_gate_sample_draw(ctypes.byref(a), rng.data_ptr(), ops._stream()), "lbbnn_gate_sample_draw")
+        self._last_keep = keep
+        out = ops.lrt_gemm(x, ws["w"], None, I=I, O=O, bias_mean=bias, mean_only=True, split=split,
+                           relu=(act == "relu"), log_softmax=(act == "log_softmax"))                       # F.linear :255
+        return out, lp, lq, keep
+
+    def sample_forward(self, input, *, activation=None, rng=None):
+        """The training-mode forward (sample=True, with log-probabilities) of ``sample_elbo(draws="hip")`` for one layer: the
+        gates, tau_w, tau_b and the weight / bias noise are drawn inside the HIP kernels from the layer's Philox state.
+        ``activation``: None, "relu" or "log_softmax" (out_features <= 16), applied in the GEMM epilogue.  ``rng``: a
+        {seed, offset} snapshot (2 int64 on the device) to draw from; default: the device's ``ops.RngState``, which this call
+        then advances by one.  Sets ``gammas``, ``alpha``, ``gamma.alpha``, ``tau_w``, ``tau_b``, ``log_prior`` and
+        ``log_variational_posterior`` (detached tensors the kernels wrote).  Returns (out, log_prior, log_q), autograd-visible."""
+        if not input.is_cuda:
+            raise RuntimeError("bnn_amd: forward needs a HIP device tensor (input is on %s); there is no CPU path"
+                               % input.device)
+        if activation not in (None, "relu", "log_softmax"):
+            raise ValueError("bnn_amd: activation must be None, 'relu' or 'log_softmax', got %r" % (activation,))
+        if activation == "log_softmax" and self.out_features > 16:
+            raise ValueError("bnn_amd: the fused log_softmax needs out_features <= 16")
+        if rng is None:
+            st = ops.RngState.get(input.device)
+            rng = st.t[:2].clone()
+            st.advance(1)
+        x = input.float()
+        params = [getattr(self, n) for n in self._names]
+        out, lp, lq = _BaseDrawFn.apply(self, x, rng, activation, *params)
+        self._publish_draws(lp, lq)
+        return out, lp, lq
+
+    def _publish_draws(self, lp, lq):
+        keep = self._last_keep
+        self.gammas, self.alpha, self.tau_w, self.tau_b = keep["gammas"], keep["alpha"], keep["tau_w"], keep["tau_b"]
+        self.gamma.alpha = keep["alpha"]
+        self.log_prior, self.log_variational_posterior = lp.detach(), lq.detach()
 
     def _mean_branch_autograd(self, x, cgamma, tau_w, tau_b, mode):
         """LBBNN-GP-MF.py:236-255 for the two deterministic branches, as autograd-visible torch ops (GPU tensors)."""
@@ -315,11 +457,19 @@ class BayesianNetwork(nn.Module):
         return (self.l1.log_variational_posterior + self.l2.log_variational_posterior
                 + self.l3.log_variational_posterior)
 
-    def sample_elbo(self, input, target, samples=SAMPLES, *, num_batches=None):
+    def sample_elbo(self, input, target, samples=SAMPLES, *, num_batches=None, draws="torch"):
         """:285-319, same positional arguments.  NUM_BATCHES / SAMPLES are module globals there (:34-67) and here
-        (``bnn_amd.base.NUM_BATCHES = 600``, ``SAMPLES = 1``); ``num_batches=`` overrides the former per call."""
+        (``bnn_amd.base.NUM_BATCHES = 600``, ``SAMPLES = 1``); ``num_batches=`` overrides the former per call.
+        ``draws``: "torch" (default) draws the gates and the Gamma precisions with torch.distributions, as the reference;
+        "hip" draws every stochastic input of the step inside the HIP kernels from the Philox state (``ops.RngState``,
+        reseeded by ``torch.manual_seed``), reads nothing back to the host, and can be captured
+        (``graphs.make_graphed_train_step``).  The two agree in distribution, not bit for bit."""
+        if draws not in ("torch", "hip"):
+            raise ValueError("bnn_amd: sample_elbo(draws=...) must be 'torch' or 'hip', got %r" % (draws,))
         if num_batches is None:
             num_batches = NUM_BATCHES
+        if draws == "hip":
+            return self._sample_elbo_hip(input, target, samples, num_batches)
         dev = input.device
         lps, lqs, nlls = [], [], []
         for _ in range(samples):
@@ -335,5 +485,38 @@ class BayesianNetwork(nn.Module):
         log_prior = torch.stack(lps).mean()
         log_q = torch.stack(lqs).mean()
         nll = torch.stack(nlls).mean()
+        loss = nll + (log_q - log_prior) / num_batches                # :318
+        return loss, log_prior, log_q, nll
+
+    def _sample_elbo_hip(self, input, target, samples, num_batches):
+        """sample_elbo(draws="hip"): per sample one Philox snapshot (the offset advances once), one _BaseDrawFn node per
+        layer with ReLU / log_softmax in the GEMM epilogues, the NLL as one launch (losses.elbo_loss)."""
+        from .losses import elbo_loss
+        if not input.is_cuda:
+            raise RuntimeError("bnn_amd: sample_elbo(draws='hip') needs a HIP device tensor (input is on %s); there is no "
+                               "CPU path" % input.device)
+        x = input.view(-1, self.dims[0]).float()
+        st = ops.RngState.get(input.device)
+        layers = (self.l1, self.l2, self.l3)
+        head = "log_softmax" if self.dims[-1] <= 16 else None
+        lps, lqs, nlls = [], [], []
+        for _ in range(samples):
+            rng = st.t[:2].clone()
+            st.advance(1)
+            h, lp, lq = x, None, None
+            for k, l in enumerate(layers):
+                h, lp_l, lq_l = _BaseDrawFn.apply(l, h, rng, "relu" if k < 2 else head, *[getattr(l, n) for n in l._names])
+                l._publish_draws(lp_l, lq_l)
+                lp = lp_l if lp is None else lp + lp_l
+                lq = lq_l if lq is None else lq + lq_l
+            if head is None:
+                h = F.log_softmax(h, dim=1)
+            lps.append(lp)
+            lqs.append(lq)
+            nlls.append(elbo_loss(h, target))
+        if samples == 1:
+            log_prior, log_q, nll = lps[0], lqs[0], nlls[0]
+        else:
+            log_prior, log_q, nll = torch.stack(lps).mean(), torch.stack(lqs).mean(), torch.stack(nlls).mean()
         loss = nll + (log_q - log_prior) / num_batches                # :318
         return loss, log_prior, log_q, nll

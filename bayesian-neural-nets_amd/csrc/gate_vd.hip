@@ -33,21 +33,118 @@ __device__ __forceinline__ void store_operand(void* base, int split, size_t O, i
     (void)O;
 }
 
+
+// ------------------------------------------------------------------------------------------------ in-kernel draws of K6 / K6b
+// (lbbnn_gate_sample_draw / lbbnn_gate_backward_draw, include/lbbnn.h)
+constexpr float kProbEps = 1.1920928955078125e-7f;      // torch.finfo(float32).eps: clamp_probs
+constexpr float kTiny = 1.17549435082228750797e-38f;    // torch.finfo(float32).tiny: _clipped_sigmoid, Gamma.rsample
+
+// 24 random bits -> (k + 0.5) 2^-24: strictly inside (0, 1), exact in fp32
+__device__ __forceinline__ float uniform24(uint32_t r) { return ((float)(r >> 8) + 0.5f) * 5.9604644775390625e-8f; }
+
+__device__ __forceinline__ float gate_u(uint64_t seed, uint64_t offs, uint32_t layer, int o, int i) {
+    const Philox4 r = philox_bits4(seed, offs, LBBNN_STREAM_GATE * 64u + layer, (uint64_t)o, (uint32_t)(i >> 2));
+    const uint32_t b = (i & 3) == 0 ? r.x : (i & 3) == 1 ? r.y : (i & 3) == 2 ? r.z : r.w;
+    return uniform24(b);
+}
+
+// RelaxedBernoulli(probs = al, temperature = T).rsample() given its uniform (torch: LogitRelaxedBernoulli.rsample + the
+// clipped SigmoidTransform); hard: Bernoulli(al).sample() as u < al.  *dcda: dc/d al (0 where a clamp is active).
+__device__ __forceinline__ float gate_draw(float al, float u, float T, bool hard, float* dcda) {
+    if (hard) { *dcda = 0.f; return u < al ? 1.f : 0.f; }
+    const float p = fminf(fmaxf(al, kProbEps), 1.f - kProbEps);
+    const float uc = fminf(fmaxf(u, kProbEps), 1.f - kProbEps);
+    const float z = (((logf(uc) - log1pf(-uc)) + logf(p)) - log1pf(-p)) / T;
+    const float s = 1.f / (1.f + expf(-z));
+    const float c = fminf(fmaxf(s, kTiny), 1.f - kProbEps);
+    const bool in = (al >= kProbEps && al <= 1.f - kProbEps) && (s >= kTiny && s <= 1.f - kProbEps);
+    *dcda = in ? (c * (1.f - c)) / (T * (p * (1.f - p))) : 0.f;
+    return c;
+}
+
+// Standard Gamma(a) of element `e` (Marsaglia & Tsang, ACM TOMS 26(3), 2000): attempt k uses Philox counter (e, k) -- one
+// normal (Box-Muller on words x, y, the same hardware forms as philox_normal4), the acceptance uniform (z) and, for a < 1,
+// the boost uniform U^(1/a) of the accepted attempt (w).  At most LBBNN_GAMMA_MAX_ATTEMPTS attempts (one is rejected with
+// probability < 0.05 for every a, so the bound is never reached in practice; if it were, the draw would be the mode-like
+// d = a' - 1/3).  NaN, non-positive or infinite a: NaN.
+__device__ __forceinline__ float std_gamma_draw(float a, uint64_t seed, uint64_t offs, uint32_t stream, uint64_t e) {
+    if (!(a > 0.f) || !(a < INFINITY)) return __builtin_nanf("");
+    const bool boost = a < 1.f;
+    const float ap = boost ? a + 1.f : a;
+    const float d = ap - 0.33333334f, c = 1.f / sqrtf(9.f * d);
+    float x = d, ub = 1.f;
+    for (int k = 0; k < LBBNN_GAMMA_MAX_ATTEMPTS; ++k) {
+        const Philox4 r = philox_bits4(seed, offs, stream, e, (uint32_t)k);
+        const float u0 = ((float)r.x + 1.0f) * 2.3283064365386963e-10f, u1 = (float)r.y * 2.3283064365386963e-10f;
+        const float n = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u0)) * __builtin_amdgcn_cosf(u1);
+        const float w = c * n;
+        if (w <= -1.f) continue;
+        const float v = (1.f + w) * (1.f + w) * (1.f + w);
+        if (logf(uniform24(r.z)) < 0.5f * n * n + d * ((1.f - v) + 3.f * log1pf(w))) {
+            x = d * v;
+            ub = uniform24(r.w);
+            break;
+        }
+    }
+    if (boost) x *= expf(logf(ub) / a);
+    return x;
+}
+// Gamma(a, rate) as torch's Gamma.rsample returns it: standard draw / rate, clamped below at FLT_MIN (NaN stays NaN)
+__device__ __forceinline__ float gamma_rate_draw(float a, float rate, uint64_t seed, uint64_t offs, uint32_t stream, uint64_t e) {
+    const float t = std_gamma_draw(a, seed, offs, stream, e) / rate;
+    return (t < kTiny) ? kTiny : t;
+}
+
+__device__ __forceinline__ double digamma_d(double x) {
+    double r = 0.0;
+    for (int k = 0; k < 16 && x < 10.0; ++k) { r -= 1.0 / x; x += 1.0; }
+    const double i = 1.0 / x, i2 = i * i;
+    return r + log(x) - 0.5 * i - i2 * (1.0 / 12 - i2 * (1.0 / 120 - i2 * (1.0 / 252 - i2 * (1.0 / 240 - i2 * (1.0 / 132)))));
+}
+// g(x, a) = dx/da of the standard Gamma draw = -(dP(a, x)/da) / f(x; a).  From P(a, x) = e^-x sum_n x^(a+n) / Gamma(a+n+1):
+// dP/da = e^-x sum_n x^(a+n) / Gamma(a+n+1) (log x - psi(a+n+1)), and the n-th term over f is (x/a) s_n with s_0 = 1,
+// s_n = s_(n-1) x / (a+n) -- no exp / lgamma, no underflow.  fp64; the terms change sign once, so the relative error is about
+// 1e-16 / Q(a, x) (Q = 1 - P): far-right-tail x lose digits, x with Q > 1e-9 keep at least seven.
+__device__ __forceinline__ float gamma_grad_one(float xf, float af) {
+    if (!(af > 0.f) || !(af < INFINITY) || xf != xf) return __builtin_nanf("");
+    if (!(xf > 0.f)) return 0.f;
+    const double x = xf, a = af, lx = log(x);
+    double psi = digamma_d(a + 1.0), s = 1.0;
+    double sum = lx - psi, mag = fabs(sum);
+    for (int n = 1; n < 8192; ++n) {
+        psi += 1.0 / (a + n);
+        s *= x / (a + n);
+        const double t = s * (lx - psi);
+        sum += t;
+        mag += fabs(t);
+        if (x < a + n && fabs(t) <= 1e-17 * mag) break;
+    }
+    return (float)(-(x / a) * sum);
+}
+
 // ------------------------------------------------------------------------------------------------ K6
 // One workgroup per output row; rows[0..3][o] = row sums of
 //   0: GaussGamma weight integrand (without the scalar C*gamma part folded: kept exact as the reference sums it)
 //   1: BetaBinomial integrand      2: Gaussian.full_log_prob integrand     3: Bernoulli.log_prob integrand
-__global__ __launch_bounds__(256) void gate_sample_kernel(const lbbnn_gate_args_t a, const uint64_t* rng) {
+template <bool DRAW>
+__global__ __launch_bounds__(256) void gate_sample_kernel(const lbbnn_gate_draw_args_t dr, const uint64_t* rng) {
+    const lbbnn_gate_args_t& a = dr.g;
     __shared__ double red[4][4];
     const int o = blockIdx.x, tid = threadIdx.x;
     const size_t ro = (size_t)o * a.I;
     const int split = (a.flags & LBBNN_F_SPLIT16) ? 1 : 0;
     uint64_t seed = 0, offs = 0;
-    if (a.mode == LBBNN_MODE_SAMPLE && !a.eps_w) { seed = rng[0]; offs = rng[1]; }
+    if (DRAW || (a.mode == LBBNN_MODE_SAMPLE && !a.eps_w)) { seed = rng[0]; offs = rng[1]; }
     float C = 0.f, cbb = 0.f, pa = 0.f, pb = 0.f, tau = 0.f;
     if (a.want_lp) {
         const float wa = a.weight_a[0], wb = a.weight_b[0];
-        tau = a.tau_w[0];
+        if (DRAW) {
+            // every workgroup draws the same tau_w (a deterministic function of the state): no launch ahead of this one
+            tau = gamma_rate_draw(wa, wb, seed, offs, LBBNN_STREAM_GAMMA_W * 64u + a.layer_id, 0);
+            if (o == 0 && tid == 0) dr.tau_w[0] = tau;
+        } else {
+            tau = a.tau_w[0];
+        }
         // a*log(b) + (a-0.5)*tau - b*tau - lgamma(a) - 0.5*log(2*pi)      LBBNN-GP-MF.py:144-145
         C = wa * logf(wb) + (wa - 0.5f) * tau - wb * tau - lgammaf(wa) - 0.5f * 1.8378770664093453f;
         pa = a.pa[0]; pb = a.pb[0];
@@ -59,7 +156,16 @@ __global__ __launch_bounds__(256) void gate_sample_kernel(const lbbnn_gate_args_
         float w = 0.f;
         if (i < a.I) {
             const float mu = a.mu[ro + i];
-            const float g = a.cgamma ? a.cgamma[ro + i] : 1.f;
+            float g, al = 0.f;
+            if (DRAW) {
+                al = sigmoid_ref(dr.lambdal[ro + i]);
+                float dcda;
+                g = gate_draw(al, gate_u(seed, offs, a.layer_id, o, i), dr.temperature, (a.exact & 8) != 0, &dcda);
+                dr.gammas[ro + i] = g;
+                if (dr.alpha) dr.alpha[ro + i] = al;
+            } else {
+                g = a.cgamma ? a.cgamma[ro + i] : 1.f;
+            }
             float sigma = 0.f;
             if (a.mode == LBBNN_MODE_SAMPLE) {
                 float e;
@@ -81,7 +187,7 @@ __global__ __launch_bounds__(256) void gate_sample_kernel(const lbbnn_gate_args_
                 const float d = w - mu;
                 const float lp = -0.9189385332046727f - logf(sigma) - (d * d) / (2.f * sigma * sigma);   // :94-97
                 s_fq += (double)logf(g * expf(lp) + (1.f - g) + 1e-8f);                              // :99-101
-                const float al = a.gamma_alpha[ro + i];
+                if (!DRAW) al = a.gamma_alpha[ro + i];
                 const float g_be = (a.exact & 8) ? rintf(g) : g;
                 s_be += (double)(g_be * logf(al + 1e-8f) + (1.f - g_be) * logf(1.f - al + 1e-8f));   // :125-127
             }
@@ -98,11 +204,13 @@ __global__ __launch_bounds__(256) void gate_sample_kernel(const lbbnn_gate_args_
 }
 
 // bias sample + bias log-probabilities + final scalars (single workgroup)
-__global__ __launch_bounds__(256) void gate_finalize_kernel(const lbbnn_gate_args_t a, const uint64_t* rng) {
+template <bool DRAW>
+__global__ __launch_bounds__(256) void gate_finalize_kernel(const lbbnn_gate_draw_args_t dr, const uint64_t* rng) {
+    const lbbnn_gate_args_t& a = dr.g;
     __shared__ double scratch[4];
     const int tid = threadIdx.x;
     uint64_t seed = 0, offs = 0;
-    if (a.mode == LBBNN_MODE_SAMPLE && !a.eps_b) { seed = rng[0]; offs = rng[1]; }
+    if (DRAW || (a.mode == LBBNN_MODE_SAMPLE && !a.eps_b)) { seed = rng[0]; offs = rng[1]; }
     double r0 = 0, r1 = 0, r2 = 0, r3 = 0, gb = 0, qb = 0;
     for (int o = tid; o < a.O; o += 256) {
         const float sb = softplus_ref(a.bias_rho[o]);
@@ -117,7 +225,10 @@ __global__ __launch_bounds__(256) void gate_finalize_kernel(const lbbnn_gate_arg
         if (a.want_lp) {
             r0 += (double)a.rows[o]; r1 += (double)a.rows[(size_t)a.O + o];
             r2 += (double)a.rows[2 * (size_t)a.O + o]; r3 += (double)a.rows[3 * (size_t)a.O + o];
-            const float ba = a.bias_a[o], bb = a.bias_b[o], tb = a.tau_b[o];
+            const float ba = a.bias_a[o], bb = a.bias_b[o];
+            float tb;
+            if (DRAW) { tb = gamma_rate_draw(ba, bb, seed, offs, LBBNN_STREAM_GAMMA_B * 64u + a.layer_id, (uint64_t)o); dr.tau_b[o] = tb; }
+            else tb = a.tau_b[o];
             const float Cb = ba * logf(bb) + (ba - 0.5f) * tb - bb * tb - lgammaf(ba) - 0.5f * 1.8378770664093453f;
             gb += (double)(Cb - tb * (b * b) + 0.f + 1e-8f);                                          // GaussGamma(bias, 1)
             const float d = b - a.bias_mu[o];
@@ -151,18 +262,28 @@ __device__ __forceinline__ float digammaf_pos(float x) {
 
 struct GateScal { float C, tau, pa, pb, glp, glq; };
 
-__global__ __launch_bounds__(256) void gate_backward_kernel(const lbbnn_gate_bwd_args_t a, const uint64_t* rng) {
+template <bool DRAW>
+__global__ __launch_bounds__(256) void gate_backward_kernel(const lbbnn_gate_bwd_draw_args_t dr, const uint64_t* rng) {
+    const lbbnn_gate_bwd_args_t& a = dr.g;
     __shared__ double red[3][4];
     const int o = blockIdx.x, tid = threadIdx.x;
     const size_t ro = (size_t)o * a.I;
     uint64_t seed = 0, offs = 0;
-    if (!a.eps_w) { seed = rng[0]; offs = rng[1]; }
+    if (DRAW || !a.eps_w) { seed = rng[0]; offs = rng[1]; }
     const float wa = a.weight_a[0], wb = a.weight_b[0], tau = a.tau_w[0], pb = a.pb[0];
     const float C = wa * logf(wb) + (wa - 0.5f) * tau - wb * tau - lgammaf(wa) - 0.5f * 1.8378770664093453f;
     const float glp = a.g_lp ? a.g_lp[0] : 0.f, glq = a.g_lq ? a.g_lq[0] : 0.f;
     double s_c = 0.0, s_w2 = 0.0, s_psi = 0.0;
     for (int i = tid; i < a.I; i += 256) {
-        const float mu = a.mu[ro + i], g = a.cgamma[ro + i];
+        const float mu = a.mu[ro + i];
+        float g, al, dcda = 0.f;
+        if (DRAW) {
+            al = sigmoid_ref(dr.lambdal[ro + i]);                 // the forward's alpha and gate, bit for bit
+            g = gate_draw(al, gate_u(seed, offs, a.layer_id, o, i), dr.temperature, (a.exact & 8) != 0, &dcda);
+        } else {
+            g = a.cgamma[ro + i];
+            al = a.gamma_alpha[ro + i];
+        }
         float e;
         if (a.eps_w) e = a.eps_w[ro + i];
         else { float n[4]; philox_normal4(seed, offs, LBBNN_STREAM_EPS_W * 64u + a.layer_id, (uint64_t)o, (uint32_t)(i >> 2), n); e = n[i & 3]; }
@@ -176,7 +297,6 @@ __global__ __launch_bounds__(256) void gate_backward_kernel(const lbbnn_gate_bwd
         const float q = glq * (g * E / D);                         // g_lq * d full_log_prob / d lp
         const float A = (a.dW ? a.dW[ro + i] : 0.f) + glp * (-2.f * tau * w) + q * (-d * is2);       // dL/dW
         const float g_wp = (a.exact & 1) ? rintf(g) : g, g_bb = (a.exact & 4) ? rintf(g) : g, g_be = (a.exact & 8) ? rintf(g) : g;
-        const float al = a.gamma_alpha[ro + i];
         float dg = A * ws + glq * ((E - 1.f) / D);
         if (!(a.exact & 1)) dg += glp * (C - 1.f);
         const float psi1 = digammaf_pos(1.f + pb - g_bb);
@@ -186,8 +306,13 @@ __global__ __launch_bounds__(256) void gate_backward_kernel(const lbbnn_gate_bwd
         a.d_mu[ro + i] = dws + q * (d * is2);
         const float dsig = dws * e + q * (-1.f / sigma + (d * d) * is2 / sigma);
         a.d_rho[ro + i] = dsig / (1.f + expf(-rho));
-        a.d_cgamma[ro + i] = dg;
-        a.d_alpha[ro + i] = glq * (g_be / (al + 1e-8f) - (1.f - g_be) / (1.f - al + 1e-8f));
+        const float dal = glq * (g_be / (al + 1e-8f) - (1.f - g_be) / (1.f - al + 1e-8f));
+        if (DRAW) {
+            dr.d_lambdal[ro + i] = (al * (1.f - al)) * (dal + dg * dcda);   // alpha = sigmoid(lambdal) feeds both
+        } else {
+            a.d_cgamma[ro + i] = dg;
+            a.d_alpha[ro + i] = dal;
+        }
         s_c += (double)g_wp; s_w2 += (double)(w * w); s_psi += (double)psi1;
     }
     s_c = wave_sum(s_c); s_w2 = wave_sum(s_w2); s_psi = wave_sum(s_psi);
@@ -197,7 +322,9 @@ __global__ __launch_bounds__(256) void gate_backward_kernel(const lbbnn_gate_bwd
     if (tid < 3) a.rows[(size_t)tid * a.O + o] = (float)((red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]));
 }
 
-__global__ __launch_bounds__(256) void gate_backward_tail_kernel(const lbbnn_gate_bwd_args_t a, const uint64_t* rng) {
+template <bool DRAW>
+__global__ __launch_bounds__(256) void gate_backward_tail_kernel(const lbbnn_gate_bwd_draw_args_t dr, const uint64_t* rng) {
+    const lbbnn_gate_bwd_args_t& a = dr.g;
     __shared__ double scratch[4];
     const int tid = threadIdx.x;
     uint64_t seed = 0, offs = 0;
@@ -215,17 +342,30 @@ __global__ __launch_bounds__(256) void gate_backward_tail_kernel(const lbbnn_gat
         const float db = (a.g_sum ? a.g_sum[o] : 0.f) + glp * (-2.f * tb * b) + glq * (-d * is2);      // dL/db
         a.d_bias_mu[o] = db + glq * (d * is2);
         a.d_bias_rho[o] = (db * e + glq * (-1.f / sb + (d * d) * is2 / sb)) / (1.f + expf(-rho));
-        a.d_bias_a[o] = glp * (logf(bb) + tb - digammaf_pos(ba));
-        a.d_bias_b[o] = glp * (ba / bb - tb);
-        a.d_tau_b[o] = glp * ((ba - 0.5f) - bb - b * b);
+        const float dtb = glp * ((ba - 0.5f) - bb - b * b);
+        if (DRAW) {
+            // tau_b = x / b with x ~ Gamma(a, 1): d tau / d a = g(x, a) / b, d tau / d b = -tau / b
+            a.d_bias_a[o] = glp * (logf(bb) + tb - digammaf_pos(ba)) + dtb * (gamma_grad_one(tb * bb, ba) / bb);
+            a.d_bias_b[o] = glp * (ba / bb - tb) - dtb * (tb / bb);
+            if (a.d_tau_b) a.d_tau_b[o] = dtb;
+        } else {
+            a.d_bias_a[o] = glp * (logf(bb) + tb - digammaf_pos(ba));
+            a.d_bias_b[o] = glp * (ba / bb - tb);
+            a.d_tau_b[o] = dtb;
+        }
     }
     r0 = block_sum<double, 4>(r0, scratch); r1 = block_sum<double, 4>(r1, scratch); r2 = block_sum<double, 4>(r2, scratch);
     if (tid == 0) {
         const float wa = a.weight_a[0], wb = a.weight_b[0], tau = a.tau_w[0], pa = a.pa[0], pb = a.pb[0];
         const double N = (double)a.O * (double)a.I;
+        const float dtw = glp * (float)(r0 * (double)((wa - 0.5f) - wb) - r1);                         // d tau_w
         a.d_scalars[0] = glp * (float)(r0 * (double)(logf(wb) + tau - digammaf_pos(wa)));             // d weight_a
         a.d_scalars[1] = glp * (float)(r0 * (double)(wa / wb - tau));                                 // d weight_b
-        a.d_scalars[2] = glp * (float)(r0 * (double)((wa - 0.5f) - wb) - r1);                         // d tau_w
+        if (DRAW) {
+            a.d_scalars[0] += dtw * (gamma_grad_one(tau * wb, wa) / wb);
+            a.d_scalars[1] -= dtw * (tau / wb);
+        }
+        a.d_scalars[2] = dtw;
         const float common = digammaf_pos(pa + pb) - digammaf_pos(1.f + pa + pb);
         a.d_scalars[3] = glp * (float)(N * (double)(common - digammaf_pos(pa)));                      // d pa
         a.d_scalars[4] = glp * (float)(r2 + N * (double)(common - digammaf_pos(pb)));                 // d pb
@@ -372,8 +512,30 @@ extern "C" int lbbnn_gate_sample(const lbbnn_gate_args_t* p, const uint64_t* rng
                       !a.pa || !a.pb || !a.bias_a || !a.bias_b || !a.tau_b || !a.rows || !a.log_prior || !a.log_q))
         return LBBNN_E_NULL;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(gate_sample_kernel, dim3(a.O), dim3(256), 0, s, a, rng);
-    hipLaunchKernelGGL(gate_finalize_kernel, dim3(1), dim3(256), 0, s, a, rng);
+    lbbnn_gate_draw_args_t d{};
+    d.g = a;
+    hipLaunchKernelGGL(gate_sample_kernel<false>, dim3(a.O), dim3(256), 0, s, d, rng);
+    hipLaunchKernelGGL(gate_finalize_kernel<false>, dim3(1), dim3(256), 0, s, d, rng);
+    return (int)hipGetLastError();
+}
+
+extern "C" int lbbnn_gate_sample_draw(const lbbnn_gate_draw_args_t* p, const uint64_t* rng, void* stream) {
+    if (!p) return LBBNN_E_NULL;
+    const lbbnn_gate_draw_args_t& d = *p;
+    const lbbnn_gate_args_t& a = d.g;
+    if (!a.mu || !a.rho || !a.bias_mu || !a.bias_rho || !a.bias_out || !d.lambdal || !d.gammas || !d.tau_w || !d.tau_b)
+        return LBBNN_E_NULL;
+    if (!a.weight_a || !a.weight_b || !a.pa || !a.pb || !a.bias_a || !a.bias_b || !a.rows || !a.log_prior || !a.log_q)
+        return LBBNN_E_NULL;
+    if (a.O <= 0 || a.I <= 0) return LBBNN_E_SHAPE;
+    if (a.mode != LBBNN_MODE_SAMPLE || !a.want_lp) return LBBNN_E_FLAGS;
+    if (a.flags & ~LBBNN_F_SPLIT16) return LBBNN_E_FLAGS;
+    if (!(d.temperature > 0.f)) return LBBNN_E_FLAGS;
+    if (a.w_out && (a.ld < a.I || (a.ld & 31))) return LBBNN_E_ALIGN;
+    if (!rng) return LBBNN_E_NOISE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(gate_sample_kernel<true>, dim3(a.O), dim3(256), 0, s, d, rng);
+    hipLaunchKernelGGL(gate_finalize_kernel<true>, dim3(1), dim3(256), 0, s, d, rng);
     return (int)hipGetLastError();
 }
 
@@ -387,8 +549,80 @@ extern "C" int lbbnn_gate_backward(const lbbnn_gate_bwd_args_t* p, const uint64_
     if ((!a.eps_w || !a.eps_b) && !rng) return LBBNN_E_NOISE;
     if (a.O <= 0 || a.I <= 0) return LBBNN_E_SHAPE;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(gate_backward_kernel, dim3(a.O), dim3(256), 0, s, a, rng);
-    hipLaunchKernelGGL(gate_backward_tail_kernel, dim3(1), dim3(256), 0, s, a, rng);
+    lbbnn_gate_bwd_draw_args_t d{};
+    d.g = a;
+    hipLaunchKernelGGL(gate_backward_kernel<false>, dim3(a.O), dim3(256), 0, s, d, rng);
+    hipLaunchKernelGGL(gate_backward_tail_kernel<false>, dim3(1), dim3(256), 0, s, d, rng);
+    return (int)hipGetLastError();
+}
+
+extern "C" int lbbnn_gate_backward_draw(const lbbnn_gate_bwd_draw_args_t* p, const uint64_t* rng, void* stream) {
+    if (!p) return LBBNN_E_NULL;
+    const lbbnn_gate_bwd_draw_args_t& d = *p;
+    const lbbnn_gate_bwd_args_t& a = d.g;
+    if (!a.mu || !a.rho || !d.lambdal || !a.bias_mu || !a.bias_rho || !a.bias_a || !a.bias_b || !a.tau_b ||
+        !a.weight_a || !a.weight_b || !a.tau_w || !a.pa || !a.pb) return LBBNN_E_NULL;
+    if (!a.d_mu || !a.d_rho || !d.d_lambdal || !a.d_bias_mu || !a.d_bias_rho || !a.d_bias_a || !a.d_bias_b ||
+        !a.d_scalars || !a.rows) return LBBNN_E_NULL;
+    if (!rng) return LBBNN_E_NOISE;
+    if (a.O <= 0 || a.I <= 0) return LBBNN_E_SHAPE;
+    if (!(d.temperature > 0.f)) return LBBNN_E_FLAGS;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(gate_backward_kernel<true>, dim3(a.O), dim3(256), 0, s, d, rng);
+    hipLaunchKernelGGL(gate_backward_tail_kernel<true>, dim3(1), dim3(256), 0, s, d, rng);
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------ test entry points
+__global__ __launch_bounds__(256) void philox_uniform_kernel(const uint64_t* rng, uint32_t stream, long long row_base,
+                                                             long long rows, long long cols, float* out) {
+    const long long gpr = (cols + 3) / 4;
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= gpr * rows) return;
+    const long long r = g / gpr, cg = g % gpr;
+    const Philox4 b = philox_bits4(rng[0], rng[1], stream, (uint64_t)(row_base + r), (uint32_t)cg);
+    const uint32_t w[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) if (cg * 4 + k < cols) out[r * cols + cg * 4 + k] = uniform24(w[k]);
+}
+
+__global__ __launch_bounds__(256) void philox_std_gamma_kernel(const uint64_t* rng, uint32_t stream, const float* a,
+                                                               const float* rate, long long n, float* out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    out[i] = rate ? gamma_rate_draw(a[i], rate[i], rng[0], rng[1], stream, (uint64_t)i)
+                  : gamma_rate_draw(a[i], 1.f, rng[0], rng[1], stream, (uint64_t)i);
+}
+
+__global__ __launch_bounds__(256) void gamma_grad_kernel(const float* x, const float* a, long long n, float* out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = gamma_grad_one(x[i], a[i]);
+}
+
+extern "C" int lbbnn_philox_uniform(const uint64_t* rng, uint32_t rng_stream, int64_t row_base, int64_t rows, int64_t cols,
+                                    float* out, void* stream) {
+    if (!rng || !out) return LBBNN_E_NULL;
+    if (rows <= 0 || cols <= 0) return LBBNN_E_SHAPE;
+    const long long groups = ((cols + 3) / 4) * rows;
+    hipLaunchKernelGGL(philox_uniform_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), rng, rng_stream, (long long)row_base, (long long)rows, (long long)cols, out);
+    return (int)hipGetLastError();
+}
+
+extern "C" int lbbnn_philox_std_gamma(const uint64_t* rng, uint32_t rng_stream, const float* a, const float* rate, int64_t n,
+                                      float* out, void* stream) {
+    if (!rng || !a || !out) return LBBNN_E_NULL;
+    if (n <= 0) return LBBNN_E_SHAPE;
+    hipLaunchKernelGGL(philox_std_gamma_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), rng, rng_stream, a, rate, (long long)n, out);
+    return (int)hipGetLastError();
+}
+
+extern "C" int lbbnn_gamma_grad(const float* x, const float* a, int64_t n, float* out, void* stream) {
+    if (!x || !a || !out) return LBBNN_E_NULL;
+    if (n <= 0) return LBBNN_E_SHAPE;
+    hipLaunchKernelGGL(gamma_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), x, a, (long long)n, out);
     return (int)hipGetLastError();
 }
 

@@ -30,6 +30,9 @@ STREAM_EPS_W = 4
 STREAM_EPS_B = 5
 STREAM_MASK = 6
 STREAM_ROW_MASK = 7
+STREAM_GATE = 8          # the baseline layer's in-kernel draws (sample_elbo(draws="hip")): gate uniforms, tau_w, tau_b
+STREAM_GAMMA_W = 9
+STREAM_GAMMA_B = 10
 
 
 # GEMM arithmetic.  A name selects the operand FORMAT of the forward's dual-moment GEMM:
@@ -173,6 +176,37 @@ def philox_normal(rng: torch.Tensor, stream_id: int, rows: int, cols: int, row_b
     out = torch.empty((rows, cols) if rows > 0 else (cols,), dtype=torch.float32, device=rng.device)
     _lib.check(_lib.lib().lbbnn_philox_normal(rng.data_ptr(), stream_id, row_base, rows, cols, out.data_ptr(),
                                               _stream()), "lbbnn_philox_normal")
+    return out
+
+
+def philox_uniform(rng: torch.Tensor, stream_id: int, rows: int, cols: int, row_base: int = 0) -> torch.Tensor:
+    """The exact uniforms of the baseline layer's in-kernel gate draw: (rows, cols), element (r, c) = counter (row_base + r,
+    c // 4), word c % 4, as ((bits >> 8) + 0.5) 2^-24."""
+    out = torch.empty((rows, cols), dtype=torch.float32, device=rng.device)
+    _lib.check(_lib.lib().lbbnn_philox_uniform(rng.data_ptr(), stream_id, row_base, rows, cols, out.data_ptr(), _stream()),
+               "lbbnn_philox_uniform")
+    return out
+
+
+def philox_std_gamma(rng: torch.Tensor, stream_id: int, a: torch.Tensor, rate: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The in-kernel Gamma draws: element i is Gamma(a[i]) from counter (i, attempt), divided by rate[i] (default 1) and
+    clamped below at FLT_MIN (what the baseline layer's tau_w / tau_b are, element 0 / element o of their streams)."""
+    a = a.detach().float().contiguous()
+    rate = None if rate is None else rate.detach().float().contiguous()
+    out = torch.empty_like(a)
+    _lib.check(_lib.lib().lbbnn_philox_std_gamma(rng.data_ptr(), stream_id, a.data_ptr(), _ptr(rate, "rate"), a.numel(),
+                                                 out.data_ptr(), _stream()), "lbbnn_philox_std_gamma")
+    return out
+
+
+def gamma_grad(x: torch.Tensor, a: torch.Tensor) -> torch.Tensor:
+    """The device's g(x, a) = -(dF(x; a)/da) / f(x; a) of the standard Gamma (the reparameterised dx/da)."""
+    x = x.detach().float().contiguous()
+    a = a.detach().float().contiguous()
+    if x.shape != a.shape:
+        raise ValueError("bnn_amd.ops.gamma_grad: x and a must have the same shape")
+    out = torch.empty_like(x)
+    _lib.check(_lib.lib().lbbnn_gamma_grad(x.data_ptr(), a.data_ptr(), x.numel(), out.data_ptr(), _stream()), "lbbnn_gamma_grad")
     return out
 
 

@@ -1,0 +1,69 @@
+#!/usr/bin/env python3
+"""The reference's baseline-LBBNN training loop (LBBNN-GP-MF.py:327-338: net.zero_grad(), net.sample_elbo(data, target),
+loss.backward(), the COND_OPT mask weight_mu.grad * gammas, optimizer.step()) with its 33-group Adam (:520-554) as
+bnn_amd.optim.Adam, on MNIST-shaped synthetic data (there is no dataset in this image).  The step draws its gates and Gamma
+precisions inside the HIP kernels (sample_elbo(draws="hip")), so it is captured once in a HIP graph and replayed.
+
+    python examples/train_base_synthetic.py               # graphed hip-draw step
+    EAGER=1 python examples/train_base_synthetic.py       # the same step, eager
+    COND_OPT=1 python examples/train_base_synthetic.py    # mask the weight_mu gradients with the drawn gates (:333-336)
+"""
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+import bnn_amd
+from bnn_amd.base import BayesianNetwork
+
+DEVICE = torch.device("cuda:0")
+BATCH_SIZE, NUM_BATCHES, EPOCHS = 100, 60, 4
+COND_OPT = os.environ.get("COND_OPT") == "1"
+torch.manual_seed(0)                                   # also seeds the in-kernel draws
+
+net = BayesianNetwork().to(DEVICE)                     # 784-400-600-10
+ls = (net.l1, net.l2, net.l3)
+groups = ([{"params": l.bias_mu, "lr": 1e-4} for l in ls] + [{"params": l.bias_rho, "lr": 1e-4} for l in ls]
+          + [{"params": l.weight_mu, "lr": 1e-4} for l in ls] + [{"params": l.weight_rho, "lr": 1e-4} for l in ls]
+          + [{"params": l.pa, "lr": 1e-3} for l in ls] + [{"params": l.pb, "lr": 1e-3} for l in ls]
+          + [{"params": l.weight_a, "lr": 1e-5} for l in ls] + [{"params": l.weight_b, "lr": 1e-5} for l in ls]
+          + [{"params": l.bias_a, "lr": 1e-5} for l in ls] + [{"params": l.bias_b, "lr": 1e-5} for l in ls]
+          + [{"params": l.lambdal, "lr": 0.1} for l in ls])
+optimizer = bnn_amd.optim.Adam(groups, lr=1e-4)
+if COND_OPT:
+    # weight_mu.grad * gammas.data (:333-336) as a gradient hook: it reads the gates of the step it runs in, so it is captured
+    # with the step (the graph's gammas buffer is rewritten by every replay)
+    for l in ls:
+        l.weight_mu.register_hook(lambda gr, l=l: gr * l.gammas)
+
+g = torch.Generator(device=DEVICE).manual_seed(7)
+proj = torch.randn(784, 10, device=DEVICE, generator=g)
+train_x = torch.rand(NUM_BATCHES, BATCH_SIZE, 1, 28, 28, device=DEVICE, generator=g)
+train_y = (train_x.view(NUM_BATCHES, BATCH_SIZE, 784) @ proj).argmax(-1)
+
+
+def elbo(net, data, target):
+    return net.sample_elbo(data, target, draws="hip")[0]
+
+
+net.train()
+if os.environ.get("EAGER") == "1":
+    def step(data, target):
+        net.zero_grad()
+        loss = elbo(net, data, target)
+        loss.backward()
+        optimizer.step()
+        return loss
+else:
+    step = bnn_amd.graphs.make_graphed_train_step(net, optimizer, elbo, train_x[0], train_y[0])
+
+for epoch in range(EPOCHS):
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    for b in range(NUM_BATCHES):
+        loss = step(train_x[b], train_y[b])
+    torch.cuda.synchronize()
+    print("epoch %d  loss %.1f  (%.3f ms/iteration)" % (epoch, float(loss.detach()), (time.perf_counter() - t0) / NUM_BATCHES * 1e3))
+with torch.no_grad():
+    print("mean inclusion probability per layer:", ["%.3f" % float(l.alpha.mean()) for l in ls])

@@ -409,6 +409,59 @@ typedef struct lbbnn_gate_bwd_args {
 
 int lbbnn_gate_backward(const lbbnn_gate_bwd_args_t* args, const uint64_t* rng, void* stream);
 
+/* K6 / K6b with in-kernel draws -- the baseline layer's whole stochastic input from the Philox state `rng` (required):
+ *   alpha = sigmoid(lambdal); u = uniform(stream GATE, counter (o, i/4))[i%4];
+ *   c = clipped_sigmoid((logit(clamp_probs(alpha)) + log u' - log1p(-u')) / temperature), u' = clamp_probs(u)
+ *       (torch's RelaxedBernoulli.rsample, LBBNN-GP-MF.py:300-302); exact bit 8 (gamma.exact): c = (u < alpha), the hard draw;
+ *   tau_w = Gamma(weight_a, weight_b) (stream GAMMA_W, element 0), tau_b[o] = Gamma(bias_a[o], bias_b[o]) (stream GAMMA_B,
+ *       element o)  (:141; Marsaglia-Tsang on Philox normals / uniforms, counter (element, attempt), at most
+ *       LBBNN_GAMMA_MAX_ATTEMPTS attempts; a NaN / non-positive / infinite shape gives NaN);
+ *   eps_w / eps_b as lbbnn_gate_sample (explicit or streams EPS_W / EPS_B).
+ * lbbnn_gate_sample_draw: `g` as for lbbnn_gate_sample with mode LBBNN_MODE_SAMPLE and want_lp = 1; g.gamma_alpha, g.cgamma,
+ * g.alpha_attr, g.tau_w, g.tau_b are not read.  Outputs in addition to g's: gammas (O,I) = c, alpha (O,I, nullable) = alpha,
+ * tau_w (1), tau_b (O).  Two launches, as lbbnn_gate_sample.
+ * lbbnn_gate_backward_draw: `g` as for lbbnn_gate_backward with the forward's tau_w / tau_b outputs in g.tau_w / g.tau_b;
+ * g.gamma_alpha, g.cgamma, g.d_cgamma, g.d_alpha, g.d_tau_b are not read / written (d_tau_b may be given).  Writes
+ * d_lambdal = alpha (1 - alpha) (d alpha + d c * dc/dalpha) and adds the Gamma reparameterisation terms
+ * (d tau * g(x, a) / b and -d tau * tau / b, x = b tau, g of lbbnn_gamma_grad) to d weight_a / d weight_b / d bias_a / d bias_b.
+ * Two launches, as lbbnn_gate_backward. */
+#define LBBNN_STREAM_GATE 8
+#define LBBNN_STREAM_GAMMA_W 9
+#define LBBNN_STREAM_GAMMA_B 10
+#define LBBNN_GAMMA_MAX_ATTEMPTS 32
+
+typedef struct lbbnn_gate_draw_args {
+    lbbnn_gate_args_t g;
+    const float* lambdal;                     /* (O,I) */
+    float *gammas, *alpha;                    /* (O,I) out; alpha nullable */
+    float *tau_w, *tau_b;                     /* (1), (O) out */
+    float temperature;
+} lbbnn_gate_draw_args_t;
+
+int lbbnn_gate_sample_draw(const lbbnn_gate_draw_args_t* args, const uint64_t* rng, void* stream);
+
+typedef struct lbbnn_gate_bwd_draw_args {
+    lbbnn_gate_bwd_args_t g;
+    const float* lambdal;                     /* (O,I) */
+    float* d_lambdal;                         /* (O,I) out */
+    float temperature;
+} lbbnn_gate_bwd_draw_args_t;
+
+int lbbnn_gate_backward_draw(const lbbnn_gate_bwd_draw_args_t* args, const uint64_t* rng, void* stream);
+
+/* Reproduce the in-kernel draws of the two kernels above (tests):
+ * lbbnn_philox_uniform: out[r][c] = uniform(counter (row_base + r, c/4))[c%4], the gate's indexing; uniform(bits) =
+ *   ((bits >> 8) + 0.5) * 2^-24, in (0, 1).  rows > 0.
+ * lbbnn_philox_std_gamma: out[i] = standard Gamma(a[i]) draw of element i (counter (i, attempt)) divided by rate[i]
+ *   (rate NULL = 1) and clamped below at FLT_MIN as torch's Gamma.rsample does.
+ * lbbnn_gamma_grad: out[i] = g(x[i], a[i]) = -(dF(x; a)/da) / f(x; a), F / f the standard Gamma cdf / density: the
+ *   implicit reparameterisation gradient dx/da that lbbnn_gate_backward_draw uses (fp64 series; relative error ~1e-16 / Q(a, x)). */
+int lbbnn_philox_uniform(const uint64_t* rng, uint32_t rng_stream, int64_t row_base, int64_t rows, int64_t cols, float* out,
+                         void* stream);
+int lbbnn_philox_std_gamma(const uint64_t* rng, uint32_t rng_stream, const float* a, const float* rate, int64_t n, float* out,
+                           void* stream);
+int lbbnn_gamma_grad(const float* x, const float* a, int64_t n, float* out, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * K7  lbbnn_vd_operands -- Gaussian variational-dropout layer (variational_dropout.py:55-68).
  *   phi = x.theta ; delta = (x^2).(theta^2) * alpha ; out = phi + sqrt(delta)*zeta        :64-67
