@@ -150,6 +150,12 @@ class GateBwdDrawArgs(ctypes.Structure):
     _fields_ = [("g", GateBwdArgs), ("lambdal", c_p), ("d_lambdal", c_p), ("temperature", ctypes.c_float)]
 
 
+class GateMemberDesc(ctypes.Structure):
+    """lbbnn_gate_member_desc_t"""
+    _fields_ = [(n, c_p) for n in ("mu", "rho", "lambdal", "bias_mu", "bias_rho", "w_out", "bias_out", "gate_rows", "gates")] + \
+               [(n, c_i) for n in ("O", "I", "ld", "flags", "exact")] + [("layer_id", c_u32)]
+
+
 class OutGradArgs(ctypes.Structure):
     """lbbnn_outgrad_args_t"""
     _fields_ = [(n, c_p) for n in ("g_out", "out", "std", "eps", "rng", "gm", "gv", "gmT", "gvT", "g_sum", "gv_sum", "work")] + \
@@ -276,6 +282,9 @@ SIGNATURES = {
     "lbbnn_gate_sample_draw": (c_i, [ctypes.POINTER(GateDrawArgs), c_p, c_p]),
     "lbbnn_gate_backward_draw": (c_i, [ctypes.POINTER(GateBwdDrawArgs), c_p, c_p]),
     "lbbnn_philox_uniform": (c_i, [c_p, c_u32, c_i64, c_i64, c_i64, c_p, c_p]),
+    "lbbnn_gate_members": (c_i, [ctypes.POINTER(GateMemberDesc), c_i, c_i, c_i, ctypes.c_float, c_p, c_u64, c_p]),
+    "lbbnn_gemm_members_mean": (c_i, [c_p, c_i, c_i64, c_p, c_i64, c_i, c_p, c_i64, c_p, c_i, c_i64, c_i, c_i, c_i, c_i, c_i,
+                                      c_p]),
     "lbbnn_philox_std_gamma": (c_i, [c_p, c_u32, c_p, c_p, c_i64, c_p, c_p]),
     "lbbnn_gamma_grad": (c_i, [c_p, c_p, c_i64, c_p, c_p]),
     "lbbnn_elbo_loss": (c_i, [c_p, c_i, c_p, c_i, c_i, c_p, ctypes.c_float, c_p, c_p]),

@@ -361,6 +361,23 @@ class BayesianLinear(nn.Module):
         self._publish_draws(lp, lq)
         return out, lp, lq
 
+    def _fill_member_desc(self, d, S, split, rows=False, keep_gates=False):
+        """lbbnn_gate_member_desc_t of this layer for an S-member evaluation draw; returns the buffers it points to."""
+        O, I, ld = self.out_features, self.in_features, ops.operand_ld(self.in_features)
+        f = dict(dtype=torch.float32, device=self.weight_mu.device)
+        P = lambda t: ops._ptr(t.detach(), "tensor")
+        buf = {"w": torch.empty((S, O, ld), **f), "bias": torch.empty((S, O), **f),
+               "rows": torch.empty((S, O), **f) if rows else None,
+               "gates": torch.empty((S, O, I), **f) if keep_gates else None}
+        d.mu, d.rho, d.lambdal = P(self.weight_mu), P(self.weight_rho), P(self.lambdal)
+        d.bias_mu, d.bias_rho = P(self.bias_mu), P(self.bias_rho)
+        d.w_out, d.bias_out = buf["w"].data_ptr(), buf["bias"].data_ptr()
+        d.gate_rows = buf["rows"].data_ptr() if rows else None
+        d.gates = buf["gates"].data_ptr() if keep_gates else None
+        d.O, d.I, d.ld, d.flags, d.exact = O, I, ld, (ops.F_SPLIT16 if split else 0), self._exact_bits()
+        d.layer_id = self._layer_id
+        return buf
+
     def _publish_draws(self, lp, lq):
         keep = self._last_keep
         self.gammas, self.alpha, self.tau_w, self.tau_b = keep["gammas"], keep["alpha"], keep["tau_w"], keep["tau_b"]
@@ -452,6 +469,88 @@ class BayesianNetwork(nn.Module):
 
     def log_prior(self):
         return self.l1.log_prior + self.l2.log_prior + self.l3.log_prior
+
+    @torch.no_grad()
+    def sample_predict(self, x, *, gates="sample", rng=None):
+        """One stochastic evaluation forward (test_ensemble's ``net.forward(data, sample=True, g1=gamma.rsample(), ...)``,
+        LBBNN-GP-MF.py:388-389, without log-probabilities): (B, classes) log-probabilities, no autograd.  Every draw comes from
+        the Philox state inside the HIP kernels -- lbbnn_gate_members (gates, weight and bias noise of all three layers) and one
+        mean-only GEMM per layer with ReLU, ReLU and log_softmax in its epilogue -- so this is member 0 of a one-member ensemble
+        (``evaluate.ensemble_forward``).  ``gates``: "sample" (the training draw: the hard gate u < alpha when ``gamma.exact``
+        is set, else the relaxed gate at ``distributions.TEMPER_PRIOR``; both read at call time) or "mpm" (the median
+        probability model, gates alpha > 0.5 and sampled weights: outofsample(medimod=True), :469-473).  ``rng``: a
+        {seed, offset} snapshot (2 int64 on the device) to draw from; default: the device's ``ops.RngState``, which this call
+        then advances by one.  The draws match the reference in distribution, not in numbers."""
+        if not x.is_cuda:
+            raise RuntimeError("bnn_amd: sample_predict needs a HIP device tensor (input is on %s); there is no CPU path"
+                               % x.device)
+        st = None
+        if rng is None:
+            st = ops.RngState.get(x.device)
+            rng = st.t
+        out = self._predict_members(x, rng, 1, gates)[0][0]
+        if st is not None:
+            st.advance(1)
+        return out
+
+    def _predict_members(self, input, rng, S, gates="sample", out=None, rows=False, keep_gates=False):
+        """S evaluation forwards of one batch; member m draws from {rng[0], rng[1] + m}, bitwise what ``sample_forward`` of the
+        three layers at that offset computes.  1 + 3 launches: lbbnn_gate_members, then lbbnn_gemm_members_mean per layer.
+        ``out``: optional (S, >= B*classes) buffer for the head.  Returns ((S, B, classes) log-probabilities, per-layer (S, O)
+        gate row sums or None, per-layer (S, O, I) gates or None).  Does not advance the live state."""
+        if not input.is_cuda:
+            raise RuntimeError("bnn_amd: sample_predict needs a HIP device tensor (input is on %s); there is no CPU path"
+                               % input.device)
+        if gates not in ("sample", "mpm"):
+            raise ValueError("bnn_amd: gates must be 'sample' or 'mpm', got %r" % (gates,))
+        layers = (self.l1, self.l2, self.l3)
+        for l in layers:
+            if l.noise:
+                raise ValueError("bnn_amd: evaluation draws its own noise in-kernel; injected draws (layer.noise) belong to the "
+                                 "torch-draw forward -- clear layer.noise first")
+        from . import distributions
+        x = input.view(-1, self.dims[0]).float()
+        if x.stride(1) != 1 or x.stride(0) < self.dims[0]:
+            x = x.contiguous()
+        B, dev = x.shape[0], x.device
+        f = dict(dtype=torch.float32, device=dev)
+        # operand format per layer: the rule of _forward_hip_draws (16-bit precisions take the bf16 hi|lo operands where the
+        # split kernel accepts the shape and the input rows are 16-B aligned; a hidden layer's input rows are the previous
+        # layer's output rows, aligned exactly when its width is a multiple of 4)
+        splits = []
+        for k, l in enumerate(layers):
+            in_ok = (x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0) if k == 0 else layers[k - 1].out_features % 4 == 0
+            splits.append(bool(ops.split_precision() and ops.split_eligible(l.in_features, l.out_features) and in_ok))
+        descs = (_lib.GateMemberDesc * 3)()
+        bufs = [l._fill_member_desc(descs[k], S, splits[k], rows, keep_gates) for k, l in enumerate(layers)]
+        stream = ops._stream()
+        _lib.check(_lib.lib().lbbnn_gate_members(descs, 3, S, ops.GATES_MPM if gates == "mpm" else ops.GATES_SAMPLE,
+                                                 float(distributions.TEMPER_PRIOR), rng.data_ptr(), 1, stream),
+                   "lbbnn_gate_members")
+        h, h_ms, ldx = x, 0, x.stride(0)
+        for k, l in enumerate(layers):
+            O, I, ld = l.out_features, l.in_features, ops.operand_ld(l.in_features)
+            o_ms = -(-(B * O) // 4) * 4                       # member stride padded to 16 B
+            head = k == 2
+            if head and out is not None:
+                o = out
+                if o.dim() != 2 or o.shape[0] != S or o.shape[1] < B * O or o.stride(0) % 4 or not o.is_contiguous():
+                    raise RuntimeError("bnn_amd: out must be a contiguous (S, >= B*classes) buffer with 16-B aligned rows")
+                o_ms = o.stride(0)
+            else:
+                o = torch.empty((S, o_ms), **f)
+            flags = (ops.F_RELU if not head else (ops.F_LOG_SOFTMAX if O <= 16 else 0)) | (ops.F_SPLIT16 if splits[k] else 0)
+            rc = _lib.lib().lbbnn_gemm_members_mean(h.data_ptr(), ldx, h_ms, bufs[k]["w"].data_ptr(), O * ld, ld,
+                                                   bufs[k]["bias"].data_ptr(), O, o.data_ptr(), O, o_ms, B, I, O, flags, S,
+                                                   stream)
+            _lib.check(rc, "lbbnn_gemm_members_mean")
+            h, h_ms, ldx = o, o_ms, O
+        res = h[:, :B * self.dims[-1]].view(S, B, self.dims[-1])
+        if self.dims[-1] > 16:
+            res = F.log_softmax(res, dim=-1)
+        for l in layers:
+            l.log_prior, l.log_variational_posterior = 0, 0          # an evaluation forward keeps no log-probabilities (:253)
+        return (res, [b["rows"] for b in bufs] if rows else None, [b["gates"] for b in bufs] if keep_gates else None)
 
     def log_variational_posterior(self):
         return (self.l1.log_variational_posterior + self.l2.log_variational_posterior

@@ -1,6 +1,7 @@
 // K6 (baseline LBBNN gate x Gaussian weight sampling + Monte-Carlo log-probabilities) and
 // K7 (variational-dropout operand pass) -- see include/lbbnn.h.  Both are one-pass HBM-bound kernels
 // that feed the same dual-moment GEMM.
+#include <climits>
 #include <cmath>
 #include "lbbnn_device.h"
 #include "lbbnn_internal.h"
@@ -12,6 +13,11 @@ using namespace lbbnn;
 __device__ __forceinline__ uint32_t bf16_rne_bits(float f) {
     const uint32_t u = __float_as_uint(f);
     return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+// the split bf16 pair of one operand value: hi | lo << 16 (hi = RNE(v), lo = RNE(v - hi))
+__device__ __forceinline__ uint32_t bf16_hi_lo(float v) {
+    const uint32_t h = bf16_rne_bits(v);
+    return h | (bf16_rne_bits(v - __uint_as_float(h << 16)) << 16);
 }
 // store one operand value at [o][i] either as fp32 or in the split bf16 hi|lo layout
 // split: 0 = fp32, 1 = bf16 hi|lo (LBBNN_F_SPLIT16), 2 = fp16 in the hi unit, zero lo (LBBNN_F_HALF16: the single-product
@@ -27,9 +33,9 @@ __device__ __forceinline__ void store_operand(void* base, int split, size_t O, i
         (void)O;
         return;
     }
-    const uint32_t h = bf16_rne_bits(v);
-    w[at] = (uint16_t)h;
-    w[at + kSplitLoOffset] = (uint16_t)bf16_rne_bits(v - __uint_as_float(h << 16));
+    const uint32_t hl = bf16_hi_lo(v);
+    w[at] = (uint16_t)hl;
+    w[at + kSplitLoOffset] = (uint16_t)(hl >> 16);
     (void)O;
 }
 
@@ -372,6 +378,150 @@ __global__ __launch_bounds__(256) void gate_backward_tail_kernel(const lbbnn_gat
     }
 }
 
+// ------------------------------------------------------------------------------------------------ K6e
+// lbbnn_gate_members (include/lbbnn.h): the sampled operands of every layer and every ensemble member in one launch.  One
+// workgroup per output row (rows of all layers concatenated); a thread owns up to kGmGroups groups of 8 consecutive k, keeps
+// mu, sigma and alpha of them in registers, then loops over the members.  Per member and group: two Philox calls for the four
+// normals of each quad (the training kernel computes four and uses one), two for the gate uniforms (SAMPLE), and 32 B of
+// operand written as two float4 (fp32) or one 16-B hi unit + one 16-B lo unit (split layout, lbbnn_device.h).  The
+// expressions are those of gate_sample_kernel<true> / gate_finalize_kernel<true>, so the operands are bitwise theirs.
+// G (template): groups per thread, the smallest of 1, 2, 4 that covers the widest layer (register footprint ~ 24 G floats)
+constexpr int kGmThreads = 128;
+constexpr int kGmMaxLd = kGmThreads * 4 * 8;   // 4096
+
+struct GateMembersLaunch {
+    lbbnn_gate_member_desc_t l[LBBNN_MAX_LAYERS];
+    int row0[LBBNN_MAX_LAYERS], row_end[LBBNN_MAX_LAYERS];   // blockIdx.x range of each layer (unused layers: INT_MAX)
+    int vec[LBBNN_MAX_LAYERS];                               // (O,I) inputs readable as float4
+    int members, gates;
+    float temperature;
+    uint64_t member_advance;
+};
+
+template <int kGmGroups>
+__global__ __launch_bounds__(kGmThreads) void gate_members_kernel(const GateMembersLaunch ga, const uint64_t* rng) {
+    __shared__ float red[2][kGmThreads / 64];
+    const int bx = blockIdx.x;
+    const int li = (bx >= ga.row_end[0]) + (bx >= ga.row_end[1]) + (bx >= ga.row_end[2]);
+    lbbnn_gate_member_desc_t L;
+    LBBNN_SELECT_LAYER(L, ga.l, li);
+    int row0, vec;
+    LBBNN_SELECT_LAYER(row0, ga.row0, li);
+    LBBNN_SELECT_LAYER(vec, ga.vec, li);
+    const int o = bx - row0, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const size_t ro = (size_t)o * L.I;
+    const bool sample = ga.gates == LBBNN_GATES_SAMPLE, hard = (L.exact & 8) != 0;
+    const uint64_t seed = rng[0], off0 = rng[1];
+    const uint32_t s_gate = LBBNN_STREAM_GATE * 64u + L.layer_id, s_w = LBBNN_STREAM_EPS_W * 64u + L.layer_id;
+
+    float mu[kGmGroups][8], sg[kGmGroups][8], al[kGmGroups][8];
+#pragma unroll
+    for (int gi = 0; gi < kGmGroups; ++gi) {
+        const int i0 = 8 * (tid + gi * kGmThreads);
+        float r[8], lam[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { mu[gi][e] = 0.f; r[e] = 0.f; lam[e] = 0.f; }
+        if (i0 < L.I) {
+            if (vec) {
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    if (i0 + 4 * q >= L.I) continue;                      // I % 4 == 0: a quad is wholly in or out
+                    const float4 m4 = *reinterpret_cast<const float4*>(L.mu + ro + i0 + 4 * q);
+                    const float4 r4 = *reinterpret_cast<const float4*>(L.rho + ro + i0 + 4 * q);
+                    const float4 l4 = *reinterpret_cast<const float4*>(L.lambdal + ro + i0 + 4 * q);
+                    mu[gi][4 * q] = m4.x; mu[gi][4 * q + 1] = m4.y; mu[gi][4 * q + 2] = m4.z; mu[gi][4 * q + 3] = m4.w;
+                    r[4 * q] = r4.x; r[4 * q + 1] = r4.y; r[4 * q + 2] = r4.z; r[4 * q + 3] = r4.w;
+                    lam[4 * q] = l4.x; lam[4 * q + 1] = l4.y; lam[4 * q + 2] = l4.z; lam[4 * q + 3] = l4.w;
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    if (i0 + e < L.I) { mu[gi][e] = L.mu[ro + i0 + e]; r[e] = L.rho[ro + i0 + e]; lam[e] = L.lambdal[ro + i0 + e]; }
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { sg[gi][e] = softplus_ref(r[e]); al[gi][e] = sigmoid_ref(lam[e]); }
+    }
+
+    // the member biases: thread t draws those of members t, t + kGmThreads, ...
+    if (tid < ga.members) {
+        const float sb = softplus_ref(L.bias_rho[o]), bm = L.bias_mu[o];
+        for (int m = tid; m < ga.members; m += kGmThreads) {
+            float n[4];
+            philox_normal4(seed, off0 + (uint64_t)m * ga.member_advance, LBBNN_STREAM_EPS_B * 64u + L.layer_id,
+                           (uint64_t)(o >> 2), 0u, n);
+            const float e = n[o & 3];
+            L.bias_out[(size_t)m * L.O + o] = bm + sb * e;                                   // :234
+        }
+    }
+
+    const size_t w_ms = (size_t)L.O * L.ld;                  // member stride in 4-byte units (fp32 and split rows alike)
+    for (int m = 0; m < ga.members; ++m) {
+        const uint64_t offs = off0 + (uint64_t)m * ga.member_advance;
+        float gsum = 0.f;
+#pragma unroll
+        for (int gi = 0; gi < kGmGroups; ++gi) {
+            const int i0 = 8 * (tid + gi * kGmThreads);
+            if (i0 >= L.ld) continue;
+            float w[8], c[8];
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int iq = i0 + 4 * q;
+                if (iq >= L.I) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { w[4 * q + e] = 0.f; c[4 * q + e] = 0.f; }
+                    continue;
+                }
+                float n[4], u[4] = {0.f, 0.f, 0.f, 0.f};
+                philox_normal4(seed, offs, s_w, (uint64_t)o, (uint32_t)(iq >> 2), n);
+                if (sample) {
+                    const Philox4 r = philox_bits4(seed, offs, s_gate, (uint64_t)o, (uint32_t)(iq >> 2));
+                    u[0] = uniform24(r.x); u[1] = uniform24(r.y); u[2] = uniform24(r.z); u[3] = uniform24(r.w);
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int k = 4 * q + e;
+                    float g = 0.f, v = 0.f;
+                    if (iq + e < L.I) {
+                        float dcda;
+                        g = sample ? gate_draw(al[gi][k], u[e], ga.temperature, hard, &dcda) : (al[gi][k] > 0.5f ? 1.f : 0.f);
+                        const float sigma = sg[gi][k], mu_k = mu[gi][k], ek = n[e];
+                        v = g * (mu_k + sigma * ek);                                            // :232-233
+                    }
+                    w[k] = v; c[k] = g;
+                    gsum += g;
+                }
+            }
+            if (L.flags & LBBNN_F_SPLIT16) {
+                uint32_t hl[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) hl[k] = bf16_hi_lo(w[k]);
+                uint16_t* const p = static_cast<uint16_t*>(L.w_out) + 2 * (m * w_ms) + split_hi_index((size_t)o, i0, L.ld);
+                *reinterpret_cast<uint4*>(p) = make_uint4((hl[0] & 0xFFFFu) | (hl[1] << 16), (hl[2] & 0xFFFFu) | (hl[3] << 16),
+                                                          (hl[4] & 0xFFFFu) | (hl[5] << 16), (hl[6] & 0xFFFFu) | (hl[7] << 16));
+                *reinterpret_cast<uint4*>(p + kSplitLoOffset) =
+                    make_uint4((hl[0] >> 16) | (hl[1] & 0xFFFF0000u), (hl[2] >> 16) | (hl[3] & 0xFFFF0000u),
+                               (hl[4] >> 16) | (hl[5] & 0xFFFF0000u), (hl[6] >> 16) | (hl[7] & 0xFFFF0000u));
+            } else {
+                float* const p = static_cast<float*>(L.w_out) + m * w_ms + (size_t)o * L.ld + i0;
+                *reinterpret_cast<float4*>(p) = make_float4(w[0], w[1], w[2], w[3]);
+                *reinterpret_cast<float4*>(p + 4) = make_float4(w[4], w[5], w[6], w[7]);
+            }
+            if (L.gates) {
+                float* const p = L.gates + (size_t)m * L.O * L.I + ro;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) if (i0 + k < L.I) p[i0 + k] = c[k];
+            }
+        }
+        if (L.gate_rows) {                                    // uniform: per-member row sum, fixed order (lanes, then waves)
+            const float s = wave_sum(gsum);
+            if (lane == 0) red[m & 1][wv] = s;
+            __syncthreads();                                  // (double buffer: one barrier per member)
+            if (tid == 0) L.gate_rows[(size_t)m * L.O + o] = red[m & 1][0] + red[m & 1][1];
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ K7
 // 32x32 tiles of theta (I,O) through LDS: coalesced reads along O, coalesced writes along I.
 __global__ __launch_bounds__(256) void vd_operands_kernel(const float* __restrict__ theta, void* e_w, void* var_w,
@@ -570,6 +720,41 @@ extern "C" int lbbnn_gate_backward_draw(const lbbnn_gate_bwd_draw_args_t* p, con
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(gate_backward_kernel<true>, dim3(a.O), dim3(256), 0, s, d, rng);
     hipLaunchKernelGGL(gate_backward_tail_kernel<true>, dim3(1), dim3(256), 0, s, d, rng);
+    return (int)hipGetLastError();
+}
+
+extern "C" int lbbnn_gate_members(const lbbnn_gate_member_desc_t* layers, int n, int members, int gates, float temperature,
+                                  const uint64_t* rng, uint64_t member_advance, void* stream) {
+    if (!layers) return LBBNN_E_NULL;
+    if (n < 1 || n > LBBNN_MAX_LAYERS || members < 1 || members > 65535) return LBBNN_E_SHAPE;
+    if (gates != LBBNN_GATES_SAMPLE && gates != LBBNN_GATES_MPM) return LBBNN_E_FLAGS;
+    if (gates == LBBNN_GATES_SAMPLE && !(temperature > 0.f)) return LBBNN_E_FLAGS;
+    GateMembersLaunch ga{};
+    long long rows = 0;
+    int max_ld = 0;
+    for (int l = 0; l < LBBNN_MAX_LAYERS; ++l) { ga.row0[l] = INT_MAX; ga.row_end[l] = INT_MAX; }
+    for (int l = 0; l < n; ++l) {
+        const lbbnn_gate_member_desc_t& d = layers[l];
+        if (!d.mu || !d.rho || !d.lambdal || !d.bias_mu || !d.bias_rho || !d.w_out || !d.bias_out) return LBBNN_E_NULL;
+        if (d.O <= 0 || d.I <= 0 || d.ld > kGmMaxLd) return LBBNN_E_SHAPE;
+        if (d.ld < d.I || (d.ld & 31) || (reinterpret_cast<uintptr_t>(d.w_out) & 15u)) return LBBNN_E_ALIGN;
+        if (d.flags & ~LBBNN_F_SPLIT16) return LBBNN_E_FLAGS;
+        ga.l[l] = d;
+        max_ld = d.ld > max_ld ? d.ld : max_ld;
+        ga.vec[l] = (d.I % 4) == 0 &&
+                    ((reinterpret_cast<uintptr_t>(d.mu) | reinterpret_cast<uintptr_t>(d.rho) | reinterpret_cast<uintptr_t>(d.lambdal)) & 15u) == 0;
+        ga.row0[l] = (int)rows;
+        rows += d.O;
+        if (rows > INT_MAX) return LBBNN_E_SHAPE;
+        ga.row_end[l] = (int)rows;
+    }
+    if (!rng) return LBBNN_E_NOISE;
+    ga.members = members; ga.gates = gates; ga.temperature = temperature; ga.member_advance = member_advance;
+    const dim3 grid((unsigned)rows), block(kGmThreads);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (max_ld <= kGmThreads * 8) hipLaunchKernelGGL(gate_members_kernel<1>, grid, block, 0, s, ga, rng);
+    else if (max_ld <= kGmThreads * 16) hipLaunchKernelGGL(gate_members_kernel<2>, grid, block, 0, s, ga, rng);
+    else hipLaunchKernelGGL(gate_members_kernel<4>, grid, block, 0, s, ga, rng);
     return (int)hipGetLastError();
 }
 

@@ -57,9 +57,10 @@ struct GemmArgs {
     // lbbnn_lrt_gemm_members: gridDim.z = members; member m = blockIdx.z is the same product on x + m*x_ms, e_w + m*w_ms
     // (var_w shared), out + m*o_ms, its noise drawn at Philox offset rng[1] + m*m_adv -- an ensemble of forwards
     // (test_ensemble, LBBNN-GP-MF-MNF.py:286-294) in one launch, every member bit-identical to its own launch
+    // (lbbnn_gemm_members_mean: bias_mean + m*b_ms as well -- each member its own bias; 0 = shared)
     int single16;                // LBBNN_F_SINGLE16 (host-side dispatch only)
     int members;
-    long long x_ms, w_ms, o_ms;
+    long long x_ms, w_ms, o_ms, b_ms;
     unsigned long long m_adv, m_off;     // m_off: filled in by member_view()
 };
 
@@ -69,6 +70,7 @@ __device__ __forceinline__ GemmArgs member_view(const GemmArgs& in) {
     if (in.members > 1) {
         const long long m = blockIdx.z;
         a.x = in.x + m * in.x_ms; a.e_w = in.e_w + m * in.w_ms; a.out = in.out + m * in.o_ms;
+        if (in.bias_mean) a.bias_mean = in.bias_mean + m * in.b_ms;
         a.m_off = (unsigned long long)m * in.m_adv;
     }
     return a;
@@ -947,7 +949,7 @@ static int lrt_gemm_impl(const float* x, int ldx, const void* e_w, const void* v
                          const FinalizePiggy* fin = nullptr, bool* hosted = nullptr,
                          const float* comb_x = nullptr, int ld_cx = 0, const float* comb_add = nullptr, int ld_ca = 0,
                          int members = 1, long long x_ms = 0, long long w_ms = 0, long long o_ms = 0,
-                         unsigned long long m_adv = 0) {
+                         unsigned long long m_adv = 0, long long b_ms = 0) {
     if (B == 0 && I > 0 && O > 0) return 0;        // empty batch (torch.mm of 0 rows, LBBNN-GP-MF-LRT.py:172): nothing to do
     if (!x || !e_w || !out) return LBBNN_E_NULL;
     if (B <= 0 || I <= 0 || O <= 0 || ldx < I || ldo < O) return LBBNN_E_SHAPE;
@@ -974,7 +976,7 @@ static int lrt_gemm_impl(const float* x, int ldx, const void* e_w, const void* v
     if (fin) a.fin = *fin; else a.fin = FinalizePiggy{};
     a.comb_x = comb_x; a.comb_add = comb_add; a.ld_cx = ld_cx; a.ld_ca = ld_ca;
     a.single16 = (flags & LBBNN_F_HALF16) ? 2 : ((flags & LBBNN_F_SINGLE16) ? 1 : 0);
-    a.members = members; a.x_ms = x_ms; a.w_ms = w_ms; a.o_ms = o_ms; a.m_adv = m_adv; a.m_off = 0;
+    a.members = members; a.x_ms = x_ms; a.w_ms = w_ms; a.o_ms = o_ms; a.b_ms = b_ms; a.m_adv = m_adv; a.m_off = 0;
     if (members > 1 && (kchunk || fin || eps || std_out || comb_x)) return LBBNN_E_FLAGS;
 
     const bool xvec = ((I & 3) == 0) && ((ldx & 3) == 0) && ((reinterpret_cast<uintptr_t>(x) & 15u) == 0);
@@ -1092,6 +1094,27 @@ extern "C" int lbbnn_lrt_gemm_members(const float* x, int ldx, int64_t x_mstride
     return lrt_gemm_impl(x, ldx, e_w, var_w, ld, bias_mean, bias_var, nullptr, nullptr, rng, rng_stream, row_offset, out, ldo,
                          nullptr, B, I, O, flags, stream, 0, nullptr, nullptr, nullptr, 0, nullptr, 0, members,
                          (long long)x_mstride, (long long)w_mstride, (long long)o_mstride, member_advance);
+}
+
+// The mean-only product of every member of an ensemble in ONE launch, each member with its own weights and bias
+// (include/lbbnn.h): the sampled baseline layer's F.linear (LBBNN-GP-MF.py:255) for all members of lbbnn_gate_members.
+// The tile configuration depends on (B, I, O) only, so member m takes the same kernel and summation order as its own
+// lbbnn_lrt_gemm(LBBNN_F_MEAN_ONLY) call: fp32 tiles / LDS-DMA tiles, the bf16x3 kernel (launch_split) and the skinny
+// O <= 16 head with its fused log_softmax all address their member through member_view (blockIdx.z).
+extern "C" int lbbnn_gemm_members_mean(const float* x, int ldx, int64_t x_mstride, const void* w, int64_t w_mstride, int ld,
+                                       const float* bias, int64_t b_mstride, float* out, int ldo, int64_t o_mstride,
+                                       int B, int I, int O, int flags, int members, void* stream) {
+    if (!x || !w || !out) return LBBNN_E_NULL;
+    if (members < 1 || members > 65535) return LBBNN_E_SHAPE;
+    if (flags & ~(LBBNN_F_RELU | LBBNN_F_SPLIT16 | LBBNN_F_LOG_SOFTMAX)) return LBBNN_E_FLAGS;
+    if ((flags & LBBNN_F_LOG_SOFTMAX) && O > 16) return LBBNN_E_FLAGS;
+    if (x_mstride < 0 || w_mstride < 0 || b_mstride < 0 || o_mstride < (int64_t)B * ldo) return LBBNN_E_SHAPE;
+    if ((x_mstride & 3) || (w_mstride & 3) || (o_mstride & 3)) return LBBNN_E_ALIGN;       // every member 16-B aligned
+    if (flags & LBBNN_F_SPLIT16)                                                           // 32-bit buffer offsets
+        if (((size_t)(B - 1) * ldx + I) * 4 >= 0x7FFFFFF0u) return LBBNN_E_SHAPE;
+    return lrt_gemm_impl(x, ldx, w, nullptr, ld, bias, nullptr, nullptr, nullptr, nullptr, 0u, 0, out, ldo, nullptr,
+                         B, I, O, flags | LBBNN_F_MEAN_ONLY, stream, 0, nullptr, nullptr, nullptr, 0, nullptr, 0, members,
+                         (long long)x_mstride, (long long)w_mstride, (long long)o_mstride, 0ull, (long long)b_mstride);
 }
 
 // Mean-only product with the input-gradient combination in its epilogue (include/lbbnn.h)

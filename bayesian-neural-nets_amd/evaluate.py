@@ -7,6 +7,12 @@
 * density[s] = mean of one Bernoulli draw of every layer's inclusion probabilities (``layer.gamma.rsample()``).
 
 The reference's own ``test_ensemble`` also runs unchanged on these modules; this is the batched convenience form.
+
+Baseline LBBNN networks (``base.BayesianNetwork``, LBBNN-GP-MF.py:345-502) take their own batched form, ``base_ensemble``:
+one lbbnn_gate_members launch draws every member's gates, weights and biases (the training kernels' streams and counters,
+member m at Philox offset live + m), then one mean-only GEMM launch per layer runs all members.  ``gates="mpm"`` selects the
+median probability model of ``outofsample(medimod=True)``.  ``predictive_entropy`` is the ``outofsample`` entropy of every
+family.
 """
 from typing import Dict, Optional
 
@@ -99,12 +105,73 @@ def ensemble_forward_batched(net, data: torch.Tensor, samples: int = 10) -> torc
     return h
 
 
+def _is_base(net) -> bool:
+    from . import base
+    return isinstance(net, base.BayesianNetwork)
+
+
 @torch.no_grad()
-def ensemble_forward(net, data: torch.Tensor, samples: int = 10, batched=None) -> torch.Tensor:
-    """(samples, B, classes) log-probabilities of ``samples`` stochastic forwards (net left in eval mode).
-    ``batched``: None = the one-launch-per-kernel form when the network qualifies (``_batched_ok``), else the loop of
-    fused single forwards; True / False force one of them."""
+def base_ensemble(net, data: torch.Tensor, samples: int = 10, *, gates: str = "sample", max_members: Optional[int] = None,
+                  keep_gates: bool = False) -> Dict[str, object]:
+    """``samples`` evaluation forwards of a baseline LBBNN network in 1 + 3 launches per chunk of at most ``max_members``
+    members (default: all in one).  Member m draws at Philox offset (live offset + m) and equals, bit for bit, what
+    ``net.sample_predict`` / the layers' ``sample_forward`` compute at that offset; chunked and unchunked results are the same
+    bits.  The live offset advances by ``samples``.  Returns ``outputs`` (samples, B, classes) log-probabilities,
+    ``gate_rows`` (per layer (samples, O): the sum over each row of the gates the member used) and, with ``keep_gates``,
+    ``gates`` (per layer (samples, O, I))."""
+    if not _is_base(net):
+        raise ValueError("bnn_amd: base_ensemble takes a baseline LBBNN network (bnn_amd.base.BayesianNetwork)")
+    if not data.is_cuda:
+        raise RuntimeError("bnn_amd: ensemble evaluation needs a HIP device tensor (data is on %s); there is no CPU path"
+                           % data.device)
+    S = int(samples)
+    if S < 1:
+        raise ValueError("bnn_amd: samples must be >= 1")
+    chunk = S if max_members is None else int(max_members)
+    if chunk < 1:
+        raise ValueError("bnn_amd: max_members must be >= 1")
     net.eval()
+    B, C = data.reshape(-1, net.dims[0]).shape[0], net.dims[-1]
+    st = ops.RngState.get(data.device)
+    head = torch.empty((S, -(-(B * C) // 4) * 4), dtype=torch.float32, device=data.device)   # 16-B aligned member rows
+    rows, kept, outs = [], [], []
+    for m0 in range(0, S, chunk):
+        c = min(chunk, S - m0)
+        o, r, g = net._predict_members(data, st.t, c, gates, out=head[m0:m0 + c], rows=True, keep_gates=keep_gates)
+        st.advance(c)
+        outs.append(o)
+        rows.append(r)
+        kept.append(g)
+    if C <= 16:
+        outputs = head[:, :B * C].view(S, B, C)             # the chunks wrote their log-probabilities into `head`
+    else:
+        outputs = outs[0] if len(outs) == 1 else torch.cat(outs)
+    cat = lambda parts: [p[0] if len(parts) == 1 else torch.cat(p) for p in zip(*parts)]
+    return {"outputs": outputs, "gate_rows": cat(rows), "gates": cat(kept) if keep_gates else None}
+
+
+@torch.no_grad()
+def ensemble_forward(net, data: torch.Tensor, samples: int = 10, batched=None, *, gates: str = "sample",
+                     max_members: Optional[int] = None) -> torch.Tensor:
+    """(samples, B, classes) log-probabilities of ``samples`` stochastic forwards (net left in eval mode).
+    ``batched``: None = the one-launch-per-kernel form when the network qualifies (``_batched_ok``; a baseline network on a
+    HIP device: ``base_ensemble``), else the loop of fused single forwards (``net.sample_predict`` for a baseline network);
+    True / False force one of them.  Either form advances the live Philox offset by ``samples``.
+    ``gates`` ("sample" or "mpm") and ``max_members`` (members per launch of the batched form) apply to baseline networks
+    only."""
+    net.eval()
+    if _is_base(net):
+        if gates not in ("sample", "mpm"):
+            raise ValueError("bnn_amd: gates must be 'sample' or 'mpm', got %r" % (gates,))
+        if batched is None:
+            batched = data.is_cuda
+        if batched:
+            return base_ensemble(net, data, samples, gates=gates, max_members=max_members)["outputs"]
+        return torch.stack([net.sample_predict(data, gates=gates) for _ in range(samples)])
+    if gates != "sample":
+        raise ValueError("bnn_amd: gates=%r (the median probability model) exists for baseline LBBNN networks only" % (gates,))
+    if max_members is not None:
+        raise ValueError("bnn_amd: max_members applies to baseline LBBNN networks only")
     if batched is None:
         batched = _batched_ok(net, data)
     if batched:
@@ -115,6 +182,12 @@ def ensemble_forward(net, data: torch.Tensor, samples: int = 10, batched=None) -
 
 @torch.no_grad()
 def ensemble_eval(net, data: torch.Tensor, target: Optional[torch.Tensor] = None, samples: int = 10) -> Dict[str, object]:
+    """test_ensemble's numbers for one batch: ``outputs``, ``pred_ensemble``, ``pred_posterior_mean``, ``density`` (and
+    ``correct_*`` with a target).  Baseline networks: ``density[s]`` is the mean gate of member s over all weights -- the gates
+    the member actually used (the reference draws a separate set, LBBNN-GP-MF.py:390-394) -- and the posterior mean is the
+    mode-2 forward (weight = alpha * mu) with alpha = sigmoid(lambdal) set as the reference sets it (:369-374, :413)."""
+    if _is_base(net):
+        return _base_ensemble_eval(net, data, target, samples)
     outputs = ensemble_forward(net, data, samples)
     density = []
     for _ in range(samples):
@@ -128,3 +201,34 @@ def ensemble_eval(net, data: torch.Tensor, target: Optional[torch.Tensor] = None
         res["correct_ensemble"] = int(pred_ens.eq(target).sum())
         res["correct_posterior_mean"] = int(pred_mean.eq(target).sum())
     return res
+
+
+def _base_ensemble_eval(net, data, target, samples):
+    r = base_ensemble(net, data, samples)
+    outputs = r["outputs"]
+    layers = (net.l1, net.l2, net.l3)
+    n_w = sum(l.out_features * l.in_features for l in layers)
+    density = torch.stack([rw.double().sum(1) for rw in r["gate_rows"]]).sum(0) / n_w
+    for l in layers:
+        l.alpha = 1 / (1 + torch.exp(-l.lambdal.detach()))                  # :369-374
+        l.gamma.alpha = l.alpha
+    pred_mean = net(data, None, None, None, sample=False).argmax(1)          # :413 (mode 2: weight = alpha * mu)
+    pred_ens = outputs.mean(0).argmax(1)
+    res = {"outputs": outputs, "pred_ensemble": pred_ens, "pred_posterior_mean": pred_mean, "density": density.float()}
+    if target is not None:
+        res["correct_ensemble"] = int(pred_ens.eq(target).sum())
+        res["correct_posterior_mean"] = int(pred_mean.eq(target).sum())
+    return res
+
+
+@torch.no_grad()
+def predictive_entropy(outputs: torch.Tensor) -> torch.Tensor:
+    """Per-row entropy of the ensemble's predictive distribution as ``outofsample`` computes it (LBBNN-GP-MF.py:476-496,
+    LBBNN-GP-MF-LRT.py:318-334): per member sigmoid(log-probabilities) normalised over the classes of each row, the mean over
+    the members, then -sum p log p per row.  ``outputs``: (samples, B, classes); returns (B,).  Any family."""
+    if outputs.dim() != 3:
+        raise ValueError("bnn_amd: outputs must be (samples, B, classes), got %s" % (tuple(outputs.shape),))
+    p = torch.sigmoid(outputs.float())
+    p = p / p.sum(-1, keepdim=True)
+    m = p.mean(0)
+    return -(m * torch.log(m)).sum(-1)

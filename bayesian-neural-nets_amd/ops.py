@@ -33,6 +33,8 @@ STREAM_ROW_MASK = 7
 STREAM_GATE = 8          # the baseline layer's in-kernel draws (sample_elbo(draws="hip")): gate uniforms, tau_w, tau_b
 STREAM_GAMMA_W = 9
 STREAM_GAMMA_B = 10
+GATES_SAMPLE = 0         # lbbnn_gate_members: gates drawn as in training; the median probability model (alpha > 0.5)
+GATES_MPM = 1
 
 
 # GEMM arithmetic.  A name selects the operand FORMAT of the forward's dual-moment GEMM:

@@ -7,6 +7,9 @@ precisions inside the HIP kernels (sample_elbo(draws="hip")), so it is captured 
     python examples/train_base_synthetic.py               # graphed hip-draw step
     EAGER=1 python examples/train_base_synthetic.py       # the same step, eager
     COND_OPT=1 python examples/train_base_synthetic.py    # mask the weight_mu gradients with the drawn gates (:333-336)
+
+It ends with the reference's evaluation on a held-out synthetic batch: bnn_amd.evaluate.ensemble_eval (test_ensemble) and the
+accuracy and predictive entropy of the median probability model (outofsample(medimod=True)).
 """
 import os
 import sys
@@ -67,3 +70,16 @@ for epoch in range(EPOCHS):
     print("epoch %d  loss %.1f  (%.3f ms/iteration)" % (epoch, float(loss.detach()), (time.perf_counter() - t0) / NUM_BATCHES * 1e3))
 with torch.no_grad():
     print("mean inclusion probability per layer:", ["%.3f" % float(l.alpha.mean()) for l in ls])
+
+# test_ensemble (:345-441) on a held-out synthetic batch: hard gates as the reference sets them before its test (:619-621), ten
+# members drawn in one launch; then the median probability model of outofsample(medimod=True) (:469-473)
+for l in ls:
+    l.gamma.exact = True
+test_x = torch.rand(1000, 1, 28, 28, device=DEVICE, generator=g)
+test_y = (test_x.view(1000, 784) @ proj).argmax(-1)
+res = bnn_amd.evaluate.ensemble_eval(net, test_x, test_y, samples=10)
+print("held-out: ensemble accuracy %.3f, posterior-mean accuracy %.3f, density %.3f"
+      % (res["correct_ensemble"] / 1000, res["correct_posterior_mean"] / 1000, float(res["density"].mean())))
+mpm = bnn_amd.evaluate.ensemble_forward(net, test_x, 10, gates="mpm")
+print("median probability model: accuracy %.3f, mean predictive entropy %.3f"
+      % (float(mpm.mean(0).argmax(1).eq(test_y).float().mean()), float(bnn_amd.evaluate.predictive_entropy(mpm).mean())))

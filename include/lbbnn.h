@@ -463,6 +463,48 @@ int lbbnn_philox_std_gamma(const uint64_t* rng, uint32_t rng_stream, const float
 int lbbnn_gamma_grad(const float* x, const float* a, int64_t n, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Ensemble evaluation of the baseline LBBNN (test_ensemble / outofsample, LBBNN-GP-MF.py:345-502): `members` stochastic
+ * forwards of one batch in 1 + n launches instead of 2 + 1 per layer and member.
+ *
+ * lbbnn_gate_members: the gate x Gaussian weight draw of every layer and every member in ONE launch (one workgroup per
+ *   output row of each layer; mu, rho, lambdal read once, alpha = sigmoid(lambdal) and sigma = softplus(rho) computed once).
+ *   Member m draws from the Philox state {rng[0], rng[1] + m * member_advance} with the streams and counters of
+ *   lbbnn_gate_sample_draw: gate uniform from stream GATE*64 + layer_id at counter (o, i/4), eps_w from EPS_W*64 + layer_id,
+ *   eps_b from EPS_B*64 + layer_id.  Gates:
+ *     gates = LBBNN_GATES_SAMPLE: c as lbbnn_gate_sample_draw draws it (the hard draw u < alpha when exact bit 8 is set,
+ *             else the relaxed gate at `temperature`, which must then be > 0);
+ *     gates = LBBNN_GATES_MPM:    c = (alpha > 0.5), the median probability model (outofsample(medimod=True), :469-473).
+ *   w = c * (mu + sigma * eps_w) and bias = bias_mu + softplus(bias_rho) * eps_b: member m's w_out and bias_out are bitwise
+ *   what lbbnn_gate_sample_draw writes at offset rng[1] + m * member_advance.  No log-probabilities, no Gamma draws.
+ *   Per layer: w_out [members][O][ld] GEMM operands (fp32, or the split bf16 hi|lo layout with LBBNN_F_SPLIT16; zero tail
+ *   [I, ld); 16-B aligned), bias_out [members][O]; nullable gate_rows [members][O] = sum_i c (fixed summation order: bitwise
+ *   reproducible) and gates [members][O][I] = c.  ld a multiple of 32, I <= ld <= 4096.  rng is required (LBBNN_E_NOISE).
+ * lbbnn_gemm_members_mean: the mean-only product out = x . w^T + bias of lbbnn_lrt_gemm(LBBNN_F_MEAN_ONLY) for every member,
+ *   gridDim.z = members: x + m * x_mstride (0 = the same input for every member), w + m * w_mstride, bias + m * b_mstride
+ *   (floats; bias nullable), out + m * o_mstride.  Member m is bitwise the single lbbnn_lrt_gemm call on its slices.
+ *   flags: LBBNN_F_RELU | LBBNN_F_SPLIT16 | LBBNN_F_LOG_SOFTMAX (O <= 16); LBBNN_F_MEAN_ONLY is implied.  x_mstride,
+ *   w_mstride and o_mstride multiples of 4 (every member 16-B aligned); o_mstride >= B * ldo.  1 <= members <= 65535. */
+#define LBBNN_GATES_SAMPLE 0
+#define LBBNN_GATES_MPM 1
+
+typedef struct lbbnn_gate_member_desc {
+    const float *mu, *rho, *lambdal;          /* (O,I) */
+    const float *bias_mu, *bias_rho;          /* (O)   */
+    void* w_out;                              /* [members][O][ld] */
+    float* bias_out;                          /* [members][O]     */
+    float* gate_rows;                         /* [members][O], nullable */
+    float* gates;                             /* [members][O][I], nullable */
+    int O, I, ld, flags, exact;               /* flags: 0 | LBBNN_F_SPLIT16; exact: the layer's exact bits (8 = gamma) */
+    uint32_t layer_id;
+} lbbnn_gate_member_desc_t;
+
+int lbbnn_gate_members(const lbbnn_gate_member_desc_t* layers, int n, int members, int gates, float temperature,
+                       const uint64_t* rng, uint64_t member_advance, void* stream);
+int lbbnn_gemm_members_mean(const float* x, int ldx, int64_t x_mstride, const void* w, int64_t w_mstride, int ld,
+                            const float* bias, int64_t b_mstride, float* out, int ldo, int64_t o_mstride,
+                            int B, int I, int O, int flags, int members, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K7  lbbnn_vd_operands -- Gaussian variational-dropout layer (variational_dropout.py:55-68).
  *   phi = x.theta ; delta = (x^2).(theta^2) * alpha ; out = phi + sqrt(delta)*zeta        :64-67
  * theta is (I,O) row-major (NN layout).  This pass writes the GEMM operands theta^T and (theta^2)^T as
