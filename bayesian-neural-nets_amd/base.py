@@ -508,6 +508,8 @@ class BayesianNetwork(nn.Module):
             if l.noise:
                 raise ValueError("bnn_amd: evaluation draws its own noise in-kernel; injected draws (layer.noise) belong to the "
                                  "torch-draw forward -- clear layer.noise first")
+        if any(ops.operand_ld(l.in_features) > ops.GATE_MEMBERS_MAX_LD for l in layers):
+            return self._predict_members_loop(input, rng, S, gates, out, rows, keep_gates)
         from . import distributions
         x = input.view(-1, self.dims[0]).float()
         if x.stride(1) != 1 or x.stride(0) < self.dims[0]:
@@ -551,6 +553,45 @@ class BayesianNetwork(nn.Module):
         for l in layers:
             l.log_prior, l.log_variational_posterior = 0, 0          # an evaluation forward keeps no log-probabilities (:253)
         return (res, [b["rows"] for b in bufs] if rows else None, [b["gates"] for b in bufs] if keep_gates else None)
+
+    def _predict_members_loop(self, input, rng, S, gates, out, rows, keep_gates):
+        """``_predict_members`` for a network with a layer wider than lbbnn_gate_members takes (operand_ld(in_features) >
+        ops.GATE_MEMBERS_MAX_LD): member m is the chain of the layers' ``sample_forward`` at {rng[0], rng[1] + m} -- by
+        definition what the batched form computes -- and its gates / gate row sums are the ones that chain drew.  3 layer
+        calls per member; the layers keep the last member's draws, as after ``sample_forward``.  The median probability model
+        has no training-kernel chain: gates="mpm" raises."""
+        if gates != "sample":
+            raise ValueError("bnn_amd: gates='mpm' needs every layer within lbbnn_gate_members' width (operand_ld(in_features) "
+                             "<= %d)" % ops.GATE_MEMBERS_MAX_LD)
+        layers = (self.l1, self.l2, self.l3)
+        C = self.dims[-1]
+        head = "log_softmax" if C <= 16 else None
+        x = input.view(-1, self.dims[0]).float()
+        if x.stride(1) != 1 or x.stride(0) < self.dims[0]:
+            x = x.contiguous()
+        B = x.shape[0]
+        res = torch.empty((S, B, C), dtype=torch.float32, device=x.device)
+        g_rows = [torch.empty((S, l.out_features), dtype=torch.float32, device=x.device) for l in layers] if rows else None
+        g_all = [torch.empty((S, l.out_features, l.in_features), dtype=torch.float32, device=x.device)
+                 for l in layers] if keep_gates else None
+        for m in range(S):
+            r = rng[:2].clone()
+            r[1] += m
+            h = x
+            for k, l in enumerate(layers):
+                h, _, _ = l.sample_forward(h, activation="relu" if k < 2 else head, rng=r)
+                if rows:
+                    g_rows[k][m] = l.gammas.sum(1)
+                if keep_gates:
+                    g_all[k][m] = l.gammas
+            res[m] = h if head else F.log_softmax(h, dim=1)
+        if out is not None:
+            if out.dim() != 2 or out.shape[0] != S or out.shape[1] < B * C:
+                raise RuntimeError("bnn_amd: out must be a (S, >= B*classes) buffer")
+            out[:, :B * C].copy_(res.view(S, B * C))
+        for l in layers:
+            l.log_prior, l.log_variational_posterior = 0, 0          # an evaluation forward keeps no log-probabilities (:253)
+        return res, g_rows, g_all
 
     def log_variational_posterior(self):
         return (self.l1.log_variational_posterior + self.l2.log_variational_posterior

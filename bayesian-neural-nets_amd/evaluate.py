@@ -118,7 +118,9 @@ def base_ensemble(net, data: torch.Tensor, samples: int = 10, *, gates: str = "s
     ``net.sample_predict`` / the layers' ``sample_forward`` compute at that offset; chunked and unchunked results are the same
     bits.  The live offset advances by ``samples``.  Returns ``outputs`` (samples, B, classes) log-probabilities,
     ``gate_rows`` (per layer (samples, O): the sum over each row of the gates the member used) and, with ``keep_gates``,
-    ``gates`` (per layer (samples, O, I))."""
+    ``gates`` (per layer (samples, O, I)).  A network with a layer wider than lbbnn_gate_members takes
+    (``ops.operand_ld(in_features) > ops.GATE_MEMBERS_MAX_LD``) runs each member as its ``sample_forward`` chain instead
+    (``BayesianNetwork._predict_members_loop``; ``gates="mpm"`` raises there)."""
     if not _is_base(net):
         raise ValueError("bnn_amd: base_ensemble takes a baseline LBBNN network (bnn_amd.base.BayesianNetwork)")
     if not data.is_cuda:

@@ -35,6 +35,7 @@ STREAM_GAMMA_W = 9
 STREAM_GAMMA_B = 10
 GATES_SAMPLE = 0         # lbbnn_gate_members: gates drawn as in training; the median probability model (alpha > 0.5)
 GATES_MPM = 1
+GATE_MEMBERS_MAX_LD = 4096  # widest operand row lbbnn_gate_members takes (kGmMaxLd); wider layers: BayesianNetwork's member loop
 
 
 # GEMM arithmetic.  A name selects the operand FORMAT of the forward's dual-moment GEMM:

@@ -162,3 +162,39 @@ def test_hip_draws_need_a_device_tensor():
         net.sample_elbo(x, y, draws="hip")
     with pytest.raises(RuntimeError, match="HIP device"):
         net.l1.sample_forward(x.view(2, -1))
+
+
+@pytest.mark.parametrize("T", [0.5, 0.001])
+def test_relaxed_reference_is_torch_relaxed_bernoulli(T):
+    """tests/base_draw_ref._relaxed, the gate reference of every GPU draw test, against torch's own
+    RelaxedBernoulli(probs, T).rsample() on the same torch.rand uniforms (reseeded): the values in fp32 (the same operations:
+    equal), and in fp64 the values and the autograd gradient with respect to lambdal wherever the fp32 clamp constants of the
+    reference do not bite (fp64 torch clamps at the fp64 constants)."""
+    from base_draw_ref import _relaxed, gate_clamp_classes
+    lam = torch.empty(20000, dtype=torch.float64).uniform_(-8, 8, generator=torch.Generator().manual_seed(1))
+    RB = torch.distributions.RelaxedBernoulli
+    # fp32
+    p32 = torch.sigmoid(lam.float())
+    torch.manual_seed(5)
+    u32 = torch.rand(p32.shape, dtype=torch.float32)
+    torch.manual_seed(5)
+    ref32 = RB(probs=p32, temperature=torch.tensor(T)).rsample()
+    assert torch.equal(_relaxed(p32, u32, T), ref32)
+    # fp64 with autograd through alpha = sigmoid(lambdal)
+    l1 = lam.clone().requires_grad_(True)
+    l2 = lam.clone().requires_grad_(True)
+    torch.manual_seed(6)
+    u64 = torch.rand(lam.shape, dtype=torch.float64)
+    mine = _relaxed(torch.sigmoid(l1), u64, T)
+    torch.manual_seed(6)
+    theirs = RB(probs=torch.sigmoid(l2), temperature=torch.tensor(T, dtype=torch.float64)).rsample()
+    w = torch.randn(lam.shape, dtype=torch.float64, generator=torch.Generator().manual_seed(2))
+    (mine * w).sum().backward()
+    (theirs * w).sum().backward()
+    inside, outside = gate_clamp_classes(torch.sigmoid(lam), u64, T)
+    assert int(inside.sum()) > 100
+    assert torch.allclose(mine[inside], theirs[inside], rtol=1e-12, atol=0)
+    assert torch.allclose(l1.grad[inside], l2.grad[inside], rtol=1e-9, atol=0)
+    # outside the fp32 clamps the reference's gate is a clamp constant with no gradient
+    assert (l1.grad[outside] == 0).all()
+    assert ((mine[outside] == torch.finfo(torch.float32).tiny) | (mine[outside] == 1 - torch.finfo(torch.float32).eps)).all()

@@ -5,13 +5,13 @@ are the documented draws, the outputs match the fp64 oracle on the regenerated n
 import pytest
 import torch
 
+from base_draw_ref import _chain, _relaxed, _rng
 from conftest import rel_err
 from oracle import lbbnn_oracle as orc
 
 pytestmark = pytest.mark.gpu
 
 TIGHT = 5e-6
-F32 = torch.finfo(torch.float32)
 
 
 @pytest.fixture(scope="module")
@@ -36,12 +36,6 @@ def temper(bnn):
     bnn.distributions.TEMPER_PRIOR = old
 
 
-def _relaxed(alpha, u, T):
-    p, uc = alpha.clamp(min=F32.eps, max=1 - F32.eps), u.clamp(min=F32.eps, max=1 - F32.eps)
-    z = (uc.log() - (-uc).log1p() + p.log() - (-p).log1p()) / T
-    return torch.clamp(torch.sigmoid(z), min=F32.tiny, max=1.0 - F32.eps)
-
-
 def _net(bnn, dev, dims, hard, seed=0):
     torch.manual_seed(seed)
     net = bnn.base.BayesianNetwork(dims).to(dev)
@@ -50,18 +44,6 @@ def _net(bnn, dev, dims, hard, seed=0):
             l.lambdal.uniform_(-2.5, 2.5)          # gates that vary (the default init puts every alpha in (0.5, 0.73))
             l.gamma.exact = hard
     return net
-
-
-def _rng(dev, seed, offset):
-    return torch.tensor([seed, offset], dtype=torch.int64, device=dev)
-
-
-def _chain(net, x, rng):
-    """The training kernels on the same draws: sample_forward of the three layers at one Philox snapshot."""
-    h = x.view(-1, net.dims[0])
-    for k, l in enumerate((net.l1, net.l2, net.l3)):
-        h, _, _ = l.sample_forward(h, activation="relu" if k < 2 else "log_softmax", rng=rng)
-    return h
 
 
 SHAPES = [((784, 400, 600, 10), 1000, 10), ((50, 37, 29, 3), 33, 3)]
