@@ -285,6 +285,8 @@ SIGNATURES = {
     "lbbnn_gate_members": (c_i, [ctypes.POINTER(GateMemberDesc), c_i, c_i, c_i, ctypes.c_float, c_p, c_u64, c_p]),
     "lbbnn_gemm_members_mean": (c_i, [c_p, c_i, c_i64, c_p, c_i64, c_i, c_p, c_i64, c_p, c_i, c_i64, c_i, c_i, c_i, c_i, c_i,
                                       c_p]),
+    "lbbnn_vd_gemm_members": (c_i, [c_p, c_i, c_i64, c_p, c_p, c_i, c_p, c_p, c_u32, c_i64, c_u64, c_p, c_i, c_i64,
+                                    c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     "lbbnn_philox_std_gamma": (c_i, [c_p, c_u32, c_p, c_p, c_i64, c_p, c_p]),
     "lbbnn_gamma_grad": (c_i, [c_p, c_p, c_i64, c_p, c_p]),
     "lbbnn_elbo_loss": (c_i, [c_p, c_i, c_p, c_i, c_i, c_p, ctypes.c_float, c_p, c_p]),

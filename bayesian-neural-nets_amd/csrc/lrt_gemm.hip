@@ -62,6 +62,11 @@ struct GemmArgs {
     int members;
     long long x_ms, w_ms, o_ms, b_ms;
     unsigned long long m_adv, m_off;     // m_off: filled in by member_view()
+    // lbbnn_vd_gemm_members fan-out: fan > 0 => the grid has no member dimension (members = 1); every workgroup computes its
+    // tile's two products ONCE and its epilogue writes member m = 0 .. fan-1 to out + m*o_ms with the noise drawn at Philox
+    // offset rng[1] + m*m_adv (fan_store4) -- the first layer of a variational-dropout ensemble, whose input and weights are
+    // the same for every member.  0 = off.
+    int fan;
 };
 
 __device__ __forceinline__ GemmArgs member_view(const GemmArgs& in) {
@@ -155,6 +160,19 @@ __device__ __forceinline__ void store4_rows(float* p, bool vec, int o, int O, co
     }
 }
 
+// Fan-out epilogue of out[b][o..o+3] for member m (GemmArgs::fan): epilogue4 at Philox offset rng[1] + m*m_adv, stored to
+// member m's output.  Every fan-out kernel's epilogue goes through here, so member m's values are, bit for bit, the ones the
+// same kernel writes in a single launch at that offset (same accumulators, same epilogue4).  No explicit eps, std_out or
+// combine operands in this mode.
+__device__ __forceinline__ void fan_store4(const GemmArgs& a, const EpiCtx& ec, const OConst& oc, int m, int b, int o,
+                                           const floatx4& am, const floatx4& av) {
+    EpiCtx em = ec;
+    em.offs = ec.offs + (unsigned long long)m * a.m_adv;
+    float res[4], sd[4];
+    epilogue4<false>(a, em, oc, b, o, am, av, nullptr, nullptr, nullptr, res, sd);
+    store4_rows(a.out + (size_t)m * a.o_ms + (size_t)b * a.ldo + o, ec.ovec, o, a.O, res);
+}
+
 // Epilogue of a wave's TO x TB accumulator tiles (lane: out[b][o .. o+3] of tile (i, j), o = o0 + 16 i + 4 q,
 // b = brow0 + 16 j).  Two phases.  (1) EVERY load the epilogue needs -- the per-feature constants of the TO o-tiles, the
 // explicit eps or the combine operands where the call has them -- is issued back to back, before the first store.  (2)
@@ -162,15 +180,33 @@ __device__ __forceinline__ void store4_rows(float* p, bool vec, int o, int O, co
 // loop: `s_waitcnt vmcnt(0)` before their use also waited for the previous o-tile's STORES (vmcnt counts stores), five
 // dependent round trips per workgroup at the point of the launch where nothing else is left to overlap them
 // (tools/gemm_ksweep.py: 16.4 us of a launch did not depend on K).
-template <int TO, int TB, bool MEAN_ONLY>
+// FAN: the fan-out form (GemmArgs::fan): the same constants, then every member's tiles, member-outermost.
+template <int TO, int TB, bool MEAN_ONLY, bool FAN = false>
 __device__ __forceinline__ void epilogue_tile(const GemmArgs& a, int o0, int q, int brow0,
                                               const floatx4 (&accm)[TO][TB], const floatx4 (&accv)[TO][TB]) {
+    static_assert(!FAN || !MEAN_ONLY, "fan-out draws noise");
     EpiCtx ec = make_epi_ctx<MEAN_ONLY>(a);
     OConst oc[TO];
 #pragma unroll
     for (int i = 0; i < TO; ++i) {
         const int o = o0 + i * 16 + 4 * q;
         if (o < a.O) oc[i] = load_oconst(a, o);
+    }
+    if (FAN) {
+        __builtin_amdgcn_sched_barrier(0);
+        for (int m = 0; m < a.fan; ++m) {
+#pragma unroll
+            for (int i = 0; i < TO; ++i) {
+                const int o = o0 + i * 16 + 4 * q;
+                if (o >= a.O) continue;
+#pragma unroll
+                for (int j = 0; j < TB; ++j) {
+                    const int b = brow0 + j * 16;
+                    if (b < a.B) fan_store4(a, ec, oc[i], m, b, o, accm[i][j], accv[i][j]);
+                }
+            }
+        }
+        return;
     }
     const bool pre_eps = !MEAN_ONLY && a.eps != nullptr;
     const bool pre_comb = MEAN_ONLY && a.comb_x != nullptr;
@@ -217,7 +253,7 @@ __device__ __forceinline__ void epilogue_tile(const GemmArgs& a, int o0, int q, 
 // to the last valid row -- their accumulators are never stored) and advance by 16 floats per chunk.
 // Only a K tail (I % 16 != 0) takes the guarded path, and only for the x rows (the weight operands
 // are zero-padded to ld by the weight pass).
-template <int TO, int TB, int WB, bool MEAN_ONLY, bool XVEC>
+template <int TO, int TB, int WB, bool MEAN_ONLY, bool XVEC, bool FAN = false>
 __global__ __launch_bounds__(WB * 64, 2) void lrt_gemm_f32_kernel(const GemmArgs a_in) {
     const GemmArgs a = member_view(a_in);
     constexpr int NT = WB * 64;
@@ -366,7 +402,7 @@ __global__ __launch_bounds__(WB * 64, 2) void lrt_gemm_f32_kernel(const GemmArgs
     }
 
     // ---- epilogue: lane holds out[b][o .. o+3] for each (i, j) tile
-    epilogue_tile<TO, TB, MEAN_ONLY>(a, o0, q, b0 + wv * TB * 16 + lr, accm, accv);
+    epilogue_tile<TO, TB, MEAN_ONLY, FAN>(a, o0, q, b0 + wv * TB * 16 + lr, accm, accv);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -388,7 +424,7 @@ constexpr int DROW = 16;                     // floats per LDS row in the DMA im
 
 __device__ __forceinline__ int swz(int rowgrp) { return (0x78 >> (2 * (rowgrp & 3))) & 3; }   // F = {0,2,3,1}
 
-template <int TO, int TB, int WB, bool MEAN_ONLY>
+template <int TO, int TB, int WB, bool MEAN_ONLY, bool FAN = false>
 __global__ __launch_bounds__(WB * 64, 2) void lrt_gemm_f32_dma_kernel(const GemmArgs a_in) {
     const GemmArgs a = member_view(a_in);
     constexpr int BN = TO * 16, BM = TB * WB * 16;
@@ -504,7 +540,7 @@ __global__ __launch_bounds__(WB * 64, 2) void lrt_gemm_f32_dma_kernel(const Gemm
     }
 
     // ---- epilogue (identical to the register-staged kernel)
-    epilogue_tile<TO, TB, MEAN_ONLY>(a, o0, q, b0 + wv * TB * 16 + lr, accm, accv);
+    epilogue_tile<TO, TB, MEAN_ONLY, FAN>(a, o0, q, b0 + wv * TB * 16 + lr, accm, accv);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -544,7 +580,7 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 // (the body is a __device__ function: with the LDS-DMA builtin fed from an array element directly inside a __global__ template,
 // hipcc 7.2's host pass silently drops the kernel's host stub -- undefined symbol at load time)
-template <int TO, int TB, int WB, bool MEAN_ONLY, int NP, bool F16>
+template <int TO, int TB, int WB, bool MEAN_ONLY, int NP, bool F16, bool FAN>
 __device__ __forceinline__ void lrt_gemm_bf16x3_body(const GemmArgs& a_in) {
     static_assert(!F16 || NP == 1, "fp16 operands exist in the single-product form only");
     const GemmArgs a = member_view(a_in);
@@ -749,11 +785,11 @@ __device__ __forceinline__ void lrt_gemm_bf16x3_body(const GemmArgs& a_in) {
 
     GemmArgs ao = a;                                     // split-K: partial product z goes to its own output slab
     if (a.kchunk) ao.out = a.out + (size_t)blockIdx.z * a.split_stride;
-    epilogue_tile<TO, TB, MEAN_ONLY>(ao, o0, q, b0 + wv * TB * 16 + lr, accm, accv);
+    epilogue_tile<TO, TB, MEAN_ONLY, FAN>(ao, o0, q, b0 + wv * TB * 16 + lr, accm, accv);
 }
-template <int TO, int TB, int WB, bool MEAN_ONLY, int NP = 3, bool F16 = false>
+template <int TO, int TB, int WB, bool MEAN_ONLY, int NP = 3, bool F16 = false, bool FAN = false>
 __global__ __launch_bounds__(WB * 64, (TB * TO > 10) ? 1 : (WB == 8 ? 4 : 2)) void lrt_gemm_bf16x3_kernel(const GemmArgs a_in) {
-    lrt_gemm_bf16x3_body<TO, TB, WB, MEAN_ONLY, NP, F16>(a_in);
+    lrt_gemm_bf16x3_body<TO, TB, WB, MEAN_ONLY, NP, F16, FAN>(a_in);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -773,8 +809,9 @@ __global__ __launch_bounds__(WB * 64, (TB * TO > 10) ? 1 : (WB == 8 ? 4 : 2)) vo
 constexpr int SK_WAVES = 16;
 constexpr int SK_NCH = 5;      // chunks per wave per batch: covers I <= 16*16*5 = 1280 in one batch
 
-template <bool MEAN_ONLY, bool XVEC>
+template <bool MEAN_ONLY, bool XVEC, bool FAN = false>
 __global__ __launch_bounds__(SK_WAVES * 64) void lrt_gemm_skinny_kernel(const GemmArgs a_in) {
+    static_assert(!FAN || !MEAN_ONLY, "fan-out draws noise");
     const GemmArgs a = member_view(a_in);
     __shared__ __attribute__((aligned(16))) float red[SK_WAVES][2][64][4];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -853,6 +890,11 @@ __global__ __launch_bounds__(SK_WAVES * 64) void lrt_gemm_skinny_kernel(const Ge
         sm += *reinterpret_cast<const floatx4*>(&red[w][0][lane][0]);
         if (!MEAN_ONLY) sv += *reinterpret_cast<const floatx4*>(&red[w][1][lane][0]);
     }
+    if (FAN) {                                           // (no log_softmax in the fan-out form)
+        if (live)
+            for (int m = 0; m < a.fan; ++m) fan_store4(a, ec, oc, m, b, o, sm, sv);
+        return;
+    }
     float res[4] = {0.f, 0.f, 0.f, 0.f}, sd[4] = {0.f, 0.f, 0.f, 0.f};
     if (live) epilogue4<MEAN_ONLY>(a, ec, oc, b, o, sm, sv, pa, pa, pb, res, sd);
     if (a.log_softmax) {
@@ -879,7 +921,8 @@ __global__ __launch_bounds__(SK_WAVES * 64) void lrt_gemm_skinny_kernel(const Ge
 
 // *hosted (if non-NULL, and a.fin.n > 0): set to true when the launch carries the finalize row; otherwise the caller
 // runs the finalize as a launch of its own
-template <int TO, int TB, int WB>
+// FAN: the fan-out kernels (GemmArgs::fan; never mean-only, no finalize): same tile, same grid, same kernel choice
+template <int TO, int TB, int WB, bool FAN = false>
 int launch_cfg(GemmArgs& a, bool mean_only, bool xvec, hipStream_t s, bool* hosted) {
     constexpr int BN = TO * 16, BM = TB * WB * 16;
     dim3 grid((a.O + BN - 1) / BN, (a.B + BM - 1) / BM, a.members > 1 ? a.members : 1);
@@ -896,11 +939,16 @@ int launch_cfg(GemmArgs& a, bool mean_only, bool xvec, hipStream_t s, bool* host
             if (piggy_lds_bytes(a.fin) <= (mean_only ? l_mean : l_full)) { grid.y += 1; *hosted = true; }
             else a.fin.n = 0;
         }
+        if constexpr (FAN) return launch_one(lrt_gemm_f32_dma_kernel<TO, TB, WB, false, true>, grid, block, l_full, s, a);
         if (mean_only) return launch_one(lrt_gemm_f32_dma_kernel<TO, TB, WB, true>, grid, block, l_mean, s, a);
         return launch_one(lrt_gemm_f32_dma_kernel<TO, TB, WB, false>, grid, block, l_full, s, a);
     }
     const size_t lds_full = lds_request(2u * (BM + 2 * BN) * LDS_LD * sizeof(float), nblocks);
     const size_t lds_mean = lds_request(2u * (BM + BN) * LDS_LD * sizeof(float), nblocks);
+    if constexpr (FAN) {
+        if (xvec) return launch_one(lrt_gemm_f32_kernel<TO, TB, WB, false, true, true>, grid, block, lds_full, s, a);
+        return launch_one(lrt_gemm_f32_kernel<TO, TB, WB, false, false, true>, grid, block, lds_full, s, a);
+    }
     if (mean_only) {
         if (xvec) return launch_one(lrt_gemm_f32_kernel<TO, TB, WB, true, true>, grid, block, lds_mean, s, a);
         return launch_one(lrt_gemm_f32_kernel<TO, TB, WB, true, false>, grid, block, lds_mean, s, a);
@@ -909,7 +957,7 @@ int launch_cfg(GemmArgs& a, bool mean_only, bool xvec, hipStream_t s, bool* host
     return launch_one(lrt_gemm_f32_kernel<TO, TB, WB, false, false>, grid, block, lds_full, s, a);
 }
 
-template <int TO, int TB, int WB>
+template <int TO, int TB, int WB, bool FAN = false>
 int launch_split_cfg(GemmArgs& a, bool mean_only, hipStream_t s, bool* hosted) {
     constexpr int BN = TO * 16, BM = TB * WB * 16;
     dim3 grid((a.O + BN - 1) / BN, (a.B + BM - 1) / BM,
@@ -925,19 +973,25 @@ int launch_split_cfg(GemmArgs& a, bool mean_only, hipStream_t s, bool* hosted) {
         if (piggy_lds_bytes(a.fin) <= (mean_only ? l_mean : l_full)) { grid.y += 1; *hosted = true; }
         else a.fin.n = 0;
     }
+    if constexpr (FAN) {
+        if (a.single16 == 2) return launch_one(lrt_gemm_bf16x3_kernel<TO, TB, WB, false, 1, true, true>, grid, block, l_full, s, a);
+        if (a.single16) return launch_one(lrt_gemm_bf16x3_kernel<TO, TB, WB, false, 1, false, true>, grid, block, l_full, s, a);
+        return launch_one(lrt_gemm_bf16x3_kernel<TO, TB, WB, false, 3, false, true>, grid, block, l_full, s, a);
+    }
     if (a.single16 == 2 && !mean_only) return launch_one(lrt_gemm_bf16x3_kernel<TO, TB, WB, false, 1, true>, grid, block, l_full, s, a);
     if (a.single16 && !mean_only) return launch_one(lrt_gemm_bf16x3_kernel<TO, TB, WB, false, 1>, grid, block, l_full, s, a);
     if (mean_only) return launch_one(lrt_gemm_bf16x3_kernel<TO, TB, WB, true>, grid, block, l_mean, s, a);
     return launch_one(lrt_gemm_bf16x3_kernel<TO, TB, WB, false>, grid, block, l_full, s, a);
 }
 
+template <bool FAN = false>
 int launch_split(GemmArgs& a, bool mean_only, hipStream_t s, bool* hosted) {
     // 128x80 tile, 2 workgroups/CU, 2 LDS stages.  Variants measured and dropped: 256x80 3-stage ring
     // (one workgroup/CU), 128x160 with 4 or 8 waves, x split once per tile through LDS, x delivered pre-split.
     const long nz = a.kchunk ? (a.I + a.kchunk - 1) / a.kchunk : 1;
     const long blocks_big = (long)((a.O + 79) / 80) * ((a.B + 127) / 128) * nz;
-    if (blocks_big >= 256 && a.B >= 96) return launch_split_cfg<5, 2, 4>(a, mean_only, s, hosted);
-    return launch_split_cfg<5, 1, 2>(a, mean_only, s, hosted);
+    if (blocks_big >= 256 && a.B >= 96) return launch_split_cfg<5, 2, 4, FAN>(a, mean_only, s, hosted);
+    return launch_split_cfg<5, 1, 2, FAN>(a, mean_only, s, hosted);
 }
 
 }  // namespace
@@ -949,7 +1003,7 @@ static int lrt_gemm_impl(const float* x, int ldx, const void* e_w, const void* v
                          const FinalizePiggy* fin = nullptr, bool* hosted = nullptr,
                          const float* comb_x = nullptr, int ld_cx = 0, const float* comb_add = nullptr, int ld_ca = 0,
                          int members = 1, long long x_ms = 0, long long w_ms = 0, long long o_ms = 0,
-                         unsigned long long m_adv = 0, long long b_ms = 0) {
+                         unsigned long long m_adv = 0, long long b_ms = 0, int fan = 0) {
     if (B == 0 && I > 0 && O > 0) return 0;        // empty batch (torch.mm of 0 rows, LBBNN-GP-MF-LRT.py:172): nothing to do
     if (!x || !e_w || !out) return LBBNN_E_NULL;
     if (B <= 0 || I <= 0 || O <= 0 || ldx < I || ldo < O) return LBBNN_E_SHAPE;
@@ -977,7 +1031,9 @@ static int lrt_gemm_impl(const float* x, int ldx, const void* e_w, const void* v
     a.comb_x = comb_x; a.comb_add = comb_add; a.ld_cx = ld_cx; a.ld_ca = ld_ca;
     a.single16 = (flags & LBBNN_F_HALF16) ? 2 : ((flags & LBBNN_F_SINGLE16) ? 1 : 0);
     a.members = members; a.x_ms = x_ms; a.w_ms = w_ms; a.o_ms = o_ms; a.b_ms = b_ms; a.m_adv = m_adv; a.m_off = 0;
+    a.fan = fan;
     if (members > 1 && (kchunk || fin || eps || std_out || comb_x)) return LBBNN_E_FLAGS;
+    if (fan && (members != 1 || mean_only || kchunk || fin || eps || std_out || comb_x || a.log_softmax)) return LBBNN_E_FLAGS;
 
     const bool xvec = ((I & 3) == 0) && ((ldx & 3) == 0) && ((reinterpret_cast<uintptr_t>(x) & 15u) == 0);
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -990,12 +1046,15 @@ static int lrt_gemm_impl(const float* x, int ldx, const void* e_w, const void* v
         if (!xvec || (I & 7) || O <= 16 || (tail && (ld - I) < 8)) return LBBNN_E_ALIGN;
         // the split kernel addresses x and the operands through 32-bit buffer offsets
         if (((size_t)(B - 1) * ldx + I) * 4 >= 0x7FFFFFF0u || (size_t)O * ld * 4 >= 0x7FFFFFF0u) return LBBNN_E_SHAPE;
-        return launch_split(a, mean_only, s, hosted);
+        return fan ? launch_split<true>(a, mean_only, s, hosted) : launch_split(a, mean_only, s, hosted);
     }
     if (O <= 16) {
         a.fin.n = 0;
         dim3 grid((B + 15) / 16, 1, a.members > 1 ? a.members : 1), block(SK_WAVES * 64);
-        if (mean_only) {
+        if (fan) {
+            if (xvec) hipLaunchKernelGGL((lrt_gemm_skinny_kernel<false, true, true>), grid, block, 0, s, a);
+            else      hipLaunchKernelGGL((lrt_gemm_skinny_kernel<false, false, true>), grid, block, 0, s, a);
+        } else if (mean_only) {
             if (xvec) hipLaunchKernelGGL((lrt_gemm_skinny_kernel<true, true>), grid, block, 0, s, a);
             else      hipLaunchKernelGGL((lrt_gemm_skinny_kernel<true, false>), grid, block, 0, s, a);
         } else {
@@ -1005,6 +1064,10 @@ static int lrt_gemm_impl(const float* x, int ldx, const void* e_w, const void* v
         return (int)hipGetLastError();
     }
     const long blocks_big = (long)((O + 79) / 80) * ((B + 127) / 128);
+    if (fan) {
+        if (blocks_big >= 256) return launch_cfg<5, 2, 4, true>(a, mean_only, xvec, s, hosted);
+        return launch_cfg<5, 1, 2, true>(a, mean_only, xvec, s, hosted);
+    }
     if (blocks_big >= 256) return launch_cfg<5, 2, 4>(a, mean_only, xvec, s, hosted);
     return launch_cfg<5, 1, 2>(a, mean_only, xvec, s, hosted);
 }
@@ -1094,6 +1157,29 @@ extern "C" int lbbnn_lrt_gemm_members(const float* x, int ldx, int64_t x_mstride
     return lrt_gemm_impl(x, ldx, e_w, var_w, ld, bias_mean, bias_var, nullptr, nullptr, rng, rng_stream, row_offset, out, ldo,
                          nullptr, B, I, O, flags, stream, 0, nullptr, nullptr, nullptr, 0, nullptr, 0, members,
                          (long long)x_mstride, (long long)w_mstride, (long long)o_mstride, member_advance);
+}
+
+// Variational dropout's dual-moment GEMM for every member of an ensemble in ONE launch (include/lbbnn.h): shared weight
+// operands, var_scale = alpha, no bias.  fanout = 0: gridDim.z = members, member m reads x + m*x_mstride (member_view).
+// fanout = 1: one grid, each workgroup computes its tile's two products once and writes every member (GemmArgs::fan).  The tile
+// configuration depends on (B, I, O, flags) only, so member m takes the kernel and summation order of its own lbbnn_lrt_gemm.
+extern "C" int lbbnn_vd_gemm_members(const float* x, int ldx, int64_t x_mstride, const void* e_w, const void* var_w, int ld,
+                                     const float* var_scale, const uint64_t* rng, uint32_t rng_stream, int64_t row_offset,
+                                     uint64_t member_advance, float* out, int ldo, int64_t o_mstride,
+                                     int B, int I, int O, int flags, int members, int fanout, void* stream) {
+    if (members < 1 || members > 65535) return LBBNN_E_SHAPE;
+    if (fanout != 0 && fanout != 1) return LBBNN_E_SHAPE;
+    if (fanout && x_mstride != 0) return LBBNN_E_SHAPE;
+    if (x_mstride < 0 || o_mstride < 0 || o_mstride < (int64_t)B * ldo) return LBBNN_E_SHAPE;
+    if ((x_mstride & 3) || (o_mstride & 3)) return LBBNN_E_ALIGN;                         // every member 16-B aligned
+    if (flags & ~(LBBNN_F_RELU | LBBNN_F_SPLIT16 | LBBNN_F_SINGLE16 | LBBNN_F_HALF16)) return LBBNN_E_FLAGS;
+    if (!rng) return LBBNN_E_NOISE;
+    if (flags & LBBNN_F_SPLIT16)                                                           // 32-bit buffer offsets
+        if (((size_t)(B - 1) * ldx + I) * 4 >= 0x7FFFFFF0u) return LBBNN_E_SHAPE;
+    return lrt_gemm_impl(x, ldx, e_w, var_w, ld, nullptr, nullptr, var_scale, nullptr, rng, rng_stream, row_offset, out, ldo,
+                         nullptr, B, I, O, flags, stream, 0, nullptr, nullptr, nullptr, 0, nullptr, 0,
+                         fanout ? 1 : members, (long long)x_mstride, 0ll, (long long)o_mstride, member_advance, 0ll,
+                         fanout ? members : 0);
 }
 
 // The mean-only product of every member of an ensemble in ONE launch, each member with its own weights and bias

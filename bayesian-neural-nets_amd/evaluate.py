@@ -13,6 +13,11 @@ one lbbnn_gate_members launch draws every member's gates, weights and biases (th
 member m at Philox offset live + m), then one mean-only GEMM launch per layer runs all members.  ``gates="mpm"`` selects the
 median probability model of ``outofsample(medimod=True)``.  ``predictive_entropy`` is the ``outofsample`` entropy of every
 family.
+
+Variational-dropout networks (``vd.BNN``, variational_dropout.py:154-160) take ``vd_ensemble``: theta is shared by every
+member, so each layer's operands are formed once, the first layer's two products (same input, same weights for every member)
+are computed once and fanned out to all members in its epilogue, and every later layer runs all members in one launch
+(lbbnn_vd_gemm_members).  Member m is bitwise the m-th of ``samples`` consecutive ``net(data)`` calls.
 """
 from typing import Dict, Optional
 
@@ -105,6 +110,76 @@ def ensemble_forward_batched(net, data: torch.Tensor, samples: int = 10) -> torc
     return h
 
 
+def _is_vd(net) -> bool:
+    from . import vd
+    return isinstance(net, vd.BNN)
+
+
+def _vd_check(net, data, samples, max_members):
+    if not _is_vd(net):
+        raise ValueError("bnn_amd: vd_ensemble takes a variational-dropout network (bnn_amd.vd.BNN)")
+    S = int(samples)
+    if S < 1:
+        raise ValueError("bnn_amd: samples must be >= 1")
+    chunk = S if max_members is None else int(max_members)
+    if chunk < 1:
+        raise ValueError("bnn_amd: max_members must be >= 1")
+    return S, chunk
+
+
+@torch.no_grad()
+def vd_ensemble(net, data: torch.Tensor, samples: int = 10, *, max_members: Optional[int] = None) -> torch.Tensor:
+    """(samples, B, classes) log-probabilities of ``samples`` forwards of a variational-dropout network
+    (variational_dropout.py:154-160: ``all_predictions[x] = model(images)``), bitwise the loop of ``samples`` consecutive
+    ``net(data)`` calls, in chunks of at most ``max_members`` members (default: all; chunked and unchunked results are the same
+    bits).  Per chunk: one lbbnn_vd_operands per layer (theta is shared), the first layer ONCE with its epilogue writing every
+    member (fan-out), each later layer one launch for all members, and the log_softmax of ``BNN.forward``.  A single forward
+    advances the live Philox offset by 1 after each of its L layers, so member m's layer i draws at offset live + L*m + i here
+    too (member_advance = L); the live offset ends at live + L*samples.  Per layer the kernel (split or not, SINGLE16,
+    HALF16) is the one ``BayesianLayer._forward_hip`` picks for that member's input.  Injected noise (``layer.noise``) is
+    not supported here (ValueError): the loop form of ``ensemble_forward(batched=False)`` takes it."""
+    S, chunk = _vd_check(net, data, samples, max_members)
+    layers = net._layers()
+    if any(l.noise for l in layers):
+        raise ValueError("bnn_amd: vd_ensemble draws in-kernel noise; a layer has injected noise (use batched=False)")
+    if not data.is_cuda:
+        raise RuntimeError("bnn_amd: ensemble evaluation needs a HIP device tensor (data is on %s); there is no CPU path"
+                           % data.device)
+    net.eval()
+    L = len(layers)
+    x = data.view(-1, net.dims[0]).float()                    # as BNN.forward / BayesianLayer.forward
+    B, C, dev = x.shape[0], net.dims[-1], x.device
+    st = ops.RngState.get(dev)
+    f = dict(dtype=torch.float32, device=dev)
+    pad = lambda n: -(-n // 4) * 4                             # member strides padded to 16 B
+    head = torch.empty((S, pad(B * C)), **f)
+    outputs = head[:, :B * C].view(S, B, C)
+    if B == 0:
+        st.advance(L * S)
+        return torch.log_softmax(outputs, dim=-1)
+    single = ops.get_precision() in ("bf16", "fp16")          # as ops.lrt_gemm reads it
+    for m0 in range(0, S, chunk):
+        c = min(chunk, S - m0)
+        h = x
+        for i, l in enumerate(layers):
+            # the kernel choice of the loop: _forward_hip decides on member 0's input rows, and every member's rows have the
+            # same stride and 16-B alignment (the padded member stride)
+            split, half = l._arith(h if i == 0 else h[0])
+            if i == 0 and (x.stride(1) != 1 or x.stride(0) < l.n):
+                h = x.contiguous()                            # (what ops.lrt_gemm does with such rows, after the choice)
+            e_w, var_w = l._operands(split, half)
+            last = i == L - 1
+            out = outputs[m0:m0 + c] if last else torch.empty((c, pad(B * l.m)), **f)[:, :B * l.m].view(c, B, l.m)
+            ops.vd_gemm_members(h, e_w, var_w, l.alpha, st.t, I=l.n, O=l.m, members=c, fanout=i == 0,
+                                rng_stream=ops.STREAM_EPS_OUT * 64 + l._layer_id, row_offset=l.row_offset,
+                                member_advance=L, relu=not last, split=split, single=split and single, half=half, out=out)
+            st.advance(1)                                     # layer i + 1 draws at the next offset, as in the loop
+            h = out
+        if c > 1:
+            st.advance(L * (c - 1))                           # the other members' offsets
+    return torch.log_softmax(outputs, dim=-1)
+
+
 def _is_base(net) -> bool:
     from . import base
     return isinstance(net, base.BayesianNetwork)
@@ -159,9 +234,21 @@ def ensemble_forward(net, data: torch.Tensor, samples: int = 10, batched=None, *
     ``batched``: None = the one-launch-per-kernel form when the network qualifies (``_batched_ok``; a baseline network on a
     HIP device: ``base_ensemble``), else the loop of fused single forwards (``net.sample_predict`` for a baseline network);
     True / False force one of them.  Either form advances the live Philox offset by ``samples``.
-    ``gates`` ("sample" or "mpm") and ``max_members`` (members per launch of the batched form) apply to baseline networks
-    only."""
+    ``gates`` ("sample" or "mpm") applies to baseline networks only, ``max_members`` (members per launch of the batched form)
+    to baseline and variational-dropout networks.  A variational-dropout network (``vd.BNN``): None = ``vd_ensemble`` on a
+    HIP device when no layer has injected noise, else the loop of ``net(data)``; True with injected noise raises ValueError."""
     net.eval()
+    if _is_vd(net):
+        if gates != "sample":
+            raise ValueError("bnn_amd: gates=%r (the median probability model) exists for baseline LBBNN networks only"
+                             % (gates,))
+        _vd_check(net, data, samples, max_members)
+        noisy = any(l.noise for l in net._layers())
+        if batched is None:
+            batched = data.is_cuda and not noisy
+        if batched:
+            return vd_ensemble(net, data, samples, max_members=max_members)
+        return torch.stack([net(data) for _ in range(int(samples))])
     if _is_base(net):
         if gates not in ("sample", "mpm"):
             raise ValueError("bnn_amd: gates must be 'sample' or 'mpm', got %r" % (gates,))
@@ -185,11 +272,14 @@ def ensemble_forward(net, data: torch.Tensor, samples: int = 10, batched=None, *
 @torch.no_grad()
 def ensemble_eval(net, data: torch.Tensor, target: Optional[torch.Tensor] = None, samples: int = 10) -> Dict[str, object]:
     """test_ensemble's numbers for one batch: ``outputs``, ``pred_ensemble``, ``pred_posterior_mean``, ``density`` (and
-    ``correct_*`` with a target).  Baseline networks: ``density[s]`` is the mean gate of member s over all weights -- the gates
+    ``correct_*`` with a target).  Variational-dropout networks: ``outputs``, ``pred_ensemble``, and ``loss`` and
+    ``correct_ensemble`` with a target (``_vd_ensemble_eval``).  Baseline networks: ``density[s]`` is the mean gate of member s over all weights -- the gates
     the member actually used (the reference draws a separate set, LBBNN-GP-MF.py:390-394) -- and the posterior mean is the
     mode-2 forward (weight = alpha * mu) with alpha = sigmoid(lambdal) set as the reference sets it (:369-374, :413)."""
     if _is_base(net):
         return _base_ensemble_eval(net, data, target, samples)
+    if _is_vd(net):
+        return _vd_ensemble_eval(net, data, target, samples)
     outputs = ensemble_forward(net, data, samples)
     density = []
     for _ in range(samples):
@@ -202,6 +292,22 @@ def ensemble_eval(net, data: torch.Tensor, target: Optional[torch.Tensor] = None
     if target is not None:
         res["correct_ensemble"] = int(pred_ens.eq(target).sum())
         res["correct_posterior_mean"] = int(pred_mean.eq(target).sum())
+    return res
+
+
+def _vd_ensemble_eval(net, data, target, samples):
+    """Variational dropout's validation numbers (variational_dropout.py:154-174): ``outputs``, ``pred_ensemble`` = argmax of
+    ``outputs.mean(0)`` and, with a target, ``loss`` = ``vd.loss_fn(outputs.mean(0), target, net)`` and ``correct_ensemble``.
+    No ``pred_posterior_mean`` or ``density``: the reference's VD script computes neither."""
+    from . import vd
+    outputs = ensemble_forward(net, data, samples)
+    mean = outputs.mean(0)
+    pred_ens = mean.argmax(1)
+    res = {"outputs": outputs, "pred_ensemble": pred_ens}
+    if target is not None:
+        res["loss"] = vd.loss_fn(mean, target, net)
+        net.eval()                                            # (loss_fn's `model.train()` call, :91)
+        res["correct_ensemble"] = int(pred_ens.eq(target).sum())
     return res
 
 

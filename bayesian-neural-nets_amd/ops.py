@@ -476,6 +476,39 @@ def lrt_gemm(x, e_w, var_w, *, I: int, O: int, bias_mean=None, bias_var=None, va
     return out
 
 
+def vd_gemm_members(x, e_w, var_w, var_scale, rng: torch.Tensor, *, I: int, O: int, members: int, fanout: bool = False,
+                    rng_stream: int = 0, row_offset: int = 0, member_advance: int = 1, relu: bool = False,
+                    split: bool = False, single: bool = False, half: bool = False, out: Optional[torch.Tensor] = None):
+    """lbbnn_vd_gemm_members: variational dropout's dual-moment GEMM (var_scale = alpha, no bias) for ``members`` members,
+    member m drawing its noise at Philox offset rng[1] + m * member_advance.  ``fanout``: x is the (B, I) input every member
+    shares, whose two products are computed once; else x is (members, B, I) with a member stride that is a multiple of 4.
+    ``out``: (members, B, O) with dense rows and a member stride that is a multiple of 4 (default: rows padded to 16 B per
+    member).  single / half: one bf16 / fp16 product per moment (with ``split``)."""
+    if fanout:
+        if x.dim() != 2 or x.shape[1] != I:
+            raise RuntimeError("bnn_amd: fan-out input must be (B,%d), got %s" % (I, tuple(x.shape)))
+        ldx, x_ms, B = x.stride(0), 0, x.shape[0]
+        xp = _ptr_rows(x, "input")
+    else:
+        if x.dim() != 3 or x.shape[0] != members or x.shape[2] != I:
+            raise RuntimeError("bnn_amd: input must be (%d,B,%d), got %s" % (members, I, tuple(x.shape)))
+        ldx, x_ms, B = x.stride(1), x.stride(0), x.shape[1]
+        xp = _ptr_rows(x[0], "input")
+    if out is None:
+        o_ms = -(-(B * O) // 4) * 4
+        out = torch.empty((members, o_ms), dtype=torch.float32, device=x.device)[:, :B * O].view(members, B, O)
+    if tuple(out.shape) != (members, B, O) or out.stride(2) != 1:
+        raise RuntimeError("bnn_amd: out must be (%d,%d,%d) with dense rows" % (members, B, O))
+    flags = ((F_RELU if relu else 0) | (F_SPLIT16 if split else 0) | (F_SINGLE16 if (split and single) else 0)
+             | (F_HALF16 if (split and half) else 0))
+    rc = _lib.lib().lbbnn_vd_gemm_members(
+        xp, ldx, x_ms, _ptr(e_w), _ptr(var_w), operand_ld(I), _ptr(var_scale, "var_scale"), _ptr(rng, "rng"), rng_stream,
+        row_offset, member_advance, _ptr_rows(out[0], "out"), out.stride(1), out.stride(0), B, I, O, flags, members,
+        1 if fanout else 0, _stream())
+    _lib.check(rc, "lbbnn_vd_gemm_members")
+    return out
+
+
 def plane_ld(n: int) -> int:
     return operand_ld(n)
 

@@ -84,20 +84,31 @@ class BayesianLayer(nn.Module):
         self._layer_id = next(_ids) % 64
         self._ws = None
 
-    def _forward_hip(self, x, relu=False, save_rng=False, std_out=None):
-        dev = x.device
+    def _arith(self, x):
+        """(split, half) of the GEMM for input rows ``x``: the bf16 hi | lo kernels when a 16-bit precision is set and the
+        shape and the rows allow them; ``half``: one fp16 product per moment (BASELINE configs[4]: "fp16 MFMA")."""
+        split = (ops.split_precision() and ops.split_eligible(self.n, self.m)
+                 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0)
+        return split, split and ops.get_precision() == "fp16"
+
+    def _operands(self, split, half):
+        """lbbnn_vd_operands into the layer's workspace: the GEMM operands (e_w, var_w) of theta and theta^2."""
+        dev = self.theta.device
         ld = ops.operand_ld(self.n)
         if self._ws is None or self._ws[0].device != dev:
             self._ws = (torch.empty((self.m, ld), dtype=torch.float32, device=dev),
                         torch.empty((self.m, ld), dtype=torch.float32, device=dev))
         e_w, var_w = self._ws
-        split = (ops.split_precision() and ops.split_eligible(self.n, self.m)
-                 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0)
-        half = split and ops.get_precision() == "fp16"          # one fp16 product per moment (BASELINE configs[4]: "fp16 MFMA")
         _lib.check(_lib.lib().lbbnn_vd_operands(ops._ptr(self.theta.detach(), "theta"), e_w.data_ptr(), var_w.data_ptr(),
                                                 ld, self.n, self.m,
                                                 (ops.F_SPLIT16 if split else 0) | (ops.F_HALF16 if half else 0), ops._stream()),
                    "lbbnn_vd_operands")
+        return e_w, var_w
+
+    def _forward_hip(self, x, relu=False, save_rng=False, std_out=None):
+        dev = x.device
+        split, half = self._arith(x)
+        e_w, var_w = self._operands(split, half)
         zeta = (self.noise or {}).get("zeta")
         rng, st = None, None
         if zeta is None:
@@ -120,25 +131,34 @@ class BayesianLayer(nn.Module):
         return self._forward_hip(x)[0]
 
 
+MAX_LAYERS = 16          # layer i draws from Philox stream id 48 + i, and stream ids stay below 64
+
+
 class BNN(nn.Module):
-    """variational_dropout.py:72-86 (784-1200-1200-1200-10 there; ``dims=`` added)."""
+    """variational_dropout.py:72-86 (784-1200-1200-1200-10 there; ``dims=`` added).  Any depth from 1 to 16 layers
+    (``len(dims)`` 2 .. 17): layers ``l1 .. lN``, ReLU between them, log_softmax after the last."""
 
     def __init__(self, dims=(28 * 28, 1200, 1200, 1200, 10)):
         super().__init__()
-        self.dims = tuple(dims)
-        self.l1 = BayesianLayer(dims[0], dims[1])
-        self.l2 = BayesianLayer(dims[1], dims[2])
-        self.l3 = BayesianLayer(dims[2], dims[3])
-        self.l4 = BayesianLayer(dims[3], dims[4])
-        for i, l in enumerate((self.l1, self.l2, self.l3, self.l4)):
+        dims = tuple(int(d) for d in dims)
+        if not 2 <= len(dims) <= MAX_LAYERS + 1:
+            raise ValueError("bnn_amd: vd.BNN takes 1 to %d layers (len(dims) 2 to %d), got dims=%s"
+                             % (MAX_LAYERS, MAX_LAYERS + 1, dims))
+        self.dims = dims
+        for i in range(len(dims) - 1):
+            setattr(self, "l%d" % (i + 1), BayesianLayer(dims[i], dims[i + 1]))
+        for i, l in enumerate(self._layers()):
             l._layer_id = 48 + i              # per-network Philox stream ids (not the process-wide counter)
+
+    def _layers(self):
+        return [getattr(self, "l%d" % (i + 1)) for i in range(len(self.dims) - 1)]
 
     def forward(self, x):
         x = x.view(-1, self.dims[0])
-        x = F.relu(self.l1(x))
-        x = F.relu(self.l2(x))
-        x = F.relu(self.l3(x))
-        return F.log_softmax(self.l4(x), dim=1)
+        layers = self._layers()
+        for l in layers[:-1]:
+            x = F.relu(l(x))
+        return F.log_softmax(layers[-1](x), dim=1)
 
 
 NUM_BATCHES = 600.0      # len(train_loader.dataset) / config['batch_size'] = 60000 / 100 (variational_dropout.py:90-95)

@@ -505,6 +505,26 @@ int lbbnn_gemm_members_mean(const float* x, int ldx, int64_t x_mstride, const vo
                             int B, int I, int O, int flags, int members, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Ensemble evaluation of variational dropout (variational_dropout.py:154-160: num_test_ensemble_samples forwards of one
+ * batch).  theta is shared by every member (no per-member weight draw), so one lbbnn_vd_operands per layer serves all members.
+ *
+ * lbbnn_vd_gemm_members: the dual-moment GEMM of lbbnn_lrt_gemm with var_scale (alpha) and no bias for `members` members:
+ *   out[m][b][o] = mean + sqrt(var * var_scale[o]) * eps_m (+ReLU), e_w / var_w shared (lbbnn_vd_operands), eps_m the in-kernel
+ *   draw at Philox offset rng[1] + m * member_advance (stream rng_stream, row row_offset + b, column group o/4).
+ *   fanout = 0: gridDim.z = members; member m reads x + m * x_mstride and writes out + m * o_mstride.
+ *   fanout = 1: x_mstride must be 0 (the same input for every member: the first layer); the grid has no member dimension --
+ *     each workgroup computes its tile's two products once and writes every member's out + m * o_mstride.
+ *   Either way member m is bitwise the single lbbnn_lrt_gemm(var_scale) call at offset rng[1] + m * member_advance: the kernel
+ *   and tile are the ones that call picks (fp32, LDS-DMA, bf16x3 with LBBNN_F_SPLIT16 [| LBBNN_F_SINGLE16 [| LBBNN_F_HALF16]],
+ *   or the O <= 16 kernel).  flags: LBBNN_F_RELU | LBBNN_F_SPLIT16 | LBBNN_F_SINGLE16 | LBBNN_F_HALF16, else LBBNN_E_FLAGS.
+ *   1 <= members <= 65535 and fanout in {0, 1} (LBBNN_E_SHAPE); strides >= 0, o_mstride >= B * ldo (LBBNN_E_SHAPE), x_mstride
+ *   and o_mstride multiples of 4 (LBBNN_E_ALIGN); rng required (LBBNN_E_NOISE).  The caller advances rng afterwards. */
+int lbbnn_vd_gemm_members(const float* x, int ldx, int64_t x_mstride, const void* e_w, const void* var_w, int ld,
+                          const float* var_scale, const uint64_t* rng, uint32_t rng_stream, int64_t row_offset,
+                          uint64_t member_advance, float* out, int ldo, int64_t o_mstride,
+                          int B, int I, int O, int flags, int members, int fanout, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K7  lbbnn_vd_operands -- Gaussian variational-dropout layer (variational_dropout.py:55-68).
  *   phi = x.theta ; delta = (x^2).(theta^2) * alpha ; out = phi + sqrt(delta)*zeta        :64-67
  * theta is (I,O) row-major (NN layout).  This pass writes the GEMM operands theta^T and (theta^2)^T as
