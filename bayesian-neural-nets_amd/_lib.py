@@ -156,6 +156,15 @@ class GateMemberDesc(ctypes.Structure):
                [(n, c_i) for n in ("O", "I", "ld", "flags", "exact")] + [("layer_id", c_u32)]
 
 
+class FrozenDesc(ctypes.Structure):
+    """lbbnn_frozen_desc_t"""
+    _fields_ = [(n, c_p) for n in ("weight_mu", "weight_rho", "lambdal", "bias_rho", "q0_mean", "q0_log_var")] + \
+               [("z_flow", PlanarFlow)] + \
+               [(n, c_p) for n in ("e0", "e_w", "var_w", "bias_var", "kept_rows", "z_fwd", "e_w_members")] + \
+               [("z_mstride", c_i64)] + [(n, c_i) for n in ("O", "I", "ld", "flags", "mode")] + \
+               [("cut", ctypes.c_float), ("layer_id", c_u32)]
+
+
 class OutGradArgs(ctypes.Structure):
     """lbbnn_outgrad_args_t"""
     _fields_ = [(n, c_p) for n in ("g_out", "out", "std", "eps", "rng", "gm", "gv", "gmT", "gvT", "g_sum", "gv_sum", "work")] + \
@@ -294,6 +303,8 @@ SIGNATURES = {
     "lbbnn_elbo_loss_backward_logits": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, ctypes.c_float, c_p, c_p, c_p, c_p]),
     "lbbnn_log_softmax_backward": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_p]),
     "lbbnn_log_softmax_rows": (c_i, [c_p, c_i, c_p, c_i, c_i, c_i, c_p]),
+    "lbbnn_frozen_operands": (c_i, [ctypes.POINTER(FrozenDesc), c_i, c_p]),
+    "lbbnn_frozen_members": (c_i, [ctypes.POINTER(FrozenDesc), c_i, c_i, c_p, c_u64, c_p]),
 }
 
 _lib = None

@@ -18,10 +18,17 @@ Variational-dropout networks (``vd.BNN``, variational_dropout.py:154-160) take `
 member, so each layer's operands are formed once, the first layer's two products (same input, same weights for every member)
 are computed once and fanned out to all members in its epilogue, and every later layer runs all members in one launch
 (lbbnn_vd_gemm_members).  Member m is bitwise the m-th of ``samples`` consecutive ``net(data)`` calls.
+
+LRT and MNF networks also have a *frozen evaluation model*, ``freeze(net, gates="alpha" | "mpm")`` -> ``FrozenNetwork``: a
+snapshot of the GEMM operands taken once (lbbnn_frozen_operands), with the gates as trained or thresholded -- the median
+probability model of ``outofsample(net, loader, medimod=True)`` (LBBNN-GP-MF-LRT.py:295-314, LBBNN-GP-MF-MNF.py:342-366) --
+which the member GEMMs then evaluate without reading the parameters again, and which reports its own density.
 """
-from typing import Dict, Optional
+import math
+from typing import Dict, List, Optional
 
 import torch
+from torch import nn
 
 from . import ops
 
@@ -235,9 +242,17 @@ def ensemble_forward(net, data: torch.Tensor, samples: int = 10, batched=None, *
     HIP device: ``base_ensemble``), else the loop of fused single forwards (``net.sample_predict`` for a baseline network);
     True / False force one of them.  Either form advances the live Philox offset by ``samples``.
     ``gates`` ("sample" or "mpm") applies to baseline networks only, ``max_members`` (members per launch of the batched form)
-    to baseline and variational-dropout networks.  A variational-dropout network (``vd.BNN``): None = ``vd_ensemble`` on a
+    to baseline and variational-dropout networks and frozen models.  A ``FrozenNetwork`` (``freeze``): its ``ensemble``.
+    A variational-dropout network (``vd.BNN``): None = ``vd_ensemble`` on a
     HIP device when no layer has injected noise, else the loop of ``net(data)``; True with injected noise raises ValueError."""
     net.eval()
+    if _is_frozen(net):
+        if gates != "sample":
+            raise ValueError("bnn_amd: gates=%r: the gates of a frozen model were fixed by evaluate.freeze(net, gates=...) "
+                             "(this one has gates=%r); freeze again to change them" % (gates, net.gates))
+        if batched is False:
+            raise ValueError("bnn_amd: a frozen model has no loop-of-forwards form; leave batched at None")
+        return net.ensemble(data, samples, max_members=max_members)
     if _is_vd(net):
         if gates != "sample":
             raise ValueError("bnn_amd: gates=%r (the median probability model) exists for baseline LBBNN networks only"
@@ -258,7 +273,9 @@ def ensemble_forward(net, data: torch.Tensor, samples: int = 10, batched=None, *
             return base_ensemble(net, data, samples, gates=gates, max_members=max_members)["outputs"]
         return torch.stack([net.sample_predict(data, gates=gates) for _ in range(samples)])
     if gates != "sample":
-        raise ValueError("bnn_amd: gates=%r (the median probability model) exists for baseline LBBNN networks only" % (gates,))
+        raise ValueError("bnn_amd: gates=%r is not an option of ensemble_forward for an LRT / MNF network; the median "
+                         "probability model of such a network is evaluate.freeze(net, gates=\"mpm\").ensemble(data, samples)"
+                         % (gates,))
     if max_members is not None:
         raise ValueError("bnn_amd: max_members applies to baseline LBBNN networks only")
     if batched is None:
@@ -272,10 +289,14 @@ def ensemble_forward(net, data: torch.Tensor, samples: int = 10, batched=None, *
 @torch.no_grad()
 def ensemble_eval(net, data: torch.Tensor, target: Optional[torch.Tensor] = None, samples: int = 10) -> Dict[str, object]:
     """test_ensemble's numbers for one batch: ``outputs``, ``pred_ensemble``, ``pred_posterior_mean``, ``density`` (and
-    ``correct_*`` with a target).  Variational-dropout networks: ``outputs``, ``pred_ensemble``, and ``loss`` and
+    ``correct_*`` with a target).  Frozen models (``freeze``): the same keys, ``pred_posterior_mean`` from
+    ``frozen(data, sample=False)`` and ``density`` = ``samples`` copies of ``frozen.density`` (fixed gates are not resampled).
+    Variational-dropout networks: ``outputs``, ``pred_ensemble``, and ``loss`` and
     ``correct_ensemble`` with a target (``_vd_ensemble_eval``).  Baseline networks: ``density[s]`` is the mean gate of member s over all weights -- the gates
     the member actually used (the reference draws a separate set, LBBNN-GP-MF.py:390-394) -- and the posterior mean is the
     mode-2 forward (weight = alpha * mu) with alpha = sigmoid(lambdal) set as the reference sets it (:369-374, :413)."""
+    if _is_frozen(net):
+        return _frozen_ensemble_eval(net, data, target, samples)
     if _is_base(net):
         return _base_ensemble_eval(net, data, target, samples)
     if _is_vd(net):
@@ -289,6 +310,18 @@ def ensemble_eval(net, data: torch.Tensor, target: Optional[torch.Tensor] = None
     pred_mean = net(data, sample=False).argmax(1)
     res = {"outputs": outputs, "pred_ensemble": pred_ens, "pred_posterior_mean": pred_mean,
            "density": torch.stack(density)}
+    if target is not None:
+        res["correct_ensemble"] = int(pred_ens.eq(target).sum())
+        res["correct_posterior_mean"] = int(pred_mean.eq(target).sum())
+    return res
+
+
+def _frozen_ensemble_eval(net, data, target, samples):
+    outputs = net.ensemble(data, samples)
+    pred_ens = outputs.mean(0).argmax(1)
+    pred_mean = net(data, sample=False).argmax(1)
+    density = torch.full((int(samples),), net.density, dtype=torch.float32, device=outputs.device)
+    res = {"outputs": outputs, "pred_ensemble": pred_ens, "pred_posterior_mean": pred_mean, "density": density}
     if target is not None:
         res["correct_ensemble"] = int(pred_ens.eq(target).sum())
         res["correct_posterior_mean"] = int(pred_mean.eq(target).sum())
@@ -340,3 +373,386 @@ def predictive_entropy(outputs: torch.Tensor) -> torch.Tensor:
     p = p / p.sum(-1, keepdim=True)
     m = p.mean(0)
     return -(m * torch.log(m)).sum(-1)
+
+
+# ----------------------------------------------------------------------------------------- frozen evaluation model
+FROZEN_GATES = ("alpha", "mpm")
+
+
+def _empty(*size, **kw):
+    """Every device buffer of a FrozenNetwork comes from here (the tests hand out NaN-filled ones through it)."""
+    return torch.empty(*size, **kw)
+
+
+def _is_frozen(net) -> bool:
+    return isinstance(net, FrozenNetwork)
+
+
+def _pad4(n: int) -> int:
+    return -(-n // 4) * 4
+
+
+class FrozenNetwork(nn.Module):
+    """A trained LRT / MNF network frozen for evaluation (built by ``freeze``; no parameters, buffers only).
+
+    Per layer it holds ``e0`` = weight_mu * a as plain fp32 rows, the GEMM operands ``e_w`` (of e0) and ``var_w`` (of
+    sigma^2 a^2) in the format of the network's precision at freeze time (fp32, or bf16 hi | lo under any 16-bit setting: the
+    member dimension of the ensemble kernels exists in that format only), ``bias_var``, a copy of ``bias_mu`` and -- MNF -- of
+    ``q0_mean``, ``q0_log_var`` and the planar z flow, and ``kept_rows``: per output row the number of weights with
+    ``lambdal > logit(threshold)``.  The gate value a is alpha = sigmoid(lambdal) (``gates="alpha"``: today's evaluation
+    forward) or the indicator of ``lambdal > logit(threshold)`` (``gates="mpm"``: the median probability model at the default
+    threshold 0.5); the bias and z are never gated.  Nothing here follows the source network's parameters until ``refresh()``.
+    """
+
+    def __init__(self, dims, family: str = "lrt", gates: str = "alpha", threshold: float = 0.5, device=None):
+        super().__init__()
+        if gates not in FROZEN_GATES:
+            raise ValueError("bnn_amd: gates must be 'alpha' (the gates as trained) or 'mpm' (the median probability model), "
+                             "got %r" % (gates,))
+        threshold = float(threshold)
+        if not 0.0 < threshold < 1.0:
+            raise ValueError("bnn_amd: threshold must lie strictly between 0 and 1 (0.5 = the median probability model), got %r"
+                             % (threshold,))
+        if family not in ("lrt", "mnf"):
+            raise ValueError("bnn_amd: family must be 'lrt' or 'mnf', got %r" % (family,))
+        self.dims = tuple(int(d) for d in dims)
+        self.family, self.gates, self.threshold = family, gates, threshold
+        # logit(threshold) as the fp32 value the kernel compares lambdal with (exactly 0 at 0.5)
+        self.cut = float(torch.tensor(math.log(threshold / (1.0 - threshold)), dtype=torch.float32))
+        self.last_z = None
+        self._src = [None]              # the source network, in a list so that it is not registered as a submodule
+        self._split, self._layer_ids, self._row_offsets, self._T = [], [], [], []
+        self._members_ok = True
+        self._mcap, self._zbuf, self._ewm = 0, None, []
+        for i in range(len(self.dims) - 1):
+            self.register_buffer("kept_rows_%d" % i, torch.zeros(self.dims[i + 1], dtype=torch.int32, device=device))
+
+    # ------------------------------------------------------------------------------------- statistics
+    @property
+    def n_layers(self) -> int:
+        return len(self.dims) - 1
+
+    def _buf(self, name: str, i: int) -> torch.Tensor:
+        return getattr(self, "%s_%d" % (name, i))
+
+    @property
+    def kept_rows(self) -> List[torch.Tensor]:
+        """Per layer (O,) int32: weights of each output row with lambdal > logit(threshold) (in either gates mode)."""
+        return [self._buf("kept_rows", i) for i in range(self.n_layers)]
+
+    @property
+    def kept(self) -> List[int]:
+        return [int(k.sum()) for k in self.kept_rows]
+
+    @property
+    def density(self) -> float:
+        """Kept weights / all weights over every layer -- the density the thesis reports for the median probability model."""
+        total = sum(self.dims[i] * self.dims[i + 1] for i in range(self.n_layers))
+        return sum(self.kept) / total
+
+    def extra_repr(self) -> str:
+        return "dims=%s, family=%s, gates=%s, threshold=%g" % (self.dims, self.family, self.gates, self.threshold)
+
+    # ------------------------------------------------------------------------------------- snapshot
+    def _bind(self, net):
+        """Allocate every buffer for ``net``'s layers (once) and take the first snapshot."""
+        layers = net._layers()
+        dev = layers[0].weight_mu.device
+        f = dict(dtype=torch.float32, device=dev)
+        self._src = [net]
+        for i, l in enumerate(layers):
+            O, I = l.out_features, l.in_features
+            ld = ops.operand_ld(I)
+            # the operand format, by the rule of ensemble_forward_batched: any 16-bit precision -> bf16 hi | lo where the split
+            # kernels take the shape and the rows the previous layer writes stay 16-B aligned
+            self._split.append(bool(l._split(None)) and (i == 0 or layers[i - 1].out_features % 4 == 0))
+            if I % 4 or ld > 2048:
+                self._members_ok = False
+            for name, shape in (("e0", (O, ld)), ("e_w", (O, ld)), ("var_w", (O, ld)), ("bias_var", (O,)), ("bias_mu", (O,))):
+                self.register_buffer("%s_%d" % (name, i), _empty(shape, **f))
+            if l._mnf:
+                T = len(l.z_flow.transforms)
+                self._T.append(T)
+                for name, shape in (("q0_mean", (I,)), ("q0_log_var", (I,)), ("flow_u", (T, I)), ("flow_w", (T, I)),
+                                    ("flow_b", (T, 1))):
+                    self.register_buffer("%s_%d" % (name, i), _empty(shape, **f))
+            else:
+                self._T.append(0)
+        self.refresh()
+        return self
+
+    def _descs(self, src_layers=None):
+        """lbbnn_frozen_desc_t of every layer; with ``src_layers`` the parameter pointers are filled too (refresh)."""
+        from . import _lib
+        n = self.n_layers
+        descs = (_lib.FrozenDesc * n)()
+        for i in range(n):
+            d = descs[i]
+            d.O, d.I = self.dims[i + 1], self.dims[i]
+            d.ld = ops.operand_ld(d.I)
+            d.flags = ops.F_SPLIT16 if self._split[i] else 0
+            d.mode = 1 if self.gates == "mpm" else 0
+            d.cut, d.layer_id = self.cut, self._layer_ids[i]
+            d.e0, d.e_w, d.var_w = (self._buf(k, i).data_ptr() for k in ("e0", "e_w", "var_w"))
+            d.bias_var, d.kept_rows = self._buf("bias_var", i).data_ptr(), self._buf("kept_rows", i).data_ptr()
+            if src_layers is not None:
+                l = src_layers[i]
+                d.weight_mu, d.weight_rho, d.lambdal = l.weight_mu.data_ptr(), l.weight_rho.data_ptr(), l.lambdal.data_ptr()
+                d.bias_rho = l.bias_rho.data_ptr()
+            if self.family == "mnf":
+                d.q0_mean, d.q0_log_var = self._buf("q0_mean", i).data_ptr(), self._buf("q0_log_var", i).data_ptr()
+                u, w, b = self._buf("flow_u", i), self._buf("flow_w", i), self._buf("flow_b", i)
+                d.z_flow.T = self._T[i]
+                for t in range(self._T[i]):
+                    d.z_flow.u[t], d.z_flow.w[t], d.z_flow.b[t] = u[t].data_ptr(), w[t].data_ptr(), b[t].data_ptr()
+        return descs
+
+    @torch.no_grad()
+    def refresh(self):
+        """Take the snapshot again from the source network's current parameters, into the same buffers: ONE
+        lbbnn_frozen_operands launch for all layers, plus copies of the small vectors (bias_mu; q0 and the z flow of an MNF
+        layer).  For evaluate-every-epoch loops."""
+        from . import _lib
+        net = self._src[0]
+        if net is None:
+            raise RuntimeError("bnn_amd: this FrozenNetwork is not bound to a network; build it with evaluate.freeze(net)")
+        layers = net._layers()
+        _check_freezable_layers(layers)
+        dev = self._buf("e0", 0).device
+        if layers[0].weight_mu.device != dev:
+            raise RuntimeError("bnn_amd: the source network moved from %s to %s since freeze(); freeze it again"
+                               % (dev, layers[0].weight_mu.device))
+        self._layer_ids = [int(l._layer_id) for l in layers]
+        self._row_offsets = [int(l.row_offset) for l in layers]
+        dst, src = [], []
+        for i, l in enumerate(layers):
+            for name in ("weight_mu", "weight_rho", "lambdal"):
+                p = getattr(l, name)
+                if not p.is_contiguous():
+                    raise RuntimeError("bnn_amd: %s of layer %d is not contiguous" % (name, i + 1))
+            dst.append(self._buf("bias_mu", i)); src.append(l.bias_mu.detach())
+            if l._mnf:
+                dst += [self._buf("q0_mean", i), self._buf("q0_log_var", i)]
+                src += [l.q0_mean.detach(), l.q0_log_var.detach()]
+                for t, tr in enumerate(l.z_flow.transforms):
+                    dst += [self._buf("flow_u", i)[t], self._buf("flow_w", i)[t], self._buf("flow_b", i)[t]]
+                    src += [tr.u.detach().reshape(-1), tr.w.detach().reshape(-1), tr.bias.detach().reshape(-1)]
+        torch._foreach_copy_(dst, src)                       # the small vectors of every layer in one fused copy
+        descs = self._descs(layers)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(_lib.lib().lbbnn_frozen_operands(descs, self.n_layers, stream), "lbbnn_frozen_operands")
+        return self
+
+    # ------------------------------------------------------------------------------------- evaluation
+    def _input(self, data):
+        x = data.reshape(-1, self.dims[0])
+        if not x.is_cuda:
+            raise RuntimeError("bnn_amd: a frozen model evaluates on a HIP device tensor (data is on %s); there is no CPU path"
+                               % data.device)
+        if x.device != self._buf("e0", 0).device:
+            raise RuntimeError("bnn_amd: data is on %s, the frozen model on %s" % (x.device, self._buf("e0", 0).device))
+        x = x.float() if x.dtype != torch.float32 else x
+        if x.stride(1) != 1 or x.stride(0) < self.dims[0]:
+            x = x.contiguous()
+        if self._split[0]:
+            # the bf16 hi | lo kernels read x rows as 16-B vectors through 32-bit offsets
+            if x.shape[0] * x.stride(0) * 4 >= 0x7FFFFFF0:
+                raise ValueError("bnn_amd: a batch of %d rows exceeds the 2 GiB the 16-bit kernels address; split it"
+                                 % x.shape[0])
+            if x.stride(0) % 4 or x.data_ptr() % 16:
+                x = x.clone(memory_format=torch.contiguous_format)
+        return x
+
+    def _member_buffers(self, c: int):
+        """z [c][sum of ld] (every MNF layer's block side by side: one member stride, one flow launch) and the member mean
+        operands [c][O][ld] per layer; allocated for the largest chunk seen, smaller chunks use a prefix."""
+        if c > self._mcap:
+            dev = self._buf("e0", 0).device
+            f = dict(dtype=torch.float32, device=dev)
+            lds = [ops.operand_ld(self.dims[i]) for i in range(self.n_layers)]
+            self._zbuf = _empty((c, sum(lds)), **f)
+            self._ewm = [_empty((c, self.dims[i + 1], lds[i]), **f) for i in range(self.n_layers)]
+            self._mcap = c
+        return self._zbuf, self._ewm
+
+    def _draw_members(self, c: int, rng, stream):
+        """MNF: member m's z at Philox offset rng[1] + m and its mean operand E0 * z_m (lbbnn_frozen_members)."""
+        from . import _lib
+        zbuf, ewm = self._member_buffers(c)
+        descs = self._descs()
+        off = 0
+        for i in range(self.n_layers):
+            descs[i].z_fwd = zbuf.data_ptr() + 4 * off
+            descs[i].z_mstride = zbuf.stride(0)
+            descs[i].e_w_members = ewm[i].data_ptr()
+            off += ops.operand_ld(self.dims[i])
+        _lib.check(_lib.lib().lbbnn_frozen_members(descs, self.n_layers, c, rng.data_ptr(), 1, stream), "lbbnn_frozen_members")
+        return zbuf, ewm
+
+    def _z_of(self, zbuf, c):
+        out, off = [], 0
+        for i in range(self.n_layers):
+            out.append(zbuf[:c, off:off + self.dims[i]].clone())
+            off += ops.operand_ld(self.dims[i])
+        return out
+
+    def _chunk(self, x, c: int, st, head, zs):
+        """Members live .. live + c - 1 of the ensemble into head (c, pad4(B * classes)): MNF 2 launches for z and the member
+        operands, then one lbbnn_lrt_gemm_members launch per layer."""
+        from . import _lib
+        B, dev, n = x.shape[0], x.device, self.n_layers
+        rng = st.t
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        mnf = self.family == "mnf"
+        if mnf:
+            zbuf, ewm = self._draw_members(c, rng, stream)
+            if zs is not None:
+                zs.append(self._z_of(zbuf, c))
+        h, h_ms = x, 0                                       # the first layer reads the same rows for every member
+        for i in range(n):
+            O, I = self.dims[i + 1], self.dims[i]
+            ld = ops.operand_ld(I)
+            last = i == n - 1
+            o_ms = _pad4(B * O)                              # member stride padded to 16 B
+            out = head if last else _empty((c, o_ms), dtype=torch.float32, device=dev)
+            flags = (0 if last else ops.F_RELU) | (ops.F_SPLIT16 if self._split[i] else 0) | \
+                    (ops.F_LOG_SOFTMAX if (last and O <= 16) else 0)
+            e_ptr, w_ms = (ewm[i].data_ptr(), O * ld) if mnf else (self._buf("e_w", i).data_ptr(), 0)
+            rc = _lib.lib().lbbnn_lrt_gemm_members(
+                h.data_ptr(), (h.stride(0) if i == 0 else self.dims[i]), h_ms, e_ptr, w_ms, self._buf("var_w", i).data_ptr(), ld,
+                self._buf("bias_mu", i).data_ptr(), self._buf("bias_var", i).data_ptr(), rng.data_ptr(),
+                ops.STREAM_EPS_OUT * 64 + self._layer_ids[i], self._row_offsets[i], 1, out.data_ptr(), O, o_ms, B, I, O,
+                flags, c, stream)
+            _lib.check(rc, "lbbnn_lrt_gemm_members")
+            h, h_ms = out, o_ms
+        st.advance(c)                                        # as c single forwards would have
+
+    def _chain(self, x, st, e_ws, stochastic: bool):
+        """One member as a chain of single lbbnn_lrt_gemm calls on the frozen operands, drawing at the live offset."""
+        h, n = x, self.n_layers
+        for i in range(n):
+            O, I = self.dims[i + 1], self.dims[i]
+            last = i == n - 1
+            h = ops.lrt_gemm(h, e_ws[i], self._buf("var_w", i), I=I, O=O, bias_mean=self._buf("bias_mu", i),
+                             bias_var=self._buf("bias_var", i), rng=st.t, rng_stream=ops.STREAM_EPS_OUT * 64 + self._layer_ids[i],
+                             row_offset=self._row_offsets[i], relu=not last, mean_only=not stochastic,
+                             log_softmax=last and O <= 16, split=self._split[i], single=False)
+        return h if self.dims[-1] <= 16 else torch.log_softmax(h, dim=1)
+
+    @torch.no_grad()
+    def ensemble(self, data: torch.Tensor, samples: int = 10, *, max_members: Optional[int] = None,
+                 keep_z: bool = False) -> torch.Tensor:
+        """(samples, B, classes) log-probabilities of ``samples`` stochastic forwards of the frozen model.  Member m draws where
+        the m-th member of ``ensemble_forward_batched`` draws: eps of layer i from stream STREAM_EPS_OUT * 64 + layer id with the
+        layer's row_offset at Philox offset live + m, z of an MNF layer from its q0 and z flow at the same offset.  The live
+        offset advances by ``samples``.  ``max_members``: members per launch (default: all); chunked and unchunked results are
+        the same bits.  ``keep_z``: ``self.last_z`` = per layer the (samples, in_features) z every member used (None entries for
+        an LRT model).  An LRT model with a layer the member GEMM does not take (in_features % 4 != 0 or an operand row wider
+        than 2048) runs every member as a chain of single GEMM calls on the frozen operands instead -- same draws, same shape."""
+        S = int(samples)
+        if S < 1:
+            raise ValueError("bnn_amd: samples must be >= 1")
+        chunk = S if max_members is None else int(max_members)
+        if chunk < 1:
+            raise ValueError("bnn_amd: max_members must be >= 1")
+        x = self._input(data)
+        B, C, dev = x.shape[0], self.dims[-1], x.device
+        st = ops.RngState.get(dev)
+        self.last_z = None
+        with torch.cuda.device(dev):
+            if B == 0:
+                st.advance(S)
+                return torch.zeros((S, 0, C), dtype=torch.float32, device=dev)
+            if not self._members_ok:                         # (LRT only: freeze refuses such an MNF network)
+                outs = []
+                for _ in range(S):
+                    outs.append(self._chain(x, st, [self._buf("e_w", i) for i in range(self.n_layers)], True))
+                    st.advance(1)
+                if keep_z:
+                    self.last_z = [None] * self.n_layers
+                return torch.stack(outs)
+            head = _empty((S, _pad4(B * C)), dtype=torch.float32, device=dev)
+            zs = [] if (keep_z and self.family == "mnf") else None
+            for m0 in range(0, S, chunk):
+                c = min(chunk, S - m0)
+                self._chunk(x, c, st, head[m0:m0 + c], zs)
+        if keep_z:
+            self.last_z = [torch.cat(parts) for parts in zip(*zs)] if zs is not None else [None] * self.n_layers
+        outputs = head[:, :B * C].view(S, B, C)
+        return outputs if C <= 16 else torch.log_softmax(outputs, dim=-1)
+
+    @torch.no_grad()
+    def forward(self, data: torch.Tensor, sample: bool = False) -> torch.Tensor:
+        """(B, classes) log-probabilities of one member.  ``sample=True``: member 0 of ``ensemble(data, 1)``.
+        ``sample=False``: the posterior-mean branch x . E0^T + bias_mu (LBBNN-GP-MF-LRT.py:178-180); an MNF model still draws
+        its z (LBBNN-GP-MF-MNF.py:203) and advances the live offset by 1, an LRT model draws nothing."""
+        if sample:
+            return self.ensemble(data, 1)[0]
+        x = self._input(data)
+        dev = x.device
+        st = ops.RngState.get(dev)
+        with torch.cuda.device(dev):
+            if self.family == "mnf":
+                _, ewm = self._draw_members(1, st.t, torch.cuda.current_stream(dev).cuda_stream)
+                out = self._chain(x, st, [e[0] for e in ewm], False)
+                st.advance(1)
+                return out
+            return self._chain(x, st, [self._buf("e_w", i) for i in range(self.n_layers)], False)
+
+
+def _check_freezable_layers(layers):
+    from . import _lib
+    if len(layers) > _lib.MAX_LAYERS:
+        raise ValueError("bnn_amd: freeze takes networks of at most %d layers" % _lib.MAX_LAYERS)
+    for i, l in enumerate(layers):
+        if l.noise:
+            raise ValueError("bnn_amd: layer %d has injected noise (layer.noise); a frozen model draws in-kernel noise only -- "
+                             "clear it, or evaluate with ensemble_forward(net, data, samples, batched=False)" % (i + 1))
+        if getattr(l, "as_written", False):
+            raise ValueError("bnn_amd: layer %d has as_written set; a frozen model implements the corrected forward only -- "
+                             "evaluate such a network with ensemble_forward(net, data, samples, batched=False)" % (i + 1))
+        if l._mnf:
+            if l._check_flows() != "planar" or len(l.z_flow.transforms) > 4:
+                raise ValueError("bnn_amd: layer %d: a frozen MNF model needs planar flows with at most 4 transforms (it has "
+                                 "z_flow=%s with %d); evaluate this network with ensemble_forward(net, data, samples)"
+                                 % (i + 1, l.z_flow.kind, len(l.z_flow.transforms)))
+            if l.in_features % 4 or ops.operand_ld(l.in_features) > 2048:
+                raise ValueError("bnn_amd: layer %d: a frozen MNF model needs in_features %% 4 == 0 and operand rows of at most "
+                                 "2048 (in_features = %d); evaluate this network with ensemble_forward(net, data, samples)"
+                                 % (i + 1, l.in_features))
+
+
+def freeze(net, gates: str = "alpha", *, threshold: float = 0.5) -> FrozenNetwork:
+    """Frozen evaluation model of an LRT / MNF network (``lrt.BayesianNetwork``, ``mnf.BayesianNetwork``) on a HIP device.
+
+    ``gates="alpha"``: the gates as trained, a = sigmoid(lambdal) -- ``frozen.ensemble(x, S)`` computes what
+    ``ensemble_forward(net, x, S)`` computes from the same Philox offset.  ``gates="mpm"``: the median probability model of
+    ``outofsample(net, loader, medimod=True)``: a weight is kept (a = 1) iff ``lambdal > logit(threshold)``, compared in fp32;
+    at the default threshold 0.5 that is ``alpha > 0.5``, which an fp32 ``sigmoid(lambdal) > 0.5`` matches except for
+    0 < lambdal < ~6e-8 (alpha rounds to exactly 0.5 there; the frozen model keeps those weights).  The operand format is the
+    network's precision at this moment ("fp32" -> fp32 operands, any 16-bit setting -> bf16 hi | lo)."""
+    from . import layers as L
+    if gates not in FROZEN_GATES:
+        raise ValueError("bnn_amd: gates must be 'alpha' (the gates as trained) or 'mpm' (the median probability model), got %r"
+                         % (gates,))
+    if not 0.0 < float(threshold) < 1.0:
+        raise ValueError("bnn_amd: threshold must lie strictly between 0 and 1 (0.5 = the median probability model), got %r"
+                         % (threshold,))
+    if _is_base(net):
+        raise TypeError("bnn_amd: freeze takes an LRT / MNF network; a baseline LBBNN network has its own median probability "
+                        "model: ensemble_forward(net, data, samples, gates=\"mpm\")")
+    if _is_vd(net):
+        raise TypeError("bnn_amd: freeze takes an LRT / MNF network; a variational-dropout network has no gates -- use "
+                        "vd_ensemble(net, data, samples)")
+    if not isinstance(net, L._NetworkBase):
+        raise TypeError("bnn_amd: freeze takes an lrt.BayesianNetwork or mnf.BayesianNetwork, got %s" % type(net).__name__)
+    layers = net._layers()
+    _check_freezable_layers(layers)
+    if not layers[0].weight_mu.is_cuda:
+        raise RuntimeError("bnn_amd: freeze needs the network on a HIP device (it is on %s); there is no CPU path"
+                           % layers[0].weight_mu.device)
+    family = "mnf" if layers[0]._mnf else "lrt"
+    fz = FrozenNetwork(net.dims, family, gates, threshold, device=layers[0].weight_mu.device)
+    fz.eval()
+    return fz._bind(net)

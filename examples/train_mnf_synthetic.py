@@ -7,6 +7,7 @@ labels stands in for the loaders.
 
     python examples/train_mnf_synthetic.py            # eager loop, the reference's default RNVP flows
     GRAPH=1 python examples/train_mnf_synthetic.py    # the same step captured once in a HIP graph and replayed
+    FLOWS=Planar python examples/train_mnf_synthetic.py   # planar flows; ends with the median probability model (frozen)
 """
 import os
 import sys
@@ -25,7 +26,8 @@ BATCH_SIZE, NUM_BATCHES, EPOCHS, TEST_SAMPLES = 1000, 12, 6, 10
 bnn_amd.set_precision("bf16x3")
 torch.manual_seed(1)                                # the reference seeds per run (:409); also seeds the in-kernel noise
 
-net = BayesianNetwork().to(DEVICE)                  # 784-400-600-10, RNVP flows, num_transforms=2 (:244-250)
+FLOWS = os.environ.get("FLOWS", "RNVP")
+net = BayesianNetwork(z_flow_type=FLOWS, r_flow_type=FLOWS).to(DEVICE)     # 784-400-600-10, RNVP flows, num_transforms=2 (:244-250)
 optimizer = bnn_amd.optim.Adam(net.parameters(), lr=1e-3)      # torch.optim.Adam works too (:358)
 
 g = torch.Generator(device=DEVICE).manual_seed(7)
@@ -62,3 +64,16 @@ for epoch in range(EPOCHS):
 res = ensemble_eval(net, test_x, test_y, samples=TEST_SAMPLES)
 print("density %.3f | posterior mean %.3f | ensemble %.3f" % (float(res["density"].mean()),
       res["correct_posterior_mean"] / BATCH_SIZE, res["correct_ensemble"] / BATCH_SIZE))
+
+# the median probability model of outofsample(net, loader, medimod=True) (LBBNN-GP-MF-MNF.py:342-366): keep a weight iff its
+# inclusion probability exceeds 0.5 -- a frozen snapshot of the trained network, evaluated without touching the parameters
+# again.  (A frozen MNF model draws z through planar flows; with the default RNVP flows this step is left out.)
+if FLOWS == "Planar":
+    mpm = bnn_amd.evaluate.freeze(net, gates="mpm")
+    res = ensemble_eval(mpm, test_x, test_y, samples=TEST_SAMPLES)
+    print("median probability model: density %.3f (kept per layer %s) | posterior mean %.3f | ensemble %.3f | mean predictive "
+          "entropy %.3f" % (mpm.density, mpm.kept, res["correct_posterior_mean"] / BATCH_SIZE,
+                            res["correct_ensemble"] / BATCH_SIZE,
+                            float(bnn_amd.evaluate.predictive_entropy(res["outputs"]).mean())))
+else:
+    print("median probability model: run with FLOWS=Planar (evaluate.freeze takes planar z flows)")

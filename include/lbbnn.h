@@ -525,6 +525,68 @@ int lbbnn_vd_gemm_members(const float* x, int ldx, int64_t x_mstride, const void
                           int B, int I, int O, int flags, int members, int fanout, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Frozen evaluation model of an LRT / MNF network: the GEMM operands taken ONCE from the trained parameters, with the gates
+ * as trained or thresholded (the median probability model of outofsample(net, loader, medimod=True),
+ * LBBNN-GP-MF-LRT.py:295-314, LBBNN-GP-MF-MNF.py:342-366), which the member GEMMs above then evaluate without reading the
+ * parameters again.
+ *
+ * Per weight, with sigma = log1p(exp(weight_rho)), alpha = 1/(1+exp(-lambdal)) and the gate value a:
+ *   mode = LBBNN_FROZEN_ALPHA: a = alpha -- the evaluation forward (...LRT.py:167-180, ...MNF.py:191-206); the operands are
+ *                              the values lbbnn_weight_pass writes (the same device functions in the same order);
+ *   mode = LBBNN_FROZEN_MPM:   a = 1 where lambdal > cut, else 0, compared in fp32; cut = logit(threshold), 0 for the
+ *                              median model alpha > 0.5.  (An fp32 sigmoid(lambdal) > 0.5 differs only for 0 < lambdal <
+ *                              ~6e-8, where the rounded alpha is exactly 0.5; NaN is never kept.)
+ *   E0 = weight_mu * a (mpm: weight_mu itself or +0.0),  V = sigma^2 * a^2 (mpm: sigma^2 or 0).  The bias is never gated.
+ *
+ * lbbnn_frozen_operands: ONE launch for all n <= LBBNN_MAX_LAYERS layers.  Per layer it reads weight_mu, weight_rho, lambdal
+ *   (O,I) and bias_rho (O) once and writes
+ *     e0        [O][ld] plain fp32 E0, zero tail [I, ld);
+ *     e_w       [O][ld] GEMM operand of E0 (fp32, or the bf16 hi | lo layout with LBBNN_F_SPLIT16 in flags): what an LRT
+ *               layer, and an MNF layer at z = 1, multiply with;
+ *     var_w     [O][ld] GEMM operand of V in the same format;   bias_var (O) = softplus(bias_rho)^2;
+ *     kept_rows (O) int32: the number of weights of the row with lambdal > cut, in BOTH modes.
+ *   All five outputs are required (LBBNN_E_NULL).  1 <= I <= ld (LBBNN_E_SHAPE), ld a multiple of 32, e0 / e_w / var_w 16-B
+ *   aligned, every other pointer 4-B aligned (LBBNN_E_ALIGN); LBBNN_F_SPLIT16 needs I % 4 == 0 and 16-B aligned parameters
+ *   (LBBNN_E_ALIGN), fp32 operands take any I.  flags other than 0 | LBBNN_F_SPLIT16, or an unknown mode: LBBNN_E_FLAGS.
+ *   The fields q0_mean ... e_w_members are not read by this call.
+ *
+ * lbbnn_frozen_members: the per-member part, for the MNF layers among the n descriptors (q0_mean != NULL; LRT layers are
+ *   skipped -- their e_w is shared by every member: lbbnn_lrt_gemm_members takes w_mstride = 0).  Member m's z_k is drawn and
+ *   pushed through the planar z_flow exactly as lbbnn_ensemble_operands does it (Philox offset rng[1] + m * member_advance,
+ *   stream LBBNN_STREAM_EPS_Z * 64 + layer_id; more than one member needs z_flow.T <= 4) into z_fwd + m * z_mstride, then ONE
+ *   launch writes e_w_members + m * O * ld = operand(E0 * z_m) (format by flags) for every member and MNF layer.  z is not
+ *   gated.  When all MNF layers have the same z_mstride (their z blocks side by side in one [members][z_mstride] buffer) the
+ *   flows of all layers are one launch, else one launch per layer.
+ *   1 <= members <= 65535, 1 <= I <= ld, I <= z_mstride, 0 <= z_flow.T <= LBBNN_MAX_FLOW_T (LBBNN_E_SHAPE); I, z_mstride
+ *   multiples of 4, ld of 32, e0 / z_fwd / e_w_members 16-B aligned (LBBNN_E_ALIGN); rng == NULL with an MNF layer present:
+ *   LBBNN_E_NOISE.  No MNF layer: a successful no-op.  The caller advances rng afterwards, as for lbbnn_ensemble_operands. */
+#define LBBNN_FROZEN_ALPHA 0
+#define LBBNN_FROZEN_MPM 1
+
+typedef struct lbbnn_frozen_desc {
+    const float *weight_mu, *weight_rho, *lambdal;   /* (O,I) */
+    const float *bias_rho;                           /* (O)   */
+    const float *q0_mean, *q0_log_var;               /* (I); both NULL for an LRT layer */
+    lbbnn_planar_flow_t z_flow;                      /* MNF layers: the planar z flow   */
+    float* e0;                                       /* [O][ld] fp32                    */
+    void *e_w, *var_w;                               /* [O][ld] GEMM operands           */
+    float* bias_var;                                 /* (O)                             */
+    int32_t* kept_rows;                              /* (O)                             */
+    float* z_fwd;                                    /* MNF: member m's z at z_fwd + m * z_mstride (I floats used) */
+    void* e_w_members;                               /* MNF: [members][O][ld] GEMM operands */
+    int64_t z_mstride;                               /* floats                          */
+    int O, I, ld;
+    int flags;                                       /* 0 | LBBNN_F_SPLIT16             */
+    int mode;                                        /* LBBNN_FROZEN_ALPHA | LBBNN_FROZEN_MPM */
+    float cut;                                       /* logit(threshold), LBBNN_FROZEN_MPM and kept_rows */
+    uint32_t layer_id;
+} lbbnn_frozen_desc_t;
+
+int lbbnn_frozen_operands(const lbbnn_frozen_desc_t* layers, int n, void* stream);
+int lbbnn_frozen_members(const lbbnn_frozen_desc_t* layers, int n, int members, const uint64_t* rng,
+                         uint64_t member_advance, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K7  lbbnn_vd_operands -- Gaussian variational-dropout layer (variational_dropout.py:55-68).
  *   phi = x.theta ; delta = (x^2).(theta^2) * alpha ; out = phi + sqrt(delta)*zeta        :64-67
  * theta is (I,O) row-major (NN layout).  This pass writes the GEMM operands theta^T and (theta^2)^T as

@@ -1,0 +1,248 @@
+"""CPU tier of the frozen evaluation model (include/lbbnn.h lbbnn_frozen_operands / lbbnn_frozen_members,
+evaluate.freeze / FrozenNetwork): the entry points are exported and bound, the descriptor matches the header, the argument
+checks return the documented codes without launching, the Python interface refuses what it cannot run and says what to use
+instead, and kept / density follow from kept_rows."""
+import ctypes
+import os
+import subprocess
+
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("lbbnn_frozen_operands", "lbbnn_frozen_members")
+E_NULL, E_SHAPE, E_ALIGN, E_FLAGS, E_NOISE = -1, -2, -3, -4, -5
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as ge
+    from bnn_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        ge.build()
+    return _lib.lib()
+
+
+def test_new_symbols_exported_and_bound_abi_unchanged(lib):
+    from bnn_amd import _lib
+    for n in NEW:
+        assert hasattr(lib, n), n
+        assert n in _lib.SIGNATURES, n
+    assert lib.lbbnn_abi_version() == 1
+
+
+def test_frozen_desc_layout_matches_the_header(tmp_path):
+    from bnn_amd import _lib
+    cname, cls = "lbbnn_frozen_desc_t", _lib.FrozenDesc
+    fields = ("weight_mu", "bias_rho", "q0_log_var", "z_flow", "e0", "var_w", "kept_rows", "z_fwd", "e_w_members",
+              "z_mstride", "O", "ld", "flags", "mode", "cut", "layer_id")
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "%s"' % os.path.join(ROOT, "include", "lbbnn.h"),
+             "int main(void) {", 'printf("size %%zu\\n", sizeof(%s));' % cname]
+    lines += ['printf("%s %%zu\\n", offsetof(%s, %s));' % (f, cname, f) for f in fields]
+    lines += ['printf("alpha %d\\n", LBBNN_FROZEN_ALPHA);', 'printf("mpm %d\\n", LBBNN_FROZEN_MPM);', "return 0; }"]
+    src = tmp_path / "sizes.c"
+    src.write_text("\n".join(lines))
+    exe = tmp_path / "sizes"
+    subprocess.run(["gcc", "-std=c99", "-o", str(exe), str(src)], check=True)
+    got = dict((l.split()[0], int(l.split()[1]))
+               for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    assert ctypes.sizeof(cls) == got["size"]
+    for f in fields:
+        assert getattr(cls, f).offset == got[f], f
+    assert (got["alpha"], got["mpm"]) == (0, 1)               # the modes FrozenNetwork._descs writes
+
+
+def _desc(_lib, O=4, I=4, ld=32, mnf=False, n=1):
+    """Descriptors whose pointers are never dereferenced: every call below must fail before launching."""
+    d = (_lib.FrozenDesc * n)()
+    for k in range(n):
+        for j, name in enumerate(("weight_mu", "weight_rho", "lambdal", "bias_rho", "e0", "e_w", "var_w", "bias_var",
+                                  "kept_rows")):
+            setattr(d[k], name, 4096 * (j + 1))
+        d[k].O, d[k].I, d[k].ld, d[k].flags, d[k].mode, d[k].cut, d[k].layer_id = O, I, ld, 0, 0, 0.0, k
+        if mnf:
+            d[k].q0_mean, d[k].q0_log_var, d[k].z_fwd, d[k].e_w_members = 4096 * 20, 4096 * 21, 4096 * 22, 4096 * 23
+            d[k].z_mstride = ld
+            d[k].z_flow.T = 0
+    return d
+
+
+def test_frozen_operands_argument_checks(lib):
+    from bnn_amd import _lib
+    ops_ = lib.lbbnn_frozen_operands
+    assert ops_(None, 1, None) == E_NULL
+    assert ops_(_desc(_lib), 0, None) == E_SHAPE
+    assert ops_(_desc(_lib, n=1), _lib.MAX_LAYERS + 1, None) == E_SHAPE
+    for name in ("weight_mu", "weight_rho", "lambdal", "bias_rho", "e0", "e_w", "var_w", "bias_var", "kept_rows"):
+        d = _desc(_lib)
+        setattr(d[0], name, None)
+        assert ops_(d, 1, None) == E_NULL, name
+    assert ops_(_desc(_lib, O=0), 1, None) == E_SHAPE
+    assert ops_(_desc(_lib, I=0), 1, None) == E_SHAPE
+    assert ops_(_desc(_lib, I=33, ld=32), 1, None) == E_SHAPE            # I > ld
+    assert ops_(_desc(_lib, I=4, ld=48), 1, None) == E_ALIGN             # ld % 32 != 0
+    for name in ("e0", "e_w", "var_w"):                                   # 16-B vector stores
+        d = _desc(_lib)
+        setattr(d[0], name, 4096 + 4)
+        assert ops_(d, 1, None) == E_ALIGN, name
+    d = _desc(_lib)
+    d[0].lambdal = 4096 + 2                                               # not even a float boundary
+    assert ops_(d, 1, None) == E_ALIGN
+    d = _desc(_lib)
+    d[0].flags, d[0].weight_mu = 0x4, 4096 + 4                            # bf16 hi | lo operands need aligned float4 rows
+    assert ops_(d, 1, None) == E_ALIGN
+    d = _desc(_lib, I=6)
+    d[0].flags = 0x4                                                      # ... and I % 4 == 0
+    assert ops_(d, 1, None) == E_ALIGN
+    for mode in (2, -1):
+        d = _desc(_lib)
+        d[0].mode = mode
+        assert ops_(d, 1, None) == E_FLAGS, mode
+    d = _desc(_lib)
+    d[0].flags = 0x1
+    assert ops_(d, 1, None) == E_FLAGS
+    d = _desc(_lib, n=2)                                                  # the second descriptor is checked too
+    d[1].mode = 7
+    assert ops_(d, 2, None) == E_FLAGS
+
+
+def test_frozen_members_argument_checks(lib):
+    from bnn_amd import _lib
+    mem = lib.lbbnn_frozen_members
+    rng = ctypes.c_void_p(4096 * 30)
+    assert mem(None, 1, 1, rng, 1, None) == E_NULL
+    assert mem(_desc(_lib, mnf=True), 0, 1, rng, 1, None) == E_SHAPE
+    assert mem(_desc(_lib, mnf=True), _lib.MAX_LAYERS + 1, 1, rng, 1, None) == E_SHAPE
+    assert mem(_desc(_lib, mnf=True), 1, 0, rng, 1, None) == E_SHAPE
+    assert mem(_desc(_lib, mnf=True), 1, 65536, rng, 1, None) == E_SHAPE
+    assert mem(_desc(_lib, mnf=True), 1, 2, None, 1, None) == E_NOISE     # an MNF layer draws z: rng required
+    assert mem(_desc(_lib, mnf=False), 1, 2, None, 1, None) == 0          # LRT layers only: nothing to do, nothing launched
+    for name in ("q0_log_var", "z_fwd", "e0", "e_w_members"):
+        d = _desc(_lib, mnf=True)
+        setattr(d[0], name, None)
+        assert mem(d, 1, 2, rng, 1, None) == E_NULL, name
+    assert mem(_desc(_lib, mnf=True, I=33, ld=32), 1, 2, rng, 1, None) == E_SHAPE
+    d = _desc(_lib, mnf=True)
+    d[0].z_flow.T = 17
+    assert mem(d, 1, 2, rng, 1, None) == E_SHAPE
+    d[0].z_flow.T = 2                                                     # transforms without parameters
+    assert mem(d, 1, 2, rng, 1, None) == E_NULL
+    d = _desc(_lib, mnf=True, I=8)
+    d[0].z_mstride = 4                                                    # shorter than a z vector
+    assert mem(d, 1, 2, rng, 1, None) == E_SHAPE
+    assert mem(_desc(_lib, mnf=True, I=6), 1, 2, rng, 1, None) == E_ALIGN
+    assert mem(_desc(_lib, mnf=True, ld=48), 1, 2, rng, 1, None) == E_ALIGN
+    d = _desc(_lib, mnf=True)
+    d[0].z_fwd = 4096 * 22 + 4
+    assert mem(d, 1, 2, rng, 1, None) == E_ALIGN
+    d = _desc(_lib, mnf=True)
+    d[0].flags = 0x2
+    assert mem(d, 1, 2, rng, 1, None) == E_FLAGS
+
+
+def test_freeze_refusals_say_what_to_use():
+    import bnn_amd
+    from bnn_amd import evaluate
+    torch.manual_seed(0)
+    lrt = bnn_amd.lrt.BayesianNetwork((20, 16, 12, 3))
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        evaluate.freeze(lrt)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        evaluate.freeze(bnn_amd.mnf.BayesianNetwork((20, 16, 12, 3), 2, z_flow_type="Planar", r_flow_type="Planar"), "mpm")
+    with pytest.raises(ValueError, match="'alpha'.*'mpm'"):
+        evaluate.freeze(lrt, gates="sample")
+    for t in (0.0, 1.0, -0.1, 1.5):
+        with pytest.raises(ValueError, match="threshold"):
+            evaluate.freeze(lrt, "mpm", threshold=t)
+    with pytest.raises(TypeError, match='gates="mpm"'):
+        evaluate.freeze(bnn_amd.base.BayesianNetwork((20, 16, 12, 3)))
+    with pytest.raises(TypeError, match="vd_ensemble"):
+        evaluate.freeze(bnn_amd.vd.BNN((20, 16, 12, 3)))
+    with pytest.raises(TypeError, match="lrt.BayesianNetwork"):
+        evaluate.freeze(torch.nn.Linear(4, 4))
+
+
+def test_layer_refusals_of_freeze():
+    """What a frozen model cannot represent is refused before anything else (so also without a device); a network that
+    passes these checks gets as far as the device check."""
+    import bnn_amd
+    from bnn_amd import evaluate
+    torch.manual_seed(0)
+    planar = dict(z_flow_type="Planar", r_flow_type="Planar")
+    lrt = bnn_amd.lrt.BayesianNetwork((20, 16, 12, 3))
+    lrt.l2.noise = {"eps_out": torch.zeros(5, 12)}
+    with pytest.raises(ValueError, match="injected noise.*batched=False"):
+        evaluate.freeze(lrt)
+    lrt.l2.noise = None
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        evaluate.freeze(lrt)
+    with pytest.raises(RuntimeError, match="no CPU path"):                # outside the member rule: an LRT network still freezes
+        evaluate.freeze(bnn_amd.lrt.BayesianNetwork((21, 16, 12, 3)))
+    with pytest.raises(ValueError, match="planar flows.*ensemble_forward"):
+        evaluate.freeze(bnn_amd.mnf.BayesianNetwork((20, 16, 12, 3), 2, z_flow_type="RNVP", r_flow_type="RNVP"))
+    with pytest.raises(ValueError, match="at most 4 transforms.*ensemble_forward"):
+        evaluate.freeze(bnn_amd.mnf.BayesianNetwork((20, 16, 12, 3), 5, **planar), "mpm")
+    with pytest.raises(ValueError, match="in_features % 4 == 0.*ensemble_forward"):
+        evaluate.freeze(bnn_amd.mnf.BayesianNetwork((22, 16, 12, 3), 2, **planar))
+    mnf = bnn_amd.mnf.BayesianNetwork((20, 16, 12, 3), 2, **planar)
+    mnf.l1.as_written = True
+    with pytest.raises(ValueError, match="as_written"):
+        evaluate.freeze(mnf)
+    mnf.l1.as_written = False
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        evaluate.freeze(mnf)
+
+
+def test_frozen_network_constructor_refusals():
+    from bnn_amd import evaluate
+    with pytest.raises(ValueError, match="'alpha'.*'mpm'"):
+        evaluate.FrozenNetwork((20, 16, 12, 3), "lrt", "sample")
+    with pytest.raises(ValueError, match="threshold"):
+        evaluate.FrozenNetwork((20, 16, 12, 3), "lrt", "mpm", 1.0)
+    with pytest.raises(ValueError, match="family"):
+        evaluate.FrozenNetwork((20, 16, 12, 3), "base")
+    fz = evaluate.FrozenNetwork((20, 16, 12, 3), "lrt", "mpm")
+    assert list(fz.parameters()) == []                                    # buffers only
+    assert fz.cut == 0.0 and fz.gates == "mpm" and fz.threshold == 0.5 and fz.dims == (20, 16, 12, 3)
+    with pytest.raises(RuntimeError, match="evaluate.freeze"):
+        fz.refresh()                                                      # not bound to a network
+
+
+def test_ensemble_forward_refusals():
+    import bnn_amd
+    from bnn_amd import evaluate
+    torch.manual_seed(0)
+    x = torch.rand(5, 20)
+    lrt = bnn_amd.lrt.BayesianNetwork((20, 16, 12, 3))
+    with pytest.raises(ValueError, match="evaluate.freeze"):              # still a ValueError; now it says where to go
+        evaluate.ensemble_forward(lrt, x, 3, gates="mpm")
+    mnf = bnn_amd.mnf.BayesianNetwork((20, 16, 12, 3), 2, z_flow_type="Planar", r_flow_type="Planar")
+    with pytest.raises(ValueError, match="evaluate.freeze"):
+        evaluate.ensemble_forward(mnf, x, 3, gates="mpm")
+    fz = evaluate.FrozenNetwork((20, 16, 12, 3), "lrt", "alpha")
+    for g in ("mpm", "alpha"):
+        with pytest.raises(ValueError, match="fixed by evaluate.freeze"):
+            evaluate.ensemble_forward(fz, x, 3, gates=g)
+    with pytest.raises(ValueError, match="batched"):
+        evaluate.ensemble_forward(fz, x, 3, batched=False)
+
+
+@pytest.mark.parametrize("threshold", [0.5, 0.1, 0.9])
+def test_kept_and_density_follow_kept_rows(threshold):
+    from bnn_amd import evaluate
+    dims = (20, 16, 12, 3)
+    fz = evaluate.FrozenNetwork(dims, "mnf", "mpm", threshold)
+    cut = torch.logit(torch.tensor(threshold, dtype=torch.float64)).float()
+    assert fz.cut == float(cut)
+    g = torch.Generator().manual_seed(3)
+    kept, total = [], 0
+    for i in range(3):
+        lam = torch.empty(dims[i + 1], dims[i]).uniform_(-3, 3, generator=g)
+        rows = (lam > cut).sum(1)
+        fz.kept_rows[i].copy_(rows)
+        assert fz.kept_rows[i].dtype == torch.int32 and fz.kept_rows[i].shape == (dims[i + 1],)
+        kept.append(int(rows.sum()))
+        total += lam.numel()
+    assert fz.kept == kept
+    assert isinstance(fz.density, float) and fz.density == sum(kept) / total
+    assert 0.0 < fz.density < 1.0
