@@ -128,6 +128,7 @@ class DenseGrad(ctypes.Structure):
 
 
 MAX_DENSE_T = 8
+MAX_HIDDEN = 128
 
 
 class GateBwdArgs(ctypes.Structure):
@@ -163,6 +164,12 @@ class FrozenDesc(ctypes.Structure):
                [(n, c_p) for n in ("e0", "e_w", "var_w", "bias_var", "kept_rows", "z_fwd", "e_w_members")] + \
                [("z_mstride", c_i64)] + [(n, c_i) for n in ("O", "I", "ld", "flags", "mode")] + \
                [("cut", ctypes.c_float), ("layer_id", c_u32)]
+
+
+class DenseMembers(ctypes.Structure):
+    """lbbnn_dense_members_t"""
+    _fields_ = [("q0_mean", c_p), ("q0_log_var", c_p), ("zt", ctypes.POINTER(DenseTransform)), ("T", c_i), ("I", c_i),
+                ("layer_id", c_u32), ("z_fwd", c_p), ("z_mstride", c_i64), ("mask_out", c_p)]
 
 
 class OutGradArgs(ctypes.Structure):
@@ -305,6 +312,9 @@ SIGNATURES = {
     "lbbnn_log_softmax_rows": (c_i, [c_p, c_i, c_p, c_i, c_i, c_i, c_p]),
     "lbbnn_frozen_operands": (c_i, [ctypes.POINTER(FrozenDesc), c_i, c_p]),
     "lbbnn_frozen_members": (c_i, [ctypes.POINTER(FrozenDesc), c_i, c_i, c_p, c_u64, c_p]),
+    "lbbnn_flow_dense_members_max_dim": (c_i, []),
+    "lbbnn_flow_dense_members": (c_i, [ctypes.POINTER(DenseMembers), c_i, c_i, c_p, c_u64, c_p]),
+    "lbbnn_frozen_members_dense": (c_i, [ctypes.POINTER(FrozenDesc), ctypes.POINTER(DenseMembers), c_i, c_i, c_p, c_u64, c_p]),
 }
 
 _lib = None

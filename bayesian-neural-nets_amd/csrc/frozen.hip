@@ -12,6 +12,8 @@
 //     same groups; the stores are 16-B vectors into the padded rows either way (fp32 operands only there, as K1).
 //   frozen_scale_kernel -- lbbnn_frozen_members: e_w_members[m] = operand(E0 * z_m) for every member (gridDim.y) and MNF
 //     layer in one launch: 4 B read (e0, L2-resident across members) and 4 B written per weight and member.
+//     lbbnn_frozen_members_dense is the same launch behind lbbnn_flow_dense_members (flow_dense_members.hip) instead of the
+//     planar-flow launch: the z of RNVP / MNF-type z flows.
 #include <cstdlib>
 #include "lbbnn_device.h"
 #include "lbbnn_internal.h"
@@ -245,11 +247,14 @@ extern "C" int lbbnn_frozen_operands(const lbbnn_frozen_desc_t* L, int n, void* 
     return (int)hipGetLastError();
 }
 
-extern "C" int lbbnn_frozen_members(const lbbnn_frozen_desc_t* L, int n, int members, const uint64_t* rng,
-                                    uint64_t member_advance, void* stream) {
-    if (!L) return LBBNN_E_NULL;
+// the per-member part of a frozen model: the z flows of the MNF layers (planar: d.z_flow; dense: F, lbbnn_flow_dense_members),
+// then frozen_scale_kernel
+static int frozen_members_impl(const lbbnn_frozen_desc_t* L, const lbbnn_dense_members_t* F, bool dense, int n, int members,
+                               const uint64_t* rng, uint64_t member_advance, void* stream) {
+    if (!L || (dense && !F)) return LBBNN_E_NULL;
     if (n <= 0 || n > LBBNN_MAX_LAYERS || members < 1 || members > 65535) return LBBNN_E_SHAPE;
     FlowArgs fa[LBBNN_MAX_LAYERS];
+    lbbnn_dense_members_t fd[LBBNN_MAX_LAYERS];
     ScaleBatch bt = {};
     int nf = 0, wgs = 0;
     bool one_stride = true;
@@ -257,19 +262,26 @@ extern "C" int lbbnn_frozen_members(const lbbnn_frozen_desc_t* L, int n, int mem
         const lbbnn_frozen_desc_t& d = L[i];
         if (!d.q0_mean) continue;                           // an LRT layer: its e_w is shared by every member
         if (!d.q0_log_var || !d.z_fwd || !d.e0 || !d.e_w_members) return LBBNN_E_NULL;
-        if (d.z_flow.T < 0 || d.z_flow.T > LBBNN_MAX_FLOW_T) return LBBNN_E_SHAPE;
-        for (int t = 0; t < d.z_flow.T; ++t)
-            if (!d.z_flow.u[t] || !d.z_flow.w[t] || !d.z_flow.b[t]) return LBBNN_E_NULL;
+        if (!dense) {
+            if (d.z_flow.T < 0 || d.z_flow.T > LBBNN_MAX_FLOW_T) return LBBNN_E_SHAPE;
+            for (int t = 0; t < d.z_flow.T; ++t)
+                if (!d.z_flow.u[t] || !d.z_flow.w[t] || !d.z_flow.b[t]) return LBBNN_E_NULL;
+        }
         if (!rng) return LBBNN_E_NOISE;
         if (d.O <= 0 || d.I <= 0 || d.ld < d.I || d.I > LBBNN_MAX_FLOW_DIM) return LBBNN_E_SHAPE;
         if (d.z_mstride < d.I) return LBBNN_E_SHAPE;
         if ((d.ld & 31) || (d.I & 3) || (d.z_mstride & 3)) return LBBNN_E_ALIGN;
         if (!aligned16(d.e0) || !aligned16(d.e_w_members) || !aligned16(d.z_fwd)) return LBBNN_E_ALIGN;
         if (d.flags & ~LBBNN_F_SPLIT16) return LBBNN_E_FLAGS;
-        FlowArgs& f = fa[nf];
-        f = FlowArgs{};
-        f.q0_mean = d.q0_mean; f.q0_log_var = d.q0_log_var; f.rng = rng; f.z_fwd = d.z_fwd; f.zf = d.z_flow; f.rf.T = 0;
-        f.I = d.I; f.want_kl = 0; f.layer = d.layer_id & 63u;
+        if (dense) {
+            fd[nf] = F[i];
+            fd[nf].z_fwd = d.z_fwd; fd[nf].z_mstride = d.z_mstride;
+        } else {
+            FlowArgs& f = fa[nf];
+            f = FlowArgs{};
+            f.q0_mean = d.q0_mean; f.q0_log_var = d.q0_log_var; f.rng = rng; f.z_fwd = d.z_fwd; f.zf = d.z_flow; f.rf.T = 0;
+            f.I = d.I; f.want_kl = 0; f.layer = d.layer_id & 63u;
+        }
         ScaleLayer& a = bt.l[nf];
         a.e0 = d.e0; a.z = d.z_fwd; a.e_w_members = static_cast<float*>(d.e_w_members); a.z_ms = (long long)d.z_mstride;
         a.O = d.O; a.I = d.I; a.ld = d.ld; a.split = (d.flags & LBBNN_F_SPLIT16) ? 1 : 0;
@@ -283,7 +295,10 @@ extern "C" int lbbnn_frozen_members(const lbbnn_frozen_desc_t* L, int n, int mem
     hipStream_t s = static_cast<hipStream_t>(stream);
     // one flow launch serves every layer when they share the member stride of z (a caller lays the layers' z blocks out
     // side by side in one [members][stride] buffer); else one launch per layer (n <= 4), as lbbnn_ensemble_operands
-    if (one_stride) {
+    if (dense) {
+        const int rc = lbbnn_flow_dense_members(fd, nf, members, rng, member_advance, stream);   // all layers, one launch
+        if (rc) return rc;
+    } else if (one_stride) {
         const int rc = launch_flow_planar(fa, nf, s, members, member_advance, bt.l[0].z_ms);
         if (rc) return rc;
     } else {
@@ -294,4 +309,14 @@ extern "C" int lbbnn_frozen_members(const lbbnn_frozen_desc_t* L, int n, int mem
     }
     hipLaunchKernelGGL(frozen_scale_kernel, dim3(wgs, members), dim3(kFzNT), 0, s, bt);
     return (int)hipGetLastError();
+}
+
+extern "C" int lbbnn_frozen_members(const lbbnn_frozen_desc_t* L, int n, int members, const uint64_t* rng,
+                                    uint64_t member_advance, void* stream) {
+    return frozen_members_impl(L, nullptr, false, n, members, rng, member_advance, stream);
+}
+
+extern "C" int lbbnn_frozen_members_dense(const lbbnn_frozen_desc_t* L, const lbbnn_dense_members_t* F, int n, int members,
+                                          const uint64_t* rng, uint64_t member_advance, void* stream) {
+    return frozen_members_impl(L, F, true, n, members, rng, member_advance, stream);
 }

@@ -23,6 +23,8 @@ LRT and MNF networks also have a *frozen evaluation model*, ``freeze(net, gates=
 snapshot of the GEMM operands taken once (lbbnn_frozen_operands), with the gates as trained or thresholded -- the median
 probability model of ``outofsample(net, loader, medimod=True)`` (LBBNN-GP-MF-LRT.py:295-314, LBBNN-GP-MF-MNF.py:342-366) --
 which the member GEMMs then evaluate without reading the parameters again, and which reports its own density.
+``freeze(net, gates, dense=True)`` also takes an MNF network with RNVP / MNF-type z flows (the reference's default): every
+member's z through the coupling flows is then ONE lbbnn_flow_dense_members launch for all layers and members.
 """
 import math
 from typing import Dict, List, Optional
@@ -115,6 +117,11 @@ def ensemble_forward_batched(net, data: torch.Tensor, samples: int = 10) -> torc
     net._kl_total = None
     del keep
     return h
+
+
+def _has_dense_flows(net) -> bool:
+    from . import layers as L
+    return isinstance(net, L._NetworkBase) and any(l._mnf and l._check_flows() == "dense" for l in net._layers())
 
 
 def _is_vd(net) -> bool:
@@ -240,7 +247,9 @@ def ensemble_forward(net, data: torch.Tensor, samples: int = 10, batched=None, *
     """(samples, B, classes) log-probabilities of ``samples`` stochastic forwards (net left in eval mode).
     ``batched``: None = the one-launch-per-kernel form when the network qualifies (``_batched_ok``; a baseline network on a
     HIP device: ``base_ensemble``), else the loop of fused single forwards (``net.sample_predict`` for a baseline network);
-    True / False force one of them.  Either form advances the live Philox offset by ``samples``.
+    True / False force one of them (True on an MNF network with RNVP / MNF-type z flows: ``freeze(net, "alpha",
+    dense=True).ensemble`` -- the loop's draws, results equal to rounding).  Either form advances the live Philox offset by
+    ``samples``.
     ``gates`` ("sample" or "mpm") applies to baseline networks only, ``max_members`` (members per launch of the batched form)
     to baseline and variational-dropout networks and frozen models.  A ``FrozenNetwork`` (``freeze``): its ``ensemble``.
     A variational-dropout network (``vd.BNN``): None = ``vd_ensemble`` on a
@@ -280,6 +289,10 @@ def ensemble_forward(net, data: torch.Tensor, samples: int = 10, batched=None, *
         raise ValueError("bnn_amd: max_members applies to baseline LBBNN networks only")
     if batched is None:
         batched = _batched_ok(net, data)
+    if batched and _has_dense_flows(net):
+        # RNVP / MNF-type z flows: the batched form is the frozen alpha model (same draws as the loop, equal to rounding);
+        # batched=None keeps the loop for such a network
+        return freeze(net, "alpha", dense=True).ensemble(data, samples)
     if batched:
         return ensemble_forward_batched(net, data, samples)
     outs = [net(data, sample=True) for _ in range(samples)]
@@ -398,13 +411,16 @@ class FrozenNetwork(nn.Module):
     Per layer it holds ``e0`` = weight_mu * a as plain fp32 rows, the GEMM operands ``e_w`` (of e0) and ``var_w`` (of
     sigma^2 a^2) in the format of the network's precision at freeze time (fp32, or bf16 hi | lo under any 16-bit setting: the
     member dimension of the ensemble kernels exists in that format only), ``bias_var``, a copy of ``bias_mu`` and -- MNF -- of
-    ``q0_mean``, ``q0_log_var`` and the planar z flow, and ``kept_rows``: per output row the number of weights with
+    ``q0_mean``, ``q0_log_var`` and the z flow (``flows`` = "planar": u, w, b per transform; "dense": every parameter of
+    the RNVP / MNF-type coupling networks, buffers ``zflow_<layer>_<transform>_<name>``; the r flow is not copied: evaluation
+    never runs it), and ``kept_rows``: per output row the number of weights with
     ``lambdal > logit(threshold)``.  The gate value a is alpha = sigmoid(lambdal) (``gates="alpha"``: today's evaluation
     forward) or the indicator of ``lambdal > logit(threshold)`` (``gates="mpm"``: the median probability model at the default
     threshold 0.5); the bias and z are never gated.  Nothing here follows the source network's parameters until ``refresh()``.
     """
 
-    def __init__(self, dims, family: str = "lrt", gates: str = "alpha", threshold: float = 0.5, device=None):
+    def __init__(self, dims, family: str = "lrt", gates: str = "alpha", threshold: float = 0.5, device=None,
+                 flows: Optional[str] = None):
         super().__init__()
         if gates not in FROZEN_GATES:
             raise ValueError("bnn_amd: gates must be 'alpha' (the gates as trained) or 'mpm' (the median probability model), "
@@ -415,11 +431,18 @@ class FrozenNetwork(nn.Module):
                              % (threshold,))
         if family not in ("lrt", "mnf"):
             raise ValueError("bnn_amd: family must be 'lrt' or 'mnf', got %r" % (family,))
+        flows = ("planar" if family == "mnf" else None) if flows is None else flows
+        if flows not in ((None,) if family == "lrt" else ("planar", "dense")):
+            raise ValueError("bnn_amd: flows must be 'planar' or 'dense' for an MNF model and None for an LRT model, got %r"
+                             % (flows,))
         self.dims = tuple(int(d) for d in dims)
         self.family, self.gates, self.threshold = family, gates, threshold
+        self.flows = flows              # the z flow family of an MNF model: "planar" | "dense" (RNVP / MNF type); LRT: None
         # logit(threshold) as the fp32 value the kernel compares lambdal with (exactly 0 at 0.5)
         self.cut = float(torch.tensor(math.log(threshold / (1.0 - threshold)), dtype=torch.float32))
         self.last_z = None
+        self.last_masks = None
+        self._zt, self._zflow_names = [], []   # dense flows: per layer the lbbnn_dense_transform_t array / the parameter names
         self._src = [None]              # the source network, in a list so that it is not registered as a submodule
         self._split, self._layer_ids, self._row_offsets, self._T = [], [], [], []
         self._members_ok = True
@@ -451,7 +474,8 @@ class FrozenNetwork(nn.Module):
         return sum(self.kept) / total
 
     def extra_repr(self) -> str:
-        return "dims=%s, family=%s, gates=%s, threshold=%g" % (self.dims, self.family, self.gates, self.threshold)
+        flows = ", flows=%s" % self.flows if self.flows else ""
+        return "dims=%s, family=%s%s, gates=%s, threshold=%g" % (self.dims, self.family, flows, self.gates, self.threshold)
 
     # ------------------------------------------------------------------------------------- snapshot
     def _bind(self, net):
@@ -473,13 +497,50 @@ class FrozenNetwork(nn.Module):
             if l._mnf:
                 T = len(l.z_flow.transforms)
                 self._T.append(T)
-                for name, shape in (("q0_mean", (I,)), ("q0_log_var", (I,)), ("flow_u", (T, I)), ("flow_w", (T, I)),
-                                    ("flow_b", (T, 1))):
+                vecs = [("q0_mean", (I,)), ("q0_log_var", (I,))]
+                if self.flows == "planar":
+                    vecs += [("flow_u", (T, I)), ("flow_w", (T, I)), ("flow_b", (T, 1))]
+                for name, shape in vecs:
                     self.register_buffer("%s_%d" % (name, i), _empty(shape, **f))
+                if self.flows == "dense":
+                    names = []
+                    for t, tr in enumerate(l.z_flow.transforms):
+                        names.append([k for k, _ in tr.named_parameters()])
+                        for k, p in tr.named_parameters():
+                            self.register_buffer(self._zflow_buf(i, t, k), _empty(tuple(p.shape), **f))
+                    self._zflow_names.append(names)
+                    self._zt.append(self._dense_transforms(i, l.z_flow.kind))
             else:
                 self._T.append(0)
         self.refresh()
         return self
+
+    @staticmethod
+    def _zflow_buf(i: int, t: int, name: str) -> str:
+        return "zflow_%d_%d_%s" % (i, t, name.replace(".", "_"))
+
+    def _dense_transforms(self, i: int, kind: str):
+        """lbbnn_dense_transform_t of every transform of layer i's z flow, pointing at this model's copies (built once: the
+        buffers never move)."""
+        from . import _lib
+        T = self._T[i]
+        arr = (_lib.DenseTransform * max(T, 1))()
+        for t in range(T):
+            g = lambda k: getattr(self, self._zflow_buf(i, t, k))
+            d = arr[t]
+            if kind == "RNVP":                               # flows2.py:188-219: 4-layer MLP, shift (t) and scale (s) heads
+                d.kind, d.hidden = 0, g("network.0.weight").shape[0]
+                d.w_in, d.b_in = g("network.0.weight").data_ptr(), g("network.0.bias").data_ptr()
+                for m, k in enumerate((2, 4, 6)):
+                    d.w_mid[m], d.b_mid[m] = g("network.%d.weight" % k).data_ptr(), g("network.%d.bias" % k).data_ptr()
+                a, b = "t", "s"
+            else:                                            # flows2.py:225-241: f, then the g (mu) and k (sigma) heads
+                d.kind, d.hidden = 1, g("f.weight").shape[0]
+                d.w_in, d.b_in = g("f.weight").data_ptr(), g("f.bias").data_ptr()
+                a, b = "g", "k"
+            d.w_a, d.b_a = g(a + ".weight").data_ptr(), g(a + ".bias").data_ptr()
+            d.w_b, d.b_b = g(b + ".weight").data_ptr(), g(b + ".bias").data_ptr()
+        return arr
 
     def _descs(self, src_layers=None):
         """lbbnn_frozen_desc_t of every layer; with ``src_layers`` the parameter pointers are filled too (refresh)."""
@@ -501,23 +562,26 @@ class FrozenNetwork(nn.Module):
                 d.bias_rho = l.bias_rho.data_ptr()
             if self.family == "mnf":
                 d.q0_mean, d.q0_log_var = self._buf("q0_mean", i).data_ptr(), self._buf("q0_log_var", i).data_ptr()
-                u, w, b = self._buf("flow_u", i), self._buf("flow_w", i), self._buf("flow_b", i)
-                d.z_flow.T = self._T[i]
-                for t in range(self._T[i]):
-                    d.z_flow.u[t], d.z_flow.w[t], d.z_flow.b[t] = u[t].data_ptr(), w[t].data_ptr(), b[t].data_ptr()
+                if self.flows == "planar":
+                    u, w, b = self._buf("flow_u", i), self._buf("flow_w", i), self._buf("flow_b", i)
+                    d.z_flow.T = self._T[i]
+                    for t in range(self._T[i]):
+                        d.z_flow.u[t], d.z_flow.w[t], d.z_flow.b[t] = u[t].data_ptr(), w[t].data_ptr(), b[t].data_ptr()
         return descs
 
     @torch.no_grad()
     def refresh(self):
         """Take the snapshot again from the source network's current parameters, into the same buffers: ONE
         lbbnn_frozen_operands launch for all layers, plus copies of the small vectors (bias_mu; q0 and the z flow of an MNF
-        layer).  For evaluate-every-epoch loops."""
+        layer -- the coupling networks of a dense flow ride in the same fused copy).  For evaluate-every-epoch loops."""
         from . import _lib
         net = self._src[0]
         if net is None:
             raise RuntimeError("bnn_amd: this FrozenNetwork is not bound to a network; build it with evaluate.freeze(net)")
         layers = net._layers()
-        _check_freezable_layers(layers)
+        _check_freezable_layers(layers, dense=self.flows == "dense")
+        if self.family == "mnf" and any(l._check_flows() != self.flows for l in layers):
+            raise RuntimeError("bnn_amd: the source network's flows changed family since freeze(); freeze it again")
         dev = self._buf("e0", 0).device
         if layers[0].weight_mu.device != dev:
             raise RuntimeError("bnn_amd: the source network moved from %s to %s since freeze(); freeze it again"
@@ -535,8 +599,13 @@ class FrozenNetwork(nn.Module):
                 dst += [self._buf("q0_mean", i), self._buf("q0_log_var", i)]
                 src += [l.q0_mean.detach(), l.q0_log_var.detach()]
                 for t, tr in enumerate(l.z_flow.transforms):
-                    dst += [self._buf("flow_u", i)[t], self._buf("flow_w", i)[t], self._buf("flow_b", i)[t]]
-                    src += [tr.u.detach().reshape(-1), tr.w.detach().reshape(-1), tr.bias.detach().reshape(-1)]
+                    if self.flows == "dense":
+                        ps = dict(tr.named_parameters())
+                        for k in self._zflow_names[i][t]:
+                            dst.append(getattr(self, self._zflow_buf(i, t, k))); src.append(ps[k].detach())
+                    else:
+                        dst += [self._buf("flow_u", i)[t], self._buf("flow_w", i)[t], self._buf("flow_b", i)[t]]
+                        src += [tr.u.detach().reshape(-1), tr.w.detach().reshape(-1), tr.bias.detach().reshape(-1)]
         torch._foreach_copy_(dst, src)                       # the small vectors of every layer in one fused copy
         descs = self._descs(layers)
         with torch.cuda.device(dev):
@@ -576,8 +645,9 @@ class FrozenNetwork(nn.Module):
             self._mcap = c
         return self._zbuf, self._ewm
 
-    def _draw_members(self, c: int, rng, stream):
-        """MNF: member m's z at Philox offset rng[1] + m and its mean operand E0 * z_m (lbbnn_frozen_members)."""
+    def _draw_members(self, c: int, rng, stream, masks=None):
+        """MNF: member m's z at Philox offset rng[1] + m and its mean operand E0 * z_m (lbbnn_frozen_members; dense flows:
+        lbbnn_frozen_members_dense, with ``masks`` a list that receives per layer the (c, T, I) masks the members used)."""
         from . import _lib
         zbuf, ewm = self._member_buffers(c)
         descs = self._descs()
@@ -587,6 +657,21 @@ class FrozenNetwork(nn.Module):
             descs[i].z_mstride = zbuf.stride(0)
             descs[i].e_w_members = ewm[i].data_ptr()
             off += ops.operand_ld(self.dims[i])
+        if self.flows == "dense":
+            import ctypes
+            fl = (_lib.DenseMembers * self.n_layers)()
+            for i in range(self.n_layers):
+                d = fl[i]
+                d.q0_mean, d.q0_log_var = descs[i].q0_mean, descs[i].q0_log_var
+                d.zt = ctypes.cast(self._zt[i], ctypes.POINTER(_lib.DenseTransform))
+                d.T, d.I, d.layer_id = self._T[i], self.dims[i], self._layer_ids[i]
+                d.z_fwd, d.z_mstride = descs[i].z_fwd, descs[i].z_mstride
+                if masks is not None:
+                    masks.append(_empty((c, self._T[i], self.dims[i]), dtype=torch.float32, device=zbuf.device))
+                    d.mask_out = masks[-1].data_ptr()
+            _lib.check(_lib.lib().lbbnn_frozen_members_dense(descs, fl, self.n_layers, c, rng.data_ptr(), 1, stream),
+                       "lbbnn_frozen_members_dense")
+            return zbuf, ewm
         _lib.check(_lib.lib().lbbnn_frozen_members(descs, self.n_layers, c, rng.data_ptr(), 1, stream), "lbbnn_frozen_members")
         return zbuf, ewm
 
@@ -597,7 +682,7 @@ class FrozenNetwork(nn.Module):
             off += ops.operand_ld(self.dims[i])
         return out
 
-    def _chunk(self, x, c: int, st, head, zs):
+    def _chunk(self, x, c: int, st, head, zs, ms=None):
         """Members live .. live + c - 1 of the ensemble into head (c, pad4(B * classes)): MNF 2 launches for z and the member
         operands, then one lbbnn_lrt_gemm_members launch per layer."""
         from . import _lib
@@ -606,9 +691,12 @@ class FrozenNetwork(nn.Module):
         stream = torch.cuda.current_stream(dev).cuda_stream
         mnf = self.family == "mnf"
         if mnf:
-            zbuf, ewm = self._draw_members(c, rng, stream)
+            masks = [] if ms is not None else None
+            zbuf, ewm = self._draw_members(c, rng, stream, masks)
             if zs is not None:
                 zs.append(self._z_of(zbuf, c))
+            if ms is not None:
+                ms.append(masks)
         h, h_ms = x, 0                                       # the first layer reads the same rows for every member
         for i in range(n):
             O, I = self.dims[i + 1], self.dims[i]
@@ -642,13 +730,14 @@ class FrozenNetwork(nn.Module):
 
     @torch.no_grad()
     def ensemble(self, data: torch.Tensor, samples: int = 10, *, max_members: Optional[int] = None,
-                 keep_z: bool = False) -> torch.Tensor:
+                 keep_z: bool = False, keep_masks: bool = False) -> torch.Tensor:
         """(samples, B, classes) log-probabilities of ``samples`` stochastic forwards of the frozen model.  Member m draws where
         the m-th member of ``ensemble_forward_batched`` draws: eps of layer i from stream STREAM_EPS_OUT * 64 + layer id with the
         layer's row_offset at Philox offset live + m, z of an MNF layer from its q0 and z flow at the same offset.  The live
         offset advances by ``samples``.  ``max_members``: members per launch (default: all); chunked and unchunked results are
         the same bits.  ``keep_z``: ``self.last_z`` = per layer the (samples, in_features) z every member used (None entries for
-        an LRT model).  An LRT model with a layer the member GEMM does not take (in_features % 4 != 0 or an operand row wider
+        an LRT model).  ``keep_masks`` (dense flows): ``self.last_masks`` = per layer the (samples, T, in_features) Bernoulli
+        masks of the coupling transforms every member used (None for any other model).  An LRT model with a layer the member GEMM does not take (in_features % 4 != 0 or an operand row wider
         than 2048) runs every member as a chain of single GEMM calls on the frozen operands instead -- same draws, same shape."""
         S = int(samples)
         if S < 1:
@@ -659,10 +748,21 @@ class FrozenNetwork(nn.Module):
         x = self._input(data)
         B, C, dev = x.shape[0], self.dims[-1], x.device
         st = ops.RngState.get(dev)
-        self.last_z = None
+        self.last_z = self.last_masks = None
         with torch.cuda.device(dev):
             if B == 0:
-                st.advance(S)
+                if self.flows == "dense" and (keep_z or keep_masks):   # no rows to evaluate, but the members' draws exist
+                    zs, ms = [], []
+                    stream = torch.cuda.current_stream(dev).cuda_stream
+                    for m0 in range(0, S, chunk):
+                        c = min(chunk, S - m0)
+                        ms.append([])
+                        zs.append(self._z_of(self._draw_members(c, st.t, stream, ms[-1])[0], c))
+                        st.advance(c)
+                    self.last_z = [torch.cat(parts) for parts in zip(*zs)] if keep_z else None
+                    self.last_masks = [torch.cat(parts) for parts in zip(*ms)] if keep_masks else None
+                else:
+                    st.advance(S)
                 return torch.zeros((S, 0, C), dtype=torch.float32, device=dev)
             if not self._members_ok:                         # (LRT only: freeze refuses such an MNF network)
                 outs = []
@@ -674,9 +774,12 @@ class FrozenNetwork(nn.Module):
                 return torch.stack(outs)
             head = _empty((S, _pad4(B * C)), dtype=torch.float32, device=dev)
             zs = [] if (keep_z and self.family == "mnf") else None
+            ms = [] if (keep_masks and self.flows == "dense") else None
             for m0 in range(0, S, chunk):
                 c = min(chunk, S - m0)
-                self._chunk(x, c, st, head[m0:m0 + c], zs)
+                self._chunk(x, c, st, head[m0:m0 + c], zs, ms)
+        if ms is not None:
+            self.last_masks = [torch.cat(parts) for parts in zip(*ms)]
         if keep_z:
             self.last_z = [torch.cat(parts) for parts in zip(*zs)] if zs is not None else [None] * self.n_layers
         outputs = head[:, :B * C].view(S, B, C)
@@ -701,7 +804,7 @@ class FrozenNetwork(nn.Module):
             return self._chain(x, st, [self._buf("e_w", i) for i in range(self.n_layers)], False)
 
 
-def _check_freezable_layers(layers):
+def _check_freezable_layers(layers, dense: bool = False):
     from . import _lib
     if len(layers) > _lib.MAX_LAYERS:
         raise ValueError("bnn_amd: freeze takes networks of at most %d layers" % _lib.MAX_LAYERS)
@@ -712,7 +815,28 @@ def _check_freezable_layers(layers):
         if getattr(l, "as_written", False):
             raise ValueError("bnn_amd: layer %d has as_written set; a frozen model implements the corrected forward only -- "
                              "evaluate such a network with ensemble_forward(net, data, samples, batched=False)" % (i + 1))
-        if l._mnf:
+        if l._mnf and dense and l._check_flows() == "dense":
+            I, T = l.in_features, len(l.z_flow.transforms)
+            loop = "evaluate this network with the loop form, ensemble_forward(net, data, samples)"
+            if any(ll._mnf and ll._check_flows() != "dense" for ll in layers):
+                raise ValueError("bnn_amd: layer %d has dense z flows, another layer has not; a frozen model takes one flow "
+                                 "family for all layers; %s" % (i + 1, loop))
+            if I % 4:
+                raise ValueError("bnn_amd: layer %d: a frozen model with dense z flows needs in_features %% 4 == 0 "
+                                 "(in_features = %d); %s" % (i + 1, I, loop))
+            lim = int(_lib.lib().lbbnn_flow_dense_members_max_dim())
+            if I > lim:
+                raise ValueError("bnn_amd: layer %d: in_features = %d is beyond what the member kernel of the dense z flows holds "
+                                 "in LDS (%d); %s" % (i + 1, I, lim, loop))
+            if T > _lib.MAX_DENSE_T:
+                raise ValueError("bnn_amd: layer %d: z_flow has %d transforms, the member kernel of the dense z flows takes at "
+                                 "most %d; %s" % (i + 1, T, _lib.MAX_DENSE_T, loop))
+            hidden = max([p.shape[0] for tr in l.z_flow.transforms for k, p in tr.named_parameters()
+                          if k in ("network.0.weight", "f.weight")] or [1])
+            if hidden > _lib.MAX_HIDDEN:
+                raise ValueError("bnn_amd: layer %d: the coupling networks of z_flow have %d hidden units, the member kernel takes "
+                                 "at most %d; %s" % (i + 1, hidden, _lib.MAX_HIDDEN, loop))
+        elif l._mnf:
             if l._check_flows() != "planar" or len(l.z_flow.transforms) > 4:
                 raise ValueError("bnn_amd: layer %d: a frozen MNF model needs planar flows with at most 4 transforms (it has "
                                  "z_flow=%s with %d); evaluate this network with ensemble_forward(net, data, samples)"
@@ -723,7 +847,7 @@ def _check_freezable_layers(layers):
                                  % (i + 1, l.in_features))
 
 
-def freeze(net, gates: str = "alpha", *, threshold: float = 0.5) -> FrozenNetwork:
+def freeze(net, gates: str = "alpha", *, threshold: float = 0.5, dense: bool = False) -> FrozenNetwork:
     """Frozen evaluation model of an LRT / MNF network (``lrt.BayesianNetwork``, ``mnf.BayesianNetwork``) on a HIP device.
 
     ``gates="alpha"``: the gates as trained, a = sigmoid(lambdal) -- ``frozen.ensemble(x, S)`` computes what
@@ -731,7 +855,19 @@ def freeze(net, gates: str = "alpha", *, threshold: float = 0.5) -> FrozenNetwor
     ``outofsample(net, loader, medimod=True)``: a weight is kept (a = 1) iff ``lambdal > logit(threshold)``, compared in fp32;
     at the default threshold 0.5 that is ``alpha > 0.5``, which an fp32 ``sigmoid(lambdal) > 0.5`` matches except for
     0 < lambdal < ~6e-8 (alpha rounds to exactly 0.5 there; the frozen model keeps those weights).  The operand format is the
-    network's precision at this moment ("fp32" -> fp32 operands, any 16-bit setting -> bf16 hi | lo)."""
+    network's precision at this moment ("fp32" -> fp32 operands, any 16-bit setting -> bf16 hi | lo).
+
+    ``dense=True`` also accepts an MNF network whose z flows are dense coupling flows (RNVP / MNF type: the reference's
+    default, LBBNN-GP-MF-MNF.py:46-47), with ``in_features % 4 == 0``, ``in_features`` within
+    ``lbbnn_flow_dense_members_max_dim()`` (1408), at most 8 transforms, and no ``noise`` / ``as_written``; the model then also
+    carries a snapshot of the coupling networks of every z flow, and every member's z is one lbbnn_flow_dense_members launch for
+    all layers and members.  The keyword is opt-in because the promise above is weaker there: member m has the SAME DRAWS
+    (eps_z, the Bernoulli masks, eps_out) as the m-th forward of the loop, but the member kernel sums the coupling networks'
+    affine steps on the matrix cores in another order than the single forward's GEMVs, so the outputs are EQUAL TO FP32
+    ROUNDING, not bit for bit.  The loop draws its masks from torch's generator when LBBNN_TORCH_MASKS=1 is set; a frozen
+    model always draws them in the kernel (Philox stream LBBNN_STREAM_MASK).  A planar or LRT network with ``dense=True``
+    takes the path, and gives the bits, of ``dense=False``.  Each refusal is a ValueError that names the layer; the loop form
+    ``ensemble_forward(net, data, samples)`` takes every network."""
     from . import layers as L
     if gates not in FROZEN_GATES:
         raise ValueError("bnn_amd: gates must be 'alpha' (the gates as trained) or 'mpm' (the median probability model), got %r"
@@ -748,11 +884,12 @@ def freeze(net, gates: str = "alpha", *, threshold: float = 0.5) -> FrozenNetwor
     if not isinstance(net, L._NetworkBase):
         raise TypeError("bnn_amd: freeze takes an lrt.BayesianNetwork or mnf.BayesianNetwork, got %s" % type(net).__name__)
     layers = net._layers()
-    _check_freezable_layers(layers)
+    _check_freezable_layers(layers, dense=bool(dense))
     if not layers[0].weight_mu.is_cuda:
         raise RuntimeError("bnn_amd: freeze needs the network on a HIP device (it is on %s); there is no CPU path"
                            % layers[0].weight_mu.device)
     family = "mnf" if layers[0]._mnf else "lrt"
-    fz = FrozenNetwork(net.dims, family, gates, threshold, device=layers[0].weight_mu.device)
+    flows = layers[0]._check_flows() if family == "mnf" else None          # "planar" | "dense" (checked above)
+    fz = FrozenNetwork(net.dims, family, gates, threshold, device=layers[0].weight_mu.device, flows=flows)
     fz.eval()
     return fz._bind(net)

@@ -7,7 +7,8 @@ labels stands in for the loaders.
 
     python examples/train_mnf_synthetic.py            # eager loop, the reference's default RNVP flows
     GRAPH=1 python examples/train_mnf_synthetic.py    # the same step captured once in a HIP graph and replayed
-    FLOWS=Planar python examples/train_mnf_synthetic.py   # planar flows; ends with the median probability model (frozen)
+    FLOWS=Planar python examples/train_mnf_synthetic.py   # planar flows
+Either way it ends with the median probability model (a frozen snapshot, evaluate.freeze).
 """
 import os
 import sys
@@ -67,13 +68,14 @@ print("density %.3f | posterior mean %.3f | ensemble %.3f" % (float(res["density
 
 # the median probability model of outofsample(net, loader, medimod=True) (LBBNN-GP-MF-MNF.py:342-366): keep a weight iff its
 # inclusion probability exceeds 0.5 -- a frozen snapshot of the trained network, evaluated without touching the parameters
-# again.  (A frozen MNF model draws z through planar flows; with the default RNVP flows this step is left out.)
-if FLOWS == "Planar":
-    mpm = bnn_amd.evaluate.freeze(net, gates="mpm")
+# again.  dense=True also takes the default RNVP / MNF-type z flows (every member's z in one lbbnn_flow_dense_members launch;
+# members have the loop's draws and equal it to fp32 rounding); a planar network takes the same path with or without it.
+if FLOWS in ("Planar", "RNVP", "MNF"):
+    mpm = bnn_amd.evaluate.freeze(net, gates="mpm", dense=True)
     res = ensemble_eval(mpm, test_x, test_y, samples=TEST_SAMPLES)
     print("median probability model: density %.3f (kept per layer %s) | posterior mean %.3f | ensemble %.3f | mean predictive "
           "entropy %.3f" % (mpm.density, mpm.kept, res["correct_posterior_mean"] / BATCH_SIZE,
                             res["correct_ensemble"] / BATCH_SIZE,
                             float(bnn_amd.evaluate.predictive_entropy(res["outputs"]).mean())))
 else:
-    print("median probability model: run with FLOWS=Planar (evaluate.freeze takes planar z flows)")
+    print("median probability model: evaluate.freeze takes planar, RNVP and MNF-type z flows (FLOWS=%s)" % FLOWS)

@@ -587,6 +587,52 @@ int lbbnn_frozen_members(const lbbnn_frozen_desc_t* layers, int n, int members, 
                          uint64_t member_advance, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * K4m  lbbnn_flow_dense_members -- z of every member of an evaluation ensemble through the DENSE coupling z flows (RNVP /
+ * MNF type, flows2.py:188-241; the reference's default Z_FLOW_TYPE, LBBNN-GP-MF-MNF.py:46) of up to LBBNN_MAX_LAYERS MNF
+ * layers in ONE launch, whatever the member count: grid = (ceil(members / 16), n), one workgroup carries 16 members of one
+ * layer through the whole chain with z resident in LDS, the affine steps on v_mfma_f32_16x16x4_f32 (exact fp32) with the
+ * members as the 16 columns, so every coupling matrix is read once per 16 members.
+ *
+ * Draw contract: member m is the forward-draw z of the single forward (lbbnn_layers_dense_flows with draw_masks = 1, no
+ * explicit eps) at Philox state {seed, off} = {rng[0], rng[1] + m * member_advance}, with lid = layer_id & 63:
+ *   eps_i = philox_normal4(seed, off, LBBNN_STREAM_EPS_Z * 64 + lid, counter (i / 4, 0))[i % 4]
+ *   z0_i  = q0_mean_i + sqrtf(expf(q0_log_var_i)) * eps_i                       (LBBNN-GP-MF-MNF.py:183-185)
+ *   mask of transform t at element i = bit t of word 0 of philox_bits4(seed, off, LBBNN_STREAM_MASK * 64 + lid, counter (i, 0))
+ *   (words 1 / 2 are the KL branch's and the r flow's masks: evaluation draws neither), then the T transforms of
+ *   flows2.py:206-219 (RNVP) / :233-241 (MNF type).  Same draws as the single forward; the sums of the affine steps run on
+ *   the matrix cores in another order than its GEMVs, so z is equal to fp32 rounding, not bit for bit.  A member's z does
+ *   not depend on `members` or on its position (chunks of an ensemble give the same bits as one call).
+ * Only z is written (z_fwd + m * z_mstride, I floats); no log-determinant (evaluation draws no KL, ...MNF.py:208).
+ * mask_out: NULL, or [members][T][I] floats in {0,1}: the masks used.  zt: T transforms of ONE kind; their mask_fwd /
+ * mask_kl fields are ignored.
+ * Checks, before any launch: NULL layers / q0_mean / q0_log_var / z_fwd / zt / a transform's matrices: LBBNN_E_NULL;
+ * rng == NULL: LBBNN_E_NOISE; 1 <= n <= LBBNN_MAX_LAYERS, 1 <= members <= 65535, 0 <= T <= LBBNN_MAX_DENSE_T,
+ * 1 <= I <= lbbnn_flow_dense_members_max_dim() (LDS: 1.25 KiB per 16 elements of z -- the z image and one byte of mask bits
+ * per element and member -- plus 49 KiB for the hidden matrices and partials, within 160 KiB), 1 <= hidden <=
+ * LBBNN_MAX_HIDDEN, z_mstride >= I, a kind other than LBBNN_FLOW_RNVP / LBBNN_FLOW_MNF or kinds mixed within a layer:
+ * LBBNN_E_SHAPE; I % 4, z_mstride % 4, z_fwd off a 16-B boundary: LBBNN_E_ALIGN.
+ *
+ * lbbnn_frozen_members_dense: lbbnn_frozen_members for a frozen model whose MNF layers have dense z flows: F[i] describes
+ *   the z flow of layers[i] (entries of LRT layers, q0_mean == NULL in layers[i], are not read); z_fwd and z_mstride are
+ *   taken from layers[i], whose z_flow field is ignored.  One lbbnn_flow_dense_members launch for all MNF layers, then the
+ *   launch of lbbnn_frozen_members that writes e_w_members + m * O * ld = operand(E0 * z_m).  The checks of both. */
+typedef struct lbbnn_dense_members {
+    const float *q0_mean, *q0_log_var;               /* (I)                                                    */
+    const lbbnn_dense_transform_t* zt;               /* T transforms (host array); mask_fwd / mask_kl ignored  */
+    int T, I;
+    uint32_t layer_id;
+    float* z_fwd;                                    /* member m's z at z_fwd + m * z_mstride                  */
+    int64_t z_mstride;                               /* floats                                                 */
+    float* mask_out;                                 /* NULL, or [members][T][I]                               */
+} lbbnn_dense_members_t;
+
+int lbbnn_flow_dense_members_max_dim(void);
+int lbbnn_flow_dense_members(const lbbnn_dense_members_t* layers, int n, int members, const uint64_t* rng,
+                             uint64_t member_advance, void* stream);
+int lbbnn_frozen_members_dense(const lbbnn_frozen_desc_t* layers, const lbbnn_dense_members_t* flows, int n, int members,
+                               const uint64_t* rng, uint64_t member_advance, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K7  lbbnn_vd_operands -- Gaussian variational-dropout layer (variational_dropout.py:55-68).
  *   phi = x.theta ; delta = (x^2).(theta^2) * alpha ; out = phi + sqrt(delta)*zeta        :64-67
  * theta is (I,O) row-major (NN layout).  This pass writes the GEMM operands theta^T and (theta^2)^T as
