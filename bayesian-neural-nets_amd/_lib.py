@@ -109,6 +109,25 @@ class AdamList(ctypes.Structure):
                 ("v", c_p * ADAM_MAX_TENSORS), ("numel", c_i64 * ADAM_MAX_TENSORS), ("n", c_i)]
 
 
+ADAM_GROUPS_MAX_TENSORS = 64
+ADAM_CHUNK = 4096                      # LBBNN_ADAM_CHUNK: elements per workgroup of the list kernels = per partial of lbbnn_grad_sumsq
+ADAM_F_DECOUPLED = 0x1
+ADAM_F_INACTIVE = 0x2
+
+
+class AdamHyper(ctypes.Structure):
+    """lbbnn_adam_hyper_t: one row of the device table (6 x 4 bytes)"""
+    _fields_ = [("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
+                ("weight_decay", ctypes.c_float), ("flags", c_u32)]
+
+
+class AdamGroupList(ctypes.Structure):
+    """lbbnn_adam_group_list_t"""
+    _fields_ = [("p", c_p * ADAM_GROUPS_MAX_TENSORS), ("g", c_p * ADAM_GROUPS_MAX_TENSORS), ("m", c_p * ADAM_GROUPS_MAX_TENSORS),
+                ("v", c_p * ADAM_GROUPS_MAX_TENSORS), ("mask", c_p * ADAM_GROUPS_MAX_TENSORS),
+                ("numel", c_i64 * ADAM_GROUPS_MAX_TENSORS), ("group", c_i * ADAM_GROUPS_MAX_TENSORS), ("n", c_i)]
+
+
 class CopyList(ctypes.Structure):
     """lbbnn_copy_list_t"""
     _fields_ = [("dst", c_p * ADAM_MAX_TENSORS), ("src", c_p * ADAM_MAX_TENSORS), ("numel", c_i64 * ADAM_MAX_TENSORS), ("n", c_i)]
@@ -252,6 +271,9 @@ SIGNATURES = {
     "lbbnn_multi_copy": (c_i, [ctypes.POINTER(CopyList), c_p]),
     "lbbnn_adam_step": (c_i, [ctypes.POINTER(AdamList), ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                               ctypes.c_float, c_p, c_i, c_p]),
+    "lbbnn_adam_step_groups": (c_i, [ctypes.POINTER(AdamGroupList), c_p, c_p, c_i, c_p, c_p, c_i, c_p]),
+    "lbbnn_grad_sumsq_workspace": (c_i64, [c_i64]),
+    "lbbnn_grad_sumsq": (c_i, [ctypes.POINTER(AdamGroupList), c_p, c_i64, c_i64, ctypes.c_float, c_p, c_p, c_p]),
     "lbbnn_matmul_splitk": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     "lbbnn_lrt_gemm_combine": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     "lbbnn_dx_combine": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p]),

@@ -1,9 +1,12 @@
 // lbbnn_adam_step: multi-tensor Adam in one launch (see include/lbbnn.h).  HBM-bound elementwise: 16 B read + 12 B
 // written per parameter.  Workgroup -> (tensor, 4096-element chunk) by a binary search over the per-tensor chunk
 // prefix held in the kernel arguments (read through the kernarg pointer: scalar loads, no scratch copy).
+// lbbnn_adam_step_groups: the same pass for the tensors of any number of parameter groups, hyper-parameters and step counters
+// read from device tables; lbbnn_grad_sumsq: the global gradient norm for clipping, fixed-order sums.
 #include <cmath>
 #include "lbbnn_device.h"
 #include "lbbnn_internal.h"
+#include "reduce_partials.h"
 
 namespace {
 
@@ -68,6 +71,159 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamKArgs ka) {
 
 __global__ void adam_advance_kernel(float* step) { step[0] += 1.f; }
 
+// ---- lbbnn_adam_step_groups / lbbnn_grad_sumsq: the list kernels with per-group hyper-parameters read from device memory ----
+static_assert(CHUNK == LBBNN_ADAM_CHUNK, "include/lbbnn.h documents the chunk size");
+
+struct GroupsKArgs {
+    lbbnn_adam_group_list_t l;
+    int first[LBBNN_ADAM_GROUPS_MAX_TENSORS + 1];     // first workgroup of tensor i; first[n] = number of updating workgroups
+    const lbbnn_adam_hyper_t* hyper;
+    float* step;
+    const float* grad_scale;
+    unsigned* ticket;
+    int n_groups, advance;
+};
+static_assert(sizeof(GroupsKArgs) <= 4096, "kernel-argument segment");
+
+__global__ __launch_bounds__(256) void adam_groups_kernel(const GroupsKArgs ka) {
+    const LBBNN_CONST_AS GroupsKArgs& a = *kernarg_as<GroupsKArgs>();
+    const int blk = blockIdx.x;
+    if (blk < a.first[a.l.n]) {                               // (an advance-only launch has one workgroup and no tensor)
+        int lo = 0, hi = a.l.n;                               // largest i with first[i] <= blk
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (a.first[mid] <= blk) lo = mid; else hi = mid; }
+        const int ti = lo;
+        float* __restrict__ p = a.l.p[ti];
+        const float* __restrict__ g = a.l.g[ti];
+        float* __restrict__ m = a.l.m[ti];
+        float* __restrict__ v = a.l.v[ti];
+        const float* __restrict__ mk = a.l.mask[ti];
+        const int64_t n = a.l.numel[ti];
+        const int64_t base = (int64_t)(blk - a.first[ti]) * CHUNK;
+        const int gi = a.l.group[ti];
+        const lbbnn_adam_hyper_t h = a.hyper[gi];
+        const float t = a.step[gi] + 1.f;
+        const float bc1 = 1.f - powf(h.beta1, t), bc2s = sqrtf(1.f - powf(h.beta2, t));
+        const bool decoupled = (h.flags & LBBNN_ADAM_F_DECOUPLED) != 0;
+        const float step_size = h.lr / bc1, b1 = h.beta1, b2 = h.beta2, eps = h.eps, wd = decoupled ? 0.f : h.weight_decay;
+        const float shrink = 1.f - h.lr * h.weight_decay;
+        const bool scaled = a.grad_scale != nullptr;
+        const float gscale = scaled ? a.grad_scale[0] : 1.f;
+        const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                           reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(mk)) & 15u) == 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int64_t i = base + (int64_t)(threadIdx.x + 256 * k) * 4;
+            if (i >= n) break;
+            float pp[4], gg[4], mm[4], vv[4];
+            const int cnt = (int)((n - i) < 4 ? (n - i) : 4);
+            if (vec && cnt == 4) {
+                const float4 a0 = *reinterpret_cast<const float4*>(p + i), a1 = *reinterpret_cast<const float4*>(g + i);
+                const float4 a2 = *reinterpret_cast<const float4*>(m + i), a3 = *reinterpret_cast<const float4*>(v + i);
+                pp[0] = a0.x; pp[1] = a0.y; pp[2] = a0.z; pp[3] = a0.w;  gg[0] = a1.x; gg[1] = a1.y; gg[2] = a1.z; gg[3] = a1.w;
+                mm[0] = a2.x; mm[1] = a2.y; mm[2] = a2.z; mm[3] = a2.w;  vv[0] = a3.x; vv[1] = a3.y; vv[2] = a3.z; vv[3] = a3.w;
+                if (mk) { const float4 a4 = *reinterpret_cast<const float4*>(mk + i); gg[0] *= a4.x; gg[1] *= a4.y; gg[2] *= a4.z; gg[3] *= a4.w; }
+            } else {
+                for (int q = 0; q < 4; ++q) {
+                    const bool in = q < cnt;
+                    pp[q] = in ? p[i + q] : 0.f; gg[q] = in ? g[i + q] : 0.f; mm[q] = in ? m[i + q] : 0.f; vv[q] = in ? v[i + q] : 0.f;
+                    if (mk && in) gg[q] *= mk[i + q];
+                }
+            }
+            if (scaled) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) gg[q] *= gscale;
+            }
+            if (decoupled) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) pp[q] *= shrink;
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {                     // adam_kernel's update, expression for expression
+                const float gq = gg[q] + wd * pp[q];
+                mm[q] = b1 * mm[q] + (1.f - b1) * gq;
+                vv[q] = b2 * vv[q] + (1.f - b2) * gq * gq;
+                const float denom = sqrtf(vv[q]) / bc2s + eps;
+                pp[q] = pp[q] - step_size * (mm[q] / denom);
+            }
+            if (vec && cnt == 4) {
+                *reinterpret_cast<float4*>(p + i) = make_float4(pp[0], pp[1], pp[2], pp[3]);
+                *reinterpret_cast<float4*>(m + i) = make_float4(mm[0], mm[1], mm[2], mm[3]);
+                *reinterpret_cast<float4*>(v + i) = make_float4(vv[0], vv[1], vv[2], vv[3]);
+            } else {
+                for (int q = 0; q < cnt; ++q) { p[i + q] = pp[q]; m[i + q] = mm[q]; v[i + q] = vv[q]; }
+            }
+        }
+    }
+    if (!a.advance) return;
+    // The counters advance in this launch.  Every wave reaches this barrier only after its last use of step[gi] (a value that
+    // was used has been returned by its load), thread 0 draws the workgroup's ticket after the barrier, and only the holder of
+    // the last ticket -- drawn after every other workgroup's barrier -- writes the counters: no workgroup can read an
+    // advanced one.  The next launch reads them across a kernel boundary.
+    __shared__ int last;
+    __syncthreads();
+    if (threadIdx.x == 0) last = atomicAdd(a.ticket, 1u) == gridDim.x - 1 ? 1 : 0;
+    __syncthreads();
+    if (!last) return;
+    for (int gq = threadIdx.x; gq < a.n_groups; gq += 256)
+        if (!(a.hyper[gq].flags & LBBNN_ADAM_F_INACTIVE)) a.step[gq] += 1.f;
+    if (threadIdx.x == 0) atomicExch(a.ticket, 0u);
+}
+
+struct SumsqKArgs {
+    lbbnn_adam_group_list_t l;
+    int first[LBBNN_ADAM_GROUPS_MAX_TENSORS + 1];
+    float* work;                                              // already offset to this list's first partial
+    int pad;                                                  // zeros written after the last partial (to a multiple of 64 overall)
+};
+static_assert(sizeof(SumsqKArgs) <= 4096, "kernel-argument segment");
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const SumsqKArgs ka) {
+    const LBBNN_CONST_AS SumsqKArgs& a = *kernarg_as<SumsqKArgs>();
+    __shared__ float scratch[4];
+    const int blk = blockIdx.x;
+    int lo = 0, hi = a.l.n;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (a.first[mid] <= blk) lo = mid; else hi = mid; }
+    const float* __restrict__ g = a.l.g[lo];
+    const float* __restrict__ mk = a.l.mask[lo];
+    const int64_t n = a.l.numel[lo], base = (int64_t)(blk - a.first[lo]) * CHUNK;
+    const bool vec = ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(mk)) & 15u) == 0;
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int64_t i = base + (int64_t)(threadIdx.x + 256 * k) * 4;
+        if (i >= n) break;
+        float gg[4] = {0.f, 0.f, 0.f, 0.f};
+        if (vec && i + 4 <= n) {
+            const float4 a1 = *reinterpret_cast<const float4*>(g + i);
+            gg[0] = a1.x; gg[1] = a1.y; gg[2] = a1.z; gg[3] = a1.w;
+            if (mk) { const float4 a4 = *reinterpret_cast<const float4*>(mk + i); gg[0] *= a4.x; gg[1] *= a4.y; gg[2] *= a4.z; gg[3] *= a4.w; }
+        } else {
+            for (int q = 0; q < 4 && i + q < n; ++q) gg[q] = mk ? g[i + q] * mk[i + q] : g[i + q];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s += gg[q] * gg[q];
+    }
+    s = block_sum<float, 4>(s, scratch);
+    if (threadIdx.x == 0) a.work[blk] = s;
+    if (blk == (int)gridDim.x - 1 && (int)threadIdx.x < a.pad) a.work[gridDim.x + threadIdx.x] = 0.f;
+}
+
+// work: rows x 64 partials (zero padded); cols = 64 floats behind them
+__global__ __launch_bounds__(1024) void grad_norm_finalize_kernel(float* work, int rows, float max_norm, float* norm, float* grad_scale) {
+    __shared__ float part[3][16][64];
+    float* cols = work + (size_t)rows * 64;
+    float* const out[3] = {cols, nullptr, nullptr};
+    reduce_partials_body(work, 64, 0, rows, 64, 1, out, 0, part);
+    if (threadIdx.x < 64) {                                   // the lanes of wave 0 wrote cols[lane] themselves
+        const float ss = wave_sum(cols[threadIdx.x]);
+        if (threadIdx.x == 0) {
+            const float nrm = sqrtf(ss), c = max_norm / (nrm + 1e-6f);
+            norm[0] = nrm;
+            grad_scale[0] = c > 1.f ? 1.f : c;                // (a NaN norm compares false and stays NaN, as torch.clamp keeps it)
+        }
+    }
+}
+
 struct CopyKArgs { lbbnn_copy_list_t l; int first[LBBNN_ADAM_MAX_TENSORS + 1]; };
 
 __global__ __launch_bounds__(256) void multi_copy_kernel(const CopyKArgs ka) {
@@ -113,6 +269,65 @@ extern "C" int lbbnn_adam_step(const lbbnn_adam_list_t* list, float lr, float be
         hipLaunchKernelGGL(adam_kernel, dim3(nb), dim3(256), 0, s, ka);
     }
     if (advance) hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, s, step);
+    return (int)hipGetLastError();
+}
+
+// list checks shared by the two list entry points: 0, or the LBBNN_E_* code; fills first[] and the workgroup count
+static int groups_list_blocks(const lbbnn_adam_group_list_t* list, bool update, int n_groups, int* first, int64_t* blocks) {
+    if (list->n < 0 || list->n > LBBNN_ADAM_GROUPS_MAX_TENSORS) return LBBNN_E_SHAPE;
+    int64_t nb = 0;
+    for (int i = 0; i < list->n; ++i) {
+        if (!list->g[i] || (update && (!list->p[i] || !list->m[i] || !list->v[i]))) return LBBNN_E_NULL;
+        if (list->numel[i] <= 0 || (update && (list->group[i] < 0 || list->group[i] >= n_groups))) return LBBNN_E_SHAPE;
+        first[i] = (int)nb;
+        nb += (list->numel[i] + CHUNK - 1) / CHUNK;
+        if (nb > 0x7fffffff) return LBBNN_E_SHAPE;
+    }
+    for (int i = list->n; i <= LBBNN_ADAM_GROUPS_MAX_TENSORS; ++i) first[i] = (int)nb;
+    *blocks = nb;
+    return 0;
+}
+
+extern "C" int lbbnn_adam_step_groups(const lbbnn_adam_group_list_t* list, const lbbnn_adam_hyper_t* hyper, float* step,
+                                      int n_groups, const float* grad_scale, uint32_t* ticket, int advance, void* stream) {
+    if (!list || !hyper || !step || (advance && !ticket)) return LBBNN_E_NULL;
+    if (n_groups < 1 || n_groups > 65536) return LBBNN_E_SHAPE;
+    GroupsKArgs ka;
+    int64_t nb = 0;
+    const int rc = groups_list_blocks(list, true, n_groups, ka.first, &nb);
+    if (rc) return rc;
+    if (nb == 0 && !advance) return 0;
+    ka.l = *list;
+    ka.hyper = hyper; ka.step = step; ka.grad_scale = grad_scale; ka.ticket = ticket;
+    ka.n_groups = n_groups; ka.advance = advance ? 1 : 0;
+    hipLaunchKernelGGL(adam_groups_kernel, dim3((unsigned)(nb > 0 ? nb : 1)), dim3(256), 0, static_cast<hipStream_t>(stream), ka);
+    return (int)hipGetLastError();
+}
+
+extern "C" int64_t lbbnn_grad_sumsq_workspace(int64_t partials) {
+    if (partials < 0) return 0;
+    return ((partials + 63) / 64) * 64 + 64;
+}
+
+extern "C" int lbbnn_grad_sumsq(const lbbnn_adam_group_list_t* list, float* work, int64_t work_offset, int64_t finalize_count,
+                                float max_norm, float* norm, float* grad_scale, void* stream) {
+    if (!list || !work || (finalize_count > 0 && (!norm || !grad_scale))) return LBBNN_E_NULL;
+    if (work_offset < 0 || finalize_count < 0) return LBBNN_E_SHAPE;
+    SumsqKArgs ka;
+    int64_t nb = 0;
+    const int rc = groups_list_blocks(list, false, 0, ka.first, &nb);
+    if (rc) return rc;
+    if (finalize_count > 0 && (finalize_count != work_offset + nb || !(max_norm > 0.f) || finalize_count > 0x7fffffff)) return LBBNN_E_SHAPE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (nb > 0) {
+        ka.l = *list;
+        ka.work = work + work_offset;
+        ka.pad = (int)(((work_offset + nb + 63) / 64) * 64 - (work_offset + nb));
+        hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)nb), dim3(256), 0, s, ka);
+    }
+    if (finalize_count > 0)
+        hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(1024), 0, s, work, (int)((finalize_count + 63) / 64), max_norm, norm,
+                           grad_scale);
     return (int)hipGetLastError();
 }
 

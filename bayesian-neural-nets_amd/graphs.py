@@ -106,7 +106,9 @@ def capture(graph, **kw):
 def make_graphed_train_step(net, optimizer, loss_fn, example_x, example_y, warmup: int = 3, overlap_vector_backward=None):
     """loss_fn(net, x, y) -> scalar loss.  The optimizer must be capture-safe: ``bnn_amd.optim.Adam`` (device-side
     step counter) or ``torch.optim.Adam(capturable=True)``.  The warm-up steps run eagerly first, so optimizer state is
-    allocated outside the capture.
+    allocated outside the capture.  ``bnn_amd.optim.Adam`` reads its learning rates (and betas, eps, weight decay) from a
+    device table: ``step`` pushes the groups' current values before every replay (``push_hyperparameters``: a copy only when
+    one changed), so ``torch.optim.lr_scheduler`` and edits of ``param_groups`` work under the one captured graph.
     ``overlap_vector_backward``: the vector-sized backward chains of the MNF layers are deferred
     (``layers.vector_backward_overlap``): each layer's backward only files its chain, and all layers' chains are issued
     in the same launches after the backward pass, before the optimizer step (planar: one launch instead of three; RNVP /
@@ -153,6 +155,8 @@ def make_graphed_train_step(net, optimizer, loss_fn, example_x, example_y, warmu
     if _quiet is not None:
         _quiet(True)
 
+    push = getattr(optimizer, "push_hyperparameters", None)
+
     def step(x, y):
         # a batch that already lies in the graph's input buffers (step.inputs: a loader that writes its host-to-device copy
         # straight into them) costs no device-to-device copy: 2 x ~4.7 us ahead of every replay otherwise
@@ -160,6 +164,8 @@ def make_graphed_train_step(net, optimizer, loss_fn, example_x, example_y, warmu
             static_x.copy_(x)
         if y.data_ptr() != static_y.data_ptr():
             static_y.copy_(y)
+        if push is not None:
+            push()                                 # a scheduler's / the caller's edits of param_groups reach the device table
         graph.replay()
         return static_loss
 

@@ -1,10 +1,25 @@
 """``Adam`` with ``torch.optim.Adam``'s constructor and update rule (the optimizer of the reference's training scripts:
 ``optim.Adam(net.parameters(), lr=...)``, LBBNN-GP-MF-LRT.py:358, LBBNN-GP-MF-MNF.py:421; per-parameter groups in
-LBBNN-GP-MF.py:520-554), executed as ONE multi-tensor HIP launch per parameter group (``lbbnn_adam_step``) instead of
-torch's ~115 small kernels for the 66 parameter tensors of the headline net.  The step counter lives on the device, so
-``step()`` is HIP-graph capturable as it is (no ``capturable=`` switch needed).
+LBBNN-GP-MF.py:520-554), executed as ONE multi-tensor HIP launch for ALL parameter groups (``lbbnn_adam_step_groups``; one per
+``_lib.ADAM_GROUPS_MAX_TENSORS`` tensors) instead of torch's ~115 small kernels for the 66 parameter tensors of the headline net.
 
-Not supported (raise): ``amsgrad``, ``maximize``, sparse gradients, non-fp32 or CPU parameters.
+Everything a schedule may change lives on the device: one table row ``{lr, beta1, beta2, eps, weight_decay, flags}`` and one
+step counter per group, read by the kernel when it runs.  ``step()`` is therefore HIP-graph capturable as it is (no
+``capturable=`` switch needed), and a ``torch.optim.lr_scheduler`` or a plain ``group["lr"] = ...`` takes effect on the next
+replay of a captured step: ``push_hyperparameters()`` copies the table when a value changed (``step()`` calls it outside a
+capture; the graphed steps of ``graphs`` and ``parallel`` call it before every replay).
+
+Beyond torch.optim.Adam's keywords:
+  ``decoupled_weight_decay=True``  AdamW's decay, ``p *= 1 - lr * weight_decay`` ahead of the plain update.
+  ``max_grad_norm=c``              global L2-norm clipping over all groups (``torch.nn.utils.clip_grad_norm_``'s formula) in one
+                                   extra call (two launches).  Unlike ``clip_grad_norm_``, ``.grad`` is NOT rescaled: the
+                                   scale is a device scalar applied inside the update; ``optimizer.grad_norm`` is a device
+                                   tensor with the norm before clipping of the last step (reading it inside the step needs no
+                                   synchronisation).
+  ``set_grad_mask(param, mask)``   multiply ``param``'s gradient by ``mask`` inside the update (and inside the norm): the
+                                   reference's COND_OPT, ``weight_mu.grad * gammas`` (LBBNN-GP-MF.py:333-336), without a hook.
+
+Not supported (raise): ``amsgrad``, ``maximize``, sparse gradients, non-fp32 or CPU parameters, parameters on several devices.
 """
 import ctypes
 
@@ -13,18 +28,116 @@ import torch
 from . import _lib
 
 
+def hyper_values(param_groups):
+    """The values the device table holds, per group, as plain host numbers: (lr, beta1, beta2, eps, weight_decay, flags).
+    flags: _lib.ADAM_F_DECOUPLED from the group's ``decoupled_weight_decay``, _lib.ADAM_F_INACTIVE for a
+    group without parameters."""
+    rows = []
+    for group in param_groups:
+        b1, b2 = group["betas"]
+        flags = (_lib.ADAM_F_DECOUPLED if group.get("decoupled_weight_decay") else 0) | \
+                (0 if group["params"] else _lib.ADAM_F_INACTIVE)
+        rows.append((float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), flags))
+    return tuple(rows)
+
+
+def hyper_dirty(pushed, current):
+    """True exactly when the table on the device (``pushed``: the hyper_values() it was filled from, None = never) differs
+    from ``current`` in some group's lr, betas, eps, weight_decay (or flags), or in the number of groups.  Pure host logic."""
+    return pushed is None or tuple(pushed) != tuple(current)
+
+
+def chunk_entries(entries, limit=None):
+    """``entries`` in per-launch lists of at most ``limit`` (default: the kernel's tensor limit); one empty list when there
+    is nothing to update (the counters still advance)."""
+    limit = limit or _lib.ADAM_GROUPS_MAX_TENSORS
+    return [entries[i:i + limit] for i in range(0, len(entries), limit)] or [[]]
+
+
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *,
-                 maximize=False, capturable=True):
+                 maximize=False, capturable=True, decoupled_weight_decay=False, max_grad_norm=None):
         if amsgrad or maximize:
             raise NotImplementedError("bnn_amd.optim.Adam: amsgrad / maximize are not implemented")
         if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1) or weight_decay < 0:
             raise ValueError("bnn_amd.optim.Adam: invalid hyper-parameter")
+        if max_grad_norm is not None and not (max_grad_norm > 0):
+            raise ValueError("bnn_amd.optim.Adam: max_grad_norm must be positive (or None)")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         # (the extra keys are torch.optim.Adam's own group keys at their defaults: a state_dict of this optimizer then loads
         # into torch.optim.Adam and back)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
                                       foreach=None, capturable=False, differentiable=False, fused=None,
-                                      decoupled_weight_decay=False))
+                                      decoupled_weight_decay=bool(decoupled_weight_decay)))
+
+    # ---- device tables ---------------------------------------------------------------------------------------------------
+    # All groups share ONE hyper-parameter table (G rows of lbbnn_adam_hyper_t) and ONE counter array (G floats);
+    # group["step_dev"] is the one-element view of the group's counter.  The tables are (re)built lazily, outside a capture:
+    # at the first step, after add_param_group, after load_state_dict.
+    def _tables(self):
+        tab = self.__dict__.get("_tab")
+        groups = self.param_groups
+        if tab is not None and tab["n"] == len(groups) and all(g.get("step_dev") is v for g, v in zip(groups, tab["views"])):
+            return tab
+        dev = next((p.device for g in groups for p in g["params"]), None)
+        if dev is None or dev.type != "cuda":
+            raise RuntimeError("bnn_amd.optim.Adam needs contiguous float32 parameters on a HIP device")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("bnn_amd.optim.Adam: the parameter groups changed; the device tables cannot be rebuilt inside a "
+                               "graph capture (run one eager step, or push_hyperparameters(), first)")
+        steps = torch.zeros(len(groups), dtype=torch.float32, device=dev)
+        for i, g in enumerate(groups):                                  # counters of the groups that had one carry over
+            if g.get("step_dev") is not None:
+                steps[i:i + 1].copy_(g["step_dev"].reshape(-1)[:1])
+        views = [steps[i:i + 1] for i in range(len(groups))]
+        for g, v in zip(groups, views):
+            g["step_dev"] = v
+        tab = dict(n=len(groups), dev=dev, steps=steps, views=views, hyper=torch.zeros(len(groups), 6, dtype=torch.float32, device=dev),
+                   ticket=torch.zeros(4, dtype=torch.int32, device=dev), norm=torch.zeros(1, dtype=torch.float32, device=dev),
+                   scale=torch.ones(1, dtype=torch.float32, device=dev), pushed=None, work=None)
+        self.__dict__["_tab"] = tab
+        self.__dict__.pop("_lists", None)
+        return tab
+
+    def push_hyperparameters(self):
+        """Copy the groups' lr / betas / eps / weight_decay to the device table if one of them changed since the last push
+        (``hyper_dirty``); returns whether it copied.  Call it before replaying a captured ``step()`` (the graphed steps of
+        this package do); an eager ``step()`` calls it itself.  Never inside a capture: a host-to-device copy there would be
+        replayed with the values of capture time."""
+        tab = self._tables()
+        cur = hyper_values(self.param_groups)
+        if not hyper_dirty(tab["pushed"], cur):
+            return False
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("bnn_amd.optim.Adam.push_hyperparameters: called inside a graph capture")
+        host = torch.empty(len(cur), 6, dtype=torch.float32)
+        host[:, :5] = torch.tensor([r[:5] for r in cur], dtype=torch.float64).to(torch.float32)   # rounded as c_float rounds
+        host.view(torch.int32)[:, 5] = torch.tensor([r[5] for r in cur], dtype=torch.int32)
+        tab["hyper"].copy_(host)
+        tab["pushed"] = cur
+        return True
+
+    @property
+    def grad_norm(self):
+        """Device tensor (1 element): the global L2 norm of the (masked) gradients of the last step, before clipping.  Only
+        written when ``max_grad_norm`` is set."""
+        return self._tables()["norm"]
+
+    def set_grad_mask(self, param, mask):
+        """Multiply ``param``'s gradient elementwise by ``mask`` inside the update: a tensor of ``param``'s shape, or a
+        zero-argument callable returning the current one (``lambda: layer.gammas``: the layer rebinds ``gammas`` on every
+        forward), resolved at ``step()`` time -- under a capture to the graph's static buffer.  ``None`` removes the mask."""
+        if not any(param is p for g in self.param_groups for p in g["params"]):
+            raise ValueError("bnn_amd.optim.Adam.set_grad_mask: not a parameter of this optimizer")
+        masks = self.__dict__.setdefault("_masks", {})
+        if mask is None:
+            masks.pop(id(param), None)
+        else:
+            masks[id(param)] = mask
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        self.__dict__.pop("_lists", None)                       # the tables regrow at the next step / push (outside capture)
 
     def _group_state(self, group):
         st = self.state
@@ -34,10 +147,6 @@ class Adam(torch.optim.Optimizer):
                     raise RuntimeError("bnn_amd.optim.Adam needs contiguous float32 parameters on a HIP device")
                 st[p]["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st[p]["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-        if "step_dev" not in group:
-            ref = group["params"][0]
-            group["step_dev"] = torch.zeros(1, dtype=torch.float32, device=ref.device)
-        return group["step_dev"]
 
     # torch.optim.Adam keeps one ``state[p]["step"]`` per parameter; this optimizer keeps ONE device-side counter per
     # parameter group (``group["step_dev"]``: every parameter of a group is updated in the same launch, so their counts
@@ -68,12 +177,28 @@ class Adam(torch.optim.Optimizer):
                     break
         super().load_state_dict(state_dict)
         self.__dict__.pop("_lists", None)                       # kernel-argument lists point at the old m / v buffers
+        self.__dict__.pop("_tab", None)
         for gi, group in enumerate(self.param_groups):
             group.pop("step_dev", None)
             for p in group["params"]:
                 self.state.get(p, {}).pop("step", None)
-            if gi in steps and group["params"]:
-                group["step_dev"] = torch.full((1,), steps[gi], dtype=torch.float32, device=group["params"][0].device)
+        if any(g["params"] for g in self.param_groups):
+            tab = self._tables()                                    # fresh counters, all zero
+            for gi, count in steps.items():
+                tab["steps"][gi] = count
+
+    def _resolve_mask(self, p, keep):
+        m = self.__dict__.get("_masks", {}).get(id(p))
+        if m is None:
+            return None
+        if callable(m) and not isinstance(m, torch.Tensor):
+            m = m()
+        if not isinstance(m, torch.Tensor) or m.shape != p.shape or m.device != p.device:
+            raise RuntimeError("bnn_amd.optim.Adam: a gradient mask must be a tensor of its parameter's shape on its device")
+        if m.dtype != torch.float32 or not m.is_contiguous():
+            m = m.detach().contiguous().float()
+            keep.append(m)
+        return m
 
     @torch.no_grad()
     def step(self, closure=None, grads=None):
@@ -86,46 +211,76 @@ class Adam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        for group in self.param_groups:
-            if not group["params"]:
-                continue
-            step = self._group_state(group)
-            ps = [p for p in group["params"] if (id(p) in override or p.grad is not None)]
-            stream = torch.cuda.current_stream(step.device).cuda_stream
-            b1, b2 = group["betas"]
-            keep = []
-            chunks = [ps[i:i + _lib.ADAM_MAX_TENSORS] for i in range(0, len(ps), _lib.ADAM_MAX_TENSORS)] or [[]]
-            cache = self.__dict__.setdefault("_lists", {}).setdefault(id(group), {})    # not in param_groups: state_dict() stays plain
-            for ci, chunk in enumerate(chunks):
-                gs = []
-                for p in chunk:
-                    g = override.get(id(p), p.grad)
-                    if g.is_sparse:
-                        raise RuntimeError("bnn_amd.optim.Adam does not support sparse gradients")
-                    if not g.is_contiguous() or g.dtype != torch.float32:
-                        g = g.contiguous().float()
-                        keep.append(g)
-                    gs.append(g)
-                # the kernel-argument list is rebuilt only when a pointer changed (gradients living in a flat bucket, or
-                # accumulated in place, keep their addresses: 5 ctypes stores per tensor saved on every step)
-                # (the m / v addresses are part of the key: optimizer.state may be replaced or cleared between steps --
-                # load_state_dict, a fresh state after a checkpoint restore -- and a stale list would update freed buffers)
-                key = (tuple(p.data_ptr() for p in chunk), tuple(g.data_ptr() for g in gs),
-                       tuple(self.state[p]["exp_avg"].data_ptr() for p in chunk),
-                       tuple(self.state[p]["exp_avg_sq"].data_ptr() for p in chunk))
-                hit = cache.get(ci)
-                if hit is None or hit[0] != key:
-                    lst = _lib.AdamList()
-                    lst.n = len(chunk)
-                    for k, (p, g) in enumerate(zip(chunk, gs)):
-                        st = self.state[p]
-                        lst.p[k], lst.g[k] = p.data_ptr(), g.data_ptr()
-                        lst.m[k], lst.v[k], lst.numel[k] = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()
-                    cache[ci] = (key, lst)
-                else:
-                    lst = hit[1]
-                rc = _lib.lib().lbbnn_adam_step(ctypes.byref(lst), group["lr"], b1, b2, group["eps"], group["weight_decay"],
-                                                step.data_ptr(), 1 if ci == len(chunks) - 1 else 0, stream)
-                _lib.check(rc, "lbbnn_adam_step")
-            del keep
+        if not any(g["params"] for g in self.param_groups):
+            return loss
+        tab = self._tables()
+        if not torch.cuda.is_current_stream_capturing():
+            self.push_hyperparameters()
+        elif hyper_dirty(tab["pushed"], hyper_values(self.param_groups)):
+            raise RuntimeError("bnn_amd.optim.Adam: hyper-parameters changed since the last push and step() runs inside a graph "
+                               "capture; call push_hyperparameters() before the capture")
+        dev = tab["dev"]
+        keep = []
+        entries = []                                                # (group index, parameter, gradient, mask or None)
+        for gi, group in enumerate(self.param_groups):
+            self._group_state(group)
+            for p in group["params"]:
+                g = override.get(id(p), p.grad)
+                if g is None:
+                    continue
+                if p.device != dev:
+                    raise RuntimeError("bnn_amd.optim.Adam: all parameters must live on one device")
+                if g.is_sparse:
+                    raise RuntimeError("bnn_amd.optim.Adam does not support sparse gradients")
+                if not g.is_contiguous() or g.dtype != torch.float32:
+                    g = g.contiguous().float()
+                    keep.append(g)
+                entries.append((gi, p, g, self._resolve_mask(p, keep)))
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        chunks = chunk_entries(entries)
+        cache = self.__dict__.setdefault("_lists", {})              # not in param_groups: state_dict() stays plain
+        lists = []
+        for ci, chunk in enumerate(chunks):
+            # the kernel-argument list is rebuilt only when a pointer changed (gradients living in a flat bucket, or
+            # accumulated in place, keep their addresses: 7 ctypes stores per tensor saved on every step)
+            # (the m / v addresses are part of the key: optimizer.state may be replaced or cleared between steps --
+            # load_state_dict, a fresh state after a checkpoint restore -- and a stale list would update freed buffers; so is
+            # the mask's: a callable may hand out another buffer)
+            key = tuple((gi, p.data_ptr(), g.data_ptr(), self.state[p]["exp_avg"].data_ptr(),
+                         self.state[p]["exp_avg_sq"].data_ptr(), 0 if m is None else m.data_ptr()) for gi, p, g, m in chunk)
+            hit = cache.get(ci)
+            if hit is None or hit[0] != key:
+                lst = _lib.AdamGroupList()
+                lst.n = len(chunk)
+                for k, (gi, p, g, m) in enumerate(chunk):
+                    st = self.state[p]
+                    lst.p[k], lst.g[k], lst.mask[k] = p.data_ptr(), g.data_ptr(), (None if m is None else m.data_ptr())
+                    lst.m[k], lst.v[k], lst.numel[k] = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()
+                    lst.group[k] = gi
+                cache[ci] = (key, lst)
+            else:
+                lst = hit[1]
+            lists.append(lst)
+        lib = _lib.lib()
+        scale = None
+        if self.max_grad_norm is not None and entries:
+            # global norm first, over every list: per-workgroup partials, then ONE fixed-order reduction that leaves the norm
+            # and min(1, max_norm / (norm + 1e-6)) on the device for the update launches below
+            counts = [sum((p.numel() + _lib.ADAM_CHUNK - 1) // _lib.ADAM_CHUNK for _, p, _, _ in chunk) for chunk in chunks]
+            need = lib.lbbnn_grad_sumsq_workspace(sum(counts))
+            if tab["work"] is None or tab["work"].numel() < need:
+                tab["work"] = torch.empty(need, dtype=torch.float32, device=dev)
+            off = 0
+            for ci, lst in enumerate(lists):
+                last = ci == len(lists) - 1
+                rc = lib.lbbnn_grad_sumsq(ctypes.byref(lst), tab["work"].data_ptr(), off, off + counts[ci] if last else 0,
+                                          self.max_grad_norm, tab["norm"].data_ptr(), tab["scale"].data_ptr(), stream)
+                _lib.check(rc, "lbbnn_grad_sumsq")
+                off += counts[ci]
+            scale = tab["scale"].data_ptr()
+        for ci, lst in enumerate(lists):
+            rc = lib.lbbnn_adam_step_groups(ctypes.byref(lst), tab["hyper"].data_ptr(), tab["steps"].data_ptr(), tab["n"], scale,
+                                            tab["ticket"].data_ptr(), 1 if ci == len(lists) - 1 else 0, stream)
+            _lib.check(rc, "lbbnn_adam_step_groups")
+        del keep
         return loss

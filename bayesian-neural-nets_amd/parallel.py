@@ -224,6 +224,8 @@ class DataParallelELBO:
         if self.bucket.last:
             self.bucket.last += " between two HIP graphs"
 
+        push = getattr(optimizer, "push_hyperparameters", None)
+
         def step(x, y):
             if x.data_ptr() != static_x.data_ptr():       # (a batch written straight into step.inputs needs no copy)
                 static_x.copy_(x)
@@ -231,6 +233,8 @@ class DataParallelELBO:
                 static_y.copy_(y)
             g_a.replay()
             self.bucket.collective(self.group)
+            if push is not None:
+                push()                                 # lr schedules / edits of param_groups reach the optimizer's device table
             g_b.replay()
             return static_loss
 

@@ -7,6 +7,7 @@ precisions inside the HIP kernels (sample_elbo(draws="hip")), so it is captured 
     python examples/train_base_synthetic.py               # graphed hip-draw step
     EAGER=1 python examples/train_base_synthetic.py       # the same step, eager
     COND_OPT=1 python examples/train_base_synthetic.py    # mask the weight_mu gradients with the drawn gates (:333-336)
+    DECAY=1 python examples/train_base_synthetic.py       # halve every group's rate each epoch (lr_scheduler, same graph)
 
 It ends with the reference's evaluation on a held-out synthetic batch: bnn_amd.evaluate.ensemble_eval (test_ensemble) and the
 accuracy and predictive entropy of the median probability model (outofsample(medimod=True)).
@@ -24,6 +25,7 @@ from bnn_amd.base import BayesianNetwork
 DEVICE = torch.device("cuda:0")
 BATCH_SIZE, NUM_BATCHES, EPOCHS = 100, 60, 4
 COND_OPT = os.environ.get("COND_OPT") == "1"
+DECAY = os.environ.get("DECAY") == "1"
 torch.manual_seed(0)                                   # also seeds the in-kernel draws
 
 net = BayesianNetwork().to(DEVICE)                     # 784-400-600-10
@@ -36,10 +38,18 @@ groups = ([{"params": l.bias_mu, "lr": 1e-4} for l in ls] + [{"params": l.bias_r
           + [{"params": l.lambdal, "lr": 0.1} for l in ls])
 optimizer = bnn_amd.optim.Adam(groups, lr=1e-4)
 if COND_OPT:
-    # weight_mu.grad * gammas.data (:333-336) as a gradient hook: it reads the gates of the step it runs in, so it is captured
-    # with the step (the graph's gammas buffer is rewritten by every replay)
+    # weight_mu.grad * gammas.data (:333-336) as a gradient mask of the optimizer: the callable is resolved when step() runs, so
+    # under the capture it is the graph's gammas buffer, rewritten by every replay; the product happens inside the update
+    # launch (a register_hook(lambda gr: gr * l.gammas) per layer does the same with three more kernels)
     for l in ls:
-        l.weight_mu.register_hook(lambda gr, l=l: gr * l.gammas)
+        optimizer.set_grad_mask(l.weight_mu, lambda l=l: l.gammas)
+# the rates live in a device table that the captured update reads, so a scheduler works under the ONE graph: step() below
+# pushes the groups' current values before every replay (a copy only when one changed)
+scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=1, gamma=0.5) if DECAY else None
+# The reference's switch at epoch 20 (:559-604) builds a new optimizer with rate 0 for pa / pb / weight_a / weight_b / bias_a /
+# bias_b and 1e-4 for lambdal: here that part is `group["lr"] = ...` on this optimizer, no re-capture.  The same switch also
+# sets the priors' `exact` flags, which are host values baked into the captured kernels' arguments: that part still needs
+# a new make_graphed_train_step.
 
 g = torch.Generator(device=DEVICE).manual_seed(7)
 proj = torch.randn(784, 10, device=DEVICE, generator=g)
@@ -67,7 +77,10 @@ for epoch in range(EPOCHS):
     for b in range(NUM_BATCHES):
         loss = step(train_x[b], train_y[b])
     torch.cuda.synchronize()
-    print("epoch %d  loss %.1f  (%.3f ms/iteration)" % (epoch, float(loss.detach()), (time.perf_counter() - t0) / NUM_BATCHES * 1e3))
+    print("epoch %d  loss %.1f  (%.3f ms/iteration)%s" % (epoch, float(loss.detach()), (time.perf_counter() - t0) / NUM_BATCHES * 1e3,
+                                                          "  lambdal rate %.4g" % optimizer.param_groups[-1]["lr"] if DECAY else ""))
+    if scheduler is not None:
+        scheduler.step()
 with torch.no_grad():
     print("mean inclusion probability per layer:", ["%.3f" % float(l.alpha.mean()) for l in ls])
 

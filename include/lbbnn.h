@@ -913,6 +913,63 @@ typedef struct lbbnn_adam_list {
 int lbbnn_adam_step(const lbbnn_adam_list_t* list, float lr, float beta1, float beta2, float eps, float weight_decay,
                     float* step, int advance, void* stream);
 
+/* lbbnn_adam_step_groups -- the same update for a list of tensors that belong to ANY NUMBER of parameter groups, in ONE
+ * launch (the reference's baseline optimizer has 33 single-tensor groups with four rates, LBBNN-GP-MF.py:520-554).
+ * Nothing a scheduler may change is a kernel argument: tensor i reads row group[i] of `hyper`, a DEVICE table of n_groups
+ * rows, when the kernel runs, so a captured graph follows the table (lr decay, freezing a group with lr = 0) without a
+ * re-capture.  Per element, with h = hyper[group[i]] and t = step[group[i]] + 1:
+ *   g' = g;  mask[i] != NULL: g' = g' * mask[i][e] (COND_OPT, LBBNN-GP-MF.py:333-336);  grad_scale != NULL: g' = g' * *grad_scale
+ *   LBBNN_ADAM_F_DECOUPLED: p = p * (1 - h.lr * h.weight_decay), then the update with weight_decay = 0 (AdamW)
+ *   otherwise lbbnn_adam_step's update, expression for expression: without mask, scale and decoupled decay the results
+ *   are bitwise those of lbbnn_adam_step with the same five values.
+ * step: n_groups device-side float counters, one per group, contiguous.  advance != 0 (set it on the last list of an
+ * optimizer step): every group without LBBNN_ADAM_F_INACTIVE gets step[g] += 1, IN THE SAME LAUNCH, by the workgroup that
+ * finishes last (a ticket drawn from *ticket after the workgroup's last use of its counter; DESIGN.md 9.1 has the argument
+ * why no workgroup can read an advanced counter).  ticket: one device uint32 the caller zeroes ONCE; the last workgroup
+ * leaves it at zero again.  One optimizer may have one such launch in flight at a time (launches of one stream are).
+ * list->n == 0 with advance != 0 is a one-workgroup launch that only advances.  Launches: exactly 1.
+ * Checks (before any HIP call): list / hyper / step, ticket with advance, a tensor's p / g / m / v: LBBNN_E_NULL;
+ * n outside [0, LBBNN_ADAM_GROUPS_MAX_TENSORS], n_groups outside [1, 65536], numel <= 0, group[i] outside [0, n_groups):
+ * LBBNN_E_SHAPE.  The list goes by value in the kernel arguments (4 KiB segment), hence the lower tensor limit. */
+#define LBBNN_ADAM_GROUPS_MAX_TENSORS 64
+#define LBBNN_ADAM_CHUNK 4096          /* elements per workgroup of the list kernels = per partial of lbbnn_grad_sumsq */
+#define LBBNN_ADAM_F_DECOUPLED 0x1     /* decoupled weight decay (torch.optim.AdamW)                     */
+#define LBBNN_ADAM_F_INACTIVE 0x2      /* a group without parameters: its counter does not advance       */
+typedef struct lbbnn_adam_hyper {      /* one row of the device table; 24 bytes                          */
+    float lr, beta1, beta2, eps, weight_decay;
+    uint32_t flags;
+} lbbnn_adam_hyper_t;
+typedef struct lbbnn_adam_group_list {
+    float* p[LBBNN_ADAM_GROUPS_MAX_TENSORS];
+    const float* g[LBBNN_ADAM_GROUPS_MAX_TENSORS];
+    float* m[LBBNN_ADAM_GROUPS_MAX_TENSORS];
+    float* v[LBBNN_ADAM_GROUPS_MAX_TENSORS];
+    const float* mask[LBBNN_ADAM_GROUPS_MAX_TENSORS];   /* same shape as g; NULL = no mask */
+    int64_t numel[LBBNN_ADAM_GROUPS_MAX_TENSORS];
+    int group[LBBNN_ADAM_GROUPS_MAX_TENSORS];
+    int n;
+} lbbnn_adam_group_list_t;
+
+int lbbnn_adam_step_groups(const lbbnn_adam_group_list_t* list, const lbbnn_adam_hyper_t* hyper, float* step, int n_groups,
+                           const float* grad_scale, uint32_t* ticket, int advance, void* stream);
+
+/* lbbnn_grad_sumsq -- global L2 norm of the (masked) gradients of a list, for torch.nn.utils.clip_grad_norm_'s clipping
+ * applied inside lbbnn_adam_step_groups (p / m / v / group of the list are not read).  Launch 1: workgroup b of the list
+ * (tensor i owns ceil(numel[i] / LBBNN_ADAM_CHUNK) consecutive workgroups, tensors in list order) writes
+ * work[work_offset + b] = sum over its chunk of (mask * g)^2, added in a fixed order.  finalize_count > 0 (set it on the last
+ * list of a step, to the number of partials of all its lists) adds launch 2, one workgroup: the partials work[0 ..
+ * finalize_count) are summed in the fixed order of the project's two-level column sums (64 columns, every 16th row per wave,
+ * then the 16 wave partials, then the 64 columns by a fixed butterfly), and
+ *   *norm = sqrt(sum),  *grad_scale = min(1, max_norm / (*norm + 1e-6))      (clip_grad_norm_'s formula; a NaN norm gives NaN)
+ * No atomics: *norm is bitwise reproducible from run to run.  Launches: 1, or 2 with finalize_count > 0.
+ * work: lbbnn_grad_sumsq_workspace(partials of all lists) floats (the partials padded to a multiple of 64, plus 64).
+ * Checks: list / work, norm / grad_scale with finalize_count > 0, a tensor's g: LBBNN_E_NULL; n outside [0,
+ * LBBNN_ADAM_GROUPS_MAX_TENSORS], numel <= 0, work_offset < 0, finalize_count < 0, and with finalize_count > 0: finalize_count !=
+ * work_offset + this list's partials (the zero padding is written behind the last list), max_norm <= 0: LBBNN_E_SHAPE. */
+int64_t lbbnn_grad_sumsq_workspace(int64_t partials);
+int lbbnn_grad_sumsq(const lbbnn_adam_group_list_t* list, float* work, int64_t work_offset, int64_t finalize_count,
+                     float max_norm, float* norm, float* grad_scale, void* stream);
+
 /* lbbnn_matmul_splitk -- split-K form of the mean-only bf16x3 product for long contractions with few output tiles
  * (the weight gradients dW = G^T.x: K = batch):  out[z] (B,O; row stride ldo; slab stride B*ldo) =
  * x[:, Kz] . w[:, Kz]^T with Kz = [z*kchunk, min(I, (z+1)*kchunk)), z < ceil(I / kchunk); kchunk a multiple of 32.
