@@ -233,6 +233,19 @@ class DenseBwdArgs(ctypes.Structure):
                [("Tz", c_i), ("Tr", c_i), ("O", c_i), ("I", c_i), ("rng", c_p), ("layer_id", c_u32)]
 
 
+EVAL_COUNTS = 6                        # LBBNN_EVAL_COUNTS, in the header's order:
+EVAL_COUNT_NAMES = ("rows", "rows_with_target", "bad_targets", "correct_ensemble", "correct_posterior_mean",
+                    "entropy_nonfinite")
+
+
+class EvalMetricsArgs(ctypes.Structure):
+    """lbbnn_eval_metrics_args_t"""
+    _fields_ = [("logp", c_p), ("m_stride", c_i64), ("ldp", c_i64), ("mean_logp", c_p), ("ldm", c_i64), ("target", c_p),
+                ("ens_logp", c_p), ("pred_ensemble", c_p), ("pred_mean", c_p), ("entropy", c_p),
+                ("counts", c_p), ("correct_member", c_p), ("confusion", c_p), ("sums", c_p), ("work", c_p),
+                ("S", c_i), ("B", c_i), ("C", c_i)]
+
+
 # name -> (restype, argtypes); must list every symbol include/lbbnn.h declares
 SIGNATURES = {
     "lbbnn_abi_version": (c_i, []),
@@ -337,6 +350,8 @@ SIGNATURES = {
     "lbbnn_flow_dense_members_max_dim": (c_i, []),
     "lbbnn_flow_dense_members": (c_i, [ctypes.POINTER(DenseMembers), c_i, c_i, c_p, c_u64, c_p]),
     "lbbnn_frozen_members_dense": (c_i, [ctypes.POINTER(FrozenDesc), ctypes.POINTER(DenseMembers), c_i, c_i, c_p, c_u64, c_p]),
+    "lbbnn_eval_metrics_work_bytes": (c_i64, [c_i, c_i, c_i]),
+    "lbbnn_eval_metrics": (c_i, [ctypes.POINTER(EvalMetricsArgs), c_p]),
 }
 
 _lib = None

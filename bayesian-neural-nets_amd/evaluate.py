@@ -388,6 +388,206 @@ def predictive_entropy(outputs: torch.Tensor) -> torch.Tensor:
     return -(m * torch.log(m)).sum(-1)
 
 
+# ----------------------------------------------------------------------------------------- metrics on the device
+def _dense_rows(t: torch.Tensor, rows: int, cols: int):
+    """(tensor, row stride) of a (rows, cols) fp32 view the metrics kernel reads in place, or of its contiguous copy."""
+    ld = t.stride(0) if rows > 1 else cols
+    if (cols > 1 and t.stride(1) != 1) or ld < cols:
+        t, ld = t.contiguous(), cols
+    return t, ld
+
+
+@torch.no_grad()
+def ensemble_metrics(outputs: torch.Tensor, target: Optional[torch.Tensor] = None,
+                     mean_outputs: Optional[torch.Tensor] = None, *, acc: Optional["EvalAccumulator"] = None) -> Dict[str, object]:
+    """The per-row numbers of the reference's evaluation loops from one (samples, B, classes) block of log-probabilities, in
+    ONE lbbnn_eval_metrics call (1 launch; 2 with ``acc``) and without a host synchronisation:
+
+    * ``mean_log_probs`` (B, classes): the mean over the members (test_ensemble's ``outputs.mean(0)``,
+      LBBNN-GP-MF-MNF.py:312-315), summed in member order in fp32 and divided by ``samples`` -- a fixed arithmetic
+      (include/lbbnn.h), so the values and everything derived from them are reproducible bit for bit on the CPU;
+    * ``pred_ensemble`` (B,) int64: its argmax by numpy.argmax's rule (NaN is the maximum, the lowest index wins a tie);
+    * ``pred_posterior_mean`` (B,) int64 when ``mean_outputs`` (B, classes), the posterior-mean forward, is given;
+    * ``entropy`` (B,): ``predictive_entropy(outputs)`` (outofsample, :370-392) computed in the same pass.
+
+    ``outputs`` is any fp32 HIP tensor whose last dimension is dense -- the strided views ``FrozenNetwork.ensemble`` /
+    ``base_ensemble`` / ``vd_ensemble`` return are read in place; classes <= 64.  ``target`` (B,) int64 matters with ``acc``
+    only: an ``EvalAccumulator`` whose running totals this call adds to (``EvalAccumulator.update`` is this call)."""
+    import ctypes
+    from . import _lib
+    if outputs.dim() != 3:
+        raise ValueError("bnn_amd: outputs must be (samples, B, classes), got %s" % (tuple(outputs.shape),))
+    if not outputs.is_cuda:
+        raise RuntimeError("bnn_amd: ensemble_metrics needs a HIP device tensor (outputs is on %s); there is no CPU path"
+                           % outputs.device)
+    S, B, C = outputs.shape
+    if not 1 <= C <= 64:
+        raise ValueError("bnn_amd: ensemble_metrics takes 1 to 64 classes, got %d" % C)
+    if not 1 <= S <= 65535:
+        raise ValueError("bnn_amd: ensemble_metrics takes 1 to 65535 members, got %d" % S)
+    dev = outputs.device
+    o = outputs if outputs.dtype == torch.float32 else outputs.float()
+    ldp = o.stride(1) if B > 1 else C
+    ms = o.stride(0) if S > 1 else 0
+    if (C > 1 and o.stride(2) != 1) or ldp < C or (S > 1 and B > 0 and ms < (B - 1) * ldp + C):
+        o, ldp, ms = o.contiguous(), C, B * C
+    a = _lib.EvalMetricsArgs()
+    a.logp, a.m_stride, a.ldp, a.S, a.B, a.C = o.data_ptr(), ms, ldp, S, B, C
+    keep = [o]
+    if mean_outputs is not None:
+        if tuple(mean_outputs.shape) != (B, C) or mean_outputs.device != dev:
+            raise ValueError("bnn_amd: mean_outputs must be (%d, %d) on %s, got %s on %s"
+                             % (B, C, dev, tuple(mean_outputs.shape), mean_outputs.device))
+        mo, ldm = _dense_rows(mean_outputs if mean_outputs.dtype == torch.float32 else mean_outputs.float(), B, C)
+        a.mean_logp, a.ldm = mo.data_ptr(), ldm
+        keep.append(mo)
+    if target is not None:
+        if tuple(target.shape) != (B,) or target.device != dev:
+            raise ValueError("bnn_amd: target must be (%d,) on %s, got %s on %s" % (B, dev, tuple(target.shape), target.device))
+        t = target if target.dtype == torch.int64 else target.long()
+        t = t if (B < 2 or t.stride(0) == 1) else t.contiguous()
+        a.target = t.data_ptr()
+        keep.append(t)
+    # the per-row outputs as one allocation: [pred_ensemble | pred_posterior_mean] int64, then [mean_log_probs | entropy] fp32
+    buf = torch.empty(2 * B + (B * C + B + 1) // 2, dtype=torch.int64, device=dev)
+    fl = buf[2 * B:].view(torch.float32)
+    res = {"mean_log_probs": fl[:B * C].view(B, C), "pred_ensemble": buf[:B], "entropy": fl[B * C:B * C + B]}
+    a.ens_logp, a.pred_ensemble, a.entropy = fl.data_ptr(), buf.data_ptr(), fl.data_ptr() + 4 * B * C
+    if mean_outputs is not None:
+        res["pred_posterior_mean"] = buf[B:2 * B]
+        a.pred_mean = buf.data_ptr() + 8 * B
+    if acc is not None:
+        acc._fill(a, S, B, C, dev)
+    if B > 0:                                                # (an empty batch has no storage to point at, and nothing to add)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(_lib.lib().lbbnn_eval_metrics(ctypes.byref(a), stream), "lbbnn_eval_metrics")
+    if acc is not None:
+        acc._note(mean_outputs is not None)
+    del keep
+    return res
+
+
+class EvalAccumulator:
+    """Running totals of an evaluation pass, kept on the device: ``update`` adds a batch (no host read), ``result`` reads them
+    -- the ONLY synchronisation of a pass.  What the reference's loops accumulate on the host with an ``.item()`` per batch:
+    test_ensemble's two correct counts (LBBNN-GP-MF-MNF.py:316-323), outofsample's per-member ``corrects``, ensemble correct
+    count and entropies (:370-392), VD's validation nll sum, correct count and confusion matrix
+    (variational_dropout.py:160-176).  ``classes`` <= 64 and ``samples`` are fixed for the accumulator's life."""
+
+    def __init__(self, classes: int, samples: int, device):
+        from . import _lib
+        C, S = int(classes), int(samples)
+        if not 1 <= C <= 64:
+            raise ValueError("bnn_amd: EvalAccumulator takes 1 to 64 classes, got %d" % C)
+        if not 1 <= S <= 65535:
+            raise ValueError("bnn_amd: EvalAccumulator takes 1 to 65535 members, got %d" % S)
+        self.classes, self.samples, self.device = C, S, torch.device(device)
+        n = _lib.EVAL_COUNTS
+        # one buffer, one read: counts | correct_member | confusion | the two double sums (bit patterns)
+        self._totals = torch.zeros(n + S + C * C + 2, dtype=torch.int64, device=self.device)
+        self._work = None
+        self.updates = self.posterior_mean_updates = 0
+
+    def _fill(self, a, S, B, C, dev):
+        """Point the totals of an lbbnn_eval_metrics_args_t at this accumulator (work memory grows to the largest batch)."""
+        from . import _lib
+        if (S, C) != (self.samples, self.classes):
+            raise ValueError("bnn_amd: this EvalAccumulator was built for %d members and %d classes, the outputs have %d and %d"
+                             % (self.samples, self.classes, S, C))
+        if dev != self._totals.device:
+            raise ValueError("bnn_amd: the outputs are on %s, the accumulator on %s" % (dev, self._totals.device))
+        need = int(_lib.lib().lbbnn_eval_metrics_work_bytes(S, B, C))
+        if self._work is None or self._work.numel() * 8 < need:
+            self._work = torch.empty(need // 8, dtype=torch.float64, device=dev)
+        n, base = _lib.EVAL_COUNTS, self._totals.data_ptr()
+        a.counts, a.correct_member, a.confusion = base, base + 8 * n, base + 8 * (n + S)
+        a.sums, a.work = base + 8 * (n + S + C * C), self._work.data_ptr()
+
+    def _note(self, with_mean: bool):
+        self.updates += 1
+        self.posterior_mean_updates += int(with_mean)
+
+    def update(self, outputs: torch.Tensor, target: Optional[torch.Tensor], mean_outputs: Optional[torch.Tensor] = None):
+        """``ensemble_metrics(outputs, target, mean_outputs)`` of one batch, its numbers added to the totals."""
+        return ensemble_metrics(outputs, target, mean_outputs, acc=self)
+
+    def reset(self):
+        self._totals.zero_()
+        self.updates = self.posterior_mean_updates = 0
+
+    def _read(self):
+        """The totals as a host int64 array (the one device-to-host copy)."""
+        return self._totals.cpu().numpy()
+
+    def result(self, strict: bool = True) -> Dict[str, object]:
+        """Python numbers: ``rows``, ``rows_with_target``, ``bad_targets``, ``correct_ensemble``, ``correct_posterior_mean``,
+        ``entropy_nonfinite``, ``nll_sum`` (``F.nll_loss(outputs.mean(0), target, reduction="sum")`` over the pass),
+        ``entropy_sum`` (over the rows with a finite entropy); ``correct_member`` (samples,) and ``confusion`` (classes,
+        classes; rows = true labels) as numpy arrays; and derived ``accuracy_ensemble``, ``accuracy_posterior_mean`` (None when
+        no update carried posterior-mean outputs), ``nll_mean`` (over the rows with a target) and ``entropy_mean`` (over the
+        finite rows) -- NaN where the denominator is 0.  ``strict``: targets outside [0, classes) raise IndexError, as
+        ``F.nll_loss`` would have; with ``strict=False`` they are reported in ``bad_targets`` and left out of the totals."""
+        import numpy as np
+        from . import _lib
+        h = np.ascontiguousarray(self._read(), dtype=np.int64)
+        n, S, C = _lib.EVAL_COUNTS, self.samples, self.classes
+        res = {k: int(h[i]) for i, k in enumerate(_lib.EVAL_COUNT_NAMES)}
+        if strict and res["bad_targets"]:
+            raise IndexError("bnn_amd: %d target(s) outside [0, %d) in this evaluation pass" % (res["bad_targets"], C))
+        sums = h[n + S + C * C:].view(np.float64)
+        res["correct_member"] = h[n:n + S].copy()
+        res["confusion"] = h[n + S:n + S + C * C].reshape(C, C).copy()
+        res["nll_sum"], res["entropy_sum"] = float(sums[0]), float(sums[1])
+        nt, nf = res["rows_with_target"], res["rows"] - res["entropy_nonfinite"]
+        div = lambda x, d: x / d if d else float("nan")
+        res["accuracy_ensemble"] = div(res["correct_ensemble"], nt)
+        res["accuracy_posterior_mean"] = div(res["correct_posterior_mean"], nt) if self.posterior_mean_updates else None
+        res["nll_mean"] = div(res["nll_sum"], nt)
+        res["entropy_mean"] = div(res["entropy_sum"], nf)
+        return res
+
+
+def _eval_forwards(net, data, samples: int, posterior_mean: bool, gates: str):
+    """(outputs, mean_outputs or None) of one batch, by family, as ``ensemble_eval`` dispatches."""
+    if _is_frozen(net):
+        if gates != "sample":
+            raise ValueError("bnn_amd: gates=%r: the gates of a frozen model were fixed by evaluate.freeze" % (gates,))
+        outputs = net.ensemble(data, samples)
+        return outputs, (net(data, sample=False) if posterior_mean else None)
+    if _is_base(net):
+        outputs = base_ensemble(net, data, samples, gates=gates)["outputs"]
+        if not posterior_mean:
+            return outputs, None
+        for l in (net.l1, net.l2, net.l3):
+            l.alpha = 1 / (1 + torch.exp(-l.lambdal.detach()))                  # LBBNN-GP-MF.py:369-374
+            l.gamma.alpha = l.alpha
+        return outputs, net(data, None, None, None, sample=False)              # :413 (mode 2: weight = alpha * mu)
+    if _is_vd(net):
+        return ensemble_forward(net, data, samples, gates=gates), None         # VD has no posterior-mean forward
+    outputs = ensemble_forward(net, data, samples, gates=gates)
+    return outputs, (net(data, sample=False) if posterior_mean else None)
+
+
+@torch.no_grad()
+def evaluate_batches(net, batches, samples: int = 10, *, acc: Optional[EvalAccumulator] = None, posterior_mean: bool = True,
+                     gates: str = "sample") -> Dict[str, object]:
+    """A whole evaluation pass with ONE host synchronisation: for every ``(x, y)`` of ``batches`` (device tensors) the ensemble
+    forward of the network's family -- ``ensemble_forward`` / ``FrozenNetwork.ensemble`` / ``base_ensemble`` / ``vd_ensemble``,
+    the dispatch and the draws of ``ensemble_eval`` -- the posterior-mean forward where the family has one (``posterior_mean``;
+    variational dropout has none) and ``acc.update``; returns ``acc.result()``.  ``acc``: an ``EvalAccumulator`` to add to
+    (default: a fresh one).  ``gates="mpm"``: the median probability model of a baseline network."""
+    S = int(samples)
+    for x, y in batches:
+        outputs, mean = _eval_forwards(net, x, S, posterior_mean, gates)
+        if acc is None:
+            acc = EvalAccumulator(outputs.shape[-1], S, outputs.device)
+        acc.update(outputs, y, mean)
+    if acc is None:
+        raise ValueError("bnn_amd: evaluate_batches got no batches and no accumulator")
+    return acc.result()
+
+
 # ----------------------------------------------------------------------------------------- frozen evaluation model
 FROZEN_GATES = ("alpha", "mpm")
 

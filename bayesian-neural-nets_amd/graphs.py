@@ -175,6 +175,60 @@ def make_graphed_train_step(net, optimizer, loss_fn, example_x, example_y, warmu
     return step
 
 
+def make_graphed_eval_step(frozen, example_x, example_y, samples: int, acc, warmup: int = 2):
+    """One evaluation step of a frozen model (``evaluate.freeze``: LRT, MNF with planar or dense z flows) as ONE HIP graph on a
+    single stream, no forked branches: ``frozen.ensemble(x, samples)``, the posterior-mean forward ``frozen(x, sample=False)``
+    and ``acc.update`` (lbbnn_eval_metrics: the metrics and the running totals of ``acc``, an ``evaluate.EvalAccumulator``).
+    Nothing in the step reads the device, and the Philox offset advances inside the graph, so every replay draws fresh members
+    -- the members the eager calls would draw from the same offset.  The warm-up steps run eagerly first (buffers exist before
+    the capture); the Philox state and ``acc``'s totals are put back afterwards, so building the step changes neither.
+    Returns ``step(x, y)`` -> the per-row dict of ``acc.update`` (static buffers, overwritten by the next replay); read the
+    totals with ``acc.result()`` when the pass is over."""
+    from . import evaluate, ops
+    if not evaluate._is_frozen(frozen):
+        raise TypeError("bnn_amd.graphs.make_graphed_eval_step takes a frozen model (evaluate.freeze), got %s"
+                        % type(frozen).__name__)
+    if not example_x.is_cuda:
+        raise RuntimeError("bnn_amd.graphs.make_graphed_eval_step needs HIP tensors (example_x is on %s)" % example_x.device)
+    dev = example_x.device
+    S = int(samples)
+    static_x, static_y = example_x.clone(), example_y.clone()
+
+    def body():
+        outputs = frozen.ensemble(static_x, S)
+        return acc.update(outputs, static_y, frozen(static_x, sample=False))
+
+    st = ops.RngState.get(dev)
+    rng0, totals0, counts0 = st.t.clone(), acc._totals.clone(), (acc.updates, acc.posterior_mean_updates)
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        for _ in range(max(1, int(warmup))):
+            body()
+        st.t.copy_(rng0)
+        acc._totals.copy_(totals0)
+    torch.cuda.current_stream(dev).wait_stream(side)
+    acc.updates, acc.posterior_mean_updates = counts0
+    graph = torch.cuda.CUDAGraph()
+    torch.cuda.synchronize(dev)
+    with capture(graph):
+        rows = body()
+    acc.updates, acc.posterior_mean_updates = counts0        # the capture enqueued nothing
+
+    def step(x, y):
+        if x.data_ptr() != static_x.data_ptr():
+            static_x.copy_(x)
+        if y.data_ptr() != static_y.data_ptr():
+            static_y.copy_(y)
+        graph.replay()
+        acc._note(True)
+        return rows
+
+    step.graph = graph
+    step.inputs = (static_x, static_y)
+    return step
+
+
 class LaunchPlan:
     """The no-grad forward of a network as a RECORDED LIST OF C CALLS, replayed without the Python in between.
 

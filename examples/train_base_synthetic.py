@@ -96,3 +96,18 @@ print("held-out: ensemble accuracy %.3f, posterior-mean accuracy %.3f, density %
 mpm = bnn_amd.evaluate.ensemble_forward(net, test_x, 10, gates="mpm")
 print("median probability model: accuracy %.3f, mean predictive entropy %.3f"
       % (float(mpm.mean(0).argmax(1).eq(test_y).float().mean()), float(bnn_amd.evaluate.predictive_entropy(mpm).mean())))
+
+# A whole test pass with ONE host read: several held-out batches through an EvalAccumulator (per batch: base_ensemble, the
+# posterior-mean forward and one lbbnn_eval_metrics call; the totals stay on the device until result()) -- the sampled gates,
+# then the median probability model.
+test_batches = []
+for _ in range(5):
+    bx = torch.rand(200, 1, 28, 28, device=DEVICE, generator=g)
+    test_batches.append((bx, (bx.view(200, 784) @ proj).argmax(-1)))
+for gates in ("sample", "mpm"):
+    tot = bnn_amd.evaluate.evaluate_batches(net, test_batches, samples=10, gates=gates)
+    print("test pass over %d rows, gates=%s (one host read): ensemble %.3f | posterior mean %.3f | members %.3f .. %.3f | nll %.3f "
+          "| mean predictive entropy %.3f"
+          % (tot["rows"], gates, tot["accuracy_ensemble"], tot["accuracy_posterior_mean"],
+             tot["correct_member"].min() / tot["rows_with_target"], tot["correct_member"].max() / tot["rows_with_target"],
+             tot["nll_mean"], tot["entropy_mean"]))

@@ -79,3 +79,27 @@ if FLOWS in ("Planar", "RNVP", "MNF"):
                             float(bnn_amd.evaluate.predictive_entropy(res["outputs"]).mean())))
 else:
     print("median probability model: evaluate.freeze takes planar, RNVP and MNF-type z flows (FLOWS=%s)" % FLOWS)
+
+# A whole test pass with ONE host read: several test batches through an EvalAccumulator.  Every batch is the ensemble, the
+# posterior-mean forward and one lbbnn_eval_metrics call whose running totals (correct counts, per-member corrects, nll sum,
+# predictive entropy, confusion matrix) stay on the device; result() reads them when the pass is over -- what test_ensemble
+# (:312-323) and outofsample (:370-392) accumulate on the host with an .item() per batch.
+test_batches = []
+for _ in range(4):
+    bx = torch.rand(BATCH_SIZE, 1, 28, 28, device=DEVICE, generator=g)
+    test_batches.append((bx, (bx.view(BATCH_SIZE, 784) @ proj).argmax(-1)))
+model = mpm if FLOWS in ("Planar", "RNVP", "MNF") else net
+tot = bnn_amd.evaluate.evaluate_batches(model, test_batches, samples=TEST_SAMPLES)
+print("test pass over %d rows (one host read): ensemble %.3f | posterior mean %.3f | members %s | nll %.3f | mean predictive "
+      "entropy %.3f" % (tot["rows"], tot["accuracy_ensemble"], tot["accuracy_posterior_mean"],
+                        " ".join("%.3f" % (c / tot["rows_with_target"]) for c in tot["correct_member"]), tot["nll_mean"],
+                        tot["entropy_mean"]))
+if FLOWS in ("Planar", "RNVP", "MNF"):
+    # ... and the same pass replayed from one HIP graph per batch (ensemble + posterior-mean forward + metrics, single stream)
+    acc = bnn_amd.evaluate.EvalAccumulator(10, TEST_SAMPLES, DEVICE)
+    eval_step = bnn_amd.graphs.make_graphed_eval_step(mpm, test_batches[0][0], test_batches[0][1], TEST_SAMPLES, acc)
+    for bx, by in test_batches:
+        eval_step(bx, by)
+    tot = acc.result()
+    print("graphed test pass: ensemble %.3f | posterior mean %.3f | confusion matrix diagonal %s"
+          % (tot["accuracy_ensemble"], tot["accuracy_posterior_mean"], tot["confusion"].diagonal().tolist()))

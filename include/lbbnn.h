@@ -1166,6 +1166,67 @@ int lbbnn_weight_pass_f16(const float* mu, const float* rho, const float* lambda
                           float* kl_rows, float* act_mu, float* act_var, float* bias_var,
                           int O, int I, int flags /* 0 | LBBNN_F_VAR1 */, void* stream);
 
+/* lbbnn_eval_metrics -- every number the reference's evaluation loops report, from one (S members, B rows, C classes) block of
+ * log-probabilities (test_ensemble, LBBNN-GP-MF-MNF.py:312-323; outofsample, :370-392; VD's validation,
+ * variational_dropout.py:160-176), with running totals that stay on the device.  No host synchronisation, no allocation.
+ * Launches: 1, or 2 with totals (the second, one workgroup, adds the double sums); B == 0: a successful no-op, no launch.
+ *
+ * Inputs.  logp: member m, row b, class c at logp + m * m_stride + b * ldp + c (64-bit offsets: the padded head buffer of the
+ * member GEMMs as it is, or a dense (S,B,C) tensor).  mean_logp (optional): (B,C) rows of stride ldm, the posterior-mean
+ * forward.  target (optional): B int64 class indices.  1 <= S <= 65535, B >= 0, 1 <= C <= 64.
+ *
+ * Per-row outputs, each optional (NULL = not written):
+ *   ens_logp[b * C + c]  the mean over the members, with THIS arithmetic: acc = logp[0]; acc += logp[m] for m = 1 .. S-1
+ *                        ascending, in fp32; then acc / (float)S by IEEE (correctly rounded) division.  A CPU restatement
+ *                        in fp32 reproduces it bit for bit.
+ *   pred_ensemble[b]     argmax over c of ens_logp[b] by numpy.argmax's rule: a NaN compares as the maximum, the lowest index
+ *                        of the maximum wins (-0 == +0).
+ *   pred_mean[b]         the same argmax of mean_logp[b] (needs mean_logp: LBBNN_E_NULL otherwise).
+ *   entropy[b]           outofsample's predictive entropy in fp32: per member sigmoid(logp) = 1 / (1 + exp(-logp)) divided by
+ *                        its sum over the classes of the row, the mean over the members (sum in member order, / S), then
+ *                        -sum_c p log p.  A row where that expression is not finite is stored as computed.
+ *
+ * Running totals: counts, correct_member, confusion, sums and work are given together or not at all.  They are ADDED TO, so
+ * consecutive calls accumulate over batches; the caller zeroes them.
+ *   counts[LBBNN_EVAL_COUNTS] (int64), in this order:
+ *     rows, rows_with_target (target given and inside [0, C)), bad_targets (target given and outside [0, C); such rows are
+ *     left out of every total that needs a target), correct_ensemble (pred_ensemble == target), correct_posterior_mean (the
+ *     argmax of mean_logp == target; stays 0 without mean_logp), entropy_nonfinite (rows whose entropy is inf or NaN)
+ *   correct_member[S] (int64)   rows whose member-m argmax (same rule) == target: outofsample's `corrects`
+ *   confusion[C * C] (int64)    confusion[target * C + pred_ensemble]: rows are the true labels (variational_dropout.py:176)
+ *   sums[2] (double)            sums[0] += -sum_b (double)ens_logp[b][target_b]: F.nll_loss(outputs.mean(0), target,
+ *                               reduction="sum"), the data term of VD's validation loss;  sums[1] += sum of (double)entropy[b]
+ *                               over the rows where it is finite.
+ * Every total is bitwise reproducible from run to run: the integer totals are exact (integer atomics), and each workgroup
+ * leaves its two double partials in `work`, which the second launch adds in a fixed order -- no float atomics.
+ * work: lbbnn_eval_metrics_work_bytes(S, B, C) bytes (> 0 for every valid shape, non-decreasing in B), 8-B aligned.
+ *
+ * Checks, before anything is launched: a NULL args / logp, some but not all of the totals pointers, totals without work,
+ * pred_mean without mean_logp: LBBNN_E_NULL.  S, C or B out of range, ldp < C, ldm < C, and with S > 1 and B > 0 a member stride
+ * that does not hold B rows (m_stride < (B - 1) * ldp + C): LBBNN_E_SHAPE.  A pointer off its natural alignment (4 B for the
+ * floats, 8 B for int64 / double / work): LBBNN_E_ALIGN. */
+#define LBBNN_EVAL_COUNTS 6
+typedef struct lbbnn_eval_metrics_args {
+    const float* logp;
+    int64_t m_stride, ldp;
+    const float* mean_logp;
+    int64_t ldm;
+    const int64_t* target;
+    float* ens_logp;
+    int64_t* pred_ensemble;
+    int64_t* pred_mean;
+    float* entropy;
+    int64_t* counts;
+    int64_t* correct_member;
+    int64_t* confusion;
+    double* sums;
+    void* work;
+    int S, B, C;
+} lbbnn_eval_metrics_args_t;
+
+int64_t lbbnn_eval_metrics_work_bytes(int S, int B, int C);
+int lbbnn_eval_metrics(const lbbnn_eval_metrics_args_t* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
