@@ -246,6 +246,22 @@ class EvalMetricsArgs(ctypes.Structure):
                 ("S", c_i), ("B", c_i), ("C", c_i)]
 
 
+UNC_COUNTS = 6                         # LBBNN_UNC_COUNTS, in the header's order:
+UNC_COUNT_NAMES = ("rows", "rows_with_target", "bad_targets", "correct_bma", "nonfinite_rows", "log_score_nonfinite")
+UNC_SUMS = 6                           # LBBNN_UNC_SUMS, in the header's order:
+UNC_SUM_NAMES = ("total_entropy", "expected_entropy", "mutual_information", "confidence", "brier", "log_score")
+
+
+class EvalUncertaintyArgs(ctypes.Structure):
+    """lbbnn_eval_uncertainty_args_t"""
+    _fields_ = [("logp", c_p), ("m_stride", c_i64), ("ldp", c_i64), ("target", c_p),
+                ("bma_probs", c_p), ("pred_bma", c_p), ("confidence", c_p), ("total_entropy", c_p), ("expected_entropy", c_p),
+                ("mutual_information", c_p), ("brier", c_p), ("log_score", c_p),
+                ("counts", c_p), ("sums", c_p), ("bin_rows", c_p), ("bin_rows_with_target", c_p), ("bin_correct", c_p),
+                ("bin_conf_sum", c_p), ("hist", c_p), ("work", c_p),
+                ("S", c_i), ("B", c_i), ("C", c_i), ("conf_bins", c_i), ("hist_bins", c_i), ("ent_scale", ctypes.c_float)]
+
+
 # name -> (restype, argtypes); must list every symbol include/lbbnn.h declares
 SIGNATURES = {
     "lbbnn_abi_version": (c_i, []),
@@ -352,6 +368,8 @@ SIGNATURES = {
     "lbbnn_frozen_members_dense": (c_i, [ctypes.POINTER(FrozenDesc), ctypes.POINTER(DenseMembers), c_i, c_i, c_p, c_u64, c_p]),
     "lbbnn_eval_metrics_work_bytes": (c_i64, [c_i, c_i, c_i]),
     "lbbnn_eval_metrics": (c_i, [ctypes.POINTER(EvalMetricsArgs), c_p]),
+    "lbbnn_eval_uncertainty_work_bytes": (c_i64, [c_i, c_i, c_i, c_i]),
+    "lbbnn_eval_uncertainty": (c_i, [ctypes.POINTER(EvalUncertaintyArgs), c_p]),
 }
 
 _lib = None

@@ -397,6 +397,35 @@ def _dense_rows(t: torch.Tensor, rows: int, cols: int):
     return t, ld
 
 
+def _member_block(outputs: torch.Tensor, who: str):
+    """(tensor, S, B, C, member stride, row stride) of the (samples, B, classes) fp32 block the metrics kernels read in place: any
+    HIP tensor whose last dimension is dense and whose members do not overlap, else its contiguous copy."""
+    if outputs.dim() != 3:
+        raise ValueError("bnn_amd: outputs must be (samples, B, classes), got %s" % (tuple(outputs.shape),))
+    if not outputs.is_cuda:
+        raise RuntimeError("bnn_amd: %s needs a HIP device tensor (outputs is on %s); there is no CPU path"
+                           % (who, outputs.device))
+    S, B, C = outputs.shape
+    if not 1 <= C <= 64:
+        raise ValueError("bnn_amd: %s takes 1 to 64 classes, got %d" % (who, C))
+    if not 1 <= S <= 65535:
+        raise ValueError("bnn_amd: %s takes 1 to 65535 members, got %d" % (who, S))
+    o = outputs if outputs.dtype == torch.float32 else outputs.float()
+    ldp = o.stride(1) if B > 1 else C
+    ms = o.stride(0) if S > 1 else 0
+    if (C > 1 and o.stride(2) != 1) or ldp < C or (S > 1 and B > 0 and ms < (B - 1) * ldp + C):
+        o, ldp, ms = o.contiguous(), C, B * C
+    return o, S, B, C, ms, ldp
+
+
+def _target_rows(target: torch.Tensor, B: int, dev) -> torch.Tensor:
+    """``target`` as the dense (B,) int64 tensor the metrics kernels read."""
+    if tuple(target.shape) != (B,) or target.device != dev:
+        raise ValueError("bnn_amd: target must be (%d,) on %s, got %s on %s" % (B, dev, tuple(target.shape), target.device))
+    t = target if target.dtype == torch.int64 else target.long()
+    return t if (B < 2 or t.stride(0) == 1) else t.contiguous()
+
+
 @torch.no_grad()
 def ensemble_metrics(outputs: torch.Tensor, target: Optional[torch.Tensor] = None,
                      mean_outputs: Optional[torch.Tensor] = None, *, acc: Optional["EvalAccumulator"] = None) -> Dict[str, object]:
@@ -415,22 +444,8 @@ def ensemble_metrics(outputs: torch.Tensor, target: Optional[torch.Tensor] = Non
     only: an ``EvalAccumulator`` whose running totals this call adds to (``EvalAccumulator.update`` is this call)."""
     import ctypes
     from . import _lib
-    if outputs.dim() != 3:
-        raise ValueError("bnn_amd: outputs must be (samples, B, classes), got %s" % (tuple(outputs.shape),))
-    if not outputs.is_cuda:
-        raise RuntimeError("bnn_amd: ensemble_metrics needs a HIP device tensor (outputs is on %s); there is no CPU path"
-                           % outputs.device)
-    S, B, C = outputs.shape
-    if not 1 <= C <= 64:
-        raise ValueError("bnn_amd: ensemble_metrics takes 1 to 64 classes, got %d" % C)
-    if not 1 <= S <= 65535:
-        raise ValueError("bnn_amd: ensemble_metrics takes 1 to 65535 members, got %d" % S)
+    o, S, B, C, ms, ldp = _member_block(outputs, "ensemble_metrics")
     dev = outputs.device
-    o = outputs if outputs.dtype == torch.float32 else outputs.float()
-    ldp = o.stride(1) if B > 1 else C
-    ms = o.stride(0) if S > 1 else 0
-    if (C > 1 and o.stride(2) != 1) or ldp < C or (S > 1 and B > 0 and ms < (B - 1) * ldp + C):
-        o, ldp, ms = o.contiguous(), C, B * C
     a = _lib.EvalMetricsArgs()
     a.logp, a.m_stride, a.ldp, a.S, a.B, a.C = o.data_ptr(), ms, ldp, S, B, C
     keep = [o]
@@ -442,10 +457,7 @@ def ensemble_metrics(outputs: torch.Tensor, target: Optional[torch.Tensor] = Non
         a.mean_logp, a.ldm = mo.data_ptr(), ldm
         keep.append(mo)
     if target is not None:
-        if tuple(target.shape) != (B,) or target.device != dev:
-            raise ValueError("bnn_amd: target must be (%d,) on %s, got %s on %s" % (B, dev, tuple(target.shape), target.device))
-        t = target if target.dtype == torch.int64 else target.long()
-        t = t if (B < 2 or t.stride(0) == 1) else t.contiguous()
+        t = _target_rows(target, B, dev)
         a.target = t.data_ptr()
         keep.append(t)
     # the per-row outputs as one allocation: [pred_ensemble | pred_posterior_mean] int64, then [mean_log_probs | entropy] fp32
@@ -548,6 +560,207 @@ class EvalAccumulator:
         return res
 
 
+# ----------------------------------------------------------------------------------------- uncertainty on the device
+UNCERTAINTY_ROW_KEYS = ("confidence", "total_entropy", "expected_entropy", "mutual_information", "brier", "log_score")
+OOD_SCORES = ("total_entropy", "mutual_information", "max_prob")
+
+
+def _ent_scale(classes: int, hist_bins: int):
+    """The fp32 factor lbbnn_eval_uncertainty multiplies an entropy by to find its histogram bin: K / ln C (0 for one class)."""
+    import numpy as np
+    return np.float32(hist_bins / math.log(classes)) if classes > 1 else np.float32(0.0)
+
+
+@torch.no_grad()
+def ensemble_uncertainty(outputs: torch.Tensor, target: Optional[torch.Tensor] = None, *,
+                         acc: Optional["UncertaintyAccumulator"] = None) -> Dict[str, object]:
+    """How good the ensemble's uncertainty is, per row, from one (samples, B, classes) block of log-probabilities in ONE
+    lbbnn_eval_uncertainty call (1 launch; 2 with ``acc``) and without a host synchronisation (arithmetic: include/lbbnn.h):
+
+    * ``bma_probs`` (B, classes): the predictive distribution of the Bayesian model average, mean_s exp(outputs[s]);
+      ``pred_bma`` (B,) int64 its argmax (numpy.argmax's rule) and ``confidence`` (B,) its maximum;
+    * ``total_entropy`` = H[p], ``expected_entropy`` = mean_s H[p_s] (the aleatoric part) and ``mutual_information`` = their
+      difference, clamped at 0 (the epistemic part, BALD: large when the members disagree, 0 when each is equally unsure);
+    * with ``target`` (B,): ``brier`` = sum_c (p_c - [c == target])^2 and ``log_score`` = -log p_target, the log score of the
+      model average (not ``nll_sum``'s mean log-probability), finite whenever one member gives the target a finite
+      log-probability; NaN in both for rows without a target inside [0, classes).
+
+    ``outputs``: as ``ensemble_metrics`` takes it (strided views are read in place; classes <= 64).  ``acc``: an
+    ``UncertaintyAccumulator`` whose running totals this call adds to (``UncertaintyAccumulator.update`` is this call)."""
+    import ctypes
+    from . import _lib
+    o, S, B, C, ms, ldp = _member_block(outputs, "ensemble_uncertainty")
+    dev = outputs.device
+    a = _lib.EvalUncertaintyArgs()
+    a.logp, a.m_stride, a.ldp, a.S, a.B, a.C = o.data_ptr(), ms, ldp, S, B, C
+    keep = [o]
+    if target is not None:
+        t = _target_rows(target, B, dev)
+        a.target = t.data_ptr()
+        keep.append(t)
+    # the per-row outputs as one allocation: pred_bma int64, then [bma_probs | the six per-row floats] fp32
+    n = len(UNCERTAINTY_ROW_KEYS)
+    buf = torch.empty(B + (B * C + n * B + 1) // 2, dtype=torch.int64, device=dev)
+    fl = buf[B:].view(torch.float32)
+    res = {"bma_probs": fl[:B * C].view(B, C), "pred_bma": buf[:B]}
+    a.bma_probs, a.pred_bma = fl.data_ptr(), buf.data_ptr()
+    for i, k in enumerate(UNCERTAINTY_ROW_KEYS):
+        res[k] = fl[B * C + i * B:B * C + (i + 1) * B]
+        setattr(a, k, fl.data_ptr() + 4 * (B * C + i * B))
+    if acc is not None:
+        acc._fill(a, S, B, C, dev)
+    if B > 0:                                                # (an empty batch has no storage to point at, and nothing to add)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(_lib.lib().lbbnn_eval_uncertainty(ctypes.byref(a), stream), "lbbnn_eval_uncertainty")
+    if acc is not None:
+        acc.updates += 1
+    del keep
+    return res
+
+
+class UncertaintyAccumulator:
+    """Running uncertainty and calibration totals of an evaluation pass, kept on the device: ``update`` adds a batch (no host
+    read), ``result`` reads them -- one buffer, one copy.  Counts, the sums of the per-row numbers of ``ensemble_uncertainty``,
+    a reliability table over ``conf_bins`` equal-width confidence bins and ``hist_bins``-bin histograms of the three
+    out-of-distribution scores (total entropy and mutual information over [0, ln classes], 1 - confidence over [0, 1]).
+    ``classes`` <= 64, ``samples``, ``conf_bins`` <= 100 and ``hist_bins`` <= 4096 are fixed for the accumulator's life."""
+
+    def __init__(self, classes: int, samples: int, device, conf_bins: int = 20, hist_bins: int = 1024):
+        from . import _lib
+        C, S, M, K = int(classes), int(samples), int(conf_bins), int(hist_bins)
+        if not 1 <= C <= 64:
+            raise ValueError("bnn_amd: UncertaintyAccumulator takes 1 to 64 classes, got %d" % C)
+        if not 1 <= S <= 65535:
+            raise ValueError("bnn_amd: UncertaintyAccumulator takes 1 to 65535 members, got %d" % S)
+        if not 1 <= M <= 100:
+            raise ValueError("bnn_amd: UncertaintyAccumulator takes 1 to 100 confidence bins, got %d" % M)
+        if not 1 <= K <= 4096:
+            raise ValueError("bnn_amd: UncertaintyAccumulator takes 1 to 4096 histogram bins, got %d" % K)
+        self.classes, self.samples, self.conf_bins, self.hist_bins, self.device = C, S, M, K, torch.device(device)
+        self.ent_scale = _ent_scale(C, K)
+        # one buffer, one read: counts | sums | bin_rows | bin_rows_with_target | bin_correct | bin_conf_sum | hist (the doubles
+        # as bit patterns)
+        self._totals = torch.zeros(self._offsets()["end"], dtype=torch.int64, device=self.device)
+        self._work = None
+        self.updates = 0
+
+    def _offsets(self) -> Dict[str, int]:
+        """Where each total starts in the buffer, in 8-byte words."""
+        from . import _lib
+        M, K = self.conf_bins, self.hist_bins
+        off, at = {}, 0
+        for name, n in (("counts", _lib.UNC_COUNTS), ("sums", _lib.UNC_SUMS), ("bin_rows", M), ("bin_rows_with_target", M),
+                        ("bin_correct", M), ("bin_conf_sum", M), ("hist", 3 * K)):
+            off[name] = at
+            at += n
+        off["end"] = at
+        return off
+
+    def _fill(self, a, S, B, C, dev):
+        """Point the totals of an lbbnn_eval_uncertainty_args_t at this accumulator (work memory grows to the largest batch)."""
+        from . import _lib
+        if (S, C) != (self.samples, self.classes):
+            raise ValueError("bnn_amd: this UncertaintyAccumulator was built for %d members and %d classes, the outputs have "
+                             "%d and %d" % (self.samples, self.classes, S, C))
+        if dev != self._totals.device:
+            raise ValueError("bnn_amd: the outputs are on %s, the accumulator on %s" % (dev, self._totals.device))
+        need = int(_lib.lib().lbbnn_eval_uncertainty_work_bytes(S, B, C, self.conf_bins))
+        if self._work is None or self._work.numel() * 8 < need:
+            self._work = torch.empty(need // 8, dtype=torch.float64, device=dev)
+        base = self._totals.data_ptr()
+        for name, at in self._offsets().items():
+            if name != "end":
+                setattr(a, name, base + 8 * at)
+        a.work = self._work.data_ptr()
+        a.conf_bins, a.hist_bins, a.ent_scale = self.conf_bins, self.hist_bins, float(self.ent_scale)
+
+    def update(self, outputs: torch.Tensor, target: Optional[torch.Tensor] = None):
+        """``ensemble_uncertainty(outputs, target)`` of one batch, its numbers added to the totals."""
+        return ensemble_uncertainty(outputs, target, acc=self)
+
+    def reset(self):
+        self._totals.zero_()
+        self.updates = 0
+
+    def _read(self):
+        """The totals as a host int64 array (the one device-to-host copy)."""
+        return self._totals.cpu().numpy()
+
+    def result(self, strict: bool = True) -> Dict[str, object]:
+        """Python numbers and numpy arrays.  The raw totals: the counts ``rows``, ``rows_with_target``, ``bad_targets``,
+        ``correct_bma``, ``nonfinite_rows`` (rows whose confidence, entropies or mutual information are not finite: they are in
+        no sum, bin or histogram), ``log_score_nonfinite``; ``<name>_sum`` for total_entropy, expected_entropy,
+        mutual_information, confidence (over the finite rows), brier and log_score (over the finite rows with a target);
+        ``bin_rows``, ``bin_rows_with_target``, ``bin_correct``, ``bin_conf_sum`` (conf_bins,).  Derived: ``<name>_mean``,
+        ``accuracy_bma``, ``ece`` = sum_m n_m / N |correct_m / n_m - conf_sum_m / n_m| and ``mce`` (the largest gap) over the
+        rows with a target, empty bins skipped; ``reliability`` (per bin: ``edges``, ``rows``, ``rows_with_target``,
+        ``accuracy``, ``confidence``); ``selective`` (per threshold k / conf_bins: ``coverage`` and ``accuracy`` of the rows with
+        a target whose confidence is at least the threshold -- what abstaining below it would give); ``histograms``: for each of
+        ``OOD_SCORES`` its ``counts`` and ``edges`` (``max_prob`` is the histogram of 1 - confidence, so that a higher score
+        means less certain in all three).  NaN where a denominator is 0.  ``strict``: as ``EvalAccumulator.result``."""
+        import numpy as np
+        from . import _lib
+        h = np.ascontiguousarray(self._read(), dtype=np.int64)
+        off, M, K, C = self._offsets(), self.conf_bins, self.hist_bins, self.classes
+        res = {k: int(h[off["counts"] + i]) for i, k in enumerate(_lib.UNC_COUNT_NAMES)}
+        if strict and res["bad_targets"]:
+            raise IndexError("bnn_amd: %d target(s) outside [0, %d) in this evaluation pass" % (res["bad_targets"], C))
+        res.update(classes=C, samples=self.samples, conf_bins=M, hist_bins=K)
+        part = lambda name, n: h[off[name]:off[name] + n]
+        sums = part("sums", _lib.UNC_SUMS).view(np.float64)
+        n_rows, n_t, n_c = part("bin_rows", M).copy(), part("bin_rows_with_target", M).copy(), part("bin_correct", M).copy()
+        conf_sum = part("bin_conf_sum", M).view(np.float64).copy()
+        res.update(bin_rows=n_rows, bin_rows_with_target=n_t, bin_correct=n_c, bin_conf_sum=conf_sum)
+        div = lambda x, d: x / d if d else float("nan")
+        nf, N = res["rows"] - res["nonfinite_rows"], int(n_t.sum())
+        for i, k in enumerate(_lib.UNC_SUM_NAMES):
+            res[k + "_sum"] = float(sums[i])
+            res[k + "_mean"] = div(float(sums[i]), nf if i < 4 else N if k == "brier" else N - res["log_score_nonfinite"])
+        res["accuracy_bma"] = div(res["correct_bma"], res["rows_with_target"])
+        full = n_t > 0
+        with np.errstate(all="ignore"):
+            acc_m, conf_m = n_c / n_t, conf_sum / n_t          # NaN in the empty bins
+        gap = np.abs(acc_m[full] - conf_m[full])
+        res["ece"] = float((n_t[full] / N * gap).sum()) if N else float("nan")
+        res["mce"] = float(gap.max()) if N else float("nan")
+        res["reliability"] = {"edges": np.arange(M + 1) / M, "rows": n_rows, "rows_with_target": n_t, "accuracy": acc_m,
+                              "confidence": conf_m}
+        kept_t, kept_c = n_t[::-1].cumsum()[::-1], n_c[::-1].cumsum()[::-1]      # bins k .. M-1: confidence >= k / M
+        with np.errstate(all="ignore"):
+            res["selective"] = {"threshold": np.arange(M) / M, "coverage": kept_t / N if N else np.full(M, np.nan),
+                                "accuracy": kept_c / kept_t}
+        hist = part("hist", 3 * K).reshape(3, K)
+        ent_edges = np.arange(K + 1) * (math.log(C) / K if C > 1 else 0.0)
+        res["histograms"] = {k: {"counts": hist[i].copy(), "edges": ent_edges if i < 2 else np.arange(K + 1) / K}
+                             for i, k in enumerate(OOD_SCORES)}
+        return res
+
+
+def ood_auroc(in_result: Dict[str, object], out_result: Dict[str, object], score: str = "total_entropy"):
+    """``(auroc, half_width)`` of telling an out-of-distribution pass from an in-distribution pass by ``score``
+    ("total_entropy" | "mutual_information" | "max_prob": 1 - confidence; higher = out of distribution), from the histograms
+    of two ``UncertaintyAccumulator.result()``s -- the reference's outofsample study (the entropy CDFs of FMNIST / KMNIST against
+    MNIST) as one number.  Pairs that fall in the same bin count 1/2; ``half_width`` = 0.5 sum_k in_k out_k / (N_in N_out) is
+    what they could change, so the AUROC of the per-row scores themselves lies in [auroc - half_width, auroc + half_width].
+    Both passes must have the same number of classes and histogram bins (ValueError)."""
+    import numpy as np
+    if score not in OOD_SCORES:
+        raise ValueError("bnn_amd: score must be one of %s, got %r" % (OOD_SCORES, score))
+    for k in ("classes", "hist_bins"):
+        if in_result[k] != out_result[k]:
+            raise ValueError("bnn_amd: ood_auroc needs two passes with the same %s, got %d and %d" % (k, in_result[k], out_result[k]))
+    hi = np.asarray(in_result["histograms"][score]["counts"], dtype=np.int64)
+    ho = np.asarray(out_result["histograms"][score]["counts"], dtype=np.int64)
+    n_in, n_out = int(hi.sum()), int(ho.sum())
+    if not n_in or not n_out:
+        return float("nan"), float("nan")
+    below = np.concatenate([[0], hi.cumsum()[:-1]])            # in-distribution rows in lower bins
+    ties = int((hi * ho).sum())
+    pairs = n_in * n_out
+    return (int((ho * below).sum()) + 0.5 * ties) / pairs, 0.5 * ties / pairs
+
+
 def _eval_forwards(net, data, samples: int, posterior_mean: bool, gates: str):
     """(outputs, mean_outputs or None) of one batch, by family, as ``ensemble_eval`` dispatches."""
     if _is_frozen(net):
@@ -571,21 +784,30 @@ def _eval_forwards(net, data, samples: int, posterior_mean: bool, gates: str):
 
 @torch.no_grad()
 def evaluate_batches(net, batches, samples: int = 10, *, acc: Optional[EvalAccumulator] = None, posterior_mean: bool = True,
-                     gates: str = "sample") -> Dict[str, object]:
+                     gates: str = "sample", uncertainty: Optional[UncertaintyAccumulator] = None) -> Dict[str, object]:
     """A whole evaluation pass with ONE host synchronisation: for every ``(x, y)`` of ``batches`` (device tensors) the ensemble
     forward of the network's family -- ``ensemble_forward`` / ``FrozenNetwork.ensemble`` / ``base_ensemble`` / ``vd_ensemble``,
     the dispatch and the draws of ``ensemble_eval`` -- the posterior-mean forward where the family has one (``posterior_mean``;
     variational dropout has none) and ``acc.update``; returns ``acc.result()``.  ``acc``: an ``EvalAccumulator`` to add to
-    (default: a fresh one).  ``gates="mpm"``: the median probability model of a baseline network."""
+    (default: a fresh one).  ``gates="mpm"``: the median probability model of a baseline network.
+    ``uncertainty``: an ``UncertaintyAccumulator`` that is updated from the same ``outputs`` in the same pass (one more
+    lbbnn_eval_uncertainty call per batch, no host read); its ``result()`` -- one more copy at the end -- is merged into the
+    returned dict under its own keys (the three counts both keep, ``rows``, ``rows_with_target`` and ``bad_targets``, are
+    ``acc``'s)."""
     S = int(samples)
     for x, y in batches:
         outputs, mean = _eval_forwards(net, x, S, posterior_mean, gates)
         if acc is None:
             acc = EvalAccumulator(outputs.shape[-1], S, outputs.device)
         acc.update(outputs, y, mean)
+        if uncertainty is not None:
+            uncertainty.update(outputs, y)
     if acc is None:
         raise ValueError("bnn_amd: evaluate_batches got no batches and no accumulator")
-    return acc.result()
+    res = acc.result()
+    if uncertainty is not None:
+        res.update((k, v) for k, v in uncertainty.result().items() if k not in res)
+    return res
 
 
 # ----------------------------------------------------------------------------------------- frozen evaluation model

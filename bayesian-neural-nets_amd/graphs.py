@@ -175,7 +175,7 @@ def make_graphed_train_step(net, optimizer, loss_fn, example_x, example_y, warmu
     return step
 
 
-def make_graphed_eval_step(frozen, example_x, example_y, samples: int, acc, warmup: int = 2):
+def make_graphed_eval_step(frozen, example_x, example_y, samples: int, acc, warmup: int = 2, uncertainty=None):
     """One evaluation step of a frozen model (``evaluate.freeze``: LRT, MNF with planar or dense z flows) as ONE HIP graph on a
     single stream, no forked branches: ``frozen.ensemble(x, samples)``, the posterior-mean forward ``frozen(x, sample=False)``
     and ``acc.update`` (lbbnn_eval_metrics: the metrics and the running totals of ``acc``, an ``evaluate.EvalAccumulator``).
@@ -183,7 +183,10 @@ def make_graphed_eval_step(frozen, example_x, example_y, samples: int, acc, warm
     -- the members the eager calls would draw from the same offset.  The warm-up steps run eagerly first (buffers exist before
     the capture); the Philox state and ``acc``'s totals are put back afterwards, so building the step changes neither.
     Returns ``step(x, y)`` -> the per-row dict of ``acc.update`` (static buffers, overwritten by the next replay); read the
-    totals with ``acc.result()`` when the pass is over."""
+    totals with ``acc.result()`` when the pass is over.
+    ``uncertainty``: an ``evaluate.UncertaintyAccumulator`` updated from the same ``outputs`` in the same graph, on the same
+    stream (lbbnn_eval_uncertainty after lbbnn_eval_metrics); its totals and update count are put back after the warm-up too,
+    and its per-row numbers join the returned dict under their own keys."""
     from . import evaluate, ops
     if not evaluate._is_frozen(frozen):
         raise TypeError("bnn_amd.graphs.make_graphed_eval_step takes a frozen model (evaluate.freeze), got %s"
@@ -196,10 +199,15 @@ def make_graphed_eval_step(frozen, example_x, example_y, samples: int, acc, warm
 
     def body():
         outputs = frozen.ensemble(static_x, S)
-        return acc.update(outputs, static_y, frozen(static_x, sample=False))
+        rows = acc.update(outputs, static_y, frozen(static_x, sample=False))
+        if uncertainty is not None:
+            rows.update(uncertainty.update(outputs, static_y))
+        return rows
 
     st = ops.RngState.get(dev)
     rng0, totals0, counts0 = st.t.clone(), acc._totals.clone(), (acc.updates, acc.posterior_mean_updates)
+    if uncertainty is not None:
+        u_totals0, u_updates0 = uncertainty._totals.clone(), uncertainty.updates
     side = torch.cuda.Stream(device=dev)
     side.wait_stream(torch.cuda.current_stream(dev))
     with torch.cuda.stream(side):
@@ -207,13 +215,19 @@ def make_graphed_eval_step(frozen, example_x, example_y, samples: int, acc, warm
             body()
         st.t.copy_(rng0)
         acc._totals.copy_(totals0)
+        if uncertainty is not None:
+            uncertainty._totals.copy_(u_totals0)
     torch.cuda.current_stream(dev).wait_stream(side)
     acc.updates, acc.posterior_mean_updates = counts0
+    if uncertainty is not None:
+        uncertainty.updates = u_updates0
     graph = torch.cuda.CUDAGraph()
     torch.cuda.synchronize(dev)
     with capture(graph):
         rows = body()
     acc.updates, acc.posterior_mean_updates = counts0        # the capture enqueued nothing
+    if uncertainty is not None:
+        uncertainty.updates = u_updates0
 
     def step(x, y):
         if x.data_ptr() != static_x.data_ptr():
@@ -222,6 +236,8 @@ def make_graphed_eval_step(frozen, example_x, example_y, samples: int, acc, warm
             static_y.copy_(y)
         graph.replay()
         acc._note(True)
+        if uncertainty is not None:
+            uncertainty.updates += 1
         return rows
 
     step.graph = graph

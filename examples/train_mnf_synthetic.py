@@ -103,3 +103,18 @@ if FLOWS in ("Planar", "RNVP", "MNF"):
     tot = acc.result()
     print("graphed test pass: ensemble %.3f | posterior mean %.3f | confusion matrix diagonal %s"
           % (tot["accuracy_ensemble"], tot["accuracy_posterior_mean"], tot["confusion"].diagonal().tolist()))
+
+# How good is the uncertainty?  One in-distribution pass and one pass on noise inputs through an UncertaintyAccumulator each
+# (lbbnn_eval_uncertainty next to lbbnn_eval_metrics, the totals read once per pass): calibration, the epistemic part of the
+# predictive entropy, and the out-of-distribution study of outofsample on FMNIST / KMNIST (LBBNN-GP-MF-LRT.py:283-286) as an AUROC.
+ev = bnn_amd.evaluate
+noise_batches = [(torch.randn(BATCH_SIZE, 1, 28, 28, device=DEVICE, generator=g), by) for _, by in test_batches]
+passes = []
+for batches in (test_batches, noise_batches):
+    u = ev.UncertaintyAccumulator(10, TEST_SAMPLES, DEVICE)
+    passes.append(ev.evaluate_batches(model, batches, samples=TEST_SAMPLES, uncertainty=u))
+auroc, half_width = ev.ood_auroc(passes[0], passes[1], score="mutual_information")
+print("uncertainty: ECE %.3f | Brier %.3f | log score %.3f | mean mutual information in-distribution %.4f, on noise %.4f | "
+      "AUROC noise against test by mutual information %.3f +- %.3f"
+      % (passes[0]["ece"], passes[0]["brier_mean"], passes[0]["log_score_mean"], passes[0]["mutual_information_mean"],
+         passes[1]["mutual_information_mean"], auroc, half_width))

@@ -1227,6 +1227,93 @@ typedef struct lbbnn_eval_metrics_args {
 int64_t lbbnn_eval_metrics_work_bytes(int S, int B, int C);
 int lbbnn_eval_metrics(const lbbnn_eval_metrics_args_t* args, void* stream);
 
+/* lbbnn_eval_uncertainty -- how good the ensemble's uncertainty is, from the same (S members, B rows, C classes) block of
+ * log-probabilities lbbnn_eval_metrics reads: the predictive distribution of the Bayesian model average, its entropy split into
+ * the expected (aleatoric) part and the mutual information between prediction and parameters (epistemic, BALD), the proper
+ * scores (Brier, log score), and running totals for reliability tables (ECE / MCE, accuracy against coverage) and score
+ * histograms (AUROC between two passes).  No host synchronisation, no allocation.  Launches: 1, or 2 with totals (the second,
+ * one workgroup, adds the double sums); B == 0: a successful no-op, no launch.
+ *
+ * Inputs.  logp, m_stride, ldp, target, S, B, C: as lbbnn_eval_metrics.  conf_bins M (1..100) and hist_bins K (1..4096) matter
+ * with totals only.  ent_scale: the fp32 factor that maps an entropy to a histogram bin, computed by the caller as
+ * (float)(K / ln C) and 0 for C == 1 (finite and >= 0, LBBNN_E_SHAPE otherwise); the kernel multiplies by it and never takes
+ * log(C) itself, so the bin of a stored value is reproducible on the CPU.
+ *
+ * Per-row outputs, each optional (NULL = not written), fp32 except the prediction; exp / log are the device's expf / logf:
+ *   bma_probs[b * C + c]   pbar: acc = expf(logp[0]); acc += expf(logp[m]) for m = 1 .. S-1 ascending; then acc / (float)S by IEEE
+ *                          division.
+ *   pred_bma[b] (int64)    argmax over c of bma_probs[b] by numpy.argmax's rule (a NaN is the maximum, the lowest index wins).
+ *   confidence[b]          the maximum of bma_probs[b]: the stored value of class pred_bma[b], bit for bit.
+ *   total_entropy[b]       -sum_c pbar * logf(pbar), a term being 0 where pbar == 0.  With S == 1, where pbar = expf(l) and its
+ *                          logarithm is l itself, the value of expected_entropy[b]: the mutual information of one member is
+ *                          then exactly 0.
+ *   expected_entropy[b]    h_m = -sum_c expf(l) * l over the classes of member m (a term being 0 where expf(l) == 0), summed
+ *                          in member order, / (float)S.
+ *   mutual_information[b]  d = total_entropy - expected_entropy; 0 where d < 0 (rounding: the exact value is >= 0), else d -- a
+ *                          NaN stays a NaN.
+ *   brier[b]               sum_c (pbar_c - [c == target])^2; NaN for a row without a target inside [0, C).
+ *   log_score[b]           -(logsumexp_m logp[m][b][target] - logf((float)S)), the log score of pbar at the target, as a
+ *                          streaming logsumexp: the running maximum mx of the members seen so far is subtracted before every
+ *                          expf (s = s * expf(mx_old - l) + 1 when l raises the maximum, s += expf(l - mx) otherwise; a member
+ *                          at -inf adds nothing), then mx + logf(s).  Finite whenever one member's log-probability of the
+ *                          target is finite -- -logf(pbar_target) is not (it is inf once every expf underflows).  NaN for a
+ *                          row without a valid target.
+ *
+ * Running totals: counts, sums, the four bin arrays, hist and work are given together or not at all.  They are ADDED TO; the
+ * caller zeroes them.  A row is FINITE when its confidence, total entropy, expected entropy and mutual information all are.
+ *   counts[LBBNN_UNC_COUNTS] (int64), in this order:
+ *     rows, rows_with_target, bad_targets (as lbbnn_eval_metrics), correct_bma (pred_bma == target, every row with a valid
+ *     target), nonfinite_rows (rows that are not finite: they enter no sum, bin or histogram below), log_score_nonfinite
+ *     (finite rows with a valid target whose log_score is inf or NaN: left out of the log-score sum only)
+ *   sums[LBBNN_UNC_SUMS] (double), in this order: total entropy, expected entropy, mutual information, confidence over the
+ *     finite rows; Brier over the finite rows with a valid target; log score over those of them where it is finite.
+ *   reliability bins, M entries each, bin m = clamp((int)(confidence * (float)M), 0, M - 1):
+ *     bin_rows (int64, finite rows), bin_rows_with_target (int64, finite rows with a valid target), bin_correct (int64, those
+ *     with pred_bma == target), bin_conf_sum (double, the confidence of the finite rows with a valid target)
+ *   hist[3 * K] (int64) over the finite rows, bin k = clamp((int)(v * scale), 0, K - 1): hist[k] of v = total_entropy and
+ *     hist[K + k] of v = mutual_information with scale = ent_scale, hist[2 * K + k] of v = 1.0f - confidence with scale =
+ *     (float)K.
+ *   Every product is a single fp32 multiplication; it is clamped to [0, bins] as a float before the conversion (a product
+ *   that overflowed lands in the last bin), so no index is ever taken from a value an int cannot hold.
+ * Every total is bitwise reproducible from run to run: the integers are counted per workgroup and added with integer atomics
+ * (exact); each workgroup adds its rows' doubles in row order and leaves 6 + M partials in `work`, which the second launch
+ * adds in a fixed order -- no float atomics.
+ * work: lbbnn_eval_uncertainty_work_bytes(S, B, C, conf_bins) bytes (> 0 for every valid shape, non-decreasing in B; 0 for an
+ * invalid one), 8-B aligned.
+ *
+ * Checks, before anything is launched: a NULL args / logp, some but not all of the totals pointers: LBBNN_E_NULL.  S, C or B
+ * out of range, ldp < C, a short m_stride (as lbbnn_eval_metrics), and with totals conf_bins, hist_bins or ent_scale out of
+ * range: LBBNN_E_SHAPE.  A pointer off its natural alignment: LBBNN_E_ALIGN. */
+#define LBBNN_UNC_COUNTS 6
+#define LBBNN_UNC_SUMS 6
+typedef struct lbbnn_eval_uncertainty_args {
+    const float* logp;
+    int64_t m_stride, ldp;
+    const int64_t* target;
+    float* bma_probs;
+    int64_t* pred_bma;
+    float* confidence;
+    float* total_entropy;
+    float* expected_entropy;
+    float* mutual_information;
+    float* brier;
+    float* log_score;
+    int64_t* counts;
+    double* sums;
+    int64_t* bin_rows;
+    int64_t* bin_rows_with_target;
+    int64_t* bin_correct;
+    double* bin_conf_sum;
+    int64_t* hist;
+    void* work;
+    int S, B, C;
+    int conf_bins, hist_bins;
+    float ent_scale;
+} lbbnn_eval_uncertainty_args_t;
+
+int64_t lbbnn_eval_uncertainty_work_bytes(int S, int B, int C, int conf_bins);
+int lbbnn_eval_uncertainty(const lbbnn_eval_uncertainty_args_t* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
