@@ -30,7 +30,22 @@ class Priors(ctypes.Structure):
 
 
 MAX_FLOW_T = 16
-MAX_LAYERS = 4
+MAX_LAYERS = 4            # LBBNN_MAX_LAYERS: layers per batched launch
+MAX_DEPTH = 16            # LBBNN_MAX_DEPTH: layers per network (Philox stream ids are kind * 64 + layer id)
+
+
+def layer_groups(n: int):
+    """[(first layer, count)] of the ceil(n / MAX_LAYERS) groups of consecutive layers in which a network of n layers issues
+    its batched C calls (every struct array of such a call holds MAX_LAYERS entries)."""
+    return [(k, min(MAX_LAYERS, n - k)) for k in range(0, n, MAX_LAYERS)]
+
+
+def group_slice(arr, first: int, count: int):
+    """Entries first .. first + count - 1 of a ctypes struct array as an array of their own over the SAME memory (the view
+    keeps ``arr`` alive): what a group's call is given."""
+    if first == 0 and count == len(arr):
+        return arr
+    return (arr._type_ * count).from_buffer(arr, first * ctypes.sizeof(arr._type_))
 
 
 class PlanarFlow(ctypes.Structure):
@@ -341,6 +356,7 @@ SIGNATURES = {
     "lbbnn_layers_operands": (c_i, [ctypes.POINTER(LayerDesc), c_i, c_p, c_p]),
     "lbbnn_layers_finalize": (c_i, [ctypes.POINTER(LayerDesc), c_i, c_p, ctypes.c_uint64, c_p, c_p]),
     "lbbnn_forward_finish": (c_i, [c_p, c_u64, c_p, c_i, c_p, c_p]),
+    "lbbnn_kl_total": (c_i, [c_p, c_i, c_p, c_p]),
     "lbbnn_gate_sample": (c_i, [ctypes.POINTER(GateArgs), c_p, c_p]),
     "lbbnn_vd_operands": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     "lbbnn_weight_operands_t": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),

@@ -708,6 +708,14 @@ __global__ void forward_finish_kernel(const FinishArgs a) {
     if (a.rng) a.rng[1] += a.delta;
 }
 
+// lbbnn_kl_total: the network KL of more than LBBNN_MAX_LAYERS layers, whose finalize launches (one per group of layers)
+// left the per-layer values side by side -- the same fp32 left fold, in layer order, as the two kernels above
+__global__ void kl_total_kernel(const float* kl, int n, float* total) {
+    float s = 0.f;
+    for (int i = 0; i < n; ++i) s += kl[i];
+    *total = s;
+}
+
 __global__ __launch_bounds__(256) void philox_normal_kernel(const uint64_t* rng, uint32_t stream, long long row_base,
                                                             long long rows, long long cols, float* out) {
     // one counter (4 normals) per thread.  2-D (rows > 0): out[r][c] = N(ctr0 = row_base + r, ctr1 = c/4)[c%4],
@@ -909,6 +917,13 @@ extern "C" int lbbnn_forward_finish(uint64_t* rng, uint64_t advance, const float
     for (int i = 0; i < LBBNN_MAX_LAYERS; ++i) a.kl[i] = (kl_total && i < n) ? kl_layers[i] : nullptr;
     for (int i = 0; i < a.n; ++i) if (!a.kl[i]) return LBBNN_E_NULL;
     hipLaunchKernelGGL(forward_finish_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int lbbnn_kl_total(const float* kl_layers, int n, float* total, void* stream) {
+    if (!kl_layers || !total) return LBBNN_E_NULL;
+    if (n < 1 || n > LBBNN_MAX_DEPTH) return LBBNN_E_SHAPE;
+    hipLaunchKernelGGL(kl_total_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), kl_layers, n, total);
     return (int)hipGetLastError();
 }
 

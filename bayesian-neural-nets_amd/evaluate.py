@@ -93,7 +93,9 @@ def ensemble_forward_batched(net, data: torch.Tensor, samples: int = 10) -> torc
             descs[i].z_fwd = z.data_ptr()
         descs[i].eps_z = None
     stream = torch.cuda.current_stream(dev).cuda_stream
-    _lib.check(_lib.lib().lbbnn_ensemble_operands(descs, n, S, rng.data_ptr(), 1, stream), "lbbnn_ensemble_operands")
+    for k, cnt in _lib.layer_groups(n):                        # (every group reads the same live offset; advanced once, below)
+        _lib.check(_lib.lib().lbbnn_ensemble_operands(_lib.group_slice(descs, k, cnt), cnt, S, rng.data_ptr(), 1, stream),
+                   "lbbnn_ensemble_operands")
     h, h_ms = x, 0                                             # the first layer reads the same rows for every member
     for i, l in enumerate(layers):
         O, I = l.out_features, l.in_features
@@ -317,7 +319,7 @@ def ensemble_eval(net, data: torch.Tensor, target: Optional[torch.Tensor] = None
     outputs = ensemble_forward(net, data, samples)
     density = []
     for _ in range(samples):
-        g = [l.gamma.rsample().flatten() for l in (net.l1, net.l2, net.l3)]
+        g = [l.gamma.rsample().flatten() for l in net._layers()]
         density.append(torch.cat(g).mean())
     pred_ens = outputs.mean(0).argmax(1)
     pred_mean = net(data, sample=False).argmax(1)
@@ -1032,7 +1034,8 @@ class FrozenNetwork(nn.Module):
         descs = self._descs(layers)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(_lib.lib().lbbnn_frozen_operands(descs, self.n_layers, stream), "lbbnn_frozen_operands")
+            for k, cnt in _lib.layer_groups(self.n_layers):
+                _lib.check(_lib.lib().lbbnn_frozen_operands(_lib.group_slice(descs, k, cnt), cnt, stream), "lbbnn_frozen_operands")
         return self
 
     # ------------------------------------------------------------------------------------- evaluation
@@ -1091,10 +1094,13 @@ class FrozenNetwork(nn.Module):
                 if masks is not None:
                     masks.append(_empty((c, self._T[i], self.dims[i]), dtype=torch.float32, device=zbuf.device))
                     d.mask_out = masks[-1].data_ptr()
-            _lib.check(_lib.lib().lbbnn_frozen_members_dense(descs, fl, self.n_layers, c, rng.data_ptr(), 1, stream),
-                       "lbbnn_frozen_members_dense")
+            for k, cnt in _lib.layer_groups(self.n_layers):      # one z buffer, one call per group; the caller advances once
+                _lib.check(_lib.lib().lbbnn_frozen_members_dense(_lib.group_slice(descs, k, cnt), _lib.group_slice(fl, k, cnt), cnt,
+                                                                 c, rng.data_ptr(), 1, stream), "lbbnn_frozen_members_dense")
             return zbuf, ewm
-        _lib.check(_lib.lib().lbbnn_frozen_members(descs, self.n_layers, c, rng.data_ptr(), 1, stream), "lbbnn_frozen_members")
+        for k, cnt in _lib.layer_groups(self.n_layers):
+            _lib.check(_lib.lib().lbbnn_frozen_members(_lib.group_slice(descs, k, cnt), cnt, c, rng.data_ptr(), 1, stream),
+                       "lbbnn_frozen_members")
         return zbuf, ewm
 
     def _z_of(self, zbuf, c):
@@ -1228,8 +1234,8 @@ class FrozenNetwork(nn.Module):
 
 def _check_freezable_layers(layers, dense: bool = False):
     from . import _lib
-    if len(layers) > _lib.MAX_LAYERS:
-        raise ValueError("bnn_amd: freeze takes networks of at most %d layers" % _lib.MAX_LAYERS)
+    if len(layers) > _lib.MAX_DEPTH:
+        raise ValueError("bnn_amd: freeze takes networks of at most %d layers" % _lib.MAX_DEPTH)
     for i, l in enumerate(layers):
         if l.noise:
             raise ValueError("bnn_amd: layer %d has injected noise (layer.noise); a frozen model draws in-kernel noise only -- "

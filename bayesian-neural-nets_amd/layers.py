@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _grad, ops
+from . import _grad, _lib, ops
 from ._lib import Priors
 from .distributions import Bernoulli, Gaussian
 from .flows import PropagateFlow
@@ -166,6 +166,7 @@ def _file_adoption_checks(layer, grads):
 
 
 _layer_ids = itertools.count()
+MAX_DEPTH = 16            # layers of one network: layer i draws from Philox stream kind * 64 + i (lbbnn.h LBBNN_MAX_DEPTH)
 
 
 class _BayesLinearFn(torch.autograd.Function):
@@ -503,6 +504,7 @@ class _BayesLinearBase(nn.Module):
         self._mask_pool = None         # Bernoulli masks pre-drawn by the network for this call (one launch for all layers)
         self._preprep = None           # K3 / K1 of this call already run by the network (one launch per kind for all layers)
         self._lsm_now = False          # set by the network around the head's training forward: log_softmax in the GEMM epilogue
+        self._kl_slot = None           # set by a network deeper than one batched launch: this call's KL goes into its buffer
         self._last_masks = None
 
     # reference keeps the prior tensors as attributes; expose them lazily with the same names
@@ -614,7 +616,7 @@ class _BayesLinearBase(nn.Module):
             pre_ = self._preprep
             # (a network that drives its layers takes ONE snapshot of the shared state for all of them)
             saved["rng"] = (pre_["snap"] if (pre_ is not None and pre_.get("snap") is not None) else rng.clone()) if save_rng else None
-        kl = torch.empty((), dtype=torch.float32, device=x.device) if cfg[1] else None
+        kl = (self._kl_slot if self._kl_slot is not None else torch.empty((), dtype=torch.float32, device=x.device)) if cfg[1] else None
         self._cur_B = x.shape[0]
         self._split_now = self._split(x, cfg)
         self._last_masks = None
@@ -1062,7 +1064,9 @@ class MNFBayesianLinear(_BayesLinearBase):
 
 
 class _NetworkBase(nn.Module):
-    """3-layer MLP of Bayesian layers: ReLU, ReLU, log_softmax (LBBNN-GP-MF-LRT.py:206-214).
+    """MLP of 1 to MAX_DEPTH Bayesian layers l1 .. lN: ReLU between them, log_softmax after the last (three layers in the
+    reference, LBBNN-GP-MF-LRT.py:206-214).  The batched C calls take _lib.MAX_LAYERS layers per launch: a deeper network
+    issues them in groups of consecutive layers (_lib.layer_groups), all reading one Philox snapshot.
 
     Without autograd the forward is ONE stream and 5 launches (``_forward_streams``): the x-independent kernels of
     all layers batched into one launch per kind (flows, weight pass), and the three GEMMs with ReLU / log_softmax fused
@@ -1075,8 +1079,23 @@ class _NetworkBase(nn.Module):
     _train_kl_total = None        # training forward: the network KL as summed on the device by the KL finalize (else None)
     _pre_shared = None
 
+    _lnames = ()
+
+    def _build(self, dims, make):
+        """l1 .. lN from dims, created layer by layer in order (the seeded initial values depend on it)."""
+        dims = tuple(int(d) for d in dims)
+        if not 2 <= len(dims) <= MAX_DEPTH + 1:
+            raise ValueError("bnn_amd: %s takes 1 to %d layers (len(dims) 2 to %d), got dims=%s"
+                             % (type(self).__name__, MAX_DEPTH, MAX_DEPTH + 1, dims))
+        self.dims = dims
+        self._lnames = tuple("l%d" % (i + 1) for i in range(len(dims) - 1))
+        for i, name in enumerate(self._lnames):
+            setattr(self, name, make(dims[i], dims[i + 1]))
+        self._number_layers()
+
     def _layers(self):
-        return [self.l1, self.l2, self.l3]
+        m = self._modules
+        return [m[k] for k in self._lnames]
 
     def _number_layers(self):
         """Philox stream ids 0..n-1 inside a network (a stand-alone layer takes the next id of a process-wide counter):
@@ -1128,6 +1147,13 @@ class _NetworkBase(nn.Module):
                 self._predraw_masks([l for l in layers if l._mnf and l._check_flows() == "dense"])
                 self._preflow_dense(layers, sample)
                 self._preprep_all(layers, sample, x)
+            kl_buf = None
+            if shared and len(layers) > _lib.MAX_LAYERS and all(l.training for l in layers):
+                # deeper than one batched launch: the layers run one by one, each KL tail writes its slot of one buffer and
+                # lbbnn_kl_total adds them in layer order -- net.kl() stays ONE device total (losses._SumKLFn)
+                kl_buf = torch.empty(len(layers) + 1, dtype=torch.float32, device=x.device)
+                for i, l in enumerate(layers):
+                    l._kl_slot = kl_buf[i]
             fused_lsm = False
             try:
                 for i, l in enumerate(layers):
@@ -1136,16 +1162,19 @@ class _NetworkBase(nn.Module):
                     # autograd node then returns log-probabilities and its backward starts with lbbnn_log_softmax_backward
                     l._lsm_now = bool(shared and i == len(layers) - 1 and l.out_features <= 16 and (l.training or sample))
                     fused_lsm = l._lsm_now
-                    x = l.forward(x, sample, _relu=(i < 2))           # F.relu fused into the GEMM epilogue
+                    x = l.forward(x, sample, _relu=(i < len(layers) - 1))   # F.relu fused into the GEMM epilogue
             finally:
                 for l in layers:
                     l._advance_rng = True
                     l._lsm_now = False
+                    l._kl_slot = None
             if shared:
                 sh = self._pre_shared
                 if not (sh is not None and sh.get("advanced")):
                     ops.RngState.get(x.device).advance(1)
                 self._train_kl_total = sh["kl_total"] if (sh is not None and sh.get("hosted") and sh.get("kl_total") is not None) else None
+                if kl_buf is not None:
+                    self._train_kl_total = ops.kl_total(kl_buf, len(layers))
                 self._pre_shared = None
             return x if fused_lsm else F.log_softmax(x, dim=1)       # …LRT.py:210
         return self._forward_streams(x.float(), sample)
@@ -1295,7 +1324,7 @@ class _NetworkBase(nn.Module):
         if dense:
             self._predraw_masks([l for l, _ in dense])
             same = len({(len(l.z_flow.transforms), len(l.r_flow.transforms), c[1]) for l, c in dense}) == 1
-            groups = [dense] if same else [[lc] for lc in dense]
+            groups = ([dense[k:k + cnt] for k, cnt in _lib.layer_groups(len(dense))] if same else [[lc] for lc in dense])
             # (only while a HIP graph is being captured: launched from Python the two event calls and the stream switch cost the
             # host more than the overlap returns -- RNVP forward 0.405 -> 0.454 ms eager, 0.237 -> 0.226 ms replayed)
             # (not where the second GEMM folds the <= 16-class head into its epilogue -- a three-layer row-scaled fp16 network:
@@ -1332,6 +1361,10 @@ class _NetworkBase(nn.Module):
         # snapshots the Philox state for the rest of this forward.  The live offset is advanced by the extra workgroup of
         # the first GEMM's launch (lbbnn_lrt_gemm_finalize_adv): every workgroup of THIS launch reads it.
         snap = st.t[2:4] if st is not None else None
+        # (a network deeper than one batched launch: the FIRST group's call takes the snapshot, the others read it)
+        lgroups = _lib.layer_groups(n)
+        n0 = lgroups[0][1]
+        d0 = _lib.group_slice(descs, 0, n0)
         # A first layer in the row-scaled fp16 format reads its x as fp16 hi | lo planes: the format pass over the network
         # input rides in the SAME launch as the planar flows (lbbnn_layers_operands_x: extra workgroups on the CUs the two
         # flow workgroups per layer leave idle), so the first GEMM spends no VALU on the split and no launch is added.
@@ -1339,15 +1372,19 @@ class _NetworkBase(nn.Module):
         if (layers[0]._split_now >= 2 and _F16_FIRST_PLANES and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
                 and B > 0):
             xp = self._planes("in", B, layers[0].in_features, dev, plan)
-            _lib.check(_lib.lib().lbbnn_layers_operands_x(descs, n, rng.data_ptr() if rng is not None else None,
+            _lib.check(_lib.lib().lbbnn_layers_operands_x(d0, n0, rng.data_ptr() if rng is not None else None,
                                                           snap.data_ptr() if snap is not None else None, 0,
                                                           x.data_ptr(), x.stride(0), xp.data_ptr(), xp.stride(0), B,
                                                           layers[0].in_features, stream), "lbbnn_layers_operands_x")
             x, x_planes = xp, True
         else:
-            _lib.check(_lib.lib().lbbnn_layers_operands_snap(descs, n, rng.data_ptr() if rng is not None else None,
+            _lib.check(_lib.lib().lbbnn_layers_operands_snap(d0, n0, rng.data_ptr() if rng is not None else None,
                                                              snap.data_ptr() if snap is not None else None, 0, stream),
                        "lbbnn_layers_operands_snap")
+        for k, cnt in lgroups[1:]:
+            _lib.check(_lib.lib().lbbnn_layers_operands(_lib.group_slice(descs, k, cnt), cnt,
+                                                        snap.data_ptr() if snap is not None else None, stream),
+                       "lbbnn_layers_operands")
         if deferred is not None:
             # enqueued AFTER the weight pass: a captured graph keeps the first-recorded successor of a fork on the parent's queue,
             # and a hop to another queue costs ~11 us -- it must be the side branch that pays it, not the weight pass
@@ -1368,9 +1405,14 @@ class _NetworkBase(nn.Module):
             if i == fin_at and defer_ev is not None:
                 torch.cuda.current_stream(dev).wait_event(defer_ev)
             if i == fin_at and (want_kl or st is not None):
-                fin = (descs if want_kl else None, n if want_kl else 0, snap.data_ptr() if snap is not None else None,
-                       kls[n:].data_ptr() if all_kl else None, rng.data_ptr() if rng is not None else None,
+                # (the first group's finalize, with the network total when it is the only group, and the RNG advance)
+                fin = (d0 if want_kl else None, n0 if want_kl else 0, snap.data_ptr() if snap is not None else None,
+                       kls[n:].data_ptr() if (all_kl and len(lgroups) == 1) else None, rng.data_ptr() if rng is not None else None,
                        1 if rng is not None else 0)
+            elif want_kl and fin_at < i < fin_at + len(lgroups):
+                # group g's finalize rides in GEMM fin_at + g (every group reads the snapshot; only the first one advances)
+                k, cnt = lgroups[i - fin_at]
+                fin = (_lib.group_slice(descs, k, cnt), cnt, snap.data_ptr() if snap is not None else None, None)
             # row-scaled fp16 layers hand their activations on as fp16 hi | lo PLANES (written by the GEMM epilogue, read by
             # the next GEMM's LDS-DMA as they lie): no fp32 copy of a hidden activation is stored in this no-grad forward
             fmt = l._split_now
@@ -1404,6 +1446,8 @@ class _NetworkBase(nn.Module):
                 x, x_planes, head_done = head["out"], False, True
             else:
                 x, x_planes = (pbuf, True) if give_planes else (y, False)
+        if all_kl and len(lgroups) > 1:
+            ops.kl_total(kls, n)                                      # kls[n] = ((0 + kls[0]) + kls[1]) + ...: one launch
         if layers[-1].out_features > 16:
             x = F.log_softmax(x, dim=1)
         for i, (l, c) in enumerate(zip(layers, cfgs)):
@@ -1418,7 +1462,11 @@ class _NetworkBase(nn.Module):
             from .losses import _SumKLFn                              # ... also in the training forward: no add kernels
             return _SumKLFn.apply(self._train_kl_total, [getattr(l, "_v1_slot", None) for l in self._layers()],
                                   *[l.kl for l in self._layers()])
-        return self.l1.kl + self.l2.kl + self.l3.kl                   # …LRT.py:213-214
+        kls = [l.kl for l in self._layers()]
+        total = kls[0]
+        for k in kls[1:]:
+            total = total + k                                         # l1.kl + l2.kl + l3.kl ... (…LRT.py:213-214)
+        return total
 
     def set_row_offset(self, off: int):
         for l in self._layers():
@@ -1430,11 +1478,7 @@ class LRTBayesianNetwork(_NetworkBase):
 
     def __init__(self, dims=(28 * 28, 400, 600, 10), *, priors=None):
         super().__init__()
-        self.dims = tuple(dims)
-        self.l1 = LRTBayesianLinear(dims[0], dims[1], priors=priors)
-        self.l2 = LRTBayesianLinear(dims[1], dims[2], priors=priors)
-        self.l3 = LRTBayesianLinear(dims[2], dims[3], priors=priors)
-        self._number_layers()
+        self._build(dims, lambda i, o: LRTBayesianLinear(i, o, priors=priors))
 
 
 class MNFBayesianNetwork(_NetworkBase):
@@ -1443,9 +1487,5 @@ class MNFBayesianNetwork(_NetworkBase):
     def __init__(self, dims=(28 * 28, 400, 600, 10), num_transforms=2, *, z_flow_type="RNVP",
                  r_flow_type="RNVP", priors=None):
         super().__init__()
-        self.dims = tuple(dims)
         kw = dict(z_flow_type=z_flow_type, r_flow_type=r_flow_type, priors=priors)
-        self.l1 = MNFBayesianLinear(dims[0], dims[1], num_transforms, **kw)
-        self.l2 = MNFBayesianLinear(dims[1], dims[2], num_transforms, **kw)
-        self.l3 = MNFBayesianLinear(dims[2], dims[3], num_transforms, **kw)
-        self._number_layers()
+        self._build(dims, lambda i, o: MNFBayesianLinear(i, o, num_transforms, **kw))

@@ -937,6 +937,15 @@ def flow_dense_workspace(I: int) -> int:
 
 
 # ----------------------------------------------------------------------------------------- K5
+def kl_total(kls: torch.Tensor, n: int) -> torch.Tensor:
+    """lbbnn_kl_total: kls[n] = ((0 + kls[0]) + kls[1]) + ... + kls[n - 1] in fp32, one launch; ``kls`` holds n + 1 contiguous
+    floats (the per-layer values the finalize launches of a deep network wrote, then the total).  Returns kls[n]."""
+    if kls.dtype != torch.float32 or not kls.is_contiguous() or kls.numel() < n + 1:
+        raise RuntimeError("bnn_amd: kl_total needs a contiguous fp32 buffer of n + 1 values")
+    _lib.check(_lib.lib().lbbnn_kl_total(kls.data_ptr(), n, kls.data_ptr() + 4 * n, _stream()), "lbbnn_kl_total")
+    return kls[n]
+
+
 def kl_finalize(kl_rows, bias_mu, bias_rho, *, priors: Priors, act_mu=None, act_var=None, eps_act=None,
                 r0_b1=None, r0_b2=None, scal=None, rng: Optional[torch.Tensor] = None, layer_id: int = 0,
                 kl_out=None, kl_layer=None, accumulate: bool = False):

@@ -352,6 +352,14 @@ int lbbnn_lrt_gemm_members(const float* x, int ldx, int64_t x_mstride, const voi
 int lbbnn_forward_finish(uint64_t* rng, uint64_t advance, const float* const* kl_layers, int n,
                          float* kl_total, void* stream);
 
+/* Network KL of a network deeper than one batched launch holds.  A network of n layers issues its batched calls in
+ * ceil(n / LBBNN_MAX_LAYERS) groups of consecutive layers; each group's KL finalize writes its layers' values into ONE
+ * contiguous buffer kl_layers[0..n), and this call forms *total = ((0 + kl_layers[0]) + kl_layers[1]) + ... in fp32 -- the
+ * order and precision in which the finalize of a single group adds its total.  1 <= n <= LBBNN_MAX_DEPTH; one launch of one
+ * thread, no host read: capturable.  total may be kl_layers + n. */
+#define LBBNN_MAX_DEPTH 16
+int lbbnn_kl_total(const float* kl_layers, int n, float* total, void* stream);
+
 
 /* ---------------------------------------------------------------------------------------------
  * K6  lbbnn_gate_sample -- baseline LBBNN layer (explicit latent-binary gate x Gaussian weight sample).
