@@ -377,6 +377,10 @@ SIGNATURES = {
     "lbbnn_elbo_loss_backward_logits": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, ctypes.c_float, c_p, c_p, c_p, c_p]),
     "lbbnn_log_softmax_backward": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_p]),
     "lbbnn_log_softmax_rows": (c_i, [c_p, c_i, c_p, c_i, c_i, c_i, c_p]),
+    "lbbnn_binary_head": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_i, c_p]),
+    "lbbnn_elbo_bce_loss": (c_i, [c_p, c_i, c_p, c_i, c_i, c_i, c_p, ctypes.c_float, c_p, c_p, c_i, c_p]),
+    "lbbnn_elbo_bce_loss_backward": (c_i, [c_p, c_p, c_i, c_p, c_i, c_i, c_i, ctypes.c_float, c_p, c_p, c_p, c_p]),
+    "lbbnn_sigmoid_backward": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_p]),
     "lbbnn_frozen_operands": (c_i, [ctypes.POINTER(FrozenDesc), c_i, c_p]),
     "lbbnn_frozen_members": (c_i, [ctypes.POINTER(FrozenDesc), c_i, c_i, c_p, c_u64, c_p]),
     "lbbnn_flow_dense_members_max_dim": (c_i, []),

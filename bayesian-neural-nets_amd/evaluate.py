@@ -35,6 +35,46 @@ from torch import nn
 from . import ops
 
 
+def _head_of(net) -> str:
+    return getattr(net, "head", "log_softmax")
+
+
+def _check_log_probs(net, log_probs: bool):
+    """``log_probs=True`` is the 2-class form of a sigmoid head with ONE output unit."""
+    if not log_probs:
+        return
+    if _head_of(net) != "sigmoid":
+        raise ValueError("bnn_amd: log_probs=True applies to a head=\"sigmoid\" network (a log_softmax head returns "
+                         "log-probabilities already)")
+    if net.dims[-1] != 1:
+        raise ValueError("bnn_amd: log_probs=True needs one output unit (the two classes of a binary outcome), this head has %d"
+                         % net.dims[-1])
+
+
+def _binary_members(buf: torch.Tensor, S: int, B: int, O: int, log_probs: bool) -> torch.Tensor:
+    """The binary head over the (S, member stride) logits buffer of a member GEMM, member m's (B, O) block at buf[m, :B * O]: ONE
+    lbbnn_binary_head launch over the whole buffer as a column of single elements (the function is elementwise; the padding
+    between members is computed and never shown).  Probabilities in place -> (S, B, O); ``log_probs`` (O == 1) -> the (S, B, 2)
+    log-probabilities, a view with the buffer's member stride."""
+    ms = buf.shape[1]
+    flat = buf.view(S * ms, 1)
+    if log_probs:
+        return ops.binary_head(flat, log_probs=True, want_probs=False).view(S, ms, 2)[:, :B]
+    ops.binary_head(flat, probs=flat)
+    return buf[:, :B * O].view(S, B, O)
+
+
+def _forward_head(net, data, sample: bool, log_probs: bool):
+    """net(data, sample) of an LRT / MNF network; with ``log_probs`` the sigmoid head's 2-class log-probabilities."""
+    if not log_probs:
+        return net(data, sample=sample)
+    net._logp2_now = True
+    try:
+        return net(data, sample=sample)
+    finally:
+        net._logp2_now = False
+
+
 def _batched_ok(net, data) -> bool:
     """The one-launch-per-kernel ensemble applies to LRT networks and to MNF networks whose flows are planar with <= 4
     transforms, on a HIP device, without injected noise; anything else takes the loop of single forwards."""
@@ -52,7 +92,7 @@ def _batched_ok(net, data) -> bool:
 
 
 @torch.no_grad()
-def ensemble_forward_batched(net, data: torch.Tensor, samples: int = 10) -> torch.Tensor:
+def ensemble_forward_batched(net, data: torch.Tensor, samples: int = 10, *, log_probs: bool = False) -> torch.Tensor:
     """``samples`` stochastic evaluation forwards of one batch (LBBNN-GP-MF-MNF.py:286-294: TEST_SAMPLES x net(data,
     sample=True)) in 2 + 3 launches instead of 5 per member: one K3 and one K1 launch produce every member's z and
     operands (the variance operand, z-free, once for all), then each layer's GEMM runs all members as gridDim.z slices of
@@ -64,6 +104,8 @@ def ensemble_forward_batched(net, data: torch.Tensor, samples: int = 10) -> torc
     row-scaled fp16 kernels -- same draws, results equal to the formats' error (tools/ensemble_fuzz.py)."""
     import ctypes
     from . import _lib
+    _check_log_probs(net, log_probs)
+    sigmoid = _head_of(net) == "sigmoid"
     net.eval()
     S = int(samples)
     layers = net._layers()
@@ -101,10 +143,11 @@ def ensemble_forward_batched(net, data: torch.Tensor, samples: int = 10) -> torc
         O, I = l.out_features, l.in_features
         ws = l._workspace()
         o_ms = -(-(B * O) // 4) * 4                           # member stride padded to 16 B (vector loads / stores per member)
-        out = torch.empty((S, o_ms), **f)[:, :B * O].view(S, B, O) if o_ms != B * O else torch.empty((S, B, O), **f)
+        obuf = torch.empty((S, o_ms), **f)
+        out = obuf[:, :B * O].view(S, B, O) if o_ms != B * O else obuf.view(S, B, O)
         last = i == n - 1
         flags = (0 if last else ops.F_RELU) | (ops.F_SPLIT16 if l._split_now else 0) | \
-                (ops.F_LOG_SOFTMAX if (last and O <= 16) else 0)
+                (ops.F_LOG_SOFTMAX if (last and O <= 16 and not sigmoid) else 0)
         rc = _lib.lib().lbbnn_lrt_gemm_members(
             h.data_ptr(), h.stride(-2), h_ms, e_all[i].data_ptr(), O * ops.operand_ld(I), ws.var_w.data_ptr(),
             ops.operand_ld(I), l.bias_mu.data_ptr(), ws.bias_var.data_ptr(), rng.data_ptr(),
@@ -112,7 +155,9 @@ def ensemble_forward_batched(net, data: torch.Tensor, samples: int = 10) -> torc
         _lib.check(rc, "lbbnn_lrt_gemm_members")
         h, h_ms = out, o_ms
     st.advance(S)                                              # as S single forwards would have
-    if layers[-1].out_features > 16:
+    if sigmoid:
+        h = _binary_members(obuf, S, B, layers[-1].out_features, log_probs)
+    elif layers[-1].out_features > 16:
         h = torch.log_softmax(h, dim=-1)
     for l in layers:
         l.kl = 0
@@ -245,7 +290,7 @@ def base_ensemble(net, data: torch.Tensor, samples: int = 10, *, gates: str = "s
 
 @torch.no_grad()
 def ensemble_forward(net, data: torch.Tensor, samples: int = 10, batched=None, *, gates: str = "sample",
-                     max_members: Optional[int] = None) -> torch.Tensor:
+                     max_members: Optional[int] = None, log_probs: bool = False) -> torch.Tensor:
     """(samples, B, classes) log-probabilities of ``samples`` stochastic forwards (net left in eval mode).
     ``batched``: None = the one-launch-per-kernel form when the network qualifies (``_batched_ok``; a baseline network on a
     HIP device: ``base_ensemble``), else the loop of fused single forwards (``net.sample_predict`` for a baseline network);
@@ -255,15 +300,20 @@ def ensemble_forward(net, data: torch.Tensor, samples: int = 10, batched=None, *
     ``gates`` ("sample" or "mpm") applies to baseline networks only, ``max_members`` (members per launch of the batched form)
     to baseline and variational-dropout networks and frozen models.  A ``FrozenNetwork`` (``freeze``): its ``ensemble``.
     A variational-dropout network (``vd.BNN``): None = ``vd_ensemble`` on a
-    HIP device when no layer has injected noise, else the loop of ``net(data)``; True with injected noise raises ValueError."""
+    HIP device when no layer has injected noise, else the loop of ``net(data)``; True with injected noise raises ValueError.
+    An LRT / MNF network with ``head="sigmoid"`` (or its frozen model): (samples, B, units) PROBABILITIES, same draws and Philox
+    offsets (the head consumes no randomness); ``log_probs=True`` (one unit) returns the (samples, B, 2) log-probabilities
+    [logsigmoid(-logit), logsigmoid(logit)] instead, made from the logits by the same launch."""
     net.eval()
+    if log_probs and (_is_vd(net) or _is_base(net)):
+        raise ValueError("bnn_amd: log_probs=True applies to an LRT / MNF network with head=\"sigmoid\" or its frozen model")
     if _is_frozen(net):
         if gates != "sample":
             raise ValueError("bnn_amd: gates=%r: the gates of a frozen model were fixed by evaluate.freeze(net, gates=...) "
                              "(this one has gates=%r); freeze again to change them" % (gates, net.gates))
         if batched is False:
             raise ValueError("bnn_amd: a frozen model has no loop-of-forwards form; leave batched at None")
-        return net.ensemble(data, samples, max_members=max_members)
+        return net.ensemble(data, samples, max_members=max_members, log_probs=log_probs)
     if _is_vd(net):
         if gates != "sample":
             raise ValueError("bnn_amd: gates=%r (the median probability model) exists for baseline LBBNN networks only"
@@ -289,15 +339,16 @@ def ensemble_forward(net, data: torch.Tensor, samples: int = 10, batched=None, *
                          % (gates,))
     if max_members is not None:
         raise ValueError("bnn_amd: max_members applies to baseline LBBNN networks only")
+    _check_log_probs(net, log_probs)
     if batched is None:
         batched = _batched_ok(net, data)
     if batched and _has_dense_flows(net):
         # RNVP / MNF-type z flows: the batched form is the frozen alpha model (same draws as the loop, equal to rounding);
         # batched=None keeps the loop for such a network
-        return freeze(net, "alpha", dense=True).ensemble(data, samples)
+        return freeze(net, "alpha", dense=True).ensemble(data, samples, log_probs=log_probs)
     if batched:
-        return ensemble_forward_batched(net, data, samples)
-    outs = [net(data, sample=True) for _ in range(samples)]
+        return ensemble_forward_batched(net, data, samples, log_probs=log_probs)
+    outs = [_forward_head(net, data, True, log_probs) for _ in range(samples)]
     return torch.stack(outs)
 
 
@@ -316,13 +367,16 @@ def ensemble_eval(net, data: torch.Tensor, target: Optional[torch.Tensor] = None
         return _base_ensemble_eval(net, data, target, samples)
     if _is_vd(net):
         return _vd_ensemble_eval(net, data, target, samples)
-    outputs = ensemble_forward(net, data, samples)
+    binary = _binary_eval(net)
+    if binary and target is not None:
+        target = _binary_target(target)
+    outputs = ensemble_forward(net, data, samples, log_probs=binary)
     density = []
     for _ in range(samples):
         g = [l.gamma.rsample().flatten() for l in net._layers()]
         density.append(torch.cat(g).mean())
     pred_ens = outputs.mean(0).argmax(1)
-    pred_mean = net(data, sample=False).argmax(1)
+    pred_mean = _forward_head(net, data, False, binary).argmax(1)
     res = {"outputs": outputs, "pred_ensemble": pred_ens, "pred_posterior_mean": pred_mean,
            "density": torch.stack(density)}
     if target is not None:
@@ -331,10 +385,30 @@ def ensemble_eval(net, data: torch.Tensor, target: Optional[torch.Tensor] = None
     return res
 
 
+def _binary_eval(net) -> bool:
+    """A sigmoid head is evaluated as two classes: its one unit's (.., 2) log-probabilities go to the metrics of a ``classes =
+    2`` problem.  More than one unit (multi-label) has no class axis: ValueError."""
+    if _head_of(net) != "sigmoid":
+        return False
+    if net.dims[-1] != 1:
+        raise ValueError("bnn_amd: the evaluation metrics take a sigmoid head with ONE output unit as a 2-class problem; this "
+                         "head has %d units (multi-label): use the probabilities of ensemble_forward directly" % net.dims[-1])
+    return True
+
+
+def _binary_target(target: torch.Tensor) -> torch.Tensor:
+    """0 / 1 targets of a binary head, given as float or integer, (B,) or (B, 1): the (B,) int64 class ids, on the device."""
+    t = target.reshape(-1)
+    return t if t.dtype == torch.int64 else t.long()
+
+
 def _frozen_ensemble_eval(net, data, target, samples):
-    outputs = net.ensemble(data, samples)
+    binary = _binary_eval(net)
+    if binary and target is not None:
+        target = _binary_target(target)
+    outputs = net.ensemble(data, samples, log_probs=binary)
     pred_ens = outputs.mean(0).argmax(1)
-    pred_mean = net(data, sample=False).argmax(1)
+    pred_mean = net(data, sample=False, log_probs=binary).argmax(1)
     density = torch.full((int(samples),), net.density, dtype=torch.float32, device=outputs.device)
     res = {"outputs": outputs, "pred_ensemble": pred_ens, "pred_posterior_mean": pred_mean, "density": density}
     if target is not None:
@@ -768,8 +842,9 @@ def _eval_forwards(net, data, samples: int, posterior_mean: bool, gates: str):
     if _is_frozen(net):
         if gates != "sample":
             raise ValueError("bnn_amd: gates=%r: the gates of a frozen model were fixed by evaluate.freeze" % (gates,))
-        outputs = net.ensemble(data, samples)
-        return outputs, (net(data, sample=False) if posterior_mean else None)
+        binary = _binary_eval(net)
+        outputs = net.ensemble(data, samples, log_probs=binary)
+        return outputs, (net(data, sample=False, log_probs=binary) if posterior_mean else None)
     if _is_base(net):
         outputs = base_ensemble(net, data, samples, gates=gates)["outputs"]
         if not posterior_mean:
@@ -780,8 +855,9 @@ def _eval_forwards(net, data, samples: int, posterior_mean: bool, gates: str):
         return outputs, net(data, None, None, None, sample=False)              # :413 (mode 2: weight = alpha * mu)
     if _is_vd(net):
         return ensemble_forward(net, data, samples, gates=gates), None         # VD has no posterior-mean forward
-    outputs = ensemble_forward(net, data, samples, gates=gates)
-    return outputs, (net(data, sample=False) if posterior_mean else None)
+    binary = _binary_eval(net)
+    outputs = ensemble_forward(net, data, samples, gates=gates, log_probs=binary)
+    return outputs, (_forward_head(net, data, False, binary) if posterior_mean else None)
 
 
 @torch.no_grad()
@@ -797,8 +873,11 @@ def evaluate_batches(net, batches, samples: int = 10, *, acc: Optional[EvalAccum
     returned dict under its own keys (the three counts both keep, ``rows``, ``rows_with_target`` and ``bad_targets``, are
     ``acc``'s)."""
     S = int(samples)
+    binary = _head_of(net) == "sigmoid"
     for x, y in batches:
         outputs, mean = _eval_forwards(net, x, S, posterior_mean, gates)
+        if binary and y is not None:
+            y = _binary_target(y)                 # float 0 / 1 targets: converted on the device, no host read
         if acc is None:
             acc = EvalAccumulator(outputs.shape[-1], S, outputs.device)
         acc.update(outputs, y, mean)
@@ -844,8 +923,13 @@ class FrozenNetwork(nn.Module):
     """
 
     def __init__(self, dims, family: str = "lrt", gates: str = "alpha", threshold: float = 0.5, device=None,
-                 flows: Optional[str] = None):
+                 flows: Optional[str] = None, head: str = "log_softmax"):
         super().__init__()
+        if head not in ("log_softmax", "sigmoid"):
+            raise ValueError("bnn_amd: head must be 'log_softmax' or 'sigmoid', got %r" % (head,))
+        if head == "sigmoid" and int(dims[-1]) > 16:
+            raise ValueError("bnn_amd: a sigmoid head takes at most 16 output units, got dims[-1] = %d" % int(dims[-1]))
+        self.head = head                # carried over from the network: "sigmoid" -> probabilities (or, log_probs=True, 2 classes)
         if gates not in FROZEN_GATES:
             raise ValueError("bnn_amd: gates must be 'alpha' (the gates as trained) or 'mpm' (the median probability model), "
                              "got %r" % (gates,))
@@ -899,7 +983,8 @@ class FrozenNetwork(nn.Module):
 
     def extra_repr(self) -> str:
         flows = ", flows=%s" % self.flows if self.flows else ""
-        return "dims=%s, family=%s%s, gates=%s, threshold=%g" % (self.dims, self.family, flows, self.gates, self.threshold)
+        head = ", head=sigmoid" if self.head == "sigmoid" else ""
+        return "dims=%s, family=%s%s, gates=%s, threshold=%g%s" % (self.dims, self.family, flows, self.gates, self.threshold, head)
 
     # ------------------------------------------------------------------------------------- snapshot
     def _bind(self, net):
@@ -1133,7 +1218,7 @@ class FrozenNetwork(nn.Module):
             o_ms = _pad4(B * O)                              # member stride padded to 16 B
             out = head if last else _empty((c, o_ms), dtype=torch.float32, device=dev)
             flags = (0 if last else ops.F_RELU) | (ops.F_SPLIT16 if self._split[i] else 0) | \
-                    (ops.F_LOG_SOFTMAX if (last and O <= 16) else 0)
+                    (ops.F_LOG_SOFTMAX if (last and O <= 16 and self.head == "log_softmax") else 0)
             e_ptr, w_ms = (ewm[i].data_ptr(), O * ld) if mnf else (self._buf("e_w", i).data_ptr(), 0)
             rc = _lib.lib().lbbnn_lrt_gemm_members(
                 h.data_ptr(), (h.stride(0) if i == 0 else self.dims[i]), h_ms, e_ptr, w_ms, self._buf("var_w", i).data_ptr(), ld,
@@ -1144,7 +1229,7 @@ class FrozenNetwork(nn.Module):
             h, h_ms = out, o_ms
         st.advance(c)                                        # as c single forwards would have
 
-    def _chain(self, x, st, e_ws, stochastic: bool):
+    def _chain(self, x, st, e_ws, stochastic: bool, log_probs: bool = False):
         """One member as a chain of single lbbnn_lrt_gemm calls on the frozen operands, drawing at the live offset."""
         h, n = x, self.n_layers
         for i in range(n):
@@ -1153,12 +1238,14 @@ class FrozenNetwork(nn.Module):
             h = ops.lrt_gemm(h, e_ws[i], self._buf("var_w", i), I=I, O=O, bias_mean=self._buf("bias_mu", i),
                              bias_var=self._buf("bias_var", i), rng=st.t, rng_stream=ops.STREAM_EPS_OUT * 64 + self._layer_ids[i],
                              row_offset=self._row_offsets[i], relu=not last, mean_only=not stochastic,
-                             log_softmax=last and O <= 16, split=self._split[i], single=False)
+                             log_softmax=last and O <= 16 and self.head == "log_softmax", split=self._split[i], single=False)
+        if self.head == "sigmoid":
+            return ops.binary_head(h, log_probs=True, want_probs=False) if log_probs else ops.binary_head(h, probs=h)
         return h if self.dims[-1] <= 16 else torch.log_softmax(h, dim=1)
 
     @torch.no_grad()
     def ensemble(self, data: torch.Tensor, samples: int = 10, *, max_members: Optional[int] = None,
-                 keep_z: bool = False, keep_masks: bool = False) -> torch.Tensor:
+                 keep_z: bool = False, keep_masks: bool = False, log_probs: bool = False) -> torch.Tensor:
         """(samples, B, classes) log-probabilities of ``samples`` stochastic forwards of the frozen model.  Member m draws where
         the m-th member of ``ensemble_forward_batched`` draws: eps of layer i from stream STREAM_EPS_OUT * 64 + layer id with the
         layer's row_offset at Philox offset live + m, z of an MNF layer from its q0 and z flow at the same offset.  The live
@@ -1166,7 +1253,11 @@ class FrozenNetwork(nn.Module):
         the same bits.  ``keep_z``: ``self.last_z`` = per layer the (samples, in_features) z every member used (None entries for
         an LRT model).  ``keep_masks`` (dense flows): ``self.last_masks`` = per layer the (samples, T, in_features) Bernoulli
         masks of the coupling transforms every member used (None for any other model).  An LRT model with a layer the member GEMM does not take (in_features % 4 != 0 or an operand row wider
-        than 2048) runs every member as a chain of single GEMM calls on the frozen operands instead -- same draws, same shape."""
+        than 2048) runs every member as a chain of single GEMM calls on the frozen operands instead -- same draws, same shape.
+        A model with ``head == "sigmoid"``: (samples, B, units) probabilities -- one lbbnn_binary_head launch over the members'
+        logits, no draws of its own -- or, with ``log_probs=True`` (one unit), the (samples, B, 2) log-probabilities of the two
+        classes from the same launch."""
+        _check_log_probs(self, log_probs)
         S = int(samples)
         if S < 1:
             raise ValueError("bnn_amd: samples must be >= 1")
@@ -1191,11 +1282,11 @@ class FrozenNetwork(nn.Module):
                     self.last_masks = [torch.cat(parts) for parts in zip(*ms)] if keep_masks else None
                 else:
                     st.advance(S)
-                return torch.zeros((S, 0, C), dtype=torch.float32, device=dev)
+                return torch.zeros((S, 0, 2 if log_probs else C), dtype=torch.float32, device=dev)
             if not self._members_ok:                         # (LRT only: freeze refuses such an MNF network)
                 outs = []
                 for _ in range(S):
-                    outs.append(self._chain(x, st, [self._buf("e_w", i) for i in range(self.n_layers)], True))
+                    outs.append(self._chain(x, st, [self._buf("e_w", i) for i in range(self.n_layers)], True, log_probs))
                     st.advance(1)
                 if keep_z:
                     self.last_z = [None] * self.n_layers
@@ -1210,26 +1301,30 @@ class FrozenNetwork(nn.Module):
             self.last_masks = [torch.cat(parts) for parts in zip(*ms)]
         if keep_z:
             self.last_z = [torch.cat(parts) for parts in zip(*zs)] if zs is not None else [None] * self.n_layers
+        if self.head == "sigmoid":
+            return _binary_members(head, S, B, C, log_probs)
         outputs = head[:, :B * C].view(S, B, C)
         return outputs if C <= 16 else torch.log_softmax(outputs, dim=-1)
 
     @torch.no_grad()
-    def forward(self, data: torch.Tensor, sample: bool = False) -> torch.Tensor:
+    def forward(self, data: torch.Tensor, sample: bool = False, *, log_probs: bool = False) -> torch.Tensor:
         """(B, classes) log-probabilities of one member.  ``sample=True``: member 0 of ``ensemble(data, 1)``.
         ``sample=False``: the posterior-mean branch x . E0^T + bias_mu (LBBNN-GP-MF-LRT.py:178-180); an MNF model still draws
-        its z (LBBNN-GP-MF-MNF.py:203) and advances the live offset by 1, an LRT model draws nothing."""
+        its z (LBBNN-GP-MF-MNF.py:203) and advances the live offset by 1, an LRT model draws nothing.  A sigmoid head:
+        (B, units) probabilities, or with ``log_probs=True`` (one unit) the (B, 2) log-probabilities."""
+        _check_log_probs(self, log_probs)
         if sample:
-            return self.ensemble(data, 1)[0]
+            return self.ensemble(data, 1, log_probs=log_probs)[0]
         x = self._input(data)
         dev = x.device
         st = ops.RngState.get(dev)
         with torch.cuda.device(dev):
             if self.family == "mnf":
                 _, ewm = self._draw_members(1, st.t, torch.cuda.current_stream(dev).cuda_stream)
-                out = self._chain(x, st, [e[0] for e in ewm], False)
+                out = self._chain(x, st, [e[0] for e in ewm], False, log_probs)
                 st.advance(1)
                 return out
-            return self._chain(x, st, [self._buf("e_w", i) for i in range(self.n_layers)], False)
+            return self._chain(x, st, [self._buf("e_w", i) for i in range(self.n_layers)], False, log_probs)
 
 
 def _check_freezable_layers(layers, dense: bool = False):
@@ -1318,6 +1413,6 @@ def freeze(net, gates: str = "alpha", *, threshold: float = 0.5, dense: bool = F
                            % layers[0].weight_mu.device)
     family = "mnf" if layers[0]._mnf else "lrt"
     flows = layers[0]._check_flows() if family == "mnf" else None          # "planar" | "dense" (checked above)
-    fz = FrozenNetwork(net.dims, family, gates, threshold, device=layers[0].weight_mu.device, flows=flows)
+    fz = FrozenNetwork(net.dims, family, gates, threshold, device=layers[0].weight_mu.device, flows=flows, head=net.head)
     fz.eval()
     return fz._bind(net)

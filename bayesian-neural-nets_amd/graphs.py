@@ -197,11 +197,16 @@ def make_graphed_eval_step(frozen, example_x, example_y, samples: int, acc, warm
     S = int(samples)
     static_x, static_y = example_x.clone(), example_y.clone()
 
+    # a sigmoid head with one unit is evaluated as two classes (its (S, B, 2) log-probabilities; float 0 / 1 targets become class
+    # ids inside the graph); more than one unit: ValueError
+    binary = evaluate._binary_eval(frozen)
+
     def body():
-        outputs = frozen.ensemble(static_x, S)
-        rows = acc.update(outputs, static_y, frozen(static_x, sample=False))
+        outputs = frozen.ensemble(static_x, S, log_probs=binary)
+        y = evaluate._binary_target(static_y) if binary else static_y
+        rows = acc.update(outputs, y, frozen(static_x, sample=False, log_probs=binary))
         if uncertainty is not None:
-            rows.update(uncertainty.update(outputs, static_y))
+            rows.update(uncertainty.update(outputs, y))
         return rows
 
     st = ops.RngState.get(dev)

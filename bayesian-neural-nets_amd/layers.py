@@ -472,10 +472,36 @@ def _x_operand_pair(x, gT, g_vT, module=None):
     return xt, x2t
 
 
+class _SigmoidHeadFn(torch.autograd.Function):
+    """The binary head of a ``head="sigmoid"`` network in the training forward: lbbnn_binary_head on the last layer's logits.
+    Backward: the gradient with respect to the logits as the fused loss left it (losses._BCE_LOGITS_GRAD) when the gradient it
+    receives is the very tensor ``elbo_bce_loss`` returned for these probabilities, else lbbnn_sigmoid_backward."""
+
+    @staticmethod
+    def forward(ctx, logits):
+        probs = ops.binary_head(logits)
+        ctx.save_for_backward(probs)
+        return probs
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import losses
+        (probs,) = ctx.saved_tensors
+        ent = losses._BCE_LOGITS_GRAD.pop(probs.data_ptr(), None)
+        if ent is not None and ent[0] == g.data_ptr():
+            losses.HANDOVER["taken"] += 1
+            return ent[1]
+        losses.HANDOVER["sigmoid_backward"] += 1
+        return ops.sigmoid_backward(g, probs)
+
+
+HEADS = ("log_softmax", "sigmoid")
+
+
 class _BayesLinearBase(nn.Module):
     _mnf = False
 
-    def _common_init(self, in_features, out_features, mu_range, priors):
+    def _common_init(self, in_features, out_features, mu_range, priors, lambdal_init=(0, 1)):
         self.in_features = in_features
         self.out_features = out_features
         self.priors = priors if priors is not None else Priors()
@@ -483,7 +509,10 @@ class _BayesLinearBase(nn.Module):
         self.weight_mu = nn.Parameter(torch.Tensor(out_features, in_features).uniform_(-mu_range, mu_range))
         self.weight_rho = nn.Parameter(torch.Tensor(out_features, in_features).uniform_(-5, -4))
         self.weight = Gaussian(self.weight_mu, self.weight_rho)
-        self.lambdal = nn.Parameter(torch.Tensor(out_features, in_features).uniform_(0, 1))
+        lo, hi = (float(v) for v in lambdal_init)           # (0, 1): the reference's draw; the sim-study scripts draw U(1.5, 2.5)
+        if not lo <= hi:
+            raise ValueError("bnn_amd: lambdal_init must be (lo, hi) with lo <= hi, got %r" % (lambdal_init,))
+        self.lambdal = nn.Parameter(torch.Tensor(out_features, in_features).uniform_(lo, hi))
         self._alpha_q_init = torch.Tensor(out_features, in_features).uniform_(0.999, 0.9999)   # placeholder draw, :147
         self.gamma = Bernoulli(self._alpha_q_init)
         self.gamma.bind(self._alpha_now)
@@ -688,9 +717,9 @@ class _BayesLinearBase(nn.Module):
 class LRTBayesianLinear(_BayesLinearBase):
     """BayesianLinear(in_features, out_features) of LBBNN-GP-MF-LRT.py:129-197."""
 
-    def __init__(self, in_features, out_features, *, priors: Optional[Priors] = None):
+    def __init__(self, in_features, out_features, *, priors: Optional[Priors] = None, lambdal_init=(0, 1)):
         super().__init__()
-        self._common_init(in_features, out_features, 0.2, priors)
+        self._common_init(in_features, out_features, 0.2, priors, lambdal_init)
 
     def _param_list(self):
         return [self.weight_mu, self.weight_rho, self.lambdal, self.bias_mu, self.bias_rho]
@@ -736,9 +765,9 @@ class MNFBayesianLinear(_BayesLinearBase):
     _mnf = True
 
     def __init__(self, in_features, out_features, num_transforms, *, z_flow_type="RNVP", r_flow_type="RNVP",
-                 priors: Optional[Priors] = None):
+                 priors: Optional[Priors] = None, lambdal_init=(0, 1)):
         super().__init__()
-        self._common_init(in_features, out_features, 0.01, priors)         # weight_mu ~ U(+-0.01), :140
+        self._common_init(in_features, out_features, 0.01, priors, lambdal_init)   # weight_mu ~ U(+-0.01), :140
         self.q0_mean = nn.Parameter(0.1 * torch.randn(in_features))         # :166
         self.q0_log_var = nn.Parameter(-9 + 0.1 * torch.randn(in_features))  # :167
         self.r0_c = nn.Parameter(0.1 * torch.randn(in_features))            # :170-172
@@ -1080,13 +1109,20 @@ class _NetworkBase(nn.Module):
     _pre_shared = None
 
     _lnames = ()
+    _logp2_now = False            # set by bnn_amd.evaluate around a forward: a sigmoid head (one unit) returns the 2-class log-probabilities
+    head = "log_softmax"          # or "sigmoid": probabilities 1 / (1 + exp(-logit)) per output unit (a binary / multi-label head)
 
-    def _build(self, dims, make):
+    def _build(self, dims, make, head="log_softmax"):
         """l1 .. lN from dims, created layer by layer in order (the seeded initial values depend on it)."""
         dims = tuple(int(d) for d in dims)
         if not 2 <= len(dims) <= MAX_DEPTH + 1:
             raise ValueError("bnn_amd: %s takes 1 to %d layers (len(dims) 2 to %d), got dims=%s"
                              % (type(self).__name__, MAX_DEPTH, MAX_DEPTH + 1, dims))
+        if head not in HEADS:
+            raise ValueError("bnn_amd: head must be one of %s, got %r" % (HEADS, head))
+        if head == "sigmoid" and dims[-1] > 16:
+            raise ValueError("bnn_amd: a sigmoid head takes at most 16 output units, got dims[-1] = %d" % dims[-1])
+        self.head = head
         self.dims = dims
         self._lnames = tuple("l%d" % (i + 1) for i in range(len(dims) - 1))
         for i, name in enumerate(self._lnames):
@@ -1160,7 +1196,8 @@ class _NetworkBase(nn.Module):
                     l._advance_rng = not shared
                     # the head's F.log_softmax (…LRT.py:210) runs in its GEMM's epilogue in the training forward too: the layer's
                     # autograd node then returns log-probabilities and its backward starts with lbbnn_log_softmax_backward
-                    l._lsm_now = bool(shared and i == len(layers) - 1 and l.out_features <= 16 and (l.training or sample))
+                    l._lsm_now = bool(shared and i == len(layers) - 1 and l.out_features <= 16 and (l.training or sample)
+                                      and self.head == "log_softmax")
                     fused_lsm = l._lsm_now
                     x = l.forward(x, sample, _relu=(i < len(layers) - 1))   # F.relu fused into the GEMM epilogue
             finally:
@@ -1176,6 +1213,11 @@ class _NetworkBase(nn.Module):
                 if kl_buf is not None:
                     self._train_kl_total = ops.kl_total(kl_buf, len(layers))
                 self._pre_shared = None
+            if self.head == "sigmoid":
+                # the logits as the layer's GEMM left them, then one lbbnn_binary_head launch (no epilogue produces probabilities)
+                if self._logp2_now:
+                    return ops.binary_head(x.detach(), log_probs=True, want_probs=False)
+                return _SigmoidHeadFn.apply(x) if x.requires_grad else ops.binary_head(x)
             return x if fused_lsm else F.log_softmax(x, dim=1)       # …LRT.py:210
         return self._forward_streams(x.float(), sample)
 
@@ -1330,7 +1372,7 @@ class _NetworkBase(nn.Module):
             # (not where the second GEMM folds the <= 16-class head into its epilogue -- a three-layer row-scaled fp16 network:
             # the launch that carries the finalize does not fold, and the unfolded head is another arithmetic (fp32 skinny
             # kernel), so a captured forward would no longer be the eager one bit for bit; tools/forward_replay_fuzz.py)
-            folds_at_1 = (_HEAD_FOLD and n == 3 and layers[1]._split_now >= 2 and layers[2].out_features <= 16
+            folds_at_1 = (_HEAD_FOLD and self.head == "log_softmax" and n == 3 and layers[1]._split_now >= 2 and layers[2].out_features <= 16
                           and layers[2]._split_now == 0 and cfgs[2][0] and cfgs[1][2] and layers[1].out_features % 4 == 0)
             defer = (_DENSE_DEFER and (torch.cuda.is_current_stream_capturing() or _DENSE_DEFER == "always") and n >= 2
                      and all(c[1] for _, c in dense) and layers[1].out_features > 16 and not folds_at_1
@@ -1423,7 +1465,8 @@ class _NetworkBase(nn.Module):
             # its own epilogue (lbbnn_gemm_desc_t::head_*): the hidden activation is never stored, the head has no GEMM launch
             head = None
             nxt = layers[i + 1] if i + 1 < n else None
-            if (_HEAD_FOLD and fmt >= 2 and nxt is not None and i + 2 == n and nxt.out_features <= 16 and nxt._split_now == 0
+            # (a sigmoid head keeps its GEMM: the fold's epilogue ends in log_softmax and the binary head needs the logits)
+            if (_HEAD_FOLD and self.head == "log_softmax" and fmt >= 2 and nxt is not None and i + 2 == n and nxt.out_features <= 16 and nxt._split_now == 0
                     and cfgs[i + 1][0] and c[2] and l.out_features % 4 == 0 and fin is None):
                 wsn = nxt._workspace()
                 hout = (plan.setdefault("out%d" % (i + 1), torch.empty(B, nxt.out_features, dtype=torch.float32, device=dev))
@@ -1440,7 +1483,8 @@ class _NetworkBase(nn.Module):
             if plan is not None and not give_planes and head is None:
                 obuf = plan.setdefault("out%d" % i, torch.empty(B, l.out_features, dtype=torch.float32, device=dev))
             pbuf = self._planes(i, B, l.out_features, dev, plan) if give_planes else None
-            y = l._gemm(x, c, snap, log_softmax=(i == n - 1 and l.out_features <= 16), finalize=fin, out=obuf,
+            y = l._gemm(x, c, snap, log_softmax=(i == n - 1 and l.out_features <= 16 and self.head == "log_softmax"),
+                        finalize=fin, out=obuf,
                         x_planes=x_planes, out_planes=pbuf, want_out=(not give_planes and head is None), head=head)
             if head is not None:
                 x, x_planes, head_done = head["out"], False, True
@@ -1448,7 +1492,11 @@ class _NetworkBase(nn.Module):
                 x, x_planes = (pbuf, True) if give_planes else (y, False)
         if all_kl and len(lgroups) > 1:
             ops.kl_total(kls, n)                                      # kls[n] = ((0 + kls[0]) + kls[1]) + ...: one launch
-        if layers[-1].out_features > 16:
+        if self.head == "sigmoid" and self._logp2_now:
+            x = ops.binary_head(x, log_probs=True, want_probs=False)  # evaluate.*(log_probs=True): (B, 2) from the logits
+        elif self.head == "sigmoid":
+            x = ops.binary_head(x, probs=x)                           # in place over the last GEMM's (or the plan's) output buffer
+        elif layers[-1].out_features > 16:
             x = F.log_softmax(x, dim=1)
         for i, (l, c) in enumerate(zip(layers, cfgs)):
             l.kl = kls[i] if c[1] else 0
@@ -1472,20 +1520,25 @@ class _NetworkBase(nn.Module):
         for l in self._layers():
             l.row_offset = int(off)
 
+    def inclusion_probabilities(self):
+        """Per layer the posterior inclusion probabilities alpha = sigmoid(lambdal) as detached (O, I) tensors on the
+        parameters' device -- what the sim-study scripts report.  Nothing is read back to the host."""
+        return [torch.sigmoid(l.lambdal.detach()) for l in self._layers()]
+
 
 class LRTBayesianNetwork(_NetworkBase):
     """BayesianNetwork() of LBBNN-GP-MF-LRT.py:199-214 (reference dims 784-400-600-10; ``dims=`` added)."""
 
-    def __init__(self, dims=(28 * 28, 400, 600, 10), *, priors=None):
+    def __init__(self, dims=(28 * 28, 400, 600, 10), *, priors=None, head="log_softmax", lambdal_init=(0, 1)):
         super().__init__()
-        self._build(dims, lambda i, o: LRTBayesianLinear(i, o, priors=priors))
+        self._build(dims, lambda i, o: LRTBayesianLinear(i, o, priors=priors, lambdal_init=lambdal_init), head)
 
 
 class MNFBayesianNetwork(_NetworkBase):
     """BayesianNetwork() of LBBNN-GP-MF-MNF.py:244-260 (num_transforms=2 there)."""
 
     def __init__(self, dims=(28 * 28, 400, 600, 10), num_transforms=2, *, z_flow_type="RNVP",
-                 r_flow_type="RNVP", priors=None):
+                 r_flow_type="RNVP", priors=None, head="log_softmax", lambdal_init=(0, 1)):
         super().__init__()
-        kw = dict(z_flow_type=z_flow_type, r_flow_type=r_flow_type, priors=priors)
-        self._build(dims, lambda i, o: MNFBayesianLinear(i, o, num_transforms, **kw))
+        kw = dict(z_flow_type=z_flow_type, r_flow_type=r_flow_type, priors=priors, lambdal_init=lambdal_init)
+        self._build(dims, lambda i, o: MNFBayesianLinear(i, o, num_transforms, **kw), head)

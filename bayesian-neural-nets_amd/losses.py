@@ -1,4 +1,4 @@
-"""The scalar head of a training step as fused HIP launches (include/lbbnn.h: lbbnn_elbo_loss*).
+"""The scalar head of a training step as fused HIP launches (include/lbbnn.h: lbbnn_elbo_loss*, lbbnn_elbo_bce_loss*).
 
 ``elbo_loss(log_probs, target, kl, num_batches)`` is ``F.nll_loss(log_probs, target, reduction='sum') + kl / num_batches`` --
 what the reference's ``train()`` writes out (LBBNN-GP-MF-MNF.py:268-271; ...LRT.py:222-225) -- as ONE forward launch and ONE
@@ -70,6 +70,101 @@ def elbo_loss(log_probs, target, kl=None, num_batches=1.0):
         return _ElboLossFn.apply(log_probs, target, kl if kl is None else kl.reshape(()), 1.0 / float(num_batches))
     nll = F.nll_loss(log_probs, target, reduction="sum")
     return nll if kl is None else nll + kl / num_batches
+
+
+# The same hand-over for the binary head: the BCE loss backward forms the gradient with respect to the LOGITS in its own launch
+# when the probabilities are the very tensor a sigmoid head returned (layers._SigmoidHeadFn), and leaves it here under the
+# probabilities' address.  HANDOVER counts which way each head backward went.
+_BCE_LOGITS_GRAD = {}
+HANDOVER = {"taken": 0, "sigmoid_backward": 0}
+
+
+class _ElboBceLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, probs, target, kl, scale, stats, from_head):
+        B, O = probs.shape
+        _BCE_LOGITS_GRAD.clear()                   # entries live for one backward pass only
+        p = probs if (probs.stride(1) == 1 or O == 1) else probs.contiguous()
+        loss = torch.empty((), dtype=torch.float32, device=p.device)
+        stream = torch.cuda.current_stream(p.device).cuda_stream
+        _lib.check(_lib.lib().lbbnn_elbo_bce_loss(p.data_ptr(), p.stride(0) if B > 1 else O, target.data_ptr(), O, B, O,
+                                                  kl.data_ptr() if kl is not None else None, float(scale), loss.data_ptr(),
+                                                  stats.data_ptr() if stats is not None else None, 1, stream),
+                   "lbbnn_elbo_bce_loss")
+        ctx.save_for_backward(target, p)
+        ctx.meta = (B, O, float(scale), kl is not None, bool(from_head) and p is probs)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        target, p = ctx.saved_tensors
+        B, O, scale, has_kl, from_head = ctx.meta
+        g = g.contiguous()
+        g_probs = torch.empty((B, O), dtype=torch.float32, device=g.device)
+        g_logits = torch.empty((B, O), dtype=torch.float32, device=g.device) if from_head else None
+        g_kl = torch.empty((), dtype=torch.float32, device=g.device) if has_kl else None
+        stream = torch.cuda.current_stream(g.device).cuda_stream
+        _lib.check(_lib.lib().lbbnn_elbo_bce_loss_backward(g.data_ptr(), p.data_ptr(), p.stride(0) if B > 1 else O,
+                                                           target.data_ptr(), O, B, O, scale, g_probs.data_ptr(),
+                                                           g_logits.data_ptr() if from_head else None,
+                                                           g_kl.data_ptr() if has_kl else None, stream),
+                   "lbbnn_elbo_bce_loss_backward")
+        if from_head:
+            # the entry HOLDS p and g_probs, as _LOGITS_GRAD does: "same address" in the head's backward means "same tensor"
+            _BCE_LOGITS_GRAD[p.data_ptr()] = (g_probs.data_ptr(), g_logits, p, g_probs)
+        return g_probs, None, g_kl, None, None, None
+
+
+def _bce_target(probs, target):
+    """``target`` as the (B, O) float32 block the loss reads, or ValueError naming the mismatch -- checked before any pointer is
+    handed to the library."""
+    if not torch.is_tensor(target):
+        raise ValueError("bnn_amd: elbo_bce_loss: target must be a tensor, got %s" % type(target).__name__)
+    if probs.dim() != 2:
+        raise ValueError("bnn_amd: elbo_bce_loss: probs must be (B, O), got shape %s" % (tuple(probs.shape),))
+    if target.dtype != torch.float32:
+        raise ValueError("bnn_amd: elbo_bce_loss: target must be float32 (0 / 1 or probabilities), got %s" % target.dtype)
+    if target.device != probs.device:
+        raise ValueError("bnn_amd: elbo_bce_loss: target is on %s, probs on %s" % (target.device, probs.device))
+    if tuple(target.shape) != tuple(probs.shape) and not (probs.shape[1] == 1 and tuple(target.shape) == (probs.shape[0],)):
+        raise ValueError("bnn_amd: elbo_bce_loss: target has shape %s, probs %s" % (tuple(target.shape), tuple(probs.shape)))
+    if not target.is_contiguous():
+        raise ValueError("bnn_amd: elbo_bce_loss: target must be contiguous (strides %s)" % (tuple(target.stride()),))
+    return target.view(probs.shape)
+
+
+def elbo_bce_loss(probs, target, kl=None, num_batches=1.0, *, stats=None):
+    """nn.BCELoss(reduction='sum')(probs, target) + kl / num_batches -- the sim-study scripts' loss for a sigmoid head.
+
+    ``probs`` (B, O) probabilities, ``target`` float32 of the same shape (or (B,) against (B, 1)), contiguous, on the device of
+    ``probs``; anything else is a ValueError before any launch.  HIP float32 tensors: ONE forward and ONE backward launch
+    (lbbnn_elbo_bce_loss*); when ``probs`` is what a ``head="sigmoid"`` network returned, the backward launch also forms the
+    gradient with respect to the logits and the head's backward takes it.  Anything else (CPU tensors): the same expression in
+    torch ops.
+
+    ``stats``: an int32[4] device tensor that every call ADDS to -- correct ((p > 0.5) == (y > 0.5)), elements, bad_targets (y
+    outside [0, 1] or not finite: no loss, no gradient), nonfinite_probs.  Nothing here reads it: reading it (``stats.tolist()``)
+    is the caller's synchronisation, once per epoch in a training loop; zero it with ``stats.zero_()``."""
+    t = _bce_target(probs, target)
+    if stats is not None and not (torch.is_tensor(stats) and stats.dtype == torch.int32 and stats.numel() == 4
+                                  and stats.is_contiguous() and stats.device == probs.device):
+        raise ValueError("bnn_amd: elbo_bce_loss: stats must be a contiguous int32[4] tensor on %s" % probs.device)
+    if not 1 <= probs.shape[1] <= 16 and probs.is_cuda:
+        raise ValueError("bnn_amd: elbo_bce_loss: the fused loss takes 1 to 16 output units, got %d" % probs.shape[1])
+    if (probs.is_cuda and probs.dtype == torch.float32
+            and (kl is None or (torch.is_tensor(kl) and kl.is_cuda and kl.dtype == torch.float32 and kl.numel() == 1))):
+        from . import layers
+        from_head = isinstance(probs.grad_fn, layers._SigmoidHeadFn._backward_cls)
+        return _ElboBceLossFn.apply(probs, t, kl if kl is None else kl.reshape(()), 1.0 / float(num_batches), stats, from_head)
+    ok = (t >= 0) & (t <= 1)
+    bce = F.binary_cross_entropy(torch.where(ok, probs, torch.ones_like(probs)), torch.where(ok, t, torch.ones_like(t)),
+                                 reduction="sum")
+    if stats is not None:
+        with torch.no_grad():
+            c = ((probs > 0.5) == (t > 0.5)) & ok
+            stats += torch.stack([c.sum(), torch.tensor(t.numel(), device=t.device), (~ok).sum(),
+                                  (~torch.isfinite(probs)).sum()]).to(torch.int32)
+    return bce if kl is None else bce + kl / num_batches
 
 
 class _SumKLFn(torch.autograd.Function):

@@ -1004,6 +1004,41 @@ def log_softmax_rows(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> tor
     return out
 
 
+def binary_head(logits: torch.Tensor, *, probs: Optional[torch.Tensor] = None, log_probs: bool = False,
+                want_probs: bool = True):
+    """lbbnn_binary_head on a (B, O <= 16) block of logits with dense rows: the probabilities 1 / (1 + exp(-x)) (a new (B, O)
+    tensor, or ``probs`` -- which may be ``logits`` itself) and / or, with ``log_probs`` (O == 1), the (B, 2) log-probabilities
+    [logsigmoid(-x), logsigmoid(x)] of the two classes, from the logits in the same launch.  Returns probs, logp2 or the pair."""
+    B, O = logits.shape
+    if not (want_probs or log_probs):
+        raise ValueError("bnn_amd: binary_head has nothing to compute")
+    if log_probs and O != 1:
+        raise ValueError("bnn_amd: the 2-class log-probabilities of the binary head need one output unit, got %d" % O)
+    if want_probs and probs is None:
+        probs = torch.empty((B, O), dtype=torch.float32, device=logits.device)
+    logp2 = torch.empty((B, 2), dtype=torch.float32, device=logits.device) if log_probs else None
+    rc = _lib.lib().lbbnn_binary_head(_ptr_rows(logits, "logits"), logits.stride(0) if B > 1 else O, B, O,
+                                      _ptr_rows(probs, "probs") if want_probs else None,
+                                      (probs.stride(0) if B > 1 else O) if want_probs else 0,
+                                      logp2.data_ptr() if log_probs else None, 2, _stream())
+    _lib.check(rc, "lbbnn_binary_head")
+    if want_probs and log_probs:
+        return probs, logp2
+    return probs if want_probs else logp2
+
+
+def sigmoid_backward(g: torch.Tensor, probs: torch.Tensor) -> torch.Tensor:
+    """lbbnn_sigmoid_backward: g * ((1 - p) * p) for (B, O <= 16) tensors."""
+    B, O = g.shape
+    if g.stride(1) != 1:
+        g = g.contiguous()
+    out = torch.empty((B, O), dtype=torch.float32, device=g.device)
+    rc = _lib.lib().lbbnn_sigmoid_backward(_ptr_rows(g, "g"), g.stride(0) if B > 1 else O, _ptr_rows(probs, "probs"),
+                                           probs.stride(0) if B > 1 else O, out.data_ptr(), O, B, O, _stream())
+    _lib.check(rc, "lbbnn_sigmoid_backward")
+    return out
+
+
 # ----------------------------------------------------------------------------------------- workspaces
 class LayerWorkspace:
     """Caller-owned device buffers of one layer, allocated once and reused every forward

@@ -140,6 +140,10 @@ class DataParallelELBO:
     """
 
     def __init__(self, net, group=None):
+        if getattr(net, "head", "log_softmax") != "log_softmax":
+            # (its loss is nll_loss over class ids: on probabilities that would be a wrong number, not an error)
+            raise NotImplementedError("bnn_amd: DataParallelELBO supports log_softmax heads only; this network has head=%r"
+                                      % (net.head,))
         self.net = net
         self.group = group
         on = dist.is_available() and dist.is_initialized()

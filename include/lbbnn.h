@@ -1158,6 +1158,35 @@ int lbbnn_elbo_loss_backward_logits(const float* g, const int64_t* target, const
 int lbbnn_log_softmax_backward(const float* g, int ldg, const float* logp, int ldp, float* out, int ldo, int B, int C,
                                void* stream);
 
+/* The binary (sigmoid) head and its fused loss: torch.sigmoid on the last layer's logits and nn.BCELoss(reduction='sum') +
+ * kl / NUM_BATCHES, the logistic-regression form of the networks.  One launch each, one pass, fixed-order sums, no atomics:
+ * the same bits from run to run.  (B, O) blocks with dense rows and a free row stride (ld*, floats); 0 <= B, 1 <= O <= 16,
+ * B * O < 2^31, every ld >= O (LBBNN_E_SHAPE); a required pointer NULL: LBBNN_E_NULL; a pointer off 4 bytes: LBBNN_E_ALIGN.
+ *
+ * lbbnn_binary_head: probs[b][o] = 1 / (1 + expf(-x)) (may be `logits` itself: in place) and / or, for O == 1 only
+ *   (LBBNN_E_SHAPE otherwise; ld2 >= 2), logp2 (B, 2) = [logsigmoid(-x), logsigmoid(x)] with logsigmoid(x) = min(x, 0) -
+ *   log1pf(expf(-|x|)): the log-probabilities of the two classes, formed from the logit (finite for every finite x; log(1 - p)
+ *   would be -inf from x = 17 on).  Either output may be NULL, not both (LBBNN_E_NULL).  B == 0: a successful no-op.  A member
+ *   dimension is the caller's: (S, B, O) dense is B' = S * B, padded members are one call each.
+ * lbbnn_elbo_bce_loss: one workgroup, fp64 partial sums:
+ *   *loss = sum_{b,o} ( (y - 1) max(log1pf(-p), -100) - y max(logf(p), -100) ) + (kl ? *kl * kl_scale : 0)
+ *   -- -(y log p + (1 - y) log(1 - p)) in the spelling of torch's binary_cross_entropy, whose fp32 terms these are bit for bit.
+ *   target: fp32 in [0, 1], the shape of probs.  stats (int32[4], nullable; accumulate != 0 adds to what it holds):
+ *     [0] correct          elements with a valid target and (p > 0.5f) == (y > 0.5f): round(p) == y for 0 / 1 targets
+ *     [1] elements         B * O
+ *     [2] bad_targets      y outside [0, 1] or not finite; such elements add nothing to the loss, to `correct` or to a gradient
+ *     [3] nonfinite_probs
+ * lbbnn_elbo_bce_loss_backward: g_probs (B, O dense) = (*g) (p - y) / max((1 - p) p, 1e-12f) (torch's
+ *   binary_cross_entropy_backward) and, when g_logits (B, O dense) is given, g_logits = g_probs ((1 - p) p) in the same launch
+ *   -- bitwise what lbbnn_sigmoid_backward makes of g_probs; *g_kl = (*g) kl_scale (g_kl nullable).
+ * lbbnn_sigmoid_backward: out = g ((1 - p) p), the backward of the head for probabilities that feed another loss. */
+int lbbnn_binary_head(const float* logits, int ldi, int B, int O, float* probs, int ldp, float* logp2, int ld2, void* stream);
+int lbbnn_elbo_bce_loss(const float* probs, int ldp, const float* target, int ldt, int B, int O, const float* kl, float kl_scale,
+                        float* loss, int* stats, int accumulate, void* stream);
+int lbbnn_elbo_bce_loss_backward(const float* g, const float* probs, int ldp, const float* target, int ldt, int B, int O,
+                                 float kl_scale, float* g_probs, float* g_logits, float* g_kl, void* stream);
+int lbbnn_sigmoid_backward(const float* g, int ldg, const float* probs, int ldp, float* out, int ldo, int B, int O, void* stream);
+
 /* lbbnn_layers_operands_snap + lbbnn_format_x of the network input in the SAME launches: the planar flows of a network are two
  * latency-bound workgroups per layer, and the format job (one pass over x) runs as extra workgroups of that launch on the CUs
  * it leaves idle -- no launch of its own, nothing added to the critical path.  Falls back to a separate lbbnn_format_x launch
