@@ -110,22 +110,24 @@ def _dense_descs(kind, params, masks, grads=None):
     import ctypes
     from . import _lib
     names = _RNVP_NAMES if kind == "RNVP" else _MNF_NAMES
+    from .flows import dense_hidden
     T = len(masks)
+    n = len(names)
+    hidden = [dense_hidden(kind, dict(zip(names, params[t * n:(t + 1) * n]))) for t in range(T)]   # refusals first
     arr = (_lib.DenseTransform * max(T, 1))()
     garr = (_lib.DenseGrad * max(T, 1))() if grads is not None else None
-    n = len(names)
     for t in range(T):
         p = dict(zip(names, params[t * n:(t + 1) * n]))
         d = arr[t]
         if kind == "RNVP":
-            d.kind, d.hidden = 0, p["network.0.weight"].shape[0]
+            d.kind, d.hidden = 0, hidden[t]
             d.w_in, d.b_in = p["network.0.weight"].data_ptr(), p["network.0.bias"].data_ptr()
             for l, idx in enumerate((2, 4, 6)):
                 d.w_mid[l], d.b_mid[l] = p["network.%d.weight" % idx].data_ptr(), p["network.%d.bias" % idx].data_ptr()
             d.w_a, d.b_a, d.w_b, d.b_b = (p["t.weight"].data_ptr(), p["t.bias"].data_ptr(), p["s.weight"].data_ptr(),
                                           p["s.bias"].data_ptr())
         else:
-            d.kind, d.hidden = 1, p["f.weight"].shape[0]
+            d.kind, d.hidden = 1, hidden[t]
             d.w_in, d.b_in = p["f.weight"].data_ptr(), p["f.bias"].data_ptr()
             d.w_a, d.b_a, d.w_b, d.b_b = (p["g.weight"].data_ptr(), p["g.bias"].data_ptr(), p["k.weight"].data_ptr(),
                                           p["k.bias"].data_ptr())
@@ -186,7 +188,10 @@ class _DenseFlowFn(torch.autograd.Function):
 
 
 def _dense_hip(z, kind, tr, masks):
+    from .flows import dense_hidden
     names = _RNVP_NAMES if kind == "RNVP" else _MNF_NAMES
+    for t in tr:
+        dense_hidden(kind, t)              # (the whole parameter dict: a list of another length than 4 is refused, not cut)
     flat = [t[n] for t in tr for n in names]
     return _DenseFlowFn.apply(kind, len(masks), z, *masks, *flat)
 

@@ -422,7 +422,18 @@ static int dense_flows_impl(const lbbnn_dense_layer_t* L, int n, const uint64_t*
             for (int t = 0; t < ia.Tm[2]; ++t) ia.mk[2][t] = const_cast<float*>(d.rt[t].mask_kl);
         }
     }
-    if (phase != 2) hipLaunchKernelGGL(dense_init_kernel, dim3(gblk, npaths, n), dim3(NTC), 0, s, ib);
+    if (phase != 2) {
+        hipLaunchKernelGGL(dense_init_kernel, dim3(gblk, npaths, n), dim3(NTC), 0, s, ib);
+        // An empty z flow: z_fwd / z_kl are the draws themselves.  Copied HERE, before the r flow runs: without `save` the r
+        // flow transforms the KL draw in place (zbuf1), and a copy made after it handed r_flow(z2) to the weight pass as z2.
+        if (Tz == 0) {
+            for (int k = 0; k < n; ++k) {
+                const lbbnn_dense_layer_t& d = L[k];
+                if (want_kl) (void)hipMemcpyAsync(d.z_kl, d.save ? B[k].ZK : B[k].zbuf1, (size_t)d.I * sizeof(float), hipMemcpyDeviceToDevice, s);
+                if (d.save) (void)hipMemcpyAsync(d.z_fwd, B[k].ZF, (size_t)d.I * sizeof(float), hipMemcpyDeviceToDevice, s);
+            }
+        }
+    }
 
     for (int t = 0; t < S; ++t) {
         const bool zphase = t < Tz;
@@ -471,10 +482,6 @@ static int dense_flows_impl(const lbbnn_dense_layer_t* L, int n, const uint64_t*
     for (int k = 0; k < n; ++k) {
         const lbbnn_dense_layer_t& d = L[k];
         const Bufs& b = B[k];
-        if (phase != 2) {
-            if (want_kl && Tz == 0) (void)hipMemcpyAsync(d.z_kl, d.save ? b.ZK : b.zbuf1, (size_t)d.I * sizeof(float), hipMemcpyDeviceToDevice, s);
-            if (d.save && Tz == 0) (void)hipMemcpyAsync(d.z_fwd, b.ZF, (size_t)d.I * sizeof(float), hipMemcpyDeviceToDevice, s);
-        }
         FinishArgs& fa = fb.l[k];
         fa.ldz = b.ldz; fa.ldr = b.ldr; fa.lq0 = b.lq0;
         fa.zr = !d.save ? b.zbuf1 : ((want_kl && Tr > 0) ? b.ZR + (size_t)(Tr - 1) * d.I : b.ZK + (size_t)Tz * d.I); fa.ldf = b.ldf; fa.scal = d.scal;

@@ -1032,19 +1032,22 @@ class FrozenNetwork(nn.Module):
         """lbbnn_dense_transform_t of every transform of layer i's z flow, pointing at this model's copies (built once: the
         buffers never move)."""
         from . import _lib
+        from .flows import dense_hidden
         T = self._T[i]
+        hidden = [dense_hidden(kind, {k: getattr(self, self._zflow_buf(i, t, k)) for k in self._zflow_names[i][t]})
+                  for t in range(T)]
         arr = (_lib.DenseTransform * max(T, 1))()
         for t in range(T):
             g = lambda k: getattr(self, self._zflow_buf(i, t, k))
             d = arr[t]
             if kind == "RNVP":                               # flows2.py:188-219: 4-layer MLP, shift (t) and scale (s) heads
-                d.kind, d.hidden = 0, g("network.0.weight").shape[0]
+                d.kind, d.hidden = 0, hidden[t]
                 d.w_in, d.b_in = g("network.0.weight").data_ptr(), g("network.0.bias").data_ptr()
                 for m, k in enumerate((2, 4, 6)):
                     d.w_mid[m], d.b_mid[m] = g("network.%d.weight" % k).data_ptr(), g("network.%d.bias" % k).data_ptr()
                 a, b = "t", "s"
             else:                                            # flows2.py:225-241: f, then the g (mu) and k (sigma) heads
-                d.kind, d.hidden = 1, g("f.weight").shape[0]
+                d.kind, d.hidden = 1, hidden[t]
                 d.w_in, d.b_in = g("f.weight").data_ptr(), g("f.bias").data_ptr()
                 a, b = "g", "k"
             d.w_a, d.b_a = g(a + ".weight").data_ptr(), g(a + ".bias").data_ptr()
@@ -1354,11 +1357,13 @@ def _check_freezable_layers(layers, dense: bool = False):
             if T > _lib.MAX_DENSE_T:
                 raise ValueError("bnn_amd: layer %d: z_flow has %d transforms, the member kernel of the dense z flows takes at "
                                  "most %d; %s" % (i + 1, T, _lib.MAX_DENSE_T, loop))
-            hidden = max([p.shape[0] for tr in l.z_flow.transforms for k, p in tr.named_parameters()
-                          if k in ("network.0.weight", "f.weight")] or [1])
-            if hidden > _lib.MAX_HIDDEN:
-                raise ValueError("bnn_amd: layer %d: the coupling networks of z_flow have %d hidden units, the member kernel takes "
-                                 "at most %d; %s" % (i + 1, hidden, _lib.MAX_HIDDEN, loop))
+            from .flows import dense_hidden
+            for tr in l.z_flow.transforms:
+                try:
+                    dense_hidden(l.z_flow.kind, dict(tr.named_parameters()))
+                except ValueError as e:
+                    # (no forward of this library takes such a flow: the loop form refuses it with the same words)
+                    raise ValueError("bnn_amd: layer %d: z_flow: %s" % (i + 1, str(e).replace("bnn_amd: ", ""))) from None
         elif l._mnf:
             if l._check_flows() != "planar" or len(l.z_flow.transforms) > 4:
                 raise ValueError("bnn_amd: layer %d: a frozen MNF model needs planar flows with at most 4 transforms (it has "
@@ -1390,7 +1395,9 @@ def freeze(net, gates: str = "alpha", *, threshold: float = 0.5, dense: bool = F
     ROUNDING, not bit for bit.  The loop draws its masks from torch's generator when LBBNN_TORCH_MASKS=1 is set; a frozen
     model always draws them in the kernel (Philox stream LBBNN_STREAM_MASK).  A planar or LRT network with ``dense=True``
     takes the path, and gives the bits, of ``dense=False``.  Each refusal is a ValueError that names the layer; the loop form
-    ``ensemble_forward(net, data, samples)`` takes every network."""
+    ``ensemble_forward(net, data, samples)`` takes every network but one whose coupling networks are not of one hidden width
+    of at most ``_lib.MAX_HIDDEN`` units (``flows.dense_hidden``): no HIP kernel of this library takes those, and the loop's
+    forward refuses them with the same ValueError."""
     from . import layers as L
     if gates not in FROZEN_GATES:
         raise ValueError("bnn_amd: gates must be 'alpha' (the gates as trained) or 'mpm' (the median probability model), got %r"

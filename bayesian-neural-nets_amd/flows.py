@@ -155,6 +155,36 @@ class HouseholderTransform(_Transform):
         self.v = nn.Parameter(parameter_init(-0.01, 0.01, dim))
 
 
+def dense_hidden(kind, params):
+    """The hidden width H of one RNVP / MNF-type transform as the HIP kernels take it (lbbnn_dense_transform_t::hidden), from
+    ``params``: the transform's parameters by their state_dict names (anything with a ``.shape``).  The kernels know ONE
+    width per transform -- RNVP: four hidden layers of H units (three H x H matrices), MNF type: one of H units -- with
+    1 <= H <= LBBNN_MAX_HIDDEN, so everything else is refused here, before a descriptor is built: a ValueError that
+    names the widths.  Called by every path that hands such a transform to a kernel: ``PropagateFlow.dense_descs`` (the
+    layer's forward and backward, the row kernel), ``_grad._dense_descs`` (lbbnn_flow_dense_apply[_backward]) and
+    ``evaluate.freeze(dense=True)``.  The torch formulas of ``_grad._dense`` take any widths."""
+    from . import _lib
+    if kind == "RNVP":
+        idx = sorted(int(k.split(".")[1]) for k in params if k.startswith("network.") and k.endswith(".weight"))
+        ws = [params["network.%d.weight" % i] for i in idx]
+        widths = tuple(int(w.shape[0]) for w in ws)
+        fan_in = tuple(int(w.shape[1]) for w in ws[1:]) + tuple(int(params[k].shape[1]) for k in ("t.weight", "s.weight"))
+        what = "RNVP h_sizes = %s" % (widths,)
+        ok = len(widths) == 4 and len(set(widths)) == 1 and all(f == widths[0] for f in fan_in)
+        rule = "four hidden layers of one width"
+    elif kind == "MNF":
+        widths = (int(params["f.weight"].shape[0]),)
+        what = "MNF hidden = %d" % widths
+        ok = all(int(params[k].shape[1]) == widths[0] for k in ("g.weight", "k.weight"))
+        rule = "one hidden layer"
+    else:
+        raise ValueError("bnn_amd: %r is not a dense coupling flow (RNVP / MNF)" % (kind,))
+    if not ok or not 1 <= widths[0] <= _lib.MAX_HIDDEN:
+        raise ValueError("bnn_amd: the HIP kernels of the coupling flows take %s, 1 to %d units wide; got %s"
+                         % (rule, _lib.MAX_HIDDEN, what))
+    return widths[0]
+
+
 _KINDS = {"Planar": PlanarTransform, "RNVP": RNVP, "MNF": MNF, "Radial": RadialTransform,
           "Sylvester": SylvesterTransform, "Householder": HouseholderTransform}
 VECTOR_KINDS = ("Planar", "Radial", "Sylvester", "Householder", "mixed")     # 1-D flows: lbbnn_flow_chain
@@ -199,20 +229,21 @@ class PropagateFlow(nn.Module):
         (or None) for the forward-draw call and the KL-branch call.  Returns (array, T, keepalive)."""
         from . import _lib
         T = len(self.transforms)
+        hidden = [dense_hidden(self.kind, dict(tr.named_parameters())) for tr in self.transforms]   # refusals: before anything is built
         arr = (_lib.DenseTransform * max(T, 1))()
         keep = []
         for t, tr in enumerate(self.transforms):
             d = arr[t]
             if self.kind == "RNVP":
                 lin = [tr.network[0], tr.network[2], tr.network[4], tr.network[6]]
-                d.kind, d.hidden = 0, lin[0].out_features
+                d.kind, d.hidden = 0, hidden[t]
                 d.w_in, d.b_in = lin[0].weight.data_ptr(), lin[0].bias.data_ptr()
                 for l in range(3):
                     d.w_mid[l], d.b_mid[l] = lin[l + 1].weight.data_ptr(), lin[l + 1].bias.data_ptr()
                 d.w_a, d.b_a, d.w_b, d.b_b = (tr.t.weight.data_ptr(), tr.t.bias.data_ptr(),
                                               tr.s.weight.data_ptr(), tr.s.bias.data_ptr())
             else:
-                d.kind, d.hidden = 1, tr.f.out_features
+                d.kind, d.hidden = 1, hidden[t]
                 d.w_in, d.b_in = tr.f.weight.data_ptr(), tr.f.bias.data_ptr()
                 d.w_a, d.b_a, d.w_b, d.b_b = (tr.g.weight.data_ptr(), tr.g.bias.data_ptr(),
                                               tr.k.weight.data_ptr(), tr.k.bias.data_ptr())
