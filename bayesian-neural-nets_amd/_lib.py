@@ -200,6 +200,11 @@ class FrozenDesc(ctypes.Structure):
                [("cut", ctypes.c_float), ("layer_id", c_u32)]
 
 
+class CompactMap(ctypes.Structure):
+    """lbbnn_compact_map_t"""
+    _fields_ = [("rows", c_p), ("cols", c_p), ("O_full", c_i), ("I_full", c_i)]
+
+
 class DenseMembers(ctypes.Structure):
     """lbbnn_dense_members_t"""
     _fields_ = [("q0_mean", c_p), ("q0_log_var", c_p), ("zt", ctypes.POINTER(DenseTransform)), ("T", c_i), ("I", c_i),
@@ -386,6 +391,9 @@ SIGNATURES = {
     "lbbnn_flow_dense_members_max_dim": (c_i, []),
     "lbbnn_flow_dense_members": (c_i, [ctypes.POINTER(DenseMembers), c_i, c_i, c_p, c_u64, c_p]),
     "lbbnn_frozen_members_dense": (c_i, [ctypes.POINTER(FrozenDesc), ctypes.POINTER(DenseMembers), c_i, c_i, c_p, c_u64, c_p]),
+    "lbbnn_frozen_operands_compact": (c_i, [ctypes.POINTER(FrozenDesc), ctypes.POINTER(CompactMap), c_i, c_p]),
+    "lbbnn_frozen_members_compact": (c_i, [ctypes.POINTER(FrozenDesc), ctypes.POINTER(CompactMap), c_i, c_i, c_p, c_u64, c_p]),
+    "lbbnn_gather_columns": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_p]),
     "lbbnn_eval_metrics_work_bytes": (c_i64, [c_i, c_i, c_i]),
     "lbbnn_eval_metrics": (c_i, [ctypes.POINTER(EvalMetricsArgs), c_p]),
     "lbbnn_eval_uncertainty_work_bytes": (c_i64, [c_i, c_i, c_i, c_i]),

@@ -1375,7 +1375,244 @@ def _check_freezable_layers(layers, dense: bool = False):
                                  % (i + 1, l.in_features))
 
 
-def freeze(net, gates: str = "alpha", *, threshold: float = 0.5, dense: bool = False) -> FrozenNetwork:
+# ----------------------------------------------------------------------------------------- compact median-probability model
+def _live_structure(keep_masks, align: int):
+    """``live_structure`` plus the needed counts as host integers (ONE device read for all boundaries)."""
+    n = len(keep_masks)
+    if n < 1:
+        raise ValueError("bnn_amd: live_structure needs at least one keep mask")
+    align = int(align)
+    if align < 1:
+        raise ValueError("bnn_amd: align must be >= 1, got %d" % align)
+    for i, k in enumerate(keep_masks):
+        if k.dim() != 2 or k.dtype != torch.bool:
+            raise ValueError("bnn_amd: keep mask %d must be a 2-d bool tensor (out_features, in_features)" % i)
+        if i and k.shape[1] != keep_masks[i - 1].shape[0]:
+            raise ValueError("bnn_amd: keep mask %d has %d columns, the layer below %d rows" % (i, k.shape[1], keep_masks[i - 1].shape[0]))
+    dev = keep_masks[0].device
+    need = [None] * (n + 1)
+    need[n] = torch.ones(keep_masks[-1].shape[0], dtype=torch.bool, device=dev)
+    for i in range(n - 1, -1, -1):                           # one backward sweep: a unit is needed iff a needed unit keeps it
+        need[i] = (keep_masks[i] & need[i + 1][:, None]).any(0)
+    counts = torch.stack([nd.sum() for nd in need]).tolist()
+    live = []
+    for b, nd in enumerate(need):
+        w = nd.numel()
+        size = w if b == n else min(w, max(align, -(-counts[b] // align) * align))
+        idx = torch.arange(w, device=dev)
+        # needed units first (by index), then the unneeded ones by index: the first `size` of that order, sorted again
+        order = torch.sort(torch.where(nd, idx, idx + w)).indices[:size]
+        live.append(torch.sort(order).values.to(torch.int32))
+    return need, live, [int(c) for c in counts]
+
+
+def live_structure(keep_masks, align: int = 8):
+    """The units of a pruned network that some output depends on.  ``keep_masks``: per layer the (out_features, in_features)
+    bool mask of the kept weights (CPU or HIP tensors).  A network of n layers has n + 1 boundaries: 0 = the input features,
+    n = the output units.  Returns ``(need, live)``:
+
+    ``need[b]`` (bool, width of boundary b): ``need[n]`` is all true and ``need[i][j] = any_o(need[i+1][o] & keep_i[o][j])``
+    -- a unit is needed iff a needed unit keeps a weight from it.  A needed unit with no kept input stays: it still emits
+    relu(bias + noise).
+    ``live[b]`` (sorted int32 indices): the needed units of boundary b, topped up with the lowest-index unneeded units to
+    ``min(width_b, max(align, ceil_to_align(count)))`` units; ``live[n]`` is every output unit.  Topping up with dead units
+    is exact -- everything that consumes them has weight 0 and variance 0 -- and keeps the widths multiples of ``align``
+    (8: what the member GEMM, in_features % 4, and the bf16 hi | lo kernels, in_features % 8, take)."""
+    need, live, _ = _live_structure(keep_masks, align)
+    return need, live
+
+
+class CompactFrozenNetwork(FrozenNetwork):
+    """The median probability model without the units no output depends on (``freeze(net, "mpm", compact=True)``): a
+    ``FrozenNetwork`` whose ``dims`` are the compact widths, so every GEMM, the ensemble, the accumulators and the graphed
+    evaluation step run as for any frozen model, at the smaller shapes.
+
+    ``full_dims``: the source network's widths; ``live``: per boundary the sorted int32 indices of the units that stay
+    (buffers ``live_<b>``, ``evaluate.live_structure``); ``needed``: per boundary the number of needed units before the
+    top-up to a multiple of 8; ``active_kept`` / ``active_density``: the kept weights whose row and column are both needed,
+    and their share of all weights of the full network (the "active paths" density); ``density``: the FULL network's
+    density, to compare with; ``kept_rows``: per compact row the kept weights among the live columns.
+
+    Draws: z of an MNF layer is drawn at the full width -- member m's z is the full model's, bit for bit (``keep_z`` returns
+    it at full width) -- and gathered inside the launch that scales the member operands; eps_out of a layer is indexed by the
+    COMPACT column, so a stochastic member equals the full model's member in distribution, not in numbers.  The
+    posterior-mean forward draws no eps_out and equals the full model's to fp32 rounding.  Input rows are gathered to the
+    live features by one lbbnn_gather_columns launch; when every input feature is live there is no launch and no copy."""
+
+    def __init__(self, full_dims, live, needed, family: str = "lrt", threshold: float = 0.5, device=None, head: str = "log_softmax"):
+        full_dims = tuple(int(d) for d in full_dims)
+        if len(live) != len(full_dims) or len(needed) != len(full_dims):
+            raise ValueError("bnn_amd: a network of %d layers has %d boundaries" % (len(full_dims) - 1, len(full_dims)))
+        super().__init__([int(t.numel()) for t in live], family, "mpm", threshold, device=device, head=head)
+        self.full_dims = full_dims
+        self.needed = [int(c) for c in needed]
+        for b, t in enumerate(live):
+            self.register_buffer("live_%d" % b, t.to(device=device, dtype=torch.int32).contiguous())
+        self._input_identity = self.dims[0] == self.full_dims[0]     # sorted, unique, full width: every feature in place
+        self._maps = None
+        self._active = self._full_kept = None
+
+    @property
+    def live(self) -> List[torch.Tensor]:
+        return [self._buf("live", b) for b in range(len(self.dims))]
+
+    @property
+    def active_kept(self) -> int:
+        """Kept weights whose row and column are both needed (over every layer)."""
+        return int(self._active)
+
+    @property
+    def active_density(self) -> float:
+        return self.active_kept / sum(self.full_dims[i] * self.full_dims[i + 1] for i in range(self.n_layers))
+
+    @property
+    def density(self) -> float:
+        """Kept weights / all weights of the FULL network: what ``freeze(net, "mpm").density`` reports."""
+        return int(self._full_kept) / sum(self.full_dims[i] * self.full_dims[i + 1] for i in range(self.n_layers))
+
+    def extra_repr(self) -> str:
+        return "full_dims=%s, %s" % (self.full_dims, super().extra_repr())
+
+    # ------------------------------------------------------------------------------------- snapshot
+    @torch.no_grad()
+    def _bind(self, net, need=None, masks=None):
+        """Allocate every buffer at the compact shapes and take THE snapshot: one lbbnn_frozen_operands_compact launch per
+        layer group, index_select of bias_mu, copies of the full-width q0 and z flow of an MNF layer."""
+        from . import _lib
+        layers = net._layers()
+        dev = layers[0].weight_mu.device
+        f = dict(dtype=torch.float32, device=dev)
+        n = self.n_layers
+        self._src = [net]
+        self._layer_ids = [int(l._layer_id) for l in layers]
+        self._row_offsets = [int(l.row_offset) for l in layers]
+        if masks is not None:
+            self._full_kept = torch.stack([k.sum() for k in masks]).sum()
+            self._active = torch.stack([(k & need[i + 1][:, None] & need[i][None, :]).sum() for i, k in enumerate(masks)]).sum()
+        live = self.live
+        dst, src = [], []
+        for i, l in enumerate(layers):
+            O, I = self.dims[i + 1], self.dims[i]
+            ld = ops.operand_ld(I)
+            # the rule of FrozenNetwork._bind at the compact shape
+            self._split.append(bool(ops.split_precision(l)) and ops.split_eligible(I, O) and (i == 0 or self.dims[i] % 4 == 0))
+            if I % 4 or ld > 2048:
+                self._members_ok = False
+            for name, shape in (("e0", (O, ld)), ("e_w", (O, ld)), ("var_w", (O, ld)), ("bias_var", (O,)), ("bias_mu", (O,))):
+                self.register_buffer("%s_%d" % (name, i), _empty(shape, **f))
+            for name in ("weight_mu", "weight_rho", "lambdal"):
+                if not getattr(l, name).is_contiguous():
+                    raise RuntimeError("bnn_amd: %s of layer %d is not contiguous" % (name, i + 1))
+            torch.index_select(l.bias_mu.detach(), 0, live[i + 1].long(), out=self._buf("bias_mu", i))
+            if l._mnf:
+                T, If = len(l.z_flow.transforms), self.full_dims[i]
+                self._T.append(T)
+                for name, shape in (("q0_mean", (If,)), ("q0_log_var", (If,)), ("flow_u", (T, If)), ("flow_w", (T, If)),
+                                    ("flow_b", (T, 1))):
+                    self.register_buffer("%s_%d" % (name, i), _empty(shape, **f))
+                dst += [self._buf("q0_mean", i), self._buf("q0_log_var", i)]
+                src += [l.q0_mean.detach(), l.q0_log_var.detach()]
+                for t, tr in enumerate(l.z_flow.transforms):
+                    dst += [self._buf("flow_u", i)[t], self._buf("flow_w", i)[t], self._buf("flow_b", i)[t]]
+                    src += [tr.u.detach().reshape(-1), tr.w.detach().reshape(-1), tr.bias.detach().reshape(-1)]
+            else:
+                self._T.append(0)
+        if dst:
+            torch._foreach_copy_(dst, src)
+        if self.family == "mnf" and not self._members_ok:
+            raise ValueError("bnn_amd: a compact MNF model needs compact in_features %% 4 == 0 and operand rows of at most 2048 "
+                             "(compact dims %s); use freeze(net, \"mpm\") without compact=True" % (self.dims,))
+        self._maps = (_lib.CompactMap * n)()
+        for i in range(n):
+            m = self._maps[i]
+            m.rows, m.cols = live[i + 1].data_ptr(), live[i].data_ptr()
+            m.O_full, m.I_full = self.full_dims[i + 1], self.full_dims[i]
+        descs = self._descs(layers)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            for k, cnt in _lib.layer_groups(n):
+                _lib.check(_lib.lib().lbbnn_frozen_operands_compact(_lib.group_slice(descs, k, cnt), _lib.group_slice(self._maps, k, cnt),
+                                                                    cnt, stream), "lbbnn_frozen_operands_compact")
+        return self
+
+    def refresh(self):
+        raise NotImplementedError("bnn_amd: a compact model does not refresh: the structure, and with it every shape, may have "
+                                  "changed with the parameters -- freeze again (evaluate.freeze(net, \"mpm\", compact=True))")
+
+    # ------------------------------------------------------------------------------------- evaluation
+    def _input(self, data):
+        if self._input_identity:
+            return super()._input(data)
+        from . import _lib
+        x = data.reshape(-1, self.full_dims[0])
+        if not x.is_cuda:
+            raise RuntimeError("bnn_amd: a frozen model evaluates on a HIP device tensor (data is on %s); there is no CPU path"
+                               % data.device)
+        dev = self._buf("e0", 0).device
+        if x.device != dev:
+            raise RuntimeError("bnn_amd: data is on %s, the frozen model on %s" % (x.device, dev))
+        x = x.float() if x.dtype != torch.float32 else x
+        if x.stride(1) != 1 or x.stride(0) < self.full_dims[0]:
+            x = x.contiguous()
+        B, n_idx = x.shape[0], self.dims[0]
+        ldo = _pad4(n_idx)                                   # dense rows on 16-B boundaries: what the bf16 hi | lo kernels read
+        if self._split[0] and B * ldo * 4 >= 0x7FFFFFF0:
+            raise ValueError("bnn_amd: a batch of %d rows exceeds the 2 GiB the 16-bit kernels address; split it" % B)
+        out = _empty((B, ldo), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().lbbnn_gather_columns(x.data_ptr(), x.stride(0),
+                                                       self._buf("live", 0).data_ptr(), n_idx, out.data_ptr(), ldo, B,
+                                                       torch.cuda.current_stream(dev).cuda_stream), "lbbnn_gather_columns")
+        return out[:, :n_idx] if ldo != n_idx else out
+
+    def _member_buffers(self, c: int):
+        """As FrozenNetwork._member_buffers, with z at the FULL width of every layer (the flow runs there; the scale launch
+        gathers) and the member operands at the compact shapes."""
+        if c > self._mcap:
+            dev = self._buf("e0", 0).device
+            f = dict(dtype=torch.float32, device=dev)
+            self._zbuf = _empty((c, sum(ops.operand_ld(d) for d in self.full_dims[:-1])), **f)
+            self._ewm = [_empty((c, self.dims[i + 1], ops.operand_ld(self.dims[i])), **f) for i in range(self.n_layers)]
+            self._mcap = c
+        return self._zbuf, self._ewm
+
+    def _draw_members(self, c: int, rng, stream, masks=None):
+        """MNF: member m's full-width z at Philox offset rng[1] + m and its compact mean operand E0' * z_m[cols]
+        (lbbnn_frozen_members_compact: the flow launch of the full model, then one scale launch with the gather fused in)."""
+        from . import _lib
+        zbuf, ewm = self._member_buffers(c)
+        descs = self._descs()
+        off = 0
+        for i in range(self.n_layers):
+            descs[i].z_fwd = zbuf.data_ptr() + 4 * off
+            descs[i].z_mstride = zbuf.stride(0)
+            descs[i].e_w_members = ewm[i].data_ptr()
+            off += ops.operand_ld(self.full_dims[i])
+        for k, cnt in _lib.layer_groups(self.n_layers):
+            _lib.check(_lib.lib().lbbnn_frozen_members_compact(_lib.group_slice(descs, k, cnt), _lib.group_slice(self._maps, k, cnt),
+                                                               cnt, c, rng.data_ptr(), 1, stream), "lbbnn_frozen_members_compact")
+        return zbuf, ewm
+
+    def _z_of(self, zbuf, c):
+        out, off = [], 0
+        for i in range(self.n_layers):
+            out.append(zbuf[:c, off:off + self.full_dims[i]].clone())
+            off += ops.operand_ld(self.full_dims[i])
+        return out
+
+
+def _freeze_compact(net, layers, family, threshold) -> CompactFrozenNetwork:
+    dev = layers[0].weight_mu.device
+    cut = float(torch.tensor(math.log(threshold / (1.0 - threshold)), dtype=torch.float32))
+    # the tie rule of lbbnn_frozen_operands: lambdal > cut compared in fp32 (NaN is never kept)
+    masks = [l.lambdal.detach().float() > cut for l in layers]
+    need, live, needed = _live_structure(masks, 8)           # the ONE device read: the live counts size every buffer
+    fz = CompactFrozenNetwork(net.dims, live, needed, family, threshold, device=dev, head=net.head)
+    fz.eval()
+    return fz._bind(net, need, masks)
+
+
+def freeze(net, gates: str = "alpha", *, threshold: float = 0.5, dense: bool = False, compact: bool = False) -> FrozenNetwork:
     """Frozen evaluation model of an LRT / MNF network (``lrt.BayesianNetwork``, ``mnf.BayesianNetwork``) on a HIP device.
 
     ``gates="alpha"``: the gates as trained, a = sigmoid(lambdal) -- ``frozen.ensemble(x, S)`` computes what
@@ -1397,7 +1634,14 @@ def freeze(net, gates: str = "alpha", *, threshold: float = 0.5, dense: bool = F
     takes the path, and gives the bits, of ``dense=False``.  Each refusal is a ValueError that names the layer; the loop form
     ``ensemble_forward(net, data, samples)`` takes every network but one whose coupling networks are not of one hidden width
     of at most ``_lib.MAX_HIDDEN`` units (``flows.dense_hidden``): no HIP kernel of this library takes those, and the loop's
-    forward refuses them with the same ValueError."""
+    forward refuses them with the same ValueError.
+
+    ``compact=True`` (with ``gates="mpm"``; LRT and planar MNF networks) returns a ``CompactFrozenNetwork``: the median
+    probability model without the hidden units and input features no output depends on (``live_structure``), evaluated by
+    the same kernels at the smaller shapes.  Its posterior-mean forward equals the full model's to fp32 rounding; its
+    stochastic members equal the full model's in distribution (z is the same bits, eps_out is indexed by the compact column).
+    The one device read that sizes its buffers happens here.  Refused, each with a ValueError that says what to use instead:
+    ``gates="alpha"``, ``dense=True``, and a network with dense coupling z flows."""
     from . import layers as L
     if gates not in FROZEN_GATES:
         raise ValueError("bnn_amd: gates must be 'alpha' (the gates as trained) or 'mpm' (the median probability model), got %r"
@@ -1414,11 +1658,23 @@ def freeze(net, gates: str = "alpha", *, threshold: float = 0.5, dense: bool = F
     if not isinstance(net, L._NetworkBase):
         raise TypeError("bnn_amd: freeze takes an lrt.BayesianNetwork or mnf.BayesianNetwork, got %s" % type(net).__name__)
     layers = net._layers()
+    if compact:
+        if gates != "mpm":
+            raise ValueError("bnn_amd: compact=True needs gates=\"mpm\": alpha gates are never exactly zero, so no unit can be "
+                             "dropped -- use freeze(net, \"mpm\", compact=True), or freeze(net) for the gates as trained")
+        if dense:
+            raise ValueError("bnn_amd: compact=True does not take dense=True (the member kernel of the dense z flows keeps z in "
+                             "LDS at full width) -- use freeze(net, \"mpm\", dense=True) for the full median probability model")
+        if any(l._mnf and l._check_flows() == "dense" for l in layers):
+            raise ValueError("bnn_amd: compact=True is not built for dense coupling z flows (the member kernel keeps z in LDS at "
+                             "full width) -- use freeze(net, \"mpm\", dense=True) for the full median probability model")
     _check_freezable_layers(layers, dense=bool(dense))
     if not layers[0].weight_mu.is_cuda:
         raise RuntimeError("bnn_amd: freeze needs the network on a HIP device (it is on %s); there is no CPU path"
                            % layers[0].weight_mu.device)
     family = "mnf" if layers[0]._mnf else "lrt"
+    if compact:
+        return _freeze_compact(net, layers, family, float(threshold))
     flows = layers[0]._check_flows() if family == "mnf" else None          # "planar" | "dense" (checked above)
     fz = FrozenNetwork(net.dims, family, gates, threshold, device=layers[0].weight_mu.device, flows=flows, head=net.head)
     fz.eval()

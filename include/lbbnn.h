@@ -641,6 +641,50 @@ int lbbnn_frozen_members_dense(const lbbnn_frozen_desc_t* layers, const lbbnn_de
                                const uint64_t* rng, uint64_t member_advance, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Compact median-probability model: the frozen model of the units some output depends on.  A hidden unit or input feature
+ * whose every consumer weight is pruned (or whose consumers are themselves unneeded) leaves with its whole row and column;
+ * what remains computes the same function with smaller dense GEMMs (lbbnn_lrt_gemm_members / lbbnn_lrt_gemm at the compact
+ * shapes).  A compact layer is described by the full layer's parameters plus a map: the sorted row and column indices that
+ * stay.  The caller builds the maps (evaluate.live_structure); the kernels read them as given.
+ *
+ * lbbnn_frozen_operands_compact: lbbnn_frozen_operands for compact layers, ONE launch for all n <= LBBNN_MAX_LAYERS layers.
+ *   layers[i].O / I / ld are the COMPACT sizes O' / I' / ld'; the parameter pointers address the full (O_full, I_full)
+ *   arrays; mode must be LBBNN_FROZEN_MPM (LBBNN_E_FLAGS otherwise: alpha gates are never exactly zero).  Compact element
+ *   (o', j') is the element of lbbnn_frozen_operands at (rows[o'], cols[j']):
+ *     e0, e_w, var_w [O'][ld'] with a zero tail [I', ld');  bias_var[o'] = softplus(bias_rho[rows[o']])^2;
+ *     kept_rows[o'] = the number of j' < I' with lambdal[rows[o']][cols[j']] > cut.
+ *   Checks, before any launch: those of lbbnn_frozen_operands; maps / rows / cols NULL: LBBNN_E_NULL; O' > O_full or
+ *   I' > I_full: LBBNN_E_SHAPE; LBBNN_F_SPLIT16 needs I' % 8 == 0 (LBBNN_E_ALIGN; fp32 operands take any I').
+ *
+ * lbbnn_frozen_members_compact: lbbnn_frozen_members for a compact model.  The descriptors carry the FULL-width q0_mean,
+ *   q0_log_var, planar z_flow and z_fwd / z_mstride (>= I_full); the flow launch is the one of lbbnn_frozen_members at width
+ *   maps[i].I_full, then ONE launch writes e_w_members + m * O' * ld' = operand(e0'[o'][j'] * z_m[cols[j']]) for every
+ *   member and MNF layer: the gather of z is fused into that launch, no compact z is stored.  The checks of
+ *   lbbnn_frozen_members (I' % 4, and I_full % 4 for the flow) plus the map checks above.
+ *
+ * Draw contract of a compact model:
+ *   - z: drawn at the full width from the same Philox stream, offsets and counters as lbbnn_frozen_members, so member m's z
+ *     is bit for bit the full model's;
+ *   - eps_out of compact layer i: stream LBBNN_STREAM_EPS_OUT * 64 + layer_id, counter (row_offset + b, j' / 4) with j' the
+ *     COMPACT column (the GEMMs index the noise by the column they compute).  A stochastic member of a compact model
+ *     therefore equals the full median-probability member in distribution, not in numbers;
+ *   - the posterior-mean forward draws no eps_out: it equals the full model's to fp32 rounding (the order of the sums).
+ *
+ * lbbnn_gather_columns: out[b][j] = x[b][idx[j]] for b < B, j < n_idx; columns [n_idx, ldo) of out are written as zeros.
+ *   B == 0 is a successful no-op.  NULL x / idx / out: LBBNN_E_NULL; n_idx < 1, ldo < n_idx, ldx < 1, B < 0:
+ *   LBBNN_E_SHAPE; out off a 16-B boundary, ldo % 4 != 0: LBBNN_E_ALIGN.  idx holds column indices of x in [0, ldx). */
+typedef struct lbbnn_compact_map {
+    const int32_t* rows;                             /* (O') indices into [0, O_full) */
+    const int32_t* cols;                             /* (I') indices into [0, I_full) */
+    int O_full, I_full;
+} lbbnn_compact_map_t;
+
+int lbbnn_frozen_operands_compact(const lbbnn_frozen_desc_t* layers, const lbbnn_compact_map_t* maps, int n, void* stream);
+int lbbnn_frozen_members_compact(const lbbnn_frozen_desc_t* layers, const lbbnn_compact_map_t* maps, int n, int members,
+                                 const uint64_t* rng, uint64_t member_advance, void* stream);
+int lbbnn_gather_columns(const float* x, int ldx, const int32_t* idx, int n_idx, float* out, int ldo, int B, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K7  lbbnn_vd_operands -- Gaussian variational-dropout layer (variational_dropout.py:55-68).
  *   phi = x.theta ; delta = (x^2).(theta^2) * alpha ; out = phi + sqrt(delta)*zeta        :64-67
  * theta is (I,O) row-major (NN layout).  This pass writes the GEMM operands theta^T and (theta^2)^T as
