@@ -24,6 +24,7 @@ SAMPLES = 1              # LBBNN-GP-MF.py:38
 # CPU, where they cost nothing).  The parameters checked are softplus / sigmoid outputs and the positive prior constants: a
 # check can only fire on NaN parameters.  True restores torch's default behaviour (a ValueError at the draw).
 VALIDATE_ARGS = False
+MAX_DEPTH = _lib.MAX_DEPTH   # layers per network: layer i takes Philox stream id 32 + i (LRT / MNF: 0..15, VD: 48..63)
 NUM_BATCHES = 600        # len(train_loader) with BATCH_SIZE = 100 on MNIST (LBBNN-GP-MF.py:34,67)
 
 
@@ -146,8 +147,8 @@ class _BaseDrawFn(torch.autograd.Function):
     reparameterisation terms) -> dX = G W.  No torch distribution and no sigmoid autograd on the path."""
 
     @staticmethod
-    def forward(ctx, layer, x, rng, act, *params):
-        out, lp, lq, keep = layer._forward_hip_draws(x, rng, act)
+    def forward(ctx, layer, x, rng, act, slot, *params):
+        out, lp, lq, keep = layer._forward_hip_draws(x, rng, act, slot)
         ctx.layer, ctx.act, ctx.rng, ctx.keep = layer, act, rng, keep
         from . import graphs
         graphs.mark_autograd_node(ctx, layer)          # capture guard: graphs.assert_no_live_graph
@@ -213,7 +214,7 @@ class _BaseDrawFn(torch.autograd.Function):
         grads = {"weight_mu": d_mu, "weight_rho": d_rho, "weight_a": scal[0:1], "weight_b": scal[1:2], "lambdal": d_lam,
                  "pa": scal[3:4], "pb": scal[4:5], "bias_mu": vecs["d_bias_mu"], "bias_rho": vecs["d_bias_rho"],
                  "bias_a": vecs["d_bias_a"], "bias_b": vecs["d_bias_b"]}
-        return (None, gx, None, None, *[grads[n] for n in layer._names])
+        return (None, gx, None, None, None, *[grads[n] for n in layer._names])
 
 
 class BayesianLinear(nn.Module):
@@ -304,9 +305,11 @@ class BayesianLinear(nn.Module):
         saved["cg"] = cg
         return out, lp, lq, saved
 
-    def _forward_hip_draws(self, x, rng, act):
+    def _forward_hip_draws(self, x, rng, act, slot=None):
         """lbbnn_gate_sample_draw + the mean-only GEMM (act: None, "relu" or "log_softmax" in its epilogue).  Returns out,
-        lp, lq and the kernel-written buffers; every draw comes from the Philox state ``rng`` (2 int64 words on the device)."""
+        lp, lq and the kernel-written buffers; every draw comes from the Philox state ``rng`` (2 int64 words on the device).
+        ``slot``: the two 0-dim fp32 device tensors the kernel writes log_prior and log_q into (a network deeper than three
+        layers passes slots of its [2][n] buffer); default: fresh ones."""
         from . import distributions
         ws = self._workspace()
         dev = x.device
@@ -318,7 +321,7 @@ class BayesianLinear(nn.Module):
         keep = {"gammas": torch.empty((O, I), **f), "alpha": torch.empty((O, I), **f), "tau_w": torch.empty(1, **f),
                 "tau_b": torch.empty(O, **f), "T": float(distributions.TEMPER_PRIOR), "exact": self._exact_bits()}
         bias = torch.empty(O, **f)
-        lp, lq = torch.empty((), **f), torch.empty((), **f)
+        lp, lq = slot if slot is not None else (torch.empty((), **f), torch.empty((), **f))
         a = _lib.GateDrawArgs()
         g = a.g
         g.mu, g.rho, g.bias_mu, g.bias_rho = P(self.weight_mu), P(self.weight_rho), P(self.bias_mu), P(self.bias_rho)
@@ -357,7 +360,7 @@ class BayesianLinear(nn.Module):
             st.advance(1)
         x = input.float()
         params = [getattr(self, n) for n in self._names]
-        out, lp, lq = _BaseDrawFn.apply(self, x, rng, activation, *params)
+        out, lp, lq = _BaseDrawFn.apply(self, x, rng, activation, None, *params)
         self._publish_draws(lp, lq)
         return out, lp, lq
 
@@ -449,33 +452,100 @@ class BayesianLinear(nn.Module):
         return out
 
 
+class _FoldTotalsFn(torch.autograd.Function):
+    """log_prior and log_q of a network of more than three layers: the layers' kernels wrote their values into the slots of one
+    [2][n] buffer (the ``slot`` argument of ``_BaseDrawFn``), ONE lbbnn_fold_rows launch forms both totals as the fp32 left
+    fold in layer order.  The
+    backward hands every layer's node the upstream g_lp / g_lq tensor itself (lbbnn_gate_backward_draw reads it through a
+    pointer): no expand and no add kernel at any depth."""
+
+    @staticmethod
+    def forward(ctx, buf, *vals):
+        ctx.n = len(vals) // 2
+        ctx.set_materialize_grads(False)
+        tot = ops.fold_rows(buf, 2, ctx.n)
+        return tot[0], tot[1]
+
+    @staticmethod
+    def backward(ctx, g_lp, g_lq):
+        return (None,) + (g_lp,) * ctx.n + (g_lq,) * ctx.n
+
+
+_NOT_GIVEN = object()     # forward's sample / medimean may arrive positionally after the gates: tells "not passed" from False
+
+
 class BayesianNetwork(nn.Module):
-    """LBBNN-GP-MF.py:259-319 (reference dims 784-400-600-10; ``dims=`` added)."""
+    """LBBNN-GP-MF.py:259-319 (reference dims 784-400-600-10; ``dims=`` added): an MLP of 1 to MAX_DEPTH layers l1 .. lN
+    (``2 <= len(dims) <= MAX_DEPTH + 1``), ReLU between them, log_softmax after the last.  Layer i draws from the Philox streams
+    ``kind * 64 + 32 + i``."""
+    _fold_totals = True      # False: log_prior / log_q of sample_elbo(draws="hip") by torch adds at every depth (as up to 3 layers)
 
     def __init__(self, dims=(28 * 28, 400, 600, 10)):
         super().__init__()
-        self.dims = tuple(dims)
-        self.l1 = BayesianLinear(dims[0], dims[1], 1)
-        self.l2 = BayesianLinear(dims[1], dims[2], 1)
-        self.l3 = BayesianLinear(dims[2], dims[3], 1)
-        for i, l in enumerate((self.l1, self.l2, self.l3)):
+        dims = tuple(dims)
+        if not 2 <= len(dims) <= MAX_DEPTH + 1:
+            raise ValueError("bnn_amd: %s takes 1 to %d layers (len(dims) 2 to %d), got dims=%s"
+                             % (type(self).__name__, MAX_DEPTH, MAX_DEPTH + 1, dims))
+        self.dims = dims
+        self._lnames = tuple("l%d" % (i + 1) for i in range(len(dims) - 1))
+        for i, name in enumerate(self._lnames):
+            setattr(self, name, BayesianLinear(dims[i], dims[i + 1], 1))     # the reference passes layer id 1 to all of them
+        for i, l in enumerate(self._layers()):
             l._layer_id = 32 + i              # per-network Philox stream ids (not the process-wide counter)
 
-    def forward(self, x, g1, g2, g3, sample=False, medimean=False):
+    def _layers(self):
+        m = self._modules
+        return [m[k] for k in self._lnames]
+
+    def _gates(self, gates, named):
+        """The n gate tensors of one ``forward`` call, and what follows them positionally (``sample``, ``medimean``)."""
+        n = len(self._lnames)
+        if len(gates) > n + 2:
+            raise TypeError("bnn_amd: forward of a %d-layer network takes %d gates and at most sample, medimean after them; got "
+                            "%d positional arguments after x" % (n, n, len(gates)))
+        gs = dict(("g%d" % (i + 1), g) for i, g in enumerate(gates[:n]))
+        for k, v in named.items():
+            if not (k[:1] == "g" and k[1:].isdigit() and str(int(k[1:])) == k[1:] and 1 <= int(k[1:]) <= n):
+                raise TypeError("bnn_amd: forward got an unexpected keyword argument %r (a %d-layer network takes g1 .. g%d)"
+                                % (k, n, n))
+            if k in gs:
+                raise TypeError("bnn_amd: forward got the gate %s twice" % k)
+            gs[k] = v
+        missing = [k for k in ("g%d" % (i + 1) for i in range(n)) if k not in gs]
+        if missing:
+            raise TypeError("bnn_amd: forward of a %d-layer network needs one gate (or None) per layer; missing %s"
+                            % (n, ", ".join(missing)))
+        return [gs["g%d" % (i + 1)] for i in range(n)], gates[n:]
+
+    def forward(self, x, *gates, sample=_NOT_GIVEN, medimean=_NOT_GIVEN, **named):
+        """``net(x, g1, ..., gN, sample=False, medimean=False)``: one gate tensor (or None) per layer, positionally or as
+        ``g1=..., gN=...`` (or mixed); positional arguments after the N-th gate are ``sample`` and ``medimean``.  A wrong number
+        of gates, a gate given twice, or ``sample`` / ``medimean`` given both positionally and by name: TypeError."""
+        gs, rest = self._gates(gates, named)
+        for k, name in enumerate(("sample", "medimean")[:len(rest)]):
+            if (sample, medimean)[k] is not _NOT_GIVEN:
+                raise TypeError("bnn_amd: forward got multiple values for argument %r" % name)
+        sample = rest[0] if len(rest) > 0 else (False if sample is _NOT_GIVEN else sample)
+        medimean = rest[1] if len(rest) > 1 else (False if medimean is _NOT_GIVEN else medimean)
+        layers = self._layers()
         x = x.view(-1, self.dims[0])
-        x = F.relu(self.l1.forward(x, g1, sample, medimean))
-        x = F.relu(self.l2.forward(x, g2, sample, medimean))
-        return F.log_softmax(self.l3.forward(x, g3, sample, medimean), dim=1)
+        for l, g in zip(layers[:-1], gs[:-1]):
+            x = F.relu(l.forward(x, g, sample, medimean))
+        return F.log_softmax(layers[-1].forward(x, gs[-1], sample, medimean), dim=1)
 
     def log_prior(self):
-        return self.l1.log_prior + self.l2.log_prior + self.l3.log_prior
+        layers = self._layers()
+        t = layers[0].log_prior
+        for l in layers[1:]:
+            t = t + l.log_prior
+        return t
 
     @torch.no_grad()
     def sample_predict(self, x, *, gates="sample", rng=None):
         """One stochastic evaluation forward (test_ensemble's ``net.forward(data, sample=True, g1=gamma.rsample(), ...)``,
         LBBNN-GP-MF.py:388-389, without log-probabilities): (B, classes) log-probabilities, no autograd.  Every draw comes from
-        the Philox state inside the HIP kernels -- lbbnn_gate_members (gates, weight and bias noise of all three layers) and one
-        mean-only GEMM per layer with ReLU, ReLU and log_softmax in its epilogue -- so this is member 0 of a one-member ensemble
+        the Philox state inside the HIP kernels -- lbbnn_gate_members (gates, weight and bias noise of all layers) and one
+        mean-only GEMM per layer with ReLU or the head's log_softmax in its epilogue -- so this is member 0 of a one-member ensemble
         (``evaluate.ensemble_forward``).  ``gates``: "sample" (the training draw: the hard gate u < alpha when ``gamma.exact``
         is set, else the relaxed gate at ``distributions.TEMPER_PRIOR``; both read at call time) or "mpm" (the median
         probability model, gates alpha > 0.5 and sampled weights: outofsample(medimod=True), :469-473).  ``rng``: a
@@ -495,7 +565,8 @@ class BayesianNetwork(nn.Module):
 
     def _predict_members(self, input, rng, S, gates="sample", out=None, rows=False, keep_gates=False):
         """S evaluation forwards of one batch; member m draws from {rng[0], rng[1] + m}, bitwise what ``sample_forward`` of the
-        three layers at that offset computes.  1 + 3 launches: lbbnn_gate_members, then lbbnn_gemm_members_mean per layer.
+        layers at that offset computes.  ceil(n / 4) + n launches: lbbnn_gate_members per group of _lib.MAX_LAYERS consecutive
+        layers (every group reads the same ``rng``, member count and advance), then lbbnn_gemm_members_mean per layer.
         ``out``: optional (S, >= B*classes) buffer for the head.  Returns ((S, B, classes) log-probabilities, per-layer (S, O)
         gate row sums or None, per-layer (S, O, I) gates or None).  Does not advance the live state."""
         if not input.is_cuda:
@@ -503,7 +574,8 @@ class BayesianNetwork(nn.Module):
                                % input.device)
         if gates not in ("sample", "mpm"):
             raise ValueError("bnn_amd: gates must be 'sample' or 'mpm', got %r" % (gates,))
-        layers = (self.l1, self.l2, self.l3)
+        layers = self._layers()
+        n = len(layers)
         for l in layers:
             if l.noise:
                 raise ValueError("bnn_amd: evaluation draws its own noise in-kernel; injected draws (layer.noise) belong to the "
@@ -523,17 +595,18 @@ class BayesianNetwork(nn.Module):
         for k, l in enumerate(layers):
             in_ok = (x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0) if k == 0 else layers[k - 1].out_features % 4 == 0
             splits.append(bool(ops.split_precision() and ops.split_eligible(l.in_features, l.out_features) and in_ok))
-        descs = (_lib.GateMemberDesc * 3)()
+        descs = (_lib.GateMemberDesc * n)()
         bufs = [l._fill_member_desc(descs[k], S, splits[k], rows, keep_gates) for k, l in enumerate(layers)]
         stream = ops._stream()
-        _lib.check(_lib.lib().lbbnn_gate_members(descs, 3, S, ops.GATES_MPM if gates == "mpm" else ops.GATES_SAMPLE,
-                                                 float(distributions.TEMPER_PRIOR), rng.data_ptr(), 1, stream),
-                   "lbbnn_gate_members")
+        mode, T = (ops.GATES_MPM if gates == "mpm" else ops.GATES_SAMPLE), float(distributions.TEMPER_PRIOR)
+        for k, cnt in _lib.layer_groups(n):                    # every group reads the same offset; the caller advances once
+            _lib.check(_lib.lib().lbbnn_gate_members(_lib.group_slice(descs, k, cnt), cnt, S, mode, T, rng.data_ptr(), 1, stream),
+                       "lbbnn_gate_members")
         h, h_ms, ldx = x, 0, x.stride(0)
         for k, l in enumerate(layers):
             O, I, ld = l.out_features, l.in_features, ops.operand_ld(l.in_features)
             o_ms = -(-(B * O) // 4) * 4                       # member stride padded to 16 B
-            head = k == 2
+            head = k == n - 1
             if head and out is not None:
                 o = out
                 if o.dim() != 2 or o.shape[0] != S or o.shape[1] < B * O or o.stride(0) % 4 or not o.is_contiguous():
@@ -557,13 +630,14 @@ class BayesianNetwork(nn.Module):
     def _predict_members_loop(self, input, rng, S, gates, out, rows, keep_gates):
         """``_predict_members`` for a network with a layer wider than lbbnn_gate_members takes (operand_ld(in_features) >
         ops.GATE_MEMBERS_MAX_LD): member m is the chain of the layers' ``sample_forward`` at {rng[0], rng[1] + m} -- by
-        definition what the batched form computes -- and its gates / gate row sums are the ones that chain drew.  3 layer
+        definition what the batched form computes -- and its gates / gate row sums are the ones that chain drew.  n layer
         calls per member; the layers keep the last member's draws, as after ``sample_forward``.  The median probability model
         has no training-kernel chain: gates="mpm" raises."""
         if gates != "sample":
             raise ValueError("bnn_amd: gates='mpm' needs every layer within lbbnn_gate_members' width (operand_ld(in_features) "
                              "<= %d)" % ops.GATE_MEMBERS_MAX_LD)
-        layers = (self.l1, self.l2, self.l3)
+        layers = self._layers()
+        n = len(layers)
         C = self.dims[-1]
         head = "log_softmax" if C <= 16 else None
         x = input.view(-1, self.dims[0]).float()
@@ -579,7 +653,7 @@ class BayesianNetwork(nn.Module):
             r[1] += m
             h = x
             for k, l in enumerate(layers):
-                h, _, _ = l.sample_forward(h, activation="relu" if k < 2 else head, rng=r)
+                h, _, _ = l.sample_forward(h, activation="relu" if k < n - 1 else head, rng=r)
                 if rows:
                     g_rows[k][m] = l.gammas.sum(1)
                 if keep_gates:
@@ -594,8 +668,11 @@ class BayesianNetwork(nn.Module):
         return res, g_rows, g_all
 
     def log_variational_posterior(self):
-        return (self.l1.log_variational_posterior + self.l2.log_variational_posterior
-                + self.l3.log_variational_posterior)
+        layers = self._layers()
+        t = layers[0].log_variational_posterior
+        for l in layers[1:]:
+            t = t + l.log_variational_posterior
+        return t
 
     def sample_elbo(self, input, target, samples=SAMPLES, *, num_batches=None, draws="torch"):
         """:285-319, same positional arguments.  NUM_BATCHES / SAMPLES are module globals there (:34-67) and here
@@ -614,11 +691,11 @@ class BayesianNetwork(nn.Module):
         lps, lqs, nlls = [], [], []
         for _ in range(samples):
             gs = []
-            for l in (self.l1, self.l2, self.l3):
+            for l in self._layers():
                 l.alpha = 1 / (1 + torch.exp(-l.lambdal))             # :292-297
                 l.gamma.alpha = l.alpha
                 gs.append(l.gamma.rsample().to(dev))                  # :300-302
-            out = self.forward(input, gs[0], gs[1], gs[2], sample=True, medimean=False)
+            out = self.forward(input, *gs, sample=True, medimean=False)
             lps.append(self.log_prior())
             lqs.append(self.log_variational_posterior())
             nlls.append(F.nll_loss(out, target, reduction="sum"))
@@ -630,25 +707,39 @@ class BayesianNetwork(nn.Module):
 
     def _sample_elbo_hip(self, input, target, samples, num_batches):
         """sample_elbo(draws="hip"): per sample one Philox snapshot (the offset advances once), one _BaseDrawFn node per
-        layer with ReLU / log_softmax in the GEMM epilogues, the NLL as one launch (losses.elbo_loss)."""
+        layer with ReLU / log_softmax in the GEMM epilogues, the NLL as one launch (losses.elbo_loss).  log_prior and log_q:
+        up to three layers the chain of torch adds; deeper, one lbbnn_fold_rows launch over the slots the layers' kernels
+        wrote (_FoldTotalsFn) -- the same fp32 left fold."""
         from .losses import elbo_loss
         if not input.is_cuda:
             raise RuntimeError("bnn_amd: sample_elbo(draws='hip') needs a HIP device tensor (input is on %s); there is no "
                                "CPU path" % input.device)
         x = input.view(-1, self.dims[0]).float()
         st = ops.RngState.get(input.device)
-        layers = (self.l1, self.l2, self.l3)
+        layers = self._layers()
+        n = len(layers)
         head = "log_softmax" if self.dims[-1] <= 16 else None
+        fold = bool(self._fold_totals and n > 3)
         lps, lqs, nlls = [], [], []
         for _ in range(samples):
             rng = st.t[:2].clone()
             st.advance(1)
             h, lp, lq = x, None, None
+            buf = torch.empty((2, n), dtype=torch.float32, device=x.device) if fold else None
+            vals = ([], [])
             for k, l in enumerate(layers):
-                h, lp_l, lq_l = _BaseDrawFn.apply(l, h, rng, "relu" if k < 2 else head, *[getattr(l, n) for n in l._names])
+                slot = (buf[0, k], buf[1, k]) if fold else None       # where this layer's kernel writes (log_prior, log_q)
+                h, lp_l, lq_l = _BaseDrawFn.apply(l, h, rng, "relu" if k < n - 1 else head, slot,
+                                                  *[getattr(l, n_) for n_ in l._names])
                 l._publish_draws(lp_l, lq_l)
-                lp = lp_l if lp is None else lp + lp_l
-                lq = lq_l if lq is None else lq + lq_l
+                if fold:
+                    vals[0].append(lp_l)
+                    vals[1].append(lq_l)
+                else:
+                    lp = lp_l if lp is None else lp + lp_l
+                    lq = lq_l if lq is None else lq + lq_l
+            if fold:
+                lp, lq = _FoldTotalsFn.apply(buf, *vals[0], *vals[1])
             if head is None:
                 h = F.log_softmax(h, dim=1)
             lps.append(lp)

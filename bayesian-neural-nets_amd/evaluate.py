@@ -249,8 +249,9 @@ def _is_base(net) -> bool:
 @torch.no_grad()
 def base_ensemble(net, data: torch.Tensor, samples: int = 10, *, gates: str = "sample", max_members: Optional[int] = None,
                   keep_gates: bool = False) -> Dict[str, object]:
-    """``samples`` evaluation forwards of a baseline LBBNN network in 1 + 3 launches per chunk of at most ``max_members``
-    members (default: all in one).  Member m draws at Philox offset (live offset + m) and equals, bit for bit, what
+    """``samples`` evaluation forwards of a baseline LBBNN network of n layers in ceil(n / 4) + n launches (1 + 3 for the
+    reference's three layers) per chunk of at most ``max_members`` members (default: all in one).  Member m draws at
+    Philox offset (live offset + m) and equals, bit for bit, what
     ``net.sample_predict`` / the layers' ``sample_forward`` compute at that offset; chunked and unchunked results are the same
     bits.  The live offset advances by ``samples``.  Returns ``outputs`` (samples, B, classes) log-probabilities,
     ``gate_rows`` (per layer (samples, O): the sum over each row of the gates the member used) and, with ``keep_gates``,
@@ -436,13 +437,13 @@ def _vd_ensemble_eval(net, data, target, samples):
 def _base_ensemble_eval(net, data, target, samples):
     r = base_ensemble(net, data, samples)
     outputs = r["outputs"]
-    layers = (net.l1, net.l2, net.l3)
+    layers = net._layers()
     n_w = sum(l.out_features * l.in_features for l in layers)
     density = torch.stack([rw.double().sum(1) for rw in r["gate_rows"]]).sum(0) / n_w
     for l in layers:
         l.alpha = 1 / (1 + torch.exp(-l.lambdal.detach()))                  # :369-374
         l.gamma.alpha = l.alpha
-    pred_mean = net(data, None, None, None, sample=False).argmax(1)          # :413 (mode 2: weight = alpha * mu)
+    pred_mean = net(data, *[None] * len(layers), sample=False).argmax(1)     # :413 (mode 2: weight = alpha * mu)
     pred_ens = outputs.mean(0).argmax(1)
     res = {"outputs": outputs, "pred_ensemble": pred_ens, "pred_posterior_mean": pred_mean, "density": density.float()}
     if target is not None:
@@ -849,10 +850,11 @@ def _eval_forwards(net, data, samples: int, posterior_mean: bool, gates: str):
         outputs = base_ensemble(net, data, samples, gates=gates)["outputs"]
         if not posterior_mean:
             return outputs, None
-        for l in (net.l1, net.l2, net.l3):
+        layers = net._layers()
+        for l in layers:
             l.alpha = 1 / (1 + torch.exp(-l.lambdal.detach()))                  # LBBNN-GP-MF.py:369-374
             l.gamma.alpha = l.alpha
-        return outputs, net(data, None, None, None, sample=False)              # :413 (mode 2: weight = alpha * mu)
+        return outputs, net(data, *[None] * len(layers), sample=False)         # :413 (mode 2: weight = alpha * mu)
     if _is_vd(net):
         return ensemble_forward(net, data, samples, gates=gates), None         # VD has no posterior-mean forward
     binary = _binary_eval(net)

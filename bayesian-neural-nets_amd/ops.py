@@ -946,6 +946,18 @@ def kl_total(kls: torch.Tensor, n: int) -> torch.Tensor:
     return kls[n]
 
 
+def fold_rows(v: torch.Tensor, rows: int, n: int) -> torch.Tensor:
+    """lbbnn_fold_rows: out[r] = ((0 + v[r][0]) + v[r][1]) + ... + v[r][n - 1] in fp32 for r < rows, one launch; ``v`` is a
+    (>= rows, >= n) fp32 device tensor with dense rows.  Returns a new (rows,) tensor."""
+    if not v.is_cuda:
+        raise RuntimeError("bnn_amd: fold_rows needs a HIP device tensor (v is on %s); there is no CPU path" % v.device)
+    if v.dtype != torch.float32 or v.dim() != 2 or v.shape[0] < rows or v.shape[1] < n or (v.shape[1] > 1 and v.stride(1) != 1):
+        raise RuntimeError("bnn_amd: fold_rows needs a 2-D fp32 buffer of at least (rows, n) values with dense rows")
+    out = torch.empty(rows, dtype=torch.float32, device=v.device)
+    _lib.check(_lib.lib().lbbnn_fold_rows(v.data_ptr(), rows, n, v.stride(0), out.data_ptr(), _stream()), "lbbnn_fold_rows")
+    return out
+
+
 def kl_finalize(kl_rows, bias_mu, bias_rho, *, priors: Priors, act_mu=None, act_var=None, eps_act=None,
                 r0_b1=None, r0_b2=None, scal=None, rng: Optional[torch.Tensor] = None, layer_id: int = 0,
                 kl_out=None, kl_layer=None, accumulate: bool = False):

@@ -360,6 +360,17 @@ int lbbnn_forward_finish(uint64_t* rng, uint64_t advance, const float* const* kl
 #define LBBNN_MAX_DEPTH 16
 int lbbnn_kl_total(const float* kl_layers, int n, float* total, void* stream);
 
+/* Left folds of short rows: out[r] = ((0 + v[r * ld + 0]) + v[r * ld + 1]) + ... + v[r * ld + n - 1] in fp32 for r < rows.
+ * The log-probability totals of a baseline network of more than three layers: its layers' lbbnn_gate_sample_draw calls write
+ * log_prior into v[0][i] and log_q into v[1][i] of one [2][n] buffer, and one call (rows = 2) forms both network totals in
+ * layer order -- what the chain of fp32 adds of a three-layer network forms.  One launch, one thread per row, plain stores,
+ * no atomics, no LDS, no host read: deterministic and capturable.  out must not overlap v.
+ * Checks, before the launch: v / out NULL: LBBNN_E_NULL; rows outside [1, LBBNN_FOLD_MAX_ROWS], n outside
+ * [1, LBBNN_FOLD_MAX_N], ld < n: LBBNN_E_SHAPE; a pointer off 4 bytes: LBBNN_E_ALIGN. */
+#define LBBNN_FOLD_MAX_ROWS 64       /* one wave: the caller folds 2 rows */
+#define LBBNN_FOLD_MAX_N 64          /* a serial fold per thread: meant for one value per layer (n <= LBBNN_MAX_DEPTH) */
+int lbbnn_fold_rows(const float* v, int rows, int n, int ld, float* out, void* stream);
+
 
 /* ---------------------------------------------------------------------------------------------
  * K6  lbbnn_gate_sample -- baseline LBBNN layer (explicit latent-binary gate x Gaussian weight sample).
