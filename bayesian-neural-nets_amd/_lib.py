@@ -143,6 +143,16 @@ class AdamGroupList(ctypes.Structure):
                 ("numel", c_i64 * ADAM_GROUPS_MAX_TENSORS), ("group", c_i * ADAM_GROUPS_MAX_TENSORS), ("n", c_i)]
 
 
+SGD_F_NESTEROV = 0x1
+SGD_F_INACTIVE = 0x2
+
+
+class SgdHyper(ctypes.Structure):
+    """lbbnn_sgd_hyper_t: one row of the device table (5 x 4 bytes)"""
+    _fields_ = [("lr", ctypes.c_float), ("momentum", ctypes.c_float), ("dampening", ctypes.c_float),
+                ("weight_decay", ctypes.c_float), ("flags", c_u32)]
+
+
 class CopyList(ctypes.Structure):
     """lbbnn_copy_list_t"""
     _fields_ = [("dst", c_p * ADAM_MAX_TENSORS), ("src", c_p * ADAM_MAX_TENSORS), ("numel", c_i64 * ADAM_MAX_TENSORS), ("n", c_i)]
@@ -321,6 +331,7 @@ SIGNATURES = {
     "lbbnn_adam_step": (c_i, [ctypes.POINTER(AdamList), ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                               ctypes.c_float, c_p, c_i, c_p]),
     "lbbnn_adam_step_groups": (c_i, [ctypes.POINTER(AdamGroupList), c_p, c_p, c_i, c_p, c_p, c_i, c_p]),
+    "lbbnn_sgd_step_groups": (c_i, [ctypes.POINTER(AdamGroupList), c_p, c_p, c_i, c_p, c_p, c_i, c_p]),
     "lbbnn_grad_sumsq_workspace": (c_i64, [c_i64]),
     "lbbnn_grad_sumsq": (c_i, [ctypes.POINTER(AdamGroupList), c_p, c_i64, c_i64, ctypes.c_float, c_p, c_p, c_p]),
     "lbbnn_matmul_splitk": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),

@@ -221,19 +221,21 @@ class BayesianLinear(nn.Module):
     _names = ("weight_mu", "weight_rho", "weight_a", "weight_b", "lambdal", "pa", "pb",
               "bias_mu", "bias_rho", "bias_a", "bias_b")
 
-    def __init__(self, in_features, out_features, layer_id):
+    def __init__(self, in_features, out_features, layer_id, *, weight_mu_init=(-0.2, 0.2), lambdal_init=(0, 1)):
+        """``weight_mu_init`` / ``lambdal_init``: the uniform ranges of the two initial draws that differ between the scripts
+        (LBBNN-GP-MF.py:192,201: the defaults; LBBNN-GP-MFsim_study.py:182,190: (-0.01, 0.01) and (-0.5, 0.5))."""
         super().__init__()
         self.layer = layer_id
         self.in_features, self.out_features = in_features, out_features
         O, I = out_features, in_features
         # creation order == LBBNN-GP-MF.py:192-219 (seeded construction reproduces the reference's values)
-        self.weight_mu = nn.Parameter(torch.Tensor(O, I).uniform_(-0.2, 0.2))
+        self.weight_mu = nn.Parameter(torch.Tensor(O, I).uniform_(*weight_mu_init))
         self.weight_rho = nn.Parameter(torch.Tensor(O, I).uniform_(-5, -4))
         self.weight = Gaussian(self.weight_mu, self.weight_rho)
         self.weight_a = nn.Parameter(torch.Tensor(1).uniform_(1, 1.1))
         self.weight_b = nn.Parameter(torch.Tensor(1).uniform_(1, 1.1))
         self.weight_prior = GaussGamma(self.weight_a, self.weight_b)
-        self.lambdal = nn.Parameter(torch.Tensor(O, I).uniform_(0, 1))
+        self.lambdal = nn.Parameter(torch.Tensor(O, I).uniform_(*lambdal_init))
         self.gammas = torch.Tensor(O, I).uniform_(0.99, 1)
         self.alpha = torch.Tensor(O, I).uniform_(0.999, 0.9999)
         self.gamma = Bernoulli(self.alpha, exact=False)
@@ -477,19 +479,31 @@ _NOT_GIVEN = object()     # forward's sample / medimean may arrive positionally 
 class BayesianNetwork(nn.Module):
     """LBBNN-GP-MF.py:259-319 (reference dims 784-400-600-10; ``dims=`` added): an MLP of 1 to MAX_DEPTH layers l1 .. lN
     (``2 <= len(dims) <= MAX_DEPTH + 1``), ReLU between them, log_softmax after the last.  Layer i draws from the Philox streams
-    ``kind * 64 + 32 + i``."""
+    ``kind * 64 + 32 + i``.
+
+    ``head="sigmoid"`` (LBBNN-GP-MFsim_study.py:259-262, with ``dims=(20, 1), weight_mu_init=(-0.01, 0.01),
+    lambdal_init=(-0.5, 0.5)``): the last layer's logits go through one lbbnn_binary_head launch, ``forward`` returns the (B,
+    units <= 16) probabilities, ``sample_elbo`` takes the BCE loss and returns the script's five values, and the evaluation
+    functions treat one unit as two classes (``bnn_amd.evaluate``)."""
+    _logp2_now = False       # set by bnn_amd.evaluate around a forward: a sigmoid head (one unit) returns the 2-class log-probabilities
     _fold_totals = True      # False: log_prior / log_q of sample_elbo(draws="hip") by torch adds at every depth (as up to 3 layers)
 
-    def __init__(self, dims=(28 * 28, 400, 600, 10)):
+    def __init__(self, dims=(28 * 28, 400, 600, 10), head="log_softmax", *, weight_mu_init=(-0.2, 0.2), lambdal_init=(0, 1)):
         super().__init__()
         dims = tuple(dims)
+        if head not in ("log_softmax", "sigmoid"):
+            raise ValueError("bnn_amd: head must be 'log_softmax' or 'sigmoid', got %r" % (head,))
+        if head == "sigmoid" and dims[-1] > 16:
+            raise ValueError("bnn_amd: a sigmoid head takes at most 16 output units, got dims[-1] = %d" % dims[-1])
+        self.head = head
         if not 2 <= len(dims) <= MAX_DEPTH + 1:
             raise ValueError("bnn_amd: %s takes 1 to %d layers (len(dims) 2 to %d), got dims=%s"
                              % (type(self).__name__, MAX_DEPTH, MAX_DEPTH + 1, dims))
         self.dims = dims
         self._lnames = tuple("l%d" % (i + 1) for i in range(len(dims) - 1))
         for i, name in enumerate(self._lnames):
-            setattr(self, name, BayesianLinear(dims[i], dims[i + 1], 1))     # the reference passes layer id 1 to all of them
+            setattr(self, name, BayesianLinear(dims[i], dims[i + 1], 1,      # the reference passes layer id 1 to all of them
+                                               weight_mu_init=weight_mu_init, lambdal_init=lambdal_init))
         for i, l in enumerate(self._layers()):
             l._layer_id = 32 + i              # per-network Philox stream ids (not the process-wide counter)
 
@@ -531,7 +545,19 @@ class BayesianNetwork(nn.Module):
         x = x.view(-1, self.dims[0])
         for l, g in zip(layers[:-1], gs[:-1]):
             x = F.relu(l.forward(x, g, sample, medimean))
-        return F.log_softmax(layers[-1].forward(x, gs[-1], sample, medimean), dim=1)
+        x = layers[-1].forward(x, gs[-1], sample, medimean)
+        if self.head == "sigmoid":
+            # the logits as the last GEMM left them, then one lbbnn_binary_head launch (LBBNN-GP-MFsim_study.py:261)
+            from .layers import _SigmoidHeadFn
+            if self._logp2_now:
+                return ops.binary_head(x.detach(), log_probs=True, want_probs=False)
+            return _SigmoidHeadFn.apply(x) if x.requires_grad else ops.binary_head(x)
+        return F.log_softmax(x, dim=1)
+
+    def inclusion_probabilities(self):
+        """Per layer the posterior inclusion probabilities alpha = sigmoid(lambdal) as detached (O, I) tensors on the
+        parameters' device: the simulation study's result."""
+        return [torch.sigmoid(l.lambdal.detach()) for l in self._layers()]
 
     def log_prior(self):
         layers = self._layers()
@@ -541,7 +567,7 @@ class BayesianNetwork(nn.Module):
         return t
 
     @torch.no_grad()
-    def sample_predict(self, x, *, gates="sample", rng=None):
+    def sample_predict(self, x, *, gates="sample", rng=None, log_probs=False):
         """One stochastic evaluation forward (test_ensemble's ``net.forward(data, sample=True, g1=gamma.rsample(), ...)``,
         LBBNN-GP-MF.py:388-389, without log-probabilities): (B, classes) log-probabilities, no autograd.  Every draw comes from
         the Philox state inside the HIP kernels -- lbbnn_gate_members (gates, weight and bias noise of all layers) and one
@@ -550,7 +576,8 @@ class BayesianNetwork(nn.Module):
         is set, else the relaxed gate at ``distributions.TEMPER_PRIOR``; both read at call time) or "mpm" (the median
         probability model, gates alpha > 0.5 and sampled weights: outofsample(medimod=True), :469-473).  ``rng``: a
         {seed, offset} snapshot (2 int64 on the device) to draw from; default: the device's ``ops.RngState``, which this call
-        then advances by one.  The draws match the reference in distribution, not in numbers."""
+        then advances by one.  The draws match the reference in distribution, not in numbers.  A sigmoid head: (B, units)
+        probabilities, or with ``log_probs`` (one unit) the (B, 2) log-probabilities of the two classes."""
         if not x.is_cuda:
             raise RuntimeError("bnn_amd: sample_predict needs a HIP device tensor (input is on %s); there is no CPU path"
                                % x.device)
@@ -558,17 +585,22 @@ class BayesianNetwork(nn.Module):
         if rng is None:
             st = ops.RngState.get(x.device)
             rng = st.t
-        out = self._predict_members(x, rng, 1, gates)[0][0]
+        out = self._predict_members(x, rng, 1, gates, log_probs=log_probs)[0][0]
         if st is not None:
             st.advance(1)
         return out
 
-    def _predict_members(self, input, rng, S, gates="sample", out=None, rows=False, keep_gates=False):
+    def _predict_members(self, input, rng, S, gates="sample", out=None, rows=False, keep_gates=False, log_probs=False):
         """S evaluation forwards of one batch; member m draws from {rng[0], rng[1] + m}, bitwise what ``sample_forward`` of the
         layers at that offset computes.  ceil(n / 4) + n launches: lbbnn_gate_members per group of _lib.MAX_LAYERS consecutive
         layers (every group reads the same ``rng``, member count and advance), then lbbnn_gemm_members_mean per layer.
         ``out``: optional (S, >= B*classes) buffer for the head.  Returns ((S, B, classes) log-probabilities, per-layer (S, O)
-        gate row sums or None, per-layer (S, O, I) gates or None).  Does not advance the live state."""
+        gate row sums or None, per-layer (S, O, I) gates or None).  Does not advance the live state.  A sigmoid head: the last
+        GEMM leaves the logits, then ONE lbbnn_binary_head launch over the members' buffer: (S, B, units) probabilities (in
+        ``out`` when given), or with ``log_probs`` (one unit) the (S, B, 2) log-probabilities, a tensor of its own."""
+        from . import evaluate
+        evaluate._check_log_probs(self, log_probs)
+        sigmoid = self.head == "sigmoid"
         if not input.is_cuda:
             raise RuntimeError("bnn_amd: sample_predict needs a HIP device tensor (input is on %s); there is no CPU path"
                                % input.device)
@@ -581,7 +613,7 @@ class BayesianNetwork(nn.Module):
                 raise ValueError("bnn_amd: evaluation draws its own noise in-kernel; injected draws (layer.noise) belong to the "
                                  "torch-draw forward -- clear layer.noise first")
         if any(ops.operand_ld(l.in_features) > ops.GATE_MEMBERS_MAX_LD for l in layers):
-            return self._predict_members_loop(input, rng, S, gates, out, rows, keep_gates)
+            return self._predict_members_loop(input, rng, S, gates, out, rows, keep_gates, log_probs)
         from . import distributions
         x = input.view(-1, self.dims[0]).float()
         if x.stride(1) != 1 or x.stride(0) < self.dims[0]:
@@ -614,37 +646,49 @@ class BayesianNetwork(nn.Module):
                 o_ms = o.stride(0)
             else:
                 o = torch.empty((S, o_ms), **f)
-            flags = (ops.F_RELU if not head else (ops.F_LOG_SOFTMAX if O <= 16 else 0)) | (ops.F_SPLIT16 if splits[k] else 0)
+            flags = (ops.F_RELU if not head else (ops.F_LOG_SOFTMAX if O <= 16 and not sigmoid else 0)) | \
+                    (ops.F_SPLIT16 if splits[k] else 0)
             rc = _lib.lib().lbbnn_gemm_members_mean(h.data_ptr(), ldx, h_ms, bufs[k]["w"].data_ptr(), O * ld, ld,
                                                    bufs[k]["bias"].data_ptr(), O, o.data_ptr(), O, o_ms, B, I, O, flags, S,
                                                    stream)
             _lib.check(rc, "lbbnn_gemm_members_mean")
             h, h_ms, ldx = o, o_ms, O
-        res = h[:, :B * self.dims[-1]].view(S, B, self.dims[-1])
-        if self.dims[-1] > 16:
-            res = F.log_softmax(res, dim=-1)
+        if sigmoid:
+            res = evaluate._binary_members(h, S, B, self.dims[-1], log_probs)
+        else:
+            res = h[:, :B * self.dims[-1]].view(S, B, self.dims[-1])
+            if self.dims[-1] > 16:
+                res = F.log_softmax(res, dim=-1)
         for l in layers:
             l.log_prior, l.log_variational_posterior = 0, 0          # an evaluation forward keeps no log-probabilities (:253)
         return (res, [b["rows"] for b in bufs] if rows else None, [b["gates"] for b in bufs] if keep_gates else None)
 
-    def _predict_members_loop(self, input, rng, S, gates, out, rows, keep_gates):
+    def _predict_members_loop(self, input, rng, S, gates, out, rows, keep_gates, log_probs=False):
         """``_predict_members`` for a network with a layer wider than lbbnn_gate_members takes (operand_ld(in_features) >
         ops.GATE_MEMBERS_MAX_LD): member m is the chain of the layers' ``sample_forward`` at {rng[0], rng[1] + m} -- by
         definition what the batched form computes -- and its gates / gate row sums are the ones that chain drew.  n layer
         calls per member; the layers keep the last member's draws, as after ``sample_forward``.  The median probability model
-        has no training-kernel chain: gates="mpm" raises."""
+        has no training-kernel chain: gates="mpm" raises.  A sigmoid head: the chains leave their logits in one (S, member stride)
+        buffer (``out`` when given), then the one lbbnn_binary_head launch of the batched form."""
         if gates != "sample":
             raise ValueError("bnn_amd: gates='mpm' needs every layer within lbbnn_gate_members' width (operand_ld(in_features) "
                              "<= %d)" % ops.GATE_MEMBERS_MAX_LD)
         layers = self._layers()
         n = len(layers)
         C = self.dims[-1]
-        head = "log_softmax" if C <= 16 else None
+        sigmoid = self.head == "sigmoid"
+        head = "log_softmax" if C <= 16 and not sigmoid else None
         x = input.view(-1, self.dims[0]).float()
         if x.stride(1) != 1 or x.stride(0) < self.dims[0]:
             x = x.contiguous()
         B = x.shape[0]
-        res = torch.empty((S, B, C), dtype=torch.float32, device=x.device)
+        if sigmoid:
+            # (the chains write their logits into ``out`` itself and the head goes over it as one block: looked at first)
+            if out is not None and (out.dim() != 2 or out.shape[0] != S or out.shape[1] < B * C or not out.is_contiguous()):
+                raise RuntimeError("bnn_amd: out must be a contiguous (S, >= B*classes) buffer")
+            logits = out if out is not None else torch.empty((S, -(-(B * C) // 4) * 4), dtype=torch.float32, device=x.device)
+        else:
+            res = torch.empty((S, B, C), dtype=torch.float32, device=x.device)
         g_rows = [torch.empty((S, l.out_features), dtype=torch.float32, device=x.device) for l in layers] if rows else None
         g_all = [torch.empty((S, l.out_features, l.in_features), dtype=torch.float32, device=x.device)
                  for l in layers] if keep_gates else None
@@ -658,8 +702,14 @@ class BayesianNetwork(nn.Module):
                     g_rows[k][m] = l.gammas.sum(1)
                 if keep_gates:
                     g_all[k][m] = l.gammas
-            res[m] = h if head else F.log_softmax(h, dim=1)
-        if out is not None:
+            if sigmoid:
+                logits[m, :B * C].copy_(h.reshape(-1))
+            else:
+                res[m] = h if head else F.log_softmax(h, dim=1)
+        if sigmoid:
+            from . import evaluate
+            res = evaluate._binary_members(logits, S, B, C, log_probs)
+        elif out is not None:
             if out.dim() != 2 or out.shape[0] != S or out.shape[1] < B * C:
                 raise RuntimeError("bnn_amd: out must be a (S, >= B*classes) buffer")
             out[:, :B * C].copy_(res.view(S, B * C))
@@ -674,21 +724,32 @@ class BayesianNetwork(nn.Module):
             t = t + l.log_variational_posterior
         return t
 
-    def sample_elbo(self, input, target, samples=SAMPLES, *, num_batches=None, draws="torch"):
+    def sample_elbo(self, input, target, samples=SAMPLES, *, num_batches=None, draws="torch", stats=None):
         """:285-319, same positional arguments.  NUM_BATCHES / SAMPLES are module globals there (:34-67) and here
         (``bnn_amd.base.NUM_BATCHES = 600``, ``SAMPLES = 1``); ``num_batches=`` overrides the former per call.
         ``draws``: "torch" (default) draws the gates and the Gamma precisions with torch.distributions, as the reference;
         "hip" draws every stochastic input of the step inside the HIP kernels from the Philox state (``ops.RngState``,
         reseeded by ``torch.manual_seed``), reads nothing back to the host, and can be captured
-        (``graphs.make_graphed_train_step``).  The two agree in distribution, not bit for bit."""
+        (``graphs.make_graphed_train_step``).  The two agree in distribution, not bit for bit.
+        A sigmoid head (LBBNN-GP-MFsim_study.py:275-302): ``target`` is float32 (B,) or (B, units) (an integer 0 / 1 target is
+        converted with ``.float()``), the likelihood term is ``losses.elbo_bce_loss`` (nn.BCELoss(reduction='sum'), fused), and the
+        return has the script's five values (loss, log_prior, log_q, nll, out) with ``out`` the mean of the samples'
+        probabilities (for one sample the tensor itself).  ``stats``: the int32[4] device tensor ``elbo_bce_loss`` adds its counts
+        to (training accuracy with one read per epoch); sigmoid head only."""
         if draws not in ("torch", "hip"):
             raise ValueError("bnn_amd: sample_elbo(draws=...) must be 'torch' or 'hip', got %r" % (draws,))
         if num_batches is None:
             num_batches = NUM_BATCHES
+        sigmoid = self.head == "sigmoid"
+        if stats is not None and not sigmoid:
+            raise ValueError("bnn_amd: sample_elbo(stats=...) belongs to the BCE loss of a head=\"sigmoid\" network")
+        if sigmoid:
+            from .losses import elbo_bce_loss
+            target = target if target.dtype == torch.float32 else target.float()
         if draws == "hip":
-            return self._sample_elbo_hip(input, target, samples, num_batches)
+            return self._sample_elbo_hip(input, target, samples, num_batches, stats)
         dev = input.device
-        lps, lqs, nlls = [], [], []
+        lps, lqs, nlls, outs = [], [], [], []
         for _ in range(samples):
             gs = []
             for l in self._layers():
@@ -698,19 +759,28 @@ class BayesianNetwork(nn.Module):
             out = self.forward(input, *gs, sample=True, medimean=False)
             lps.append(self.log_prior())
             lqs.append(self.log_variational_posterior())
-            nlls.append(F.nll_loss(out, target, reduction="sum"))
+            if sigmoid:
+                nlls.append(elbo_bce_loss(out, target, stats=stats))  # sim study :292-296
+                outs.append(out)
+            else:
+                nlls.append(F.nll_loss(out, target, reduction="sum"))
         log_prior = torch.stack(lps).mean()
         log_q = torch.stack(lqs).mean()
         nll = torch.stack(nlls).mean()
         loss = nll + (log_q - log_prior) / num_batches                # :318
+        if sigmoid:
+            return loss, log_prior, log_q, nll, (outs[0] if samples == 1 else torch.stack(outs).mean(0))
         return loss, log_prior, log_q, nll
 
-    def _sample_elbo_hip(self, input, target, samples, num_batches):
+    def _sample_elbo_hip(self, input, target, samples, num_batches, stats=None):
         """sample_elbo(draws="hip"): per sample one Philox snapshot (the offset advances once), one _BaseDrawFn node per
         layer with ReLU / log_softmax in the GEMM epilogues, the NLL as one launch (losses.elbo_loss).  log_prior and log_q:
         up to three layers the chain of torch adds; deeper, one lbbnn_fold_rows launch over the slots the layers' kernels
-        wrote (_FoldTotalsFn) -- the same fp32 left fold."""
-        from .losses import elbo_loss
+        wrote (_FoldTotalsFn) -- the same fp32 left fold.  A sigmoid head: the last node runs without an activation, then the
+        head node (layers._SigmoidHeadFn) and the BCE loss (losses.elbo_bce_loss), whose backward hands the head the logits
+        gradient."""
+        from .layers import _SigmoidHeadFn
+        from .losses import elbo_bce_loss, elbo_loss
         if not input.is_cuda:
             raise RuntimeError("bnn_amd: sample_elbo(draws='hip') needs a HIP device tensor (input is on %s); there is no "
                                "CPU path" % input.device)
@@ -718,9 +788,10 @@ class BayesianNetwork(nn.Module):
         st = ops.RngState.get(input.device)
         layers = self._layers()
         n = len(layers)
-        head = "log_softmax" if self.dims[-1] <= 16 else None
+        sigmoid = self.head == "sigmoid"
+        head = "log_softmax" if self.dims[-1] <= 16 and not sigmoid else None
         fold = bool(self._fold_totals and n > 3)
-        lps, lqs, nlls = [], [], []
+        lps, lqs, nlls, outs = [], [], [], []
         for _ in range(samples):
             rng = st.t[:2].clone()
             st.advance(1)
@@ -740,14 +811,19 @@ class BayesianNetwork(nn.Module):
                     lq = lq_l if lq is None else lq + lq_l
             if fold:
                 lp, lq = _FoldTotalsFn.apply(buf, *vals[0], *vals[1])
-            if head is None:
+            if sigmoid:
+                h = _SigmoidHeadFn.apply(h)
+                outs.append(h)
+            elif head is None:
                 h = F.log_softmax(h, dim=1)
             lps.append(lp)
             lqs.append(lq)
-            nlls.append(elbo_loss(h, target))
+            nlls.append(elbo_bce_loss(h, target, stats=stats) if sigmoid else elbo_loss(h, target))
         if samples == 1:
             log_prior, log_q, nll = lps[0], lqs[0], nlls[0]
         else:
             log_prior, log_q, nll = torch.stack(lps).mean(), torch.stack(lqs).mean(), torch.stack(nlls).mean()
         loss = nll + (log_q - log_prior) / num_batches                # :318
+        if sigmoid:
+            return loss, log_prior, log_q, nll, (outs[0] if samples == 1 else torch.stack(outs).mean(0))
         return loss, log_prior, log_q, nll

@@ -2,7 +2,8 @@
 // written per parameter.  Workgroup -> (tensor, 4096-element chunk) by a binary search over the per-tensor chunk
 // prefix held in the kernel arguments (read through the kernarg pointer: scalar loads, no scratch copy).
 // lbbnn_adam_step_groups: the same pass for the tensors of any number of parameter groups, hyper-parameters and step counters
-// read from device tables; lbbnn_grad_sumsq: the global gradient norm for clipping, fixed-order sums.
+// read from device tables; lbbnn_sgd_step_groups: torch.optim.SGD's update in the same form;
+// lbbnn_grad_sumsq: the global gradient norm for clipping, fixed-order sums.
 #include <cmath>
 #include "lbbnn_device.h"
 #include "lbbnn_internal.h"
@@ -74,6 +75,23 @@ __global__ void adam_advance_kernel(float* step) { step[0] += 1.f; }
 // ---- lbbnn_adam_step_groups / lbbnn_grad_sumsq: the list kernels with per-group hyper-parameters read from device memory ----
 static_assert(CHUNK == LBBNN_ADAM_CHUNK, "include/lbbnn.h documents the chunk size");
 
+// The counters advance in the launch that used them (both list kernels end in this).  Every wave reaches this barrier only after
+// its last use of step[gi] (a value that was used has been returned by its load), thread 0 draws the workgroup's ticket after
+// the barrier, and only the holder of the last ticket -- drawn after every other workgroup's barrier -- writes the counters: no
+// workgroup can read an advanced one.  The next launch reads them across a kernel boundary.
+constexpr uint32_t F_INACTIVE = LBBNN_ADAM_F_INACTIVE;      // "a group without parameters": the same bit in both tables' flags
+static_assert(LBBNN_SGD_F_INACTIVE == F_INACTIVE, "advance_groups reads one bit for both tables");
+template <class Hyper>
+__device__ __forceinline__ void advance_groups(const Hyper* hyper, float* step, unsigned* ticket, int n_groups) {
+    __shared__ int last;
+    __syncthreads();
+    if (threadIdx.x == 0) last = atomicAdd(ticket, 1u) == gridDim.x - 1 ? 1 : 0;
+    __syncthreads();
+    if (!last) return;
+    for (int gq = threadIdx.x; gq < n_groups; gq += 256)
+        if (!(hyper[gq].flags & F_INACTIVE)) step[gq] += 1.f;
+    if (threadIdx.x == 0) atomicExch(ticket, 0u);
+}
 struct GroupsKArgs {
     lbbnn_adam_group_list_t l;
     int first[LBBNN_ADAM_GROUPS_MAX_TENSORS + 1];     // first workgroup of tensor i; first[n] = number of updating workgroups
@@ -154,19 +172,86 @@ __global__ __launch_bounds__(256) void adam_groups_kernel(const GroupsKArgs ka) 
             }
         }
     }
-    if (!a.advance) return;
-    // The counters advance in this launch.  Every wave reaches this barrier only after its last use of step[gi] (a value that
-    // was used has been returned by its load), thread 0 draws the workgroup's ticket after the barrier, and only the holder of
-    // the last ticket -- drawn after every other workgroup's barrier -- writes the counters: no workgroup can read an
-    // advanced one.  The next launch reads them across a kernel boundary.
-    __shared__ int last;
-    __syncthreads();
-    if (threadIdx.x == 0) last = atomicAdd(a.ticket, 1u) == gridDim.x - 1 ? 1 : 0;
-    __syncthreads();
-    if (!last) return;
-    for (int gq = threadIdx.x; gq < a.n_groups; gq += 256)
-        if (!(a.hyper[gq].flags & LBBNN_ADAM_F_INACTIVE)) a.step[gq] += 1.f;
-    if (threadIdx.x == 0) atomicExch(a.ticket, 0u);
+    if (a.advance) advance_groups(a.hyper, a.step, a.ticket, a.n_groups);
+}
+
+// ---- lbbnn_sgd_step_groups: torch.optim.SGD's update over the same list, one row of lbbnn_sgd_hyper_t per group ----
+struct SgdKArgs {
+    lbbnn_adam_group_list_t l;                                // v is not read; m[i] == NULL: no momentum buffer
+    int first[LBBNN_ADAM_GROUPS_MAX_TENSORS + 1];
+    const lbbnn_sgd_hyper_t* hyper;
+    float* step;
+    const float* grad_scale;
+    unsigned* ticket;
+    int n_groups, advance;
+};
+static_assert(sizeof(SgdKArgs) <= 4096, "kernel-argument segment");
+
+__global__ __launch_bounds__(256) void sgd_groups_kernel(const SgdKArgs ka) {
+    const LBBNN_CONST_AS SgdKArgs& a = *kernarg_as<SgdKArgs>();
+    const int blk = blockIdx.x;
+    if (blk < a.first[a.l.n]) {                               // (an advance-only launch has one workgroup and no tensor)
+        int lo = 0, hi = a.l.n;                               // largest i with first[i] <= blk
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (a.first[mid] <= blk) lo = mid; else hi = mid; }
+        const int ti = lo;
+        float* __restrict__ p = a.l.p[ti];
+        const float* __restrict__ g = a.l.g[ti];
+        const float* __restrict__ mk = a.l.mask[ti];
+        const int64_t n = a.l.numel[ti];
+        const int64_t base = (int64_t)(blk - a.first[ti]) * CHUNK;
+        const int gi = a.l.group[ti];
+        const lbbnn_sgd_hyper_t h = a.hyper[gi];
+        const bool first_step = a.step[gi] == 0.f;
+        const float lr = h.lr, mom = h.momentum, keep = 1.f - h.dampening, wd = h.weight_decay;
+        const bool decay = wd != 0.f, nesterov = (h.flags & LBBNN_SGD_F_NESTEROV) != 0;
+        float* __restrict__ m = mom != 0.f ? a.l.m[ti] : nullptr;         // the buffer is neither read nor written without momentum
+        const bool scaled = a.grad_scale != nullptr;
+        const float gscale = scaled ? a.grad_scale[0] : 1.f;
+        const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                           reinterpret_cast<uintptr_t>(mk)) & 15u) == 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int64_t i = base + (int64_t)(threadIdx.x + 256 * k) * 4;
+            if (i >= n) break;
+            float pp[4], gg[4], mm[4] = {0.f, 0.f, 0.f, 0.f};
+            const int cnt = (int)((n - i) < 4 ? (n - i) : 4);
+            const bool load_m = m && !first_step;             // the first step overwrites the buffer: it may hold anything
+            if (vec && cnt == 4) {
+                const float4 a0 = *reinterpret_cast<const float4*>(p + i), a1 = *reinterpret_cast<const float4*>(g + i);
+                pp[0] = a0.x; pp[1] = a0.y; pp[2] = a0.z; pp[3] = a0.w;  gg[0] = a1.x; gg[1] = a1.y; gg[2] = a1.z; gg[3] = a1.w;
+                if (load_m) { const float4 a2 = *reinterpret_cast<const float4*>(m + i); mm[0] = a2.x; mm[1] = a2.y; mm[2] = a2.z; mm[3] = a2.w; }
+                if (mk) { const float4 a4 = *reinterpret_cast<const float4*>(mk + i); gg[0] *= a4.x; gg[1] *= a4.y; gg[2] *= a4.z; gg[3] *= a4.w; }
+            } else {
+                for (int q = 0; q < 4; ++q) {
+                    const bool in = q < cnt;
+                    pp[q] = in ? p[i + q] : 0.f; gg[q] = in ? g[i + q] : 0.f;
+                    if (load_m && in) mm[q] = m[i + q];
+                    if (mk && in) gg[q] *= mk[i + q];
+                }
+            }
+            if (scaled) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) gg[q] *= gscale;
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {                     // torch.optim.SGD's _single_tensor_sgd, line for line
+                float gq = gg[q];
+                if (decay) gq = gq + wd * pp[q];
+                if (m) {
+                    mm[q] = first_step ? gq : mom * mm[q] + keep * gq;
+                    gq = nesterov ? gq + mom * mm[q] : mm[q];
+                }
+                pp[q] = pp[q] - lr * gq;
+            }
+            if (vec && cnt == 4) {
+                *reinterpret_cast<float4*>(p + i) = make_float4(pp[0], pp[1], pp[2], pp[3]);
+                if (m) *reinterpret_cast<float4*>(m + i) = make_float4(mm[0], mm[1], mm[2], mm[3]);
+            } else {
+                for (int q = 0; q < cnt; ++q) { p[i + q] = pp[q]; if (m) m[i + q] = mm[q]; }
+            }
+        }
+    }
+    if (a.advance) advance_groups(a.hyper, a.step, a.ticket, a.n_groups);
 }
 
 struct SumsqKArgs {
@@ -273,11 +358,12 @@ extern "C" int lbbnn_adam_step(const lbbnn_adam_list_t* list, float lr, float be
 }
 
 // list checks shared by the two list entry points: 0, or the LBBNN_E_* code; fills first[] and the workgroup count
-static int groups_list_blocks(const lbbnn_adam_group_list_t* list, bool update, int n_groups, int* first, int64_t* blocks) {
+// (update: p and group are checked; moments: m and v too -- Adam's; SGD reads no v and takes m[i] == NULL)
+static int groups_list_blocks(const lbbnn_adam_group_list_t* list, bool update, bool moments, int n_groups, int* first, int64_t* blocks) {
     if (list->n < 0 || list->n > LBBNN_ADAM_GROUPS_MAX_TENSORS) return LBBNN_E_SHAPE;
     int64_t nb = 0;
     for (int i = 0; i < list->n; ++i) {
-        if (!list->g[i] || (update && (!list->p[i] || !list->m[i] || !list->v[i]))) return LBBNN_E_NULL;
+        if (!list->g[i] || (update && !list->p[i]) || (moments && (!list->m[i] || !list->v[i]))) return LBBNN_E_NULL;
         if (list->numel[i] <= 0 || (update && (list->group[i] < 0 || list->group[i] >= n_groups))) return LBBNN_E_SHAPE;
         first[i] = (int)nb;
         nb += (list->numel[i] + CHUNK - 1) / CHUNK;
@@ -294,13 +380,29 @@ extern "C" int lbbnn_adam_step_groups(const lbbnn_adam_group_list_t* list, const
     if (n_groups < 1 || n_groups > 65536) return LBBNN_E_SHAPE;
     GroupsKArgs ka;
     int64_t nb = 0;
-    const int rc = groups_list_blocks(list, true, n_groups, ka.first, &nb);
+    const int rc = groups_list_blocks(list, true, true, n_groups, ka.first, &nb);
     if (rc) return rc;
     if (nb == 0 && !advance) return 0;
     ka.l = *list;
     ka.hyper = hyper; ka.step = step; ka.grad_scale = grad_scale; ka.ticket = ticket;
     ka.n_groups = n_groups; ka.advance = advance ? 1 : 0;
     hipLaunchKernelGGL(adam_groups_kernel, dim3((unsigned)(nb > 0 ? nb : 1)), dim3(256), 0, static_cast<hipStream_t>(stream), ka);
+    return (int)hipGetLastError();
+}
+
+extern "C" int lbbnn_sgd_step_groups(const lbbnn_adam_group_list_t* list, const lbbnn_sgd_hyper_t* hyper, float* step,
+                                     int n_groups, const float* grad_scale, uint32_t* ticket, int advance, void* stream) {
+    if (!list || !hyper || !step || (advance && !ticket)) return LBBNN_E_NULL;
+    if (n_groups < 1 || n_groups > 65536) return LBBNN_E_SHAPE;
+    SgdKArgs ka;
+    int64_t nb = 0;
+    const int rc = groups_list_blocks(list, true, false, n_groups, ka.first, &nb);
+    if (rc) return rc;
+    if (nb == 0 && !advance) return 0;
+    ka.l = *list;
+    ka.hyper = hyper; ka.step = step; ka.grad_scale = grad_scale; ka.ticket = ticket;
+    ka.n_groups = n_groups; ka.advance = advance ? 1 : 0;
+    hipLaunchKernelGGL(sgd_groups_kernel, dim3((unsigned)(nb > 0 ? nb : 1)), dim3(256), 0, static_cast<hipStream_t>(stream), ka);
     return (int)hipGetLastError();
 }
 
@@ -315,7 +417,7 @@ extern "C" int lbbnn_grad_sumsq(const lbbnn_adam_group_list_t* list, float* work
     if (work_offset < 0 || finalize_count < 0) return LBBNN_E_SHAPE;
     SumsqKArgs ka;
     int64_t nb = 0;
-    const int rc = groups_list_blocks(list, false, 0, ka.first, &nb);
+    const int rc = groups_list_blocks(list, false, false, 0, ka.first, &nb);
     if (rc) return rc;
     if (finalize_count > 0 && (finalize_count != work_offset + nb || !(max_norm > 0.f) || finalize_count > 0x7fffffff)) return LBBNN_E_SHAPE;
     hipStream_t s = static_cast<hipStream_t>(stream);

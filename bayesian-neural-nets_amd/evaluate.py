@@ -248,7 +248,7 @@ def _is_base(net) -> bool:
 
 @torch.no_grad()
 def base_ensemble(net, data: torch.Tensor, samples: int = 10, *, gates: str = "sample", max_members: Optional[int] = None,
-                  keep_gates: bool = False) -> Dict[str, object]:
+                  keep_gates: bool = False, log_probs: bool = False) -> Dict[str, object]:
     """``samples`` evaluation forwards of a baseline LBBNN network of n layers in ceil(n / 4) + n launches (1 + 3 for the
     reference's three layers) per chunk of at most ``max_members`` members (default: all in one).  Member m draws at
     Philox offset (live offset + m) and equals, bit for bit, what
@@ -257,9 +257,12 @@ def base_ensemble(net, data: torch.Tensor, samples: int = 10, *, gates: str = "s
     ``gate_rows`` (per layer (samples, O): the sum over each row of the gates the member used) and, with ``keep_gates``,
     ``gates`` (per layer (samples, O, I)).  A network with a layer wider than lbbnn_gate_members takes
     (``ops.operand_ld(in_features) > ops.GATE_MEMBERS_MAX_LD``) runs each member as its ``sample_forward`` chain instead
-    (``BayesianNetwork._predict_members_loop``; ``gates="mpm"`` raises there)."""
+    (``BayesianNetwork._predict_members_loop``; ``gates="mpm"`` raises there).  A network with ``head="sigmoid"``: ``outputs``
+    are the (samples, B, units) probabilities, or with ``log_probs`` (one unit) the (samples, B, 2) log-probabilities
+    [logsigmoid(-logit), logsigmoid(logit)]; one lbbnn_binary_head launch more per chunk, same draws and offsets."""
     if not _is_base(net):
         raise ValueError("bnn_amd: base_ensemble takes a baseline LBBNN network (bnn_amd.base.BayesianNetwork)")
+    _check_log_probs(net, log_probs)
     if not data.is_cuda:
         raise RuntimeError("bnn_amd: ensemble evaluation needs a HIP device tensor (data is on %s); there is no CPU path"
                            % data.device)
@@ -276,12 +279,13 @@ def base_ensemble(net, data: torch.Tensor, samples: int = 10, *, gates: str = "s
     rows, kept, outs = [], [], []
     for m0 in range(0, S, chunk):
         c = min(chunk, S - m0)
-        o, r, g = net._predict_members(data, st.t, c, gates, out=head[m0:m0 + c], rows=True, keep_gates=keep_gates)
+        o, r, g = net._predict_members(data, st.t, c, gates, out=head[m0:m0 + c], rows=True, keep_gates=keep_gates,
+                                       log_probs=log_probs)
         st.advance(c)
         outs.append(o)
         rows.append(r)
         kept.append(g)
-    if C <= 16:
+    if C <= 16 and not log_probs:
         outputs = head[:, :B * C].view(S, B, C)             # the chunks wrote their log-probabilities into `head`
     else:
         outputs = outs[0] if len(outs) == 1 else torch.cat(outs)
@@ -302,12 +306,12 @@ def ensemble_forward(net, data: torch.Tensor, samples: int = 10, batched=None, *
     to baseline and variational-dropout networks and frozen models.  A ``FrozenNetwork`` (``freeze``): its ``ensemble``.
     A variational-dropout network (``vd.BNN``): None = ``vd_ensemble`` on a
     HIP device when no layer has injected noise, else the loop of ``net(data)``; True with injected noise raises ValueError.
-    An LRT / MNF network with ``head="sigmoid"`` (or its frozen model): (samples, B, units) PROBABILITIES, same draws and Philox
+    A network with ``head="sigmoid"`` (LRT / MNF, its frozen model, or a baseline network): (samples, B, units) PROBABILITIES, same draws and Philox
     offsets (the head consumes no randomness); ``log_probs=True`` (one unit) returns the (samples, B, 2) log-probabilities
     [logsigmoid(-logit), logsigmoid(logit)] instead, made from the logits by the same launch."""
     net.eval()
-    if log_probs and (_is_vd(net) or _is_base(net)):
-        raise ValueError("bnn_amd: log_probs=True applies to an LRT / MNF network with head=\"sigmoid\" or its frozen model")
+    if log_probs and (_is_vd(net) or (_is_base(net) and _head_of(net) != "sigmoid")):
+        raise ValueError("bnn_amd: log_probs=True applies to a network with head=\"sigmoid\" or its frozen model")
     if _is_frozen(net):
         if gates != "sample":
             raise ValueError("bnn_amd: gates=%r: the gates of a frozen model were fixed by evaluate.freeze(net, gates=...) "
@@ -332,8 +336,8 @@ def ensemble_forward(net, data: torch.Tensor, samples: int = 10, batched=None, *
         if batched is None:
             batched = data.is_cuda
         if batched:
-            return base_ensemble(net, data, samples, gates=gates, max_members=max_members)["outputs"]
-        return torch.stack([net.sample_predict(data, gates=gates) for _ in range(samples)])
+            return base_ensemble(net, data, samples, gates=gates, max_members=max_members, log_probs=log_probs)["outputs"]
+        return torch.stack([net.sample_predict(data, gates=gates, log_probs=log_probs) for _ in range(samples)])
     if gates != "sample":
         raise ValueError("bnn_amd: gates=%r is not an option of ensemble_forward for an LRT / MNF network; the median "
                          "probability model of such a network is evaluate.freeze(net, gates=\"mpm\").ensemble(data, samples)"
@@ -434,16 +438,30 @@ def _vd_ensemble_eval(net, data, target, samples):
     return res
 
 
+def _base_mean_forward(net, data, binary: bool):
+    """The posterior-mean forward of a baseline network (mode 2: weight = alpha * mu, LBBNN-GP-MF.py:413) with alpha =
+    sigmoid(lambdal) set as the reference sets it (:369-374); ``binary``: the sigmoid head's 2-class log-probabilities."""
+    layers = net._layers()
+    for l in layers:
+        l.alpha = 1 / (1 + torch.exp(-l.lambdal.detach()))
+        l.gamma.alpha = l.alpha
+    net._logp2_now = bool(binary)
+    try:
+        return net(data, *[None] * len(layers), sample=False)
+    finally:
+        net._logp2_now = False
+
+
 def _base_ensemble_eval(net, data, target, samples):
-    r = base_ensemble(net, data, samples)
+    binary = _binary_eval(net)
+    if binary and target is not None:
+        target = _binary_target(target)
+    r = base_ensemble(net, data, samples, log_probs=binary)
     outputs = r["outputs"]
     layers = net._layers()
     n_w = sum(l.out_features * l.in_features for l in layers)
     density = torch.stack([rw.double().sum(1) for rw in r["gate_rows"]]).sum(0) / n_w
-    for l in layers:
-        l.alpha = 1 / (1 + torch.exp(-l.lambdal.detach()))                  # :369-374
-        l.gamma.alpha = l.alpha
-    pred_mean = net(data, *[None] * len(layers), sample=False).argmax(1)     # :413 (mode 2: weight = alpha * mu)
+    pred_mean = _base_mean_forward(net, data, binary).argmax(1)
     pred_ens = outputs.mean(0).argmax(1)
     res = {"outputs": outputs, "pred_ensemble": pred_ens, "pred_posterior_mean": pred_mean, "density": density.float()}
     if target is not None:
@@ -847,14 +865,9 @@ def _eval_forwards(net, data, samples: int, posterior_mean: bool, gates: str):
         outputs = net.ensemble(data, samples, log_probs=binary)
         return outputs, (net(data, sample=False, log_probs=binary) if posterior_mean else None)
     if _is_base(net):
-        outputs = base_ensemble(net, data, samples, gates=gates)["outputs"]
-        if not posterior_mean:
-            return outputs, None
-        layers = net._layers()
-        for l in layers:
-            l.alpha = 1 / (1 + torch.exp(-l.lambdal.detach()))                  # LBBNN-GP-MF.py:369-374
-            l.gamma.alpha = l.alpha
-        return outputs, net(data, *[None] * len(layers), sample=False)         # :413 (mode 2: weight = alpha * mu)
+        binary = _binary_eval(net)
+        outputs = base_ensemble(net, data, samples, gates=gates, log_probs=binary)["outputs"]
+        return outputs, (_base_mean_forward(net, data, binary) if posterior_mean else None)
     if _is_vd(net):
         return ensemble_forward(net, data, samples, gates=gates), None         # VD has no posterior-mean forward
     binary = _binary_eval(net)

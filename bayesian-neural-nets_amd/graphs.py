@@ -104,10 +104,10 @@ def capture(graph, **kw):
 
 
 def make_graphed_train_step(net, optimizer, loss_fn, example_x, example_y, warmup: int = 3, overlap_vector_backward=None):
-    """loss_fn(net, x, y) -> scalar loss.  The optimizer must be capture-safe: ``bnn_amd.optim.Adam`` (device-side
-    step counter) or ``torch.optim.Adam(capturable=True)``.  The warm-up steps run eagerly first, so optimizer state is
-    allocated outside the capture.  ``bnn_amd.optim.Adam`` reads its learning rates (and betas, eps, weight decay) from a
-    device table: ``step`` pushes the groups' current values before every replay (``push_hyperparameters``: a copy only when
+    """loss_fn(net, x, y) -> scalar loss.  The optimizer must be capture-safe: ``bnn_amd.optim.Adam`` or ``bnn_amd.optim.SGD``
+    (device-side step counters) or ``torch.optim.Adam(capturable=True)``.  The warm-up steps run eagerly first, so optimizer state is
+    allocated outside the capture.  ``bnn_amd.optim.Adam`` and ``SGD`` read their learning rates (and betas, eps, weight decay;
+    momentum, dampening) from a device table: ``step`` pushes the groups' current values before every replay (``push_hyperparameters``: a copy only when
     one changed), so ``torch.optim.lr_scheduler`` and edits of ``param_groups`` work under the one captured graph.
     ``overlap_vector_backward``: the vector-sized backward chains of the MNF layers are deferred
     (``layers.vector_backward_overlap``): each layer's backward only files its chain, and all layers' chains are issued

@@ -179,13 +179,13 @@ class DataParallelELBO:
             graph A   zero_grad -> forward -> nll + kl / (num_batches * world) -> backward (HIP kernels, vector chains
                       deferred and batched) -> all gradients packed into the flat bucket (one launch)
             eager     all-reduce of the bucket over RCCL (world > 1; nothing at world 1)
-            graph B   bnn_amd.optim.Adam on the reduced bucket (one launch)
+            graph B   bnn_amd.optim.Adam (or bnn_amd.optim.SGD) on the reduced bucket (one launch)
 
         Three host calls per step instead of ~90 launches: the eager step of the headline net is host-bound at ~2 ms, the
         graphs run at GPU speed.  The collective stays OUTSIDE the graphs on purpose: capturing RCCL inside a graph works
         in principle, but a capture that misbehaves would hang all N ranks, and an N-GPU node is not available to the
         build to test it on -- between two graphs the collective is the plain, well-trodden ``dist.all_reduce``.
-        ``optimizer`` must be capture-safe (``bnn_amd.optim.Adam``).  Returns step(x, y) -> loss (a static tensor).
+        ``optimizer`` must be capture-safe (``bnn_amd.optim.Adam`` or ``bnn_amd.optim.SGD``).  Returns step(x, y) -> loss (a static tensor).
         Raises RuntimeError while an autograd graph of an earlier forward through the network is still alive (a loss or
         an output of an eager step that has not been dropped): the parameters' AccumulateGrad nodes remember the stream
         they were created on, and a node created on the default stream makes autograd synchronise the capture stream

@@ -1016,6 +1016,34 @@ typedef struct lbbnn_adam_group_list {
 int lbbnn_adam_step_groups(const lbbnn_adam_group_list_t* list, const lbbnn_adam_hyper_t* hyper, float* step, int n_groups,
                            const float* grad_scale, uint32_t* ticket, int advance, void* stream);
 
+/* lbbnn_sgd_step_groups -- torch.optim.SGD's update (the optimizer of the baseline simulation study: eleven single-tensor
+ * groups at two rates, six of them set to 0 at epoch 50, LBBNN-GP-MFsim_study.py) in the form of lbbnn_adam_step_groups: a
+ * list of tensors of ANY NUMBER of parameter groups in ONE launch, every value a schedule may change read from a DEVICE table
+ * when the kernel runs.  The list is lbbnn_adam_group_list_t (so lbbnn_grad_sumsq gives the clipping scale unchanged): m[i] is
+ * the momentum buffer, NULL = no momentum for that tensor; v is not read and may be NULL.  Per element, with
+ * h = hyper[group[i]] and t = step[group[i]]:
+ *   g' = g;  mask[i] != NULL: g' = g' * mask[i][e];  grad_scale != NULL: g' = g' * *grad_scale
+ *   h.weight_decay != 0: g' = g' + h.weight_decay * p
+ *   m[i] != NULL and h.momentum != 0:  buf = (t == 0) ? g' : h.momentum * buf + (1 - h.dampening) * g'  (stored; the first step
+ *       does not read the buffer);  g' = LBBNN_SGD_F_NESTEROV ? g' + h.momentum * buf : buf
+ *   p = p - h.lr * g'
+ * The "first step" is per GROUP (t == 0), where torch keeps it per parameter: a parameter that receives its first gradient
+ * later than its group differs from torch only when dampening != 0.
+ * step / ticket / advance: as lbbnn_adam_step_groups, the same device code (every group without LBBNN_SGD_F_INACTIVE gets
+ * step[g] += 1 in the same launch, by the workgroup that finishes last).  list->n == 0 with advance != 0 is a
+ * one-workgroup launch that only advances.  Launches: exactly 1.
+ * Checks (before any HIP call): list / hyper / step, ticket with advance, a tensor's p / g: LBBNN_E_NULL; n outside [0,
+ * LBBNN_ADAM_GROUPS_MAX_TENSORS], n_groups outside [1, 65536], numel <= 0, group[i] outside [0, n_groups): LBBNN_E_SHAPE. */
+#define LBBNN_SGD_F_NESTEROV 0x1       /* Nesterov momentum                                              */
+#define LBBNN_SGD_F_INACTIVE 0x2       /* a group without parameters: its counter does not advance       */
+typedef struct lbbnn_sgd_hyper {       /* one row of the device table; 20 bytes                          */
+    float lr, momentum, dampening, weight_decay;
+    uint32_t flags;
+} lbbnn_sgd_hyper_t;
+
+int lbbnn_sgd_step_groups(const lbbnn_adam_group_list_t* list, const lbbnn_sgd_hyper_t* hyper, float* step, int n_groups,
+                          const float* grad_scale, uint32_t* ticket, int advance, void* stream);
+
 /* lbbnn_grad_sumsq -- global L2 norm of the (masked) gradients of a list, for torch.nn.utils.clip_grad_norm_'s clipping
  * applied inside lbbnn_adam_step_groups (p / m / v / group of the list are not read).  Launch 1: workgroup b of the list
  * (tensor i owns ceil(numel[i] / LBBNN_ADAM_CHUNK) consecutive workgroups, tensors in list order) writes
