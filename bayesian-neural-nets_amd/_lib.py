@@ -215,6 +215,13 @@ class CompactMap(ctypes.Structure):
     _fields_ = [("rows", c_p), ("cols", c_p), ("O_full", c_i), ("I_full", c_i)]
 
 
+class BaseFrozenDesc(ctypes.Structure):
+    """lbbnn_base_frozen_desc_t"""
+    _fields_ = [(n, c_p) for n in ("mu", "rho", "lambdal", "bias_mu", "bias_rho", "w_mu", "w_sigma", "alpha", "e_w", "b_mu",
+                                   "b_sigma", "kept_rows", "alpha_rows", "keep")] + \
+               [(n, c_i) for n in ("O", "I", "ld", "flags", "exact")] + [("layer_id", c_u32)]
+
+
 class DenseMembers(ctypes.Structure):
     """lbbnn_dense_members_t"""
     _fields_ = [("q0_mean", c_p), ("q0_log_var", c_p), ("zt", ctypes.POINTER(DenseTransform)), ("T", c_i), ("I", c_i),
@@ -406,6 +413,9 @@ SIGNATURES = {
     "lbbnn_frozen_operands_compact": (c_i, [ctypes.POINTER(FrozenDesc), ctypes.POINTER(CompactMap), c_i, c_p]),
     "lbbnn_frozen_members_compact": (c_i, [ctypes.POINTER(FrozenDesc), ctypes.POINTER(CompactMap), c_i, c_i, c_p, c_u64, c_p]),
     "lbbnn_gather_columns": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_p]),
+    "lbbnn_base_frozen_operands": (c_i, [ctypes.POINTER(BaseFrozenDesc), ctypes.POINTER(CompactMap), c_i, c_i, ctypes.c_float, c_p]),
+    "lbbnn_base_frozen_members": (c_i, [ctypes.POINTER(BaseFrozenDesc), ctypes.POINTER(CompactMap), c_i, c_i, c_i, ctypes.c_float,
+                                        ctypes.POINTER(c_p), ctypes.POINTER(c_p), ctypes.POINTER(c_p), c_p, c_u64, c_p]),
     "lbbnn_eval_metrics_work_bytes": (c_i64, [c_i, c_i, c_i]),
     "lbbnn_eval_metrics": (c_i, [ctypes.POINTER(EvalMetricsArgs), c_p]),
     "lbbnn_eval_uncertainty_work_bytes": (c_i64, [c_i, c_i, c_i, c_i]),

@@ -25,6 +25,11 @@ probability model of ``outofsample(net, loader, medimod=True)`` (LBBNN-GP-MF-LRT
 which the member GEMMs then evaluate without reading the parameters again, and which reports its own density.
 ``freeze(net, gates, dense=True)`` also takes an MNF network with RNVP / MNF-type z flows (the reference's default): every
 member's z through the coupling flows is then ONE lbbnn_flow_dense_members launch for all layers and members.
+
+Baseline networks have a frozen model of their own, ``freeze_base(net, gates="sample" | "mpm", compact=...)`` ->
+``FrozenBaseNetwork``: sigma, alpha and the gated means taken once (lbbnn_base_frozen_operands), every member then drawn from
+that snapshot (lbbnn_base_frozen_members) at the streams, offsets and counters of ``base_ensemble`` -- a full model's members are
+``base_ensemble``'s bit for bit, a compact model's weights the full model's at the rows and columns that stay.
 """
 import math
 from typing import Dict, List, Optional
@@ -916,7 +921,7 @@ def _empty(*size, **kw):
 
 
 def _is_frozen(net) -> bool:
-    return isinstance(net, FrozenNetwork)
+    return isinstance(net, (FrozenNetwork, FrozenBaseNetwork))
 
 
 def _pad4(n: int) -> int:
@@ -1694,3 +1699,466 @@ def freeze(net, gates: str = "alpha", *, threshold: float = 0.5, dense: bool = F
     fz = FrozenNetwork(net.dims, family, gates, threshold, device=layers[0].weight_mu.device, flows=flows, head=net.head)
     fz.eval()
     return fz._bind(net)
+
+
+# ----------------------------------------------------------------------------------------- frozen baseline model
+BASE_FROZEN_GATES = ("sample", "mpm")
+
+
+class FrozenBaseNetwork(nn.Module):
+    """A trained baseline LBBNN network (``base.BayesianNetwork``) frozen for evaluation (built by ``freeze_base``; no
+    parameters, buffers only): what ``test_ensemble`` and ``outofsample(net, medimod=True)`` evaluate (LBBNN-GP-MF.py:345-502).
+
+    Per layer it holds the planes ``w_mu`` and ``w_sigma`` = softplus(weight_rho) as plain fp32 rows (``gates="mpm"``: zero
+    where alpha = sigmoid(lambdal) <= threshold), ``alpha`` (``gates="sample"`` only), the posterior-mean operand ``e_w``
+    (alpha * mu, or the medimean's gated mu) in the format of the precision in force at freeze time, ``b_mu``, ``b_sigma``,
+    ``kept_rows`` (per row the weights with alpha > threshold) and ``alpha_rows`` (per row the sum of alpha); it records every
+    layer's ``exact`` bits and Philox layer id, and the head.  One lbbnn_base_frozen_members launch per group of 4 layers then
+    draws every member's weights and biases from the planes -- at the streams, offsets and counters of ``base_ensemble``, so
+    a full model's members are ``base_ensemble``'s, bit for bit -- and one lbbnn_gemm_members_mean launch per layer runs
+    them.  The relaxed gates' temperature is ``distributions.TEMPER_PRIOR`` at call time, as for ``base_ensemble``.
+
+    A compact model (``freeze_base(net, "mpm", compact=True)``) holds the rows and columns of the units some output depends
+    on (``live_structure``): ``dims`` are the compact widths, ``full_dims`` the network's, ``live`` / ``needed`` /
+    ``active_kept`` / ``active_density`` as for ``CompactFrozenNetwork``.  Every kept weight is drawn at its FULL Philox
+    counter, so member weight (o', j') and every bias are bit for bit the full model's at (live[i+1][o'], live[i][j']), and
+    the outputs equal the full model's to fp32 rounding (the order of the sums).  Nothing here follows the source network's
+    parameters until ``refresh()``."""
+
+    def __init__(self, full_dims, gates: str = "sample", threshold: float = 0.5, device=None, head: str = "log_softmax",
+                 live=None, needed=None):
+        super().__init__()
+        if head not in ("log_softmax", "sigmoid"):
+            raise ValueError("bnn_amd: head must be 'log_softmax' or 'sigmoid', got %r" % (head,))
+        if gates not in BASE_FROZEN_GATES:
+            raise ValueError("bnn_amd: gates must be 'sample' (the gates drawn as trained) or 'mpm' (the median probability "
+                             "model), got %r" % (gates,))
+        threshold = float(threshold)
+        if not 0.0 < threshold < 1.0:
+            raise ValueError("bnn_amd: threshold must lie strictly between 0 and 1 (0.5 = the median probability model), got %r"
+                             % (threshold,))
+        self.full_dims = tuple(int(d) for d in full_dims)
+        self.compact = live is not None
+        if self.compact:
+            if gates != "mpm":
+                raise ValueError("bnn_amd: a compact model needs gates=\"mpm\"")
+            if len(live) != len(self.full_dims) or len(needed) != len(self.full_dims):
+                raise ValueError("bnn_amd: a network of %d layers has %d boundaries" % (len(self.full_dims) - 1, len(self.full_dims)))
+            self.dims = tuple(int(t.numel()) for t in live)
+            self.needed = [int(c) for c in needed]
+            for b, t in enumerate(live):
+                self.register_buffer("live_%d" % b, t.to(device=device, dtype=torch.int32).contiguous())
+        else:
+            self.dims = self.full_dims
+        if head == "sigmoid" and self.dims[-1] > 16:
+            raise ValueError("bnn_amd: a sigmoid head takes at most 16 output units, got dims[-1] = %d" % self.dims[-1])
+        self.head, self.gates, self.threshold = head, gates, threshold
+        self._src = [None]              # the source network, in a list so that it is not registered as a submodule
+        self._split, self._layer_ids, self._exact = [], [], []
+        self._descs, self._maps = None, None
+        self._mcap, self._mw, self._mb, self._mptr = 0, [], [], None
+        self._active = self._full_kept = None
+        self.last_weights = self.last_biases = None
+        for i in range(len(self.dims) - 1):
+            self.register_buffer("kept_rows_%d" % i, torch.zeros(self.dims[i + 1], dtype=torch.int32, device=device))
+
+    # ------------------------------------------------------------------------------------- statistics
+    @property
+    def n_layers(self) -> int:
+        return len(self.dims) - 1
+
+    def _buf(self, name: str, i: int) -> torch.Tensor:
+        return getattr(self, "%s_%d" % (name, i))
+
+    def _n_weights(self) -> int:
+        return sum(self.full_dims[i] * self.full_dims[i + 1] for i in range(self.n_layers))
+
+    @property
+    def kept_rows(self) -> List[torch.Tensor]:
+        """Per layer (O',) int32: weights of each row with alpha > threshold, in either gates mode (a compact model: among
+        the live columns)."""
+        return [self._buf("kept_rows", i) for i in range(self.n_layers)]
+
+    @property
+    def kept(self) -> List[int]:
+        return [int(k.sum()) for k in self.kept_rows]
+
+    @property
+    def density(self) -> float:
+        """``gates="mpm"``: kept weights / all weights of the full network.  ``gates="sample"``: the EXPECTED density
+        sum(alpha) / weights (from ``alpha_rows``) -- the mean of what the members' gates draw, not a sampled value."""
+        if self.gates == "sample":
+            return float(torch.stack([self._buf("alpha_rows", i).double().sum() for i in range(self.n_layers)]).sum()) / self._n_weights()
+        if self.compact:
+            return int(self._full_kept) / self._n_weights()
+        return sum(self.kept) / self._n_weights()
+
+    @property
+    def live(self) -> List[torch.Tensor]:
+        self._need_compact("live")
+        return [self._buf("live", b) for b in range(len(self.dims))]
+
+    @property
+    def active_kept(self) -> int:
+        """Kept weights whose row and column are both needed (over every layer); a compact model only."""
+        self._need_compact("active_kept")
+        return int(self._active)
+
+    @property
+    def active_density(self) -> float:
+        return self.active_kept / self._n_weights()
+
+    def _need_compact(self, what: str):
+        if not self.compact:
+            raise RuntimeError("bnn_amd: %s belongs to a compact model (freeze_base(net, \"mpm\", compact=True))" % what)
+
+    def extra_repr(self) -> str:
+        full = "full_dims=%s, " % (self.full_dims,) if self.compact else ""
+        head = ", head=sigmoid" if self.head == "sigmoid" else ""
+        return "%sdims=%s, family=base, gates=%s, threshold=%g%s" % (full, self.dims, self.gates, self.threshold, head)
+
+    # ------------------------------------------------------------------------------------- snapshot
+    @torch.no_grad()
+    def _bind(self, net, need=None, masks=None):
+        """Allocate every buffer (once), build the descriptors that point at them, and take the first snapshot."""
+        layers = net._layers()
+        dev = layers[0].weight_mu.device
+        f = dict(dtype=torch.float32, device=dev)
+        n = self.n_layers
+        self._src = [net]
+        if masks is not None:
+            self._full_kept = torch.stack([k.sum() for k in masks]).sum()
+            self._active = torch.stack([(k & need[i + 1][:, None] & need[i][None, :]).sum() for i, k in enumerate(masks)]).sum()
+        split_now = ops.split_precision()
+        for i in range(n):
+            O, I = self.dims[i + 1], self.dims[i]
+            ld = ops.operand_ld(I)
+            # the operand format by the rule of base_ensemble, at this model's shapes
+            self._split.append(bool(split_now and ops.split_eligible(I, O) and (i == 0 or self.dims[i] % 4 == 0)))
+            planes = ("w_mu", "w_sigma", "e_w") + (("alpha",) if self.gates == "sample" else ())
+            for name in planes:
+                self.register_buffer("%s_%d" % (name, i), _empty((O, ld), **f))
+            for name in ("b_mu", "b_sigma", "alpha_rows"):
+                self.register_buffer("%s_%d" % (name, i), _empty((O,), **f))
+        self._input_identity = self.dims[0] == self.full_dims[0]
+        self._point()
+        return self._snapshot()
+
+    def _point(self):
+        """The descriptors and maps of every layer, pointing at this model's buffers (built when the buffers are made, and
+        again whenever the module is moved or cast: ``_apply``); the member buffers start over."""
+        from . import _lib
+        n = self.n_layers
+        self._descs = (_lib.BaseFrozenDesc * n)()
+        for i in range(n):
+            d = self._descs[i]
+            d.O, d.I = self.dims[i + 1], self.dims[i]
+            d.ld = ops.operand_ld(d.I)
+            d.flags = ops.F_SPLIT16 if self._split[i] else 0
+            d.w_mu, d.w_sigma, d.e_w = (self._buf(k, i).data_ptr() for k in ("w_mu", "w_sigma", "e_w"))
+            d.alpha = self._buf("alpha", i).data_ptr() if self.gates == "sample" else None
+            d.b_mu, d.b_sigma = self._buf("b_mu", i).data_ptr(), self._buf("b_sigma", i).data_ptr()
+            d.kept_rows, d.alpha_rows = self._buf("kept_rows", i).data_ptr(), self._buf("alpha_rows", i).data_ptr()
+            if self._exact:
+                d.exact, d.layer_id = self._exact[i], self._layer_ids[i]
+        if self.compact:
+            live = [self._buf("live", b) for b in range(n + 1)]
+            self._maps = (_lib.CompactMap * n)()
+            for i in range(n):
+                m = self._maps[i]
+                m.rows, m.cols = live[i + 1].data_ptr(), live[i].data_ptr()
+                m.O_full, m.I_full = self.full_dims[i + 1], self.full_dims[i]
+        self._mcap, self._mw, self._mb, self._mptr = 0, [], [], None
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        if self._descs is not None:
+            self._point()                                    # .to() / .cuda() replaced the buffers the descriptors address
+        return out
+
+    def __deepcopy__(self, memo):
+        """A copy owns its buffers, so it gets descriptors of its own (ctypes arrays of addresses are not copied)."""
+        import copy
+        held = (self._descs, self._maps, self._mcap, self._mw, self._mb, self._mptr)
+        self._descs, self._maps, self._mcap, self._mw, self._mb, self._mptr = None, None, 0, [], [], None
+        try:
+            new = type(self).__new__(type(self))
+            memo[id(self)] = new
+            new.__dict__ = copy.deepcopy(self.__dict__, memo)
+        finally:
+            self._descs, self._maps, self._mcap, self._mw, self._mb, self._mptr = held
+        if held[0] is not None:
+            new._point()
+        return new
+
+    def _snapshot(self):
+        from . import _lib
+        net = self._src[0]
+        if net is None:
+            raise RuntimeError("bnn_amd: this FrozenBaseNetwork is not bound to a network; build it with evaluate.freeze_base(net)")
+        layers = net._layers()
+        _check_base_freezable(layers)
+        dev = self._buf("w_mu", 0).device
+        if layers[0].weight_mu.device != dev or not self._buf("w_mu", 0).is_cuda:
+            raise RuntimeError("bnn_amd: the source network (on %s) and this model (on %s) must share a HIP device; freeze it "
+                               "again" % (layers[0].weight_mu.device, dev))
+        self._layer_ids = [int(l._layer_id) for l in layers]
+        self._exact = [int(l._exact_bits()) for l in layers]
+        for i, l in enumerate(layers):
+            d = self._descs[i]
+            _base_sources(d, l, i)
+            d.exact, d.layer_id = self._exact[i], self._layer_ids[i]
+        mode = ops.GATES_MPM if self.gates == "mpm" else ops.GATES_SAMPLE
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            for k, cnt in _lib.layer_groups(self.n_layers):
+                maps = _lib.group_slice(self._maps, k, cnt) if self._maps is not None else None
+                _lib.check(_lib.lib().lbbnn_base_frozen_operands(_lib.group_slice(self._descs, k, cnt), maps, cnt, mode,
+                                                                 self.threshold, stream), "lbbnn_base_frozen_operands")
+        return self
+
+    @torch.no_grad()
+    def refresh(self):
+        """Take the snapshot again from the source network's current parameters, into the same buffers: one
+        lbbnn_base_frozen_operands launch per group of 4 layers.  A compact model cannot: its shapes follow the structure."""
+        if self.compact:
+            raise NotImplementedError("bnn_amd: a compact model does not refresh: the structure, and with it every shape, may "
+                                      "have changed with the parameters -- freeze again (evaluate.freeze_base(net, \"mpm\", "
+                                      "compact=True))")
+        return self._snapshot()
+
+    # ------------------------------------------------------------------------------------- evaluation
+    def _input(self, data):
+        from . import _lib
+        x = data.reshape(-1, self.full_dims[0])
+        if not x.is_cuda:
+            raise RuntimeError("bnn_amd: a frozen model evaluates on a HIP device tensor (data is on %s); there is no CPU path"
+                               % data.device)
+        dev = self._buf("w_mu", 0).device
+        if x.device != dev:
+            raise RuntimeError("bnn_amd: data is on %s, the frozen model on %s" % (x.device, dev))
+        x = x.float() if x.dtype != torch.float32 else x
+        if x.stride(1) != 1 or x.stride(0) < self.full_dims[0]:
+            x = x.contiguous()
+        B = x.shape[0]
+        if self._input_identity:
+            if self._split[0]:
+                # the bf16 hi | lo kernels read x rows as 16-B vectors through 32-bit offsets
+                if B * x.stride(0) * 4 >= 0x7FFFFFF0:
+                    raise ValueError("bnn_amd: a batch of %d rows exceeds the 2 GiB the 16-bit kernels address; split it" % B)
+                if x.stride(0) % 4 or x.data_ptr() % 16:
+                    x = x.clone(memory_format=torch.contiguous_format)
+            return x
+        n_idx = self.dims[0]
+        ldo = _pad4(n_idx)                                   # dense rows on 16-B boundaries
+        if self._split[0] and B * ldo * 4 >= 0x7FFFFFF0:
+            raise ValueError("bnn_amd: a batch of %d rows exceeds the 2 GiB the 16-bit kernels address; split it" % B)
+        out = _empty((B, ldo), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().lbbnn_gather_columns(x.data_ptr(), x.stride(0), self._buf("live", 0).data_ptr(), n_idx,
+                                                       out.data_ptr(), ldo, B, torch.cuda.current_stream(dev).cuda_stream),
+                       "lbbnn_gather_columns")
+        return out[:, :n_idx] if ldo != n_idx else out
+
+    def _member_buffers(self, c: int):
+        """Member weights [c][O'][ld'] and biases [c][O'] per layer and the pointer arrays of the members call; allocated for
+        the largest chunk seen, smaller chunks use a prefix."""
+        from . import _lib
+        if c > self._mcap:
+            f = dict(dtype=torch.float32, device=self._buf("w_mu", 0).device)
+            n = self.n_layers
+            self._mw = [_empty((c, self.dims[i + 1], ops.operand_ld(self.dims[i])), **f) for i in range(n)]
+            self._mb = [_empty((c, self.dims[i + 1]), **f) for i in range(n)]
+            self._mptr = ((_lib.c_p * n)(*[t.data_ptr() for t in self._mw]), (_lib.c_p * n)(*[t.data_ptr() for t in self._mb]))
+            self._mcap = c
+        return self._mw, self._mb
+
+    def _gemms(self, x, c: int, ws, w_ms: bool, bs, out, stream, head_flags: bool = True):
+        """The chain of lbbnn_gemm_members_mean launches of ``c`` members (``_predict_members``'s): layer i multiplies with
+        ws[i] ([c][O'][ld'], or one [O'][ld'] operand when not ``w_ms``) and adds bs[i]; the last layer writes ``out``."""
+        from . import _lib
+        B, dev, n = x.shape[0], x.device, self.n_layers
+        sigmoid = self.head == "sigmoid"
+        h, h_ms, ldx = x, 0, x.stride(0)
+        for i in range(n):
+            O, I = self.dims[i + 1], self.dims[i]
+            ld = ops.operand_ld(I)
+            last = i == n - 1
+            o = out if last else _empty((c, _pad4(B * O)), dtype=torch.float32, device=dev)
+            flags = (ops.F_RELU if not last else (ops.F_LOG_SOFTMAX if O <= 16 and not sigmoid else 0)) | \
+                    (ops.F_SPLIT16 if self._split[i] else 0)
+            rc = _lib.lib().lbbnn_gemm_members_mean(h.data_ptr(), ldx, h_ms, ws[i].data_ptr(), O * ld if w_ms else 0, ld,
+                                                   bs[i].data_ptr(), O if w_ms else 0, o.data_ptr(), O, o.stride(0), B, I, O,
+                                                   flags, c, stream)
+            _lib.check(rc, "lbbnn_gemm_members_mean")
+            h, h_ms, ldx = o, o.stride(0), O
+        return h
+
+    def _chunk(self, x, c: int, st, head, kept):
+        """Members live .. live + c - 1 into head (c, pad4(B * classes)): ceil(n / 4) lbbnn_base_frozen_members launches, then
+        one GEMM launch per layer."""
+        from . import _lib, distributions
+        dev = x.device
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        mw, mb = self._member_buffers(c)
+        mode = ops.GATES_MPM if self.gates == "mpm" else ops.GATES_SAMPLE
+        T = float(distributions.TEMPER_PRIOR)
+        for k, cnt in _lib.layer_groups(self.n_layers):      # every group reads the same offset; advanced once below
+            maps = _lib.group_slice(self._maps, k, cnt) if self._maps is not None else None
+            rc = _lib.lib().lbbnn_base_frozen_members(_lib.group_slice(self._descs, k, cnt), maps, cnt, c, mode, T,
+                                                     _lib.group_slice(self._mptr[0], k, cnt), _lib.group_slice(self._mptr[1], k, cnt),
+                                                     None, st.t.data_ptr(), 1, stream)
+            _lib.check(rc, "lbbnn_base_frozen_members")
+        if kept is not None:
+            kept.append(([w[:c].clone() for w in mw], [b[:c].clone() for b in mb]))
+        self._gemms(x, c, mw, True, mb, head, stream)
+        st.advance(c)                                        # as c single forwards would have
+
+    def _finish(self, buf, S: int, B: int, log_probs: bool):
+        C = self.dims[-1]
+        if self.head == "sigmoid":
+            return _binary_members(buf, S, B, C, log_probs)
+        outputs = buf[:, :B * C].view(S, B, C)
+        return outputs if C <= 16 else torch.log_softmax(outputs, dim=-1)
+
+    @torch.no_grad()
+    def ensemble(self, data: torch.Tensor, samples: int = 10, *, max_members: Optional[int] = None, log_probs: bool = False,
+                 keep_weights: bool = False) -> torch.Tensor:
+        """(samples, B, classes) log-probabilities of ``samples`` members.  Member m draws at Philox offset live + m with the
+        streams and counters of ``base_ensemble``: a full model returns ``base_ensemble(net, data, samples,
+        gates=self.gates)["outputs"]`` from the same offset, bit for bit.  The live offset advances by ``samples``.
+        ``max_members``: members per launch (default: all); chunked and unchunked results are the same bits.  The member
+        buffers are kept for the largest chunk seen, and nothing here reads the device.  ``keep_weights``:
+        ``self.last_weights`` / ``self.last_biases`` = per layer the (samples, O', ld') operands as the GEMMs read them (fp32
+        rows with a zero tail; under a 16-bit precision the raw bf16 hi | lo rows of a layer the split kernels take) and the
+        (samples, O') biases.  A model with ``head == "sigmoid"``: (samples, B, units) probabilities, or with ``log_probs``
+        (one unit) the (samples, B, 2) log-probabilities of the two classes."""
+        _check_log_probs(self, log_probs)
+        S = int(samples)
+        if S < 1:
+            raise ValueError("bnn_amd: samples must be >= 1")
+        chunk = S if max_members is None else int(max_members)
+        if chunk < 1:
+            raise ValueError("bnn_amd: max_members must be >= 1")
+        x = self._input(data)
+        B, C, dev = x.shape[0], self.dims[-1], x.device
+        st = ops.RngState.get(dev)
+        self.last_weights = self.last_biases = None
+        kept = [] if keep_weights else None
+        with torch.cuda.device(dev):
+            if B == 0:
+                st.advance(S)
+                return torch.zeros((S, 0, 2 if log_probs else C), dtype=torch.float32, device=dev)
+            head = _empty((S, _pad4(B * C)), dtype=torch.float32, device=dev)
+            for m0 in range(0, S, chunk):
+                c = min(chunk, S - m0)
+                self._chunk(x, c, st, head[m0:m0 + c], kept)
+        if kept is not None:
+            self.last_weights = [torch.cat(p) for p in zip(*[k[0] for k in kept])]
+            self.last_biases = [torch.cat(p) for p in zip(*[k[1] for k in kept])]
+        return self._finish(head, S, B, log_probs)
+
+    @torch.no_grad()
+    def forward(self, data: torch.Tensor, sample: bool = False, *, log_probs: bool = False) -> torch.Tensor:
+        """(B, classes) log-probabilities.  ``sample=True``: member 0 of ``ensemble(data, 1)``.  ``sample=False``: the
+        posterior-mean forward x . e_w^T + b_mu -- weight = alpha * mu (``gates="sample"``: the mode-2 branch,
+        LBBNN-GP-MF.py:413) or the medimean's mu * [alpha > threshold] (``gates="mpm"``, :236-238); it draws nothing.  A
+        sigmoid head: (B, units) probabilities, or with ``log_probs`` (one unit) the (B, 2) log-probabilities."""
+        _check_log_probs(self, log_probs)
+        if sample:
+            return self.ensemble(data, 1, log_probs=log_probs)[0]
+        x = self._input(data)
+        B, C, dev, n = x.shape[0], self.dims[-1], x.device, self.n_layers
+        if B == 0:
+            return torch.zeros((0, 2 if log_probs else C), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            out = _empty((1, _pad4(B * C)), dtype=torch.float32, device=dev)
+            self._gemms(x, 1, [self._buf("e_w", i) for i in range(n)], False, [self._buf("b_mu", i) for i in range(n)], out,
+                        torch.cuda.current_stream(dev).cuda_stream)
+        return self._finish(out, 1, B, log_probs)[0]
+
+
+def _base_sources(d, l, i: int):
+    """The source pointers of descriptor ``d`` from baseline layer ``l`` (layer i, for the messages)."""
+    for name in ("weight_mu", "weight_rho", "lambdal", "bias_mu", "bias_rho"):
+        if not getattr(l, name).is_contiguous():
+            raise RuntimeError("bnn_amd: %s of layer %d is not contiguous" % (name, i + 1))
+    d.mu, d.rho, d.lambdal = l.weight_mu.data_ptr(), l.weight_rho.data_ptr(), l.lambdal.data_ptr()
+    d.bias_mu, d.bias_rho = l.bias_mu.data_ptr(), l.bias_rho.data_ptr()
+
+
+def _check_base_freezable(layers):
+    for i, l in enumerate(layers):
+        if l.noise:
+            raise ValueError("bnn_amd: layer %d has injected noise (layer.noise); a frozen model draws in-kernel noise only -- "
+                             "clear layer.noise first" % (i + 1))
+        if ops.operand_ld(l.in_features) > ops.GATE_MEMBERS_MAX_LD:
+            raise ValueError("bnn_amd: layer %d: in_features = %d gives operand rows wider than the member kernels take "
+                             "(operand_ld(in_features) <= %d); evaluate this network with base_ensemble(net, data, samples)"
+                             % (i + 1, l.in_features, ops.GATE_MEMBERS_MAX_LD))
+
+
+def _base_keep_masks(layers, threshold: float):
+    """Per layer the (O, I) bool mask alpha > threshold as lbbnn_base_frozen_operands compares it (a call with the keep planes
+    as its only outputs): the kernel's own fp32 sigmoid and comparison, never a host-side restatement of them."""
+    from . import _lib
+    dev = layers[0].weight_mu.device
+    n = len(layers)
+    descs = (_lib.BaseFrozenDesc * n)()
+    planes = []
+    for i, l in enumerate(layers):
+        d = descs[i]
+        _base_sources(d, l, i)
+        d.O, d.I = l.out_features, l.in_features
+        d.ld = ops.operand_ld(d.I)
+        planes.append(_empty((d.O, d.I), dtype=torch.uint8, device=dev))
+        d.keep = planes[-1].data_ptr()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        for k, cnt in _lib.layer_groups(n):
+            _lib.check(_lib.lib().lbbnn_base_frozen_operands(_lib.group_slice(descs, k, cnt), None, cnt, ops.GATES_MPM,
+                                                             threshold, stream), "lbbnn_base_frozen_operands")
+    return [p.bool() for p in planes]
+
+
+def freeze_base(net, gates: str = "sample", *, threshold: float = 0.5, compact: bool = False) -> FrozenBaseNetwork:
+    """Frozen evaluation model of a baseline LBBNN network (``base.BayesianNetwork``) on a HIP device.
+
+    ``gates="sample"``: every member draws its gates as trained (the hard draw when ``gamma.exact`` is set, else the relaxed
+    gate) -- ``frozen.ensemble(x, S)`` is ``base_ensemble(net, x, S)["outputs"]`` from the same Philox offset, bit for bit, and
+    ``frozen(x)`` the posterior mean (weight = alpha * mu).  ``gates="mpm"``: the median probability model of
+    ``outofsample(net, medimod=True)`` (LBBNN-GP-MF.py:450-502): a weight is kept iff sigmoid(lambdal) > threshold, compared in
+    fp32 by the kernel; at the default 0.5 that is ``base_ensemble(..., gates="mpm")``, bit for bit, and ``frozen(x)`` is the
+    medimean forward.  The operand format is the precision in force at this moment.
+
+    ``compact=True`` (with ``gates="mpm"``): the model without the hidden units and input features no output depends on
+    (``live_structure`` of the kernel's own keep masks); its members' weights are the full model's, bit for bit, at the rows
+    and columns that stay, its outputs equal the full model's to fp32 rounding.  The one device read that sizes its buffers
+    happens here.  Refused, each with a ValueError / TypeError that names the cause: a network that is not a
+    ``base.BayesianNetwork``, unknown ``gates``, a threshold outside (0, 1), ``compact=True`` with ``gates="sample"``, a layer
+    with injected ``noise``, a layer wider than ``ops.GATE_MEMBERS_MAX_LD`` operand columns, a network on the CPU."""
+    if not _is_base(net):
+        raise TypeError("bnn_amd: freeze_base takes a baseline LBBNN network (bnn_amd.base.BayesianNetwork), got %s; an LRT / "
+                        "MNF network has evaluate.freeze" % type(net).__name__)
+    if gates not in BASE_FROZEN_GATES:
+        raise ValueError("bnn_amd: gates must be 'sample' (the gates drawn as trained) or 'mpm' (the median probability model), "
+                         "got %r" % (gates,))
+    threshold = float(threshold)
+    if not 0.0 < threshold < 1.0:
+        raise ValueError("bnn_amd: threshold must lie strictly between 0 and 1 (0.5 = the median probability model), got %r"
+                         % (threshold,))
+    if compact and gates != "mpm":
+        raise ValueError("bnn_amd: compact=True needs gates=\"mpm\": sampled gates are never fixed at zero, so no unit can be "
+                         "dropped -- use freeze_base(net, \"mpm\", compact=True), or freeze_base(net) for the gates as trained")
+    layers = net._layers()
+    _check_base_freezable(layers)
+    dev = layers[0].weight_mu.device
+    if not layers[0].weight_mu.is_cuda:
+        raise ValueError("bnn_amd: freeze_base needs the network on a HIP device (it is on %s); there is no CPU path" % dev)
+    live = needed = need = masks = None
+    if compact:
+        masks = _base_keep_masks(layers, threshold)
+        need, live, needed = _live_structure(masks, 8)       # the ONE device read: the live counts size every buffer
+    fz = FrozenBaseNetwork(net.dims, gates, threshold, device=dev, head=net.head, live=live, needed=needed)
+    fz.eval()
+    return fz._bind(net, need, masks)

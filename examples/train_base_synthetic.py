@@ -111,3 +111,16 @@ for gates in ("sample", "mpm"):
           % (tot["rows"], gates, tot["accuracy_ensemble"], tot["accuracy_posterior_mean"],
              tot["correct_member"].min() / tot["rows_with_target"], tot["correct_member"].max() / tot["rows_with_target"],
              tot["nll_mean"], tot["entropy_mean"]))
+
+# The sparse network the method exists to produce: the median probability model frozen once, without the units no output depends
+# on (evaluate.freeze_base(net, "mpm", compact=True)), and the same test pass as replays of ONE HIP graph per batch.
+fz = bnn_amd.evaluate.freeze_base(net, "mpm", compact=True)
+acc = bnn_amd.evaluate.EvalAccumulator(10, 10, DEVICE)
+eval_step = bnn_amd.graphs.make_graphed_eval_step(fz, test_batches[0][0], test_batches[0][1], 10, acc)
+for bx, by in test_batches:
+    eval_step(bx, by)
+tot = acc.result()
+print("compact median probability model %s of %s: density %.3f, active density %.3f; graphed test pass over %d rows: ensemble "
+      "%.3f | posterior mean %.3f | nll %.3f"
+      % ("-".join(map(str, fz.dims)), "-".join(map(str, fz.full_dims)), fz.density, fz.active_density, tot["rows"],
+         tot["accuracy_ensemble"], tot["accuracy_posterior_mean"], tot["nll_mean"]))

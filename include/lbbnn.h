@@ -696,6 +696,71 @@ int lbbnn_frozen_members_compact(const lbbnn_frozen_desc_t* layers, const lbbnn_
 int lbbnn_gather_columns(const float* x, int ldx, const int32_t* idx, int n_idx, float* out, int ldo, int B, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Frozen evaluation model of a baseline LBBNN network (LBBNN-GP-MF.py:345-502: test_ensemble and outofsample): a snapshot of
+ * sigma = softplus(rho), alpha = sigmoid(lambdal) and the gated mean taken ONCE, from which every member is then drawn
+ * without reading the parameters, without drawing for weights the median probability model has pruned, and -- with a map --
+ * at the compact shape of the units some output depends on (evaluate.live_structure).
+ *
+ * lbbnn_base_frozen_operands: ONE launch for all n <= LBBNN_MAX_LAYERS layers.  layers[i].O / I / ld are the sizes O' / I' / ld'
+ *   of the planes; the sources address the full (O_full, I_full) arrays (without maps: O_full = O', I_full = I').  Element
+ *   (o', j') comes from (rows[o'], cols[j']) of the sources, the identity without maps.  sigma and alpha are formed by the
+ *   device functions of lbbnn_gate_members (bitwise its values); keep = alpha > threshold in fp32 (NaN is never kept; at 0.5
+ *   this is the c of LBBNN_GATES_MPM).  Outputs, each nullable, at least one per layer (LBBNN_E_NULL otherwise):
+ *     mode = LBBNN_GATES_SAMPLE: w_mu = mu, w_sigma = sigma, e_w = operand(alpha * mu)    (the mode-2 mean, :236-238)
+ *     mode = LBBNN_GATES_MPM:    w_mu = keep ? mu : +0.0, w_sigma = keep ? sigma : +0.0, e_w = operand(w_mu)  (medimean)
+ *     either mode: alpha; alpha_rows[o'] = sum_j' alpha (per lane in column order, then the fixed-order wave sum: bitwise
+ *     reproducible); kept_rows[o'] = sum_j' keep; b_mu = bias_mu[rows[o']]; b_sigma = softplus(bias_rho[rows[o']]);
+ *     keep [O_full][I_full] uint8 in {0, 1}, rows of I_full bytes, without maps only (LBBNN_E_FLAGS with one).
+ *   w_mu, w_sigma and alpha are plain fp32 [O'][ld']; e_w is fp32 or, with LBBNN_F_SPLIT16 in flags, the split bf16 hi|lo
+ *   layout; every tail [I', ld') is written as zeros.  lbbnn_base_frozen_members reads alpha in SAMPLE mode only.
+ *   Checks, before any launch: layers NULL, a source NULL, a map's rows / cols NULL: LBBNN_E_NULL; n outside 1 ..
+ *   LBBNN_MAX_LAYERS, O' / I' < 1, ld' < I' or > 4096, O' > O_full, I' > I_full: LBBNN_E_SHAPE; ld' % 32, a plane off a 16-B
+ *   boundary, any other pointer but keep off a 4-B boundary: LBBNN_E_ALIGN; an unknown mode, flags other than 0 |
+ *   LBBNN_F_SPLIT16, maps with LBBNN_GATES_SAMPLE (alpha gates are never exactly zero: nothing to drop), a threshold outside
+ *   (0, 1): LBBNN_E_FLAGS.
+ *
+ * lbbnn_base_frozen_members: every member's weights and biases of all n layers in ONE launch, from the snapshot planes.
+ *   Member m draws from {rng[0], rng[1] + m * member_advance} with the streams and counters of lbbnn_gate_members, ALWAYS at
+ *   the full coordinates: eps_w and the gate uniform of compact element (o', j') at counter (rows[o'], cols[j'] / 4), lane
+ *   cols[j'] % 4 of streams EPS_W / GATE * 64 + layer_id; eps_b at counter (rows[o'] / 4, 0), lane rows[o'] % 4 of EPS_B * 64
+ *   + layer_id.  One Philox evaluation serves every column of a lane's group that lies in the same quad of the full row.
+ *     mode = LBBNN_GATES_SAMPLE: w = c * (w_mu + w_sigma * eps_w), c drawn from alpha as lbbnn_gate_members draws it (the
+ *             hard draw u < alpha when exact & 8, else the relaxed gate at `temperature` > 0);
+ *     mode = LBBNN_GATES_MPM:    w = w_mu + w_sigma * eps_w; a group of columns whose w_mu and w_sigma are all zero draws
+ *             nothing and is stored as zeros;
+ *     bias = b_mu + b_sigma * eps_b.
+ *   A full model's members are bitwise those of lbbnn_gate_members from the same state (it stores -0.0 for some pruned
+ *   weights where this call stores +0.0); a compact model's member weight (o', j') is bitwise the full model's at (rows[o'],
+ *   cols[j']).  w_out[i]: [members][O'][ld'] fp32, or the split bf16 hi|lo layout with LBBNN_F_SPLIT16 in layers[i].flags,
+ *   zero tails, 16-B aligned; bias_out[i]: [members][O']; gate_rows: NULL, or n pointers, each NULL or [members][O'] = sum_j'
+ *   c (SAMPLE mode; groups of eight columns in order, each summed over the wave in a fixed order).
+ *   Checks, before any launch: those of the shapes and maps above; layers / w_out / bias_out or one of their entries, b_mu,
+ *   b_sigma, w_mu, w_sigma, and alpha in SAMPLE mode NULL: LBBNN_E_NULL; members outside 1 .. 65535: LBBNN_E_SHAPE; maps or
+ *   gate_rows with LBBNN_GATES_SAMPLE / LBBNN_GATES_MPM respectively, temperature <= 0 in SAMPLE mode: LBBNN_E_FLAGS; rng
+ *   NULL: LBBNN_E_NOISE.  The caller advances rng afterwards. */
+typedef struct lbbnn_base_frozen_desc {
+    const float *mu, *rho, *lambdal;          /* (O_full, I_full) sources: lbbnn_base_frozen_operands only */
+    const float *bias_mu, *bias_rho;          /* (O_full) */
+    float *w_mu, *w_sigma;                    /* [O'][ld'] fp32 planes */
+    float* alpha;                             /* [O'][ld'] */
+    void* e_w;                                /* [O'][ld'] GEMM operand of the posterior mean (format by flags) */
+    float *b_mu, *b_sigma;                    /* [O'] */
+    int32_t* kept_rows;                       /* [O'] */
+    float* alpha_rows;                        /* [O'] */
+    uint8_t* keep;                            /* [O_full][I_full], without maps only */
+    int O, I, ld;                             /* O', I', ld' */
+    int flags;                                /* 0 | LBBNN_F_SPLIT16: e_w, and w_out of lbbnn_base_frozen_members */
+    int exact;                                /* the layer's exact bits (8 = hard gates) */
+    uint32_t layer_id;
+} lbbnn_base_frozen_desc_t;
+
+int lbbnn_base_frozen_operands(const lbbnn_base_frozen_desc_t* layers, const lbbnn_compact_map_t* maps, int n, int mode,
+                               float threshold, void* stream);
+int lbbnn_base_frozen_members(const lbbnn_base_frozen_desc_t* layers, const lbbnn_compact_map_t* maps, int n, int members,
+                              int mode, float temperature, void* w_out[], float* bias_out[], float* gate_rows[],
+                              const uint64_t* rng, uint64_t member_advance, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K7  lbbnn_vd_operands -- Gaussian variational-dropout layer (variational_dropout.py:55-68).
  *   phi = x.theta ; delta = (x^2).(theta^2) * alpha ; out = phi + sqrt(delta)*zeta        :64-67
  * theta is (I,O) row-major (NN layout).  This pass writes the GEMM operands theta^T and (theta^2)^T as
