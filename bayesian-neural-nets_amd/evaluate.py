@@ -921,14 +921,223 @@ def _empty(*size, **kw):
 
 
 def _is_frozen(net) -> bool:
-    return isinstance(net, (FrozenNetwork, FrozenBaseNetwork))
+    return isinstance(net, _FrozenModel)
 
 
 def _pad4(n: int) -> int:
     return -(-n // 4) * 4
 
 
-class FrozenNetwork(nn.Module):
+def _cut(threshold) -> float:
+    """logit(threshold) as the fp32 value the kernels compare lambdal with (exactly 0 at 0.5); refuses a threshold outside
+    (0, 1)."""
+    if not 0.0 < float(threshold) < 1.0:
+        raise ValueError("bnn_amd: threshold must lie strictly between 0 and 1 (0.5 = the median probability model), got %r"
+                         % (threshold,))
+    return float(torch.tensor(math.log(threshold / (1.0 - threshold)), dtype=torch.float32))
+
+
+class _FrozenModel(nn.Module):
+    """What every frozen evaluation model is, whichever family it froze: the checked arguments, the shapes (``full_dims`` the
+    network's widths, ``dims`` this model's -- the compact widths when ``live`` is given), the statistics read from
+    ``kept_rows``, the compact bookkeeping, the input rows as the first GEMM reads them, the head over the members' buffer,
+    and the lifetime of cached device addresses.
+
+    A subclass sets ``GATES`` / ``GATES_DOC`` (the gates it takes, and how the refusal words them), ``FREEZE`` (the function
+    that builds it), ``_POINTER_STATE`` (the attributes that hold, or follow, device addresses of its buffers) and answers
+    ``_device()`` and ``_point()``: ``_point`` builds every long-lived array of addresses from the buffers as they are now and
+    drops the cached member buffers; it is the ONE place that does, called when the buffers are made, after ``nn.Module._apply``
+    replaced them (``.to()``, ``.float()``, ``.double()``), and on a deep copy."""
+    GATES, GATES_DOC, FREEZE = (), "", ""
+    _POINTER_STATE = ()
+
+    def __init__(self, full_dims, gates: str, threshold: float, device, head: str, live=None, needed=None):
+        super().__init__()
+        if head not in ("log_softmax", "sigmoid"):
+            raise ValueError("bnn_amd: head must be 'log_softmax' or 'sigmoid', got %r" % (head,))
+        self._check_gates(gates)
+        threshold = float(threshold)
+        self.cut = _cut(threshold)
+        self.full_dims = tuple(int(d) for d in full_dims)
+        self.compact = live is not None
+        if self.compact:
+            if gates != "mpm":
+                raise ValueError("bnn_amd: a compact model needs gates=\"mpm\"")
+            if len(live) != len(self.full_dims) or len(needed) != len(self.full_dims):
+                raise ValueError("bnn_amd: a network of %d layers has %d boundaries" % (len(self.full_dims) - 1, len(self.full_dims)))
+            self.dims = tuple(int(t.numel()) for t in live)
+            self.needed = [int(c) for c in needed]
+            for b, t in enumerate(live):
+                self.register_buffer("live_%d" % b, t.to(device=device, dtype=torch.int32).contiguous())
+        else:
+            self.dims = self.full_dims
+        if head == "sigmoid" and self.dims[-1] > 16:
+            raise ValueError("bnn_amd: a sigmoid head takes at most 16 output units, got dims[-1] = %d" % self.dims[-1])
+        # head: carried over from the network: "sigmoid" -> probabilities (or, log_probs=True, 2 classes)
+        self.head, self.gates, self.threshold = head, gates, threshold
+        self._src = [None]              # the source network, in a list so that it is not registered as a submodule
+        self._split, self._layer_ids = [], []
+        self._input_identity = self.dims[0] == self.full_dims[0]     # sorted, unique, full width: every feature in place
+        self._maps = None
+        self._active = self._full_kept = None
+        for i in range(len(self.dims) - 1):
+            self.register_buffer("kept_rows_%d" % i, torch.zeros(self.dims[i + 1], dtype=torch.int32, device=device))
+
+    @classmethod
+    def _check_gates(cls, gates):
+        if gates not in cls.GATES:
+            raise ValueError("bnn_amd: gates must be %s, got %r" % (cls.GATES_DOC, gates))
+
+    # ------------------------------------------------------------------------------------- statistics
+    @property
+    def n_layers(self) -> int:
+        return len(self.dims) - 1
+
+    def _buf(self, name: str, i: int) -> torch.Tensor:
+        return getattr(self, "%s_%d" % (name, i))
+
+    def _n_weights(self) -> int:
+        return sum(self.full_dims[i] * self.full_dims[i + 1] for i in range(self.n_layers))
+
+    @property
+    def kept_rows(self) -> List[torch.Tensor]:
+        """Per layer (O',) int32: weights of each output row past the threshold (lambdal > logit(threshold), that is alpha >
+        threshold), in either gates mode; a compact model: among the live columns."""
+        return [self._buf("kept_rows", i) for i in range(self.n_layers)]
+
+    @property
+    def kept(self) -> List[int]:
+        return [int(k.sum()) for k in self.kept_rows]
+
+    @property
+    def density(self) -> float:
+        """Kept weights / all weights over every layer of the FULL network -- the density the thesis reports for the median
+        probability model (a compact model reports what its full model does)."""
+        return (int(self._full_kept) if self.compact else sum(self.kept)) / self._n_weights()
+
+    @property
+    def live(self) -> List[torch.Tensor]:
+        self._need_compact("live")
+        return [self._buf("live", b) for b in range(len(self.dims))]
+
+    @property
+    def active_kept(self) -> int:
+        """Kept weights whose row and column are both needed (over every layer); a compact model only."""
+        self._need_compact("active_kept")
+        return int(self._active)
+
+    @property
+    def active_density(self) -> float:
+        return self.active_kept / self._n_weights()
+
+    def _need_compact(self, what: str):
+        if not self.compact:
+            raise RuntimeError("bnn_amd: %s belongs to a compact model (%s(net, \"mpm\", compact=True))" % (what, self.FREEZE))
+
+    # ------------------------------------------------------------------------------------- compact bookkeeping
+    def _count_kept(self, need, masks):
+        """``density`` and ``active_kept`` of a compact model from the full network's keep masks and ``live_structure``'s
+        ``need``, as device scalars: they are read when asked for, not here."""
+        self._full_kept = torch.stack([k.sum() for k in masks]).sum()
+        self._active = torch.stack([(k & need[i + 1][:, None] & need[i][None, :]).sum() for i, k in enumerate(masks)]).sum()
+
+    def _compact_maps(self):
+        """lbbnn_compact_map_t of every layer of a compact model, addressing its ``live_<b>`` buffers; None for a full one."""
+        if not self.compact:
+            return None
+        from . import _lib
+        maps = (_lib.CompactMap * self.n_layers)()
+        for i, m in enumerate(maps):
+            m.rows, m.cols = self._buf("live", i + 1).data_ptr(), self._buf("live", i).data_ptr()
+            m.O_full, m.I_full = self.full_dims[i + 1], self.full_dims[i]
+        return maps
+
+    # ------------------------------------------------------------------------------------- cached device addresses
+    def _device(self):
+        raise NotImplementedError
+
+    def _point(self):
+        raise NotImplementedError
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        if self._src[0] is not None:
+            self._point()                                    # .to() / .float() replaced the buffers the arrays address
+        return out
+
+    def __deepcopy__(self, memo):
+        """A copy owns its buffers, so it gets arrays of its own (ctypes arrays of addresses are not copied)."""
+        import copy
+        bound = self._src[0] is not None
+        held = dict((k, self.__dict__.pop(k)) for k in self._POINTER_STATE) if bound else {}
+        try:
+            new = type(self).__new__(type(self))
+            memo[id(self)] = new
+            new.__dict__ = copy.deepcopy(self.__dict__, memo)
+        finally:
+            self.__dict__.update(held)
+        if bound:
+            new._point()
+        return new
+
+    # ------------------------------------------------------------------------------------- evaluation
+    def _input(self, data):
+        """``data`` as the (B, dims[0]) fp32 rows the first GEMM reads: the tensor itself when every input feature is live
+        (``_input_identity``) and it already has that form, else the live columns, gathered by ONE launch."""
+        width = self.full_dims[0]
+        x = data.reshape(-1, width)
+        if not x.is_cuda:
+            raise RuntimeError("bnn_amd: a frozen model evaluates on a HIP device tensor (data is on %s); there is no CPU path"
+                               % data.device)
+        dev = self._device()
+        if x.device != dev:
+            raise RuntimeError("bnn_amd: data is on %s, the frozen model on %s" % (x.device, dev))
+        x = x.float() if x.dtype != torch.float32 else x
+        if x.stride(1) != 1 or x.stride(0) < width:
+            x = x.contiguous()
+        B = x.shape[0]
+        if self._input_identity:
+            if self._split[0]:
+                # the bf16 hi | lo kernels read x rows as 16-B vectors through 32-bit offsets
+                if B * x.stride(0) * 4 >= 0x7FFFFFF0:
+                    raise ValueError("bnn_amd: a batch of %d rows exceeds the 2 GiB the 16-bit kernels address; split it" % B)
+                if x.stride(0) % 4 or x.data_ptr() % 16:
+                    x = x.clone(memory_format=torch.contiguous_format)
+            return x
+        from . import _lib
+        n_idx = self.dims[0]
+        ldo = _pad4(n_idx)                                   # dense rows on 16-B boundaries: what the bf16 hi | lo kernels read
+        if self._split[0] and B * ldo * 4 >= 0x7FFFFFF0:
+            raise ValueError("bnn_amd: a batch of %d rows exceeds the 2 GiB the 16-bit kernels address; split it" % B)
+        out = _empty((B, ldo), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().lbbnn_gather_columns(x.data_ptr(), x.stride(0), self._buf("live", 0).data_ptr(), n_idx,
+                                                       out.data_ptr(), ldo, B, torch.cuda.current_stream(dev).cuda_stream),
+                       "lbbnn_gather_columns")
+        return out[:, :n_idx] if ldo != n_idx else out
+
+    @staticmethod
+    def _member_counts(samples, max_members):
+        """(S, chunk) of an ``ensemble`` call: the members, and how many of them one launch takes (default: all)."""
+        S = int(samples)
+        if S < 1:
+            raise ValueError("bnn_amd: samples must be >= 1")
+        chunk = S if max_members is None else int(max_members)
+        if chunk < 1:
+            raise ValueError("bnn_amd: max_members must be >= 1")
+        return S, chunk
+
+    def _finish(self, buf, S: int, B: int, log_probs: bool):
+        """The (S, pad4(B * C)) buffer the last member GEMM wrote as the (S, B, C) result: the sigmoid head's one launch, a
+        view where the GEMM applied log_softmax itself (C <= 16), torch's log_softmax otherwise."""
+        C = self.dims[-1]
+        if self.head == "sigmoid":
+            return _binary_members(buf, S, B, C, log_probs)
+        outputs = buf[:, :B * C].view(S, B, C)
+        return outputs if C <= 16 else torch.log_softmax(outputs, dim=-1)
+
+
+class FrozenNetwork(_FrozenModel):
     """A trained LRT / MNF network frozen for evaluation (built by ``freeze``; no parameters, buffers only).
 
     Per layer it holds ``e0`` = weight_mu * a as plain fp32 rows, the GEMM operands ``e_w`` (of e0) and ``var_w`` (of
@@ -941,65 +1150,34 @@ class FrozenNetwork(nn.Module):
     forward) or the indicator of ``lambdal > logit(threshold)`` (``gates="mpm"``: the median probability model at the default
     threshold 0.5); the bias and z are never gated.  Nothing here follows the source network's parameters until ``refresh()``.
     """
+    GATES, FREEZE = FROZEN_GATES, "freeze"
+    GATES_DOC = "'alpha' (the gates as trained) or 'mpm' (the median probability model)"
+    _POINTER_STATE = ("_zt", "_maps", "_mcap", "_zbuf", "_ewm")
 
     def __init__(self, dims, family: str = "lrt", gates: str = "alpha", threshold: float = 0.5, device=None,
                  flows: Optional[str] = None, head: str = "log_softmax"):
-        super().__init__()
-        if head not in ("log_softmax", "sigmoid"):
-            raise ValueError("bnn_amd: head must be 'log_softmax' or 'sigmoid', got %r" % (head,))
-        if head == "sigmoid" and int(dims[-1]) > 16:
-            raise ValueError("bnn_amd: a sigmoid head takes at most 16 output units, got dims[-1] = %d" % int(dims[-1]))
-        self.head = head                # carried over from the network: "sigmoid" -> probabilities (or, log_probs=True, 2 classes)
-        if gates not in FROZEN_GATES:
-            raise ValueError("bnn_amd: gates must be 'alpha' (the gates as trained) or 'mpm' (the median probability model), "
-                             "got %r" % (gates,))
-        threshold = float(threshold)
-        if not 0.0 < threshold < 1.0:
-            raise ValueError("bnn_amd: threshold must lie strictly between 0 and 1 (0.5 = the median probability model), got %r"
-                             % (threshold,))
+        super().__init__(dims, gates, threshold, device, head)
+        self._init_family(family, flows)
+
+    def _init_family(self, family, flows):
         if family not in ("lrt", "mnf"):
             raise ValueError("bnn_amd: family must be 'lrt' or 'mnf', got %r" % (family,))
         flows = ("planar" if family == "mnf" else None) if flows is None else flows
         if flows not in ((None,) if family == "lrt" else ("planar", "dense")):
             raise ValueError("bnn_amd: flows must be 'planar' or 'dense' for an MNF model and None for an LRT model, got %r"
                              % (flows,))
-        self.dims = tuple(int(d) for d in dims)
-        self.family, self.gates, self.threshold = family, gates, threshold
+        self.family = family
         self.flows = flows              # the z flow family of an MNF model: "planar" | "dense" (RNVP / MNF type); LRT: None
-        # logit(threshold) as the fp32 value the kernel compares lambdal with (exactly 0 at 0.5)
-        self.cut = float(torch.tensor(math.log(threshold / (1.0 - threshold)), dtype=torch.float32))
         self.last_z = None
         self.last_masks = None
-        self._zt, self._zflow_names = [], []   # dense flows: per layer the lbbnn_dense_transform_t array / the parameter names
-        self._src = [None]              # the source network, in a list so that it is not registered as a submodule
-        self._split, self._layer_ids, self._row_offsets, self._T = [], [], [], []
+        # dense flows, per layer: the parameter names and the kind of the coupling networks / the lbbnn_dense_transform_t array
+        self._zflow_names, self._zflow_kinds, self._zt = [], [], []
+        self._row_offsets, self._T = [], []
         self._members_ok = True
         self._mcap, self._zbuf, self._ewm = 0, None, []
-        for i in range(len(self.dims) - 1):
-            self.register_buffer("kept_rows_%d" % i, torch.zeros(self.dims[i + 1], dtype=torch.int32, device=device))
 
-    # ------------------------------------------------------------------------------------- statistics
-    @property
-    def n_layers(self) -> int:
-        return len(self.dims) - 1
-
-    def _buf(self, name: str, i: int) -> torch.Tensor:
-        return getattr(self, "%s_%d" % (name, i))
-
-    @property
-    def kept_rows(self) -> List[torch.Tensor]:
-        """Per layer (O,) int32: weights of each output row with lambdal > logit(threshold) (in either gates mode)."""
-        return [self._buf("kept_rows", i) for i in range(self.n_layers)]
-
-    @property
-    def kept(self) -> List[int]:
-        return [int(k.sum()) for k in self.kept_rows]
-
-    @property
-    def density(self) -> float:
-        """Kept weights / all weights over every layer -- the density the thesis reports for the median probability model."""
-        total = sum(self.dims[i] * self.dims[i + 1] for i in range(self.n_layers))
-        return sum(self.kept) / total
+    def _device(self):
+        return self._buf("e0", 0).device
 
     def extra_repr(self) -> str:
         flows = ", flows=%s" % self.flows if self.flows else ""
@@ -1007,18 +1185,22 @@ class FrozenNetwork(nn.Module):
         return "dims=%s, family=%s%s, gates=%s, threshold=%g%s" % (self.dims, self.family, flows, self.gates, self.threshold, head)
 
     # ------------------------------------------------------------------------------------- snapshot
-    def _bind(self, net):
-        """Allocate every buffer for ``net``'s layers (once) and take the first snapshot."""
+    @torch.no_grad()
+    def _bind(self, net, need=None, masks=None):
+        """Allocate every buffer for ``net``'s layers (once), at this model's shapes -- z, q0 and the z flow of an MNF layer
+        at the network's widths: the flow runs there -- and take the first snapshot."""
         layers = net._layers()
-        dev = layers[0].weight_mu.device
-        f = dict(dtype=torch.float32, device=dev)
+        f = dict(dtype=torch.float32, device=layers[0].weight_mu.device)
         self._src = [net]
+        if masks is not None:
+            self._count_kept(need, masks)
         for i, l in enumerate(layers):
-            O, I = l.out_features, l.in_features
+            O, I, If = self.dims[i + 1], self.dims[i], self.full_dims[i]
             ld = ops.operand_ld(I)
-            # the operand format, by the rule of ensemble_forward_batched: any 16-bit precision -> bf16 hi | lo where the split
-            # kernels take the shape and the rows the previous layer writes stay 16-B aligned
-            self._split.append(bool(l._split(None)) and (i == 0 or layers[i - 1].out_features % 4 == 0))
+            # the operand format, by the rule of ensemble_forward_batched (layer._split without an input) at this model's
+            # shapes: any 16-bit precision -> bf16 hi | lo where the split kernels take the shape and the rows the previous
+            # layer writes stay 16-B aligned
+            self._split.append(bool(ops.split_precision(l)) and ops.split_eligible(I, O) and (i == 0 or I % 4 == 0))
             if I % 4 or ld > 2048:
                 self._members_ok = False
             for name, shape in (("e0", (O, ld)), ("e_w", (O, ld)), ("var_w", (O, ld)), ("bias_var", (O,)), ("bias_mu", (O,))):
@@ -1026,9 +1208,9 @@ class FrozenNetwork(nn.Module):
             if l._mnf:
                 T = len(l.z_flow.transforms)
                 self._T.append(T)
-                vecs = [("q0_mean", (I,)), ("q0_log_var", (I,))]
+                vecs = [("q0_mean", (If,)), ("q0_log_var", (If,))]
                 if self.flows == "planar":
-                    vecs += [("flow_u", (T, I)), ("flow_w", (T, I)), ("flow_b", (T, 1))]
+                    vecs += [("flow_u", (T, If)), ("flow_w", (T, If)), ("flow_b", (T, 1))]
                 for name, shape in vecs:
                     self.register_buffer("%s_%d" % (name, i), _empty(shape, **f))
                 if self.flows == "dense":
@@ -1038,19 +1220,28 @@ class FrozenNetwork(nn.Module):
                         for k, p in tr.named_parameters():
                             self.register_buffer(self._zflow_buf(i, t, k), _empty(tuple(p.shape), **f))
                     self._zflow_names.append(names)
-                    self._zt.append(self._dense_transforms(i, l.z_flow.kind))
+                    self._zflow_kinds.append(l.z_flow.kind)
             else:
                 self._T.append(0)
-        self.refresh()
-        return self
+        self._point()
+        return self._snapshot(layers)
+
+    def _point(self):
+        """The arrays that outlive a call: the transforms of dense z flows and the maps of a compact model, addressing this
+        model's buffers as they are now; the member buffers start over."""
+        self._zt = [self._dense_transforms(i, kind) for i, kind in enumerate(self._zflow_kinds)]
+        self._maps = self._compact_maps()
+        self._mcap, self._zbuf, self._ewm = 0, None, []
+
+    def _snapshot(self, layers):
+        return self.refresh()
 
     @staticmethod
     def _zflow_buf(i: int, t: int, name: str) -> str:
         return "zflow_%d_%d_%s" % (i, t, name.replace(".", "_"))
 
     def _dense_transforms(self, i: int, kind: str):
-        """lbbnn_dense_transform_t of every transform of layer i's z flow, pointing at this model's copies (built once: the
-        buffers never move)."""
+        """lbbnn_dense_transform_t of every transform of layer i's z flow, pointing at this model's copies."""
         from . import _lib
         from .flows import dense_hidden
         T = self._T[i]
@@ -1090,6 +1281,9 @@ class FrozenNetwork(nn.Module):
             d.bias_var, d.kept_rows = self._buf("bias_var", i).data_ptr(), self._buf("kept_rows", i).data_ptr()
             if src_layers is not None:
                 l = src_layers[i]
+                for name in ("weight_mu", "weight_rho", "lambdal"):
+                    if not getattr(l, name).is_contiguous():
+                        raise RuntimeError("bnn_amd: %s of layer %d is not contiguous" % (name, i + 1))
                 d.weight_mu, d.weight_rho, d.lambdal = l.weight_mu.data_ptr(), l.weight_rho.data_ptr(), l.lambdal.data_ptr()
                 d.bias_rho = l.bias_rho.data_ptr()
             if self.family == "mnf":
@@ -1100,6 +1294,24 @@ class FrozenNetwork(nn.Module):
                     for t in range(self._T[i]):
                         d.z_flow.u[t], d.z_flow.w[t], d.z_flow.b[t] = u[t].data_ptr(), w[t].data_ptr(), b[t].data_ptr()
         return descs
+
+    def _z_copies(self, layers):
+        """(dst, src) of the copies that snapshot q0 and the z flow of every MNF layer."""
+        dst, src = [], []
+        for i, l in enumerate(layers):
+            if not l._mnf:
+                continue
+            dst += [self._buf("q0_mean", i), self._buf("q0_log_var", i)]
+            src += [l.q0_mean.detach(), l.q0_log_var.detach()]
+            for t, tr in enumerate(l.z_flow.transforms):
+                if self.flows == "dense":
+                    ps = dict(tr.named_parameters())
+                    for k in self._zflow_names[i][t]:
+                        dst.append(getattr(self, self._zflow_buf(i, t, k))); src.append(ps[k].detach())
+                else:
+                    dst += [self._buf("flow_u", i)[t], self._buf("flow_w", i)[t], self._buf("flow_b", i)[t]]
+                    src += [tr.u.detach().reshape(-1), tr.w.detach().reshape(-1), tr.bias.detach().reshape(-1)]
+        return dst, src
 
     @torch.no_grad()
     def refresh(self):
@@ -1120,24 +1332,9 @@ class FrozenNetwork(nn.Module):
                                % (dev, layers[0].weight_mu.device))
         self._layer_ids = [int(l._layer_id) for l in layers]
         self._row_offsets = [int(l.row_offset) for l in layers]
-        dst, src = [], []
-        for i, l in enumerate(layers):
-            for name in ("weight_mu", "weight_rho", "lambdal"):
-                p = getattr(l, name)
-                if not p.is_contiguous():
-                    raise RuntimeError("bnn_amd: %s of layer %d is not contiguous" % (name, i + 1))
-            dst.append(self._buf("bias_mu", i)); src.append(l.bias_mu.detach())
-            if l._mnf:
-                dst += [self._buf("q0_mean", i), self._buf("q0_log_var", i)]
-                src += [l.q0_mean.detach(), l.q0_log_var.detach()]
-                for t, tr in enumerate(l.z_flow.transforms):
-                    if self.flows == "dense":
-                        ps = dict(tr.named_parameters())
-                        for k in self._zflow_names[i][t]:
-                            dst.append(getattr(self, self._zflow_buf(i, t, k))); src.append(ps[k].detach())
-                    else:
-                        dst += [self._buf("flow_u", i)[t], self._buf("flow_w", i)[t], self._buf("flow_b", i)[t]]
-                        src += [tr.u.detach().reshape(-1), tr.w.detach().reshape(-1), tr.bias.detach().reshape(-1)]
+        dst, src = self._z_copies(layers)
+        dst += [self._buf("bias_mu", i) for i in range(self.n_layers)]
+        src += [l.bias_mu.detach() for l in layers]
         torch._foreach_copy_(dst, src)                       # the small vectors of every layer in one fused copy
         descs = self._descs(layers)
         with torch.cuda.device(dev):
@@ -1147,40 +1344,22 @@ class FrozenNetwork(nn.Module):
         return self
 
     # ------------------------------------------------------------------------------------- evaluation
-    def _input(self, data):
-        x = data.reshape(-1, self.dims[0])
-        if not x.is_cuda:
-            raise RuntimeError("bnn_amd: a frozen model evaluates on a HIP device tensor (data is on %s); there is no CPU path"
-                               % data.device)
-        if x.device != self._buf("e0", 0).device:
-            raise RuntimeError("bnn_amd: data is on %s, the frozen model on %s" % (x.device, self._buf("e0", 0).device))
-        x = x.float() if x.dtype != torch.float32 else x
-        if x.stride(1) != 1 or x.stride(0) < self.dims[0]:
-            x = x.contiguous()
-        if self._split[0]:
-            # the bf16 hi | lo kernels read x rows as 16-B vectors through 32-bit offsets
-            if x.shape[0] * x.stride(0) * 4 >= 0x7FFFFFF0:
-                raise ValueError("bnn_amd: a batch of %d rows exceeds the 2 GiB the 16-bit kernels address; split it"
-                                 % x.shape[0])
-            if x.stride(0) % 4 or x.data_ptr() % 16:
-                x = x.clone(memory_format=torch.contiguous_format)
-        return x
-
     def _member_buffers(self, c: int):
-        """z [c][sum of ld] (every MNF layer's block side by side: one member stride, one flow launch) and the member mean
-        operands [c][O][ld] per layer; allocated for the largest chunk seen, smaller chunks use a prefix."""
+        """z [c][sum of ld] (every MNF layer's block side by side: one member stride, one flow launch; at the network's widths:
+        the flow runs there, and the scale launch of a compact model gathers) and the member mean operands [c][O][ld] per
+        layer at this model's shapes; allocated for the largest chunk seen, smaller chunks use a prefix."""
         if c > self._mcap:
-            dev = self._buf("e0", 0).device
-            f = dict(dtype=torch.float32, device=dev)
-            lds = [ops.operand_ld(self.dims[i]) for i in range(self.n_layers)]
-            self._zbuf = _empty((c, sum(lds)), **f)
-            self._ewm = [_empty((c, self.dims[i + 1], lds[i]), **f) for i in range(self.n_layers)]
+            f = dict(dtype=torch.float32, device=self._device())
+            self._zbuf = _empty((c, sum(ops.operand_ld(d) for d in self.full_dims[:-1])), **f)
+            self._ewm = [_empty((c, self.dims[i + 1], ops.operand_ld(self.dims[i])), **f) for i in range(self.n_layers)]
             self._mcap = c
         return self._zbuf, self._ewm
 
     def _draw_members(self, c: int, rng, stream, masks=None):
         """MNF: member m's z at Philox offset rng[1] + m and its mean operand E0 * z_m (lbbnn_frozen_members; dense flows:
-        lbbnn_frozen_members_dense, with ``masks`` a list that receives per layer the (c, T, I) masks the members used)."""
+        lbbnn_frozen_members_dense, with ``masks`` a list that receives per layer the (c, T, I) masks the members used; a
+        compact model: lbbnn_frozen_members_compact -- the flow launch of the full model at the full width, then one scale
+        launch with the gather z_m[cols] fused in)."""
         from . import _lib
         zbuf, ewm = self._member_buffers(c)
         descs = self._descs()
@@ -1189,7 +1368,7 @@ class FrozenNetwork(nn.Module):
             descs[i].z_fwd = zbuf.data_ptr() + 4 * off
             descs[i].z_mstride = zbuf.stride(0)
             descs[i].e_w_members = ewm[i].data_ptr()
-            off += ops.operand_ld(self.dims[i])
+            off += ops.operand_ld(self.full_dims[i])
         if self.flows == "dense":
             import ctypes
             fl = (_lib.DenseMembers * self.n_layers)()
@@ -1207,15 +1386,19 @@ class FrozenNetwork(nn.Module):
                                                                  c, rng.data_ptr(), 1, stream), "lbbnn_frozen_members_dense")
             return zbuf, ewm
         for k, cnt in _lib.layer_groups(self.n_layers):
-            _lib.check(_lib.lib().lbbnn_frozen_members(_lib.group_slice(descs, k, cnt), cnt, c, rng.data_ptr(), 1, stream),
-                       "lbbnn_frozen_members")
+            if self._maps is not None:
+                _lib.check(_lib.lib().lbbnn_frozen_members_compact(_lib.group_slice(descs, k, cnt), _lib.group_slice(self._maps, k, cnt),
+                                                                   cnt, c, rng.data_ptr(), 1, stream), "lbbnn_frozen_members_compact")
+            else:
+                _lib.check(_lib.lib().lbbnn_frozen_members(_lib.group_slice(descs, k, cnt), cnt, c, rng.data_ptr(), 1, stream),
+                           "lbbnn_frozen_members")
         return zbuf, ewm
 
     def _z_of(self, zbuf, c):
         out, off = [], 0
         for i in range(self.n_layers):
-            out.append(zbuf[:c, off:off + self.dims[i]].clone())
-            off += ops.operand_ld(self.dims[i])
+            out.append(zbuf[:c, off:off + self.full_dims[i]].clone())
+            off += ops.operand_ld(self.full_dims[i])
         return out
 
     def _chunk(self, x, c: int, st, head, zs, ms=None):
@@ -1281,12 +1464,7 @@ class FrozenNetwork(nn.Module):
         logits, no draws of its own -- or, with ``log_probs=True`` (one unit), the (samples, B, 2) log-probabilities of the two
         classes from the same launch."""
         _check_log_probs(self, log_probs)
-        S = int(samples)
-        if S < 1:
-            raise ValueError("bnn_amd: samples must be >= 1")
-        chunk = S if max_members is None else int(max_members)
-        if chunk < 1:
-            raise ValueError("bnn_amd: max_members must be >= 1")
+        S, chunk = self._member_counts(samples, max_members)
         x = self._input(data)
         B, C, dev = x.shape[0], self.dims[-1], x.device
         st = ops.RngState.get(dev)
@@ -1324,10 +1502,7 @@ class FrozenNetwork(nn.Module):
             self.last_masks = [torch.cat(parts) for parts in zip(*ms)]
         if keep_z:
             self.last_z = [torch.cat(parts) for parts in zip(*zs)] if zs is not None else [None] * self.n_layers
-        if self.head == "sigmoid":
-            return _binary_members(head, S, B, C, log_probs)
-        outputs = head[:, :B * C].view(S, B, C)
-        return outputs if C <= 16 else torch.log_softmax(outputs, dim=-1)
+        return self._finish(head, S, B, log_probs)
 
     @torch.no_grad()
     def forward(self, data: torch.Tensor, sample: bool = False, *, log_probs: bool = False) -> torch.Tensor:
@@ -1460,97 +1635,31 @@ class CompactFrozenNetwork(FrozenNetwork):
     live features by one lbbnn_gather_columns launch; when every input feature is live there is no launch and no copy."""
 
     def __init__(self, full_dims, live, needed, family: str = "lrt", threshold: float = 0.5, device=None, head: str = "log_softmax"):
-        full_dims = tuple(int(d) for d in full_dims)
-        if len(live) != len(full_dims) or len(needed) != len(full_dims):
-            raise ValueError("bnn_amd: a network of %d layers has %d boundaries" % (len(full_dims) - 1, len(full_dims)))
-        super().__init__([int(t.numel()) for t in live], family, "mpm", threshold, device=device, head=head)
-        self.full_dims = full_dims
-        self.needed = [int(c) for c in needed]
-        for b, t in enumerate(live):
-            self.register_buffer("live_%d" % b, t.to(device=device, dtype=torch.int32).contiguous())
-        self._input_identity = self.dims[0] == self.full_dims[0]     # sorted, unique, full width: every feature in place
-        self._maps = None
-        self._active = self._full_kept = None
-
-    @property
-    def live(self) -> List[torch.Tensor]:
-        return [self._buf("live", b) for b in range(len(self.dims))]
-
-    @property
-    def active_kept(self) -> int:
-        """Kept weights whose row and column are both needed (over every layer)."""
-        return int(self._active)
-
-    @property
-    def active_density(self) -> float:
-        return self.active_kept / sum(self.full_dims[i] * self.full_dims[i + 1] for i in range(self.n_layers))
-
-    @property
-    def density(self) -> float:
-        """Kept weights / all weights of the FULL network: what ``freeze(net, "mpm").density`` reports."""
-        return int(self._full_kept) / sum(self.full_dims[i] * self.full_dims[i + 1] for i in range(self.n_layers))
+        _FrozenModel.__init__(self, full_dims, "mpm", threshold, device, head, live, needed)
+        self._init_family(family, None)
 
     def extra_repr(self) -> str:
         return "full_dims=%s, %s" % (self.full_dims, super().extra_repr())
 
-    # ------------------------------------------------------------------------------------- snapshot
-    @torch.no_grad()
-    def _bind(self, net, need=None, masks=None):
-        """Allocate every buffer at the compact shapes and take THE snapshot: one lbbnn_frozen_operands_compact launch per
-        layer group, index_select of bias_mu, copies of the full-width q0 and z flow of an MNF layer."""
+    def _snapshot(self, layers):
+        """THE snapshot: one lbbnn_frozen_operands_compact launch per layer group, index_select of bias_mu, copies of the
+        full-width q0 and z flow of an MNF layer."""
         from . import _lib
-        layers = net._layers()
-        dev = layers[0].weight_mu.device
-        f = dict(dtype=torch.float32, device=dev)
-        n = self.n_layers
-        self._src = [net]
-        self._layer_ids = [int(l._layer_id) for l in layers]
-        self._row_offsets = [int(l.row_offset) for l in layers]
-        if masks is not None:
-            self._full_kept = torch.stack([k.sum() for k in masks]).sum()
-            self._active = torch.stack([(k & need[i + 1][:, None] & need[i][None, :]).sum() for i, k in enumerate(masks)]).sum()
-        live = self.live
-        dst, src = [], []
-        for i, l in enumerate(layers):
-            O, I = self.dims[i + 1], self.dims[i]
-            ld = ops.operand_ld(I)
-            # the rule of FrozenNetwork._bind at the compact shape
-            self._split.append(bool(ops.split_precision(l)) and ops.split_eligible(I, O) and (i == 0 or self.dims[i] % 4 == 0))
-            if I % 4 or ld > 2048:
-                self._members_ok = False
-            for name, shape in (("e0", (O, ld)), ("e_w", (O, ld)), ("var_w", (O, ld)), ("bias_var", (O,)), ("bias_mu", (O,))):
-                self.register_buffer("%s_%d" % (name, i), _empty(shape, **f))
-            for name in ("weight_mu", "weight_rho", "lambdal"):
-                if not getattr(l, name).is_contiguous():
-                    raise RuntimeError("bnn_amd: %s of layer %d is not contiguous" % (name, i + 1))
-            torch.index_select(l.bias_mu.detach(), 0, live[i + 1].long(), out=self._buf("bias_mu", i))
-            if l._mnf:
-                T, If = len(l.z_flow.transforms), self.full_dims[i]
-                self._T.append(T)
-                for name, shape in (("q0_mean", (If,)), ("q0_log_var", (If,)), ("flow_u", (T, If)), ("flow_w", (T, If)),
-                                    ("flow_b", (T, 1))):
-                    self.register_buffer("%s_%d" % (name, i), _empty(shape, **f))
-                dst += [self._buf("q0_mean", i), self._buf("q0_log_var", i)]
-                src += [l.q0_mean.detach(), l.q0_log_var.detach()]
-                for t, tr in enumerate(l.z_flow.transforms):
-                    dst += [self._buf("flow_u", i)[t], self._buf("flow_w", i)[t], self._buf("flow_b", i)[t]]
-                    src += [tr.u.detach().reshape(-1), tr.w.detach().reshape(-1), tr.bias.detach().reshape(-1)]
-            else:
-                self._T.append(0)
-        if dst:
-            torch._foreach_copy_(dst, src)
         if self.family == "mnf" and not self._members_ok:
             raise ValueError("bnn_amd: a compact MNF model needs compact in_features %% 4 == 0 and operand rows of at most 2048 "
                              "(compact dims %s); use freeze(net, \"mpm\") without compact=True" % (self.dims,))
-        self._maps = (_lib.CompactMap * n)()
-        for i in range(n):
-            m = self._maps[i]
-            m.rows, m.cols = live[i + 1].data_ptr(), live[i].data_ptr()
-            m.O_full, m.I_full = self.full_dims[i + 1], self.full_dims[i]
+        self._layer_ids = [int(l._layer_id) for l in layers]
+        self._row_offsets = [int(l.row_offset) for l in layers]
+        for i, l in enumerate(layers):
+            torch.index_select(l.bias_mu.detach(), 0, self._buf("live", i + 1).long(), out=self._buf("bias_mu", i))
+        dst, src = self._z_copies(layers)
+        if dst:
+            torch._foreach_copy_(dst, src)
         descs = self._descs(layers)
+        dev = self._device()
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            for k, cnt in _lib.layer_groups(n):
+            for k, cnt in _lib.layer_groups(self.n_layers):
                 _lib.check(_lib.lib().lbbnn_frozen_operands_compact(_lib.group_slice(descs, k, cnt), _lib.group_slice(self._maps, k, cnt),
                                                                     cnt, stream), "lbbnn_frozen_operands_compact")
         return self
@@ -1559,71 +1668,10 @@ class CompactFrozenNetwork(FrozenNetwork):
         raise NotImplementedError("bnn_amd: a compact model does not refresh: the structure, and with it every shape, may have "
                                   "changed with the parameters -- freeze again (evaluate.freeze(net, \"mpm\", compact=True))")
 
-    # ------------------------------------------------------------------------------------- evaluation
-    def _input(self, data):
-        if self._input_identity:
-            return super()._input(data)
-        from . import _lib
-        x = data.reshape(-1, self.full_dims[0])
-        if not x.is_cuda:
-            raise RuntimeError("bnn_amd: a frozen model evaluates on a HIP device tensor (data is on %s); there is no CPU path"
-                               % data.device)
-        dev = self._buf("e0", 0).device
-        if x.device != dev:
-            raise RuntimeError("bnn_amd: data is on %s, the frozen model on %s" % (x.device, dev))
-        x = x.float() if x.dtype != torch.float32 else x
-        if x.stride(1) != 1 or x.stride(0) < self.full_dims[0]:
-            x = x.contiguous()
-        B, n_idx = x.shape[0], self.dims[0]
-        ldo = _pad4(n_idx)                                   # dense rows on 16-B boundaries: what the bf16 hi | lo kernels read
-        if self._split[0] and B * ldo * 4 >= 0x7FFFFFF0:
-            raise ValueError("bnn_amd: a batch of %d rows exceeds the 2 GiB the 16-bit kernels address; split it" % B)
-        out = _empty((B, ldo), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().lbbnn_gather_columns(x.data_ptr(), x.stride(0),
-                                                       self._buf("live", 0).data_ptr(), n_idx, out.data_ptr(), ldo, B,
-                                                       torch.cuda.current_stream(dev).cuda_stream), "lbbnn_gather_columns")
-        return out[:, :n_idx] if ldo != n_idx else out
-
-    def _member_buffers(self, c: int):
-        """As FrozenNetwork._member_buffers, with z at the FULL width of every layer (the flow runs there; the scale launch
-        gathers) and the member operands at the compact shapes."""
-        if c > self._mcap:
-            dev = self._buf("e0", 0).device
-            f = dict(dtype=torch.float32, device=dev)
-            self._zbuf = _empty((c, sum(ops.operand_ld(d) for d in self.full_dims[:-1])), **f)
-            self._ewm = [_empty((c, self.dims[i + 1], ops.operand_ld(self.dims[i])), **f) for i in range(self.n_layers)]
-            self._mcap = c
-        return self._zbuf, self._ewm
-
-    def _draw_members(self, c: int, rng, stream, masks=None):
-        """MNF: member m's full-width z at Philox offset rng[1] + m and its compact mean operand E0' * z_m[cols]
-        (lbbnn_frozen_members_compact: the flow launch of the full model, then one scale launch with the gather fused in)."""
-        from . import _lib
-        zbuf, ewm = self._member_buffers(c)
-        descs = self._descs()
-        off = 0
-        for i in range(self.n_layers):
-            descs[i].z_fwd = zbuf.data_ptr() + 4 * off
-            descs[i].z_mstride = zbuf.stride(0)
-            descs[i].e_w_members = ewm[i].data_ptr()
-            off += ops.operand_ld(self.full_dims[i])
-        for k, cnt in _lib.layer_groups(self.n_layers):
-            _lib.check(_lib.lib().lbbnn_frozen_members_compact(_lib.group_slice(descs, k, cnt), _lib.group_slice(self._maps, k, cnt),
-                                                               cnt, c, rng.data_ptr(), 1, stream), "lbbnn_frozen_members_compact")
-        return zbuf, ewm
-
-    def _z_of(self, zbuf, c):
-        out, off = [], 0
-        for i in range(self.n_layers):
-            out.append(zbuf[:c, off:off + self.full_dims[i]].clone())
-            off += ops.operand_ld(self.full_dims[i])
-        return out
-
 
 def _freeze_compact(net, layers, family, threshold) -> CompactFrozenNetwork:
     dev = layers[0].weight_mu.device
-    cut = float(torch.tensor(math.log(threshold / (1.0 - threshold)), dtype=torch.float32))
+    cut = _cut(threshold)
     # the tie rule of lbbnn_frozen_operands: lambdal > cut compared in fp32 (NaN is never kept)
     masks = [l.lambdal.detach().float() > cut for l in layers]
     need, live, needed = _live_structure(masks, 8)           # the ONE device read: the live counts size every buffer
@@ -1663,12 +1711,8 @@ def freeze(net, gates: str = "alpha", *, threshold: float = 0.5, dense: bool = F
     The one device read that sizes its buffers happens here.  Refused, each with a ValueError that says what to use instead:
     ``gates="alpha"``, ``dense=True``, and a network with dense coupling z flows."""
     from . import layers as L
-    if gates not in FROZEN_GATES:
-        raise ValueError("bnn_amd: gates must be 'alpha' (the gates as trained) or 'mpm' (the median probability model), got %r"
-                         % (gates,))
-    if not 0.0 < float(threshold) < 1.0:
-        raise ValueError("bnn_amd: threshold must lie strictly between 0 and 1 (0.5 = the median probability model), got %r"
-                         % (threshold,))
+    FrozenNetwork._check_gates(gates)
+    _cut(threshold)
     if _is_base(net):
         raise TypeError("bnn_amd: freeze takes an LRT / MNF network; a baseline LBBNN network has its own median probability "
                         "model: ensemble_forward(net, data, samples, gates=\"mpm\")")
@@ -1705,7 +1749,7 @@ def freeze(net, gates: str = "alpha", *, threshold: float = 0.5, dense: bool = F
 BASE_FROZEN_GATES = ("sample", "mpm")
 
 
-class FrozenBaseNetwork(nn.Module):
+class FrozenBaseNetwork(_FrozenModel):
     """A trained baseline LBBNN network (``base.BayesianNetwork``) frozen for evaluation (built by ``freeze_base``; no
     parameters, buffers only): what ``test_ensemble`` and ``outofsample(net, medimod=True)`` evaluate (LBBNN-GP-MF.py:345-502).
 
@@ -1725,63 +1769,20 @@ class FrozenBaseNetwork(nn.Module):
     the outputs equal the full model's to fp32 rounding (the order of the sums).  Nothing here follows the source network's
     parameters until ``refresh()``."""
 
+    GATES, FREEZE = BASE_FROZEN_GATES, "freeze_base"
+    GATES_DOC = "'sample' (the gates drawn as trained) or 'mpm' (the median probability model)"
+    _POINTER_STATE = ("_layer_descs", "_maps", "_mcap", "_mw", "_mb", "_mptr")
+
     def __init__(self, full_dims, gates: str = "sample", threshold: float = 0.5, device=None, head: str = "log_softmax",
                  live=None, needed=None):
-        super().__init__()
-        if head not in ("log_softmax", "sigmoid"):
-            raise ValueError("bnn_amd: head must be 'log_softmax' or 'sigmoid', got %r" % (head,))
-        if gates not in BASE_FROZEN_GATES:
-            raise ValueError("bnn_amd: gates must be 'sample' (the gates drawn as trained) or 'mpm' (the median probability "
-                             "model), got %r" % (gates,))
-        threshold = float(threshold)
-        if not 0.0 < threshold < 1.0:
-            raise ValueError("bnn_amd: threshold must lie strictly between 0 and 1 (0.5 = the median probability model), got %r"
-                             % (threshold,))
-        self.full_dims = tuple(int(d) for d in full_dims)
-        self.compact = live is not None
-        if self.compact:
-            if gates != "mpm":
-                raise ValueError("bnn_amd: a compact model needs gates=\"mpm\"")
-            if len(live) != len(self.full_dims) or len(needed) != len(self.full_dims):
-                raise ValueError("bnn_amd: a network of %d layers has %d boundaries" % (len(self.full_dims) - 1, len(self.full_dims)))
-            self.dims = tuple(int(t.numel()) for t in live)
-            self.needed = [int(c) for c in needed]
-            for b, t in enumerate(live):
-                self.register_buffer("live_%d" % b, t.to(device=device, dtype=torch.int32).contiguous())
-        else:
-            self.dims = self.full_dims
-        if head == "sigmoid" and self.dims[-1] > 16:
-            raise ValueError("bnn_amd: a sigmoid head takes at most 16 output units, got dims[-1] = %d" % self.dims[-1])
-        self.head, self.gates, self.threshold = head, gates, threshold
-        self._src = [None]              # the source network, in a list so that it is not registered as a submodule
-        self._split, self._layer_ids, self._exact = [], [], []
-        self._descs, self._maps = None, None
+        super().__init__(full_dims, gates, threshold, device, head, live, needed)
+        self._exact = []
+        self._layer_descs = None
         self._mcap, self._mw, self._mb, self._mptr = 0, [], [], None
-        self._active = self._full_kept = None
         self.last_weights = self.last_biases = None
-        for i in range(len(self.dims) - 1):
-            self.register_buffer("kept_rows_%d" % i, torch.zeros(self.dims[i + 1], dtype=torch.int32, device=device))
 
-    # ------------------------------------------------------------------------------------- statistics
-    @property
-    def n_layers(self) -> int:
-        return len(self.dims) - 1
-
-    def _buf(self, name: str, i: int) -> torch.Tensor:
-        return getattr(self, "%s_%d" % (name, i))
-
-    def _n_weights(self) -> int:
-        return sum(self.full_dims[i] * self.full_dims[i + 1] for i in range(self.n_layers))
-
-    @property
-    def kept_rows(self) -> List[torch.Tensor]:
-        """Per layer (O',) int32: weights of each row with alpha > threshold, in either gates mode (a compact model: among
-        the live columns)."""
-        return [self._buf("kept_rows", i) for i in range(self.n_layers)]
-
-    @property
-    def kept(self) -> List[int]:
-        return [int(k.sum()) for k in self.kept_rows]
+    def _device(self):
+        return self._buf("w_mu", 0).device
 
     @property
     def density(self) -> float:
@@ -1789,28 +1790,7 @@ class FrozenBaseNetwork(nn.Module):
         sum(alpha) / weights (from ``alpha_rows``) -- the mean of what the members' gates draw, not a sampled value."""
         if self.gates == "sample":
             return float(torch.stack([self._buf("alpha_rows", i).double().sum() for i in range(self.n_layers)]).sum()) / self._n_weights()
-        if self.compact:
-            return int(self._full_kept) / self._n_weights()
-        return sum(self.kept) / self._n_weights()
-
-    @property
-    def live(self) -> List[torch.Tensor]:
-        self._need_compact("live")
-        return [self._buf("live", b) for b in range(len(self.dims))]
-
-    @property
-    def active_kept(self) -> int:
-        """Kept weights whose row and column are both needed (over every layer); a compact model only."""
-        self._need_compact("active_kept")
-        return int(self._active)
-
-    @property
-    def active_density(self) -> float:
-        return self.active_kept / self._n_weights()
-
-    def _need_compact(self, what: str):
-        if not self.compact:
-            raise RuntimeError("bnn_amd: %s belongs to a compact model (freeze_base(net, \"mpm\", compact=True))" % what)
+        return super().density
 
     def extra_repr(self) -> str:
         full = "full_dims=%s, " % (self.full_dims,) if self.compact else ""
@@ -1827,8 +1807,7 @@ class FrozenBaseNetwork(nn.Module):
         n = self.n_layers
         self._src = [net]
         if masks is not None:
-            self._full_kept = torch.stack([k.sum() for k in masks]).sum()
-            self._active = torch.stack([(k & need[i + 1][:, None] & need[i][None, :]).sum() for i, k in enumerate(masks)]).sum()
+            self._count_kept(need, masks)
         split_now = ops.split_precision()
         for i in range(n):
             O, I = self.dims[i + 1], self.dims[i]
@@ -1840,18 +1819,17 @@ class FrozenBaseNetwork(nn.Module):
                 self.register_buffer("%s_%d" % (name, i), _empty((O, ld), **f))
             for name in ("b_mu", "b_sigma", "alpha_rows"):
                 self.register_buffer("%s_%d" % (name, i), _empty((O,), **f))
-        self._input_identity = self.dims[0] == self.full_dims[0]
         self._point()
         return self._snapshot()
 
     def _point(self):
-        """The descriptors and maps of every layer, pointing at this model's buffers (built when the buffers are made, and
-        again whenever the module is moved or cast: ``_apply``); the member buffers start over."""
+        """The descriptors and maps of every layer, pointing at this model's buffers as they are now; the member buffers start
+        over."""
         from . import _lib
         n = self.n_layers
-        self._descs = (_lib.BaseFrozenDesc * n)()
+        self._layer_descs = (_lib.BaseFrozenDesc * n)()
         for i in range(n):
-            d = self._descs[i]
+            d = self._layer_descs[i]
             d.O, d.I = self.dims[i + 1], self.dims[i]
             d.ld = ops.operand_ld(d.I)
             d.flags = ops.F_SPLIT16 if self._split[i] else 0
@@ -1861,35 +1839,8 @@ class FrozenBaseNetwork(nn.Module):
             d.kept_rows, d.alpha_rows = self._buf("kept_rows", i).data_ptr(), self._buf("alpha_rows", i).data_ptr()
             if self._exact:
                 d.exact, d.layer_id = self._exact[i], self._layer_ids[i]
-        if self.compact:
-            live = [self._buf("live", b) for b in range(n + 1)]
-            self._maps = (_lib.CompactMap * n)()
-            for i in range(n):
-                m = self._maps[i]
-                m.rows, m.cols = live[i + 1].data_ptr(), live[i].data_ptr()
-                m.O_full, m.I_full = self.full_dims[i + 1], self.full_dims[i]
+        self._maps = self._compact_maps()
         self._mcap, self._mw, self._mb, self._mptr = 0, [], [], None
-
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        if self._descs is not None:
-            self._point()                                    # .to() / .cuda() replaced the buffers the descriptors address
-        return out
-
-    def __deepcopy__(self, memo):
-        """A copy owns its buffers, so it gets descriptors of its own (ctypes arrays of addresses are not copied)."""
-        import copy
-        held = (self._descs, self._maps, self._mcap, self._mw, self._mb, self._mptr)
-        self._descs, self._maps, self._mcap, self._mw, self._mb, self._mptr = None, None, 0, [], [], None
-        try:
-            new = type(self).__new__(type(self))
-            memo[id(self)] = new
-            new.__dict__ = copy.deepcopy(self.__dict__, memo)
-        finally:
-            self._descs, self._maps, self._mcap, self._mw, self._mb, self._mptr = held
-        if held[0] is not None:
-            new._point()
-        return new
 
     def _snapshot(self):
         from . import _lib
@@ -1898,14 +1849,14 @@ class FrozenBaseNetwork(nn.Module):
             raise RuntimeError("bnn_amd: this FrozenBaseNetwork is not bound to a network; build it with evaluate.freeze_base(net)")
         layers = net._layers()
         _check_base_freezable(layers)
-        dev = self._buf("w_mu", 0).device
-        if layers[0].weight_mu.device != dev or not self._buf("w_mu", 0).is_cuda:
+        dev = self._device()
+        if layers[0].weight_mu.device != dev or dev.type != "cuda":
             raise RuntimeError("bnn_amd: the source network (on %s) and this model (on %s) must share a HIP device; freeze it "
                                "again" % (layers[0].weight_mu.device, dev))
         self._layer_ids = [int(l._layer_id) for l in layers]
         self._exact = [int(l._exact_bits()) for l in layers]
         for i, l in enumerate(layers):
-            d = self._descs[i]
+            d = self._layer_descs[i]
             _base_sources(d, l, i)
             d.exact, d.layer_id = self._exact[i], self._layer_ids[i]
         mode = ops.GATES_MPM if self.gates == "mpm" else ops.GATES_SAMPLE
@@ -1913,7 +1864,7 @@ class FrozenBaseNetwork(nn.Module):
             stream = torch.cuda.current_stream(dev).cuda_stream
             for k, cnt in _lib.layer_groups(self.n_layers):
                 maps = _lib.group_slice(self._maps, k, cnt) if self._maps is not None else None
-                _lib.check(_lib.lib().lbbnn_base_frozen_operands(_lib.group_slice(self._descs, k, cnt), maps, cnt, mode,
+                _lib.check(_lib.lib().lbbnn_base_frozen_operands(_lib.group_slice(self._layer_descs, k, cnt), maps, cnt, mode,
                                                                  self.threshold, stream), "lbbnn_base_frozen_operands")
         return self
 
@@ -1928,44 +1879,12 @@ class FrozenBaseNetwork(nn.Module):
         return self._snapshot()
 
     # ------------------------------------------------------------------------------------- evaluation
-    def _input(self, data):
-        from . import _lib
-        x = data.reshape(-1, self.full_dims[0])
-        if not x.is_cuda:
-            raise RuntimeError("bnn_amd: a frozen model evaluates on a HIP device tensor (data is on %s); there is no CPU path"
-                               % data.device)
-        dev = self._buf("w_mu", 0).device
-        if x.device != dev:
-            raise RuntimeError("bnn_amd: data is on %s, the frozen model on %s" % (x.device, dev))
-        x = x.float() if x.dtype != torch.float32 else x
-        if x.stride(1) != 1 or x.stride(0) < self.full_dims[0]:
-            x = x.contiguous()
-        B = x.shape[0]
-        if self._input_identity:
-            if self._split[0]:
-                # the bf16 hi | lo kernels read x rows as 16-B vectors through 32-bit offsets
-                if B * x.stride(0) * 4 >= 0x7FFFFFF0:
-                    raise ValueError("bnn_amd: a batch of %d rows exceeds the 2 GiB the 16-bit kernels address; split it" % B)
-                if x.stride(0) % 4 or x.data_ptr() % 16:
-                    x = x.clone(memory_format=torch.contiguous_format)
-            return x
-        n_idx = self.dims[0]
-        ldo = _pad4(n_idx)                                   # dense rows on 16-B boundaries
-        if self._split[0] and B * ldo * 4 >= 0x7FFFFFF0:
-            raise ValueError("bnn_amd: a batch of %d rows exceeds the 2 GiB the 16-bit kernels address; split it" % B)
-        out = _empty((B, ldo), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().lbbnn_gather_columns(x.data_ptr(), x.stride(0), self._buf("live", 0).data_ptr(), n_idx,
-                                                       out.data_ptr(), ldo, B, torch.cuda.current_stream(dev).cuda_stream),
-                       "lbbnn_gather_columns")
-        return out[:, :n_idx] if ldo != n_idx else out
-
-    def _member_buffers(self, c: int):
+    def _member_weights(self, c: int):
         """Member weights [c][O'][ld'] and biases [c][O'] per layer and the pointer arrays of the members call; allocated for
         the largest chunk seen, smaller chunks use a prefix."""
         from . import _lib
         if c > self._mcap:
-            f = dict(dtype=torch.float32, device=self._buf("w_mu", 0).device)
+            f = dict(dtype=torch.float32, device=self._device())
             n = self.n_layers
             self._mw = [_empty((c, self.dims[i + 1], ops.operand_ld(self.dims[i])), **f) for i in range(n)]
             self._mb = [_empty((c, self.dims[i + 1]), **f) for i in range(n)]
@@ -2000,12 +1919,12 @@ class FrozenBaseNetwork(nn.Module):
         from . import _lib, distributions
         dev = x.device
         stream = torch.cuda.current_stream(dev).cuda_stream
-        mw, mb = self._member_buffers(c)
+        mw, mb = self._member_weights(c)
         mode = ops.GATES_MPM if self.gates == "mpm" else ops.GATES_SAMPLE
         T = float(distributions.TEMPER_PRIOR)
         for k, cnt in _lib.layer_groups(self.n_layers):      # every group reads the same offset; advanced once below
             maps = _lib.group_slice(self._maps, k, cnt) if self._maps is not None else None
-            rc = _lib.lib().lbbnn_base_frozen_members(_lib.group_slice(self._descs, k, cnt), maps, cnt, c, mode, T,
+            rc = _lib.lib().lbbnn_base_frozen_members(_lib.group_slice(self._layer_descs, k, cnt), maps, cnt, c, mode, T,
                                                      _lib.group_slice(self._mptr[0], k, cnt), _lib.group_slice(self._mptr[1], k, cnt),
                                                      None, st.t.data_ptr(), 1, stream)
             _lib.check(rc, "lbbnn_base_frozen_members")
@@ -2013,13 +1932,6 @@ class FrozenBaseNetwork(nn.Module):
             kept.append(([w[:c].clone() for w in mw], [b[:c].clone() for b in mb]))
         self._gemms(x, c, mw, True, mb, head, stream)
         st.advance(c)                                        # as c single forwards would have
-
-    def _finish(self, buf, S: int, B: int, log_probs: bool):
-        C = self.dims[-1]
-        if self.head == "sigmoid":
-            return _binary_members(buf, S, B, C, log_probs)
-        outputs = buf[:, :B * C].view(S, B, C)
-        return outputs if C <= 16 else torch.log_softmax(outputs, dim=-1)
 
     @torch.no_grad()
     def ensemble(self, data: torch.Tensor, samples: int = 10, *, max_members: Optional[int] = None, log_probs: bool = False,
@@ -2034,12 +1946,7 @@ class FrozenBaseNetwork(nn.Module):
         (samples, O') biases.  A model with ``head == "sigmoid"``: (samples, B, units) probabilities, or with ``log_probs``
         (one unit) the (samples, B, 2) log-probabilities of the two classes."""
         _check_log_probs(self, log_probs)
-        S = int(samples)
-        if S < 1:
-            raise ValueError("bnn_amd: samples must be >= 1")
-        chunk = S if max_members is None else int(max_members)
-        if chunk < 1:
-            raise ValueError("bnn_amd: max_members must be >= 1")
+        S, chunk = self._member_counts(samples, max_members)
         x = self._input(data)
         B, C, dev = x.shape[0], self.dims[-1], x.device
         st = ops.RngState.get(dev)
@@ -2140,13 +2047,9 @@ def freeze_base(net, gates: str = "sample", *, threshold: float = 0.5, compact: 
     if not _is_base(net):
         raise TypeError("bnn_amd: freeze_base takes a baseline LBBNN network (bnn_amd.base.BayesianNetwork), got %s; an LRT / "
                         "MNF network has evaluate.freeze" % type(net).__name__)
-    if gates not in BASE_FROZEN_GATES:
-        raise ValueError("bnn_amd: gates must be 'sample' (the gates drawn as trained) or 'mpm' (the median probability model), "
-                         "got %r" % (gates,))
+    FrozenBaseNetwork._check_gates(gates)
     threshold = float(threshold)
-    if not 0.0 < threshold < 1.0:
-        raise ValueError("bnn_amd: threshold must lie strictly between 0 and 1 (0.5 = the median probability model), got %r"
-                         % (threshold,))
+    _cut(threshold)
     if compact and gates != "mpm":
         raise ValueError("bnn_amd: compact=True needs gates=\"mpm\": sampled gates are never fixed at zero, so no unit can be "
                          "dropped -- use freeze_base(net, \"mpm\", compact=True), or freeze_base(net) for the gates as trained")

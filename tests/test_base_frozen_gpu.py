@@ -249,7 +249,12 @@ def test_a_copied_or_moved_model_addresses_its_own_buffers(bnn, dev):
         getattr(fz, "w_mu_%d" % i).fill_(float("nan"))           # the original's planes are no longer usable
     bnn.manual_seed(SEED, OFF)
     assert torch.equal(twin.ensemble(x, S), want)
-    moved = twin.double().float()                                # every buffer replaced
+    old = dict(twin.named_buffers())
+    moved = twin.double().float()                                # every float buffer replaced (a cast leaves int32 ones in place)
+    for k, b in moved.named_buffers():
+        if b.is_floating_point():
+            assert b.data_ptr() != old[k].data_ptr(), k
+            old[k].fill_(float("nan"))                           # still alive: a stale address reads NaN, not freed memory
     bnn.manual_seed(SEED, OFF)
     assert torch.equal(moved.ensemble(x, S), want)
     with pytest.raises(RuntimeError, match="data is on"):
@@ -491,7 +496,7 @@ def test_members_entry_point_gate_rows_and_member_split(bnn, dev):
     arr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
     bnn.manual_seed(SEED, OFF)
     st = ops.RngState.get(dev)
-    _lib.check(_lib.lib().lbbnn_base_frozen_members(fz._descs, None, n, members, ops.GATES_SAMPLE, 0.5, arr(w), arr(b), arr(gr),
+    _lib.check(_lib.lib().lbbnn_base_frozen_members(fz._layer_descs, None, n, members, ops.GATES_SAMPLE, 0.5, arr(w), arr(b), arr(gr),
                                                     st.t.data_ptr(), 1, ops._stream()), "lbbnn_base_frozen_members")
     for i in range(n):
         I = fz.dims[i]
@@ -503,7 +508,7 @@ def test_members_entry_point_gate_rows_and_member_split(bnn, dev):
     many = 700
     w2 = [torch.empty((many, fz.dims[i + 1], 32), **f) for i in range(n)]
     b2 = [torch.empty((many, fz.dims[i + 1]), **f) for i in range(n)]
-    _lib.check(_lib.lib().lbbnn_base_frozen_members(fz._descs, None, n, many, ops.GATES_SAMPLE, 0.5, arr(w2), arr(b2), None,
+    _lib.check(_lib.lib().lbbnn_base_frozen_members(fz._layer_descs, None, n, many, ops.GATES_SAMPLE, 0.5, arr(w2), arr(b2), None,
                                                     st.t.data_ptr(), 1, ops._stream()), "lbbnn_base_frozen_members")
     for i in range(n):
         assert torch.equal(w2[i][:members], w[i]) and torch.equal(b2[i][:members], b[i]), i

@@ -431,3 +431,44 @@ def test_no_gather_when_no_input_is_unneeded_and_one_call_more_otherwise(bnn, de
         ref = full(x, sample=False)
         bnn.manual_seed(SEED, OFF)
         assert rel_err(fz(x, sample=False), ref) < BAR["fp32"]
+
+
+def test_a_copied_or_moved_model_addresses_its_own_buffers(bnn, dev):
+    """The maps of a compact model are arrays of device addresses (the live_<b> index buffers), and the member buffers are kept
+    across calls: a deep copy, or a model moved or cast, must address its own buffers.  The planar-MNF model of the test
+    above in its second state: (32, 24, 16, 3) compacts to (24, 16, 16, 3), so the input is gathered too.  The original's
+    index buffers are poisoned with zeros, which are in range at every boundary: a twin that read them would gather the wrong
+    columns, never out of bounds."""
+    import copy
+    ev = bnn.evaluate
+    dims = (32, 24, 16, 3)
+    torch.manual_seed(11)
+    net = bnn.mnf.BayesianNetwork(dims, 2, z_flow_type="Planar", r_flow_type="Planar").to(dev).eval()
+    with torch.no_grad():
+        for l in net._layers():
+            l.lambdal.fill_(2.0)
+        net.l2.lambdal[:, 1::3] = -2.0
+        net.l1.lambdal[:, 1::3] = -2.0
+    fz = ev.freeze(net, "mpm", compact=True)
+    assert fz.dims == (24, 16, 16, 3) and not fz._input_identity
+    B, S = 5, 3
+    x = _x(dev, B, dims[0])
+    bnn.manual_seed(SEED, OFF)
+    want = fz.ensemble(x, S)
+    assert want.shape == (S, B, 3) and bool(torch.isfinite(want).all())
+    twin = copy.deepcopy(fz)
+    for k, b in fz.named_buffers():
+        b.fill_(float("nan")) if b.is_floating_point() else b.zero_()
+    bnn.manual_seed(SEED, OFF)
+    assert torch.equal(twin.ensemble(x, S), want)
+    old = dict(twin.named_buffers())
+    moved = twin.double().float()                                # every float buffer replaced (a cast leaves int32 ones in place)
+    for k, b in moved.named_buffers():
+        if b.is_floating_point():
+            assert b.data_ptr() != old[k].data_ptr(), k
+            old[k].fill_(float("nan"))                           # still alive: a stale address reads NaN, not freed memory
+    bnn.manual_seed(SEED, OFF)
+    assert torch.equal(moved.ensemble(x, S, keep_z=True), want)
+    assert [tuple(z.shape) for z in moved.last_z] == [(S, 32), (S, 24), (S, 16)]      # z at the full widths
+    with pytest.raises(RuntimeError, match="data is on"):
+        moved.cpu().ensemble(x, S)

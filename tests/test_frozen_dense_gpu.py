@@ -474,3 +474,34 @@ def test_planar_and_lrt_networks_with_dense_flag_keep_their_bits(bnn, dev, preci
             assert torch.equal(oa, ob) and b.last_masks is None
             for za, zb in zip(a.last_z, b.last_z):
                 assert (za is None and zb is None) or torch.equal(za, zb)
+
+
+def test_a_copied_or_moved_model_addresses_its_own_buffers(bnn, dev):
+    """The transforms of the dense z flows are arrays of device addresses, and the member buffers are kept across calls: a deep
+    copy, or a model moved or cast, must address its own buffers.  (16, 12, 3): two layers with in_features % 4 == 0, the
+    smallest model whose transforms cover more than one layer."""
+    import copy
+    ev = bnn.evaluate
+    torch.manual_seed(11)
+    net = bnn.mnf.BayesianNetwork((16, 12, 3), 2, z_flow_type="RNVP", r_flow_type="RNVP").to(dev).eval()
+    fz = ev.freeze(net, "alpha", dense=True)
+    B, S = 5, 3
+    x = _x(dev, B, 16)
+    bnn.manual_seed(SEED, OFF)
+    want = fz.ensemble(x, S)
+    assert want.shape == (S, B, 3) and bool(torch.isfinite(want).all())
+    twin = copy.deepcopy(fz)
+    poisoned = [b.fill_(float("nan")) for k, b in fz.named_buffers() if k.startswith(("zflow_", "q0_", "e0_"))]
+    assert len(poisoned) > 6                                      # the original's flows and operands are no longer usable
+    bnn.manual_seed(SEED, OFF)
+    assert torch.equal(twin.ensemble(x, S), want)
+    old = dict(twin.named_buffers())
+    moved = twin.double().float()                                # every float buffer replaced (a cast leaves int32 ones in place)
+    for k, b in moved.named_buffers():
+        if b.is_floating_point():
+            assert b.data_ptr() != old[k].data_ptr(), k
+            old[k].fill_(float("nan"))                           # still alive: a stale address reads NaN, not freed memory
+    bnn.manual_seed(SEED, OFF)
+    assert torch.equal(moved.ensemble(x, S), want)
+    with pytest.raises(RuntimeError, match="data is on"):
+        moved.cpu().ensemble(x, S)

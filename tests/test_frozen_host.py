@@ -246,3 +246,27 @@ def test_kept_and_density_follow_kept_rows(threshold):
     assert fz.kept == kept
     assert isinstance(fz.density, float) and fz.density == sum(kept) / total
     assert 0.0 < fz.density < 1.0
+
+
+def test_unbound_models_deep_copy_and_a_full_model_has_the_compact_surface():
+    import copy
+    from bnn_amd import evaluate
+    dims = (20, 16, 12, 3)
+    fz = evaluate.FrozenNetwork(dims, "mnf", "mpm", 0.3)
+    live = [torch.arange(8, dtype=torch.int32), torch.arange(8, dtype=torch.int32), torch.arange(8, dtype=torch.int32),
+            torch.arange(3, dtype=torch.int32)]
+    cp = evaluate.CompactFrozenNetwork(dims, live, [5, 6, 7, 3], "lrt", 0.3)
+    for m in (fz, cp):
+        twin = copy.deepcopy(m)
+        assert type(twin) is type(m) and twin is not m
+        assert (twin.dims, twin.full_dims, twin.gates, twin.cut) == (m.dims, m.full_dims, m.gates, m.cut)
+        assert sorted(dict(twin.named_buffers())) == sorted(dict(m.named_buffers()))
+        assert twin.kept_rows[0].data_ptr() != m.kept_rows[0].data_ptr()
+    assert cp.compact and cp.dims == (8, 8, 8, 3) and cp.full_dims == dims
+    # a full model: the surface of a full FrozenBaseNetwork
+    base = evaluate.FrozenBaseNetwork(dims, "mpm", 0.3)
+    assert fz.full_dims == fz.dims == dims and not fz.compact and not base.compact
+    for what in ("live", "active_kept", "active_density"):
+        for m in (fz, base):
+            with pytest.raises(RuntimeError, match="belongs to a compact model"):
+                getattr(m, what)
