@@ -283,6 +283,14 @@ class EvalMetricsArgs(ctypes.Structure):
                 ("S", c_i), ("B", c_i), ("C", c_i)]
 
 
+MONITOR_COUNTS = 8                     # LBBNN_MONITOR_COUNTS, at the header's indices (LBBNN_MONITOR_STEPS ...):
+MONITOR_COUNT_NAMES = ("steps", "rows", "correct", "bad_targets", "nonfinite_rows", "nonfinite_steps", "skipped_steps", "nll_rows")
+MONITOR_SUMS = 5                       # LBBNN_MONITOR_SUMS, the doubles behind the counts:
+MONITOR_SUM_NAMES = ("nll_sum", "kl_term_sum", "loss_sum", "last_nll", "last_loss")
+MONITOR_WORDS = MONITOR_COUNTS + MONITOR_SUMS
+MONITOR_SKIPPED_STEPS = 6              # LBBNN_MONITOR_SKIPPED_STEPS: the slot the guarded optimizer steps count in
+
+
 UNC_COUNTS = 6                         # LBBNN_UNC_COUNTS, in the header's order:
 UNC_COUNT_NAMES = ("rows", "rows_with_target", "bad_targets", "correct_bma", "nonfinite_rows", "log_score_nonfinite")
 UNC_SUMS = 6                           # LBBNN_UNC_SUMS, in the header's order:
@@ -339,6 +347,8 @@ SIGNATURES = {
                               ctypes.c_float, c_p, c_i, c_p]),
     "lbbnn_adam_step_groups": (c_i, [ctypes.POINTER(AdamGroupList), c_p, c_p, c_i, c_p, c_p, c_i, c_p]),
     "lbbnn_sgd_step_groups": (c_i, [ctypes.POINTER(AdamGroupList), c_p, c_p, c_i, c_p, c_p, c_i, c_p]),
+    "lbbnn_adam_step_groups_guarded": (c_i, [ctypes.POINTER(AdamGroupList), c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p]),
+    "lbbnn_sgd_step_groups_guarded": (c_i, [ctypes.POINTER(AdamGroupList), c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p]),
     "lbbnn_grad_sumsq_workspace": (c_i64, [c_i64]),
     "lbbnn_grad_sumsq": (c_i, [ctypes.POINTER(AdamGroupList), c_p, c_i64, c_i64, ctypes.c_float, c_p, c_p, c_p]),
     "lbbnn_matmul_splitk": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
@@ -397,6 +407,7 @@ SIGNATURES = {
     "lbbnn_philox_std_gamma": (c_i, [c_p, c_u32, c_p, c_p, c_i64, c_p, c_p]),
     "lbbnn_gamma_grad": (c_i, [c_p, c_p, c_i64, c_p, c_p]),
     "lbbnn_elbo_loss": (c_i, [c_p, c_i, c_p, c_i, c_i, c_p, ctypes.c_float, c_p, c_p]),
+    "lbbnn_elbo_loss_monitor": (c_i, [c_p, c_i, c_p, c_i, c_i, c_p, ctypes.c_float, c_p, c_p, c_p, c_p]),
     "lbbnn_elbo_loss_backward": (c_i, [c_p, c_p, c_i, c_i, ctypes.c_float, c_p, c_p, c_p]),
     "lbbnn_elbo_loss_backward_logits": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, ctypes.c_float, c_p, c_p, c_p, c_p]),
     "lbbnn_log_softmax_backward": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_p]),

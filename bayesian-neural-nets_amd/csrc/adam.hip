@@ -3,7 +3,8 @@
 // prefix held in the kernel arguments (read through the kernarg pointer: scalar loads, no scratch copy).
 // lbbnn_adam_step_groups: the same pass for the tensors of any number of parameter groups, hyper-parameters and step counters
 // read from device tables; lbbnn_sgd_step_groups: torch.optim.SGD's update in the same form;
-// lbbnn_grad_sumsq: the global gradient norm for clipping, fixed-order sums.
+// lbbnn_grad_sumsq: the global gradient norm for clipping, fixed-order sums.  lbbnn_*_step_groups_guarded: the two list kernels
+// instantiated with a device-side skip word.
 #include <cmath>
 #include "lbbnn_device.h"
 #include "lbbnn_internal.h"
@@ -81,16 +82,28 @@ static_assert(CHUNK == LBBNN_ADAM_CHUNK, "include/lbbnn.h documents the chunk si
 // workgroup can read an advanced one.  The next launch reads them across a kernel boundary.
 constexpr uint32_t F_INACTIVE = LBBNN_ADAM_F_INACTIVE;      // "a group without parameters": the same bit in both tables' flags
 static_assert(LBBNN_SGD_F_INACTIVE == F_INACTIVE, "advance_groups reads one bit for both tables");
-template <class Hyper>
-__device__ __forceinline__ void advance_groups(const Hyper* hyper, float* step, unsigned* ticket, int n_groups) {
+// A guarded launch that skips (skip_step below: the same value in every workgroup) leaves the counters alone and counts the
+// skipped step instead; the ticket goes back to zero either way.
+template <bool GUARDED, class Hyper>
+__device__ __forceinline__ void advance_groups(const Hyper* hyper, float* step, unsigned* ticket, int n_groups, bool skip,
+                                               long long* skipped) {
     __shared__ int last;
     __syncthreads();
     if (threadIdx.x == 0) last = atomicAdd(ticket, 1u) == gridDim.x - 1 ? 1 : 0;
     __syncthreads();
     if (!last) return;
-    for (int gq = threadIdx.x; gq < n_groups; gq += 256)
-        if (!(hyper[gq].flags & F_INACTIVE)) step[gq] += 1.f;
+    if (GUARDED && skip) {
+        if (threadIdx.x == 0 && skipped) *skipped += 1;
+    } else {
+        for (int gq = threadIdx.x; gq < n_groups; gq += 256)
+            if (!(hyper[gq].flags & F_INACTIVE)) step[gq] += 1.f;
+    }
     if (threadIdx.x == 0) atomicExch(ticket, 0u);
+}
+// The skip word of a guarded launch, read once at kernel entry.  *guard and *grad_scale are written by earlier launches of the
+// stream (the loss, lbbnn_grad_sumsq) and by nothing in this one: every workgroup reads the same value whenever it runs.
+__device__ __forceinline__ bool skip_step(const int* guard, const float* grad_scale) {
+    return guard[0] != 0 || (grad_scale != nullptr && !isfinite(grad_scale[0]));
 }
 struct GroupsKArgs {
     lbbnn_adam_group_list_t l;
@@ -100,13 +113,17 @@ struct GroupsKArgs {
     const float* grad_scale;
     unsigned* ticket;
     int n_groups, advance;
+    const int* guard;                                         // the guarded instantiation only
+    long long* skipped;
 };
 static_assert(sizeof(GroupsKArgs) <= 4096, "kernel-argument segment");
 
+template <bool GUARDED>
 __global__ __launch_bounds__(256) void adam_groups_kernel(const GroupsKArgs ka) {
     const LBBNN_CONST_AS GroupsKArgs& a = *kernarg_as<GroupsKArgs>();
     const int blk = blockIdx.x;
-    if (blk < a.first[a.l.n]) {                               // (an advance-only launch has one workgroup and no tensor)
+    const bool skip = GUARDED ? skip_step(a.guard, a.grad_scale) : false;
+    if (!skip && blk < a.first[a.l.n]) {                      // (an advance-only launch has one workgroup and no tensor)
         int lo = 0, hi = a.l.n;                               // largest i with first[i] <= blk
         while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (a.first[mid] <= blk) lo = mid; else hi = mid; }
         const int ti = lo;
@@ -172,7 +189,7 @@ __global__ __launch_bounds__(256) void adam_groups_kernel(const GroupsKArgs ka) 
             }
         }
     }
-    if (a.advance) advance_groups(a.hyper, a.step, a.ticket, a.n_groups);
+    if (a.advance) advance_groups<GUARDED>(a.hyper, a.step, a.ticket, a.n_groups, skip, a.skipped);
 }
 
 // ---- lbbnn_sgd_step_groups: torch.optim.SGD's update over the same list, one row of lbbnn_sgd_hyper_t per group ----
@@ -184,13 +201,17 @@ struct SgdKArgs {
     const float* grad_scale;
     unsigned* ticket;
     int n_groups, advance;
+    const int* guard;                                         // the guarded instantiation only
+    long long* skipped;
 };
 static_assert(sizeof(SgdKArgs) <= 4096, "kernel-argument segment");
 
+template <bool GUARDED>
 __global__ __launch_bounds__(256) void sgd_groups_kernel(const SgdKArgs ka) {
     const LBBNN_CONST_AS SgdKArgs& a = *kernarg_as<SgdKArgs>();
     const int blk = blockIdx.x;
-    if (blk < a.first[a.l.n]) {                               // (an advance-only launch has one workgroup and no tensor)
+    const bool skip = GUARDED ? skip_step(a.guard, a.grad_scale) : false;
+    if (!skip && blk < a.first[a.l.n]) {                      // (an advance-only launch has one workgroup and no tensor)
         int lo = 0, hi = a.l.n;                               // largest i with first[i] <= blk
         while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (a.first[mid] <= blk) lo = mid; else hi = mid; }
         const int ti = lo;
@@ -251,7 +272,7 @@ __global__ __launch_bounds__(256) void sgd_groups_kernel(const SgdKArgs ka) {
             }
         }
     }
-    if (a.advance) advance_groups(a.hyper, a.step, a.ticket, a.n_groups);
+    if (a.advance) advance_groups<GUARDED>(a.hyper, a.step, a.ticket, a.n_groups, skip, a.skipped);
 }
 
 struct SumsqKArgs {
@@ -374,8 +395,10 @@ static int groups_list_blocks(const lbbnn_adam_group_list_t* list, bool update, 
     return 0;
 }
 
-extern "C" int lbbnn_adam_step_groups(const lbbnn_adam_group_list_t* list, const lbbnn_adam_hyper_t* hyper, float* step,
-                                      int n_groups, const float* grad_scale, uint32_t* ticket, int advance, void* stream) {
+// the Adam list step, unguarded (guard == NULL) or guarded
+static int adam_groups_launch(const lbbnn_adam_group_list_t* list, const lbbnn_adam_hyper_t* hyper, float* step, int n_groups,
+                              const float* grad_scale, uint32_t* ticket, int advance, const int32_t* guard, int64_t* skipped,
+                              void* stream) {
     if (!list || !hyper || !step || (advance && !ticket)) return LBBNN_E_NULL;
     if (n_groups < 1 || n_groups > 65536) return LBBNN_E_SHAPE;
     GroupsKArgs ka;
@@ -386,12 +409,28 @@ extern "C" int lbbnn_adam_step_groups(const lbbnn_adam_group_list_t* list, const
     ka.l = *list;
     ka.hyper = hyper; ka.step = step; ka.grad_scale = grad_scale; ka.ticket = ticket;
     ka.n_groups = n_groups; ka.advance = advance ? 1 : 0;
-    hipLaunchKernelGGL(adam_groups_kernel, dim3((unsigned)(nb > 0 ? nb : 1)), dim3(256), 0, static_cast<hipStream_t>(stream), ka);
+    ka.guard = guard; ka.skipped = reinterpret_cast<long long*>(skipped);
+    const dim3 grid((unsigned)(nb > 0 ? nb : 1));
+    if (guard) hipLaunchKernelGGL(adam_groups_kernel<true>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), ka);
+    else hipLaunchKernelGGL(adam_groups_kernel<false>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), ka);
     return (int)hipGetLastError();
 }
 
-extern "C" int lbbnn_sgd_step_groups(const lbbnn_adam_group_list_t* list, const lbbnn_sgd_hyper_t* hyper, float* step,
-                                     int n_groups, const float* grad_scale, uint32_t* ticket, int advance, void* stream) {
+extern "C" int lbbnn_adam_step_groups(const lbbnn_adam_group_list_t* list, const lbbnn_adam_hyper_t* hyper, float* step,
+                                      int n_groups, const float* grad_scale, uint32_t* ticket, int advance, void* stream) {
+    return adam_groups_launch(list, hyper, step, n_groups, grad_scale, ticket, advance, nullptr, nullptr, stream);
+}
+
+extern "C" int lbbnn_adam_step_groups_guarded(const lbbnn_adam_group_list_t* list, const lbbnn_adam_hyper_t* hyper, float* step,
+                                              int n_groups, const float* grad_scale, uint32_t* ticket, int advance,
+                                              const int32_t* guard, int64_t* skipped, void* stream) {
+    if (!guard) return LBBNN_E_NULL;
+    return adam_groups_launch(list, hyper, step, n_groups, grad_scale, ticket, advance, guard, skipped, stream);
+}
+
+static int sgd_groups_launch(const lbbnn_adam_group_list_t* list, const lbbnn_sgd_hyper_t* hyper, float* step, int n_groups,
+                             const float* grad_scale, uint32_t* ticket, int advance, const int32_t* guard, int64_t* skipped,
+                             void* stream) {
     if (!list || !hyper || !step || (advance && !ticket)) return LBBNN_E_NULL;
     if (n_groups < 1 || n_groups > 65536) return LBBNN_E_SHAPE;
     SgdKArgs ka;
@@ -402,8 +441,23 @@ extern "C" int lbbnn_sgd_step_groups(const lbbnn_adam_group_list_t* list, const 
     ka.l = *list;
     ka.hyper = hyper; ka.step = step; ka.grad_scale = grad_scale; ka.ticket = ticket;
     ka.n_groups = n_groups; ka.advance = advance ? 1 : 0;
-    hipLaunchKernelGGL(sgd_groups_kernel, dim3((unsigned)(nb > 0 ? nb : 1)), dim3(256), 0, static_cast<hipStream_t>(stream), ka);
+    ka.guard = guard; ka.skipped = reinterpret_cast<long long*>(skipped);
+    const dim3 grid((unsigned)(nb > 0 ? nb : 1));
+    if (guard) hipLaunchKernelGGL(sgd_groups_kernel<true>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), ka);
+    else hipLaunchKernelGGL(sgd_groups_kernel<false>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), ka);
     return (int)hipGetLastError();
+}
+
+extern "C" int lbbnn_sgd_step_groups(const lbbnn_adam_group_list_t* list, const lbbnn_sgd_hyper_t* hyper, float* step,
+                                     int n_groups, const float* grad_scale, uint32_t* ticket, int advance, void* stream) {
+    return sgd_groups_launch(list, hyper, step, n_groups, grad_scale, ticket, advance, nullptr, nullptr, stream);
+}
+
+extern "C" int lbbnn_sgd_step_groups_guarded(const lbbnn_adam_group_list_t* list, const lbbnn_sgd_hyper_t* hyper, float* step,
+                                             int n_groups, const float* grad_scale, uint32_t* ticket, int advance,
+                                             const int32_t* guard, int64_t* skipped, void* stream) {
+    if (!guard) return LBBNN_E_NULL;
+    return sgd_groups_launch(list, hyper, step, n_groups, grad_scale, ticket, advance, guard, skipped, stream);
 }
 
 extern "C" int64_t lbbnn_grad_sumsq_workspace(int64_t partials) {

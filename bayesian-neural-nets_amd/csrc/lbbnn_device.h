@@ -20,12 +20,15 @@ __device__ __forceinline__ int dpp_mov(int v) { return __builtin_amdgcn_update_d
 template <int CTRL>
 __device__ __forceinline__ float dpp_get(float v) { return __builtin_bit_cast(float, dpp_mov<CTRL>(__builtin_bit_cast(int, v))); }
 template <int CTRL>
+__device__ __forceinline__ int dpp_get(int v) { return dpp_mov<CTRL>(v); }
+template <int CTRL>
 __device__ __forceinline__ double dpp_get(double v) {
     const uint64_t b = __builtin_bit_cast(uint64_t, v);
     const uint32_t lo = (uint32_t)dpp_mov<CTRL>((int)(uint32_t)b), hi = (uint32_t)dpp_mov<CTRL>((int)(uint32_t)(b >> 32));
     return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
 }
 __device__ __forceinline__ float lane_get(float v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); }
+__device__ __forceinline__ int lane_get(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
 __device__ __forceinline__ double lane_get(double v, int l) {
     const uint64_t b = __builtin_bit_cast(uint64_t, v);
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, l), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), l);

@@ -3,6 +3,8 @@
 //
 //   lbbnn_elbo_loss           loss = -sum_b logp[b][t_b] + kl * kl_scale            F.nll_loss(reduction='sum') + kl / NUM_BATCHES,
 //                                                                                  LBBNN-GP-MF-MNF.py:268-271 (train())
+//   lbbnn_elbo_loss_monitor   the same loss (bitwise) plus the running totals of a training log and a per-step non-finite flag,
+//                             still one launch of one workgroup
 //   lbbnn_elbo_loss_backward  g_logp[b][c] = -g (c == t_b),  *g_kl = g * kl_scale
 //   lbbnn_log_softmax_backward g_logits = g_logp - exp(logp) * sum_c g_logp         backward of F.log_softmax(dim=1), :256
 // One workgroup / one pass each; sums in a fixed order (deterministic).
@@ -23,6 +25,91 @@ __global__ __launch_bounds__(1024) void elbo_loss_kernel(const float* __restrict
     }
     s = block_sum<double, 16>(s, scratch);
     if (threadIdx.x == 0) *loss = (float)(s + (kl ? (double)(*kl) * (double)kl_scale : 0.0));
+}
+
+// elbo_loss_kernel plus the training monitor.  The nll sum is elbo_loss_kernel's, term for term (same rows per thread, same
+// order, same block_sum), so *loss has its bits.  A thread reads its row's C log-probabilities in batches of 16 independent
+// loads (the target's term is picked out of the registers instead of being loaded behind the target), finds the arg-max by
+// numpy.argmax's rule (a NaN is the maximum, the lowest index wins a tie) and whether all C values are finite.  The three row
+// counts are wave sums left in LDS ahead of block_sum's barriers.  One workgroup, launches of one stream ordered: thread 0 adds
+// to the totals with plain loads and stores -- no atomics, the same bits from run to run.
+__global__ __launch_bounds__(1024) void elbo_loss_monitor_kernel(const float* __restrict__ logp, int ldp,
+                                                                 const int64_t* __restrict__ target, int B, int C, const float* kl,
+                                                                 float kl_scale, float* loss, int64_t* totals, int32_t* guard) {
+    constexpr int G = 16;
+    __shared__ double scratch[16];
+    __shared__ int counts[3][16];
+    double s = 0.0;
+    int n_correct = 0, n_bad = 0, n_nonfinite = 0;                // B < 2^31 rows: every count fits
+    int64_t t_next = (int)threadIdx.x < B ? target[threadIdx.x] : 0;
+    for (int b = threadIdx.x; b < B; b += 1024) {
+        const int64_t t = t_next;
+        if (b + 1024 < B) t_next = target[b + 1024];             // the next row's target rides with this row's loads
+        const float* __restrict__ row = logp + (size_t)b * ldp;
+        const bool valid = t >= 0 && t < C;
+        const int tc = valid ? (int)t : -1;
+        float best = -INFINITY, term = 0.f;
+        int arg = 0;
+        bool finite = true;
+        for (int c0 = 0; c0 < C; c0 += G) {
+            float v[G];
+#pragma unroll
+            for (int j = 0; j < G; ++j) v[j] = c0 + j < C ? row[c0 + j] : 0.f;
+#pragma unroll
+            for (int j = 0; j < G; ++j) {
+                const int c = c0 + j;
+                if (c < C) {
+                    finite = finite && isfinite(v[j]);
+                    if (c == tc) term = v[j];
+                    if (best == best && (v[j] > best || v[j] != v[j])) { best = v[j]; arg = c; }
+                }
+            }
+        }
+        if (valid) s -= (double)term;
+        if (!valid) ++n_bad;
+        else if (arg == tc) ++n_correct;
+        if (!finite) ++n_nonfinite;
+    }
+    n_correct = wave_sum(n_correct);
+    n_bad = wave_sum(n_bad);
+    n_nonfinite = wave_sum(n_nonfinite);
+    if ((threadIdx.x & 63) == 0) {
+        const int w = threadIdx.x >> 6;
+        counts[0][w] = n_correct; counts[1][w] = n_bad; counts[2][w] = n_nonfinite;
+    }
+    s = block_sum<double, 16>(s, scratch);                        // (its barriers also publish `counts`)
+    if (threadIdx.x == 0) {
+        int tot[3] = {0, 0, 0};
+        for (int q = 0; q < 3; ++q)
+            for (int w = 0; w < 16; ++w) tot[q] += counts[q][w];
+        int64_t cnt[LBBNN_MONITOR_COUNTS];
+        double sum[LBBNN_MONITOR_SUMS];
+        double* sums = reinterpret_cast<double*>(totals + LBBNN_MONITOR_COUNTS);
+#pragma unroll
+        for (int q = 0; q < LBBNN_MONITOR_COUNTS; ++q) cnt[q] = totals[q];      // every load ahead of the first store
+#pragma unroll
+        for (int q = 0; q < LBBNN_MONITOR_SUMS; ++q) sum[q] = sums[q];
+        const double kl_term = kl ? (double)(*kl) * (double)kl_scale : 0.0;
+        const float lf = (float)(s + kl_term);
+        const bool ok = isfinite(lf);
+        *loss = lf;
+        if (guard) *guard = ok ? 0 : 1;
+        totals[LBBNN_MONITOR_STEPS] = cnt[LBBNN_MONITOR_STEPS] + 1;
+        totals[LBBNN_MONITOR_ROWS] = cnt[LBBNN_MONITOR_ROWS] + B;
+        totals[LBBNN_MONITOR_CORRECT] = cnt[LBBNN_MONITOR_CORRECT] + tot[0];
+        totals[LBBNN_MONITOR_BAD_TARGETS] = cnt[LBBNN_MONITOR_BAD_TARGETS] + tot[1];
+        totals[LBBNN_MONITOR_NONFINITE_ROWS] = cnt[LBBNN_MONITOR_NONFINITE_ROWS] + tot[2];
+        if (ok) {                                                 // (LBBNN_MONITOR_SKIPPED_STEPS is the optimizer's word: not written)
+            totals[LBBNN_MONITOR_NLL_ROWS] = cnt[LBBNN_MONITOR_NLL_ROWS] + (B - tot[1]);
+            sums[LBBNN_MONITOR_NLL_SUM] = sum[LBBNN_MONITOR_NLL_SUM] + s;
+            sums[LBBNN_MONITOR_KL_TERM_SUM] = sum[LBBNN_MONITOR_KL_TERM_SUM] + kl_term;
+            sums[LBBNN_MONITOR_LOSS_SUM] = sum[LBBNN_MONITOR_LOSS_SUM] + (s + kl_term);
+        } else {
+            totals[LBBNN_MONITOR_NONFINITE_STEPS] = cnt[LBBNN_MONITOR_NONFINITE_STEPS] + 1;
+        }
+        sums[LBBNN_MONITOR_LAST_NLL] = s;
+        sums[LBBNN_MONITOR_LAST_LOSS] = (double)lf;
+    }
 }
 
 __global__ __launch_bounds__(256) void elbo_loss_backward_kernel(const float* g, const int64_t* __restrict__ target, int B, int C,
@@ -72,6 +159,15 @@ extern "C" int lbbnn_elbo_loss(const float* logp, int ldp, const int64_t* target
     if (B <= 0 || C <= 0 || ldp < C) return LBBNN_E_SHAPE;
     hipLaunchKernelGGL(elbo_loss_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), logp, ldp, target, B, C, kl,
                        kl_scale, loss);
+    return (int)hipGetLastError();
+}
+
+extern "C" int lbbnn_elbo_loss_monitor(const float* logp, int ldp, const int64_t* target, int B, int C, const float* kl,
+                                       float kl_scale, float* loss, int64_t* totals, int32_t* guard, void* stream) {
+    if (!logp || !target || !loss || !totals) return LBBNN_E_NULL;
+    if (B <= 0 || C <= 0 || C > 64 || ldp < C) return LBBNN_E_SHAPE;
+    hipLaunchKernelGGL(elbo_loss_monitor_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), logp, ldp, target, B, C,
+                       kl, kl_scale, loss, totals, guard);
     return (int)hipGetLastError();
 }
 

@@ -5,6 +5,10 @@ what the reference's ``train()`` writes out (LBBNN-GP-MF-MNF.py:268-271; ...LRT.
 backward launch instead of torch's nll_loss / mul / add kernels (13 + 4 + 4 us forward, 6 us + fills backward for a
 4096 x 10 batch: the reduce kernel of nll_loss runs on a single workgroup).  The reference's own spelling keeps working; this
 is the faster one for callers that want it (``bnn_amd.parallel.DataParallelELBO.loss`` uses it on HIP tensors).
+
+``TrainMonitor`` is training's counterpart of ``evaluate.EvalAccumulator``: ``elbo_loss(..., monitor=mon)`` keeps the running
+totals of a training log (loss, nll, accuracy, bad labels, non-finite steps) on the device, in the loss launch itself, and
+leaves a per-step "loss is not finite" word there that ``optim.Adam`` / ``optim.SGD`` honour after ``set_guard(mon)``.
 """
 import torch
 import torch.nn.functional as F
@@ -23,17 +27,95 @@ _FUSE_LSM_BWD = _os.environ.get("LBBNN_FUSE_LSM_BWD", "1") != "0"     # A/B knob
 _LOGITS_GRAD = {}
 
 
+class TrainMonitor:
+    """Running totals of a training pass, kept on the device: ``elbo_loss(..., monitor=mon)`` adds a step to them inside its one
+    forward launch (lbbnn_elbo_loss_monitor; no host read, capturable as it is), ``result()`` reads them -- the ONLY
+    synchronisation, once per epoch in a training loop.  What the reference's ``train()`` prints per batch (LBBNN-GP-MF-MNF.py:
+    263-275: ``loss`` and ``nll``) are ``last_loss`` and ``last_nll``; the epoch means and the training accuracy come with them.
+
+    The monitor also holds the guard word: 1 after a step whose loss is not finite, 0 after any other (per step, not sticky).
+    ``optimizer.set_guard(mon)`` makes ``bnn_amd.optim.Adam`` / ``SGD`` skip the update of such a step on the device -- no
+    parameter, moment or step counter changes -- and count it in ``skipped_steps``; with ``max_grad_norm`` set, a step whose
+    gradient norm is NaN or infinite is skipped and counted too (``max_grad_norm=float("inf")``: a pure check, nothing is clipped).
+
+    ``classes`` (1 to 64) is fixed for the monitor's life.  Under ``graphs.make_graphed_train_step`` the factory's eager warm-up
+    steps are real steps and add to the totals: ``reset()`` after building the step.  The monitor is a plain holder of two
+    buffers (``to`` / ``_apply`` move them, ``copy.deepcopy`` gives a copy its own) and caches no device address; a captured
+    graph addresses the buffers it was captured with.  Not a data-parallel guard: the loss flag is local to a rank."""
+
+    def __init__(self, classes: int, device):
+        C = int(classes)
+        if not 1 <= C <= 64:
+            raise ValueError("bnn_amd: TrainMonitor takes 1 to 64 classes, got %d" % C)
+        self.classes = C
+        # one buffer, one read: the counts | the doubles (bit patterns); the guard word has its own (int32)
+        self._totals = torch.zeros(_lib.MONITOR_WORDS, dtype=torch.int64, device=torch.device(device))
+        self._guard = torch.zeros(1, dtype=torch.int32, device=self._totals.device)
+
+    @property
+    def device(self):
+        return self._totals.device
+
+    def _apply(self, fn):
+        self._totals, self._guard = fn(self._totals), fn(self._guard)
+        return self
+
+    def to(self, device):
+        return self._apply(lambda t: t.to(device))
+
+    def reset(self):
+        self._totals.zero_()
+        self._guard.zero_()
+
+    def _skipped_ptr(self):
+        return self._totals.data_ptr() + 8 * _lib.MONITOR_SKIPPED_STEPS
+
+    def _read(self):
+        """The totals as a host int64 array (the one device-to-host copy)."""
+        return self._totals.cpu().numpy()
+
+    def result(self, strict: bool = True):
+        """Python numbers.  Counts: ``steps``, ``rows``, ``correct`` (the arg-max of a row with a valid target equals it;
+        numpy.argmax's rule), ``bad_targets`` (outside [0, classes)), ``nonfinite_rows`` (rows with an inf or NaN
+        log-probability), ``nonfinite_steps`` (steps whose loss is inf or NaN), ``skipped_steps`` (optimizer steps a guard
+        skipped), ``nll_rows`` (rows with a valid target of the finite steps).  Sums over the FINITE steps, in fp64: ``nll_sum``,
+        ``kl_term_sum`` (kl / num_batches), ``loss_sum``; of the last step, finite or not: ``last_nll``, ``last_loss``.  Derived:
+        ``nll_mean`` = nll_sum / nll_rows, ``loss_mean`` = loss_sum / finite steps, ``accuracy`` = correct / rows with a valid
+        target -- NaN where the denominator is 0.  ``strict``: targets outside [0, classes) raise IndexError, as ``F.nll_loss``
+        would have; with ``strict=False`` they are reported in ``bad_targets``."""
+        import numpy as np
+        h = np.ascontiguousarray(self._read(), dtype=np.int64)
+        n = _lib.MONITOR_COUNTS
+        res = {k: int(h[i]) for i, k in enumerate(_lib.MONITOR_COUNT_NAMES)}
+        if strict and res["bad_targets"]:
+            raise IndexError("bnn_amd: %d target(s) outside [0, %d) in this training pass" % (res["bad_targets"], self.classes))
+        sums = h[n:n + _lib.MONITOR_SUMS].view(np.float64)
+        for i, k in enumerate(_lib.MONITOR_SUM_NAMES):
+            res[k] = float(sums[i])
+        div = lambda x, d: x / d if d else float("nan")
+        res["nll_mean"] = div(res["nll_sum"], res["nll_rows"])
+        res["loss_mean"] = div(res["loss_sum"], res["steps"] - res["nonfinite_steps"])
+        res["accuracy"] = div(res["correct"], res["rows"] - res["bad_targets"])
+        return res
+
+
 class _ElboLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, log_probs, target, kl, scale):
+    def forward(ctx, log_probs, target, kl, scale, monitor):
         B, C = log_probs.shape
         _LOGITS_GRAD.clear()                       # entries live for one backward pass only
         lp = log_probs if log_probs.stride(1) == 1 else log_probs.contiguous()
         loss = torch.empty((), dtype=torch.float32, device=lp.device)
         stream = torch.cuda.current_stream(lp.device).cuda_stream
-        _lib.check(_lib.lib().lbbnn_elbo_loss(lp.data_ptr(), lp.stride(0), target.data_ptr(), B, C,
-                                              kl.data_ptr() if kl is not None else None, float(scale), loss.data_ptr(), stream),
-                   "lbbnn_elbo_loss")
+        if monitor is not None:
+            _lib.check(_lib.lib().lbbnn_elbo_loss_monitor(lp.data_ptr(), lp.stride(0), target.data_ptr(), B, C,
+                                                          kl.data_ptr() if kl is not None else None, float(scale), loss.data_ptr(),
+                                                          monitor._totals.data_ptr(), monitor._guard.data_ptr(), stream),
+                       "lbbnn_elbo_loss_monitor")
+        else:
+            _lib.check(_lib.lib().lbbnn_elbo_loss(lp.data_ptr(), lp.stride(0), target.data_ptr(), B, C,
+                                                  kl.data_ptr() if kl is not None else None, float(scale), loss.data_ptr(), stream),
+                       "lbbnn_elbo_loss")
         ctx.save_for_backward(target, lp)
         ctx.meta = (B, C, float(scale), kl is not None)
         return loss
@@ -58,16 +140,57 @@ class _ElboLossFn(torch.autograd.Function):
         else:
             _lib.check(_lib.lib().lbbnn_elbo_loss_backward(g.data_ptr(), target.data_ptr(), B, C, scale, g_logp.data_ptr(),
                                                            g_kl.data_ptr() if has_kl else None, stream), "lbbnn_elbo_loss_backward")
-        return g_logp, None, g_kl, None
+        return g_logp, None, g_kl, None, None
 
 
-def elbo_loss(log_probs, target, kl=None, num_batches=1.0):
+def _fused_kl(kl) -> bool:
+    return kl is None or (torch.is_tensor(kl) and kl.is_cuda and kl.dtype == torch.float32 and kl.numel() == 1)
+
+
+def _check_monitored(log_probs, target, kl, monitor):
+    """A monitor rides in the fused forward launch: ValueError naming what keeps this call off that path."""
+    who = "bnn_amd: elbo_loss(monitor=...): "
+    if not isinstance(monitor, TrainMonitor):
+        raise ValueError(who + "monitor must be a bnn_amd.TrainMonitor, got %s" % type(monitor).__name__)
+    if log_probs.dtype != torch.float32 or log_probs.dim() != 2:
+        raise ValueError(who + "log_probs must be float32 (B, classes), got %s %s" % (log_probs.dtype, tuple(log_probs.shape)))
+    if log_probs.shape[1] != monitor.classes:
+        raise ValueError(who + "log_probs has %d classes, the monitor was built for %d" % (log_probs.shape[1], monitor.classes))
+    if log_probs.shape[0] < 1:
+        raise ValueError(who + "an empty batch has no step to record")
+    if not log_probs.is_cuda:
+        raise ValueError(who + "the monitor lives in the fused HIP loss; log_probs is on %s" % log_probs.device)
+    if log_probs.device != monitor.device:
+        raise ValueError(who + "log_probs is on %s, the monitor on %s" % (log_probs.device, monitor.device))
+    if target.dtype != torch.int64 or not target.is_contiguous():
+        raise ValueError(who + "target must be contiguous int64 class ids, got %s with strides %s"
+                         % (target.dtype, tuple(target.stride())))
+    if not _fused_kl(kl):
+        raise ValueError(who + "kl must be None or a one-element float32 HIP tensor")
+
+
+def elbo_loss(log_probs, target, kl=None, num_batches=1.0, *, monitor=None):
     """nll_loss(log_probs, target, reduction='sum') + kl / num_batches.  HIP tensors: the fused launches; anything else (the
-    CPU host-logic tests of bnn_amd.parallel run on oracle tensors): the same expression in torch ops."""
+    CPU host-logic tests of bnn_amd.parallel run on oracle tensors): the same expression in torch ops.
+
+    ``target`` must lie on the device of ``log_probs`` and hold one class id per row: anything else is a ValueError before a
+    pointer is handed to the library.  ``monitor``: a ``TrainMonitor`` whose totals and guard word this step is recorded in, by
+    the forward launch itself (lbbnn_elbo_loss_monitor); the loss and every gradient are bitwise those of the call without one.
+    A monitor needs the fused path -- float32 (B, monitor.classes) log-probabilities on the monitor's HIP device, int64 targets
+    -- and anything else is a ValueError naming the mismatch."""
+    if torch.is_tensor(target) and log_probs.dim() == 2:
+        if target.device != log_probs.device:
+            raise ValueError("bnn_amd: elbo_loss: target is on %s, log_probs on %s" % (target.device, log_probs.device))
+        if target.numel() != log_probs.shape[0]:
+            raise ValueError("bnn_amd: elbo_loss: target has %d element(s), log_probs %d row(s)"
+                             % (target.numel(), log_probs.shape[0]))
+    if monitor is not None:
+        _check_monitored(log_probs, target, kl, monitor)
+        return _ElboLossFn.apply(log_probs, target, kl if kl is None else kl.reshape(()), 1.0 / float(num_batches), monitor)
     if (log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.dim() == 2 and target.dtype == torch.int64
             and target.is_contiguous() and (kl is None or (torch.is_tensor(kl) and kl.is_cuda and kl.dtype == torch.float32
                                                            and kl.numel() == 1))):
-        return _ElboLossFn.apply(log_probs, target, kl if kl is None else kl.reshape(()), 1.0 / float(num_batches))
+        return _ElboLossFn.apply(log_probs, target, kl if kl is None else kl.reshape(()), 1.0 / float(num_batches), None)
     nll = F.nll_loss(log_probs, target, reduction="sum")
     return nll if kl is None else nll + kl / num_batches
 

@@ -19,6 +19,9 @@ Beyond torch.optim.Adam's keywords:
   ``set_grad_mask(param, mask)``   multiply ``param``'s gradient by ``mask`` inside the update (and inside the norm): the
                                    reference's COND_OPT, ``weight_mu.grad * gammas`` (LBBNN-GP-MF.py:333-336), without a hook.
 
+  ``set_guard(monitor)``           run every step behind a ``bnn_amd.TrainMonitor``'s guard word: a step after a non-finite loss
+                                   (or, with ``max_grad_norm``, a non-finite gradient norm) is skipped on the device and counted.
+
 Not supported (raise): ``amsgrad``, ``maximize``, sparse gradients, non-fp32 or CPU parameters, parameters on several devices.
 
 ``SGD`` is the same machinery (one base class) with ``torch.optim.SGD``'s constructor and update rule -- the optimizer of the
@@ -148,6 +151,16 @@ class _GroupsOptimizer(torch.optim.Optimizer):
         else:
             masks[id(param)] = mask
 
+    def set_guard(self, monitor):
+        """``monitor``: a ``bnn_amd.TrainMonitor`` -- every ``step()`` then runs behind its guard word (the ``_guarded`` entry
+        point): after a loss that is not finite, or with ``max_grad_norm`` set a gradient norm that is not, the step changes no
+        parameter, moment or step counter and adds 1 to the monitor's ``skipped_steps``, all on the device (a replayed graph
+        included: set the guard before building the graphed step).  ``None``: the plain step again.  Not part of ``state_dict``."""
+        from .losses import TrainMonitor
+        if monitor is not None and not isinstance(monitor, TrainMonitor):
+            raise TypeError(self._NAME + ".set_guard takes a bnn_amd.TrainMonitor or None, got %s" % type(monitor).__name__)
+        self.__dict__["_guard"] = monitor
+
     def add_param_group(self, param_group):
         super().add_param_group(param_group)
         self.__dict__.pop("_lists", None)                       # the tables regrow at the next step / push (outside capture)
@@ -244,11 +257,17 @@ class _GroupsOptimizer(torch.optim.Optimizer):
                 _lib.check(rc, "lbbnn_grad_sumsq")
                 off += counts[ci]
             scale = tab["scale"].data_ptr()
-        entry = getattr(lib, self._ENTRY)
+        guard = self.__dict__.get("_guard")
+        if guard is not None and guard.device != dev:
+            raise RuntimeError(self._NAME + ": the guard's monitor is on %s, the parameters on %s" % (guard.device, dev))
+        name = self._ENTRY if guard is None else self._ENTRY + "_guarded"
+        entry = getattr(lib, name)
+        # (every list of a guarded step reads the same guard word and scale; the last one, which advances, counts the skip)
+        extra = () if guard is None else (guard._guard.data_ptr(), guard._skipped_ptr())
         for ci, lst in enumerate(lists):
             rc = entry(ctypes.byref(lst), tab["hyper"].data_ptr(), tab["steps"].data_ptr(), tab["n"], scale,
-                       tab["ticket"].data_ptr(), 1 if ci == len(lists) - 1 else 0, stream)
-            _lib.check(rc, self._ENTRY)
+                       tab["ticket"].data_ptr(), 1 if ci == len(lists) - 1 else 0, *extra, stream)
+            _lib.check(rc, name)
         del keep
         return loss
 

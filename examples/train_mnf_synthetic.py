@@ -16,7 +16,6 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-import torch.nn.functional as F
 
 import bnn_amd
 from bnn_amd.mnf import BayesianNetwork            # was: class Gaussian / Bernoulli / BayesianLinear / BayesianNetwork inline
@@ -39,9 +38,17 @@ test_x = torch.rand(BATCH_SIZE, 1, 28, 28, device=DEVICE, generator=g)
 test_y = (test_x.view(BATCH_SIZE, 784) @ proj).argmax(-1)
 
 
+# The epoch's statistics stay on the device: the fused loss adds every step to the monitor's running totals inside its own
+# launch, and the optimizer runs behind the monitor's guard word, so a batch whose loss is not finite changes no parameter and
+# is counted instead.  One host read per epoch (monitor.result()) replaces train()'s print(loss) / print(nll) per batch (:272-275).
+monitor = bnn_amd.TrainMonitor(10, DEVICE)
+optimizer.set_guard(monitor)
+
+
 def elbo(net, data, target):
     outputs = net(data, sample=True)
-    return F.nll_loss(outputs, target, reduction="sum") + net.kl() / NUM_BATCHES
+    # = F.nll_loss(outputs, target, reduction="sum") + net.kl() / NUM_BATCHES, the reference's spelling, which still works
+    return bnn_amd.elbo_loss(outputs, target, net.kl(), NUM_BATCHES, monitor=monitor)
 
 
 net.train()
@@ -56,11 +63,16 @@ else:
         return loss
 
 for epoch in range(EPOCHS):
+    monitor.reset()                                 # (also drops the warm-up steps of the graphed step's factory)
     torch.cuda.synchronize(); t0 = time.perf_counter()
     for b in range(NUM_BATCHES):
         loss = step(train_x[b], train_y[b])
     torch.cuda.synchronize()
-    print("epoch %d  loss %.1f  (%.2f ms/iteration)" % (epoch, float(loss.detach()), (time.perf_counter() - t0) / NUM_BATCHES * 1e3))
+    ms = (time.perf_counter() - t0) / NUM_BATCHES * 1e3
+    m = monitor.result()                            # the epoch's one host read
+    print("epoch %d  nll %.4f per row  loss %.1f per batch (last batch: nll %.1f, loss %.1f)  accuracy %.3f  skipped steps %d  "
+          "(%.2f ms/iteration)" % (epoch, m["nll_mean"], m["loss_mean"], m["last_nll"], m["last_loss"], m["accuracy"],
+                                   m["skipped_steps"], ms))
 
 res = ensemble_eval(net, test_x, test_y, samples=TEST_SAMPLES)
 print("density %.3f | posterior mean %.3f | ensemble %.3f" % (float(res["density"].mean()),

@@ -1109,6 +1109,26 @@ typedef struct lbbnn_sgd_hyper {       /* one row of the device table; 20 bytes 
 int lbbnn_sgd_step_groups(const lbbnn_adam_group_list_t* list, const lbbnn_sgd_hyper_t* hyper, float* step, int n_groups,
                           const float* grad_scale, uint32_t* ticket, int advance, void* stream);
 
+/* lbbnn_adam_step_groups_guarded / lbbnn_sgd_step_groups_guarded -- the two list steps above behind a device-side guard: the
+ * found-inf flag of a training step that the host never looks at (a replayed graph).  Every workgroup reads, once, at its entry,
+ *   skip = (*guard != 0) || (grad_scale != NULL && !isfinite(*grad_scale))
+ * guard: one device int32, e.g. the word lbbnn_elbo_loss_monitor writes; the second term makes clipping a gradient check
+ * (lbbnn_grad_sumsq leaves a NaN scale for a NaN or infinite norm; max_norm = inf gives a scale of exactly 1 otherwise).
+ * skip == 0: the same device code as the unguarded entry point, bitwise its result.
+ * skip != 0: no workgroup reads or writes p, m or v; with advance != 0 the workgroup that finishes last does NOT advance the
+ *   counters, adds 1 to *skipped (int64, nullable; a plain read-modify-write by one thread: launches of one stream are ordered)
+ *   and leaves the ticket at zero as always.  A step of several lists reads the same two words in every launch and counts the
+ *   skip once, in the launch with advance != 0.
+ * Both words are written by earlier launches of the stream and by nothing in this launch, so every workgroup sees the same
+ * value whenever it runs.  One launch per call, as for the unguarded entry points.
+ * Checks (before any HIP call): those of the unguarded entry point, and guard NULL: LBBNN_E_NULL. */
+int lbbnn_adam_step_groups_guarded(const lbbnn_adam_group_list_t* list, const lbbnn_adam_hyper_t* hyper, float* step, int n_groups,
+                                   const float* grad_scale, uint32_t* ticket, int advance, const int32_t* guard, int64_t* skipped,
+                                   void* stream);
+int lbbnn_sgd_step_groups_guarded(const lbbnn_adam_group_list_t* list, const lbbnn_sgd_hyper_t* hyper, float* step, int n_groups,
+                                  const float* grad_scale, uint32_t* ticket, int advance, const int32_t* guard, int64_t* skipped,
+                                  void* stream);
+
 /* lbbnn_grad_sumsq -- global L2 norm of the (masked) gradients of a list, for torch.nn.utils.clip_grad_norm_'s clipping
  * applied inside lbbnn_adam_step_groups (p / m / v / group of the list are not read).  Launch 1: workgroup b of the list
  * (tensor i owns ceil(numel[i] / LBBNN_ADAM_CHUNK) consecutive workgroups, tensors in list order) writes
@@ -1299,6 +1319,47 @@ int lbbnn_elbo_loss(const float* logp, int ldp, const int64_t* target, int B, in
                     float* loss, void* stream);
 int lbbnn_elbo_loss_backward(const float* g, const int64_t* target, int B, int C, float kl_scale, float* g_logp, float* g_kl,
                              void* stream);
+/* lbbnn_elbo_loss_monitor -- lbbnn_elbo_loss with the running totals of a training log and a per-step "loss is not finite"
+ * flag, in the SAME single launch of one workgroup.  *loss is bitwise what lbbnn_elbo_loss writes for the same arguments (the
+ * same terms, added in the same order).  The backward launches are lbbnn_elbo_loss_backward[_logits], unchanged.
+ * totals: LBBNN_MONITOR_WORDS device int64 words that every call ADDS to (the caller zeroes them); LBBNN_MONITOR_COUNTS counts,
+ * then LBBNN_MONITOR_SUMS doubles stored as their bit patterns.  Counts, at these indices:
+ *   LBBNN_MONITOR_STEPS            calls
+ *   LBBNN_MONITOR_ROWS             B
+ *   LBBNN_MONITOR_CORRECT          rows with a valid target whose arg-max over the C log-probabilities equals it, by
+ *                                  numpy.argmax's rule: a NaN compares as the maximum, the lowest index of the maximum wins
+ *   LBBNN_MONITOR_BAD_TARGETS      rows with target < 0 or >= C (no loss term, no gradient, not in `correct`)
+ *   LBBNN_MONITOR_NONFINITE_ROWS   rows whose C log-probabilities are not all finite
+ *   LBBNN_MONITOR_NONFINITE_STEPS  calls whose *loss is inf or NaN
+ *   LBBNN_MONITOR_SKIPPED_STEPS    not written here: the slot the guarded optimizer steps count in (`skipped`, below)
+ *   LBBNN_MONITOR_NLL_ROWS         rows with a valid target of the calls whose *loss is finite: what nll_sum is a sum over
+ * Sums (index LBBNN_MONITOR_COUNTS + ...), with nll = -sum_b logp[b][target[b]] and kl_term = kl ? *kl * kl_scale : 0 in fp64:
+ *   LBBNN_MONITOR_NLL_SUM, LBBNN_MONITOR_KL_TERM_SUM, LBBNN_MONITOR_LOSS_SUM   += nll, kl_term, nll + kl_term -- ONLY on a call
+ *                                  whose *loss is finite, so that one bad batch does not destroy the means of an epoch
+ *   LBBNN_MONITOR_LAST_NLL, LBBNN_MONITOR_LAST_LOSS   overwritten by every call: nll, and (double)*loss -- what train() prints
+ * guard (nullable): one device int32, OVERWRITTEN by every call: 1 when *loss is not finite, else 0 (per step, not sticky).
+ * One workgroup and the order of a stream's launches make plain read-modify-writes by one thread enough: no atomics, every
+ * total the same bits from run to run.  One monitor may have one such launch in flight at a time (launches of one stream are).
+ * Checks (before any HIP call): logp / target / loss / totals NULL: LBBNN_E_NULL; B <= 0, C <= 0, C > 64, ldp < C:
+ * LBBNN_E_SHAPE.  kl and guard are nullable. */
+#define LBBNN_MONITOR_COUNTS 8
+#define LBBNN_MONITOR_STEPS 0
+#define LBBNN_MONITOR_ROWS 1
+#define LBBNN_MONITOR_CORRECT 2
+#define LBBNN_MONITOR_BAD_TARGETS 3
+#define LBBNN_MONITOR_NONFINITE_ROWS 4
+#define LBBNN_MONITOR_NONFINITE_STEPS 5
+#define LBBNN_MONITOR_SKIPPED_STEPS 6
+#define LBBNN_MONITOR_NLL_ROWS 7
+#define LBBNN_MONITOR_SUMS 5
+#define LBBNN_MONITOR_NLL_SUM 0
+#define LBBNN_MONITOR_KL_TERM_SUM 1
+#define LBBNN_MONITOR_LOSS_SUM 2
+#define LBBNN_MONITOR_LAST_NLL 3
+#define LBBNN_MONITOR_LAST_LOSS 4
+#define LBBNN_MONITOR_WORDS (LBBNN_MONITOR_COUNTS + LBBNN_MONITOR_SUMS)
+int lbbnn_elbo_loss_monitor(const float* logp, int ldp, const int64_t* target, int B, int C, const float* kl, float kl_scale,
+                            float* loss, int64_t* totals, int32_t* guard, void* stream);
 /* lbbnn_elbo_loss_backward and, in the same launch, the gradient with respect to the LOGITS when `logp` is the log_softmax of a
  * layer's logits (what lbbnn_log_softmax_backward would make of g_logp: bitwise the same): g_logits (B,C dense). */
 int lbbnn_elbo_loss_backward_logits(const float* g, const int64_t* target, const float* logp, int ldp, int B, int C,
