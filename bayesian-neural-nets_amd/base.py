@@ -600,7 +600,6 @@ class BayesianNetwork(nn.Module):
         ``out`` when given), or with ``log_probs`` (one unit) the (S, B, 2) log-probabilities, a tensor of its own."""
         from . import evaluate
         evaluate._check_log_probs(self, log_probs)
-        sigmoid = self.head == "sigmoid"
         if not input.is_cuda:
             raise RuntimeError("bnn_amd: sample_predict needs a HIP device tensor (input is on %s); there is no CPU path"
                                % input.device)
@@ -634,31 +633,14 @@ class BayesianNetwork(nn.Module):
         for k, cnt in _lib.layer_groups(n):                    # every group reads the same offset; the caller advances once
             _lib.check(_lib.lib().lbbnn_gate_members(_lib.group_slice(descs, k, cnt), cnt, S, mode, T, rng.data_ptr(), 1, stream),
                        "lbbnn_gate_members")
-        h, h_ms, ldx = x, 0, x.stride(0)
-        for k, l in enumerate(layers):
-            O, I, ld = l.out_features, l.in_features, ops.operand_ld(l.in_features)
-            o_ms = -(-(B * O) // 4) * 4                       # member stride padded to 16 B
-            head = k == n - 1
-            if head and out is not None:
-                o = out
-                if o.dim() != 2 or o.shape[0] != S or o.shape[1] < B * O or o.stride(0) % 4 or not o.is_contiguous():
-                    raise RuntimeError("bnn_amd: out must be a contiguous (S, >= B*classes) buffer with 16-B aligned rows")
-                o_ms = o.stride(0)
-            else:
-                o = torch.empty((S, o_ms), **f)
-            flags = (ops.F_RELU if not head else (ops.F_LOG_SOFTMAX if O <= 16 and not sigmoid else 0)) | \
-                    (ops.F_SPLIT16 if splits[k] else 0)
-            rc = _lib.lib().lbbnn_gemm_members_mean(h.data_ptr(), ldx, h_ms, bufs[k]["w"].data_ptr(), O * ld, ld,
-                                                   bufs[k]["bias"].data_ptr(), O, o.data_ptr(), O, o_ms, B, I, O, flags, S,
-                                                   stream)
-            _lib.check(rc, "lbbnn_gemm_members_mean")
-            h, h_ms, ldx = o, o_ms, O
-        if sigmoid:
-            res = evaluate._binary_members(h, S, B, self.dims[-1], log_probs)
-        else:
-            res = h[:, :B * self.dims[-1]].view(S, B, self.dims[-1])
-            if self.dims[-1] > 16:
-                res = F.log_softmax(res, dim=-1)
+        C = self.dims[-1]
+        if out is None:
+            out = torch.empty((S, ops.pad4(B * C)), **f)
+        elif out.dim() != 2 or out.shape[0] != S or out.shape[1] < B * C or out.stride(0) % 4 or not out.is_contiguous():
+            raise RuntimeError("bnn_amd: out must be a contiguous (S, >= B*classes) buffer with 16-B aligned rows")
+        ops.member_gemm_chain(x, S, [(b["w"], b["bias"], s) for b, s in zip(bufs, splits)], head=self.head, out=out,
+                              stream=stream)
+        res = evaluate._members_result(out, S, B, C, self.head, log_probs)
         for l in layers:
             l.log_prior, l.log_variational_posterior = 0, 0          # an evaluation forward keeps no log-probabilities (:253)
         return (res, [b["rows"] for b in bufs] if rows else None, [b["gates"] for b in bufs] if keep_gates else None)
@@ -686,7 +668,7 @@ class BayesianNetwork(nn.Module):
             # (the chains write their logits into ``out`` itself and the head goes over it as one block: looked at first)
             if out is not None and (out.dim() != 2 or out.shape[0] != S or out.shape[1] < B * C or not out.is_contiguous()):
                 raise RuntimeError("bnn_amd: out must be a contiguous (S, >= B*classes) buffer")
-            logits = out if out is not None else torch.empty((S, -(-(B * C) // 4) * 4), dtype=torch.float32, device=x.device)
+            logits = out if out is not None else torch.empty((S, ops.pad4(B * C)), dtype=torch.float32, device=x.device)
         else:
             res = torch.empty((S, B, C), dtype=torch.float32, device=x.device)
         g_rows = [torch.empty((S, l.out_features), dtype=torch.float32, device=x.device) for l in layers] if rows else None

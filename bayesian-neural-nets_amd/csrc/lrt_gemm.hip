@@ -996,16 +996,21 @@ int launch_split(GemmArgs& a, bool mean_only, hipStream_t s, bool* hosted) {
 
 }  // namespace
 
-static int lrt_gemm_impl(const float* x, int ldx, const void* e_w, const void* var_w, int ld,
-                         const float* bias_mean, const float* bias_var, const float* var_scale,
-                         const float* eps, const uint64_t* rng, uint32_t rng_stream, int64_t row_offset,
-                         float* out, int ldo, float* std_out, int B, int I, int O, int flags, void* stream, int kchunk = 0,
-                         const FinalizePiggy* fin = nullptr, bool* hosted = nullptr,
-                         const float* comb_x = nullptr, int ld_cx = 0, const float* comb_add = nullptr, int ld_ca = 0,
-                         int members = 1, long long x_ms = 0, long long w_ms = 0, long long o_ms = 0,
-                         unsigned long long m_adv = 0, long long b_ms = 0, int fan = 0) {
+// The call record of every product is the kernels' GemmArgs.  An entry point takes gemm_args(): zero (= off) everywhere but the
+// ten fields every call has and members = 1.  It sets what its form needs by name and hands the record to lrt_gemm_dispatch,
+// which validates it, derives relu / log_softmax / single16 / split_stride / m_off from `flags`, picks the tile and launches.
+static GemmArgs gemm_args(const float* x, int ldx, const void* e_w, const void* var_w, int ld, float* out, int ldo,
+                          int B, int I, int O) {
+    GemmArgs a{};
+    a.x = x; a.e_w = static_cast<const float*>(e_w); a.var_w = static_cast<const float*>(var_w); a.out = out;
+    a.ldx = ldx; a.ld = ld; a.ldo = ldo; a.B = B; a.I = I; a.O = O; a.members = 1;
+    return a;
+}
+
+static int lrt_gemm_dispatch(GemmArgs& a, int flags, void* stream, bool* hosted = nullptr) {
+    const int B = a.B, I = a.I, O = a.O, ldx = a.ldx, ld = a.ld, ldo = a.ldo, fan = a.fan;
     if (B == 0 && I > 0 && O > 0) return 0;        // empty batch (torch.mm of 0 rows, LBBNN-GP-MF-LRT.py:172): nothing to do
-    if (!x || !e_w || !out) return LBBNN_E_NULL;
+    if (!a.x || !a.e_w || !a.out) return LBBNN_E_NULL;
     if (B <= 0 || I <= 0 || O <= 0 || ldx < I || ldo < O) return LBBNN_E_SHAPE;
     if (flags & ~(LBBNN_F_RELU | LBBNN_F_MEAN_ONLY | LBBNN_F_SPLIT16 | LBBNN_F_LOG_SOFTMAX | LBBNN_F_SINGLE16 | LBBNN_F_HALF16))
         return LBBNN_E_FLAGS;
@@ -1014,28 +1019,19 @@ static int lrt_gemm_impl(const float* x, int ldx, const void* e_w, const void* v
     if ((flags & LBBNN_F_SINGLE16) && !(flags & LBBNN_F_SPLIT16)) return LBBNN_E_FLAGS;
     const bool split = (flags & LBBNN_F_SPLIT16) != 0;
     const bool mean_only = (flags & LBBNN_F_MEAN_ONLY) != 0;
-    if (!mean_only && !var_w) return LBBNN_E_NULL;
-    if (!mean_only && !eps && !rng) return LBBNN_E_NOISE;
+    if (!mean_only && !a.var_w) return LBBNN_E_NULL;
+    if (!mean_only && !a.eps && !a.rng) return LBBNN_E_NOISE;
     if (ld < I || (ld & 31)) return LBBNN_E_ALIGN;
-    if ((reinterpret_cast<uintptr_t>(e_w) & 15u) || (var_w && (reinterpret_cast<uintptr_t>(var_w) & 15u))) return LBBNN_E_ALIGN;
+    if ((reinterpret_cast<uintptr_t>(a.e_w) & 15u) || (reinterpret_cast<uintptr_t>(a.var_w) & 15u)) return LBBNN_E_ALIGN;
 
-    GemmArgs a;
-    a.x = x; a.e_w = static_cast<const float*>(e_w); a.var_w = static_cast<const float*>(var_w);
-    a.bias_mean = bias_mean; a.bias_var = bias_var; a.var_scale = var_scale;
-    a.eps = eps; a.rng = rng; a.out = out; a.std_out = std_out; a.row_offset = row_offset;
-    a.ldx = ldx; a.ld = ld; a.ldo = ldo; a.B = B; a.I = I; a.O = O;
-    a.rng_stream = rng_stream; a.relu = (flags & LBBNN_F_RELU) ? 1 : 0;
-    a.log_softmax = (flags & LBBNN_F_LOG_SOFTMAX) ? 1 : 0;
-    a.kchunk = kchunk; a.split_stride = (long long)B * ldo;
-    if (fin) a.fin = *fin; else a.fin = FinalizePiggy{};
-    a.comb_x = comb_x; a.comb_add = comb_add; a.ld_cx = ld_cx; a.ld_ca = ld_ca;
+    a.relu = (flags & LBBNN_F_RELU) ? 1 : 0; a.log_softmax = (flags & LBBNN_F_LOG_SOFTMAX) ? 1 : 0;
     a.single16 = (flags & LBBNN_F_HALF16) ? 2 : ((flags & LBBNN_F_SINGLE16) ? 1 : 0);
-    a.members = members; a.x_ms = x_ms; a.w_ms = w_ms; a.o_ms = o_ms; a.b_ms = b_ms; a.m_adv = m_adv; a.m_off = 0;
-    a.fan = fan;
-    if (members > 1 && (kchunk || fin || eps || std_out || comb_x)) return LBBNN_E_FLAGS;
-    if (fan && (members != 1 || mean_only || kchunk || fin || eps || std_out || comb_x || a.log_softmax)) return LBBNN_E_FLAGS;
+    a.split_stride = (long long)B * ldo; a.m_off = 0;
+    const bool solo = a.kchunk || a.fin.n > 0 || a.eps || a.std_out || a.comb_x;      // forms that no member launch carries
+    if (a.members > 1 && solo) return LBBNN_E_FLAGS;
+    if (fan && (a.members != 1 || mean_only || solo || a.log_softmax)) return LBBNN_E_FLAGS;
 
-    const bool xvec = ((I & 3) == 0) && ((ldx & 3) == 0) && ((reinterpret_cast<uintptr_t>(x) & 15u) == 0);
+    const bool xvec = ((I & 3) == 0) && ((ldx & 3) == 0) && ((reinterpret_cast<uintptr_t>(a.x) & 15u) == 0);
     hipStream_t s = static_cast<hipStream_t>(stream);
     // Tile choice: 80(o) x 128(b) fills the chip for the headline shapes (B=4096, O=1200 -> 15x32 = 480
     // workgroups, 2 resident per CU); small problems take a 80x32 tile for more workgroups; a skinny
@@ -1076,8 +1072,8 @@ extern "C" int lbbnn_lrt_gemm(const float* x, int ldx, const void* e_w, const vo
                               const float* bias_mean, const float* bias_var, const float* var_scale,
                               const float* eps, const uint64_t* rng, uint32_t rng_stream, int64_t row_offset,
                               float* out, int ldo, int B, int I, int O, int flags, void* stream) {
-    return lrt_gemm_impl(x, ldx, e_w, var_w, ld, bias_mean, bias_var, var_scale, eps, rng, rng_stream, row_offset,
-                         out, ldo, nullptr, B, I, O, flags, stream);
+    return lbbnn_lrt_gemm_train(x, ldx, e_w, var_w, ld, bias_mean, bias_var, var_scale, eps, rng, rng_stream, row_offset,
+                                out, ldo, nullptr, B, I, O, flags, stream);
 }
 
 extern "C" int lbbnn_lrt_gemm_train(const float* x, int ldx, const void* e_w, const void* var_w, int ld,
@@ -1086,33 +1082,29 @@ extern "C" int lbbnn_lrt_gemm_train(const float* x, int ldx, const void* e_w, co
                                     float* out, int ldo, float* std_out, int B, int I, int O, int flags, void* stream) {
     if ((flags & LBBNN_F_MEAN_ONLY) && std_out) return LBBNN_E_FLAGS;
     // (log_softmax + std_out is the training forward of the 10-class head: the backward needs sqrt(var), not the logits)
-    return lrt_gemm_impl(x, ldx, e_w, var_w, ld, bias_mean, bias_var, var_scale, eps, rng, rng_stream, row_offset,
-                         out, ldo, std_out, B, I, O, flags, stream);
+    GemmArgs a = gemm_args(x, ldx, e_w, var_w, ld, out, ldo, B, I, O);
+    a.bias_mean = bias_mean; a.bias_var = bias_var; a.var_scale = var_scale;
+    a.eps = eps; a.rng = rng; a.rng_stream = rng_stream; a.row_offset = row_offset; a.std_out = std_out;
+    return lrt_gemm_dispatch(a, flags, stream);
 }
 
-// lbbnn_lrt_gemm with the KL finalize of a whole network carried by one extra workgroup of the same launch (include/lbbnn.h)
-static int gemm_finalize_impl(const float* x, int ldx, const void* e_w, const void* var_w, int ld,
-                              const float* bias_mean, const float* bias_var, const float* var_scale,
-                              const float* eps, const uint64_t* rng, uint32_t rng_stream, int64_t row_offset,
-                              float* out, int ldo, float* std_out, int B, int I, int O, int flags,
-                              const lbbnn_layer_desc_t* layers, int n, const uint64_t* fin_rng, float* kl_total,
-                              uint64_t* rng_live, uint64_t advance, void* stream) {
-    if ((flags & LBBNN_F_MEAN_ONLY) && std_out) return LBBNN_E_FLAGS;
+// lbbnn_lrt_gemm_train (record `a`) with the KL finalize of a whole network carried by one extra workgroup of the same launch
+static int gemm_finalize_impl(GemmArgs& a, int flags, const lbbnn_layer_desc_t* layers, int n, const uint64_t* fin_rng,
+                              float* kl_total, uint64_t* rng_live, uint64_t advance, void* stream) {
+    if ((flags & LBBNN_F_MEAN_ONLY) && a.std_out) return LBBNN_E_FLAGS;
     if (n == 0) {
         // nothing to finalize (a forward without KL): the plain GEMM, then the advance as the tiny launch it is
-        const int rc = lrt_gemm_impl(x, ldx, e_w, var_w, ld, bias_mean, bias_var, var_scale, eps, rng, rng_stream, row_offset,
-                                     out, ldo, std_out, B, I, O, flags, stream, 0);
+        const int rc = lrt_gemm_dispatch(a, flags, stream);
         if (rc || !rng_live || !advance) return rc;
         return lbbnn_rng_advance(rng_live, advance, stream);
     }
-    FinalizePiggy fin{};
+    FinalizePiggy& fin = a.fin;
     if (const int rc = fill_finalize_args(layers, n, fin_rng, fin.l, fin.active)) return rc;
     if (kl_total) for (int i = 0; i < n; ++i) if (!fin.active[i]) return LBBNN_E_NULL;   // a total needs every layer's KL
     fin.n = n; fin.total = kl_total;
     fin.rng_adv = advance ? rng_live : nullptr; fin.adv = advance;
     bool hosted = false;
-    const int rc = lrt_gemm_impl(x, ldx, e_w, var_w, ld, bias_mean, bias_var, var_scale, eps, rng, rng_stream, row_offset,
-                                 out, ldo, std_out, B, I, O, flags, stream, 0, &fin, &hosted);
+    const int rc = lrt_gemm_dispatch(a, flags, stream, &hosted);
     if (rc) return rc;
     if (hosted) return 0;
     // this GEMM's kernel cannot host the extra workgroup (small tile configuration, skinny output, LDS): same work, own launch
@@ -1127,8 +1119,10 @@ extern "C" int lbbnn_lrt_gemm_finalize(const float* x, int ldx, const void* e_w,
                                        const lbbnn_layer_desc_t* layers, int n, const uint64_t* fin_rng, float* kl_total,
                                        void* stream) {
     if (n <= 0) return LBBNN_E_SHAPE;
-    return gemm_finalize_impl(x, ldx, e_w, var_w, ld, bias_mean, bias_var, var_scale, eps, rng, rng_stream, row_offset, out, ldo,
-                              std_out, B, I, O, flags, layers, n, fin_rng, kl_total, nullptr, 0, stream);
+    GemmArgs a = gemm_args(x, ldx, e_w, var_w, ld, out, ldo, B, I, O);
+    a.bias_mean = bias_mean; a.bias_var = bias_var; a.var_scale = var_scale;
+    a.eps = eps; a.rng = rng; a.rng_stream = rng_stream; a.row_offset = row_offset; a.std_out = std_out;
+    return gemm_finalize_impl(a, flags, layers, n, fin_rng, kl_total, nullptr, 0, stream);
 }
 
 extern "C" int lbbnn_lrt_gemm_finalize_adv(const float* x, int ldx, const void* e_w, const void* var_w, int ld,
@@ -1139,8 +1133,10 @@ extern "C" int lbbnn_lrt_gemm_finalize_adv(const float* x, int ldx, const void* 
                                            uint64_t* rng_live, uint64_t advance, void* stream) {
     if (n < 0 || (n > 0 && !layers)) return LBBNN_E_SHAPE;
     if (advance && !rng_live) return LBBNN_E_NULL;
-    return gemm_finalize_impl(x, ldx, e_w, var_w, ld, bias_mean, bias_var, var_scale, eps, rng, rng_stream, row_offset, out, ldo,
-                              std_out, B, I, O, flags, layers, n, fin_rng, kl_total, rng_live, advance, stream);
+    GemmArgs a = gemm_args(x, ldx, e_w, var_w, ld, out, ldo, B, I, O);
+    a.bias_mean = bias_mean; a.bias_var = bias_var; a.var_scale = var_scale;
+    a.eps = eps; a.rng = rng; a.rng_stream = rng_stream; a.row_offset = row_offset; a.std_out = std_out;
+    return gemm_finalize_impl(a, flags, layers, n, fin_rng, kl_total, rng_live, advance, stream);
 }
 
 // An ensemble of `members` forwards of one layer in ONE launch (include/lbbnn.h)
@@ -1154,9 +1150,10 @@ extern "C" int lbbnn_lrt_gemm_members(const float* x, int ldx, int64_t x_mstride
     if ((x_mstride & 3) || (w_mstride & 3) || (o_mstride & 3)) return LBBNN_E_ALIGN;       // every member 16-B aligned (pad the stride)
     if (flags & LBBNN_F_SPLIT16)                                                           // 32-bit buffer offsets
         if (((size_t)(B - 1) * ldx + I) * 4 >= 0x7FFFFFF0u) return LBBNN_E_SHAPE;
-    return lrt_gemm_impl(x, ldx, e_w, var_w, ld, bias_mean, bias_var, nullptr, nullptr, rng, rng_stream, row_offset, out, ldo,
-                         nullptr, B, I, O, flags, stream, 0, nullptr, nullptr, nullptr, 0, nullptr, 0, members,
-                         (long long)x_mstride, (long long)w_mstride, (long long)o_mstride, member_advance);
+    GemmArgs a = gemm_args(x, ldx, e_w, var_w, ld, out, ldo, B, I, O);
+    a.bias_mean = bias_mean; a.bias_var = bias_var; a.rng = rng; a.rng_stream = rng_stream; a.row_offset = row_offset;
+    a.members = members; a.x_ms = x_mstride; a.w_ms = w_mstride; a.o_ms = o_mstride; a.m_adv = member_advance;
+    return lrt_gemm_dispatch(a, flags, stream);
 }
 
 // Variational dropout's dual-moment GEMM for every member of an ensemble in ONE launch (include/lbbnn.h): shared weight
@@ -1176,10 +1173,11 @@ extern "C" int lbbnn_vd_gemm_members(const float* x, int ldx, int64_t x_mstride,
     if (!rng) return LBBNN_E_NOISE;
     if (flags & LBBNN_F_SPLIT16)                                                           // 32-bit buffer offsets
         if (((size_t)(B - 1) * ldx + I) * 4 >= 0x7FFFFFF0u) return LBBNN_E_SHAPE;
-    return lrt_gemm_impl(x, ldx, e_w, var_w, ld, nullptr, nullptr, var_scale, nullptr, rng, rng_stream, row_offset, out, ldo,
-                         nullptr, B, I, O, flags, stream, 0, nullptr, nullptr, nullptr, 0, nullptr, 0,
-                         fanout ? 1 : members, (long long)x_mstride, 0ll, (long long)o_mstride, member_advance, 0ll,
-                         fanout ? members : 0);
+    GemmArgs a = gemm_args(x, ldx, e_w, var_w, ld, out, ldo, B, I, O);
+    a.var_scale = var_scale; a.rng = rng; a.rng_stream = rng_stream; a.row_offset = row_offset;
+    a.x_ms = x_mstride; a.o_ms = o_mstride; a.m_adv = member_advance;
+    if (fanout) a.fan = members; else a.members = members;
+    return lrt_gemm_dispatch(a, flags, stream);
 }
 
 // The mean-only product of every member of an ensemble in ONE launch, each member with its own weights and bias
@@ -1198,9 +1196,9 @@ extern "C" int lbbnn_gemm_members_mean(const float* x, int ldx, int64_t x_mstrid
     if ((x_mstride & 3) || (w_mstride & 3) || (o_mstride & 3)) return LBBNN_E_ALIGN;       // every member 16-B aligned
     if (flags & LBBNN_F_SPLIT16)                                                           // 32-bit buffer offsets
         if (((size_t)(B - 1) * ldx + I) * 4 >= 0x7FFFFFF0u) return LBBNN_E_SHAPE;
-    return lrt_gemm_impl(x, ldx, w, nullptr, ld, bias, nullptr, nullptr, nullptr, nullptr, 0u, 0, out, ldo, nullptr,
-                         B, I, O, flags | LBBNN_F_MEAN_ONLY, stream, 0, nullptr, nullptr, nullptr, 0, nullptr, 0, members,
-                         (long long)x_mstride, (long long)w_mstride, (long long)o_mstride, 0ull, (long long)b_mstride);
+    GemmArgs a = gemm_args(x, ldx, w, nullptr, ld, out, ldo, B, I, O);
+    a.bias_mean = bias; a.members = members; a.x_ms = x_mstride; a.w_ms = w_mstride; a.o_ms = o_mstride; a.b_ms = b_mstride;
+    return lrt_gemm_dispatch(a, flags | LBBNN_F_MEAN_ONLY, stream);
 }
 
 // Mean-only product with the input-gradient combination in its epilogue (include/lbbnn.h)
@@ -1211,14 +1209,16 @@ extern "C" int lbbnn_lrt_gemm_combine(const float* x, int ldx, const void* w_op,
     if (ld_cx < O || ld_ca < O) return LBBNN_E_SHAPE;
     if (flags & ~LBBNN_F_SPLIT16) return LBBNN_E_FLAGS;
     if (O <= 16) return LBBNN_E_SHAPE;                       // (the skinny kernel has its own epilogue)
-    return lrt_gemm_impl(x, ldx, w_op, nullptr, ld, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0, out, ldo, nullptr,
-                         B, I, O, flags | LBBNN_F_MEAN_ONLY, stream, 0, nullptr, nullptr, comb_x, ld_cx, comb_add, ld_ca);
+    GemmArgs a = gemm_args(x, ldx, w_op, nullptr, ld, out, ldo, B, I, O);
+    a.comb_x = comb_x; a.ld_cx = ld_cx; a.comb_add = comb_add; a.ld_ca = ld_ca;
+    return lrt_gemm_dispatch(a, flags | LBBNN_F_MEAN_ONLY, stream);
 }
 
 // Split-K plain product on the bf16x3 kernel: out[z] = x[:, Kz] . w[:, Kz]^T for the k ranges Kz = [z*kchunk, (z+1)*kchunk).
 extern "C" int lbbnn_matmul_splitk(const float* x, int ldx, const void* w_op, int ld, float* out, int ldo,
                                    int B, int I, int O, int kchunk, void* stream) {
     if (kchunk <= 0 || (kchunk & 31)) return LBBNN_E_ALIGN;
-    return lrt_gemm_impl(x, ldx, w_op, nullptr, ld, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0, out, ldo, nullptr,
-                         B, I, O, LBBNN_F_MEAN_ONLY | LBBNN_F_SPLIT16, stream, kchunk);
+    GemmArgs a = gemm_args(x, ldx, w_op, nullptr, ld, out, ldo, B, I, O);
+    a.kchunk = kchunk;
+    return lrt_gemm_dispatch(a, LBBNN_F_MEAN_ONLY | LBBNN_F_SPLIT16, stream);
 }

@@ -69,6 +69,26 @@ def _binary_members(buf: torch.Tensor, S: int, B: int, O: int, log_probs: bool) 
     return buf[:, :B * O].view(S, B, O)
 
 
+def _members_result(buf: torch.Tensor, S: int, B: int, C: int, head: str, log_probs: bool) -> torch.Tensor:
+    """The (S, >= pad4(B * C)) buffer the last member GEMM wrote as the (S, B, C) result: the sigmoid head's one launch, a view
+    where the GEMM applied log_softmax itself (C <= 16), torch's log_softmax otherwise."""
+    if head == "sigmoid":
+        return _binary_members(buf, S, B, C, log_probs)
+    outputs = buf[:, :B * C].view(S, B, C)
+    return outputs if C <= 16 else torch.log_softmax(outputs, dim=-1)
+
+
+def _member_counts(samples, max_members):
+    """(S, chunk) of an ensemble call: the members, and how many of them one launch takes (default: all)."""
+    S = int(samples)
+    if S < 1:
+        raise ValueError("bnn_amd: samples must be >= 1")
+    chunk = S if max_members is None else int(max_members)
+    if chunk < 1:
+        raise ValueError("bnn_amd: max_members must be >= 1")
+    return S, chunk
+
+
 def _forward_head(net, data, sample: bool, log_probs: bool):
     """net(data, sample) of an LRT / MNF network; with ``log_probs`` the sigmoid head's 2-class log-probabilities."""
     if not log_probs:
@@ -110,7 +130,6 @@ def ensemble_forward_batched(net, data: torch.Tensor, samples: int = 10, *, log_
     import ctypes
     from . import _lib
     _check_log_probs(net, log_probs)
-    sigmoid = _head_of(net) == "sigmoid"
     net.eval()
     S = int(samples)
     layers = net._layers()
@@ -124,15 +143,15 @@ def ensemble_forward_batched(net, data: torch.Tensor, samples: int = 10, *, log_
     rng = st.t
     f = dict(dtype=torch.float32, device=dev)
     descs = (_lib.LayerDesc * n)()
-    keep, e_all, z_all = [], [], []
+    keep, chain, z_all = [], [], []
     for i, l in enumerate(layers):
         cfg = (True, False, i < n - 1)
         # (the member dimension of the batched ensemble exists in the bf16 hi | lo format: any 16-bit precision selects it)
         l._split_now = int(bool(l._split(x if i == 0 else None)) and (i == 0 or layers[i - 1].out_features % 4 == 0))
         keep.append(l._fill_desc(descs[i], cfg, None))
         ld = ops.operand_ld(l.in_features)
-        e = torch.empty((S, l.out_features, ld), **f)
-        e_all.append(e)
+        e, ws = torch.empty((S, l.out_features, ld), **f), l._workspace()
+        chain.append((e, l.bias_mu, l._split_now, ws.var_w, ws.bias_var, ops.STREAM_EPS_OUT * 64 + l._layer_id, l.row_offset))
         descs[i].e_w = e.data_ptr()
         if l._mnf:
             z = torch.empty((S, ld), **f)
@@ -143,32 +162,15 @@ def ensemble_forward_batched(net, data: torch.Tensor, samples: int = 10, *, log_
     for k, cnt in _lib.layer_groups(n):                        # (every group reads the same live offset; advanced once, below)
         _lib.check(_lib.lib().lbbnn_ensemble_operands(_lib.group_slice(descs, k, cnt), cnt, S, rng.data_ptr(), 1, stream),
                    "lbbnn_ensemble_operands")
-    h, h_ms = x, 0                                             # the first layer reads the same rows for every member
-    for i, l in enumerate(layers):
-        O, I = l.out_features, l.in_features
-        ws = l._workspace()
-        o_ms = -(-(B * O) // 4) * 4                           # member stride padded to 16 B (vector loads / stores per member)
-        obuf = torch.empty((S, o_ms), **f)
-        out = obuf[:, :B * O].view(S, B, O) if o_ms != B * O else obuf.view(S, B, O)
-        last = i == n - 1
-        flags = (0 if last else ops.F_RELU) | (ops.F_SPLIT16 if l._split_now else 0) | \
-                (ops.F_LOG_SOFTMAX if (last and O <= 16 and not sigmoid) else 0)
-        rc = _lib.lib().lbbnn_lrt_gemm_members(
-            h.data_ptr(), h.stride(-2), h_ms, e_all[i].data_ptr(), O * ops.operand_ld(I), ws.var_w.data_ptr(),
-            ops.operand_ld(I), l.bias_mu.data_ptr(), ws.bias_var.data_ptr(), rng.data_ptr(),
-            ops.STREAM_EPS_OUT * 64 + l._layer_id, l.row_offset, 1, out.data_ptr(), O, o_ms, B, I, O, flags, S, stream)
-        _lib.check(rc, "lbbnn_lrt_gemm_members")
-        h, h_ms = out, o_ms
+    C = layers[-1].out_features
+    obuf = ops.member_gemm_chain(x, S, chain, head=_head_of(net), out=torch.empty((S, ops.pad4(B * C)), **f), rng=rng,
+                                 stream=stream)
     st.advance(S)                                              # as S single forwards would have
-    if sigmoid:
-        h = _binary_members(obuf, S, B, layers[-1].out_features, log_probs)
-    elif layers[-1].out_features > 16:
-        h = torch.log_softmax(h, dim=-1)
     for l in layers:
         l.kl = 0
     net._kl_total = None
     del keep
-    return h
+    return _members_result(obuf, S, B, C, _head_of(net), log_probs)
 
 
 def _has_dense_flows(net) -> bool:
@@ -184,13 +186,7 @@ def _is_vd(net) -> bool:
 def _vd_check(net, data, samples, max_members):
     if not _is_vd(net):
         raise ValueError("bnn_amd: vd_ensemble takes a variational-dropout network (bnn_amd.vd.BNN)")
-    S = int(samples)
-    if S < 1:
-        raise ValueError("bnn_amd: samples must be >= 1")
-    chunk = S if max_members is None else int(max_members)
-    if chunk < 1:
-        raise ValueError("bnn_amd: max_members must be >= 1")
-    return S, chunk
+    return _member_counts(samples, max_members)
 
 
 @torch.no_grad()
@@ -217,8 +213,7 @@ def vd_ensemble(net, data: torch.Tensor, samples: int = 10, *, max_members: Opti
     B, C, dev = x.shape[0], net.dims[-1], x.device
     st = ops.RngState.get(dev)
     f = dict(dtype=torch.float32, device=dev)
-    pad = lambda n: -(-n // 4) * 4                             # member strides padded to 16 B
-    head = torch.empty((S, pad(B * C)), **f)
+    head = torch.empty((S, ops.pad4(B * C)), **f)              # member strides padded to 16 B
     outputs = head[:, :B * C].view(S, B, C)
     if B == 0:
         st.advance(L * S)
@@ -235,7 +230,7 @@ def vd_ensemble(net, data: torch.Tensor, samples: int = 10, *, max_members: Opti
                 h = x.contiguous()                            # (what ops.lrt_gemm does with such rows, after the choice)
             e_w, var_w = l._operands(split, half)
             last = i == L - 1
-            out = outputs[m0:m0 + c] if last else torch.empty((c, pad(B * l.m)), **f)[:, :B * l.m].view(c, B, l.m)
+            out = outputs[m0:m0 + c] if last else torch.empty((c, ops.pad4(B * l.m)), **f)[:, :B * l.m].view(c, B, l.m)
             ops.vd_gemm_members(h, e_w, var_w, l.alpha, st.t, I=l.n, O=l.m, members=c, fanout=i == 0,
                                 rng_stream=ops.STREAM_EPS_OUT * 64 + l._layer_id, row_offset=l.row_offset,
                                 member_advance=L, relu=not last, split=split, single=split and single, half=half, out=out)
@@ -271,16 +266,11 @@ def base_ensemble(net, data: torch.Tensor, samples: int = 10, *, gates: str = "s
     if not data.is_cuda:
         raise RuntimeError("bnn_amd: ensemble evaluation needs a HIP device tensor (data is on %s); there is no CPU path"
                            % data.device)
-    S = int(samples)
-    if S < 1:
-        raise ValueError("bnn_amd: samples must be >= 1")
-    chunk = S if max_members is None else int(max_members)
-    if chunk < 1:
-        raise ValueError("bnn_amd: max_members must be >= 1")
+    S, chunk = _member_counts(samples, max_members)
     net.eval()
     B, C = data.reshape(-1, net.dims[0]).shape[0], net.dims[-1]
     st = ops.RngState.get(data.device)
-    head = torch.empty((S, -(-(B * C) // 4) * 4), dtype=torch.float32, device=data.device)   # 16-B aligned member rows
+    head = torch.empty((S, ops.pad4(B * C)), dtype=torch.float32, device=data.device)        # 16-B aligned member rows
     rows, kept, outs = [], [], []
     for m0 in range(0, S, chunk):
         c = min(chunk, S - m0)
@@ -924,10 +914,6 @@ def _is_frozen(net) -> bool:
     return isinstance(net, _FrozenModel)
 
 
-def _pad4(n: int) -> int:
-    return -(-n // 4) * 4
-
-
 def _cut(threshold) -> float:
     """logit(threshold) as the fp32 value the kernels compare lambdal with (exactly 0 at 0.5); refuses a threshold outside
     (0, 1)."""
@@ -1106,7 +1092,7 @@ class _FrozenModel(nn.Module):
             return x
         from . import _lib
         n_idx = self.dims[0]
-        ldo = _pad4(n_idx)                                   # dense rows on 16-B boundaries: what the bf16 hi | lo kernels read
+        ldo = ops.pad4(n_idx)                                # dense rows on 16-B boundaries: what the bf16 hi | lo kernels read
         if self._split[0] and B * ldo * 4 >= 0x7FFFFFF0:
             raise ValueError("bnn_amd: a batch of %d rows exceeds the 2 GiB the 16-bit kernels address; split it" % B)
         out = _empty((B, ldo), dtype=torch.float32, device=dev)
@@ -1116,25 +1102,9 @@ class _FrozenModel(nn.Module):
                        "lbbnn_gather_columns")
         return out[:, :n_idx] if ldo != n_idx else out
 
-    @staticmethod
-    def _member_counts(samples, max_members):
-        """(S, chunk) of an ``ensemble`` call: the members, and how many of them one launch takes (default: all)."""
-        S = int(samples)
-        if S < 1:
-            raise ValueError("bnn_amd: samples must be >= 1")
-        chunk = S if max_members is None else int(max_members)
-        if chunk < 1:
-            raise ValueError("bnn_amd: max_members must be >= 1")
-        return S, chunk
-
     def _finish(self, buf, S: int, B: int, log_probs: bool):
-        """The (S, pad4(B * C)) buffer the last member GEMM wrote as the (S, B, C) result: the sigmoid head's one launch, a
-        view where the GEMM applied log_softmax itself (C <= 16), torch's log_softmax otherwise."""
-        C = self.dims[-1]
-        if self.head == "sigmoid":
-            return _binary_members(buf, S, B, C, log_probs)
-        outputs = buf[:, :B * C].view(S, B, C)
-        return outputs if C <= 16 else torch.log_softmax(outputs, dim=-1)
+        """The (S, B, C) result from the (S, pad4(B * C)) buffer the last member GEMM wrote."""
+        return _members_result(buf, S, B, self.dims[-1], self.head, log_probs)
 
 
 class FrozenNetwork(_FrozenModel):
@@ -1404,8 +1374,7 @@ class FrozenNetwork(_FrozenModel):
     def _chunk(self, x, c: int, st, head, zs, ms=None):
         """Members live .. live + c - 1 of the ensemble into head (c, pad4(B * classes)): MNF 2 launches for z and the member
         operands, then one lbbnn_lrt_gemm_members launch per layer."""
-        from . import _lib
-        B, dev, n = x.shape[0], x.device, self.n_layers
+        dev, n = x.device, self.n_layers
         rng = st.t
         stream = torch.cuda.current_stream(dev).cuda_stream
         mnf = self.family == "mnf"
@@ -1416,23 +1385,10 @@ class FrozenNetwork(_FrozenModel):
                 zs.append(self._z_of(zbuf, c))
             if ms is not None:
                 ms.append(masks)
-        h, h_ms = x, 0                                       # the first layer reads the same rows for every member
-        for i in range(n):
-            O, I = self.dims[i + 1], self.dims[i]
-            ld = ops.operand_ld(I)
-            last = i == n - 1
-            o_ms = _pad4(B * O)                              # member stride padded to 16 B
-            out = head if last else _empty((c, o_ms), dtype=torch.float32, device=dev)
-            flags = (0 if last else ops.F_RELU) | (ops.F_SPLIT16 if self._split[i] else 0) | \
-                    (ops.F_LOG_SOFTMAX if (last and O <= 16 and self.head == "log_softmax") else 0)
-            e_ptr, w_ms = (ewm[i].data_ptr(), O * ld) if mnf else (self._buf("e_w", i).data_ptr(), 0)
-            rc = _lib.lib().lbbnn_lrt_gemm_members(
-                h.data_ptr(), (h.stride(0) if i == 0 else self.dims[i]), h_ms, e_ptr, w_ms, self._buf("var_w", i).data_ptr(), ld,
-                self._buf("bias_mu", i).data_ptr(), self._buf("bias_var", i).data_ptr(), rng.data_ptr(),
-                ops.STREAM_EPS_OUT * 64 + self._layer_ids[i], self._row_offsets[i], 1, out.data_ptr(), O, o_ms, B, I, O,
-                flags, c, stream)
-            _lib.check(rc, "lbbnn_lrt_gemm_members")
-            h, h_ms = out, o_ms
+        buf = self._buf
+        chain = [(ewm[i] if mnf else buf("e_w", i), buf("bias_mu", i), self._split[i], buf("var_w", i), buf("bias_var", i),
+                  ops.STREAM_EPS_OUT * 64 + self._layer_ids[i], self._row_offsets[i]) for i in range(n)]
+        ops.member_gemm_chain(x, c, chain, head=self.head, out=head, empty=_empty, rng=rng, stream=stream)
         st.advance(c)                                        # as c single forwards would have
 
     def _chain(self, x, st, e_ws, stochastic: bool, log_probs: bool = False):
@@ -1464,7 +1420,7 @@ class FrozenNetwork(_FrozenModel):
         logits, no draws of its own -- or, with ``log_probs=True`` (one unit), the (samples, B, 2) log-probabilities of the two
         classes from the same launch."""
         _check_log_probs(self, log_probs)
-        S, chunk = self._member_counts(samples, max_members)
+        S, chunk = _member_counts(samples, max_members)
         x = self._input(data)
         B, C, dev = x.shape[0], self.dims[-1], x.device
         st = ops.RngState.get(dev)
@@ -1492,7 +1448,7 @@ class FrozenNetwork(_FrozenModel):
                 if keep_z:
                     self.last_z = [None] * self.n_layers
                 return torch.stack(outs)
-            head = _empty((S, _pad4(B * C)), dtype=torch.float32, device=dev)
+            head = _empty((S, ops.pad4(B * C)), dtype=torch.float32, device=dev)
             zs = [] if (keep_z and self.family == "mnf") else None
             ms = [] if (keep_masks and self.flows == "dense") else None
             for m0 in range(0, S, chunk):
@@ -1892,27 +1848,6 @@ class FrozenBaseNetwork(_FrozenModel):
             self._mcap = c
         return self._mw, self._mb
 
-    def _gemms(self, x, c: int, ws, w_ms: bool, bs, out, stream, head_flags: bool = True):
-        """The chain of lbbnn_gemm_members_mean launches of ``c`` members (``_predict_members``'s): layer i multiplies with
-        ws[i] ([c][O'][ld'], or one [O'][ld'] operand when not ``w_ms``) and adds bs[i]; the last layer writes ``out``."""
-        from . import _lib
-        B, dev, n = x.shape[0], x.device, self.n_layers
-        sigmoid = self.head == "sigmoid"
-        h, h_ms, ldx = x, 0, x.stride(0)
-        for i in range(n):
-            O, I = self.dims[i + 1], self.dims[i]
-            ld = ops.operand_ld(I)
-            last = i == n - 1
-            o = out if last else _empty((c, _pad4(B * O)), dtype=torch.float32, device=dev)
-            flags = (ops.F_RELU if not last else (ops.F_LOG_SOFTMAX if O <= 16 and not sigmoid else 0)) | \
-                    (ops.F_SPLIT16 if self._split[i] else 0)
-            rc = _lib.lib().lbbnn_gemm_members_mean(h.data_ptr(), ldx, h_ms, ws[i].data_ptr(), O * ld if w_ms else 0, ld,
-                                                   bs[i].data_ptr(), O if w_ms else 0, o.data_ptr(), O, o.stride(0), B, I, O,
-                                                   flags, c, stream)
-            _lib.check(rc, "lbbnn_gemm_members_mean")
-            h, h_ms, ldx = o, o.stride(0), O
-        return h
-
     def _chunk(self, x, c: int, st, head, kept):
         """Members live .. live + c - 1 into head (c, pad4(B * classes)): ceil(n / 4) lbbnn_base_frozen_members launches, then
         one GEMM launch per layer."""
@@ -1930,7 +1865,7 @@ class FrozenBaseNetwork(_FrozenModel):
             _lib.check(rc, "lbbnn_base_frozen_members")
         if kept is not None:
             kept.append(([w[:c].clone() for w in mw], [b[:c].clone() for b in mb]))
-        self._gemms(x, c, mw, True, mb, head, stream)
+        ops.member_gemm_chain(x, c, list(zip(mw, mb, self._split)), head=self.head, out=head, empty=_empty, stream=stream)
         st.advance(c)                                        # as c single forwards would have
 
     @torch.no_grad()
@@ -1946,7 +1881,7 @@ class FrozenBaseNetwork(_FrozenModel):
         (samples, O') biases.  A model with ``head == "sigmoid"``: (samples, B, units) probabilities, or with ``log_probs``
         (one unit) the (samples, B, 2) log-probabilities of the two classes."""
         _check_log_probs(self, log_probs)
-        S, chunk = self._member_counts(samples, max_members)
+        S, chunk = _member_counts(samples, max_members)
         x = self._input(data)
         B, C, dev = x.shape[0], self.dims[-1], x.device
         st = ops.RngState.get(dev)
@@ -1956,7 +1891,7 @@ class FrozenBaseNetwork(_FrozenModel):
             if B == 0:
                 st.advance(S)
                 return torch.zeros((S, 0, 2 if log_probs else C), dtype=torch.float32, device=dev)
-            head = _empty((S, _pad4(B * C)), dtype=torch.float32, device=dev)
+            head = _empty((S, ops.pad4(B * C)), dtype=torch.float32, device=dev)
             for m0 in range(0, S, chunk):
                 c = min(chunk, S - m0)
                 self._chunk(x, c, st, head[m0:m0 + c], kept)
@@ -1979,9 +1914,10 @@ class FrozenBaseNetwork(_FrozenModel):
         if B == 0:
             return torch.zeros((0, 2 if log_probs else C), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            out = _empty((1, _pad4(B * C)), dtype=torch.float32, device=dev)
-            self._gemms(x, 1, [self._buf("e_w", i) for i in range(n)], False, [self._buf("b_mu", i) for i in range(n)], out,
-                        torch.cuda.current_stream(dev).cuda_stream)
+            out = _empty((1, ops.pad4(B * C)), dtype=torch.float32, device=dev)
+            chain = [(self._buf("e_w", i), self._buf("b_mu", i), self._split[i]) for i in range(n)]
+            ops.member_gemm_chain(x, 1, chain, head=self.head, out=out, empty=_empty,
+                                  stream=torch.cuda.current_stream(dev).cuda_stream)
         return self._finish(out, 1, B, log_probs)[0]
 
 

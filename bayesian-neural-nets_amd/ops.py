@@ -495,8 +495,7 @@ def vd_gemm_members(x, e_w, var_w, var_scale, rng: torch.Tensor, *, I: int, O: i
         ldx, x_ms, B = x.stride(1), x.stride(0), x.shape[1]
         xp = _ptr_rows(x[0], "input")
     if out is None:
-        o_ms = -(-(B * O) // 4) * 4
-        out = torch.empty((members, o_ms), dtype=torch.float32, device=x.device)[:, :B * O].view(members, B, O)
+        out = torch.empty((members, pad4(B * O)), dtype=torch.float32, device=x.device)[:, :B * O].view(members, B, O)
     if tuple(out.shape) != (members, B, O) or out.stride(2) != 1:
         raise RuntimeError("bnn_amd: out must be (%d,%d,%d) with dense rows" % (members, B, O))
     flags = ((F_RELU if relu else 0) | (F_SPLIT16 if split else 0) | (F_SINGLE16 if (split and single) else 0)
@@ -506,6 +505,49 @@ def vd_gemm_members(x, e_w, var_w, var_scale, rng: torch.Tensor, *, I: int, O: i
         row_offset, member_advance, _ptr_rows(out[0], "out"), out.stride(1), out.stride(0), B, I, O, flags, members,
         1 if fanout else 0, _stream())
     _lib.check(rc, "lbbnn_vd_gemm_members")
+    return out
+
+
+def pad4(n: int) -> int:
+    """n floats rounded up to a multiple of 4: rows and member blocks on 16-B boundaries."""
+    return -(-n // 4) * 4
+
+
+def member_gemm_chain(x, members: int, layers, *, head: str, out, empty=torch.empty, rng=None, stream=None):
+    """A network's layers for ``members`` members, one member-GEMM launch per layer, wired by five rules: the member stride
+    of a layer's output is pad4(B * O); every layer but the last gets ReLU; the last layer's epilogue applies log_softmax
+    exactly when O <= 16 and ``head`` is "log_softmax"; the first layer reads the (B, I0) rows ``x`` for every member (member
+    stride 0); each later layer reads what the previous one wrote, rows of ldx = its O.  ``layers``: per layer (operand, bias,
+    split) -- one (O, ld) operand for all members or (members, O, ld), one (O,) bias or (members, O), whether the layer takes
+    the bf16 hi | lo kernels: the mean-only form (lbbnn_gemm_members_mean) -- or (operand, bias, split, var_w, bias_var,
+    rng_stream, row_offset): the dual-moment form (lbbnn_lrt_gemm_members; bias, var_w and bias_var shared; member m draws at
+    Philox offset rng[1] + m of the state ``rng``).  The last layer writes ``out`` (members, >= pad4(B * O)), whose row
+    stride is its member stride; the buffers between the layers come from ``empty``."""
+    (B, I), last, dev = x.shape, len(layers) - 1, x.device
+    stream = _stream() if stream is None else stream
+    h, ldx, h_ms = x, x.stride(0), 0
+    for i, (w, bias, split, *dual) in enumerate(layers):
+        O, ld = w.size(-2), operand_ld(I)
+        if i < last:
+            o_ms, flags = pad4(B * O), F_RELU
+            o = empty((members, o_ms), dtype=torch.float32, device=dev)
+        else:
+            o, o_ms, flags = out, out.stride(0), (F_LOG_SOFTMAX if O <= 16 and head == "log_softmax" else 0)
+        if split:
+            flags |= F_SPLIT16
+        w_ms = O * ld if w.dim() == 3 else 0
+        if dual:
+            var_w, bias_var, rng_stream, row_offset = dual
+            rc = _lib.lib().lbbnn_lrt_gemm_members(
+                h.data_ptr(), ldx, h_ms, w.data_ptr(), w_ms, var_w.data_ptr(), ld, bias.data_ptr(), bias_var.data_ptr(),
+                rng.data_ptr(), rng_stream, row_offset, 1, o.data_ptr(), O, o_ms, B, I, O, flags, members, stream)
+            _lib.check(rc, "lbbnn_lrt_gemm_members")
+        else:
+            rc = _lib.lib().lbbnn_gemm_members_mean(
+                h.data_ptr(), ldx, h_ms, w.data_ptr(), w_ms, ld, bias.data_ptr(), O if bias.dim() == 2 else 0,
+                o.data_ptr(), O, o_ms, B, I, O, flags, members, stream)
+            _lib.check(rc, "lbbnn_gemm_members_mean")
+        h, ldx, h_ms, I = o, O, o_ms, O               # (h keeps the buffer alive until the launch that reads it is queued)
     return out
 
 

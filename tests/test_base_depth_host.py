@@ -224,6 +224,66 @@ def test_operand_formats_in_the_second_group_under_a_split_precision(base, monke
             assert a[14] == act | (ops.F_SPLIT16 if split[k] else 0), (precision, k)
 
 
+@pytest.mark.parametrize("wide", [False, True])
+@pytest.mark.parametrize("per_member", [False, True])
+@pytest.mark.parametrize("form", ["dual", "mean"])
+@pytest.mark.parametrize("C,head,head_flag", [(3, "log_softmax", 0x8), (18, "log_softmax", 0), (1, "sigmoid", 0),
+                                              (3, "sigmoid", 0)])
+def test_member_gemm_chain_wires_one_call_per_layer(monkeypatch, C, head, head_flag, form, per_member, wide):
+    """ops.member_gemm_chain, the one place that wires a chain of member GEMMs: per layer ONE call of the form's entry point
+    with the positional arguments the ensemble sites pass; member stride pad4(B * O) (B * O = 60, 100 and 15 / 90 / 5: the
+    padding matters), or the row stride of a caller's wider last buffer; ReLU on every layer but the last, log_softmax in the
+    last epilogue exactly for the log_softmax head with C <= 16; layer 0 reads x for every member (member stride 0); layer
+    k + 1 reads what layer k wrote; the buffers in between come from the given allocator."""
+    from bnn_amd import _lib, ops
+    B, S, I0 = 5, 3, 8
+    widths = (12, 20, C)
+    dims = (I0,) + widths
+    rec = _Recorder()
+    monkeypatch.setattr(_lib, "lib", lambda: rec)
+    monkeypatch.setattr(ops, "_stream", lambda: 77)
+    x = torch.rand(B, 12)[:, :I0]                               # rows wider than I0: ldx is the row stride
+    lds = [ops.operand_ld(i) for i in dims[:3]]
+    ws = [torch.zeros(((S,) if per_member else ()) + (dims[k + 1], lds[k])) for k in range(3)]
+    mean_per_member = per_member and form == "mean"             # (the dual-moment form has one bias for all members)
+    bs = [torch.zeros(((S,) if mean_per_member else ()) + (dims[k + 1],)) for k in range(3)]
+    splits = [False, True, False]
+    pad = [ops.pad4(B * o) for o in widths]
+    assert pad[:2] == [60, 100] and pad[2] == {3: 16, 18: 92, 1: 8}[C] and pad[2] != B * C
+    out = torch.zeros(S, pad[2] + (8 if wide else 0))
+    handed = []
+
+    def alloc(*size, **kw):
+        handed.append(torch.empty(*size, **kw))
+        return handed[-1]
+
+    if form == "dual":
+        vs, bvs = [torch.zeros(dims[k + 1], lds[k]) for k in range(3)], [torch.zeros(dims[k + 1]) for k in range(3)]
+        rng = torch.tensor([7, 11], dtype=torch.int64)
+        layers = [(ws[k], bs[k], splits[k], vs[k], bvs[k], 64 + k, 1000 * k) for k in range(3)]
+        got = ops.member_gemm_chain(x, S, layers, head=head, out=out, empty=alloc, rng=rng, stream=5)
+    else:
+        layers = [(ws[k], bs[k], splits[k]) for k in range(3)]
+        got = ops.member_gemm_chain(x, S, layers, head=head, out=out, empty=alloc)               # (the current stream)
+    assert got is out
+    name = "lbbnn_lrt_gemm_members" if form == "dual" else "lbbnn_gemm_members_mean"
+    assert [c[0] for c in rec.calls] == [name] * 3
+    assert [tuple(t.shape) for t in handed] == [(S, pad[0]), (S, pad[1])] and all(t.dtype == torch.float32 for t in handed)
+    outs = [handed[0], handed[1], out]
+    o_ms = [pad[0], pad[1], out.stride(0)]
+    for k, (_, a) in enumerate(rec.calls):
+        I, O = dims[k], dims[k + 1]
+        src = (x.data_ptr(), 12, 0) if k == 0 else (outs[k - 1].data_ptr(), I, o_ms[k - 1])
+        flags = (0x4 if splits[k] else 0) | (0x1 if k < 2 else head_flag)
+        w_ms = O * lds[k] if per_member else 0
+        if form == "dual":
+            assert a == src + (ws[k].data_ptr(), w_ms, vs[k].data_ptr(), lds[k], bs[k].data_ptr(), bvs[k].data_ptr(),
+                               rng.data_ptr(), 64 + k, 1000 * k, 1, outs[k].data_ptr(), O, o_ms[k], B, I, O, flags, S, 5)
+        else:
+            assert a == src + (ws[k].data_ptr(), w_ms, lds[k], bs[k].data_ptr(), O if per_member else 0,
+                               outs[k].data_ptr(), O, o_ms[k], B, I, O, flags, S, 77)
+
+
 def test_gate_members_refuses_more_than_one_group(base):
     """The entry point takes at most LBBNN_MAX_LAYERS descriptors: the grouping above is what keeps a deep network inside it."""
     import __graft_entry__ as ge

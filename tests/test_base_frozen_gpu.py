@@ -28,6 +28,11 @@ CASES = [((13, 9, 3), "fp32", "log_softmax"), ((40, 24, 24, 10), "bf16x3", "log_
          ((16, 16, 16, 16, 16, 4), "fp32", "log_softmax"), ((20, 1), "fp32", "sigmoid")]
 IDS = ["13-9-3", "40-24-24-10-bf16x3", "five-layers", "20-1-sigmoid"]
 GATES = ["sample", "sample-hard", "mpm"]
+# the member-GEMM chain's head cases no case above reaches: log_softmax by torch (C > 16) and the sigmoid head's probabilities
+# (log_probs off, the 4th field); B * C = 90 / 5 at B = 5, so the member stride pad4(B * C) is padded
+HEAD_CASES = [((8, 12, 20, 18), p, "log_softmax", False) for p in ("fp32", "bf16x3")] + \
+             [((8, 12, 20, 1), p, "sigmoid", False) for p in ("fp32", "bf16x3")]
+HEAD_IDS = ["8-12-20-18", "8-12-20-18-bf16x3", "8-12-20-1-probs", "8-12-20-1-probs-bf16x3"]
 
 
 @pytest.fixture(scope="module")
@@ -130,26 +135,27 @@ def _mean_weights64(net, gates, threshold=0.5):
 # ------------------------------------------------------------------------------------------- 1. the full model
 @pytest.mark.parametrize("B", [5, 70])
 @pytest.mark.parametrize("gates", GATES)
-@pytest.mark.parametrize("case", CASES, ids=IDS)
+@pytest.mark.parametrize("case", CASES + HEAD_CASES, ids=IDS + HEAD_IDS)
 def test_full_model_is_base_ensemble(bnn, dev, precision, case, gates, B):
     ev, ops = bnn.evaluate, bnn.ops
-    dims, prec, head = case
+    dims, prec, head = case[:3]
     net = _net(bnn, dev, dims, head)
     precision(prec)
     mode = "mpm" if gates == "mpm" else "sample"
     _set_hard(net, gates == "sample-hard")
     try:
-        binary = head == "sigmoid"
+        binary = head == "sigmoid" if len(case) == 3 else case[3]       # (log_probs: the sigmoid head's 2-class form)
         x = _x(dev, B, dims[0])
         st = ops.RngState.get(dev)
         bnn.manual_seed(SEED, OFF)
         want = ev.base_ensemble(net, x, S, gates=mode, log_probs=binary)["outputs"]
+        assert want.shape == (S, B, 2 if binary else dims[-1])
         bnn.manual_seed(SEED, OFF)
         w_loop, b_loop, splits = _loop_members(bnn, net, x, S, mode)
         fz = ev.freeze_base(net, mode)
         assert fz.gates == mode and fz.head == head and fz.dims == dims and fz.full_dims == dims and list(fz.parameters()) == []
         assert fz._split == splits
-        if prec == "bf16x3":
+        if prec == "bf16x3" and case in CASES:
             assert splits == [True, True, False]                 # the split layout really is in play
         bnn.manual_seed(SEED, OFF)
         got = fz.ensemble(x, S, log_probs=binary, keep_weights=True)

@@ -241,7 +241,8 @@ def test_loss_backward_against_float64(bnn, dev, B, O, pad):
 
 # ------------------------------------------------------------------------------------------- 3. the network forward
 NETS = {"lrt-20-1": ("lrt", (20, 1)), "mnf-20-1": ("mnf", (20, 1)), "lrt-12-8-1": ("lrt", (12, 8, 1)),
-        "mnf-12-8-3": ("mnf", (12, 8, 3)), "mnf-12-8-1": ("mnf", (12, 8, 1))}
+        "mnf-12-8-3": ("mnf", (12, 8, 3)), "mnf-12-8-1": ("mnf", (12, 8, 1)),
+        "lrt-8-12-20-1": ("lrt", (8, 12, 20, 1)), "mnf-8-12-20-1": ("mnf", (8, 12, 20, 1))}
 
 
 def _make(bnn, name, dev, head="sigmoid", seed=11, spread=True):
@@ -413,8 +414,8 @@ print("BCEGRAPH_OK", gl, gs)
 
 # ------------------------------------------------------------------------------------------- 6. ensembles
 @pytest.mark.parametrize("prec", ("fp32", "bf16x3"))
-@pytest.mark.parametrize("B,S", ((1, 10), (100, 10), (257, 1)))
-@pytest.mark.parametrize("name", ("lrt-20-1", "mnf-12-8-1"))
+@pytest.mark.parametrize("B,S", ((1, 10), (100, 10), (257, 1), (5, 3)))
+@pytest.mark.parametrize("name", ("lrt-20-1", "mnf-12-8-1", "lrt-8-12-20-1", "mnf-8-12-20-1"))
 def test_ensembles_agree_and_log_probs_come_from_the_logits(bnn, dev, precision, name, B, S, prec):
     ev = bnn.evaluate
     dims = NETS[name][1]
@@ -444,9 +445,13 @@ def test_ensembles_agree_and_log_probs_come_from_the_logits(bnn, dev, precision,
     print("ensembles %s B=%d S=%d %s: batched - loop %.3g (bitwise %s), frozen - loop %.3g (bitwise %s), bar %.3g"
           % (name, B, S, prec, d_b, _same(bat, loop), d_f, _same(frz, loop), bar))
     assert d_b <= bar and d_f <= bar
+    # the members' logits of the batched form are the loop's bit for bit (test_ensemble_batched_equals_loop_bitwise) and the
+    # head is one elementwise kernel over them in both forms: the same bits
+    assert _same(bat, loop)
     if S > 1:
-        chunked, _ = run(lambda: fz.ensemble(x, S, max_members=3))
-        assert _same(chunked, frz)
+        for mm in (2, 3):
+            chunked, _ = run(lambda: fz.ensemble(x, S, max_members=mm))
+            assert _same(chunked, frz)
     one, _ = run(lambda: fz(x, sample=True))
     assert _same(one, frz[0])
     # log_probs=True: (S, B, 2) from the logits of the same members, by the kernel that makes the probabilities
@@ -455,6 +460,12 @@ def test_ensembles_agree_and_log_probs_come_from_the_logits(bnn, dev, precision,
                      ("frozen", lambda: fz.ensemble(x, S, log_probs=True))):
         lp, off = run(fn)
         assert lp.shape == (S, B, 2) and torch.equal(off, off_l) and bool(torch.isfinite(lp).all()), what
+        if what == "loop":
+            lp_loop = lp
+        elif what == "batched":
+            assert _same(lp, lp_loop)
+        elif S > 1:
+            assert _same(run(lambda: fz.ensemble(x, S, max_members=2, log_probs=True))[0], lp)
         assert float((lp.double().exp().sum(-1) - 1).abs().max()) <= 1e-6, what
         # the probabilities of the same call are 1 / (1 + exp(-x)); its logits x = lp[1] - lp[0] up to rounding: the two agree
         probs = {"loop": loop, "batched": bat, "frozen": frz}[what]

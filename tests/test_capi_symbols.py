@@ -191,3 +191,96 @@ def test_bias_backward_entry_points_argument_checks(lib):
     assert lib.lbbnn_bias_backward_partials(fake, 64, 10, 1, fake, fake, None, ctypes.byref(pr), None, fake, None) == -1
     assert lib.lbbnn_bias_backward_partials(fake, 0, 10, 1, fake, fake, None, ctypes.byref(pr), fake, fake, None) == -2
     assert lib.lbbnn_bias_backward_partials(fake, 64, 0, 0, fake, fake, None, ctypes.byref(pr), fake, fake, None) == -2
+
+
+_F = ctypes.c_void_p(4096)            # never dereferenced
+_ODD = ctypes.c_void_p(4100)          # off 16 bytes
+_RELU, _MEAN, _SPLIT, _LSM, _SINGLE, _HALF = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
+_WIDE = 0x20000000                    # a row stride whose second row lies past the 32-bit buffer offsets
+
+# one dual-moment product that would launch: every row below breaks it, so nothing is launched
+_GEMM = dict(x=_F, ldx=8, e_w=_F, var_w=_F, ld=32, bias_mean=None, bias_var=None, var_scale=None, eps=_F, rng=None,
+             rng_stream=0, row_offset=0, out=_F, ldo=24, std_out=None, B=4, I=8, O=24, flags=0)
+_FIN = dict(_GEMM, layers="one", n=1, fin_rng=None, kl_total=None)
+_ADV = dict(_FIN, rng_live=None, advance=0)
+_SPLITK = dict(x=_F, ldx=8, w_op=_F, ld=32, out=_F, ldo=24, B=4, I=8, O=24, kchunk=32)
+_MEMBERS = dict(x=_F, ldx=8, x_mstride=0, e_w=_F, w_mstride=0, var_w=_F, ld=32, bias_mean=None, bias_var=None, rng=_F,
+                rng_stream=0, row_offset=0, member_advance=0, out=_F, ldo=24, o_mstride=96, B=4, I=8, O=24, flags=0, members=2)
+_VD = dict(x=_F, ldx=8, x_mstride=0, e_w=_F, var_w=_F, ld=32, var_scale=None, rng=_F, rng_stream=0, row_offset=0,
+           member_advance=0, out=_F, ldo=24, o_mstride=96, B=4, I=8, O=24, flags=0, members=2, fanout=0)
+_MMEAN = dict(x=_F, ldx=8, x_mstride=0, w=_F, w_mstride=0, ld=32, bias=None, b_mstride=0, out=_F, ldo=24, o_mstride=96,
+              B=4, I=8, O=24, flags=0, members=2)
+
+# the dispatch's early returns, in its order, as the plain dual-moment form reaches them; each row but the first of a code is
+# also invalid at a LATER check, so it pins the precedence
+_DISPATCH = [
+    (dict(B=0, x=None), 0),                                   # empty batch: nothing to do, before the NULL check
+    (dict(x=None, B=-1), -1), (dict(e_w=None), -1), (dict(out=None), -1),
+    (dict(B=-1, flags=0x100), -2), (dict(I=0), -2), (dict(O=0), -2), (dict(ldx=4), -2), (dict(ldo=8), -2),
+    (dict(flags=0x100, var_w=None), -4),                      # unknown flag
+    (dict(flags=_HALF | _SPLIT, var_w=None), -4),             # HALF16 without SINGLE16
+    (dict(flags=_HALF | _SINGLE | _SPLIT | _MEAN), -4),       # HALF16 on the mean-only form
+    (dict(flags=_LSM, var_w=None), -4),                       # log_softmax with O > 16
+    (dict(flags=_LSM | _RELU, O=8, ldo=8, var_w=None), -4),
+    (dict(flags=_SINGLE, var_w=None), -4),                    # SINGLE16 without SPLIT16
+    (dict(var_w=None, eps=None), -1),
+    (dict(eps=None, ld=30), -5),
+    (dict(ld=30, e_w=_ODD), -3), (dict(ld=0, flags=_SPLIT, O=16), -3),
+    (dict(e_w=_ODD, flags=_SPLIT, O=16), -3), (dict(var_w=_ODD), -3),
+    (dict(flags=_SPLIT, O=16, ldo=16, ldx=_WIDE), -3),        # the split kernel's operand rules, before its offset check
+    (dict(flags=_SPLIT, I=12, ldx=12), -3), (dict(flags=_SPLIT, x=_ODD), -3),
+    (dict(flags=_SPLIT, B=2, ldx=_WIDE), -2),                 # 32-bit buffer offsets: x
+    (dict(flags=_SPLIT, O=1 << 24, ldo=1 << 24), -2),         # ... and the operands
+]
+
+_RETURN_CODES = {
+    "lbbnn_lrt_gemm_train": (_GEMM, [(dict(flags=_MEAN, std_out=_F, x=None), -4)] + _DISPATCH),
+    "lbbnn_lrt_gemm_finalize": (_FIN, [
+        (dict(n=0, x=None), -2), (dict(n=-1, flags=_MEAN, std_out=_F), -2),
+        (dict(flags=_MEAN, std_out=_F, layers=None), -4),
+        (dict(layers=None, x=None), -1), (dict(n=5, x=None), -2),       # more than LBBNN_MAX_LAYERS
+        (dict(layers="want_kl", x=None), -1),                           # a KL without its buffers
+        (dict(kl_total=_F, x=None), -1),                                # a total needs every layer's KL
+    ] + _DISPATCH[1:]),                                                 # (an empty batch still launches the finalize)
+    "lbbnn_lrt_gemm_finalize_adv": (_ADV, [
+        (dict(n=-1, advance=1), -2), (dict(layers=None, advance=1), -2),
+        (dict(advance=1, flags=_MEAN, std_out=_F), -1),                 # an advance without rng_live
+        (dict(flags=_MEAN, std_out=_F, n=0, x=None), -4),
+        (dict(n=0, layers=None, x=None), -1), (dict(n=0, layers=None, B=0), 0),     # n = 0: the plain product
+        (dict(n=5, x=None), -2), (dict(layers="want_kl", x=None), -1), (dict(kl_total=_F, x=None), -1),
+    ] + _DISPATCH[1:]),
+    "lbbnn_matmul_splitk": (_SPLITK, [
+        (dict(kchunk=0, x=None), -3), (dict(kchunk=-32, x=None), -3), (dict(kchunk=48, x=None), -3),
+        (dict(B=0, x=None), 0), (dict(x=None, B=-1), -1), (dict(w_op=None), -1), (dict(out=None), -1),
+        (dict(B=-1, ld=30), -2), (dict(ldx=4), -2), (dict(ldo=8), -2),
+        (dict(ld=30, O=16), -3), (dict(w_op=_ODD, O=16), -3),
+        (dict(O=16, ldo=16, ldx=_WIDE), -3), (dict(I=12, ldx=12), -3), (dict(x=_ODD), -3),
+        (dict(B=2, ldx=_WIDE), -2), (dict(O=1 << 24, ldo=1 << 24), -2),
+    ]),
+    # the member entry points: one doubly-invalid call each -- the entry point's own checks come first, in their order
+    "lbbnn_lrt_gemm_members": (_MEMBERS, [(dict(members=0, x_mstride=2), -2), (dict(o_mstride=98, x=None), -3),
+                                          (dict(flags=_SPLIT, B=2, ldx=_WIDE, o_mstride=48, x=None), -2)]),
+    "lbbnn_vd_gemm_members": (_VD, [(dict(fanout=1, x_mstride=4, flags=_MEAN), -2), (dict(o_mstride=98, flags=_MEAN), -3),
+                                    (dict(flags=_LSM, rng=None), -4), (dict(rng=None, x=None), -5),
+                                    (dict(flags=_SPLIT, B=2, ldx=_WIDE, o_mstride=48, x=None), -2)]),
+    "lbbnn_gemm_members_mean": (_MMEAN, [(dict(x=None, members=0), -1), (dict(members=0, flags=_SINGLE), -2),
+                                         (dict(flags=_SINGLE, x_mstride=-4), -4), (dict(flags=_LSM, b_mstride=-4), -4),
+                                         (dict(b_mstride=-4, o_mstride=98), -2), (dict(o_mstride=98, ld=30), -3),
+                                         (dict(flags=_SPLIT, B=2, ldx=_WIDE, o_mstride=48, ld=30), -2)]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(_RETURN_CODES))
+def test_gemm_entry_points_early_return_codes(lib, name):
+    """Every early return of the dual-moment GEMM's entry points that no other host test calls, in the order the code takes
+    them (nothing is launched): a call that is invalid in two ways returns the code of the earlier check."""
+    from bnn_amd import _lib
+    base, rows = _RETURN_CODES[name]
+    layers = {None: None, "one": (_lib.LayerDesc * 5)(), "want_kl": (_lib.LayerDesc * 5)()}
+    layers["want_kl"][0].want_kl = 1
+    for change, code in rows:
+        assert not set(change) - set(base), change
+        args = dict(base, **change)
+        if "layers" in args:
+            args["layers"] = layers[args["layers"]]
+        assert getattr(lib, name)(*args.values(), None) == code, (name, change)

@@ -136,7 +136,7 @@ def test_against_fp64_oracle(bnn, dev, prec, p, dims, B, S):
     assert int(st.t[1]) == live + L * S
 
 
-# kernel families of the dispatch (lrt_gemm_impl): (B, I, O, flags-name, relu)
+# kernel families of the dispatch (lrt_gemm_dispatch): (B, I, O, flags-name, relu)
 FAMILIES = [
     ("fp32 register-staged", 33, 50, 37, "fp32", True),           # x rows not float4-aligned
     ("fp32 register-staged, I % 16 != 0", 70, 36, 120, "fp32", False),
