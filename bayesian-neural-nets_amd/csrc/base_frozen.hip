@@ -5,7 +5,8 @@
 // Work split of both kernels: ONE WAVE PER (COMPACT) OUTPUT ROW, kBfRows rows per workgroup, the rows of all layers
 // concatenated on gridDim.x.  A lane owns the groups of EIGHT consecutive compact columns lane, lane + 64, ... of its row: a
 // group is two float4 of every fp32 plane, or one 16-B hi unit and one 16-B lo unit of the split layout (lbbnn_device.h) -- the
-// store shapes of gate_members_kernel (gate_vd.hip), no exchange between lanes.  No LDS, no atomics; row sums are DPP wave sums.
+// store8 / store8_operand of operand_store.h (the store shapes of gate_members_kernel, gate_vd.hip), no exchange between lanes.
+// No LDS, no atomics; row sums are DPP wave sums.
 //
 //   base_frozen_operands_kernel -- sources gathered at (rows[o'], cols[j']) (float4 loads when there is no map and the rows
 //     allow it), sigma / alpha by softplus_ref / sigmoid_ref: the functions, hence the bits, of gate_members_kernel.
@@ -14,10 +15,12 @@
 //     (rows[o'], cols[j'] / 4): sorted cols keep the columns of one full quad adjacent, so a new evaluation is made only when
 //     the quad changes (identity map: one per float4, as gate_members_kernel).  MPM mode: a float4 whose w_mu and w_sigma are
 //     all zero draws nothing.
-// gate_draw / uniform24 / bf16_hi_lo restate gate_vd.hip's (which stays as it is), as frozen_compact.hip restates frozen.hip's.
+// The draw (gate_draw, uniform24), the scalar bf16 split, layer_of and map_index are operand_store.h's: the ones the live
+// kernels and frozen.hip use.
 #include <climits>
 #include "lbbnn_device.h"
 #include "lbbnn_internal.h"
+#include "operand_store.h"
 
 namespace {
 
@@ -26,8 +29,6 @@ using namespace lbbnn;
 constexpr int kBfRows = 4;                 // rows (= waves) per workgroup
 constexpr int kBfNT = 64 * kBfRows;
 constexpr int kBfMaxLd = 4096;             // GATE_MEMBERS_MAX_LD: the widest row of lbbnn_gate_members
-constexpr float kProbEps = 1.1920928955078125e-7f;      // torch.finfo(float32).eps
-constexpr float kTiny = 1.17549435082228750797e-38f;    // torch.finfo(float32).tiny
 
 struct BfLayer {
     const float* mu; const float* rho; const float* lambdal; const float* bias_mu; const float* bias_rho;
@@ -46,71 +47,15 @@ struct BfBatch {
     uint64_t member_advance;
 };
 
-__device__ __forceinline__ uint32_t bf16_rne_bits(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-// the split bf16 pair of one operand value: hi | lo << 16 (hi = RNE(v), lo = RNE(v - hi))
-__device__ __forceinline__ uint32_t bf16_hi_lo(float v) {
-    const uint32_t h = bf16_rne_bits(v);
-    return h | (bf16_rne_bits(v - __uint_as_float(h << 16)) << 16);
-}
-// 24 random bits -> (k + 0.5) 2^-24
-__device__ __forceinline__ float uniform24(uint32_t r) { return ((float)(r >> 8) + 0.5f) * 5.9604644775390625e-8f; }
-// the gate of lbbnn_gate_members: Bernoulli(al) as u < al (hard) or RelaxedBernoulli(al, T).rsample() from its uniform
-__device__ __forceinline__ float gate_draw(float al, float u, float T, bool hard) {
-    if (hard) return u < al ? 1.f : 0.f;
-    const float p = fminf(fmaxf(al, kProbEps), 1.f - kProbEps);
-    const float uc = fminf(fmaxf(u, kProbEps), 1.f - kProbEps);
-    const float z = (((logf(uc) - log1pf(-uc)) + logf(p)) - log1pf(-p)) / T;
-    const float s = 1.f / (1.f + expf(-z));
-    return fminf(fmaxf(s, kTiny), 1.f - kProbEps);
-}
 // element `k` (0..3) of a register quad without indexing memory
 __device__ __forceinline__ float pick4(const float v[4], int k) { return k == 0 ? v[0] : k == 1 ? v[1] : k == 2 ? v[2] : v[3]; }
 __device__ __forceinline__ uint32_t pick4(const Philox4& v, int k) { return k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w; }
 
-__device__ __forceinline__ int bf_layer_of(const LBBNN_CONST_AS BfBatch* bt, int& wg0) {
-    int li = 0;
-#pragma unroll
-    for (int t = 0; t < LBBNN_MAX_LAYERS - 1; ++t) if (t + 1 < bt->n && (int)blockIdx.x >= bt->wg_end[t]) li = t + 1;
-    wg0 = li ? bt->wg_end[li - 1] : 0;
-    return li;
-}
-// an index of a map as the kernels use it: inside [0, n) whatever the array holds; no map: the identity
-__device__ __forceinline__ int bf_index(const int32_t* idx, int k, int n) {
-    if (!idx) return k;
-    const int v = idx[k];
-    return v < 0 ? 0 : (v >= n ? n - 1 : v);
-}
-// eight values of columns [i0, i0 + 8) of row o of an fp32 plane / of a GEMM operand in either format
-__device__ __forceinline__ void store8(float* base, int o, int i0, int ld, const float w[8]) {
-    float* const p = base + (size_t)o * ld + i0;
-    *reinterpret_cast<float4*>(p) = make_float4(w[0], w[1], w[2], w[3]);
-    *reinterpret_cast<float4*>(p + 4) = make_float4(w[4], w[5], w[6], w[7]);
-}
-__device__ __forceinline__ void store8_operand(void* base, bool split, size_t row, int i0, int ld, const float w[8]) {
-    if (!split) {
-        float* const p = static_cast<float*>(base) + row * ld + i0;
-        *reinterpret_cast<float4*>(p) = make_float4(w[0], w[1], w[2], w[3]);
-        *reinterpret_cast<float4*>(p + 4) = make_float4(w[4], w[5], w[6], w[7]);
-        return;
-    }
-    uint32_t hl[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) hl[k] = bf16_hi_lo(w[k]);
-    uint16_t* const p = static_cast<uint16_t*>(base) + split_hi_index(row, i0, ld);
-    *reinterpret_cast<uint4*>(p) = make_uint4((hl[0] & 0xFFFFu) | (hl[1] << 16), (hl[2] & 0xFFFFu) | (hl[3] << 16),
-                                              (hl[4] & 0xFFFFu) | (hl[5] << 16), (hl[6] & 0xFFFFu) | (hl[7] << 16));
-    *reinterpret_cast<uint4*>(p + kSplitLoOffset) =
-        make_uint4((hl[0] >> 16) | (hl[1] & 0xFFFF0000u), (hl[2] >> 16) | (hl[3] & 0xFFFF0000u),
-                   (hl[4] >> 16) | (hl[5] & 0xFFFF0000u), (hl[6] >> 16) | (hl[7] & 0xFFFF0000u));
-}
 
 __global__ __launch_bounds__(kBfNT) void base_frozen_operands_kernel(const BfBatch bt_) {
     const LBBNN_CONST_AS BfBatch* bt = kernarg_as<BfBatch>();
     int wg0;
-    const int li = bf_layer_of(bt, wg0);
+    const int li = layer_of(bt, wg0);
     const LBBNN_CONST_AS BfLayer& a = bt->l[li];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int o = kBfRows * ((int)blockIdx.x - wg0) + wv;
@@ -118,7 +63,7 @@ __global__ __launch_bounds__(kBfNT) void base_frozen_operands_kernel(const BfBat
     const int I = a.I, ld = a.ld, If = a.I_full;
     const bool mpm = bt->mode == LBBNN_GATES_MPM, split = a.split != 0, vec = a.vec != 0;
     const float thr = bt->threshold;
-    const int r = bf_index(a.rows, o, a.O_full);
+    const int r = map_index(a.rows, o, a.O_full);
     const size_t rowoff = (size_t)r * If;
     const float* mu_r = a.mu + rowoff; const float* rho_r = a.rho + rowoff; const float* lam_r = a.lambdal + rowoff;
     float asum = 0.f;
@@ -142,7 +87,7 @@ __global__ __launch_bounds__(kBfNT) void base_frozen_operands_kernel(const BfBat
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 if (i0 + e < I) {
-                    const int c = bf_index(a.cols, i0 + e, If);
+                    const int c = map_index(a.cols, i0 + e, If);
                     mu[e] = mu_r[c]; rho[e] = rho_r[c]; lam[e] = lam_r[c];
                 }
             }
@@ -185,7 +130,7 @@ __global__ __launch_bounds__(kBfNT) void base_frozen_operands_kernel(const BfBat
 __global__ __launch_bounds__(kBfNT) void base_frozen_members_kernel(const BfBatch bt_, const uint64_t* rng) {
     const LBBNN_CONST_AS BfBatch* bt = kernarg_as<BfBatch>();
     int wg0;
-    const int li = bf_layer_of(bt, wg0);
+    const int li = layer_of(bt, wg0);
     const LBBNN_CONST_AS BfLayer& a = bt->l[li];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int o = kBfRows * ((int)blockIdx.x - wg0) + wv;
@@ -197,7 +142,7 @@ __global__ __launch_bounds__(kBfNT) void base_frozen_members_kernel(const BfBatc
     const uint64_t seed = rng[0], off0 = rng[1], adv = bt->member_advance;
     const uint32_t lid = a.layer_id;
     const uint32_t s_gate = LBBNN_STREAM_GATE * 64u + lid, s_w = LBBNN_STREAM_EPS_W * 64u + lid;
-    const int r = bf_index(a.rows, o, a.O_full);
+    const int r = map_index(a.rows, o, a.O_full);
 
     // the member biases, at the full row's counter: lane t draws those of members t, t + 64, ... (first member stride only)
     if (m0 == 0) {
@@ -230,7 +175,7 @@ __global__ __launch_bounds__(kBfNT) void base_frozen_members_kernel(const BfBatc
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int k = 4 * q + e;
-                col[k] = (i0 + k < I) ? bf_index(a.cols, i0 + k, If) : -1;
+                col[k] = (i0 + k < I) ? map_index(a.cols, i0 + k, If) : -1;
                 any[q] = any[q] || (i0 + k < I && (sample || wm[k] != 0.f || ws[k] != 0.f));
             }
         }
@@ -257,7 +202,8 @@ __global__ __launch_bounds__(kBfNT) void base_frozen_members_kernel(const BfBatc
                     }
                     const float ek = pick4(n, c & 3), sigma = ws[k], mu_k = wm[k];
                     if (sample) {
-                        const float g = gate_draw(al[k], uniform24(pick4(ub, c & 3)), T, hard);
+                        float dcda;                                       // (the derivative is the backward pass's)
+                        const float g = gate_draw(al[k], uniform24(pick4(ub, c & 3)), T, hard, &dcda);
                         w[k] = g * (mu_k + sigma * ek);                                         // :232-233
                         gsum += g;
                     } else {
@@ -274,9 +220,6 @@ __global__ __launch_bounds__(kBfNT) void base_frozen_members_kernel(const BfBatc
         }
     }
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 // the shape, alignment and map checks both entry points make of a layer, and the fields both kernels read
 int fill_layer(BfLayer& a, const lbbnn_base_frozen_desc_t& d, const lbbnn_compact_map_t* m) {

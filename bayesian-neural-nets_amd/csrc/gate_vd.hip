@@ -1,24 +1,17 @@
 // K6 (baseline LBBNN gate x Gaussian weight sampling + Monte-Carlo log-probabilities) and
 // K7 (variational-dropout operand pass) -- see include/lbbnn.h.  Both are one-pass HBM-bound kernels
-// that feed the same dual-moment GEMM.
+// that feed the same dual-moment GEMM.  What they store goes out in the one operand layout of operand_store.h, which also
+// holds the scalar bf16 split (bf16_hi_lo), uniform24 and gate_draw that the frozen baseline model (base_frozen.hip) shares.
 #include <climits>
 #include <cmath>
 #include "lbbnn_device.h"
 #include "lbbnn_internal.h"
+#include "operand_store.h"
 
 namespace {
 
 using namespace lbbnn;
 
-__device__ __forceinline__ uint32_t bf16_rne_bits(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-// the split bf16 pair of one operand value: hi | lo << 16 (hi = RNE(v), lo = RNE(v - hi))
-__device__ __forceinline__ uint32_t bf16_hi_lo(float v) {
-    const uint32_t h = bf16_rne_bits(v);
-    return h | (bf16_rne_bits(v - __uint_as_float(h << 16)) << 16);
-}
 // store one operand value at [o][i] either as fp32 or in the split bf16 hi|lo layout
 // split: 0 = fp32, 1 = bf16 hi|lo (LBBNN_F_SPLIT16), 2 = fp16 in the hi unit, zero lo (LBBNN_F_HALF16: the single-product
 // fp16 form of the variational-dropout operands)
@@ -42,30 +35,10 @@ __device__ __forceinline__ void store_operand(void* base, int split, size_t O, i
 
 // ------------------------------------------------------------------------------------------------ in-kernel draws of K6 / K6b
 // (lbbnn_gate_sample_draw / lbbnn_gate_backward_draw, include/lbbnn.h)
-constexpr float kProbEps = 1.1920928955078125e-7f;      // torch.finfo(float32).eps: clamp_probs
-constexpr float kTiny = 1.17549435082228750797e-38f;    // torch.finfo(float32).tiny: _clipped_sigmoid, Gamma.rsample
-
-// 24 random bits -> (k + 0.5) 2^-24: strictly inside (0, 1), exact in fp32
-__device__ __forceinline__ float uniform24(uint32_t r) { return ((float)(r >> 8) + 0.5f) * 5.9604644775390625e-8f; }
-
 __device__ __forceinline__ float gate_u(uint64_t seed, uint64_t offs, uint32_t layer, int o, int i) {
     const Philox4 r = philox_bits4(seed, offs, LBBNN_STREAM_GATE * 64u + layer, (uint64_t)o, (uint32_t)(i >> 2));
     const uint32_t b = (i & 3) == 0 ? r.x : (i & 3) == 1 ? r.y : (i & 3) == 2 ? r.z : r.w;
     return uniform24(b);
-}
-
-// RelaxedBernoulli(probs = al, temperature = T).rsample() given its uniform (torch: LogitRelaxedBernoulli.rsample + the
-// clipped SigmoidTransform); hard: Bernoulli(al).sample() as u < al.  *dcda: dc/d al (0 where a clamp is active).
-__device__ __forceinline__ float gate_draw(float al, float u, float T, bool hard, float* dcda) {
-    if (hard) { *dcda = 0.f; return u < al ? 1.f : 0.f; }
-    const float p = fminf(fmaxf(al, kProbEps), 1.f - kProbEps);
-    const float uc = fminf(fmaxf(u, kProbEps), 1.f - kProbEps);
-    const float z = (((logf(uc) - log1pf(-uc)) + logf(p)) - log1pf(-p)) / T;
-    const float s = 1.f / (1.f + expf(-z));
-    const float c = fminf(fmaxf(s, kTiny), 1.f - kProbEps);
-    const bool in = (al >= kProbEps && al <= 1.f - kProbEps) && (s >= kTiny && s <= 1.f - kProbEps);
-    *dcda = in ? (c * (1.f - c)) / (T * (p * (1.f - p))) : 0.f;
-    return c;
 }
 
 // Standard Gamma(a) of element `e` (Marsaglia & Tsang, ACM TOMS 26(3), 2000): attempt k uses Philox counter (e, k) -- one
@@ -492,6 +465,8 @@ __global__ __launch_bounds__(kGmThreads) void gate_members_kernel(const GateMemb
                     gsum += g;
                 }
             }
+            // store8_operand of operand_store.h at member m, spelled out: through the call the kernel does not compile to the
+            // same instructions (it runs in every live ensemble)
             if (L.flags & LBBNN_F_SPLIT16) {
                 uint32_t hl[8];
 #pragma unroll

@@ -27,6 +27,7 @@
 #include <cstdlib>
 #include "lbbnn_device.h"
 #include "lbbnn_internal.h"
+#include "operand_store.h"
 
 namespace {
 
@@ -37,29 +38,9 @@ struct WeightPassBatch { WeightPassArgs l[LBBNN_MAX_LAYERS]; int row_end[LBBNN_M
 
 struct Elem { float ew, vw, kl, amu, avar; };
 
-// round-to-nearest-even fp32 -> bf16 bits (finite inputs)
-__device__ __forceinline__ uint32_t bf16_rne(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ float bf16_to_f32(uint32_t b) { return __uint_as_float(b << 16); }
-// split w = hi + lo (both bf16): hi = rne(w), lo = rne(w - hi); packs 4 elements into two uint2.  The roundings are
-// the hardware's v_cvt_pk_bf16_f32 (RNE, two values per instruction): ~12 VALU per float4 instead of ~50 for the
-// integer form above, bit-identical for finite inputs.
-typedef __bf16 k1_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float k1_floatx2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t cvt_pk(float a, float b) {
-    const k1_floatx2 v = {a, b};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, k1_bf16x2));
-}
-__device__ __forceinline__ void split4(const float4 w, uint2& hi, uint2& lo) {
-    const uint32_t h0 = cvt_pk(w.x, w.y), h1 = cvt_pk(w.z, w.w);
-    hi = make_uint2(h0, h1);
-    lo = make_uint2(cvt_pk(w.x - __uint_as_float(h0 << 16), w.y - __uint_as_float(h0 & 0xFFFF0000u)),
-                    cvt_pk(w.z - __uint_as_float(h1 << 16), w.w - __uint_as_float(h1 & 0xFFFF0000u)));
-}
-
+// The bf16 split (cvt_pk / split4) and the paired store of its 16-B units are operand_store.h's.
 // fp16 forms for the row-scaled format (LBBNN_F_F16S): w * scale = hi + lo, both IEEE fp16 (v_cvt_pk_f16_f32, RNE)
+typedef float k1_floatx2 __attribute__((ext_vector_type(2)));
 typedef _Float16 k1_f16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t cvt_pk_h(float a, float b) {
     const k1_floatx2 v = {a, b};
@@ -350,7 +331,6 @@ __device__ __forceinline__ float dot4(const float4 a, const float4 b) { return (
 __device__ __forceinline__ float4 fma4(const float4 u, float s, const float4 z) {
     return make_float4(z.x + u.x * s, z.y + u.y * s, z.z + u.z * s, z.w + u.w * s);
 }
-__device__ __forceinline__ uint32_t dpp_xor1(uint32_t v) { return (uint32_t)dpp_mov<0xB1>((int)v); }   // lane ^ 1
 
 // INFLOW: some layer of the launch computes its planar flows inside its workgroups (f.on); the fused forwards since K3v have
 // none, and their instantiation carries neither that code nor its register pressure.
@@ -621,21 +601,20 @@ __global__ __launch_bounds__(RowsCfg<INFLOW>::NT, 3) void weight_rows_kernel(con
                     if (vwp) reinterpret_cast<float4*>(vwp + (size_t)o * P)[j] = vw;
                 }
             } else {
-                // 16-B units: the even lane of a pair holds k = 8m..8m+3, the odd lane k = 8m+4..8m+7; the even lane stores
-                // the hi unit (its hi half | the partner's), the odd lane the lo unit next to it -- a wave covers 1 KiB contiguous
+                // whole 16-B units through the lane-pair exchange (pair_unit: every lane takes part; vwp is wave-uniform).  The
+                // address and the store stay spelled out here: through store_pair_units the kernel does not compile to the
+                // same instructions
                 const bool odd = lane & 1;
                 const size_t at = split_hi_index((size_t)o, 4 * (j & ~1), P) + (odd ? kSplitLoOffset : 0);
                 uint2 hi, lo;
                 split4(ew, hi, lo);
                 {
-                    const uint32_t r0 = dpp_xor1(odd ? hi.x : lo.x), r1 = dpp_xor1(odd ? hi.y : lo.y);
-                    const uint4 unit = make_uint4(odd ? r0 : hi.x, odd ? r1 : hi.y, odd ? lo.x : r0, odd ? lo.y : r1);
+                    const uint4 unit = pair_unit(odd, hi, lo);
                     if (ewp && j < nq) *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(ewp) + at) = unit;
                 }
                 if (vwp) {
                     split4(vw, hi, lo);
-                    const uint32_t r0 = dpp_xor1(odd ? hi.x : lo.x), r1 = dpp_xor1(odd ? hi.y : lo.y);
-                    const uint4 unit = make_uint4(odd ? r0 : hi.x, odd ? r1 : hi.y, odd ? lo.x : r0, odd ? lo.y : r1);
+                    const uint4 unit = pair_unit(odd, hi, lo);
                     if (j < nq) *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(vwp) + at) = unit;
                 }
             }
@@ -676,8 +655,7 @@ __global__ __launch_bounds__(RowsCfg<INFLOW>::NT, 3) void weight_rows_kernel(con
                 const float4 w = ew_keep[g];
                 if (f16s) split4_hs(w, se, hi, lo);
                 else split4(w, hi, lo);
-                const uint32_t r0 = dpp_xor1(odd ? hi.x : lo.x), r1 = dpp_xor1(odd ? hi.y : lo.y);
-                const uint4 unit = make_uint4(odd ? r0 : hi.x, odd ? r1 : hi.y, odd ? lo.x : r0, odd ? lo.y : r1);
+                const uint4 unit = pair_unit(odd, hi, lo);
                 if (ewp && j < nq) *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(ewp) + at) = unit;
             }
             if (vwp && vhi_only) {
@@ -690,8 +668,7 @@ __global__ __launch_bounds__(RowsCfg<INFLOW>::NT, 3) void weight_rows_kernel(con
                 const float4 w = vw_keep[g];
                 if (f16s) split4_hs(w, sv, hi, lo);
                 else split4(w, hi, lo);
-                const uint32_t r0 = dpp_xor1(odd ? hi.x : lo.x), r1 = dpp_xor1(odd ? hi.y : lo.y);
-                const uint4 unit = make_uint4(odd ? r0 : hi.x, odd ? r1 : hi.y, odd ? lo.x : r0, odd ? lo.y : r1);
+                const uint4 unit = pair_unit(odd, hi, lo);
                 if (j < nq) *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(vwp) + at) = unit;
             }
         }
@@ -712,8 +689,6 @@ __global__ __launch_bounds__(RowsCfg<INFLOW>::NT, 3) void weight_rows_kernel(con
         a.bias_var[o] = sb * sb;                      // bias.sigma**2, LBBNN-GP-MF-LRT.py:173
     }
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
 

@@ -140,6 +140,183 @@ def test_frozen_members_argument_checks(lib):
     assert mem(d, 1, 2, rng, 1, None) == E_FLAGS
 
 
+def _early_return_rows(_lib):
+    """(entry point, label, arguments, code): one row per early return of the five frozen entry points, in the order the
+    code takes them.  Most rows are invalid a second time at a later check with another code, so a reordered check changes
+    what comes back.  No row reaches a launch: the pointers are never dereferenced."""
+    import test_frozen_compact_host as tc
+    import test_frozen_dense_host as td
+    BIG = 16384 + 4                                                       # > LBBNN_MAX_FLOW_DIM, % 4 == 0
+    BIG_LD = 16416                                                        # >= BIG, % 32 == 0
+    rng = ctypes.c_void_p(4096 * 30)
+    rows = []
+
+    def full(**kw):
+        split, z_ms = kw.pop("split", False), kw.pop("z_mstride", None)
+        d = _desc(_lib, **kw)
+        for k in range(len(d)):
+            d[k].flags = 0x4 if split else 0
+            if z_ms is not None:
+                d[k].z_mstride = z_ms
+        return d
+
+    def compact(**kw):
+        split, z_ms = kw.pop("split", False), kw.pop("z_mstride", None)
+        d, m = tc._desc(_lib, **kw)
+        for k in range(len(d)):
+            d[k].flags = 0x4 if split else 0
+            if z_ms is not None:
+                d[k].z_mstride = z_ms
+        return d, m
+
+    def dense(**kw):
+        z_ms = kw.pop("z_mstride", None)
+        d = td._desc(_lib, **kw)
+        if z_ms is not None:
+            for k in range(len(d)):
+                d[k].z_mstride = z_ms
+        return d
+
+    def edit(d, k=0, **fields):
+        for name, v in fields.items():
+            if name == "T":
+                d[k].z_flow.T = v
+            else:
+                setattr(d[k], name, v)
+        return d
+
+    # ---------------------------------------------------------------- lbbnn_frozen_operands(L, n, stream)
+    e = "lbbnn_frozen_operands"
+    rows += [
+        (e, "L null, n = 0", (None, 0, None), E_NULL),
+        (e, "n = 0, weight_mu null", (edit(full(), weight_mu=None), 0, None), E_SHAPE),
+        (e, "n too large, e0 null", (edit(full(), e0=None), _lib.MAX_LAYERS + 1, None), E_SHAPE),
+        (e, "kept_rows null, ld = 48", (edit(full(ld=48), kept_rows=None), 1, None), E_NULL),
+        (e, "bias_rho null, O = 0", (edit(full(O=0), bias_rho=None), 1, None), E_NULL),
+        (e, "O = 0, ld = 48", (full(O=0, ld=48), 1, None), E_SHAPE),
+        (e, "I > ld, e0 misaligned", (edit(full(I=33, ld=32), e0=4096 + 4), 1, None), E_SHAPE),
+        (e, "ld = 48, unknown flag", (edit(full(ld=48), flags=0x1), 1, None), E_ALIGN),
+        (e, "e_w misaligned, mode 7", (edit(full(), e_w=4096 + 4, mode=7), 1, None), E_ALIGN),
+        (e, "lambdal off a float, unknown flag", (edit(full(), lambdal=4096 + 2, flags=0x1), 1, None), E_ALIGN),
+        (e, "unknown flag beside split, I = 6", (edit(full(I=6), flags=0x5), 1, None), E_FLAGS),
+        (e, "mode 2, split with I = 6", (edit(full(I=6, split=True), mode=2), 1, None), E_FLAGS),
+        (e, "split with I = 6", (full(I=6, split=True), 1, None), E_ALIGN),
+        (e, "split with weight_mu off 16 B", (edit(full(split=True), weight_mu=4096 + 4), 1, None), E_ALIGN),
+        # no I % 8 rule for split operands here (the compact call has it): layer 0 passes, layer 1 is what fails
+        (e, "split with I = 12 passes; second layer: mode 7", (edit(full(I=12, split=True, n=2), 1, mode=7), 2, None), E_FLAGS),
+        (e, "second layer: kept_rows null, ld = 48", (edit(full(n=2), 1, kept_rows=None, ld=48), 2, None), E_NULL),
+    ]
+    # ---------------------------------------------------------------- lbbnn_frozen_operands_compact(L, M, n, stream)
+    e = "lbbnn_frozen_operands_compact"
+
+    def cm(dm, k=0, **fields):                                            # edit the map
+        for name, v in fields.items():
+            setattr(dm[1][k], name, v)
+        return dm
+
+    def cd(dm, k=0, **fields):                                            # edit the descriptor
+        edit(dm[0], k, **fields)
+        return dm
+    rows += [
+        (e, "L null, n = 0", (None, compact()[1], 0, None), E_NULL),
+        (e, "M null, n = 0", (compact()[0], None, 0, None), E_NULL),
+        (e, "n = 0, rows null", (*cm(compact(), rows=None), 0, None), E_SHAPE),
+        (e, "kept_rows null, ld = 48", (*cd(compact(ld=48), kept_rows=None), 1, None), E_NULL),
+        (e, "O = 0, cols null", (*cm(compact(O=0), cols=None), 1, None), E_SHAPE),
+        (e, "ld = 48, mode 0", (*cd(compact(ld=48), mode=0), 1, None), E_ALIGN),
+        (e, "var_w misaligned, mode 0", (*cd(compact(), var_w=4096 + 4, mode=0), 1, None), E_ALIGN),
+        (e, "lambdal off a float, mode 0", (*cd(compact(), lambdal=4096 + 2, mode=0), 1, None), E_ALIGN),
+        (e, "unknown flag, cols null", (*cm(cd(compact(), flags=0x1), cols=None), 1, None), E_FLAGS),
+        (e, "mode 0, cols null", (*cm(cd(compact(), mode=0), cols=None), 1, None), E_FLAGS),
+        (e, "cols null, split with I = 12", (*cm(compact(I=12, split=True), cols=None), 1, None), E_NULL),
+        (e, "O' > O_full, rows misaligned", (*cm(compact(O=9, O_full=8), rows=4096 * 40 + 2), 1, None), E_SHAPE),
+        (e, "I' > I_full, split with I' = 20", (*compact(I=20, I_full=16, split=True), 1, None), E_SHAPE),
+        (e, "cols off an int, split with I' = 12", (*cm(compact(I=12, split=True), cols=4096 * 41 + 2), 1, None), E_ALIGN),
+        (e, "split with I' = 12", (*compact(I=12, split=True), 1, None), E_ALIGN),
+        (e, "second layer: mode 0, cols null", (*cm(cd(compact(n=2), 1, mode=0), 1, cols=None), 2, None), E_FLAGS),
+    ]
+    # ---------------------------------------------------------------- lbbnn_frozen_members(L, n, members, rng, adv, stream)
+    e = "lbbnn_frozen_members"
+    mf = lambda **kw: full(mnf=True, **kw)
+    rows += [
+        (e, "L null, n = 0", (None, 0, 1, rng, 1, None), E_NULL),
+        (e, "n = 0, e0 null", (edit(mf(), e0=None), 0, 1, rng, 1, None), E_SHAPE),
+        (e, "members = 0, q0_log_var null", (edit(mf(), q0_log_var=None), 1, 0, rng, 1, None), E_SHAPE),
+        (e, "q0_log_var null, T = 17", (edit(mf(), q0_log_var=None, T=17), 1, 2, rng, 1, None), E_NULL),
+        (e, "T = 17, no rng", (edit(mf(), T=17), 1, 2, None, 1, None), E_SHAPE),
+        (e, "transforms without parameters, no rng", (edit(mf(), T=2), 1, 2, None, 1, None), E_NULL),
+        (e, "no rng, O = 0", (mf(O=0), 1, 2, None, 1, None), E_NOISE),
+        (e, "O = 0, ld = 48", (mf(O=0, ld=48), 1, 2, rng, 1, None), E_SHAPE),
+        # the flow runs at I: refused beyond LBBNN_MAX_FLOW_DIM (the compact call has no such test of I')
+        (e, "I > LBBNN_MAX_FLOW_DIM, z_fwd misaligned", (edit(mf(I=BIG, ld=BIG_LD), z_fwd=4096 * 22 + 4), 1, 2, rng, 1, None), E_SHAPE),
+        (e, "z_mstride < I, ld = 48", (mf(I=8, ld=48, z_mstride=4), 1, 2, rng, 1, None), E_SHAPE),
+        (e, "ld = 48, unknown flag", (edit(mf(ld=48), flags=0x2), 1, 2, rng, 1, None), E_ALIGN),
+        (e, "I = 6, unknown flag", (edit(mf(I=6), flags=0x2), 1, 2, rng, 1, None), E_ALIGN),
+        (e, "z_fwd misaligned, unknown flag", (edit(mf(), z_fwd=4096 * 22 + 4, flags=0x2), 1, 2, rng, 1, None), E_ALIGN),
+        (e, "unknown flag", (edit(mf(), flags=0x2), 1, 2, rng, 1, None), E_FLAGS),
+        (e, "split with I = 12 passes; second layer: unknown flag", (edit(mf(I=12, split=True, n=2), 1, flags=0x2), 2, 2, rng, 1, None),
+         E_FLAGS),
+        (e, "first layer LRT; second layer: no rng, O = 0", (edit(edit(mf(n=2), 0, q0_mean=None), 1, O=0), 2, 2, None, 1, None), E_NOISE),
+    ]
+    # ---------------------------------------------------------------- lbbnn_frozen_members_dense(L, F, n, members, rng, adv, stream)
+    e = "lbbnn_frozen_members_dense"
+    flows, keep = td._flows(_lib, n=2)
+    rows += [
+        (e, "L null, n = 0", (None, flows, 0, 1, rng, 1, None), E_NULL),
+        (e, "F null, n = 0", (dense(), None, 0, 1, rng, 1, None), E_NULL),
+        (e, "members = 65536, z_fwd null", (edit(dense(), z_fwd=None), flows, 1, 65536, rng, 1, None), E_SHAPE),
+        (e, "e_w_members null, no rng", (edit(dense(), e_w_members=None), flows, 1, 2, None, 1, None), E_NULL),
+        (e, "z_flow.T is not read: no rng, O = 0", (edit(dense(O=0), T=99), flows, 1, 2, None, 1, None), E_NOISE),
+        (e, "I > LBBNN_MAX_FLOW_DIM, z_fwd misaligned", (edit(dense(I=BIG, ld=BIG_LD), z_fwd=4096 * 22 + 8), flows, 1, 2, rng, 1, None),
+         E_SHAPE),
+        (e, "z_mstride < I, ld = 48", (dense(I=8, ld=48, z_mstride=4), flows, 1, 2, rng, 1, None), E_SHAPE),
+        (e, "z_mstride % 4, unknown flag", (edit(dense(z_mstride=34), flags=0x2), flows, 1, 2, rng, 1, None), E_ALIGN),
+        (e, "e0 misaligned, unknown flag", (edit(dense(), e0=4096 * 5 + 4, flags=0x2), flows, 1, 2, rng, 1, None), E_ALIGN),
+        (e, "unknown flag", (edit(dense(), flags=0x2), flows, 1, 2, rng, 1, None), E_FLAGS),
+        (e, "second layer: z_mstride < I, ld = 48", (edit(dense(n=2), 1, ld=48, z_mstride=4), flows, 2, 2, rng, 1, None), E_SHAPE),
+    ]
+    # ---------------------------------------------------------------- lbbnn_frozen_members_compact(L, M, n, members, rng, adv, stream)
+    e = "lbbnn_frozen_members_compact"
+    mc = lambda **kw: compact(mnf=True, **kw)
+    rows += [
+        (e, "L null, members = 0", (None, mc()[1], 1, 0, rng, 1, None), E_NULL),
+        (e, "M null, members = 0", (mc()[0], None, 1, 0, rng, 1, None), E_NULL),
+        (e, "members = 65536, rows null", (*cm(mc(), rows=None), 1, 65536, rng, 1, None), E_SHAPE),
+        (e, "e0 null, T = 17", (*cd(mc(), e0=None, T=17), 1, 2, rng, 1, None), E_NULL),
+        (e, "T = 17, no rng", (*cd(mc(), T=17), 1, 2, None, 1, None), E_SHAPE),
+        (e, "transforms without parameters, no rng", (*cd(mc(), T=2), 1, 2, None, 1, None), E_NULL),
+        (e, "no rng, O = 0", (*mc(O=0), 1, 2, None, 1, None), E_NOISE),
+        (e, "O = 0, rows null", (*cm(mc(O=0), rows=None), 1, 2, rng, 1, None), E_SHAPE),
+        # no test of I' against LBBNN_MAX_FLOW_DIM (the flow runs at I_full): the map's null pointer is what is found
+        (e, "I' > LBBNN_MAX_FLOW_DIM is not refused as such: rows null",
+         (*cm(mc(I=BIG, ld=BIG_LD, I_full=BIG + 4, z_mstride=BIG_LD), rows=None), 1, 2, rng, 1, None), E_NULL),
+        (e, "rows null, z_mstride < I_full", (*cm(mc(z_mstride=8), rows=None), 1, 2, rng, 1, None), E_NULL),
+        (e, "O' > O_full, z_fwd misaligned", (*cd(mc(O=9, O_full=8), z_fwd=4096 * 22 + 4), 1, 2, rng, 1, None), E_SHAPE),
+        (e, "cols off an int, z_mstride < I_full", (*cm(mc(z_mstride=8), cols=4096 * 41 + 2), 1, 2, rng, 1, None), E_ALIGN),
+        (e, "I_full > LBBNN_MAX_FLOW_DIM, ld = 48", (*mc(ld=48, I_full=BIG, z_mstride=BIG_LD), 1, 2, rng, 1, None), E_SHAPE),
+        (e, "z_mstride < I_full, ld = 48", (*mc(ld=48, z_mstride=8), 1, 2, rng, 1, None), E_SHAPE),
+        (e, "I_full % 4, unknown flag", (*cd(mc(I_full=18), flags=0x2), 1, 2, rng, 1, None), E_ALIGN),
+        (e, "z_fwd misaligned, unknown flag", (*cd(mc(), z_fwd=4096 * 22 + 4, flags=0x2), 1, 2, rng, 1, None), E_ALIGN),
+        (e, "unknown flag beside split, I' = 12", (*cd(mc(I=12), flags=0x6), 1, 2, rng, 1, None), E_FLAGS),
+        (e, "split with I' = 12", (*mc(I=12, split=True), 1, 2, rng, 1, None), E_ALIGN),
+        (e, "second layer: I_full % 4, unknown flag", (*cd(cm(mc(n=2), 1, I_full=18), 1, flags=0x2), 2, 2, rng, 1, None), E_ALIGN),
+    ]
+    return rows, keep
+
+
+def test_frozen_entry_points_early_return_order(lib):
+    """Every early return of lbbnn_frozen_operands, lbbnn_frozen_operands_compact, lbbnn_frozen_members,
+    lbbnn_frozen_members_dense and lbbnn_frozen_members_compact, in the order each entry point takes them, with the two
+    places where the full and the compact calls differ on purpose: I against LBBNN_MAX_FLOW_DIM (members) and I % 8 with
+    the split flag (operands, members)."""
+    from bnn_amd import _lib
+    rows, keep = _early_return_rows(_lib)
+    assert {r[0] for r in rows} == {"lbbnn_frozen_operands", "lbbnn_frozen_operands_compact", "lbbnn_frozen_members",
+                                    "lbbnn_frozen_members_dense", "lbbnn_frozen_members_compact"}
+    got = [(entry, label, getattr(lib, entry)(*args)) for entry, label, args, _ in rows]
+    assert got == [(entry, label, code) for entry, label, _, code in rows]
+
+
 def test_freeze_refusals_say_what_to_use():
     import bnn_amd
     from bnn_amd import evaluate
