@@ -414,6 +414,7 @@ SIGNATURES = {
     "lbbnn_log_softmax_rows": (c_i, [c_p, c_i, c_p, c_i, c_i, c_i, c_p]),
     "lbbnn_binary_head": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_i, c_p]),
     "lbbnn_elbo_bce_loss": (c_i, [c_p, c_i, c_p, c_i, c_i, c_i, c_p, ctypes.c_float, c_p, c_p, c_i, c_p]),
+    "lbbnn_elbo_bce_loss_monitor": (c_i, [c_p, c_i, c_p, c_i, c_i, c_i, c_p, ctypes.c_float, c_p, c_p, c_i, c_p, c_p, c_p]),
     "lbbnn_elbo_bce_loss_backward": (c_i, [c_p, c_p, c_i, c_p, c_i, c_i, c_i, ctypes.c_float, c_p, c_p, c_p, c_p]),
     "lbbnn_sigmoid_backward": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_p]),
     "lbbnn_frozen_operands": (c_i, [ctypes.POINTER(FrozenDesc), c_i, c_p]),

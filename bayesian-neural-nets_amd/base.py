@@ -706,7 +706,7 @@ class BayesianNetwork(nn.Module):
             t = t + l.log_variational_posterior
         return t
 
-    def sample_elbo(self, input, target, samples=SAMPLES, *, num_batches=None, draws="torch", stats=None):
+    def sample_elbo(self, input, target, samples=SAMPLES, *, num_batches=None, draws="torch", stats=None, monitor=None):
         """:285-319, same positional arguments.  NUM_BATCHES / SAMPLES are module globals there (:34-67) and here
         (``bnn_amd.base.NUM_BATCHES = 600``, ``SAMPLES = 1``); ``num_batches=`` overrides the former per call.
         ``draws``: "torch" (default) draws the gates and the Gamma precisions with torch.distributions, as the reference;
@@ -717,7 +717,17 @@ class BayesianNetwork(nn.Module):
         converted with ``.float()``), the likelihood term is ``losses.elbo_bce_loss`` (nn.BCELoss(reduction='sum'), fused), and the
         return has the script's five values (loss, log_prior, log_q, nll, out) with ``out`` the mean of the samples'
         probabilities (for one sample the tensor itself).  ``stats``: the int32[4] device tensor ``elbo_bce_loss`` adds its counts
-        to (training accuracy with one read per epoch); sigmoid head only."""
+        to (training accuracy with one read per epoch); sigmoid head only.
+        ``monitor``: a ``losses.TrainMonitor`` (``dims[-1]`` classes / units) that records the step and holds the guard word
+        for ``optimizer.set_guard``; both heads, both ``draws`` modes, ``samples == 1`` only (one monitored step is one loss
+        launch) and HIP tensors only.  The step's loss is then ONE fused launch, ``losses.elbo_loss(out, target, log_q -
+        log_prior, num_batches, monitor=monitor)`` (``elbo_bce_loss`` for a sigmoid head), in place of the nll launch and the
+        torch expression ``nll + (log_q - log_prior) / num_batches``; the returned ``nll`` is ``(loss - (log_q - log_prior) /
+        num_batches).detach()`` (the reference only prints it).  The fused loss rounds ONCE, from fp64, so it equals the
+        unfused one to fp32 rounding, not bit for bit; likewise the gradients of ``log_prior`` and ``log_q``: g * (1 / N)
+        against g / N.  ``log_prior`` and ``log_q`` themselves are the same bits.  Without a monitor nothing changes.  The guard
+        catches a loss that is not finite -- e.g. an invalid ``a``, ``b``, ``pa``, ``pb`` whose draw or density comes out NaN or
+        inf -- not an invalid parameter whose loss stays finite (VALIDATE_ARGS)."""
         if draws not in ("torch", "hip"):
             raise ValueError("bnn_amd: sample_elbo(draws=...) must be 'torch' or 'hip', got %r" % (draws,))
         if num_batches is None:
@@ -728,8 +738,17 @@ class BayesianNetwork(nn.Module):
         if sigmoid:
             from .losses import elbo_bce_loss
             target = target if target.dtype == torch.float32 else target.float()
+        if monitor is not None:
+            from .losses import TrainMonitor
+            who = "bnn_amd: sample_elbo(monitor=...): "
+            if not isinstance(monitor, TrainMonitor):
+                raise ValueError(who + "monitor must be a bnn_amd.TrainMonitor, got %s" % type(monitor).__name__)
+            if samples != 1:
+                raise ValueError(who + "one monitored step is one loss launch: samples must be 1, got %d" % samples)
+            if draws == "torch" and not input.is_cuda:
+                raise ValueError(who + "the monitor lives in the fused HIP loss; input is on %s" % input.device)
         if draws == "hip":
-            return self._sample_elbo_hip(input, target, samples, num_batches, stats)
+            return self._sample_elbo_hip(input, target, samples, num_batches, stats, monitor)
         dev = input.device
         lps, lqs, nlls, outs = [], [], [], []
         for _ in range(samples):
@@ -741,6 +760,8 @@ class BayesianNetwork(nn.Module):
             out = self.forward(input, *gs, sample=True, medimean=False)
             lps.append(self.log_prior())
             lqs.append(self.log_variational_posterior())
+            if monitor is not None:
+                return self._monitored_elbo(out, target, lps[0], lqs[0], num_batches, stats, monitor)
             if sigmoid:
                 nlls.append(elbo_bce_loss(out, target, stats=stats))  # sim study :292-296
                 outs.append(out)
@@ -754,7 +775,17 @@ class BayesianNetwork(nn.Module):
             return loss, log_prior, log_q, nll, (outs[0] if samples == 1 else torch.stack(outs).mean(0))
         return loss, log_prior, log_q, nll
 
-    def _sample_elbo_hip(self, input, target, samples, num_batches, stats=None):
+    def _monitored_elbo(self, out, target, log_prior, log_q, num_batches, stats, monitor):
+        """The tail of a monitored step (samples == 1): the whole ELBO in the one fused loss launch that records it."""
+        from .losses import elbo_bce_loss, elbo_loss
+        kl = log_q - log_prior
+        if self.head == "sigmoid":
+            loss = elbo_bce_loss(out, target, kl, num_batches, stats=stats, monitor=monitor)
+            return loss, log_prior, log_q, loss.detach() - kl.detach() / num_batches, out
+        loss = elbo_loss(out, target, kl, num_batches, monitor=monitor)
+        return loss, log_prior, log_q, loss.detach() - kl.detach() / num_batches
+
+    def _sample_elbo_hip(self, input, target, samples, num_batches, stats=None, monitor=None):
         """sample_elbo(draws="hip"): per sample one Philox snapshot (the offset advances once), one _BaseDrawFn node per
         layer with ReLU / log_softmax in the GEMM epilogues, the NLL as one launch (losses.elbo_loss).  log_prior and log_q:
         up to three layers the chain of torch adds; deeper, one lbbnn_fold_rows launch over the slots the layers' kernels
@@ -800,6 +831,8 @@ class BayesianNetwork(nn.Module):
                 h = F.log_softmax(h, dim=1)
             lps.append(lp)
             lqs.append(lq)
+            if monitor is not None:
+                return self._monitored_elbo(h, target, lp, lq, num_batches, stats, monitor)
             nlls.append(elbo_bce_loss(h, target, stats=stats) if sigmoid else elbo_loss(h, target))
         if samples == 1:
             log_prior, log_q, nll = lps[0], lqs[0], nlls[0]

@@ -3,6 +3,8 @@
 //
 //   lbbnn_binary_head              probs = 1 / (1 + exp(-x));  O == 1: logp2 = [logsigmoid(-x), logsigmoid(x)] from the LOGIT
 //   lbbnn_elbo_bce_loss            loss = sum (y - 1) max(log1p(-p), -100) - y max(log p, -100) + kl * kl_scale, and counts
+//   lbbnn_elbo_bce_loss_monitor    the same loss and counts (bitwise) plus the running totals of a training log and a per-step
+//                                  non-finite flag, still one launch of one workgroup
 //   lbbnn_elbo_bce_loss_backward   g_probs = g (p - y) / max((1 - p) p, 1e-12);  g_logits = g_probs ((1 - p) p);  g_kl = g kl_scale
 //   lbbnn_sigmoid_backward         out = g ((1 - p) p)
 // One pass each; the loss is one workgroup with fp64 partial sums in a fixed order (deterministic), no atomics.  The products and
@@ -34,33 +36,91 @@ __global__ __launch_bounds__(256) void binary_head_kernel(const float* logits, i
     }
 }
 
-__global__ __launch_bounds__(1024) void elbo_bce_loss_kernel(const float* __restrict__ probs, int ldp, const float* __restrict__ target,
-                                                             int ldt, long long n, int O, const float* kl, float kl_scale,
-                                                             float* loss, int* stats, int accumulate) {
-    __shared__ double scratch[16];
-    double s = 0.0, n_ok = 0.0, n_bad = 0.0, n_nonfinite = 0.0;      // the counts are whole numbers < 2^53: exact in fp64
+// The one pass of the BCE loss, shared by the plain and the monitored kernel so that both add the same terms in the same order:
+// element i of the (B, O) block goes to thread i % 1024, a thread adds its elements in rising i, block_sum<double, 16> adds the
+// threads.  Every thread returns the four block totals (the counts are whole numbers < 2^53: exact in fp64).
+struct BceSums { double s, n_ok, n_bad, n_nonfinite; };
+
+__device__ __forceinline__ BceSums bce_sums(const float* __restrict__ probs, int ldp, const float* __restrict__ target, int ldt,
+                                            long long n, int O, double* scratch) {
+    double s = 0.0, n_ok = 0.0, n_bad = 0.0, n_nonfinite = 0.0;
     for (long long i = threadIdx.x; i < n; i += 1024) {
         const long long b = i / O;
         const int o = (int)(i - b * O);
         const float p = probs[b * ldp + o], y = target[b * ldt + o];
         if (!isfinite(p)) n_nonfinite += 1.0;
         if (!target_ok(y)) { n_bad += 1.0; continue; }
-        // torch's own spelling (binary_cross_entropy: log(1 - p) as log1p(-p), the two products in this order), so that the
-        // terms are torch's bits: p = 2e-9 against y = 0 costs 2e-9, not the 0 that logf(1.f - p) rounds to
+        // torch's own spelling (binary_cross_entropy: log(1 - p) as log1p(-p), the two products in this order): p = 2e-9
+        // against y = 0 costs 2e-9, not the 0 that logf(1.f - p) rounds to.  log1pf gives torch.log1p's bits; logf differs
+        // from torch.log in the last bit for about a third of the probabilities (measured)
         const float lp = fmaxf(logf(p), -100.f), lq = fmaxf(log1pf(-p), -100.f);
         s += (double)((y - 1.f) * lq - y * lp);
         if ((p > 0.5f) == (y > 0.5f)) n_ok += 1.0;
     }
-    s = block_sum<double, 16>(s, scratch);
-    n_ok = block_sum<double, 16>(n_ok, scratch);
-    n_bad = block_sum<double, 16>(n_bad, scratch);
-    n_nonfinite = block_sum<double, 16>(n_nonfinite, scratch);
+    BceSums r;
+    r.s = block_sum<double, 16>(s, scratch);
+    r.n_ok = block_sum<double, 16>(n_ok, scratch);
+    r.n_bad = block_sum<double, 16>(n_bad, scratch);
+    r.n_nonfinite = block_sum<double, 16>(n_nonfinite, scratch);
+    return r;
+}
+
+__device__ __forceinline__ void bce_stats(int* stats, int accumulate, const BceSums& r, long long n) {
+    const int c[4] = {(int)r.n_ok, (int)n, (int)r.n_bad, (int)r.n_nonfinite};
+    for (int k = 0; k < 4; ++k) stats[k] = (accumulate ? stats[k] : 0) + c[k];
+}
+
+__global__ __launch_bounds__(1024) void elbo_bce_loss_kernel(const float* __restrict__ probs, int ldp, const float* __restrict__ target,
+                                                             int ldt, long long n, int O, const float* kl, float kl_scale,
+                                                             float* loss, int* stats, int accumulate) {
+    __shared__ double scratch[16];
+    const BceSums r = bce_sums(probs, ldp, target, ldt, n, O, scratch);
     if (threadIdx.x == 0) {
-        *loss = (float)(s + (kl ? (double)(*kl) * (double)kl_scale : 0.0));
-        if (stats) {
-            const int c[4] = {(int)n_ok, (int)n, (int)n_bad, (int)n_nonfinite};
-            for (int k = 0; k < 4; ++k) stats[k] = (accumulate ? stats[k] : 0) + c[k];
+        *loss = (float)(r.s + (kl ? (double)(*kl) * (double)kl_scale : 0.0));
+        if (stats) bce_stats(stats, accumulate, r, n);
+    }
+}
+
+// elbo_bce_loss_kernel plus the training monitor: the same pass, so *loss and stats are its bits.  The unit of
+// account of the totals is one element (b, o): the four block totals of the pass are the counts of the step.  One workgroup,
+// launches of one stream ordered: thread 0 adds to the totals with plain loads and stores -- no atomics, the same bits from run
+// to run.
+__global__ __launch_bounds__(1024) void elbo_bce_loss_monitor_kernel(const float* __restrict__ probs, int ldp,
+                                                                     const float* __restrict__ target, int ldt, long long n, int O,
+                                                                     const float* kl, float kl_scale, float* loss, int* stats,
+                                                                     int accumulate, int64_t* totals, int32_t* guard) {
+    __shared__ double scratch[16];
+    const BceSums r = bce_sums(probs, ldp, target, ldt, n, O, scratch);
+    if (threadIdx.x == 0) {
+        int64_t cnt[LBBNN_MONITOR_COUNTS];
+        double sum[LBBNN_MONITOR_SUMS];
+        double* sums = reinterpret_cast<double*>(totals + LBBNN_MONITOR_COUNTS);
+#pragma unroll
+        for (int q = 0; q < LBBNN_MONITOR_COUNTS; ++q) cnt[q] = totals[q];      // every load ahead of the first store
+#pragma unroll
+        for (int q = 0; q < LBBNN_MONITOR_SUMS; ++q) sum[q] = sums[q];
+        const double kl_term = kl ? (double)(*kl) * (double)kl_scale : 0.0;
+        const float lf = (float)(r.s + kl_term);
+        const bool ok = isfinite(lf);
+        const int64_t bad = (int64_t)r.n_bad;
+        *loss = lf;
+        if (stats) bce_stats(stats, accumulate, r, n);
+        if (guard) *guard = ok ? 0 : 1;
+        totals[LBBNN_MONITOR_STEPS] = cnt[LBBNN_MONITOR_STEPS] + 1;
+        totals[LBBNN_MONITOR_ROWS] = cnt[LBBNN_MONITOR_ROWS] + n;
+        totals[LBBNN_MONITOR_CORRECT] = cnt[LBBNN_MONITOR_CORRECT] + (int64_t)r.n_ok;
+        totals[LBBNN_MONITOR_BAD_TARGETS] = cnt[LBBNN_MONITOR_BAD_TARGETS] + bad;
+        totals[LBBNN_MONITOR_NONFINITE_ROWS] = cnt[LBBNN_MONITOR_NONFINITE_ROWS] + (int64_t)r.n_nonfinite;
+        if (ok) {                                                 // (LBBNN_MONITOR_SKIPPED_STEPS is the optimizer's word: not written)
+            totals[LBBNN_MONITOR_NLL_ROWS] = cnt[LBBNN_MONITOR_NLL_ROWS] + (n - bad);
+            sums[LBBNN_MONITOR_NLL_SUM] = sum[LBBNN_MONITOR_NLL_SUM] + r.s;
+            sums[LBBNN_MONITOR_KL_TERM_SUM] = sum[LBBNN_MONITOR_KL_TERM_SUM] + kl_term;
+            sums[LBBNN_MONITOR_LOSS_SUM] = sum[LBBNN_MONITOR_LOSS_SUM] + (r.s + kl_term);
+        } else {
+            totals[LBBNN_MONITOR_NONFINITE_STEPS] = cnt[LBBNN_MONITOR_NONFINITE_STEPS] + 1;
         }
+        sums[LBBNN_MONITOR_LAST_NLL] = r.s;
+        sums[LBBNN_MONITOR_LAST_LOSS] = (double)lf;
     }
 }
 
@@ -116,6 +176,18 @@ extern "C" int lbbnn_elbo_bce_loss(const float* probs, int ldp, const float* tar
     if (off4(probs) || off4(target) || off4(kl) || off4(loss) || off4(stats)) return LBBNN_E_ALIGN;
     hipLaunchKernelGGL(elbo_bce_loss_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), probs, ldp, target, ldt,
                        (long long)B * O, O, kl, kl_scale, loss, stats, accumulate);
+    return (int)hipGetLastError();
+}
+
+extern "C" int lbbnn_elbo_bce_loss_monitor(const float* probs, int ldp, const float* target, int ldt, int B, int O, const float* kl,
+                                           float kl_scale, float* loss, int* stats, int accumulate, int64_t* totals,
+                                           int32_t* guard, void* stream) {
+    if (!probs || !target || !loss || !totals) return LBBNN_E_NULL;
+    if (bad_shape(B, O) || B < 1 || ldp < O || ldt < O) return LBBNN_E_SHAPE;
+    if (off4(probs) || off4(target) || off4(kl) || off4(loss) || off4(stats) || off4(guard) || ((uintptr_t)totals & 7))
+        return LBBNN_E_ALIGN;
+    hipLaunchKernelGGL(elbo_bce_loss_monitor_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), probs, ldp, target,
+                       ldt, (long long)B * O, O, kl, kl_scale, loss, stats, accumulate, totals, guard);
     return (int)hipGetLastError();
 }
 

@@ -41,7 +41,12 @@ class TrainMonitor:
     ``classes`` (1 to 64) is fixed for the monitor's life.  Under ``graphs.make_graphed_train_step`` the factory's eager warm-up
     steps are real steps and add to the totals: ``reset()`` after building the step.  The monitor is a plain holder of two
     buffers (``to`` / ``_apply`` move them, ``copy.deepcopy`` gives a copy its own) and caches no device address; a captured
-    graph addresses the buffers it was captured with.  Not a data-parallel guard: the loss flag is local to a rank."""
+    graph addresses the buffers it was captured with.  Not a data-parallel guard: the loss flag is local to a rank.
+
+    The binary loss records into the same monitor: ``elbo_bce_loss(..., monitor=mon)`` with ``TrainMonitor(units, device)``
+    (lbbnn_elbo_bce_loss_monitor).  Its unit of account is one element (b, o) of the (B, units) block, so ``rows`` grows by
+    B * units a step; ``base.BayesianNetwork.sample_elbo(monitor=)`` and ``vd.loss_fn(monitor=)`` pass a monitor on to the loss
+    of their family."""
 
     def __init__(self, classes: int, device):
         C = int(classes)
@@ -64,6 +69,7 @@ class TrainMonitor:
         return self._apply(lambda t: t.to(device))
 
     def reset(self):
+        """Zero the totals and the guard word (either loss; after building a graphed step, whose warm-up steps count)."""
         self._totals.zero_()
         self._guard.zero_()
 
@@ -82,7 +88,13 @@ class TrainMonitor:
         ``kl_term_sum`` (kl / num_batches), ``loss_sum``; of the last step, finite or not: ``last_nll``, ``last_loss``.  Derived:
         ``nll_mean`` = nll_sum / nll_rows, ``loss_mean`` = loss_sum / finite steps, ``accuracy`` = correct / rows with a valid
         target -- NaN where the denominator is 0.  ``strict``: targets outside [0, classes) raise IndexError, as ``F.nll_loss``
-        would have; with ``strict=False`` they are reported in ``bad_targets``."""
+        would have; with ``strict=False`` they are reported in ``bad_targets``.
+
+        After ``elbo_bce_loss(monitor=)`` the same keys count ELEMENTS: ``rows`` B * units per step, ``correct`` elements with a
+        valid target and (p > 0.5) == (y > 0.5), ``bad_targets`` targets outside [0, 1] or NaN (the IndexError of ``strict`` names
+        ``[0, classes)``; it means these), ``nonfinite_rows`` probabilities that are inf or NaN (such an element costs the loss
+        100, it does not make it non-finite), ``nll_rows`` elements with a valid target of the finite steps; ``nll_mean`` is the
+        mean BCE per element and ``accuracy`` the fraction of elements on the right side of 0.5."""
         import numpy as np
         h = np.ascontiguousarray(self._read(), dtype=np.int64)
         n = _lib.MONITOR_COUNTS
@@ -204,16 +216,23 @@ HANDOVER = {"taken": 0, "sigmoid_backward": 0}
 
 class _ElboBceLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, probs, target, kl, scale, stats, from_head):
+    def forward(ctx, probs, target, kl, scale, stats, from_head, monitor=None):
         B, O = probs.shape
         _BCE_LOGITS_GRAD.clear()                   # entries live for one backward pass only
         p = probs if (probs.stride(1) == 1 or O == 1) else probs.contiguous()
         loss = torch.empty((), dtype=torch.float32, device=p.device)
         stream = torch.cuda.current_stream(p.device).cuda_stream
-        _lib.check(_lib.lib().lbbnn_elbo_bce_loss(p.data_ptr(), p.stride(0) if B > 1 else O, target.data_ptr(), O, B, O,
-                                                  kl.data_ptr() if kl is not None else None, float(scale), loss.data_ptr(),
-                                                  stats.data_ptr() if stats is not None else None, 1, stream),
-                   "lbbnn_elbo_bce_loss")
+        if monitor is not None:
+            _lib.check(_lib.lib().lbbnn_elbo_bce_loss_monitor(p.data_ptr(), p.stride(0) if B > 1 else O, target.data_ptr(), O, B, O,
+                                                              kl.data_ptr() if kl is not None else None, float(scale),
+                                                              loss.data_ptr(), stats.data_ptr() if stats is not None else None, 1,
+                                                              monitor._totals.data_ptr(), monitor._guard.data_ptr(), stream),
+                       "lbbnn_elbo_bce_loss_monitor")
+        else:
+            _lib.check(_lib.lib().lbbnn_elbo_bce_loss(p.data_ptr(), p.stride(0) if B > 1 else O, target.data_ptr(), O, B, O,
+                                                      kl.data_ptr() if kl is not None else None, float(scale), loss.data_ptr(),
+                                                      stats.data_ptr() if stats is not None else None, 1, stream),
+                       "lbbnn_elbo_bce_loss")
         ctx.save_for_backward(target, p)
         ctx.meta = (B, O, float(scale), kl is not None, bool(from_head) and p is probs)
         return loss
@@ -235,7 +254,7 @@ class _ElboBceLossFn(torch.autograd.Function):
         if from_head:
             # the entry HOLDS p and g_probs, as _LOGITS_GRAD does: "same address" in the head's backward means "same tensor"
             _BCE_LOGITS_GRAD[p.data_ptr()] = (g_probs.data_ptr(), g_logits, p, g_probs)
-        return g_probs, None, g_kl, None, None, None
+        return g_probs, None, g_kl, None, None, None, None
 
 
 def _bce_target(probs, target):
@@ -256,7 +275,26 @@ def _bce_target(probs, target):
     return target.view(probs.shape)
 
 
-def elbo_bce_loss(probs, target, kl=None, num_batches=1.0, *, stats=None):
+def _check_monitored_bce(probs, kl, monitor):
+    """``_check_monitored`` for the BCE loss: ValueError naming what keeps this call off the fused, monitored launch."""
+    who = "bnn_amd: elbo_bce_loss(monitor=...): "
+    if not isinstance(monitor, TrainMonitor):
+        raise ValueError(who + "monitor must be a bnn_amd.TrainMonitor, got %s" % type(monitor).__name__)
+    if probs.dtype != torch.float32 or probs.dim() != 2:
+        raise ValueError(who + "probs must be float32 (B, units), got %s %s" % (probs.dtype, tuple(probs.shape)))
+    if probs.shape[1] != monitor.classes:
+        raise ValueError(who + "probs has %d units, the monitor was built for %d" % (probs.shape[1], monitor.classes))
+    if probs.shape[0] < 1:
+        raise ValueError(who + "an empty batch has no step to record")
+    if not _fused_kl(kl):
+        raise ValueError(who + "kl must be None or a one-element float32 HIP tensor")
+    if not probs.is_cuda:
+        raise ValueError(who + "the monitor lives in the fused HIP loss; probs is on %s" % probs.device)
+    if probs.device != monitor.device:
+        raise ValueError(who + "probs is on %s, the monitor on %s" % (probs.device, monitor.device))
+
+
+def elbo_bce_loss(probs, target, kl=None, num_batches=1.0, *, stats=None, monitor=None):
     """nn.BCELoss(reduction='sum')(probs, target) + kl / num_batches -- the sim-study scripts' loss for a sigmoid head.
 
     ``probs`` (B, O) probabilities, ``target`` float32 of the same shape (or (B,) against (B, 1)), contiguous, on the device of
@@ -267,8 +305,16 @@ def elbo_bce_loss(probs, target, kl=None, num_batches=1.0, *, stats=None):
 
     ``stats``: an int32[4] device tensor that every call ADDS to -- correct ((p > 0.5) == (y > 0.5)), elements, bad_targets (y
     outside [0, 1] or not finite: no loss, no gradient), nonfinite_probs.  Nothing here reads it: reading it (``stats.tolist()``)
-    is the caller's synchronisation, once per epoch in a training loop; zero it with ``stats.zero_()``."""
+    is the caller's synchronisation, once per epoch in a training loop; zero it with ``stats.zero_()``.
+
+    ``monitor``: a ``TrainMonitor(units, device)`` whose totals and guard word this step is recorded in, by the forward launch
+    itself (lbbnn_elbo_bce_loss_monitor); the loss, ``stats`` and every gradient are bitwise those of the call without one.  The
+    monitor counts ELEMENTS (b, o), see ``TrainMonitor.result``.  It needs the fused path -- float32 (B, monitor.classes)
+    probabilities on the monitor's HIP device, a non-empty batch, ``kl`` None or a one-element float32 HIP tensor -- and anything
+    else is a ValueError naming the mismatch."""
     t = _bce_target(probs, target)
+    if monitor is not None:
+        _check_monitored_bce(probs, kl, monitor)
     if stats is not None and not (torch.is_tensor(stats) and stats.dtype == torch.int32 and stats.numel() == 4
                                   and stats.is_contiguous() and stats.device == probs.device):
         raise ValueError("bnn_amd: elbo_bce_loss: stats must be a contiguous int32[4] tensor on %s" % probs.device)
@@ -278,7 +324,8 @@ def elbo_bce_loss(probs, target, kl=None, num_batches=1.0, *, stats=None):
             and (kl is None or (torch.is_tensor(kl) and kl.is_cuda and kl.dtype == torch.float32 and kl.numel() == 1))):
         from . import layers
         from_head = isinstance(probs.grad_fn, layers._SigmoidHeadFn._backward_cls)
-        return _ElboBceLossFn.apply(probs, t, kl if kl is None else kl.reshape(()), 1.0 / float(num_batches), stats, from_head)
+        return _ElboBceLossFn.apply(probs, t, kl if kl is None else kl.reshape(()), 1.0 / float(num_batches), stats, from_head,
+                                    monitor)
     ok = (t >= 0) & (t <= 1)
     bce = F.binary_cross_entropy(torch.where(ok, probs, torch.ones_like(probs)), torch.where(ok, t, torch.ones_like(t)),
                                  reduction="sum")

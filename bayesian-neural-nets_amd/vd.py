@@ -164,18 +164,35 @@ class BNN(nn.Module):
 NUM_BATCHES = 600.0      # len(train_loader.dataset) / config['batch_size'] = 60000 / 100 (variational_dropout.py:90-95)
 
 
-def loss_fn(prediction, target, model, *, num_batches=None):
-    """variational_dropout.py:89-106, callable with the reference's three positional arguments.  There ``num_batches``
-    = N / batch_size is computed from the module-level loaders; here it is a keyword (default: the module constant
-    NUM_BATCHES = 600, the reference's MNIST value).  As in the reference, ``if model.train():`` (:91) is a CALL: it
-    flips the model to training mode and is always truthy, so N is always the training set's size."""
-    if num_batches is None:
-        num_batches = NUM_BATCHES
-    model.train()                                                    # :91 (side effect kept)
+def kl(model):
+    """The ``KL`` total of ``loss_fn`` (variational_dropout.py:97-102) -- the sum over the model's ``BayesianLayer`` children
+    of (0.5 log alpha + c1 alpha + c2 alpha^2 + c3 alpha^3).sum(), added in the order of ``model.children()`` -- as a 0-d
+    float32 tensor on the model's device: the ``kl`` argument of ``bnn_amd.elbo_loss`` for a VD network."""
     KL = 0
     c1, c2, c3 = 1.16145124, -1.50204118, 0.58629921
     for layer in model.children():
         if isinstance(layer, BayesianLayer):
             a = layer.alpha
             KL = KL + (0.5 * torch.log(a) + c1 * a + c2 * a ** 2 + c3 * a ** 3).sum()
-    return KL / num_batches + F.nll_loss(prediction, target, reduction="sum")
+    if not torch.is_tensor(KL):                                      # no BayesianLayer child
+        dev = next(itertools.chain(model.parameters(), model.buffers(), [torch.zeros(())])).device
+        KL = torch.zeros((), dtype=torch.float32, device=dev)
+    return KL.float()
+
+
+def loss_fn(prediction, target, model, *, num_batches=None, monitor=None):
+    """variational_dropout.py:89-106, callable with the reference's three positional arguments.  There ``num_batches``
+    = N / batch_size is computed from the module-level loaders; here it is a keyword (default: the module constant
+    NUM_BATCHES = 600, the reference's MNIST value).  As in the reference, ``if model.train():`` (:91) is a CALL: it
+    flips the model to training mode and is always truthy, so N is always the training set's size.
+    ``monitor``: a ``bnn_amd.TrainMonitor``; the loss is then ``bnn_amd.elbo_loss(prediction, target, kl(model), num_batches,
+    monitor=monitor)``, one fused launch that records the step and leaves the guard word (it rounds once, from fp64: equal to
+    the expression below to fp32 rounding, not bit for bit).  Without one the expression is the reference's, as before (its
+    ``KL`` is ``kl(model)``)."""
+    if num_batches is None:
+        num_batches = NUM_BATCHES
+    model.train()                                                    # :91 (side effect kept)
+    if monitor is not None:
+        from .losses import elbo_loss
+        return elbo_loss(prediction, target, kl(model), num_batches, monitor=monitor)
+    return kl(model) / num_batches + F.nll_loss(prediction, target, reduction="sum")

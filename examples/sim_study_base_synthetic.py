@@ -4,12 +4,14 @@ with explicit latent binary gates, a sigmoid on its output, BCELoss(sum) + (log_
 eleven single-tensor groups at two rates, and the posterior inclusion probabilities alpha = sigmoid(lambdal) as the result.
 
     net = base.BayesianNetwork((20, 1), head="sigmoid", weight_mu_init=(-0.01, 0.01), lambdal_init=(-0.5, 0.5))
-    loss, log_prior, log_q, nll, out = net.sample_elbo(x, y, num_batches=NUM_BATCHES, draws="hip", stats=stats)
+    monitor = bnn_amd.TrainMonitor(1, DEVICE); optimizer.set_guard(monitor)
+    loss, log_prior, log_q, nll, out = net.sample_elbo(x, y, num_batches=NUM_BATCHES, draws="hip", monitor=monitor)
 
 The data are made here: 2000 rows of 20 standard-normal covariates, a sparse weight vector of this script's own, y ~
-Bernoulli(sigmoid(x . w)).  The whole step -- in-kernel draws, forward, head, fused loss with its counts, backward, the one-launch
-SGD -- is captured in a HIP graph.  At the switch epoch (the script's epoch 50) the three priors go ``exact`` and the six prior
-groups' rates go to 0; the training accuracy of an epoch comes from the device-side counts, read once per epoch.
+Bernoulli(sigmoid(x . w)).  The whole step -- in-kernel draws, forward, head, the whole ELBO as one fused loss launch with the
+training monitor, backward, the one-launch SGD behind the monitor's guard -- is captured in a HIP graph.  At the switch epoch (the script's epoch 50) the three priors go ``exact`` and the six prior
+groups' rates go to 0; the epoch's mean loss, mean nll and training accuracy come from the monitor's device-side totals, read once per epoch, and
+a step whose loss is not finite (the prior parameters are trainable and unchecked: base.VALIDATE_ARGS) changes no parameter.
 
     python examples/sim_study_base_synthetic.py
     EPOCHS=500 SWITCH=50 python examples/sim_study_base_synthetic.py
@@ -45,11 +47,12 @@ RATES = [("bias_mu", 1e-4), ("bias_rho", 1e-4), ("weight_mu", 1e-4), ("weight_rh
          ("weight_a", 1e-3), ("weight_b", 1e-3), ("bias_a", 1e-3), ("bias_b", 1e-3), ("lambdal", 1e-3)]
 PRIOR_GROUPS = range(4, 10)                                          # pa, pb, weight_a, weight_b, bias_a, bias_b
 optimizer = bnn_amd.optim.SGD([{"params": getattr(l1, n), "lr": r} for n, r in RATES], lr=0.01)
-stats = torch.zeros(4, dtype=torch.int32, device=DEVICE)             # correct, elements, bad targets, non-finite probabilities
+monitor = bnn_amd.TrainMonitor(1, DEVICE)                            # one output unit; the totals count elements (b, o)
+optimizer.set_guard(monitor)
 
 
 def elbo(net, data, target):
-    return net.sample_elbo(data, target, num_batches=NUM_BATCHES, draws="hip", stats=stats)[0]
+    return net.sample_elbo(data, target, num_batches=NUM_BATCHES, draws="hip", monitor=monitor)[0]
 
 
 def capture():
@@ -70,14 +73,15 @@ for epoch in range(EPOCHS):
         bnn_amd.graphs.release_module_graph_refs(net)
         del step
         step = capture()
-    stats.zero_()
+    monitor.reset()                                                  # (also drops the warm-up steps of a capture)
     for b in range(NUM_BATCHES):
         rows = slice(b * BATCH_SIZE, (b + 1) * BATCH_SIZE)
         loss = step(x_all[rows], y_all[rows])
     if epoch % 25 == 24 or epoch == EPOCHS - 1:
-        correct, elements, bad, nonfinite = stats.tolist()           # the epoch's one host read
-        print("epoch %3d  loss %9.2f  training accuracy %.3f (%d rows)" % (epoch + 1, float(loss.detach()), correct / elements, elements))
-        assert bad == 0 and nonfinite == 0
+        m = monitor.result()                                         # the epoch's one host read
+        print("epoch %3d  loss_mean %9.2f  nll_mean %.4f  accuracy %.3f (%d rows)  nonfinite_steps %d  skipped_steps %d"
+              % (epoch + 1, m["loss_mean"], m["nll_mean"], m["accuracy"], m["rows"], m["nonfinite_steps"], m["skipped_steps"]))
+        assert m["nonfinite_rows"] == 0
 if EPOCHS > SWITCH:
     assert all(torch.equal(optimizer.param_groups[i]["params"][0].detach(), f) for i, f in zip(PRIOR_GROUPS, frozen))
     print("the six prior parameters are bitwise what they were at the switch (rate 0 through the device table)")

@@ -4,12 +4,13 @@ latent-binary papers: ONE Bayesian layer 20 -> 1, a sigmoid on its output, BCELo
 inclusion probabilities alpha = sigmoid(lambdal) as the result.
 
     net = lrt.BayesianNetwork((20, 1), head="sigmoid", priors=..., lambdal_init=(1.5, 2.5))
-    loss = bnn_amd.elbo_bce_loss(net(x, sample=True), y, net.kl(), NUM_BATCHES, stats=stats)
+    monitor = bnn_amd.TrainMonitor(1, DEVICE); optimizer.set_guard(monitor)
+    loss = bnn_amd.elbo_bce_loss(net(x, sample=True), y, net.kl(), NUM_BATCHES, monitor=monitor)
 
 The data are synthetic and made here: 2000 rows of 20 standard-normal covariates, a sparse weight vector of this script's own
-(five non-zero entries), y ~ Bernoulli(sigmoid(x . w)).  The whole step -- forward, head, fused loss with its counts, backward,
-Adam -- is captured once in a HIP graph; the training accuracy of an epoch comes from the device-side counts, read once per
-epoch.  Run on an LRT network and on an MNF network with this package's planar flows.
+(five non-zero entries), y ~ Bernoulli(sigmoid(x . w)).  The whole step -- forward, head, fused loss with the training monitor, backward,
+Adam behind the monitor's guard -- is captured once in a HIP graph; the epoch's mean loss, mean nll and training accuracy come
+from the monitor's device-side totals, read once per epoch, and a step whose loss is not finite changes no parameter and is counted.  Run on an LRT network and on an MNF network with this package's planar flows.
 
     python examples/sim_study_synthetic.py
     EPOCHS=600 python examples/sim_study_synthetic.py
@@ -42,21 +43,24 @@ support = w_true != 0
 def run(name, net):
     net = net.to(DEVICE).train()
     optimizer = bnn_amd.optim.Adam(net.parameters(), lr=0.01)
-    stats = torch.zeros(4, dtype=torch.int32, device=DEVICE)         # correct, elements, bad targets, non-finite probabilities
+    monitor = bnn_amd.TrainMonitor(1, DEVICE)                        # one output unit; the totals count elements (b, o)
+    optimizer.set_guard(monitor)
 
     def elbo(net, data, target):
-        return bnn_amd.elbo_bce_loss(net(data, sample=True), target, net.kl(), NUM_BATCHES, stats=stats)
+        return bnn_amd.elbo_bce_loss(net(data, sample=True), target, net.kl(), NUM_BATCHES, monitor=monitor)
 
     step = bnn_amd.graphs.make_graphed_train_step(net, optimizer, elbo, x_all[:BATCH_SIZE], y_all[:BATCH_SIZE])
     for epoch in range(EPOCHS):
-        stats.zero_()
+        monitor.reset()                                              # (also drops the warm-up steps of the step's factory)
         for b in range(NUM_BATCHES):
             rows = slice(b * BATCH_SIZE, (b + 1) * BATCH_SIZE)
             loss = step(x_all[rows], y_all[rows])
         if epoch % 50 == 49 or epoch == EPOCHS - 1:
-            correct, elements, bad, nonfinite = stats.tolist()           # the epoch's one host read
-            print("%s epoch %3d  loss %8.2f  training accuracy %.3f (%d rows)" % (name, epoch + 1, float(loss.detach()), correct / elements, elements))
-            assert bad == 0 and nonfinite == 0
+            m = monitor.result()                                         # the epoch's one host read
+            print("%s epoch %3d  loss_mean %8.2f  nll_mean %.4f  accuracy %.3f (%d rows)  nonfinite_steps %d  skipped_steps %d"
+                  % (name, epoch + 1, m["loss_mean"], m["nll_mean"], m["accuracy"], m["rows"], m["nonfinite_steps"],
+                     m["skipped_steps"]))
+            assert m["nonfinite_rows"] == 0
     alpha = net.inclusion_probabilities()[0].reshape(-1).cpu()
     chosen = alpha > 0.5
     print("%s inclusion probabilities: %s" % (name, " ".join("%.2f" % a for a in alpha.tolist())))

@@ -2,7 +2,9 @@
 """The reference's baseline-LBBNN training loop (LBBNN-GP-MF.py:327-338: net.zero_grad(), net.sample_elbo(data, target),
 loss.backward(), the COND_OPT mask weight_mu.grad * gammas, optimizer.step()) with its 33-group Adam (:520-554) as
 bnn_amd.optim.Adam, on MNIST-shaped synthetic data (there is no dataset in this image).  The step draws its gates and Gamma
-precisions inside the HIP kernels (sample_elbo(draws="hip")), so it is captured once in a HIP graph and replayed.
+precisions inside the HIP kernels (sample_elbo(draws="hip")), so it is captured once in a HIP graph and replayed.  The ELBO is
+one fused loss launch that also keeps the epoch's totals on the device (monitor=), and Adam runs behind the monitor's guard: a
+step whose loss is not finite changes no parameter and is counted.
 
     python examples/train_base_synthetic.py               # graphed hip-draw step
     EAGER=1 python examples/train_base_synthetic.py       # the same step, eager
@@ -57,8 +59,13 @@ train_x = torch.rand(NUM_BATCHES, BATCH_SIZE, 1, 28, 28, device=DEVICE, generato
 train_y = (train_x.view(NUM_BATCHES, BATCH_SIZE, 784) @ proj).argmax(-1)
 
 
+# the reference's train() reads loss, log_prior, log_q and nll back (:339-342); here one read per epoch
+monitor = bnn_amd.TrainMonitor(10, DEVICE)
+optimizer.set_guard(monitor)
+
+
 def elbo(net, data, target):
-    return net.sample_elbo(data, target, draws="hip")[0]
+    return net.sample_elbo(data, target, draws="hip", monitor=monitor)[0]
 
 
 net.train()
@@ -73,12 +80,16 @@ else:
     step = bnn_amd.graphs.make_graphed_train_step(net, optimizer, elbo, train_x[0], train_y[0])
 
 for epoch in range(EPOCHS):
+    monitor.reset()                                    # (also drops the warm-up steps of the graphed step's factory)
     torch.cuda.synchronize(); t0 = time.perf_counter()
     for b in range(NUM_BATCHES):
         loss = step(train_x[b], train_y[b])
     torch.cuda.synchronize()
-    print("epoch %d  loss %.1f  (%.3f ms/iteration)%s" % (epoch, float(loss.detach()), (time.perf_counter() - t0) / NUM_BATCHES * 1e3,
-                                                          "  lambdal rate %.4g" % optimizer.param_groups[-1]["lr"] if DECAY else ""))
+    dt = (time.perf_counter() - t0) / NUM_BATCHES * 1e3
+    m = monitor.result()                               # the epoch's one host read
+    print("epoch %d  loss_mean %.1f  nll_mean %.4f  accuracy %.3f  nonfinite_steps %d  skipped_steps %d  (%.3f ms/iteration)%s"
+          % (epoch, m["loss_mean"], m["nll_mean"], m["accuracy"], m["nonfinite_steps"], m["skipped_steps"], dt,
+             "  lambdal rate %.4g" % optimizer.param_groups[-1]["lr"] if DECAY else ""))
     if scheduler is not None:
         scheduler.step()
 with torch.no_grad():

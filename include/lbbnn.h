@@ -1379,7 +1379,8 @@ int lbbnn_log_softmax_backward(const float* g, int ldg, const float* logp, int l
  *   dimension is the caller's: (S, B, O) dense is B' = S * B, padded members are one call each.
  * lbbnn_elbo_bce_loss: one workgroup, fp64 partial sums:
  *   *loss = sum_{b,o} ( (y - 1) max(log1pf(-p), -100) - y max(logf(p), -100) ) + (kl ? *kl * kl_scale : 0)
- *   -- -(y log p + (1 - y) log(1 - p)) in the spelling of torch's binary_cross_entropy, whose fp32 terms these are bit for bit.
+ *   -- -(y log p + (1 - y) log(1 - p)) in the spelling of torch's binary_cross_entropy (its fp32 terms up to the last bit of
+ *   logf, which is not torch.log's on every input; log1pf agrees with torch.log1p).
  *   target: fp32 in [0, 1], the shape of probs.  stats (int32[4], nullable; accumulate != 0 adds to what it holds):
  *     [0] correct          elements with a valid target and (p > 0.5f) == (y > 0.5f): round(p) == y for 0 / 1 targets
  *     [1] elements         B * O
@@ -1395,6 +1396,33 @@ int lbbnn_elbo_bce_loss(const float* probs, int ldp, const float* target, int ld
 int lbbnn_elbo_bce_loss_backward(const float* g, const float* probs, int ldp, const float* target, int ldt, int B, int O,
                                  float kl_scale, float* g_probs, float* g_logits, float* g_kl, void* stream);
 int lbbnn_sigmoid_backward(const float* g, int ldg, const float* probs, int ldp, float* out, int ldo, int B, int O, void* stream);
+/* lbbnn_elbo_bce_loss_monitor -- lbbnn_elbo_bce_loss with the running totals of a training log and a per-step "loss is not
+ * finite" flag, in the SAME single launch of one workgroup: what lbbnn_elbo_loss_monitor is to lbbnn_elbo_loss.  *loss and
+ * stats are bitwise what lbbnn_elbo_bce_loss writes for the same arguments (one shared pass: the same terms, added in the same
+ * order).  The backward launch is lbbnn_elbo_bce_loss_backward, unchanged.
+ * totals / guard: the LBBNN_MONITOR_WORDS int64 words and the int32 word of lbbnn_elbo_loss_monitor, the same layout.  A "row"
+ * of this loss is ONE ELEMENT (b, o) of the (B, O) block -- one Bernoulli observation -- so with n = B * O every call adds:
+ *   LBBNN_MONITOR_STEPS            1
+ *   LBBNN_MONITOR_ROWS             n
+ *   LBBNN_MONITOR_CORRECT          elements with a valid target and (p > 0.5f) == (y > 0.5f)              (stats[0])
+ *   LBBNN_MONITOR_BAD_TARGETS      elements whose target is outside [0, 1] or NaN: no loss term, no gradient (stats[2])
+ *   LBBNN_MONITOR_NONFINITE_ROWS   elements whose p is inf or NaN                                           (stats[3])
+ *   LBBNN_MONITOR_NONFINITE_STEPS  1 when *loss is inf or NaN
+ *   LBBNN_MONITOR_SKIPPED_STEPS    not written here: the guarded optimizer steps' slot
+ *   LBBNN_MONITOR_NLL_ROWS         n - bad_targets, when *loss is finite
+ * Sums, with nll = the fp64 sum of the fp32 BCE terms and kl_term = kl ? *kl * kl_scale : 0 in fp64:
+ *   LBBNN_MONITOR_NLL_SUM, LBBNN_MONITOR_KL_TERM_SUM, LBBNN_MONITOR_LOSS_SUM   += nll, kl_term, nll + kl_term -- ONLY on a call
+ *                                  whose *loss is finite
+ *   LBBNN_MONITOR_LAST_NLL, LBBNN_MONITOR_LAST_LOSS   overwritten by every call: nll, and (double)*loss
+ * A NaN probability against a valid target is NOT a non-finite loss: max(logf(NaN), -100) is -100 (fmaxf returns its number),
+ * so the element costs 100 and is counted in LBBNN_MONITOR_NONFINITE_ROWS; the flag follows *loss alone.
+ * guard (nullable): OVERWRITTEN by every call: 1 when *loss is not finite, else 0.  No atomics: thread 0 reads every total
+ * ahead of its first store; one monitor may have one such launch in flight at a time (launches of one stream are).
+ * Checks (before any HIP call): probs / target / loss / totals NULL: LBBNN_E_NULL; O outside 1..16, B < 1, B * O >= 2^31,
+ * ldp < O, ldt < O: LBBNN_E_SHAPE; a pointer off 4 bytes, totals off 8: LBBNN_E_ALIGN.  kl, stats and guard are nullable. */
+int lbbnn_elbo_bce_loss_monitor(const float* probs, int ldp, const float* target, int ldt, int B, int O, const float* kl,
+                                float kl_scale, float* loss, int* stats, int accumulate, int64_t* totals, int32_t* guard,
+                                void* stream);
 
 /* lbbnn_layers_operands_snap + lbbnn_format_x of the network input in the SAME launches: the planar flows of a network are two
  * latency-bound workgroups per layer, and the format job (one pass over x) runs as extra workgroups of that launch on the CUs
