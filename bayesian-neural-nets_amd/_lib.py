@@ -307,6 +307,21 @@ class EvalUncertaintyArgs(ctypes.Structure):
                 ("S", c_i), ("B", c_i), ("C", c_i), ("conf_bins", c_i), ("hist_bins", c_i), ("ent_scale", ctypes.c_float)]
 
 
+REG_COUNTS = 5                         # LBBNN_REG_COUNTS, in the header's order:
+REG_COUNT_NAMES = ("elements", "elements_with_target", "bad_targets", "nonfinite_elements", "scored_elements")
+REG_SUMS = 8                           # LBBNN_REG_SUMS, in the header's order:
+REG_SUM_NAMES = ("sq_err", "abs_err", "log_density", "epistemic_var", "total_var", "y", "y2", "posterior_mean_sq_err")
+REG_ROW_KEYS = ("pred_mean", "epistemic_var", "aleatoric_var", "total_std", "sq_err", "log_density", "pit")
+
+
+class EvalRegressionArgs(ctypes.Structure):
+    """lbbnn_eval_regression_args_t"""
+    _fields_ = [("out", c_p), ("m_stride", c_i64), ("ldp", c_i64), ("mean_out", c_p), ("ldm", c_i64), ("target", c_p),
+                ("ldt", c_i64), ("log_var", c_p)] + [(n, c_p) for n in REG_ROW_KEYS] + \
+               [("counts", c_p), ("sums", c_p), ("pit_hist", c_p), ("work", c_p), ("S", c_i), ("B", c_i), ("O", c_i),
+                ("pit_bins", c_i)]
+
+
 # name -> (restype, argtypes); must list every symbol include/lbbnn.h declares
 SIGNATURES = {
     "lbbnn_abi_version": (c_i, []),
@@ -432,6 +447,13 @@ SIGNATURES = {
     "lbbnn_eval_metrics": (c_i, [ctypes.POINTER(EvalMetricsArgs), c_p]),
     "lbbnn_eval_uncertainty_work_bytes": (c_i64, [c_i, c_i, c_i, c_i]),
     "lbbnn_eval_uncertainty": (c_i, [ctypes.POINTER(EvalUncertaintyArgs), c_p]),
+    "lbbnn_eval_regression_work_bytes": (c_i64, [c_i, c_i, c_i]),
+    "lbbnn_eval_regression": (c_i, [ctypes.POINTER(EvalRegressionArgs), c_p]),
+    "lbbnn_elbo_gaussian_loss": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_p, ctypes.c_float, c_p, c_p, c_p, c_p]),
+    "lbbnn_elbo_gaussian_loss_monitor": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_p, ctypes.c_float, c_p, c_p, c_p, c_p, c_p,
+                                               c_p]),
+    "lbbnn_elbo_gaussian_loss_backward": (c_i, [c_p, c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, ctypes.c_float, c_p, c_p, c_p, c_p,
+                                                c_p]),
 }
 
 _lib = None

@@ -30,6 +30,10 @@ Baseline networks have a frozen model of their own, ``freeze_base(net, gates="sa
 ``FrozenBaseNetwork``: sigma, alpha and the gated means taken once (lbbnn_base_frozen_operands), every member then drawn from
 that snapshot (lbbnn_base_frozen_members) at the streams, offsets and counters of ``base_ensemble`` -- a full model's members are
 ``base_ensemble``'s bit for bit, a compact model's weights the full model's at the rows and columns that stay.
+
+An LRT / MNF network with ``head="identity"`` (regression) returns raw outputs from every ensemble form above and from its frozen
+models; ``ensemble_regression`` / ``RegressionAccumulator`` (lbbnn_eval_regression) are its metrics -- predictive mean, epistemic
+and aleatoric variance, mixture log density, PIT -- and the classification tools refuse such a model.
 """
 import math
 from typing import Dict, List, Optional
@@ -48,6 +52,9 @@ def _check_log_probs(net, log_probs: bool):
     """``log_probs=True`` is the 2-class form of a sigmoid head with ONE output unit."""
     if not log_probs:
         return
+    if _head_of(net) == "identity":
+        raise ValueError("bnn_amd: log_probs=True applies to a head=\"sigmoid\" network; an identity head returns raw outputs "
+                         "(regression) and has no log-probabilities")
     if _head_of(net) != "sigmoid":
         raise ValueError("bnn_amd: log_probs=True applies to a head=\"sigmoid\" network (a log_softmax head returns "
                          "log-probabilities already)")
@@ -75,6 +82,8 @@ def _members_result(buf: torch.Tensor, S: int, B: int, C: int, head: str, log_pr
     if head == "sigmoid":
         return _binary_members(buf, S, B, C, log_probs)
     outputs = buf[:, :B * C].view(S, B, C)
+    if head == "identity":
+        return outputs                                      # the raw outputs: the sigmoid head minus its launch
     return outputs if C <= 16 else torch.log_softmax(outputs, dim=-1)
 
 
@@ -303,7 +312,9 @@ def ensemble_forward(net, data: torch.Tensor, samples: int = 10, batched=None, *
     HIP device when no layer has injected noise, else the loop of ``net(data)``; True with injected noise raises ValueError.
     A network with ``head="sigmoid"`` (LRT / MNF, its frozen model, or a baseline network): (samples, B, units) PROBABILITIES, same draws and Philox
     offsets (the head consumes no randomness); ``log_probs=True`` (one unit) returns the (samples, B, 2) log-probabilities
-    [logsigmoid(-logit), logsigmoid(logit)] instead, made from the logits by the same launch."""
+    [logsigmoid(-logit), logsigmoid(logit)] instead, made from the logits by the same launch.
+    A network with ``head="identity"`` (LRT / MNF or its frozen model): (samples, B, units) RAW outputs, the same draws and
+    offsets, no head launch; ``log_probs=True`` is a ValueError."""
     net.eval()
     if log_probs and (_is_vd(net) or (_is_base(net) and _head_of(net) != "sigmoid")):
         raise ValueError("bnn_amd: log_probs=True applies to a network with head=\"sigmoid\" or its frozen model")
@@ -385,9 +396,15 @@ def ensemble_eval(net, data: torch.Tensor, target: Optional[torch.Tensor] = None
     return res
 
 
+_NOT_CLASSIFICATION = ("bnn_amd: this model has head=\"identity\" (regression): ensemble_eval, predictive_entropy, EvalAccumulator "
+                       "and UncertaintyAccumulator are classification tools; use evaluate.RegressionAccumulator")
+
+
 def _binary_eval(net) -> bool:
     """A sigmoid head is evaluated as two classes: its one unit's (.., 2) log-probabilities go to the metrics of a ``classes =
     2`` problem.  More than one unit (multi-label) has no class axis: ValueError."""
+    if _head_of(net) == "identity":
+        raise ValueError(_NOT_CLASSIFICATION)
     if _head_of(net) != "sigmoid":
         return False
     if net.dims[-1] != 1:
@@ -470,6 +487,8 @@ def predictive_entropy(outputs: torch.Tensor) -> torch.Tensor:
     """Per-row entropy of the ensemble's predictive distribution as ``outofsample`` computes it (LBBNN-GP-MF.py:476-496,
     LBBNN-GP-MF-LRT.py:318-334): per member sigmoid(log-probabilities) normalised over the classes of each row, the mean over
     the members, then -sum p log p per row.  ``outputs``: (samples, B, classes); returns (B,).  Any family."""
+    if not torch.is_tensor(outputs) and _head_of(outputs) == "identity":
+        raise ValueError(_NOT_CLASSIFICATION)
     if outputs.dim() != 3:
         raise ValueError("bnn_amd: outputs must be (samples, B, classes), got %s" % (tuple(outputs.shape),))
     p = torch.sigmoid(outputs.float())
@@ -851,6 +870,221 @@ def ood_auroc(in_result: Dict[str, object], out_result: Dict[str, object], score
     return (int((ho * below).sum()) + 0.5 * ties) / pairs, 0.5 * ties / pairs
 
 
+# ----------------------------------------------------------------------------------------- regression on the device
+def pit_coverage(pit_hist, level: float) -> float:
+    """The share of the PIT values of a pass that fall inside the central interval [(1 - level) / 2, (1 + level) / 2] -- the
+    empirical coverage of the central ``level`` predictive interval, ``level`` itself for a calibrated model -- from a PIT
+    histogram of equal-width bins.  The two edges must be bin edges (with 20 bins: 0.5, 0.8, 0.9 ...): ValueError otherwise.
+    NaN for an empty histogram."""
+    import numpy as np
+    h = np.asarray(pit_hist, dtype=np.int64)
+    K, level = int(h.shape[0]), float(level)
+    if not 0.0 < level <= 1.0:
+        raise ValueError("bnn_amd: coverage level must lie in (0, 1], got %r" % (level,))
+    lo, hi = (1.0 - level) / 2.0 * K, (1.0 + level) / 2.0 * K
+    if abs(lo - round(lo)) > 1e-9 or abs(hi - round(hi)) > 1e-9:
+        raise ValueError("bnn_amd: coverage(%r): the interval [%g, %g] does not end on bin edges of a %d-bin PIT histogram"
+                         % (level, (1.0 - level) / 2.0, (1.0 + level) / 2.0, K))
+    n = int(h.sum())
+    return float(h[int(round(lo)):int(round(hi))].sum()) / n if n else float("nan")
+
+
+def _regression_target(target: torch.Tensor, B: int, O: int, dev) -> torch.Tensor:
+    """``target`` as the dense (B, O) float32 block the regression kernel reads."""
+    if not torch.is_tensor(target) or target.device != dev or \
+            (tuple(target.shape) != (B, O) and not (O == 1 and tuple(target.shape) == (B,))):
+        raise ValueError("bnn_amd: target must be (%d, %d)%s on %s, got %s"
+                         % (B, O, " or (%d,)" % B if O == 1 else "", dev,
+                            "%s on %s" % (tuple(target.shape), target.device) if torch.is_tensor(target) else type(target).__name__))
+    t = target if target.dtype == torch.float32 else target.float()
+    return t.contiguous().view(B, O)
+
+
+def _regression_log_var(log_var, O: int, dev) -> torch.Tensor:
+    """``log_var`` as the (O,) float32 device tensor the kernel reads through its pointer: a live tensor as it is, a number as
+    a tensor filled with it."""
+    if torch.is_tensor(log_var):
+        if log_var.dtype != torch.float32 or tuple(log_var.shape) != (O,) or log_var.device != dev or not log_var.is_contiguous():
+            raise ValueError("bnn_amd: log_var must be a number or a contiguous float32 (%d,) tensor on %s, got %s %s on %s"
+                             % (O, dev, log_var.dtype, tuple(log_var.shape), log_var.device))
+        return log_var.detach()
+    if isinstance(log_var, bool) or not isinstance(log_var, (int, float)):
+        raise ValueError("bnn_amd: log_var must be a number or a float32 (%d,) tensor, got %s" % (O, type(log_var).__name__))
+    return torch.full((O,), float(log_var), dtype=torch.float32, device=dev)
+
+
+@torch.no_grad()
+def ensemble_regression(outputs: torch.Tensor, target: Optional[torch.Tensor] = None, log_var=0.0,
+                        mean_outputs: Optional[torch.Tensor] = None, *,
+                        acc: Optional["RegressionAccumulator"] = None) -> Dict[str, object]:
+    """The per-element numbers of a regression ensemble from one (samples, B, units) block of raw outputs (an identity-head
+    network's ``ensemble_forward`` / ``FrozenNetwork.ensemble``) under a normal likelihood with log-variance ``log_var`` per
+    output unit, in ONE lbbnn_eval_regression call (1 launch; 2 with ``acc``) and without a host synchronisation (arithmetic:
+    include/lbbnn.h), each (B, units):
+
+    * ``pred_mean``: the mean over the members, summed in member order in fp32 and divided by ``samples`` (reproducible bit
+      for bit on the CPU), and ``epistemic_var``: the members' variance about it, in the same fixed arithmetic;
+    * ``aleatoric_var`` = exp(log_var) and ``total_std`` = sqrt(epistemic_var + aleatoric_var);
+    * with ``target`` (B, units) (or (B,) for one unit): ``sq_err`` = (y - pred_mean)^2, ``log_density`` = the log of the
+      members' mixture density at y (a streaming logsumexp: finite whenever one member's density is) and ``pit`` = the mixture's
+      CDF at y; NaN in all three for elements whose target is NaN or infinite, or without a target.
+
+    ``outputs``: as ``ensemble_metrics`` takes it (strided views are read in place); units <= 16.  ``log_var``: a number, or a
+    live float32 (units,) device tensor (the parameter the training loss learned).  ``acc``: a ``RegressionAccumulator`` whose
+    running totals this call adds to (``RegressionAccumulator.update`` is this call with the accumulator's ``log_var``)."""
+    import ctypes
+    from . import _lib
+    o, S, B, O, ms, ldp = _member_block(outputs, "ensemble_regression")
+    if O > 16:
+        raise ValueError("bnn_amd: ensemble_regression takes 1 to 16 output units, got %d" % O)
+    dev = outputs.device
+    lv = acc._log_var if acc is not None else _regression_log_var(log_var, O, dev)
+    a = _lib.EvalRegressionArgs()
+    a.out, a.m_stride, a.ldp, a.S, a.B, a.O, a.log_var = o.data_ptr(), ms, ldp, S, B, O, lv.data_ptr()
+    keep = [o, lv]
+    if mean_outputs is not None:
+        if tuple(mean_outputs.shape) != (B, O) or mean_outputs.device != dev:
+            raise ValueError("bnn_amd: mean_outputs must be (%d, %d) on %s, got %s on %s"
+                             % (B, O, dev, tuple(mean_outputs.shape), mean_outputs.device))
+        mo, ldm = _dense_rows(mean_outputs if mean_outputs.dtype == torch.float32 else mean_outputs.float(), B, O)
+        a.mean_out, a.ldm = mo.data_ptr(), ldm
+        keep.append(mo)
+    if target is not None:
+        t = _regression_target(target, B, O, dev)
+        a.target, a.ldt = t.data_ptr(), O
+        keep.append(t)
+    keys = _lib.REG_ROW_KEYS
+    buf = torch.empty((len(keys), B, O), dtype=torch.float32, device=dev)      # the per-element outputs as one allocation
+    res = {}
+    for i, k in enumerate(keys):
+        res[k] = buf[i]
+        setattr(a, k, buf.data_ptr() + 4 * i * B * O)
+    if acc is not None:
+        acc._fill(a, S, B, O, dev)
+    if B > 0:                                                # (an empty batch has no storage to point at, and nothing to add)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(_lib.lib().lbbnn_eval_regression(ctypes.byref(a), stream), "lbbnn_eval_regression")
+    if acc is not None:
+        acc._note(mean_outputs is not None)
+    del keep
+    return res
+
+
+class RegressionAccumulator:
+    """Running regression totals of an evaluation pass, kept on the device: ``update`` adds a batch (no host read), ``result``
+    reads them -- one buffer, one copy, the ONLY synchronisation of a pass.  The counterpart of ``EvalAccumulator`` /
+    ``UncertaintyAccumulator`` for a network with ``head="identity"``: error sums, the log density of the members' mixture,
+    the epistemic and total predictive variance, and a histogram of the probability integral transform (calibration).
+
+    ``units`` (1 to 16), ``samples`` and ``pit_bins`` (1 to 1024) are fixed for the accumulator's life.  ``log_var``: the
+    log-variance of the normal likelihood per output unit -- a number, or a live float32 (units,) device tensor (e.g. the
+    ``nn.Parameter`` that ``elbo_gaussian_loss`` trained), which the kernel reads through its pointer at every update."""
+
+    def __init__(self, units: int, samples: int, device, log_var, pit_bins: int = 20):
+        from . import _lib
+        O, S, K = int(units), int(samples), int(pit_bins)
+        if not 1 <= O <= 16:
+            raise ValueError("bnn_amd: RegressionAccumulator takes 1 to 16 output units, got %d" % O)
+        if not 1 <= S <= 65535:
+            raise ValueError("bnn_amd: RegressionAccumulator takes 1 to 65535 members, got %d" % S)
+        if not 1 <= K <= 1024:
+            raise ValueError("bnn_amd: RegressionAccumulator takes 1 to 1024 PIT bins, got %d" % K)
+        self.units, self.samples, self.pit_bins, self.device = O, S, K, torch.device(device)
+        # one buffer, one read: counts | sums (bit patterns) | pit_hist
+        self._totals = torch.zeros(_lib.REG_COUNTS + _lib.REG_SUMS + K, dtype=torch.int64, device=self.device)
+        self._log_var = _regression_log_var(log_var, O, self._totals.device)
+        self._work = None
+        self.updates = self.posterior_mean_updates = 0
+
+    def _fill(self, a, S, B, O, dev):
+        """Point the totals of an lbbnn_eval_regression_args_t at this accumulator (work memory grows to the largest batch)."""
+        from . import _lib
+        if (S, O) != (self.samples, self.units):
+            raise ValueError("bnn_amd: this RegressionAccumulator was built for %d members and %d units, the outputs have %d and %d"
+                             % (self.samples, self.units, S, O))
+        if dev != self._totals.device:
+            raise ValueError("bnn_amd: the outputs are on %s, the accumulator on %s" % (dev, self._totals.device))
+        need = int(_lib.lib().lbbnn_eval_regression_work_bytes(S, B, O))
+        if self._work is None or self._work.numel() * 8 < need:
+            self._work = torch.empty(need // 8, dtype=torch.float64, device=dev)
+        base = self._totals.data_ptr()
+        a.counts, a.sums, a.pit_hist = base, base + 8 * _lib.REG_COUNTS, base + 8 * (_lib.REG_COUNTS + _lib.REG_SUMS)
+        a.work, a.pit_bins = self._work.data_ptr(), self.pit_bins
+
+    def _note(self, with_mean: bool):
+        self.updates += 1
+        self.posterior_mean_updates += int(with_mean)
+
+    def update(self, outputs: torch.Tensor, target: Optional[torch.Tensor] = None, mean_outputs: Optional[torch.Tensor] = None):
+        """``ensemble_regression(outputs, target, self's log_var, mean_outputs)`` of one batch, its numbers added to the totals."""
+        return ensemble_regression(outputs, target, None, mean_outputs, acc=self)
+
+    def reset(self):
+        self._totals.zero_()
+        self.updates = self.posterior_mean_updates = 0
+
+    def _read(self):
+        """The totals as a host int64 array (the one device-to-host copy)."""
+        return self._totals.cpu().numpy()
+
+    def result(self, strict: bool = True) -> Dict[str, object]:
+        """Python numbers.  Counts: ``elements``, ``elements_with_target``, ``bad_targets`` (NaN or infinite targets),
+        ``nonfinite_elements`` (a member's output or the log-variance is not finite: in no sum and no bin),
+        ``scored_elements`` (finite, with a valid target: what the error sums are over).  ``<name>_sum`` for sq_err, abs_err,
+        log_density, y, y2, posterior_mean_sq_err (over the scored elements), epistemic_var and total_var (over the finite
+        ones).  Derived: ``rmse``, ``mae``, ``mean_log_density``, ``r2`` = 1 - sq_err_sum / (y2_sum - y_sum^2 / n),
+        ``mean_epistemic_var``, ``mean_total_var``, ``rmse_posterior_mean`` (None when no update carried posterior-mean
+        outputs) -- NaN where a denominator is 0; ``pit_hist`` (pit_bins,) as a numpy array and ``coverage``: a function
+        ``coverage(level)`` = ``pit_coverage(pit_hist, level)``, the share of PIT values in the central ``level`` interval
+        (ValueError when its edges are not bin edges).  ``strict``: as ``EvalAccumulator.result`` -- bad targets raise
+        IndexError; with ``strict=False`` they are reported in ``bad_targets`` and left out of the totals."""
+        import functools
+        import numpy as np
+        from . import _lib
+        h = np.ascontiguousarray(self._read(), dtype=np.int64)
+        nc, ns = _lib.REG_COUNTS, _lib.REG_SUMS
+        res = {k: int(h[i]) for i, k in enumerate(_lib.REG_COUNT_NAMES)}
+        if strict and res["bad_targets"]:
+            raise IndexError("bnn_amd: %d target(s) that are NaN or infinite in this evaluation pass" % res["bad_targets"])
+        res.update(units=self.units, samples=self.samples, pit_bins=self.pit_bins)
+        sums = h[nc:nc + ns].view(np.float64)
+        for i, k in enumerate(_lib.REG_SUM_NAMES):
+            res[k + "_sum"] = float(sums[i])
+        div = lambda x, d: x / d if d else float("nan")
+        n, nf = res["scored_elements"], res["elements"] - res["nonfinite_elements"]
+        root = lambda v: math.sqrt(v) if v >= 0 else float("nan")
+        res["rmse"] = root(div(res["sq_err_sum"], n))
+        res["mae"] = div(res["abs_err_sum"], n)
+        res["mean_log_density"] = div(res["log_density_sum"], n)
+        sst = res["y2_sum"] - div(res["y_sum"] ** 2, n)
+        res["r2"] = 1.0 - div(res["sq_err_sum"], sst) if n else float("nan")
+        res["mean_epistemic_var"] = div(res["epistemic_var_sum"], nf)
+        res["mean_total_var"] = div(res["total_var_sum"], nf)
+        res["rmse_posterior_mean"] = root(div(res["posterior_mean_sq_err_sum"], n)) if self.posterior_mean_updates else None
+        res["pit_hist"] = h[nc + ns:].copy()
+        res["coverage"] = functools.partial(pit_coverage, res["pit_hist"])
+        return res
+
+
+def _regression_pass(net, acc, uncertainty, who: str) -> bool:
+    """Whether ``net`` (head) and ``acc`` make a regression pass; ValueError naming the mismatch when only one of them does."""
+    reg_net, reg_acc = _head_of(net) == "identity", isinstance(acc, RegressionAccumulator)
+    if reg_net and not reg_acc:
+        raise ValueError("bnn_amd: %s: this model has head=\"identity\" (regression): acc must be an "
+                         "evaluate.RegressionAccumulator, got %s (EvalAccumulator and UncertaintyAccumulator are classification "
+                         "tools)" % (who, "None" if acc is None else type(acc).__name__))
+    if reg_acc and not reg_net:
+        raise ValueError("bnn_amd: %s: a RegressionAccumulator takes a model with head=\"identity\", this one has head=%r"
+                         % (who, _head_of(net)))
+    if reg_net and uncertainty is not None:
+        raise ValueError("bnn_amd: %s: uncertainty= is a classification tool (UncertaintyAccumulator); a head=\"identity\" model "
+                         "takes acc=RegressionAccumulator alone" % who)
+    if reg_net and not (_is_frozen(net) or hasattr(net, "_forward_streams")):
+        raise ValueError("bnn_amd: %s: a regression pass takes an LRT / MNF network or its frozen model" % who)
+    return reg_net
+
+
 def _eval_forwards(net, data, samples: int, posterior_mean: bool, gates: str):
     """(outputs, mean_outputs or None) of one batch, by family, as ``ensemble_eval`` dispatches."""
     if _is_frozen(net):
@@ -881,8 +1115,22 @@ def evaluate_batches(net, batches, samples: int = 10, *, acc: Optional[EvalAccum
     ``uncertainty``: an ``UncertaintyAccumulator`` that is updated from the same ``outputs`` in the same pass (one more
     lbbnn_eval_uncertainty call per batch, no host read); its ``result()`` -- one more copy at the end -- is merged into the
     returned dict under its own keys (the three counts both keep, ``rows``, ``rows_with_target`` and ``bad_targets``, are
-    ``acc``'s)."""
+    ``acc``'s).
+    A network with ``head="identity"`` (LRT / MNF, or its frozen model) is a regression pass: ``acc`` is then required and must
+    be a ``RegressionAccumulator`` (its ``update`` takes the raw outputs, the float32 (B, units) targets and the posterior-mean
+    forward), ``uncertainty`` must be None; any other pairing is a ValueError naming the mismatch."""
     S = int(samples)
+    if _regression_pass(net, acc, uncertainty, "evaluate_batches"):
+        # a head="identity" LRT / MNF network or its frozen model: the raw outputs go to acc, a RegressionAccumulator
+        if gates != "sample":
+            raise ValueError("bnn_amd: gates=%r is not an option of a regression pass" % (gates,))
+        for x, y in batches:
+            outputs = net.ensemble(x, S) if _is_frozen(net) else ensemble_forward(net, x, S)
+            mean = None
+            if posterior_mean:
+                mean = net(x, sample=False)
+            acc.update(outputs, y, mean)
+        return acc.result()
     binary = _head_of(net) == "sigmoid"
     for x, y in batches:
         outputs, mean = _eval_forwards(net, x, S, posterior_mean, gates)
@@ -939,8 +1187,8 @@ class _FrozenModel(nn.Module):
 
     def __init__(self, full_dims, gates: str, threshold: float, device, head: str, live=None, needed=None):
         super().__init__()
-        if head not in ("log_softmax", "sigmoid"):
-            raise ValueError("bnn_amd: head must be 'log_softmax' or 'sigmoid', got %r" % (head,))
+        if head not in ("log_softmax", "sigmoid", "identity"):
+            raise ValueError("bnn_amd: head must be 'log_softmax', 'sigmoid' or 'identity', got %r" % (head,))
         self._check_gates(gates)
         threshold = float(threshold)
         self.cut = _cut(threshold)
@@ -957,8 +1205,9 @@ class _FrozenModel(nn.Module):
                 self.register_buffer("live_%d" % b, t.to(device=device, dtype=torch.int32).contiguous())
         else:
             self.dims = self.full_dims
-        if head == "sigmoid" and self.dims[-1] > 16:
-            raise ValueError("bnn_amd: a sigmoid head takes at most 16 output units, got dims[-1] = %d" % self.dims[-1])
+        if head in ("sigmoid", "identity") and self.dims[-1] > 16:
+            raise ValueError("bnn_amd: %s head takes at most 16 output units, got dims[-1] = %d"
+                             % ("a sigmoid" if head == "sigmoid" else "an identity", self.dims[-1]))
         # head: carried over from the network: "sigmoid" -> probabilities (or, log_probs=True, 2 classes)
         self.head, self.gates, self.threshold = head, gates, threshold
         self._src = [None]              # the source network, in a list so that it is not registered as a submodule
@@ -1151,7 +1400,7 @@ class FrozenNetwork(_FrozenModel):
 
     def extra_repr(self) -> str:
         flows = ", flows=%s" % self.flows if self.flows else ""
-        head = ", head=sigmoid" if self.head == "sigmoid" else ""
+        head = ", head=%s" % self.head if self.head != "log_softmax" else ""
         return "dims=%s, family=%s%s, gates=%s, threshold=%g%s" % (self.dims, self.family, flows, self.gates, self.threshold, head)
 
     # ------------------------------------------------------------------------------------- snapshot
@@ -1403,6 +1652,8 @@ class FrozenNetwork(_FrozenModel):
                              log_softmax=last and O <= 16 and self.head == "log_softmax", split=self._split[i], single=False)
         if self.head == "sigmoid":
             return ops.binary_head(h, log_probs=True, want_probs=False) if log_probs else ops.binary_head(h, probs=h)
+        if self.head == "identity":
+            return h
         return h if self.dims[-1] <= 16 else torch.log_softmax(h, dim=1)
 
     @torch.no_grad()
@@ -1750,7 +2001,7 @@ class FrozenBaseNetwork(_FrozenModel):
 
     def extra_repr(self) -> str:
         full = "full_dims=%s, " % (self.full_dims,) if self.compact else ""
-        head = ", head=sigmoid" if self.head == "sigmoid" else ""
+        head = ", head=%s" % self.head if self.head != "log_softmax" else ""
         return "%sdims=%s, family=base, gates=%s, threshold=%g%s" % (full, self.dims, self.gates, self.threshold, head)
 
     # ------------------------------------------------------------------------------------- snapshot

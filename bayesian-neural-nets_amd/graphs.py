@@ -186,7 +186,10 @@ def make_graphed_eval_step(frozen, example_x, example_y, samples: int, acc, warm
     totals with ``acc.result()`` when the pass is over.
     ``uncertainty``: an ``evaluate.UncertaintyAccumulator`` updated from the same ``outputs`` in the same graph, on the same
     stream (lbbnn_eval_uncertainty after lbbnn_eval_metrics); its totals and update count are put back after the warm-up too,
-    and its per-row numbers join the returned dict under their own keys."""
+    and its per-row numbers join the returned dict under their own keys.
+    A frozen model with ``head="identity"`` takes ``acc`` = an ``evaluate.RegressionAccumulator`` (and no ``uncertainty``): the
+    step is the ensemble, the posterior-mean forward and lbbnn_eval_regression in one graph; ``example_y`` is the float32
+    (B, units) target.  Any other pairing of head and accumulator is a ValueError."""
     from . import evaluate, ops
     if not evaluate._is_frozen(frozen):
         raise TypeError("bnn_amd.graphs.make_graphed_eval_step takes a frozen model (evaluate.freeze), got %s"
@@ -199,9 +202,13 @@ def make_graphed_eval_step(frozen, example_x, example_y, samples: int, acc, warm
 
     # a sigmoid head with one unit is evaluated as two classes (its (S, B, 2) log-probabilities; float 0 / 1 targets become class
     # ids inside the graph); more than one unit: ValueError
-    binary = evaluate._binary_eval(frozen)
+    # a head="identity" model (regression): the raw outputs and the posterior-mean forward go to acc, a RegressionAccumulator
+    regression = evaluate._regression_pass(frozen, acc, uncertainty, "graphs.make_graphed_eval_step")
+    binary = False if regression else evaluate._binary_eval(frozen)
 
     def body():
+        if regression:
+            return acc.update(frozen.ensemble(static_x, S), static_y, frozen(static_x, sample=False))
         outputs = frozen.ensemble(static_x, S, log_probs=binary)
         y = evaluate._binary_target(static_y) if binary else static_y
         rows = acc.update(outputs, y, frozen(static_x, sample=False, log_probs=binary))

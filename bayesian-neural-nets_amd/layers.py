@@ -495,7 +495,7 @@ class _SigmoidHeadFn(torch.autograd.Function):
         return ops.sigmoid_backward(g, probs)
 
 
-HEADS = ("log_softmax", "sigmoid")
+HEADS = ("log_softmax", "sigmoid", "identity")
 
 
 class _BayesLinearBase(nn.Module):
@@ -1111,6 +1111,7 @@ class _NetworkBase(nn.Module):
     _lnames = ()
     _logp2_now = False            # set by bnn_amd.evaluate around a forward: a sigmoid head (one unit) returns the 2-class log-probabilities
     head = "log_softmax"          # or "sigmoid": probabilities 1 / (1 + exp(-logit)) per output unit (a binary / multi-label head)
+                                  # or "identity": the last layer's raw output (regression): no launch, no draw of its own
 
     def _build(self, dims, make, head="log_softmax"):
         """l1 .. lN from dims, created layer by layer in order (the seeded initial values depend on it)."""
@@ -1122,6 +1123,8 @@ class _NetworkBase(nn.Module):
             raise ValueError("bnn_amd: head must be one of %s, got %r" % (HEADS, head))
         if head == "sigmoid" and dims[-1] > 16:
             raise ValueError("bnn_amd: a sigmoid head takes at most 16 output units, got dims[-1] = %d" % dims[-1])
+        if head == "identity" and dims[-1] > 16:
+            raise ValueError("bnn_amd: an identity head takes at most 16 output units, got dims[-1] = %d" % dims[-1])
         self.head = head
         self.dims = dims
         self._lnames = tuple("l%d" % (i + 1) for i in range(len(dims) - 1))
@@ -1218,6 +1221,8 @@ class _NetworkBase(nn.Module):
                 if self._logp2_now:
                     return ops.binary_head(x.detach(), log_probs=True, want_probs=False)
                 return _SigmoidHeadFn.apply(x) if x.requires_grad else ops.binary_head(x)
+            if self.head == "identity":
+                return x                                             # the last GEMM's output as it is (regression)
             return x if fused_lsm else F.log_softmax(x, dim=1)       # …LRT.py:210
         return self._forward_streams(x.float(), sample)
 
@@ -1496,6 +1501,8 @@ class _NetworkBase(nn.Module):
             x = ops.binary_head(x, log_probs=True, want_probs=False)  # evaluate.*(log_probs=True): (B, 2) from the logits
         elif self.head == "sigmoid":
             x = ops.binary_head(x, probs=x)                           # in place over the last GEMM's (or the plan's) output buffer
+        elif self.head == "identity":
+            pass                                                      # the last GEMM's (or the plan's) output buffer as it is
         elif layers[-1].out_features > 16:
             x = F.log_softmax(x, dim=1)
         for i, (l, c) in enumerate(zip(layers, cfgs)):

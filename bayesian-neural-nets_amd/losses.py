@@ -9,6 +9,9 @@ is the faster one for callers that want it (``bnn_amd.parallel.DataParallelELBO.
 ``TrainMonitor`` is training's counterpart of ``evaluate.EvalAccumulator``: ``elbo_loss(..., monitor=mon)`` keeps the running
 totals of a training log (loss, nll, accuracy, bad labels, non-finite steps) on the device, in the loss launch itself, and
 leaves a per-step "loss is not finite" word there that ``optim.Adam`` / ``optim.SGD`` honour after ``set_guard(mon)``.
+
+``elbo_bce_loss`` (a ``head="sigmoid"`` network) and ``elbo_gaussian_loss`` (a ``head="identity"`` network: regression with a
+normal likelihood, lbbnn_elbo_gaussian_loss*) are the same step for the other two heads, with the same monitor.
 """
 import torch
 import torch.nn.functional as F
@@ -94,7 +97,12 @@ class TrainMonitor:
         valid target and (p > 0.5) == (y > 0.5), ``bad_targets`` targets outside [0, 1] or NaN (the IndexError of ``strict`` names
         ``[0, classes)``; it means these), ``nonfinite_rows`` probabilities that are inf or NaN (such an element costs the loss
         100, it does not make it non-finite), ``nll_rows`` elements with a valid target of the finite steps; ``nll_mean`` is the
-        mean BCE per element and ``accuracy`` the fraction of elements on the right side of 0.5."""
+        mean BCE per element and ``accuracy`` the fraction of elements on the right side of 0.5.
+
+        After ``elbo_gaussian_loss(monitor=)`` they count ELEMENTS too: ``correct`` elements with a valid target and
+        |y - mean| <= exp(0.5 log_var), so ``accuracy`` reads as the ONE-SIGMA COVERAGE (about 0.683 for a calibrated Gaussian),
+        ``bad_targets`` targets that are NaN or infinite, ``nonfinite_rows`` elements whose mean or log-variance is inf or NaN
+        (such an element does make the loss non-finite), ``nll_mean`` the mean Gaussian negative log-likelihood per element."""
         import numpy as np
         h = np.ascontiguousarray(self._read(), dtype=np.int64)
         n = _lib.MONITOR_COUNTS
@@ -335,6 +343,153 @@ def elbo_bce_loss(probs, target, kl=None, num_batches=1.0, *, stats=None, monito
             stats += torch.stack([c.sum(), torch.tensor(t.numel(), device=t.device), (~ok).sum(),
                                   (~torch.isfinite(probs)).sum()]).to(torch.int32)
     return bce if kl is None else bce + kl / num_batches
+
+
+class _ElboGaussianLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mean, target, log_var, kl, scale, stats, monitor):
+        B, O = mean.shape
+        m = mean if (mean.stride(1) == 1 or O == 1) else mean.contiguous()
+        shared = log_var.dim() == 1
+        lv = log_var if (shared or log_var.stride(1) == 1 or O == 1) else log_var.contiguous()
+        lv = lv if (not shared or lv.is_contiguous()) else lv.contiguous()
+        ldm = m.stride(0) if B > 1 else O
+        ldv = 0 if shared else (lv.stride(0) if B > 1 else O)
+        if ldm < O:
+            m, ldm = m.contiguous(), O                       # (an expanded row: the kernel reads real rows)
+        if not shared and ldv < O:
+            lv, ldv = lv.contiguous(), O
+        loss = torch.empty((), dtype=torch.float32, device=m.device)
+        # d loss / d log_var[o] of a shared noise level, up to the factor g: column sums the forward pass leaves as a by-product
+        cols = torch.empty(O, dtype=torch.float32, device=m.device) if shared else None
+        stream = torch.cuda.current_stream(m.device).cuda_stream
+        head = (m.data_ptr(), ldm, target.data_ptr(), O, lv.data_ptr(), ldv, B, O, kl.data_ptr() if kl is not None else None,
+                float(scale), loss.data_ptr(), stats.data_ptr() if stats is not None else None,
+                cols.data_ptr() if shared else None)
+        if monitor is not None:
+            _lib.check(_lib.lib().lbbnn_elbo_gaussian_loss_monitor(*head, monitor._totals.data_ptr(), monitor._guard.data_ptr(),
+                                                                   stream), "lbbnn_elbo_gaussian_loss_monitor")
+        else:
+            _lib.check(_lib.lib().lbbnn_elbo_gaussian_loss(*head, stream), "lbbnn_elbo_gaussian_loss")
+        ctx.save_for_backward(target, m, lv, cols)
+        ctx.meta = (B, O, ldm, ldv, float(scale), kl is not None, tuple(log_var.shape))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        target, m, lv, cols = ctx.saved_tensors
+        B, O, ldm, ldv, scale, has_kl, lv_shape = ctx.meta
+        g = g.contiguous()
+        g_mean = torch.empty((B, O), dtype=torch.float32, device=g.device)
+        g_lv = torch.empty(lv_shape, dtype=torch.float32, device=g.device) if ctx.needs_input_grad[2] else None
+        g_kl = torch.empty((), dtype=torch.float32, device=g.device) if has_kl else None
+        stream = torch.cuda.current_stream(g.device).cuda_stream
+        _lib.check(_lib.lib().lbbnn_elbo_gaussian_loss_backward(g.data_ptr(), m.data_ptr(), ldm, target.data_ptr(), O, lv.data_ptr(),
+                                                                ldv, B, O, scale, cols.data_ptr() if cols is not None else None,
+                                                                g_mean.data_ptr(), g_lv.data_ptr() if g_lv is not None else None,
+                                                                g_kl.data_ptr() if has_kl else None, stream),
+                   "lbbnn_elbo_gaussian_loss_backward")
+        return g_mean, None, g_lv, g_kl, None, None, None
+
+
+LOG_2PI = 1.8378770664093453
+
+
+def _gaussian_args(mean, target, log_var):
+    """``target`` as the (B, O) float32 block the loss reads and ``log_var`` as given, or ValueError naming the mismatch --
+    checked before any pointer is handed to the library."""
+    who = "bnn_amd: elbo_gaussian_loss: "
+    if not torch.is_tensor(mean) or mean.dim() != 2:
+        raise ValueError(who + "mean must be a (B, O) tensor, got %s"
+                         % (tuple(mean.shape) if torch.is_tensor(mean) else type(mean).__name__,))
+    if mean.dtype != torch.float32:
+        raise ValueError(who + "mean must be float32, got %s" % mean.dtype)
+    if not torch.is_tensor(target):
+        raise ValueError(who + "target must be a tensor, got %s" % type(target).__name__)
+    if target.dtype != torch.float32:
+        raise ValueError(who + "target must be float32, got %s" % target.dtype)
+    if target.device != mean.device:
+        raise ValueError(who + "target is on %s, mean on %s" % (target.device, mean.device))
+    B, O = mean.shape
+    if tuple(target.shape) != (B, O) and not (O == 1 and tuple(target.shape) == (B,)):
+        raise ValueError(who + "target has shape %s, mean %s" % (tuple(target.shape), (B, O)))
+    if not target.is_contiguous():
+        raise ValueError(who + "target must be contiguous (strides %s)" % (tuple(target.stride()),))
+    if not torch.is_tensor(log_var):
+        raise ValueError(who + "log_var must be a tensor of shape (O,) or (B, O), got %s" % type(log_var).__name__)
+    if log_var.dtype != torch.float32:
+        raise ValueError(who + "log_var must be float32, got %s" % log_var.dtype)
+    if log_var.device != mean.device:
+        raise ValueError(who + "log_var is on %s, mean on %s" % (log_var.device, mean.device))
+    if tuple(log_var.shape) not in ((O,), (B, O)):
+        raise ValueError(who + "log_var has shape %s, expected (%d,) or (%d, %d)" % (tuple(log_var.shape), O, B, O))
+    return target.view(B, O)
+
+
+def _check_monitored_gaussian(mean, kl, monitor):
+    """``_check_monitored_bce`` for the Gaussian loss: ValueError naming what keeps this call off the fused, monitored launch."""
+    who = "bnn_amd: elbo_gaussian_loss(monitor=...): "
+    if not isinstance(monitor, TrainMonitor):
+        raise ValueError(who + "monitor must be a bnn_amd.TrainMonitor, got %s" % type(monitor).__name__)
+    if mean.shape[1] != monitor.classes:
+        raise ValueError(who + "mean has %d units, the monitor was built for %d" % (mean.shape[1], monitor.classes))
+    if mean.shape[0] < 1:
+        raise ValueError(who + "an empty batch has no step to record")
+    if not _fused_kl(kl):
+        raise ValueError(who + "kl must be None or a one-element float32 HIP tensor")
+    if not mean.is_cuda:
+        raise ValueError(who + "the monitor lives in the fused HIP loss; mean is on %s" % mean.device)
+    if mean.device != monitor.device:
+        raise ValueError(who + "mean is on %s, the monitor on %s" % (mean.device, monitor.device))
+
+
+def elbo_gaussian_loss(mean, target, log_var, kl=None, num_batches=1.0, *, stats=None, monitor=None):
+    """sum_{b,o} 0.5 (log(2 pi) + lv + (y - m)^2 exp(-lv)) + kl / num_batches -- ``F.gaussian_nll_loss(mean, target, exp(log_var),
+    full=True, reduction="sum") + kl / num_batches``: the ELBO loss of a regression network (``head="identity"``).
+
+    ``mean`` (B, O) float32, possibly a strided view (a column slice of a wider output); ``target`` float32 of the same shape
+    (or (B,) against (B, 1)), contiguous, on the device of ``mean``; ``log_var`` float32 on that device, of shape (O,) -- one
+    noise level per output unit, typically an ``nn.Parameter`` the optimizer also steps -- or (B, O), one per element and
+    possibly a strided view (the other half of a heteroscedastic network's output).  Anything else is a ValueError before any
+    launch.  HIP tensors: ONE forward launch and ONE backward launch (lbbnn_elbo_gaussian_loss*); the gradient of a shared
+    ``log_var`` is a column sum over the batch that the forward launch leaves as a by-product (fp64, fixed order: the same bits
+    from run to run).  CPU tensors: the same expression in torch ops.
+
+    A target that is NaN or infinite is a bad target: no loss term, no gradient, counted.  A non-finite ``mean`` or
+    ``log_var`` makes the loss non-finite.
+
+    ``stats``: a float64[4] device tensor that every call ADDS to -- squared-error sum, absolute-error sum, elements with a
+    valid target, bad targets.  Nothing here reads it: ``(stats[0] / stats[2]).sqrt()`` is the training RMSE, one read per
+    epoch; zero it with ``stats.zero_()``.
+
+    ``monitor``: a ``TrainMonitor(units, device)`` whose totals and guard word this step is recorded in, by the forward launch
+    itself (lbbnn_elbo_gaussian_loss_monitor); the loss, ``stats`` and every gradient are bitwise those of the call without one.
+    The monitor counts ELEMENTS (b, o), as for ``elbo_bce_loss``.  ``correct`` counts the elements with a valid target and
+    |y - m| <= exp(0.5 lv), so ``result()["accuracy"]`` reads as the ONE-SIGMA COVERAGE: about 0.683 for a calibrated Gaussian.
+    ``bad_targets`` are the NaN / infinite targets (``result(strict=True)`` raises on them), ``nonfinite_rows`` the elements
+    whose mean or log-variance is not finite.  A monitor needs the fused path -- HIP tensors on the monitor's device, a
+    non-empty batch, ``kl`` None or a one-element float32 HIP tensor -- and anything else is a ValueError."""
+    t = _gaussian_args(mean, target, log_var)
+    if monitor is not None:
+        _check_monitored_gaussian(mean, kl, monitor)
+    if stats is not None and not (torch.is_tensor(stats) and stats.dtype == torch.float64 and stats.numel() == 4
+                                  and stats.is_contiguous() and stats.device == mean.device):
+        raise ValueError("bnn_amd: elbo_gaussian_loss: stats must be a contiguous float64[4] tensor on %s" % mean.device)
+    if not 1 <= mean.shape[1] <= 16 and mean.is_cuda:
+        raise ValueError("bnn_amd: elbo_gaussian_loss: the fused loss takes 1 to 16 output units, got %d" % mean.shape[1])
+    # (an empty batch has no storage to point the kernel at: it takes the torch expression, the kl term alone)
+    if mean.is_cuda and _fused_kl(kl) and mean.shape[0] > 0:
+        return _ElboGaussianLossFn.apply(mean, t, log_var, kl if kl is None else kl.reshape(()), 1.0 / float(num_batches), stats,
+                                         monitor)
+    ok = torch.isfinite(t)
+    d = torch.where(ok, t, mean.detach()) - mean
+    term = 0.5 * ((LOG_2PI + log_var) + (d * d) * torch.exp(-log_var))
+    nll = torch.where(ok, term, torch.zeros_like(term)).sum()
+    if stats is not None:
+        with torch.no_grad():
+            dd = torch.where(ok, d, torch.zeros_like(d)).double()
+            stats += torch.stack([(dd * dd).sum(), dd.abs().sum(), ok.sum().double(), (~ok).sum().double()])
+    return nll if kl is None else nll + kl / num_batches
 
 
 class _SumKLFn(torch.autograd.Function):

@@ -1588,6 +1588,136 @@ typedef struct lbbnn_eval_uncertainty_args {
 int64_t lbbnn_eval_uncertainty_work_bytes(int S, int B, int C, int conf_bins);
 int lbbnn_eval_uncertainty(const lbbnn_eval_uncertainty_args_t* args, void* stream);
 
+/* The fused Gaussian ELBO loss of a regression network (head "identity": the last layer's raw output m is the mean of a normal
+ * likelihood whose log-variance is lv): F.gaussian_nll_loss(m, y, exp(lv), full=True, reduction='sum') + kl / NUM_BATCHES.  One
+ * forward launch of one 1024-thread workgroup, one pass, fp64 partial sums in a fixed order, no atomics: the same bits from run to
+ * run.  (B, O) blocks with dense rows and a free row stride (ld*, floats); 0 <= B, 1 <= O <= 16, B * O < 2^31.
+ * log_var: ldv == 0: O floats, one noise level per output unit; ldv >= O: a (B, O) block of row stride ldv, one per element.
+ *
+ * Element (b, o), with y = target, every operation a single fp32 one in this order (no fused multiply-add):
+ *   d = y - m;  iv = expf(-lv);  q = (d * d) * iv;  term = 0.5f * ((L + lv) + q);  dlv = 0.5f * (1.f - q)
+ *   with L = (float)1.8378770664093453 = log(2 pi).
+ * A target that is NaN or infinite is a BAD target: the element has no term, no gradient, and is counted.  A non-finite m or lv
+ * makes the term, and with it the loss, non-finite (and is counted, bad target or not).
+ * lbbnn_elbo_gaussian_loss:
+ *   *loss = (float)(sum_{b,o} (double)term + (kl ? (double)*kl * (double)kl_scale : 0)).  The first T = (1024 / O) * O threads
+ *   work, thread t on the elements t, t + T, ... in rising order (all of column t % O); the threads' fp64 sums are added by the
+ *   fixed wave butterfly, the 16 wave totals in wave order by one thread after the workgroup's single barrier.
+ *   stats (double[4], nullable) is ADDED TO by thread 0 with plain loads and stores (the caller zeroes it):
+ *     [0] += sum (double)(d * d)   [1] += sum (double)fabsf(d)   over the elements with a valid target
+ *     [2] += elements with a valid target                        [3] += bad targets
+ *   lv_cols (O floats, nullable; ldv == 0 only, LBBNN_E_SHAPE otherwise): lv_cols[o] = (float)(sum_b (double)dlv[b][o]) over
+ *   the valid targets of column o, the threads of the column added in the same fixed order -- d loss / d lv[o] up to the factor
+ *   *g, a by-product of the pass.
+ * lbbnn_elbo_gaussian_loss_backward (one multi-workgroup launch): g_mean (B, O dense) = ((*g) * (m - y)) * iv, 0 for a bad
+ *   target; g_lv (nullable): ldv >= O: (B, O dense) = ((*g) * 0.5f) * (1.f - (d * d) * iv), 0 for a bad target; ldv == 0: O
+ *   floats, g_lv[o] = (*g) * lv_cols[o] with lv_cols as the forward left them (required then: LBBNN_E_NULL);  *g_kl = (*g) *
+ *   kl_scale (g_kl nullable).
+ * Checks (before any HIP call): a required pointer NULL: LBBNN_E_NULL; B < 0, O outside 1..16, B * O >= 2^31, ldm < O, ldt < O,
+ * 0 < ldv < O or ldv < 0, lv_cols with ldv != 0: LBBNN_E_SHAPE; a pointer off 4 bytes, stats off 8: LBBNN_E_ALIGN. */
+int lbbnn_elbo_gaussian_loss(const float* mean, int ldm, const float* target, int ldt, const float* log_var, int ldv, int B, int O,
+                             const float* kl, float kl_scale, float* loss, double* stats, float* lv_cols, void* stream);
+int lbbnn_elbo_gaussian_loss_backward(const float* g, const float* mean, int ldm, const float* target, int ldt,
+                                      const float* log_var, int ldv, int B, int O, float kl_scale, const float* lv_cols,
+                                      float* g_mean, float* g_lv, float* g_kl, void* stream);
+/* lbbnn_elbo_gaussian_loss_monitor -- lbbnn_elbo_gaussian_loss with the running totals of a training log and a per-step "loss is
+ * not finite" flag, in the SAME single launch of one workgroup.  *loss, stats and lv_cols are bitwise what
+ * lbbnn_elbo_gaussian_loss writes for the same arguments (one shared pass).  The backward launch is unchanged.
+ * totals / guard: the LBBNN_MONITOR_WORDS int64 words and the int32 word of lbbnn_elbo_loss_monitor, the same layout.  A "row" is
+ * ONE ELEMENT (b, o), as for lbbnn_elbo_bce_loss_monitor; with n = B * O every call adds:
+ *   LBBNN_MONITOR_STEPS            1
+ *   LBBNN_MONITOR_ROWS             n
+ *   LBBNN_MONITOR_CORRECT          elements with a valid target and fabsf(d) <= expf(0.5f * lv): inside one standard deviation
+ *                                  (the share of them is the one-sigma coverage, 0.683 for a calibrated normal)
+ *   LBBNN_MONITOR_BAD_TARGETS      elements whose target is NaN or infinite                                  (stats[3])
+ *   LBBNN_MONITOR_NONFINITE_ROWS   elements whose m or lv is inf or NaN
+ *   LBBNN_MONITOR_NONFINITE_STEPS  1 when *loss is inf or NaN
+ *   LBBNN_MONITOR_SKIPPED_STEPS    not written here: the guarded optimizer steps' slot
+ *   LBBNN_MONITOR_NLL_ROWS         n - bad_targets, when *loss is finite
+ * Sums, with nll = the fp64 sum of the fp32 terms and kl_term = kl ? *kl * kl_scale : 0 in fp64: as
+ * lbbnn_elbo_bce_loss_monitor (NLL_SUM, KL_TERM_SUM, LOSS_SUM only on a call whose *loss is finite; LAST_NLL, LAST_LOSS
+ * overwritten by every call).  guard (nullable): OVERWRITTEN by every call: 1 when *loss is not finite, else 0.
+ * Checks: those of lbbnn_elbo_gaussian_loss with B < 1: LBBNN_E_SHAPE, and totals NULL: LBBNN_E_NULL; totals off 8 bytes, guard
+ * off 4: LBBNN_E_ALIGN. */
+int lbbnn_elbo_gaussian_loss_monitor(const float* mean, int ldm, const float* target, int ldt, const float* log_var, int ldv,
+                                     int B, int O, const float* kl, float kl_scale, float* loss, double* stats, float* lv_cols,
+                                     int64_t* totals, int32_t* guard, void* stream);
+
+/* lbbnn_eval_regression -- the evaluation numbers of a regression ensemble, from one (S members, B rows, O units) block of raw
+ * outputs (the member GEMMs of an identity-head network) under a normal likelihood with log-variance lv = log_var[o] per output
+ * unit, with running totals that stay on the device.  No host synchronisation, no allocation.  Launches: 1, or 2 with totals
+ * (the second, one workgroup, adds the double sums); B == 0: a successful no-op, no launch.
+ *
+ * Inputs.  out: member s, row b, unit o at out + s * m_stride + b * ldp + o (64-bit offsets: the padded buffer of the member
+ * GEMMs as it is, or a dense (S, B, O) tensor).  mean_out (optional): (B, O) rows of stride ldm, the posterior-mean forward.
+ * target (optional): (B, O) fp32 rows of stride ldt; a NaN or infinite target is a BAD target.  log_var: O floats, read through
+ * the pointer by every call (a live parameter).  1 <= S <= 65535, B >= 0, 1 <= O <= 16, B * O < 2^31.
+ *
+ * Per-element outputs (B * O dense, element b * O + o), each optional (NULL = not written).  m_s is member s's output, y the
+ * target; every operation is a single fp32 one in the order written (no fused multiply-add); expf / logf / erfcf / sqrtf are the
+ * device's:
+ *   pred_mean      acc = m_0; acc += m_s for s = 1 .. S-1 ascending; then acc / (float)S by IEEE division.  A CPU restatement in
+ *                  fp32 reproduces it bit for bit.
+ *   epistemic_var  d_s = m_s - pred_mean; acc = d_0 * d_0; acc += d_s * d_s ascending; then acc / (float)S.  Bit-reproducible too.
+ *   aleatoric_var  expf(lv)
+ *   total_std      sqrtf(epistemic_var + aleatoric_var)
+ *   sq_err         e = y - pred_mean; e * e.  NaN without a valid target.
+ *   log_density    the log of the members' mixture density at y: with r_s = y - m_s, iv = expf(-lv), L = (float)log(2 pi) and
+ *                  t_s = -0.5f * ((L + lv) + (r_s * r_s) * iv), the streaming logsumexp of lbbnn_eval_uncertainty's log_score
+ *                  (s = s * expf(mx_old - t) + 1 when t raises the running maximum mx, s += expf(t - mx) otherwise; a term at -inf
+ *                  adds nothing), then (mx + logf(s)) - logf((float)S).  Finite whenever one member's term is finite, where
+ *                  logf(mean expf(t_s)) is -inf once every expf underflows.  NaN without a valid target.
+ *   pit            the probability integral transform of y under the mixture: with hs = expf(-0.5f * lv),
+ *                  Phi_s = 0.5f * erfcf(-((r_s * hs) * (float)(1 / sqrt 2))); acc = Phi_0; acc += Phi_s ascending; acc / (float)S.
+ *                  NaN without a valid target.
+ *
+ * Running totals: counts, sums, pit_hist and work are given together or not at all.  They are ADDED TO; the caller zeroes them.
+ * An element is FINITE when lv and every member's output are; it is SCORED when it is finite and has a valid target.
+ *   counts[LBBNN_REG_COUNTS] (int64), in this order: elements, elements with a valid target, bad targets (target given and NaN
+ *     or infinite), non-finite elements (they enter no sum and no bin), scored elements
+ *   sums[LBBNN_REG_SUMS] (double), in this order: sq_err, |y - pred_mean|, log_density, y, y * y (fp32 product) and the squared
+ *     error (y - mean_out)^2 of the posterior-mean forward (0 without mean_out) over the SCORED elements -- at positions 0, 1, 2,
+ *     5, 6, 7 -- and epistemic_var, epistemic_var + aleatoric_var over the FINITE elements at positions 3, 4
+ *   pit_hist[pit_bins] (int64) over the scored elements, bin = clamp((int)(pit * (float)pit_bins), 0, pit_bins - 1): a single fp32
+ *     product, clamped to [0, pit_bins] as a float before the conversion.  1 <= pit_bins <= 1024.
+ * Every total is bitwise reproducible from run to run: the integers are counted per workgroup and added with integer atomics
+ * (exact); each workgroup of 256 consecutive elements adds its doubles in element order and leaves LBBNN_REG_SUMS partials in
+ * `work`, which the second launch adds in a fixed order -- no float atomics.
+ * work: lbbnn_eval_regression_work_bytes(S, B, O) bytes (> 0 for every valid shape, non-decreasing in B; 0 for an invalid one),
+ * 8-B aligned.
+ *
+ * Checks, before anything is launched, in this order: a NULL args / out / log_var, some but not all of the totals pointers:
+ * LBBNN_E_NULL.  S, O or B out of range, ldp < O, ldm < O with mean_out, ldt < O with target, a short m_stride (S > 1, B > 0,
+ * m_stride < (B - 1) * ldp + O), B * O >= 2^31, and with totals pit_bins out of range: LBBNN_E_SHAPE.  A pointer off its natural
+ * alignment (4 B for the floats, 8 B for int64 / double / work): LBBNN_E_ALIGN. */
+#define LBBNN_REG_COUNTS 5
+#define LBBNN_REG_SUMS 8
+typedef struct lbbnn_eval_regression_args {
+    const float* out;
+    int64_t m_stride, ldp;
+    const float* mean_out;
+    int64_t ldm;
+    const float* target;
+    int64_t ldt;
+    const float* log_var;
+    float* pred_mean;
+    float* epistemic_var;
+    float* aleatoric_var;
+    float* total_std;
+    float* sq_err;
+    float* log_density;
+    float* pit;
+    int64_t* counts;
+    double* sums;
+    int64_t* pit_hist;
+    void* work;
+    int S, B, O;
+    int pit_bins;
+} lbbnn_eval_regression_args_t;
+
+int64_t lbbnn_eval_regression_work_bytes(int S, int B, int O);
+int lbbnn_eval_regression(const lbbnn_eval_regression_args_t* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
