@@ -322,6 +322,24 @@ class EvalRegressionArgs(ctypes.Structure):
                 ("pit_bins", c_i)]
 
 
+SCORE_MAX_LEVELS = 4                   # LBBNN_SCORE_MAX_LEVELS
+SCORE_MAX_MEMBERS = 64                 # LBBNN_SCORE_MAX_MEMBERS
+SCORE_COUNTS = REG_COUNTS + SCORE_MAX_LEVELS           # LBBNN_SCORE_COUNTS: REG_COUNT_NAMES, then inside[level]
+SCORE_SUMS = REG_SUMS + 2 + 2 * SCORE_MAX_LEVELS       # LBBNN_SCORE_SUMS: REG_SUM_NAMES, these two, width[level], interval_score[level]
+SCORE_SUM_NAMES = REG_SUM_NAMES + ("aleatoric_var", "crps")
+SCORE_ROW_KEYS = REG_ROW_KEYS + ("crps",)              # (B, units) each
+SCORE_LEVEL_KEYS = ("lower", "upper", "interval_score")     # (levels, B, units) each
+
+
+class EvalScoresArgs(ctypes.Structure):
+    """lbbnn_eval_scores_args_t"""
+    _fields_ = [("out", c_p), ("m_stride", c_i64), ("ldp", c_i64), ("mean_out", c_p), ("ldm", c_i64), ("target", c_p),
+                ("ldt", c_i64), ("log_var", c_p), ("lv_mstride", c_i64), ("lv_ld", c_i64)] + \
+               [(n, c_p) for n in SCORE_ROW_KEYS + SCORE_LEVEL_KEYS] + \
+               [("counts", c_p), ("sums", c_p), ("pit_hist", c_p), ("work", c_p), ("S", c_i), ("B", c_i), ("O", c_i),
+                ("pit_bins", c_i), ("n_levels", c_i), ("levels", ctypes.c_float * SCORE_MAX_LEVELS)]
+
+
 # name -> (restype, argtypes); must list every symbol include/lbbnn.h declares
 SIGNATURES = {
     "lbbnn_abi_version": (c_i, []),
@@ -449,6 +467,8 @@ SIGNATURES = {
     "lbbnn_eval_uncertainty": (c_i, [ctypes.POINTER(EvalUncertaintyArgs), c_p]),
     "lbbnn_eval_regression_work_bytes": (c_i64, [c_i, c_i, c_i]),
     "lbbnn_eval_regression": (c_i, [ctypes.POINTER(EvalRegressionArgs), c_p]),
+    "lbbnn_eval_regression_scores_work_bytes": (c_i64, [c_i, c_i, c_i, c_i]),
+    "lbbnn_eval_regression_scores": (c_i, [ctypes.POINTER(EvalScoresArgs), c_p]),
     "lbbnn_elbo_gaussian_loss": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_p, ctypes.c_float, c_p, c_p, c_p, c_p]),
     "lbbnn_elbo_gaussian_loss_monitor": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_p, ctypes.c_float, c_p, c_p, c_p, c_p, c_p,
                                                c_p]),

@@ -33,10 +33,12 @@ that snapshot (lbbnn_base_frozen_members) at the streams, offsets and counters o
 
 An LRT / MNF network with ``head="identity"`` (regression) returns raw outputs from every ensemble form above and from its frozen
 models; ``ensemble_regression`` / ``RegressionAccumulator`` (lbbnn_eval_regression) are its metrics -- predictive mean, epistemic
-and aleatoric variance, mixture log density, PIT -- and the classification tools refuse such a model.
+and aleatoric variance, mixture log density, PIT -- and the classification tools refuse such a model.  ``ensemble_scores`` /
+``RegressionScoreAccumulator`` / ``predict_regression`` (lbbnn_eval_regression_scores) are the same for a noise level per element
+or per member -- e.g. a network whose outputs carry their own log-variances -- plus the CRPS and prediction intervals.
 """
 import math
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import torch
 from torch import nn
@@ -1039,10 +1041,14 @@ class RegressionAccumulator:
         ``coverage(level)`` = ``pit_coverage(pit_hist, level)``, the share of PIT values in the central ``level`` interval
         (ValueError when its edges are not bin edges).  ``strict``: as ``EvalAccumulator.result`` -- bad targets raise
         IndexError; with ``strict=False`` they are reported in ``bad_targets`` and left out of the totals."""
+        import numpy as np
+        return self._result_of(np.ascontiguousarray(self._read(), dtype=np.int64), strict)
+
+    def _result_of(self, h, strict: bool) -> Dict[str, object]:
+        """``result`` from the host copy ``h`` of totals laid out counts | sums | pit_hist."""
         import functools
         import numpy as np
         from . import _lib
-        h = np.ascontiguousarray(self._read(), dtype=np.int64)
         nc, ns = _lib.REG_COUNTS, _lib.REG_SUMS
         res = {k: int(h[i]) for i, k in enumerate(_lib.REG_COUNT_NAMES)}
         if strict and res["bad_targets"]:
@@ -1065,6 +1071,236 @@ class RegressionAccumulator:
         res["pit_hist"] = h[nc + ns:].copy()
         res["coverage"] = functools.partial(pit_coverage, res["pit_hist"])
         return res
+
+
+def _score_levels(levels) -> Tuple[float, ...]:
+    """``levels`` as a tuple of at most 4 central interval levels, each in [0.01, 0.999] as the float32 the kernel reads."""
+    from . import _lib
+    try:
+        lv = tuple(float(p) for p in levels)
+    except TypeError:
+        raise ValueError("bnn_amd: levels must be a sequence of numbers, got %s" % type(levels).__name__)
+    if len(lv) > _lib.SCORE_MAX_LEVELS:
+        raise ValueError("bnn_amd: at most %d interval levels, got %d" % (_lib.SCORE_MAX_LEVELS, len(lv)))
+    f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))
+    for p in lv:
+        if not f32(0.01) <= f32(p) <= f32(0.999):              # as the library compares them; a NaN fails both comparisons
+            raise ValueError("bnn_amd: an interval level must lie in [0.01, 0.999], got %r" % (p,))
+    return lv
+
+
+def _scores_log_var(log_var, S: int, B: int, O: int, dev):
+    """(tensor, member stride, row stride) of the log-variance operand of lbbnn_eval_regression_scores: a number or a (O,) tensor
+    as ``_regression_log_var`` takes them -> (0, 0); a float32 (B, O) tensor -> (0, ld); a float32 (S, B, O) tensor -> (ms, ld),
+    read in place where the last dimension is dense and the members do not overlap."""
+    if not torch.is_tensor(log_var) or log_var.dim() < 2:
+        return _regression_log_var(log_var, O, dev), 0, 0
+    if log_var.dtype != torch.float32 or log_var.device != dev or tuple(log_var.shape) not in ((B, O), (S, B, O)):
+        raise ValueError("bnn_amd: log_var must be a number, \"output\", or a float32 tensor of shape (%d,), (%d, %d) or (%d, %d, %d) "
+                         "on %s, got %s %s on %s" % (O, B, O, S, B, O, dev, log_var.dtype, tuple(log_var.shape), log_var.device))
+    lv = log_var.detach()
+    if lv.dim() == 2:
+        lv, ld = _dense_rows(lv, B, O)
+        return lv, 0, ld
+    ld = lv.stride(1) if B > 1 else O
+    ms = lv.stride(0) if S > 1 else 0
+    if (O > 1 and lv.stride(2) != 1) or ld < O or (S > 1 and B > 0 and ms < (B - 1) * ld + O):
+        lv, ld, ms = lv.contiguous(), O, B * O
+    if S == 1:
+        ms = 0
+    return lv, ms, ld
+
+
+@torch.no_grad()
+def ensemble_scores(outputs: torch.Tensor, target: Optional[torch.Tensor] = None, log_var=0.0,
+                    mean_outputs: Optional[torch.Tensor] = None, *, levels=(0.9,),
+                    acc: Optional["RegressionScoreAccumulator"] = None) -> Dict[str, object]:
+    """``ensemble_regression`` for a noise level that may differ per element or per member, with two more scores: the
+    per-element numbers of a regression ensemble from one (samples, B, units) block of member means under a normal likelihood,
+    in ONE lbbnn_eval_regression_scores call (1 launch; 2 with ``acc``) and without a host synchronisation (arithmetic:
+    include/lbbnn.h).  Each (B, units):
+
+    * ``pred_mean``, ``epistemic_var``: ``ensemble_regression``'s, the same bits;
+    * ``aleatoric_var`` = the members' mean of exp(log_var) and ``total_std`` = sqrt(epistemic_var + aleatoric_var);
+    * with ``target``: ``sq_err``, ``log_density`` and ``pit`` of the members' mixture, each member with its own variance, and
+      ``crps``: the continuous ranked probability score of that mixture in closed form; NaN without a valid target;
+
+    and (len(levels), B, units): ``lower`` / ``upper``, the (1 - p) / 2 and (1 + p) / 2 quantiles of the mixture for each central
+    level p of ``levels`` (at most 4, each in [0.01, 0.999]), and with ``target`` the ``interval_score``
+    (upper - lower) + 2 / (1 - p) * (the distance by which the target misses the interval).  An element one of whose members has
+    a non-finite mean, or a log-variance that is non-finite or beyond +-80, is NaN in every output.
+
+    ``outputs``: as ``ensemble_regression`` takes it, at most 64 members.  ``log_var``: a number; a live float32 (units,) tensor;
+    a float32 (B, units) tensor (one value per element); a float32 (samples, B, units) tensor (one per member and element); or
+    the string ``"output"``: ``outputs`` is then (samples, B, 2 * units) with the means in columns [0, units) and the
+    log-variances in [units, 2 * units) -- what a ``dims[-1] == 2 * units`` identity-head network trained with
+    ``elbo_gaussian_loss(out[:, :units], y, out[:, units:])`` returns -- read in place, and ``mean_outputs`` is
+    (B, 2 * units), of which only the mean columns are read.  ``acc``: a ``RegressionScoreAccumulator`` whose running totals this
+    call adds to (its ``levels`` are used)."""
+    import ctypes
+    from . import _lib
+    in_output = isinstance(log_var, str)
+    if in_output and log_var != "output":
+        raise ValueError("bnn_amd: log_var must be a number, a tensor or the string \"output\", got %r" % (log_var,))
+    if acc is not None and not isinstance(acc, RegressionScoreAccumulator):
+        raise ValueError("bnn_amd: ensemble_scores takes acc=RegressionScoreAccumulator, got %s" % type(acc).__name__)
+    lev = acc.levels if acc is not None else _score_levels(levels)
+    o, S, B, C, ms, ldp = _member_block(outputs, "ensemble_scores")
+    if in_output and C % 2:
+        raise ValueError("bnn_amd: log_var=\"output\" takes outputs with 2 * units columns, got %d" % C)
+    O = C // 2 if in_output else C
+    if O > 16:
+        raise ValueError("bnn_amd: ensemble_scores takes 1 to 16 output units, got %d" % O)
+    if S > _lib.SCORE_MAX_MEMBERS:
+        raise ValueError("bnn_amd: ensemble_scores takes 1 to %d members, got %d" % (_lib.SCORE_MAX_MEMBERS, S))
+    dev = outputs.device
+    a = _lib.EvalScoresArgs()
+    a.out, a.m_stride, a.ldp, a.S, a.B, a.O = o.data_ptr(), ms, ldp, S, B, O
+    if in_output:
+        # the upper columns of the members' own buffer; one member: its rows are one value per element
+        lv, a.lv_mstride, a.lv_ld = o, ms, ldp
+        a.log_var = o.data_ptr() + 4 * O
+    else:
+        lv, a.lv_mstride, a.lv_ld = _scores_log_var(log_var, S, B, O, dev)
+        a.log_var = lv.data_ptr()
+    keep = [o, lv]
+    if mean_outputs is not None:
+        if tuple(mean_outputs.shape) != (B, C) or mean_outputs.device != dev:
+            raise ValueError("bnn_amd: mean_outputs must be (%d, %d) on %s, got %s on %s"
+                             % (B, C, dev, tuple(mean_outputs.shape), mean_outputs.device))
+        mo, ldm = _dense_rows(mean_outputs if mean_outputs.dtype == torch.float32 else mean_outputs.float(), B, C)
+        a.mean_out, a.ldm = mo.data_ptr(), ldm
+        keep.append(mo)
+    if target is not None:
+        t = _regression_target(target, B, O, dev)
+        a.target, a.ldt = t.data_ptr(), O
+        keep.append(t)
+    a.n_levels = L = len(lev)
+    for i, p in enumerate(lev):
+        a.levels[i] = p
+    rows, per_level = _lib.SCORE_ROW_KEYS, _lib.SCORE_LEVEL_KEYS
+    buf = torch.empty((len(rows) + L * len(per_level), B, O), dtype=torch.float32, device=dev)    # one allocation
+    res = {}
+    for i, k in enumerate(rows):
+        res[k] = buf[i]
+        setattr(a, k, buf.data_ptr() + 4 * i * B * O)
+    for j, k in enumerate(per_level):
+        first = len(rows) + j * L
+        res[k] = buf[first:first + L]
+        if L:
+            setattr(a, k, buf.data_ptr() + 4 * first * B * O)
+    if acc is not None:
+        acc._fill(a, S, B, O, dev)
+    if B > 0:                                                # (an empty batch has no storage to point at, and nothing to add)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(_lib.lib().lbbnn_eval_regression_scores(ctypes.byref(a), stream), "lbbnn_eval_regression_scores")
+    if acc is not None:
+        acc._note(mean_outputs is not None)
+    del keep
+    return res
+
+
+class RegressionScoreAccumulator(RegressionAccumulator):
+    """A ``RegressionAccumulator`` for a noise level of any layout, with the CRPS and prediction intervals: ``update`` is
+    ``ensemble_scores`` with the accumulator's ``log_var`` and ``levels``, its numbers added to totals on the device (no host
+    read); ``result`` reads them in one copy.  ``evaluate_batches`` and ``graphs.make_graphed_eval_step`` take it wherever they
+    take a ``RegressionAccumulator``.
+
+    ``units`` (1 to 16), ``samples`` (1 to 64: the CRPS is quadratic in it), ``pit_bins`` and ``levels`` (at most 4 central
+    interval levels, each in [0.01, 0.999]) are fixed for the accumulator's life.  ``log_var``: a number, a live float32 (units,)
+    device tensor, or ``"output"`` -- the model then has ``dims[-1] == 2 * units`` and every member's outputs carry the
+    log-variances in their upper ``units`` columns.  A per-batch (B, units) or (samples, B, units) tensor goes to ``update``."""
+
+    def __init__(self, units: int, samples: int, device, log_var, pit_bins: int = 20, levels=(0.5, 0.9)):
+        from . import _lib
+        self.in_output = isinstance(log_var, str)
+        if self.in_output and log_var != "output":
+            raise ValueError("bnn_amd: log_var must be a number, a float32 (units,) tensor or the string \"output\", got %r" % (log_var,))
+        super().__init__(units, samples, device, 0.0 if self.in_output else log_var, pit_bins)
+        if self.samples > _lib.SCORE_MAX_MEMBERS:
+            raise ValueError("bnn_amd: RegressionScoreAccumulator takes 1 to %d members, got %d" % (_lib.SCORE_MAX_MEMBERS, self.samples))
+        self.levels = _score_levels(levels)
+        # one buffer, one read: counts | sums (bit patterns) | pit_hist
+        self._totals = torch.zeros(_lib.SCORE_COUNTS + _lib.SCORE_SUMS + self.pit_bins, dtype=torch.int64, device=self.device)
+
+    def _fill(self, a, S, B, O, dev):
+        """Point the totals of an lbbnn_eval_scores_args_t at this accumulator (work memory grows to the largest batch)."""
+        from . import _lib
+        if (S, O) != (self.samples, self.units):
+            raise ValueError("bnn_amd: this RegressionScoreAccumulator was built for %d members and %d units, the outputs have %d and %d"
+                             % (self.samples, self.units, S, O))
+        if dev != self._totals.device:
+            raise ValueError("bnn_amd: the outputs are on %s, the accumulator on %s" % (dev, self._totals.device))
+        need = int(_lib.lib().lbbnn_eval_regression_scores_work_bytes(S, B, O, len(self.levels)))
+        if self._work is None or self._work.numel() * 8 < need:
+            self._work = torch.empty(need // 8, dtype=torch.float64, device=dev)
+        base = self._totals.data_ptr()
+        a.counts, a.sums = base, base + 8 * _lib.SCORE_COUNTS
+        a.pit_hist = base + 8 * (_lib.SCORE_COUNTS + _lib.SCORE_SUMS)
+        a.work, a.pit_bins = self._work.data_ptr(), self.pit_bins
+
+    def update(self, outputs: torch.Tensor, target: Optional[torch.Tensor] = None, mean_outputs: Optional[torch.Tensor] = None,
+               *, log_var=None):
+        """``ensemble_scores(outputs, target, log_var, mean_outputs)`` of one batch with the accumulator's levels, its numbers
+        added to the totals.  ``log_var``: None for the accumulator's own, or this batch's float32 (B, units) /
+        (samples, B, units) tensor."""
+        if self.in_output:
+            if log_var is not None:
+                raise ValueError("bnn_amd: this RegressionScoreAccumulator reads log_var from the outputs (log_var=\"output\")")
+            if outputs.dim() == 3 and outputs.shape[-1] != 2 * self.units:
+                raise ValueError("bnn_amd: log_var=\"output\" with %d units takes outputs of 2 * units = %d columns (the model's "
+                                 "dims[-1]), got %d" % (self.units, 2 * self.units, outputs.shape[-1]))
+            return ensemble_scores(outputs, target, "output", mean_outputs, acc=self)
+        if log_var is not None and not (torch.is_tensor(log_var) and log_var.dim() >= 2):
+            raise ValueError("bnn_amd: update takes log_var=None or this batch's (B, units) / (samples, B, units) tensor")
+        return ensemble_scores(outputs, target, self._log_var if log_var is None else log_var, mean_outputs, acc=self)
+
+    def result(self, strict: bool = True) -> Dict[str, object]:
+        """Everything ``RegressionAccumulator.result`` returns, under the same keys (``total_var`` is epistemic plus the
+        members' mean aleatoric variance), and: ``aleatoric_var_sum`` / ``mean_aleatoric_var`` over the finite elements,
+        ``crps_sum`` / ``crps`` (the mean over the scored elements), ``levels`` and ``intervals``: per level a dict of
+        ``level``, ``inside`` (scored elements with lower <= y <= upper), ``coverage`` = inside / scored, ``width_sum`` /
+        ``mean_width`` and ``interval_score_sum`` / ``mean_interval_score`` over the scored elements.  NaN where a denominator
+        is 0.  ``strict``: as ``RegressionAccumulator.result``."""
+        import numpy as np
+        from . import _lib
+        h = np.ascontiguousarray(self._read(), dtype=np.int64)
+        nc, ns, rc, rs, ml = _lib.SCORE_COUNTS, _lib.SCORE_SUMS, _lib.REG_COUNTS, _lib.REG_SUMS, _lib.SCORE_MAX_LEVELS
+        res = self._result_of(np.concatenate([h[:rc], h[nc:nc + rs], h[nc + ns:]]), strict)
+        sums = h[nc:nc + ns].view(np.float64)
+        div = lambda x, d: x / d if d else float("nan")
+        n, nf = res["scored_elements"], res["elements"] - res["nonfinite_elements"]
+        res["aleatoric_var_sum"], res["crps_sum"] = float(sums[rs]), float(sums[rs + 1])
+        res["mean_aleatoric_var"] = div(res["aleatoric_var_sum"], nf)
+        res["crps"] = div(res["crps_sum"], n)
+        res["levels"] = self.levels
+        res["intervals"] = []
+        for l, p in enumerate(self.levels):
+            w, s, inside = float(sums[rs + 2 + l]), float(sums[rs + 2 + ml + l]), int(h[rc + l])
+            res["intervals"].append(dict(level=p, inside=inside, coverage=div(inside, n), width_sum=w, mean_width=div(w, n),
+                                         interval_score_sum=s, mean_interval_score=div(s, n)))
+        return res
+
+
+@torch.no_grad()
+def predict_regression(model, x: torch.Tensor, samples: int, log_var, levels=(0.9,)) -> Dict[str, torch.Tensor]:
+    """The predictive distribution of an identity-head LRT / MNF network or its frozen model at ``x`` as device tensors, nothing
+    read on the host: the ensemble of ``samples`` members (at most 64) and one ``ensemble_scores`` call without a target.
+    ``pred_mean``, ``total_std``, ``epistemic_var``, ``aleatoric_var``: (B, units); ``lower``, ``upper``: (len(levels), B, units),
+    the bounds of the central ``levels`` intervals of the members' mixture.  ``log_var``: as ``ensemble_scores`` takes it;
+    ``"output"`` for a model whose outputs carry the log-variances in their upper half (units = dims[-1] / 2)."""
+    if _head_of(model) != "identity" or not (_is_frozen(model) or hasattr(model, "_forward_streams")):
+        raise ValueError("bnn_amd: predict_regression takes an LRT / MNF network with head=\"identity\" or its frozen model, "
+                         "got %s with head=%r" % (type(model).__name__, _head_of(model)))
+    from . import _lib
+    lev = _score_levels(levels)
+    S = int(samples)
+    if not 1 <= S <= _lib.SCORE_MAX_MEMBERS:
+        raise ValueError("bnn_amd: predict_regression takes 1 to %d members, got %d" % (_lib.SCORE_MAX_MEMBERS, S))
+    outputs = model.ensemble(x, S) if _is_frozen(model) else ensemble_forward(model, x, S)
+    rows = ensemble_scores(outputs, None, log_var, levels=lev)
+    return {k: rows[k] for k in ("pred_mean", "total_std", "epistemic_var", "aleatoric_var", "lower", "upper")}
 
 
 def _regression_pass(net, acc, uncertainty, who: str) -> bool:

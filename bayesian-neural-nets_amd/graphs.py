@@ -189,7 +189,9 @@ def make_graphed_eval_step(frozen, example_x, example_y, samples: int, acc, warm
     and its per-row numbers join the returned dict under their own keys.
     A frozen model with ``head="identity"`` takes ``acc`` = an ``evaluate.RegressionAccumulator`` (and no ``uncertainty``): the
     step is the ensemble, the posterior-mean forward and lbbnn_eval_regression in one graph; ``example_y`` is the float32
-    (B, units) target.  Any other pairing of head and accumulator is a ValueError."""
+    (B, units) target.  An ``evaluate.RegressionScoreAccumulator`` is one of those: the metrics launch is then
+    lbbnn_eval_regression_scores (with ``log_var="output"`` the model has ``2 * units`` outputs and ``example_y`` stays
+    (B, units)).  Any other pairing of head and accumulator is a ValueError."""
     from . import evaluate, ops
     if not evaluate._is_frozen(frozen):
         raise TypeError("bnn_amd.graphs.make_graphed_eval_step takes a frozen model (evaluate.freeze), got %s"

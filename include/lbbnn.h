@@ -1718,6 +1718,100 @@ typedef struct lbbnn_eval_regression_args {
 int64_t lbbnn_eval_regression_work_bytes(int S, int B, int O);
 int lbbnn_eval_regression(const lbbnn_eval_regression_args_t* args, void* stream);
 
+/* lbbnn_eval_regression_scores -- lbbnn_eval_regression for a heteroscedastic ensemble, with two more scores: the numbers above
+ * from one (S members, B rows, O units) block of member means under a normal likelihood whose log-variance operand has strides of
+ * its own, plus the CRPS of the members' mixture and central prediction intervals, with running totals that stay on the device.
+ * No host synchronisation, no allocation.  Launches: 1, or 2 with totals; B == 0: a successful no-op, no launch.
+ *
+ * Inputs.  out, m_stride, ldp, mean_out, ldm, target, ldt: as lbbnn_eval_regression (of mean_out only columns [0, O) are read).
+ * log_var: member s, row b, unit o at log_var + s * lv_mstride + b * lv_ld + o, read through the pointer by every call:
+ *   (lv_mstride, lv_ld) = (0, 0)    one value per unit, log_var[o]
+ *                         (0, ld)   one value per element, shared by the members; ld >= O
+ *                         (ms, ld)  one value per member and element; ld >= O, ms >= (B - 1) * ld + O when S > 1 and B > 0
+ * The last form may point INTO the buffer of `out` at a column offset: a (S, B, 2 O) ensemble output with means in columns [0, O)
+ * and log-variances in [O, 2 O) is out = buf, log_var = buf + O, lv_mstride = m_stride, lv_ld = ldp, read in place.
+ * levels[n_levels]: central interval levels p, 0 <= n_levels <= LBBNN_SCORE_MAX_LEVELS, each in [0.01, 0.999] (host values).
+ * 1 <= S <= LBBNN_SCORE_MAX_MEMBERS (the CRPS is quadratic in S), B >= 0, 1 <= O <= 16, B * O < 2^31.
+ *
+ * An element is FINITE when every member's mean is finite and every member's log-variance has |lv_s| <= 80 (a NaN fails; the
+ * bound keeps expf(+-lv) normal in fp32); it is SCORED when it is finite and has a valid target.  A non-finite element gets NaN
+ * in EVERY per-element output and enters no sum and no bin.
+ *
+ * Per-element outputs, each optional, (B, O) dense, element e = b * O + o; lower / upper / interval_score are (n_levels, B, O),
+ * level l at l * B * O + e.  m_s, lv_s: member s's mean and log-variance, y the target; single fp32 operations in the order
+ * written unless stated (no fused multiply-add); expf / logf / erfcf / erff / sqrtf are the device's:
+ *   pred_mean, epistemic_var   lbbnn_eval_regression's expressions and order: the same bits for a finite element
+ *   aleatoric_var  acc = expf(lv_0); acc += expf(lv_s) ascending; acc / (float)S
+ *   total_std      sqrtf(epistemic_var + aleatoric_var)
+ *   sq_err, log_density, pit   lbbnn_eval_regression's with lv_s for lv: t_s = -0.5f * ((L + lv_s) + (r_s * r_s) * expf(-lv_s)) in
+ *                  the streaming logsumexp; Phi_s = 0.5f * erfcf(-((r_s * expf(-0.5f * lv_s)) * (float)(1 / sqrt 2))).  NaN
+ *                  without a valid target.
+ *   crps           the continuous ranked probability score of the mixture at y in closed form (Grimit et al. 2006).  With
+ *                  A(m, v) = 2 sd phi(z) + |m| erff(z / sqrt 2), sd = sqrtf(v), z = |m| / sd (= E|N(m, v)|, both terms >= 0) and
+ *                  v_s = expf(lv_s):  crps = (1 / S) sum_s A(y - m_s, v_s) - (1 / 2 S^2) sum_{s,t} A(m_s - m_t, v_s + v_t).
+ *                  Each A is fp32; both sums are accumulated in DOUBLE -- the first over s ascending, the second as
+ *                  sum_s [A(0, 2 v_s) + 2 sum_{t < s} A(m_s - m_t, v_s + v_t)], s and t ascending -- combined in double and
+ *                  rounded to fp32 once.  NaN without a valid target.
+ *   lower, upper   the (1 - p) / 2 and (1 + p) / 2 quantiles of the mixture CDF F(x) = pit's expression at x: 26 bisection steps
+ *                  from the bracket [min_s (m_s - 8 sd_s), max_s (m_s + 8 sd_s)] (F(mid) < target raises the lower end), the
+ *                  midpoint of the last bracket returned.  A fixed iteration count: deterministic, and lower <= upper always.
+ *   interval_score (u - l) + (2.f / (1.f - p)) * (fmaxf(l - y, 0) + fmaxf(y - u, 0)).  NaN without a valid target.
+ *
+ * Running totals: counts, sums, pit_hist and work are given together or not at all.  They are ADDED TO; the caller zeroes them.
+ *   counts[LBBNN_SCORE_COUNTS] (int64): the five of lbbnn_eval_regression, then inside[l], l < LBBNN_SCORE_MAX_LEVELS: the scored
+ *     elements with lower_l <= y <= upper_l (levels >= n_levels are not touched)
+ *   sums[LBBNN_SCORE_SUMS] (double): the eight of lbbnn_eval_regression at the same positions (total variance = epistemic_var +
+ *     aleatoric_var), then aleatoric_var over the FINITE elements at 8, crps over the SCORED elements at 9, width_l = upper_l -
+ *     lower_l over the scored elements at 10 + l and interval_score_l at 10 + LBBNN_SCORE_MAX_LEVELS + l
+ *   pit_hist[pit_bins] (int64): as lbbnn_eval_regression.
+ * Every total is bitwise reproducible from run to run, by the construction of lbbnn_eval_regression's: integer atomics for the
+ * integers; each workgroup -- 64 consecutive elements here -- adds its doubles in element order and leaves LBBNN_SCORE_SUMS
+ * partials in `work`, which the second launch adds in a fixed order.
+ * work: lbbnn_eval_regression_scores_work_bytes(S, B, O, n_levels) bytes (> 0 for every valid shape, non-decreasing in B; 0 for
+ * an invalid one), 8-B aligned.
+ *
+ * Checks, before anything is launched, in this order: a NULL args / out / log_var, some but not all of the totals pointers:
+ * LBBNN_E_NULL.  S, O or B out of range, ldp < O, ldm < O with mean_out, ldt < O with target, a short m_stride, B * O >= 2^31,
+ * 0 < lv_ld < O, lv_mstride < 0, lv_mstride != 0 with lv_ld == 0, a short lv_mstride (S > 1, B > 0, 0 < lv_mstride <
+ * (B - 1) * lv_ld + O), n_levels out of range, a level outside [0.01, 0.999] (or NaN), and with totals pit_bins out of range:
+ * LBBNN_E_SHAPE.  A pointer off its natural alignment: LBBNN_E_ALIGN. */
+#define LBBNN_SCORE_MAX_LEVELS 4
+#define LBBNN_SCORE_MAX_MEMBERS 64
+#define LBBNN_SCORE_COUNTS (LBBNN_REG_COUNTS + LBBNN_SCORE_MAX_LEVELS)
+#define LBBNN_SCORE_SUMS (LBBNN_REG_SUMS + 2 + 2 * LBBNN_SCORE_MAX_LEVELS)
+typedef struct lbbnn_eval_scores_args {
+    const float* out;
+    int64_t m_stride, ldp;
+    const float* mean_out;
+    int64_t ldm;
+    const float* target;
+    int64_t ldt;
+    const float* log_var;
+    int64_t lv_mstride, lv_ld;
+    float* pred_mean;
+    float* epistemic_var;
+    float* aleatoric_var;
+    float* total_std;
+    float* sq_err;
+    float* log_density;
+    float* pit;
+    float* crps;
+    float* lower;
+    float* upper;
+    float* interval_score;
+    int64_t* counts;
+    double* sums;
+    int64_t* pit_hist;
+    void* work;
+    int S, B, O;
+    int pit_bins;
+    int n_levels;
+    float levels[LBBNN_SCORE_MAX_LEVELS];
+} lbbnn_eval_scores_args_t;
+
+int64_t lbbnn_eval_regression_scores_work_bytes(int S, int B, int O, int levels);
+int lbbnn_eval_regression_scores(const lbbnn_eval_scores_args_t* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
