@@ -15,8 +15,10 @@ namespace {
 // through every L2: 8 W + x = 113 MB at the 1200 x 1200 layer against 86 MB).  Falls back to the b-major run when the
 // b-tile count is not a multiple of 4, and to the identity when the grid is not a multiple of 8.  Bijective in both
 // forms; speed only, never correctness.
-__device__ __forceinline__ void tile_of_block(int& ox, int& by, int extra_rows = 0) {
-    const int nx = gridDim.x, ny = gridDim.y - extra_rows, n = nx * ny;
+// (nx, ny): the tile grid -- handed in by a caller that carries it in its kernel arguments (one scalar fetch with the
+// rest of them instead of a read of the dispatch packet behind it), else taken from the launch grid less `extra_rows`.
+__device__ __forceinline__ void tile_of_block(int& ox, int& by, int nx, int ny) {
+    const int n = nx * ny;
     int t = blockIdx.y * nx + blockIdx.x;
     if ((n & 7) == 0 && (ny & 3) == 0) {
         const int xcd = t & 7, s = t >> 3, per = n >> 3, q = ny >> 2;      // per: tiles per XCD, q: b tiles per group
@@ -27,6 +29,9 @@ __device__ __forceinline__ void tile_of_block(int& ox, int& by, int extra_rows =
     }
     if ((n & 7) == 0) t = (t & 7) * (n >> 3) + (t >> 3);
     ox = t % nx; by = t / nx;
+}
+__device__ __forceinline__ void tile_of_block(int& ox, int& by, int extra_rows = 0) {
+    tile_of_block(ox, by, (int)gridDim.x, (int)gridDim.y - extra_rows);
 }
 
 // Workgroup residency matters more than anything else here: the kernel is MFMA-issue bound, so a CU

@@ -61,6 +61,9 @@ struct G16Args {
     // with the <= 16 rows of the NEXT layer's fp32 operands and writes partial moments to h_slab[o tile][b][2][16]
     const float* h_e; const float* h_v; float* h_slab;
     int h_ld, h_C;
+    // the tile grid (launch16): grid.x x grid.y without the finalize row, so that a workgroup finds its tile -- and whether
+    // it is the finalize row, which exists only behind the tiles -- from this one fetch, not from the dispatch packet
+    int gx, gy;
     FinalizePiggy fin;
 };
 
@@ -74,53 +77,114 @@ __device__ __forceinline__ uint32_t cvt_pk_h(float a, float b) {
 __device__ __forceinline__ float h_lo(uint32_t p) { return (float)__builtin_bit_cast(f16x2, p)[0]; }
 __device__ __forceinline__ float h_hi(uint32_t p) { return (float)__builtin_bit_cast(f16x2, p)[1]; }
 
-struct OC16 { float bm[4], bv[4], vs[4], ms[4]; };
+// The epilogue's operands, staged ONCE per workgroup in the K-step buffer that is idle during the last step (it was consumed
+// in step nsteps - 2; with one step the second buffer is never used at all) -- every wave used to fetch all of them itself,
+// 16 lanes per address: 25 (35 with the head fold) 1-KiB wave loads at the head of a VALU-bound epilogue, and their values
+// held 80 (120) registers through it.  Image, BN = 16 TO features:
+//   float bm[BN] | bv[BN] | vs[BN] | ms[BN]      per-feature constants, vs = (wvar_scale 2^8) var_scale; fills 0, 0, 1, 1
+//   uint4 he[TO][64]                             head fold: (ehd | eld) of lane (class lr, quad q) of tile row i at [i][16 q + lr]
+//   uint4 hv[TO][64]                             (vhd | vld), vld = 0 with one variance product
+// The loop's closing s_waitcnt + barrier publishes the image; the epilogue reads one float4 per array and tile row.
+template <int TO>
+struct EpiImage {
+    static constexpr int BN = TO * 16;
+    static constexpr int kConst = 0, kHeadE = 4 * BN * 4, kHeadV = kHeadE + TO * 64 * 16, kBytes = kHeadV + TO * 64 * 16;
+};
 
-__device__ __forceinline__ void ld4f(const float* p, int o, int O, float fill, float out[4]) {
-    if (!p) { out[0] = out[1] = out[2] = out[3] = fill; return; }
-    if (o + 3 < O && ((reinterpret_cast<uintptr_t>(p + o) & 15u) == 0)) {
-        const float4 t = *reinterpret_cast<const float4*>(p + o);
-        out[0] = t.x; out[1] = t.y; out[2] = t.z; out[3] = t.w;
-    } else {
+// The epilogue and its staging read their arguments from the kernarg segment where they use them (scalar loads): fetched with
+// the by-value struct at kernel entry, the twenty epilogue-only fields stay in SGPRs through the K loop, and the spills that
+// follow take the kernel's scratch allocation with them.
+typedef const LBBNN_CONST_AS G16Args KArgs;
+
+// Values a thread carries from stage_load to stage_store: the image is written behind the last step's MFMAs, loads first.
+template <int NQ>
+struct EpiStage { float c[5]; float4 he[NQ], hv[NQ]; };
+
+// One float per thread and array: any alignment, any O tail, a null pointer -> the fill value.
+__device__ __forceinline__ float ld1f(const float* p, int o, bool in, float fill) { return (p && in) ? p[o] : fill; }
+
+template <int TO, int WB>
+__device__ __forceinline__ void stage_load(const KArgs& a, int o0, int tid, EpiStage<(TO + WB - 1) / WB>& st) {
+    constexpr int BN = TO * 16, NQ = (TO + WB - 1) / WB;
+    static_assert(WB * 64 >= BN, "one thread per feature");
+    if (tid < BN) {
+        const int o = o0 + tid;
+        const bool in = o < a.O;
+        st.c[0] = ld1f(a.bias_mean, o, in, 0.f);
+        st.c[1] = ld1f(a.bias_var, o, in, 0.f);
+        st.c[2] = ld1f(a.var_scale, o, in, 1.f);
+        st.c[3] = ld1f(a.mean_scale, o, in, 1.f);
+        st.c[4] = ld1f(a.wvar_scale, o, in, 1.f);
+    }
+    if (a.h_slab) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) out[r] = (o + r < O) ? p[o + r] : fill;
+        for (int u = 0; u < NQ; ++u) {
+            const int s = tid + u * WB * 64;                      // slot [i][16 q + lr]
+            const int o = o0 + (s >> 6) * 16 + 4 * ((s >> 4) & 3), cls = s & 15;
+            st.he[u] = make_float4(0.f, 0.f, 0.f, 0.f); st.hv[u] = st.he[u];
+            if (s < TO * 64 && cls < a.h_C && o < a.O) {
+                st.he[u] = *reinterpret_cast<const float4*>(a.h_e + (size_t)cls * a.h_ld + o);
+                st.hv[u] = *reinterpret_cast<const float4*>(a.h_v + (size_t)cls * a.h_ld + o);
+            }
+        }
+    }
+}
+
+template <int TO, int WB, int NPV>
+__device__ __forceinline__ void stage_store(const KArgs& a, int tid, const EpiStage<(TO + WB - 1) / WB>& st, char* img) {
+    constexpr int BN = TO * 16, NQ = (TO + WB - 1) / WB;
+    typedef EpiImage<TO> IM;
+    if (tid < BN) {
+        float* c = reinterpret_cast<float*>(img + IM::kConst);
+        c[tid] = st.c[0];
+        c[BN + tid] = st.c[1];
+        c[2 * BN + tid] = (st.c[4] * kS2inv) * st.c[2];           // exact powers of two first
+        c[3 * BN + tid] = st.c[3];
+    }
+    if (a.h_slab) {
+#pragma unroll
+        for (int u = 0; u < NQ; ++u) {
+            const int s = tid + u * WB * 64;
+            if (s >= TO * 64) continue;
+            const float4 e4 = st.he[u], v4 = st.hv[u];
+            const uint32_t eh0 = cvt_pk_h(e4.x * kHeadES, e4.y * kHeadES), eh1 = cvt_pk_h(e4.z * kHeadES, e4.w * kHeadES);
+            const uint32_t el0 = cvt_pk_h(e4.x * kHeadES - h_lo(eh0), e4.y * kHeadES - h_hi(eh0));
+            const uint32_t el1 = cvt_pk_h(e4.z * kHeadES - h_lo(eh1), e4.w * kHeadES - h_hi(eh1));
+            const uint32_t vh0 = cvt_pk_h(v4.x * kHeadVS, v4.y * kHeadVS), vh1 = cvt_pk_h(v4.z * kHeadVS, v4.w * kHeadVS);
+            uint32_t vl0 = 0, vl1 = 0;
+            if (NPV == 3) {
+                vl0 = cvt_pk_h(v4.x * kHeadVS - h_lo(vh0), v4.y * kHeadVS - h_hi(vh0));
+                vl1 = cvt_pk_h(v4.z * kHeadVS - h_lo(vh1), v4.w * kHeadVS - h_hi(vh1));
+            }
+            reinterpret_cast<uint4*>(img + IM::kHeadE)[s] = make_uint4(eh0, eh1, el0, el1);
+            reinterpret_cast<uint4*>(img + IM::kHeadV)[s] = make_uint4(vh0, vh1, vl0, vl1);
+        }
     }
 }
 
 // Epilogue of a wave's TO x TB accumulator tiles (lane: out[b][o .. o+3] of tile (i, j), o = o0 + 16 i + 4 q, b = brow0 + 16 j).
-// Phase 1: every load (per-feature constants, explicit eps) back to back.  Phase 2 per tile: noise, arithmetic, stores --
+// Phase 1: the explicit eps loads back to back.  Phase 2 per tile row: the row's constants (and head fragments) from the
+//   staged image `img` (EpiImage), then per tile: noise, arithmetic, stores --
 //   fp32 `out` (float4 per lane), sqrt(var) for the backward pass, and the fp16 hi | lo PLANES of the next layer's x: the
 //   lane pair (q, q ^ 1) holds the 8 consecutive k of one 16-B unit pair, v_permlane16_swap_b32 moves the halves so that
 //   the even lane stores the hi unit and the odd lane the lo unit (16 B each, 64 B contiguous per row and tile).
+//   Noise: tile t = i TB + j < NPRE was drawn by the caller ahead of the K loop (`pre`, zeros where the tile is not live);
+//   the others are drawn here -- counter-based Philox gives the same bits wherever it runs.
 //   Head fold (a.h_slab): the NEXT layer is a <= 16-class head (LBBNN-GP-MF-MNF.py:256: l3 on relu(l2)).  Its two moment
 //   products over THIS workgroup's 80 features are formed here, on the matrix cores: the accumulator layout of a 16 x 16
 //   tile (lane (b, q): features 4q..4q+3 of row b) IS the B-operand layout of v_mfma_f32_16x16x16_f16 (k = 4q + r), the A
 //   operand is the head's weight tile (lane (class, q)), both as fp16 hi + lo with 3 + 1 (3) products like the main loop.
 //   Each wave owns its 32 rows, so nothing is reduced across waves: per o tile a slab row of 2 x 16 floats per batch row;
 //   head_finalize_kernel adds the slabs in o-tile order.  Saves the h2 store + re-read and the head's own launch.
-template <int TO, int TB, int NPV>
-__device__ __forceinline__ void epilogue16(const G16Args& a, int o0, int q, int lr, int brow0,
+template <int TO, int TB, int NPV, int NPRE>
+__device__ __forceinline__ void epilogue16(const KArgs& a, int o0, int q, int lr, int brow0, const char* img,
+                                           uint64_t seed, uint64_t offs, const float (&pre)[NPRE > 0 ? NPRE : 1][4],
                                            const floatx4 (&accm)[TO][TB], const floatx4 (&accv)[TO][TB]) {
+    typedef EpiImage<TO> IM;
+    constexpr int BN = TO * 16;
     const bool ovec = ((a.O & 3) == 0) && (!a.out || (((a.ldo & 3) == 0) && ((reinterpret_cast<uintptr_t>(a.out) & 15u) == 0))) &&
                       (!a.eps || (reinterpret_cast<uintptr_t>(a.eps) & 15u) == 0) &&
                       (!a.std_out || (reinterpret_cast<uintptr_t>(a.std_out) & 15u) == 0);
-    uint64_t seed = 0, offs = 0;
-    if (!a.eps) { seed = a.rng[0]; offs = a.rng[1]; }
-    OC16 oc[TO];
-#pragma unroll
-    for (int i = 0; i < TO; ++i) {
-        const int o = o0 + i * 16 + 4 * q;
-        if (o < a.O) {
-            ld4f(a.bias_mean, o, a.O, 0.f, oc[i].bm);
-            ld4f(a.bias_var, o, a.O, 0.f, oc[i].bv);
-            ld4f(a.var_scale, o, a.O, 1.f, oc[i].vs);
-            ld4f(a.mean_scale, o, a.O, 1.f, oc[i].ms);
-            float wv[4];
-            ld4f(a.wvar_scale, o, a.O, 1.f, wv);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) oc[i].vs[r] = (wv[r] * kS2inv) * oc[i].vs[r];      // exact powers of two first
-        }
-    }
     float pe[TO][TB][4];
     if (a.eps) {
 #pragma unroll
@@ -140,18 +204,7 @@ __device__ __forceinline__ void epilogue16(const G16Args& a, int o0, int q, int 
         }
     }
     const bool head = a.h_slab != nullptr;
-    float4 he4[TO], hv4[TO];                              // head fold: this lane's A fragments (class lr, features o .. o+3)
-    if (head) {
-#pragma unroll
-        for (int i = 0; i < TO; ++i) {
-            const int o = o0 + i * 16 + 4 * q;
-            he4[i] = make_float4(0.f, 0.f, 0.f, 0.f); hv4[i] = he4[i];
-            if (lr < a.h_C && o < a.O) {
-                he4[i] = *reinterpret_cast<const float4*>(a.h_e + (size_t)lr * a.h_ld + o);
-                hv4[i] = *reinterpret_cast<const float4*>(a.h_v + (size_t)lr * a.h_ld + o);
-            }
-        }
-    }
+    const float* cst = reinterpret_cast<const float*>(img + IM::kConst);
     __builtin_amdgcn_sched_barrier(0);
     const bool odd = q & 1;
     floatx4 hm[TB], hv[TB];
@@ -161,20 +214,18 @@ __device__ __forceinline__ void epilogue16(const G16Args& a, int o0, int q, int 
     for (int i = 0; i < TO; ++i) {
         const int o = o0 + i * 16 + 4 * q;
         const bool oin = o < a.O;
+        const int fo = i * 16 + 4 * q;
+        const float4 bm = *reinterpret_cast<const float4*>(cst + fo), bv = *reinterpret_cast<const float4*>(cst + BN + fo);
+        const float4 vs = *reinterpret_cast<const float4*>(cst + 2 * BN + fo), ms = *reinterpret_cast<const float4*>(cst + 3 * BN + fo);
+        const float c_bm[4] = {bm.x, bm.y, bm.z, bm.w}, c_bv[4] = {bv.x, bv.y, bv.z, bv.w};
+        const float c_vs[4] = {vs.x, vs.y, vs.z, vs.w}, c_ms[4] = {ms.x, ms.y, ms.z, ms.w};
         f16x4 ehd = {0, 0, 0, 0}, eld = {0, 0, 0, 0}, vhd = {0, 0, 0, 0}, vld = {0, 0, 0, 0};
         if (head) {
-            const float4 e4 = he4[i], v4 = hv4[i];
-            const uint32_t eh0 = cvt_pk_h(e4.x * kHeadES, e4.y * kHeadES), eh1 = cvt_pk_h(e4.z * kHeadES, e4.w * kHeadES);
-            const uint32_t el0 = cvt_pk_h(e4.x * kHeadES - h_lo(eh0), e4.y * kHeadES - h_hi(eh0));
-            const uint32_t el1 = cvt_pk_h(e4.z * kHeadES - h_lo(eh1), e4.w * kHeadES - h_hi(eh1));
-            const uint32_t vh0 = cvt_pk_h(v4.x * kHeadVS, v4.y * kHeadVS), vh1 = cvt_pk_h(v4.z * kHeadVS, v4.w * kHeadVS);
-            ehd = __builtin_bit_cast(f16x4, make_uint2(eh0, eh1)); eld = __builtin_bit_cast(f16x4, make_uint2(el0, el1));
-            vhd = __builtin_bit_cast(f16x4, make_uint2(vh0, vh1));
-            if (NPV == 3) {
-                const uint32_t vl0 = cvt_pk_h(v4.x * kHeadVS - h_lo(vh0), v4.y * kHeadVS - h_hi(vh0));
-                const uint32_t vl1 = cvt_pk_h(v4.z * kHeadVS - h_lo(vh1), v4.w * kHeadVS - h_hi(vh1));
-                vld = __builtin_bit_cast(f16x4, make_uint2(vl0, vl1));
-            }
+            const uint4 ea = reinterpret_cast<const uint4*>(img + IM::kHeadE)[i * 64 + 16 * q + lr];
+            const uint4 va = reinterpret_cast<const uint4*>(img + IM::kHeadV)[i * 64 + 16 * q + lr];
+            ehd = __builtin_bit_cast(f16x4, make_uint2(ea.x, ea.y)); eld = __builtin_bit_cast(f16x4, make_uint2(ea.z, ea.w));
+            vhd = __builtin_bit_cast(f16x4, make_uint2(va.x, va.y));
+            if (NPV == 3) vld = __builtin_bit_cast(f16x4, make_uint2(va.z, va.w));
         }
 #pragma unroll
         for (int j = 0; j < TB; ++j) {
@@ -184,14 +235,17 @@ __device__ __forceinline__ void epilogue16(const G16Args& a, int o0, int q, int 
             if (a.eps) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) e[r] = pe[i][j][r];
+            } else if (i * TB + j < NPRE) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) e[r] = pre[i * TB + j < NPRE ? i * TB + j : 0][r];
             } else if (live) {
                 philox_normal4(seed, offs, a.rng_stream, (uint64_t)(a.row_offset + b), (uint32_t)(o >> 2), e);
             }
             float res[4], sd[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                sd[r] = sqrt_hw(accv[i][j][r] * oc[i].vs[r] + oc[i].bv[r]);
-                const float m = accm[i][j][r] * oc[i].ms[r] + oc[i].bm[r] + sd[r] * e[r];
+                sd[r] = sqrt_hw(accv[i][j][r] * c_vs[r] + c_bv[r]);
+                const float m = accm[i][j][r] * c_ms[r] + c_bm[r] + sd[r] * e[r];
                 res[r] = a.relu ? fmaxf(m, 0.f) : m;
             }
             if (a.out && live) {
@@ -262,29 +316,42 @@ __device__ __forceinline__ void epilogue16(const G16Args& a, int o0, int q, int 
     }
 }
 
+// Accumulator tiles whose noise is drawn in the launch ramp, between the issue of the first step's LDS-DMA and the first
+// barrier (0 .. TO TB; the rest is drawn in the epilogue): 4, by measurement (gemm_f16s_body keeps the numbers).
+// -DLBBNN_G16_NPRE=n overrides it for A/B builds.
+#ifndef LBBNN_G16_NPRE
+#define LBBNN_G16_NPRE 4
+#endif
+constexpr int npre_of(int TO, int TB, int NPV) {               // three variance products leave no registers for it
+    return NPV == 3 ? 0 : (LBBNN_G16_NPRE < TO * TB ? LBBNN_G16_NPRE : TO * TB);
+}
+
 // NPV: products of the variance GEMM (1 or 3).  XPL: x given as fp16 hi | lo planes (else fp32 rows, split in registers).
 template <int TO, int TB, int WB, int NPV, bool XPL>
 __device__ __forceinline__ void gemm_f16s_body(const G16Args& a) {
     static_assert(NPV == 1 || NPV == 3, "one or three variance products");
-    constexpr int BN = TO * 16, BM = TB * WB * 16;
+    constexpr int BN = TO * 16, BM = TB * WB * 16, NPRE = npre_of(TO, TB, NPV);
     // LDS image of one K step: X BM rows x 128 B | E BN rows x 128 B (hi | lo units) | V: BN rows x 128 B (NPV == 3), or
     // BN rows x 64 B = the hi parts alone, a plain fp16 matrix in memory (NPV == 1: a quarter fewer weight bytes per step)
     constexpr int VROW = NPV == 1 ? 64 : 128;
     constexpr int XB = BM * 128, WRB = BN * 128, VRB = BN * VROW, BUFB = XB + WRB + VRB;
     constexpr int NGX = BM / 8, NGW = BN / 8, NGV = VRB / 1024, NG = NGX + NGW + NGV, NPW = (NG + WB - 1) / WB;
     static_assert(VRB % 1024 == 0, "whole 1-KiB pieces");
+    static_assert(EpiImage<TO>::kBytes <= BUFB, "the epilogue's operand image fits one K-step buffer");
     extern __shared__ __attribute__((aligned(16))) char smc[];
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lr = lane & 15, q = lane >> 4;
-    if (a.fin.n > 0 && blockIdx.y == gridDim.y - 1) {                          // the finalize row (uniform per workgroup)
+    if ((int)blockIdx.y >= a.gy) {                                             // the finalize row (uniform per workgroup)
         if (blockIdx.x == 0) kl_finalize_piggy<WB>(kernarg_as<G16Args>()->fin, reinterpret_cast<float*>(smc));
         return;
     }
     int tox, tby;
-    tile_of_block(tox, tby, a.fin.n > 0 ? 1 : 0);
+    tile_of_block(tox, tby, a.gx, a.gy);
     const int o0 = tox * BN, b0 = tby * BM;
+    uint64_t seed = 0, offs = 0;
+    if (!a.eps) { seed = a.rng[0]; offs = a.rng[1]; }
 
     // LDS-DMA through buffer descriptors (see lrt_gemm_bf16x3_body): per-lane byte offsets computed once, the K step
     // advances a scalar offset of 128 B in every region.  fp32 x: lanes past I in the K tail are pointed out of range
@@ -483,8 +550,38 @@ __device__ __forceinline__ void gemm_f16s_body(const G16Args& a) {
     // (The first layer's in-register split of fp32 x on v_fma_mixlo/mixhi_f16 (f16(x - float(h)) in one instruction per
     // element, inline asm: 3 VALU per pair instead of the compiler's 5, bit-identical): forward 0.1240 / 0.1238 / 0.1237 ms
     // against 0.1240 / 0.1237 / 0.1237 -- the 16 instructions per wave-step are not on the chain either; dropped.)
+    // (The launch's K-independent part: epilogue operands staged once per workgroup (EpiImage) and NPRE tiles' noise drawn in
+    // the ramp.  All bit-identical; forward ms, builds in alternating processes, one line per box (profiles/f16_epilogue_ab.txt):
+    //   parent 0.1290 | image loaded AHEAD of the last step's MFMAs and written after them 0.1336 -- the wave issues in order and
+    //     21 more live registers cross the MFMAs: slower than fetching per wave; dropped | loads and writes behind the MFMAs,
+    //     NPRE = 6: 0.1216
+    //   parent 0.1245 | behind the MFMAs, NPRE = 0 / 4 / 6 / 8: 0.1198 / 0.1172 / 0.1189 / 0.1199 (8 spills 3 VGPRs with fp32 x)
+    //   parent 0.1214 | NPRE = 0 / 4: 0.1169 / 0.1166 | the staging as ONE function with every load unconditional (clamped
+    //     index, fill selected afterwards: one round trip instead of three): 0.1192; dropped, the form below is the measured one.
+    // The first step's round trip hides about four tiles' Philox; what is drawn beyond that delays the first MFMA by as much as
+    // the epilogue gains.  Three variance products leave no registers for it (NPRE = 6: 47-52 VGPRs spilled): NPRE = 0 there.)
+    const int brow0 = b0 + wv * TB * 16 + lr;
+    float pre[NPRE > 0 ? NPRE : 1][4];
     dma_step(0, smc);
+    if (NPRE > 0) {
+        // the first pieces are on their round trip and the VALU has nothing else to do: the Philox rounds of the first NPRE
+        // tiles sit ahead of the first barrier (same counters, stream and guards as the epilogue's own draws)
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int t = 0; t < NPRE; ++t) {
+            const int o = o0 + (t / TB) * 16 + 4 * q, b = brow0 + (t % TB) * 16;
+            pre[t][0] = pre[t][1] = pre[t][2] = pre[t][3] = 0.f;
+            if (!a.eps && o < a.O && b < a.B)
+                philox_normal4(seed, offs, a.rng_stream, (uint64_t)(a.row_offset + b), (uint32_t)(o >> 2), pre[t]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
     __syncthreads();
+    // The last step issues no LDS-DMA; the buffer it would have filled is idle (consumed in step nsteps - 2, and with one
+    // step never used): the epilogue's operand image goes there, loads and ds_writes behind the step's MFMAs, published by
+    // the step's own closing s_waitcnt + barrier.  The steps before it run the stream they always ran.
+    char* const img = smc + (nsteps & 1) * BUFB;
+    EpiStage<(TO + WB - 1) / WB> st;
     for (int c = 0; c < nsteps; ++c) {
         read_frags(smc + (c & 1) * BUFB);
         __builtin_amdgcn_sched_barrier(0);
@@ -492,9 +589,13 @@ __device__ __forceinline__ void gemm_f16s_body(const G16Args& a) {
         __builtin_amdgcn_sched_barrier(0);
         mfmas();
         __builtin_amdgcn_sched_barrier(0);
+        if (c + 1 == nsteps) {
+            stage_load<TO, WB>(*kernarg_as<G16Args>(), o0, tid, st);
+            stage_store<TO, WB, NPV>(*kernarg_as<G16Args>(), tid, st, img);
+        }
         __syncthreads();
     }
-    epilogue16<TO, TB, NPV>(a, o0, q, lr, b0 + wv * TB * 16 + lr, accm, accv);
+    epilogue16<TO, TB, NPV, NPRE>(*kernarg_as<G16Args>(), o0, q, lr, brow0, img, seed, offs, pre, accm, accv);
 }
 
 template <int TO, int TB, int WB, int NPV, bool XPL>
@@ -509,6 +610,7 @@ int launch16(G16Args& a, int npv, bool xpl, hipStream_t s, bool* hosted) {
     const long nblocks = (long)grid.x * grid.y;
     const size_t lds = lds_request(2u * (BM * 128 + BN * 128 + BN * (npv == 1 ? 64 : 128)), nblocks);
     const int fin_n = a.fin.n;
+    a.gx = (int)grid.x; a.gy = (int)grid.y;
     a.fin.n = 0;
     if (fin_n > 0 && hosted) {
         a.fin.n = fin_n;
