@@ -340,6 +340,15 @@ class EvalScoresArgs(ctypes.Structure):
                 ("pit_bins", c_i), ("n_levels", c_i), ("levels", ctypes.c_float * SCORE_MAX_LEVELS)]
 
 
+STRUCTURE_MAX_LAYERS = 16             # LBBNN_STRUCTURE_MAX_LAYERS: layers per lbbnn_gate_structure call (= MAX_DEPTH)
+STRUCTURE_MAX_WIDTH = 4096             # LBBNN_STRUCTURE_MAX_WIDTH: units per boundary
+
+
+class StructureDesc(ctypes.Structure):
+    """lbbnn_structure_desc_t"""
+    _fields_ = [("lambdal", c_p), ("O", c_i), ("I", c_i), ("ld", c_i), ("layer_id", c_u32)]
+
+
 # name -> (restype, argtypes); must list every symbol include/lbbnn.h declares
 SIGNATURES = {
     "lbbnn_abi_version": (c_i, []),
@@ -474,6 +483,8 @@ SIGNATURES = {
                                                c_p]),
     "lbbnn_elbo_gaussian_loss_backward": (c_i, [c_p, c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, ctypes.c_float, c_p, c_p, c_p, c_p,
                                                 c_p]),
+    "lbbnn_gate_structure_width": (c_i64, [ctypes.POINTER(StructureDesc), c_i]),
+    "lbbnn_gate_structure": (c_i, [ctypes.POINTER(StructureDesc), c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
 }
 
 _lib = None

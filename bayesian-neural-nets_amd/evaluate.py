@@ -36,6 +36,10 @@ models; ``ensemble_regression`` / ``RegressionAccumulator`` (lbbnn_eval_regressi
 and aleatoric variance, mixture log density, PIT -- and the classification tools refuse such a model.  ``ensemble_scores`` /
 ``RegressionScoreAccumulator`` / ``predict_regression`` (lbbnn_eval_regression_scores) are the same for a noise level per element
 or per member -- e.g. a network whose outputs carry their own log-variances -- plus the CRPS and prediction intervals.
+
+``structure_posterior`` (lbbnn_gate_structure) samples the posterior over the sparse architectures of an LRT, MNF or baseline
+network: per sample the hard gates of every layer and ``live_structure``'s sweep in one launch -- kept and active-path weights,
+needed units, and how often each input feature and hidden unit lies on an active path to some output.
 """
 import math
 from typing import Dict, List, Optional, Tuple
@@ -2058,6 +2062,86 @@ def live_structure(keep_masks, align: int = 8):
     (8: what the member GEMM, in_features % 4, and the bf16 hi | lo kernels, in_features % 8, take)."""
     need, live, _ = _live_structure(keep_masks, align)
     return need, live
+
+
+# ----------------------------------------------------------------------------------------- posterior over structures
+@torch.no_grad()
+def structure_posterior(net, samples: int = 1000, *, rng: Optional[torch.Tensor] = None, max_members: Optional[int] = None,
+                        keep_need: bool = False) -> Dict[str, object]:
+    """The posterior over the sparse architectures of a latent-binary network (LRT, MNF or baseline, any depth), from
+    ``samples`` draws of every gate matrix: ONE lbbnn_gate_structure launch per chunk of at most ``max_members`` samples
+    (default: all) draws gamma ~ Bernoulli(sigmoid(lambdal)) from Philox and runs ``live_structure``'s sweep on it without
+    storing a gate.  A network of n layers has n + 1 boundaries (0 = the input features, n = the outputs).  Device tensors:
+
+    ``kept`` (S, n) int32: the gates drawn 1 per layer; ``needed`` (S, n + 1) int32: the units of each boundary some output
+    depends on; ``active_kept`` (S, n) int32: the kept weights of needed rows (their columns are needed by construction);
+    ``density`` / ``active_density`` (S,) fp64: their sums over the layers divided by all weights (``density[s]`` is the
+    ``density[i]`` of the reference's ``test_ensemble``); ``feature_count`` (I0,) int32 and ``feature_prob`` = count / S: how
+    often an input feature lies on an active path to some output; ``unit_count`` / ``unit_prob``: the same per hidden
+    boundary (a list, empty for one layer); with ``keep_need``: ``need``, per boundary the (S, width) bool masks.
+
+    Sample s draws at Philox offset (live offset + s) with the gate stream of each layer, and the live offset advances by
+    ``samples`` -- what ``base_ensemble`` does: for a baseline network with hard gates (``layer.gamma.exact``) these are the
+    structures of the very members ``base_ensemble(net, x, samples)`` draws from the same state.  ``rng``: an explicit
+    {seed, offset} int64 device tensor to draw from instead; nothing is advanced then.  Chunked and unchunked calls give the
+    same bits.  No host read: with ``rng`` the call can be captured in a HIP graph.  Layers are at most 4096 wide."""
+    from . import _lib, layers as L
+    if _is_frozen(net):
+        raise ValueError("bnn_amd: structure_posterior draws the gates of a live network; a frozen model has fixed its gates "
+                         "(its structure is net.density / evaluate.live_structure)")
+    if _is_vd(net):
+        raise ValueError("bnn_amd: structure_posterior takes a latent-binary network (LRT, MNF or baseline); a "
+                         "variational-dropout network has no gates")
+    if not (_is_base(net) or isinstance(net, L._NetworkBase)):
+        raise ValueError("bnn_amd: structure_posterior takes an LRT, MNF or baseline LBBNN network, got %s" % type(net).__name__)
+    S, chunk = _member_counts(samples, max_members)
+    chunk = min(chunk, 65535)
+    layers = net._layers()
+    n = len(layers)
+    for i, l in enumerate(layers):
+        if max(l.in_features, l.out_features) > _lib.STRUCTURE_MAX_WIDTH:
+            raise ValueError("bnn_amd: layer %d is %d x %d: structure_posterior takes layers of at most %d units a side"
+                             % (i + 1, l.out_features, l.in_features, _lib.STRUCTURE_MAX_WIDTH))
+    lams = [l.lambdal.detach() for l in layers]
+    dev = lams[0].device
+    if not all(t.is_cuda for t in lams):
+        raise RuntimeError("bnn_amd: structure_posterior needs the network on a HIP device (lambdal is on %s); there is no CPU path"
+                           % dev)
+    if rng is not None and (not rng.is_cuda or rng.dtype != torch.int64 or rng.numel() < 2 or not rng.is_contiguous()):
+        raise RuntimeError("bnn_amd: rng must be a contiguous int64 {seed, offset} tensor on a HIP device; there is no CPU path")
+    descs, width = ops.structure_descs(lams, [int(l._layer_id) for l in layers])
+    widths = [layers[0].in_features] + [l.out_features for l in layers]
+    if width != sum(widths):
+        raise ValueError("bnn_amd: structure_posterior: the layers do not chain (widths %s)" % (widths,))
+    i32 = dict(dtype=torch.int32, device=dev)
+    kept, needed, active = torch.empty((S, n), **i32), torch.empty((S, n + 1), **i32), torch.empty((S, n), **i32)
+    feature_count = torch.zeros(widths[0], **i32)
+    unit_count = torch.zeros(sum(widths[1:-1]), **i32) if n > 1 else None
+    need_out = torch.empty((S, width), dtype=torch.uint8, device=dev) if keep_need else None
+    st = ops.RngState.get(dev) if rng is None else None
+    # an explicit state and more than one chunk: a copy walks the chunks' offsets, the caller's tensor stays as it is
+    state = st.t if st is not None else (rng if chunk >= S else rng[:2].clone())
+    for m0 in range(0, S, chunk):
+        c = min(chunk, S - m0)
+        ops.gate_structure(descs, n, c, state, kept=kept[m0:m0 + c], needed=needed[m0:m0 + c], active=active[m0:m0 + c],
+                           feature_count=feature_count, unit_count=unit_count,
+                           need_out=need_out[m0:m0 + c] if keep_need else None)
+        if st is not None:
+            st.advance(c)
+        elif m0 + c < S:
+            _lib.check(_lib.lib().lbbnn_rng_advance(state.data_ptr(), c, ops._stream()), "lbbnn_rng_advance")
+    # divisors as device tensors: a true fp64 division (by a Python scalar torch multiplies with the rounded reciprocal)
+    weights = torch.full((), float(sum(l.in_features * l.out_features for l in layers)), dtype=torch.float64, device=dev)
+    count = torch.full((), float(S), dtype=torch.float64, device=dev)
+    bounds = [sum(widths[:b]) for b in range(n + 2)]
+    hidden = [unit_count[bounds[b] - widths[0]:bounds[b + 1] - widths[0]] for b in range(1, n)]
+    res = {"kept": kept, "needed": needed, "active_kept": active,
+           "density": kept.sum(1, dtype=torch.float64) / weights, "active_density": active.sum(1, dtype=torch.float64) / weights,
+           "feature_count": feature_count, "feature_prob": feature_count.double() / count,
+           "unit_count": hidden, "unit_prob": [h.double() / count for h in hidden]}
+    if keep_need:
+        res["need"] = [need_out[:, bounds[b]:bounds[b + 1]].bool() for b in range(n + 1)]
+    return res
 
 
 class CompactFrozenNetwork(FrozenNetwork):

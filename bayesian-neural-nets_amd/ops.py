@@ -1093,6 +1093,38 @@ def sigmoid_backward(g: torch.Tensor, probs: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def structure_descs(lambdals: Sequence[torch.Tensor], layer_ids: Sequence[int]):
+    """The lbbnn_structure_desc_t array of a chain of (O, I) fp32 lambdal tensors with dense rows (first layer first), and the
+    width lbbnn_gate_structure_width gives it (0: the call would refuse these layers)."""
+    n = len(lambdals)
+    descs = (_lib.StructureDesc * max(n, 1))()
+    for d, lam, lid in zip(descs, lambdals, layer_ids):
+        d.lambdal = _ptr_rows(lam, "lambdal")
+        d.O, d.I, d.ld, d.layer_id = lam.shape[0], lam.shape[1], (lam.stride(0) if lam.shape[0] > 1 else lam.shape[1]), int(lid)
+    return descs, int(_lib.lib().lbbnn_gate_structure_width(descs, n))
+
+
+def gate_structure(descs, n: int, samples: int, rng: torch.Tensor, *, kept, needed, active, feature_count, unit_count=None,
+                   need_out=None):
+    """lbbnn_gate_structure on caller-allocated int32 outputs: kept / active (samples, n), needed (samples, n + 1) are written;
+    feature_count (I0,) and unit_count (hidden widths, concatenated; nullable) are ADDED TO; need_out: nullable uint8
+    (samples, width).  Sample s draws at Philox offset rng[1] + s; the caller advances the state."""
+    for name, t, dt in (("kept", kept, torch.int32), ("needed", needed, torch.int32), ("active", active, torch.int32),
+                        ("feature_count", feature_count, torch.int32), ("unit_count", unit_count, torch.int32),
+                        ("need_out", need_out, torch.uint8)):
+        if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous()):
+            raise RuntimeError("bnn_amd: %s must be a contiguous %s tensor on a HIP device (no CPU path)" % (name, dt))
+    if kept.numel() < samples * n or active.numel() < samples * n or needed.numel() < samples * (n + 1):
+        raise ValueError("bnn_amd: gate_structure outputs are smaller than (samples, layers)")
+    widths = [descs[0].I] + [descs[l].O for l in range(n)]
+    if (feature_count.numel() < widths[0] or (unit_count is not None and unit_count.numel() < sum(widths[1:-1]))
+            or (need_out is not None and need_out.numel() < samples * sum(widths))):
+        raise ValueError("bnn_amd: gate_structure totals / need_out are smaller than the network's boundaries %s" % (widths,))
+    p = lambda t: None if t is None else t.data_ptr()
+    _lib.check(_lib.lib().lbbnn_gate_structure(descs, n, samples, rng.data_ptr(), p(kept), p(needed), p(active),
+                                               p(feature_count), p(unit_count), p(need_out), _stream()), "lbbnn_gate_structure")
+
+
 # ----------------------------------------------------------------------------------------- workspaces
 class LayerWorkspace:
     """Caller-owned device buffers of one layer, allocated once and reused every forward

@@ -1812,6 +1812,46 @@ typedef struct lbbnn_eval_scores_args {
 int64_t lbbnn_eval_regression_scores_work_bytes(int S, int B, int O, int levels);
 int lbbnn_eval_regression_scores(const lbbnn_eval_scores_args_t* args, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * lbbnn_gate_structure: the posterior over the STRUCTURES of a latent-binary network -- per sample the hard gates of every layer
+ * are drawn and the units some output depends on are found (evaluate.live_structure's sweep), in ONE launch for the whole
+ * network and all samples, without storing a gate.  Integers only: every output is exact and the same bits on every run.
+ *
+ * layers[l], l < n: lambdal (O, I) with rows ld floats apart, and the layer's Philox id.  Boundary b of the network, b = 0 .. n:
+ * 0 = the input features (width layers[0].I), b = the outputs of layer b - 1 (width layers[b - 1].O).  For sample s < samples:
+ *   gamma_l[o][i] = u < alpha, alpha = 1 / (1 + expf(-lambdal[o][i])) in fp32 (the device's expf), u = ((bits >> 8) + 0.5) 2^-24
+ *     from word i % 4 of Philox counter (o, i / 4) of stream LBBNN_STREAM_GATE * 64 + layer_id at state {rng[0], rng[1] + s}: the
+ *     hard draw of lbbnn_gate_sample_draw / lbbnn_gate_members (exact bit 8), bit for bit.  A NaN lambdal is never kept.
+ *   need[n][o] = 1;  need[l][i] = any_o(need[l + 1][o] & gamma_l[o][i])
+ *   kept[s * n + l]         = sum_{o,i} gamma_l[o][i]                    (every weight is drawn, needed row or not)
+ *   needed[s * (n + 1) + b] = sum_j need[b][j]
+ *   active[s * n + l]       = sum_{o : need[l + 1][o]} sum_i gamma_l[o][i]   (such a weight's column is needed by construction)
+ *   need_out (nullable): [samples][width] uint8 in {0, 1}, width = lbbnn_gate_structure_width(layers, n) = the widths of all
+ *     n + 1 boundaries; boundary b of sample s starts at s * width + (the widths of boundaries 0 .. b - 1).
+ * Totals over the samples, ADDED TO (integer atomics; the caller zeroes them, so chunks of samples accumulate):
+ *   feature_count[i] += sum_s need[0][i];  unit_count (nullable): the hidden boundaries 1 .. n - 1 one after the other,
+ *   unit_count[(widths of boundaries 1 .. b - 1) + j] += sum_s need[b][j].
+ * The caller advances rng afterwards (by `samples`).  Nothing is read back or allocated: the call can be captured in a graph.
+ *
+ * Checks, before anything is launched, in this order: layers / kept / needed / active / feature_count NULL: LBBNN_E_NULL; n
+ * outside 1 .. LBBNN_STRUCTURE_MAX_LAYERS, samples outside 1 .. 65535: LBBNN_E_SHAPE; per layer a NULL lambdal: LBBNN_E_NULL, O
+ * or I outside 1 .. LBBNN_STRUCTURE_MAX_WIDTH, ld < I, I != the O of the layer below: LBBNN_E_SHAPE, lambdal off a 4-B
+ * boundary: LBBNN_E_ALIGN; an output off a 4-B boundary: LBBNN_E_ALIGN; rng NULL: LBBNN_E_NOISE.  lambdal rows are read as
+ * float4 when I % 4 == 0, ld % 4 == 0 and the base is 16-B aligned, element by element otherwise.
+ * lbbnn_gate_structure_width: the width above, or 0 for layers the call would refuse. */
+#define LBBNN_STRUCTURE_MAX_LAYERS 16
+#define LBBNN_STRUCTURE_MAX_WIDTH 4096
+typedef struct lbbnn_structure_desc {
+    const float* lambdal;
+    int O, I, ld;
+    uint32_t layer_id;
+} lbbnn_structure_desc_t;
+
+int64_t lbbnn_gate_structure_width(const lbbnn_structure_desc_t* layers, int n);
+int lbbnn_gate_structure(const lbbnn_structure_desc_t* layers, int n, int samples, const uint64_t* rng,
+                         int32_t* kept, int32_t* needed, int32_t* active, int32_t* feature_count, int32_t* unit_count,
+                         uint8_t* need_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
