@@ -349,6 +349,20 @@ class StructureDesc(ctypes.Structure):
     _fields_ = [("lambdal", c_p), ("O", c_i), ("I", c_i), ("ld", c_i), ("layer_id", c_u32)]
 
 
+EXPLAIN_SEED, EXPLAIN_MASK, EXPLAIN_FINISH = 0, 1, 2    # LBBNN_EXPLAIN_*: the modes of lbbnn_explain_step
+EXPLAIN_MAX_OUTPUTS = 16               # LBBNN_EXPLAIN_MAX_OUTPUTS: rows of G per input row
+EXPLAIN_MAX_ROWS = 1 << 24             # LBBNN_EXPLAIN_MAX_ROWS: B * C'
+
+
+class ExplainStepArgs(ctypes.Structure):
+    """lbbnn_explain_step_args_t"""
+    _fields_ = [("mode", c_i), ("B", c_i), ("C", c_i), ("width", c_i), ("g", c_p), ("ldg", c_i64), ("w", c_p), ("ldw", c_i64),
+                ("w_rows", c_i), ("targets", c_p), ("h", c_p), ("ldh", c_i64), ("bias", c_p), ("bias_out", c_p),
+                ("intercept", c_p), ("active", c_p), ("ld_active", c_i64), ("mask_out", c_p), ("ldm", c_i64),
+                ("logits", c_p), ("ldl", c_i64), ("map", c_p), ("full_width", c_i), ("contributions", c_p), ("ldc", c_i64),
+                ("residual", c_p)]
+
+
 # name -> (restype, argtypes); must list every symbol include/lbbnn.h declares
 SIGNATURES = {
     "lbbnn_abi_version": (c_i, []),
@@ -485,6 +499,10 @@ SIGNATURES = {
                                                 c_p]),
     "lbbnn_gate_structure_width": (c_i64, [ctypes.POINTER(StructureDesc), c_i]),
     "lbbnn_gate_structure": (c_i, [ctypes.POINTER(StructureDesc), c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "lbbnn_explain_step": (c_i, [ctypes.POINTER(ExplainStepArgs), c_p]),
+    "lbbnn_explain_work_bytes": (c_i64, [c_i, c_i, c_i]),
+    "lbbnn_explain_totals": (c_i, [c_p, c_i64, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "lbbnn_explain_operand": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),
 }
 
 _lib = None

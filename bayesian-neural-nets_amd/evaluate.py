@@ -40,6 +40,11 @@ or per member -- e.g. a network whose outputs carry their own log-variances -- p
 ``structure_posterior`` (lbbnn_gate_structure) samples the posterior over the sparse architectures of an LRT, MNF or baseline
 network: per sample the hard gates of every layer and ``live_structure``'s sweep in one launch -- kept and active-path weights,
 needed units, and how often each input feature and hidden unit lies on an active path to some output.
+
+``explain`` (lbbnn_explain_step between mean-only GEMMs) answers the local question for a frozen LRT / MNF model: its
+posterior-mean forward is a ReLU chain on fixed operands, so per row the pre-head output is exactly linear in the input, and the
+call returns every input's contribution ``J[b, c, i] * x[b, i]``, the bias path and a residual that ties them to the logits;
+``ExplanationAccumulator`` / ``explain_batches`` (lbbnn_explain_totals) average them over a pass on the device.
 """
 import math
 from typing import Dict, List, Optional, Tuple
@@ -1634,6 +1639,7 @@ class FrozenNetwork(_FrozenModel):
         self._row_offsets, self._T = [], []
         self._members_ok = True
         self._mcap, self._zbuf, self._ewm = 0, None, []
+        self._xops = None              # explain's fp32 operands of this snapshot (LRT; made on first use)
 
     def _device(self):
         return self._buf("e0", 0).device
@@ -1691,6 +1697,7 @@ class FrozenNetwork(_FrozenModel):
         self._zt = [self._dense_transforms(i, kind) for i, kind in enumerate(self._zflow_kinds)]
         self._maps = self._compact_maps()
         self._mcap, self._zbuf, self._ewm = 0, None, []
+        self._xops = None
 
     def _snapshot(self, layers):
         return self.refresh()
@@ -1791,6 +1798,7 @@ class FrozenNetwork(_FrozenModel):
                                % (dev, layers[0].weight_mu.device))
         self._layer_ids = [int(l._layer_id) for l in layers]
         self._row_offsets = [int(l.row_offset) for l in layers]
+        self._xops = None                                    # explain's operands belong to the old snapshot
         dst, src = self._z_copies(layers)
         dst += [self._buf("bias_mu", i) for i in range(self.n_layers)]
         src += [l.bias_mu.detach() for l in layers]
@@ -1895,6 +1903,47 @@ class FrozenNetwork(_FrozenModel):
         if self.head == "identity":
             return h
         return h if self.dims[-1] <= 16 else torch.log_softmax(h, dim=1)
+
+    def _chain_keep(self, x, st, e_ws):
+        """``_chain``'s posterior-mean forward for ``evaluate.explain``: the same lbbnn_lrt_gemm calls on the same operands,
+        with the hidden activations kept and the last layer left before the head -- (logits, [h_1 .. h_{L-1}]).  The hidden
+        layers are the bits ``_chain`` computes; the logits are what ``head="identity"`` returns."""
+        h, n, hs = x, self.n_layers, []
+        for i in range(n):
+            O, I = self.dims[i + 1], self.dims[i]
+            last = i == n - 1
+            h = ops.lrt_gemm(h, e_ws[i], self._buf("var_w", i), I=I, O=O, bias_mean=self._buf("bias_mu", i),
+                             bias_var=self._buf("bias_var", i), rng=st.t, rng_stream=ops.STREAM_EPS_OUT * 64 + self._layer_ids[i],
+                             row_offset=self._row_offsets[i], relu=not last, mean_only=True, log_softmax=False,
+                             split=self._split[i], single=False)
+            if not last:
+                hs.append(h)
+        return h, hs
+
+    def _explain_operands(self, e_ws, stream):
+        """What the sweep of ``evaluate.explain`` multiplies by, per layer: ``rows`` -- the mean operand the forward read, as
+        fp32 rows [O][operand_ld(I)] (an fp32 operand is used where it lies; a bf16 hi | lo operand becomes hi + lo, exact in
+        fp32: lbbnn_explain_operand) -- and ``wt`` -- its transpose as an fp32 GEMM operand [I][operand_ld(O)]
+        (lbbnn_transpose_operand; None for the last layer, whose rows seed the sweep).  An LRT model keeps them until the next
+        snapshot (``refresh``, ``.to()``); an MNF model's operands carry this call's z and are made per call."""
+        from . import _lib
+        keep = self.family == "lrt"
+        if keep and self._xops is not None:
+            return self._xops
+        rows, wts = [], []
+        for i in range(self.n_layers):
+            O, I = self.dims[i + 1], self.dims[i]
+            ld = ops.operand_ld(I)
+            w = e_ws[i]
+            if self._split[i]:
+                w32 = _empty((O, ld), dtype=torch.float32, device=w.device)
+                _lib.check(_lib.lib().lbbnn_explain_operand(w.data_ptr(), O, I, ld, w32.data_ptr(), stream), "lbbnn_explain_operand")
+                w = w32
+            rows.append(w)
+            wts.append(ops.transpose_operand(w[:, :I]) if i < self.n_layers - 1 else None)
+        if keep:
+            self._xops = (rows, wts)
+        return rows, wts
 
     @torch.no_grad()
     def ensemble(self, data: torch.Tensor, samples: int = 10, *, max_members: Optional[int] = None,
@@ -2572,3 +2621,271 @@ def freeze_base(net, gates: str = "sample", *, threshold: float = 0.5, compact: 
     fz = FrozenBaseNetwork(net.dims, gates, threshold, device=dev, head=net.head, live=live, needed=needed)
     fz.eval()
     return fz._bind(net, need, masks)
+
+
+# ----------------------------------------------------------------------------------------- local explanations
+def _check_explainable(fz):
+    """``explain`` takes a FrozenNetwork of family LRT or planar MNF; everything else is refused with what to use instead."""
+    from . import layers as L
+    if isinstance(fz, FrozenBaseNetwork) or _is_base(fz):
+        raise TypeError("bnn_amd: explain is not built for the baseline family (its frozen model draws its weights per member); "
+                        "explain an LRT / MNF network: evaluate.explain(evaluate.freeze(net, \"mpm\"), data)")
+    if _is_vd(fz):
+        raise TypeError("bnn_amd: explain takes a frozen LRT / MNF model; a variational-dropout network has no gates and no frozen "
+                        "model -- train an lrt.BayesianNetwork and use evaluate.explain(evaluate.freeze(net, \"mpm\"), data)")
+    if isinstance(fz, L._NetworkBase):
+        raise TypeError("bnn_amd: explain takes a frozen model, not the network itself: evaluate.explain(evaluate.freeze(net, "
+                        "\"mpm\"), data) (or gates=\"alpha\" for the gates as trained)")
+    if not isinstance(fz, FrozenNetwork):
+        raise TypeError("bnn_amd: explain takes a FrozenNetwork (evaluate.freeze(net, \"alpha\" | \"mpm\")), got %s"
+                        % type(fz).__name__)
+    if fz.flows == "dense":
+        raise ValueError("bnn_amd: explain is not built for dense=True models (RNVP / MNF-type z flows); use planar z flows "
+                         "(mnf.BayesianNetwork(..., z_flow_type=\"Planar\")) or an LRT network")
+
+
+def _check_explain_rows(B: int, Cp: int):
+    from . import _lib
+    if B * Cp > _lib.EXPLAIN_MAX_ROWS:
+        raise ValueError("bnn_amd: explain takes at most 2**24 rows of (batch x explained outputs) per call, got %d x %d; split "
+                         "the batch" % (B, Cp))
+
+
+def _explain_step(a, what, stream):
+    import ctypes
+    from . import _lib
+    _lib.check(_lib.lib().lbbnn_explain_step(ctypes.byref(a), stream), "lbbnn_explain_step (%s)" % what)
+
+
+@torch.no_grad()
+def explain(fz, data: torch.Tensor, *, targets=None, keep_masks: bool = False, acc=None) -> Dict[str, object]:
+    """Which inputs drove which output of the frozen posterior-mean forward ``fz(data, sample=False)``, row by row.  That
+    forward is a ReLU chain on fixed operands, so its pre-head output is exactly ``logits[b, c] = sum_i J[b, c, i] x[b, i] +
+    k[b, c]`` with ``J(b) = W_L D_{L-1}(b) .. D_1(b) W_1``; this computes the terms of that sum on the device.
+
+    ``fz``: a ``FrozenNetwork`` (LRT or planar MNF, gates "alpha" or "mpm", full or compact, any head, 1 to 16 layers).
+    ``targets``: None -- every output (C' = C, needs C <= 16); a (B,) int64 device tensor -- one output per row (C' = 1; a value
+    outside [0, C) raises IndexError, found by one host read); ``"pred"`` -- the row's largest logit, taken on the device.
+    Returns device tensors: ``logits`` (B, C), the last layer before the head; ``contributions`` (B, C', full_dims[0]) =
+    J * x at the network's own feature index (a compact model's dropped features are exactly 0.0); ``intercept`` (B, C'), the
+    bias path b_L + sum_l <G_l D_l, b_l>, computed on its own; ``residual`` (B, C') = logits - (sum_i contributions +
+    intercept), the caller's self-check; ``active`` (B, L - 1) int32, hidden units with h_l > 0; ``targets`` (None, or the (B,)
+    tensor in force); with ``keep_masks`` ``masks``, per hidden layer a (B, O_l) bool tensor of h_l > 0 (a compact model: its
+    own units); an MNF model: ``z``, per layer the (in_features,) z this call drew.
+    An MNF model draws one z per layer at the live Philox offset and advances it by 1, as ``fz(data)`` does; an LRT model
+    draws nothing.  The masks are h_l > 0 of the very forward that produced ``logits``.  The sweep is fp32 whatever the model's
+    precision: its operands are the values the forward's products multiplied by (``FrozenNetwork._explain_operands``).
+    ``acc``: an ``ExplanationAccumulator`` that takes this batch in the same call."""
+    import ctypes
+    from . import _lib
+    _check_explainable(fz)
+    if not isinstance(data, torch.Tensor):
+        raise TypeError("bnn_amd: explain takes a device tensor of input rows, got %s" % type(data).__name__)
+    if not data.is_cuda:
+        raise ValueError("bnn_amd: explain runs on the HIP device (data is on %s); there is no CPU path -- move it with "
+                         "data.to(device)" % data.device)
+    if fz._src[0] is None:
+        raise ValueError("bnn_amd: this FrozenNetwork is not bound to a network; build it with evaluate.freeze(net)")
+    n, C, F = fz.n_layers, fz.dims[-1], fz.full_dims[0]
+    x = fz._input(data)
+    B, dev = x.shape[0], x.device
+    pred = isinstance(targets, str)
+    if pred and targets != "pred":
+        raise ValueError("bnn_amd: targets must be None, \"pred\" or a (B,) int64 device tensor, got %r" % (targets,))
+    if targets is None:
+        if C > _lib.EXPLAIN_MAX_OUTPUTS:
+            raise ValueError("bnn_amd: explaining every output takes at most %d outputs, this model has %d; pass targets= (one "
+                             "output per row, e.g. targets=\"pred\")" % (_lib.EXPLAIN_MAX_OUTPUTS, C))
+        Cp = C
+    else:
+        Cp = 1
+        if not pred:
+            if not isinstance(targets, torch.Tensor) or targets.dtype != torch.int64 or tuple(targets.shape) != (B,):
+                raise ValueError("bnn_amd: targets must be a (%d,) int64 tensor (one output per row)" % B)
+            if targets.device != dev:
+                raise ValueError("bnn_amd: targets is on %s, the model on %s; move it with targets.to(device)" % (targets.device, dev))
+            targets = targets.contiguous()
+            if B and bool(((targets < 0) | (targets >= C)).any()):
+                raise IndexError("bnn_amd: a target lies outside [0, %d)" % C)
+    _check_explain_rows(B, Cp)
+    f = dict(dtype=torch.float32, device=dev)
+    st = ops.RngState.get(dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        zs = None
+        if fz.family == "mnf":
+            zbuf, ewm = fz._draw_members(1, st.t, stream)
+            e_ws = [e[0] for e in ewm]
+            zs = [z[0] for z in fz._z_of(zbuf, 1)]
+        else:
+            e_ws = [fz._buf("e_w", i) for i in range(n)]
+        if B == 0:
+            if zs is not None:
+                st.advance(1)
+            res = dict(logits=torch.zeros((0, C), **f), contributions=torch.zeros((0, Cp, F), **f),
+                       intercept=torch.zeros((0, Cp), **f), residual=torch.zeros((0, Cp), **f),
+                       active=torch.zeros((0, n - 1), dtype=torch.int32, device=dev),
+                       targets=torch.zeros(0, dtype=torch.int64, device=dev) if targets is not None else None)
+            if keep_masks:
+                res["masks"] = [torch.zeros((0, fz.dims[i + 1]), dtype=torch.bool, device=dev) for i in range(n - 1)]
+            if zs is not None:
+                res["z"] = zs
+            if acc is not None:
+                acc.update(res)
+            return res
+        logits, hs = fz._chain_keep(x, st, e_ws)
+        if zs is not None:
+            st.advance(1)
+        if pred:
+            targets = torch.argmax(logits, dim=1)
+        rows, wts = fz._explain_operands(e_ws, stream)
+        R = B * Cp
+        intercept, residual = _empty((B, Cp), **f), _empty((B, Cp), **f)
+        active = _empty((B, n - 1), dtype=torch.int32, device=dev)
+        masks = [_empty((B, fz.dims[i + 1]), dtype=torch.bool, device=dev) for i in range(n - 1)] if keep_masks else None
+        scatter = fz.compact and not fz._input_identity
+        contributions = torch.zeros((B, Cp, F), **f) if scatter else _empty((B, Cp, F), **f)
+        a = _lib.ExplainStepArgs()
+        a.B, a.C, a.w_rows = B, Cp, C
+        a.targets = targets.data_ptr() if targets is not None else None
+        a.intercept = intercept.data_ptr()
+        g = None
+        for l in range(n - 2, -1, -1):                       # hidden layer l: h_l = hs[l], width dims[l + 1]
+            width = fz.dims[l + 1]
+            h = hs[l]
+            if g is None:                                    # seed: the last layer's rows, no product
+                g = _empty((R, ops.pad4(width)), **f)
+                a.mode, a.w, a.ldw, a.bias_out = _lib.EXPLAIN_SEED, rows[n - 1].data_ptr(), rows[n - 1].stride(0), \
+                    fz._buf("bias_mu", n - 1).data_ptr()
+            else:                                            # G_l = (G_{l+1} W_{l+1}) D_l
+                g = ops.lrt_gemm(g[:, :fz.dims[l + 2]], wts[l + 1], None, I=fz.dims[l + 2], O=width, mean_only=True,
+                                 out=_empty((R, ops.pad4(width)), **f)[:, :width])
+                a.mode, a.w, a.bias_out = _lib.EXPLAIN_MASK, None, None
+            a.width, a.g, a.ldg = width, g.data_ptr(), g.stride(0)
+            a.h, a.ldh, a.bias = h.data_ptr(), h.stride(0), fz._buf("bias_mu", l).data_ptr()
+            a.active, a.ld_active = active.data_ptr() + 4 * l, n - 1
+            a.mask_out, a.ldm = (masks[l].data_ptr(), masks[l].stride(0)) if keep_masks else (None, 0)
+            _explain_step(a, "seed" if a.mode == _lib.EXPLAIN_SEED else "mask", stream)
+        width = fz.dims[0]
+        if g is not None:
+            g = ops.lrt_gemm(g[:, :fz.dims[1]], wts[0], None, I=fz.dims[1], O=width, mean_only=True,
+                             out=_empty((R, ops.pad4(width)), **f)[:, :width])
+            a.g, a.ldg, a.w, a.bias_out = g.data_ptr(), g.stride(0), None, None
+        else:                                                # one layer: J is the rows of W_1, the intercept its bias
+            a.g, a.ldg = None, 0
+            a.w, a.ldw, a.bias_out = rows[0].data_ptr(), rows[0].stride(0), fz._buf("bias_mu", 0).data_ptr()
+        a.mode, a.width = _lib.EXPLAIN_FINISH, width
+        a.h, a.ldh, a.bias = x.data_ptr(), x.stride(0) if B > 1 else max(x.stride(0), width), None
+        a.active, a.mask_out = None, None
+        a.logits, a.ldl = logits.data_ptr(), logits.stride(0) if B > 1 else C
+        a.map, a.full_width = (fz._buf("live", 0).data_ptr() if scatter else None), F
+        a.contributions, a.ldc, a.residual = contributions.data_ptr(), F, residual.data_ptr()
+        _explain_step(a, "finish", stream)
+        res = dict(logits=logits, contributions=contributions, intercept=intercept, residual=residual, active=active,
+                   targets=targets)
+        if keep_masks:
+            res["masks"] = masks
+        if zs is not None:
+            res["z"] = zs
+        if acc is not None:
+            acc.update(res)
+    return res
+
+
+def _explanation_means(rows, total, abs_total):
+    """(mean_contribution, mean_abs_contribution) of an ExplanationAccumulator from its totals: each output's sums over its
+    rows; NaN for an output no row was counted for."""
+    import numpy as np
+    rows = np.asarray(rows, dtype=np.int64)
+    den = np.where(rows > 0, rows, 1).astype(np.float64)[:, None]
+    nan = np.where(rows > 0, 0.0, np.nan)[:, None]
+    return np.asarray(total, dtype=np.float64) / den + nan, np.asarray(abs_total, dtype=np.float64) / den + nan
+
+
+class ExplanationAccumulator:
+    """Running totals of ``explain`` over an evaluation pass, kept on the device: per output the number of explained rows and
+    the fp64 sums of the contributions and of their absolute values per input feature.  ``update`` adds a batch with no host
+    read (lbbnn_explain_totals: per-workgroup fp64 partials, then a fixed-order add -- the same bits on every run, no float
+    atomics); ``result`` is the one read.  With ``targets`` (one output per row) a row is counted under its target.
+    ``outputs`` <= 16 and ``features`` (the network's ``full_dims[0]``) are fixed for the accumulator's life."""
+
+    def __init__(self, outputs: int, features: int, device):
+        from . import _lib
+        C, F = int(outputs), int(features)
+        if not 1 <= C <= _lib.EXPLAIN_MAX_OUTPUTS:
+            raise ValueError("bnn_amd: ExplanationAccumulator takes 1 to %d outputs, got %d" % (_lib.EXPLAIN_MAX_OUTPUTS, C))
+        if F < 1:
+            raise ValueError("bnn_amd: ExplanationAccumulator takes at least one feature, got %d" % F)
+        self.outputs, self.features, self.device = C, F, torch.device(device)
+        # one buffer, one read: rows | the sums (bit patterns of doubles) | the sums of absolute values
+        self._totals = torch.zeros(C + 2 * C * F, dtype=torch.int64, device=self.device)
+        self._work = None
+        self.updates = 0
+
+    def update(self, result: Dict[str, object]):
+        """Add the batch an ``explain`` call returned."""
+        from . import _lib
+        contributions, targets = result["contributions"], result.get("targets")
+        B, Cp, F = contributions.shape
+        C = self.outputs
+        if F != self.features or (targets is None and Cp != C) or (targets is not None and Cp != 1):
+            raise ValueError("bnn_amd: this ExplanationAccumulator was built for %d outputs and %d features, the result has "
+                             "%d explained outputs per row and %d features" % (C, self.features, Cp, F))
+        if result["logits"].shape[1] != C:
+            raise ValueError("bnn_amd: this ExplanationAccumulator was built for %d outputs, the model has %d"
+                             % (C, result["logits"].shape[1]))
+        dev = contributions.device
+        if not contributions.is_cuda or dev != self._totals.device:
+            raise ValueError("bnn_amd: the result is on %s, the accumulator on %s" % (dev, self._totals.device))
+        self.updates += 1
+        if B == 0:
+            return self
+        need = int(_lib.lib().lbbnn_explain_work_bytes(B, C, F))
+        if self._work is None or self._work.numel() * 8 < need:
+            self._work = torch.empty(need // 8, dtype=torch.float64, device=dev)
+        base = self._totals.data_ptr()
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().lbbnn_explain_totals(contributions.data_ptr(), F, targets.data_ptr() if targets is not None else None,
+                                                       B, C, F, base + 8 * C, base + 8 * (C + C * F), base, self._work.data_ptr(),
+                                                       torch.cuda.current_stream(dev).cuda_stream), "lbbnn_explain_totals")
+        return self
+
+    def reset(self):
+        self._totals.zero_()
+        self.updates = 0
+
+    def _read(self):
+        """The totals as a host int64 array (the one device-to-host copy)."""
+        return self._totals.cpu().numpy()
+
+    def result(self) -> Dict[str, object]:
+        """``rows`` (outputs,) int64: explained rows per output; ``mean_contribution`` and ``mean_abs_contribution`` (outputs,
+        features) float64: the sums over those rows divided by ``rows`` (NaN for an output without rows) --
+        ``mean_abs_contribution`` is the global importance that sits beside ``structure_posterior``'s ``feature_prob``; and the
+        raw ``sum_contribution`` / ``sum_abs_contribution``."""
+        import numpy as np
+        h = np.ascontiguousarray(self._read(), dtype=np.int64)
+        C, F = self.outputs, self.features
+        rows = h[:C].copy()
+        total = h[C:C + C * F].view(np.float64).reshape(C, F).copy()
+        abs_total = h[C + C * F:].view(np.float64).reshape(C, F).copy()
+        mean, mean_abs = _explanation_means(rows, total, abs_total)
+        return dict(rows=rows, mean_contribution=mean, mean_abs_contribution=mean_abs, sum_contribution=total,
+                    sum_abs_contribution=abs_total)
+
+
+@torch.no_grad()
+def explain_batches(fz, batches, acc: Optional[ExplanationAccumulator] = None, targets: str = "all") -> ExplanationAccumulator:
+    """A whole pass of ``explain`` with no host read: every batch of ``batches`` (a device tensor, or a tuple whose first entry
+    is one) goes through ``explain(fz, x, acc=acc)``; ``targets="all"`` explains every output, ``"pred"`` each row's predicted
+    output (the totals are then indexed by the predicted class).  Returns the accumulator (default: a fresh one); its
+    ``result()`` is the one read."""
+    if targets not in ("all", "pred"):
+        raise ValueError("bnn_amd: explain_batches takes targets=\"all\" or \"pred\", got %r" % (targets,))
+    _check_explainable(fz)
+    if acc is None:
+        acc = ExplanationAccumulator(fz.dims[-1], fz.full_dims[0], fz._device())
+    for batch in batches:
+        x = batch[0] if isinstance(batch, (tuple, list)) else batch
+        explain(fz, x, targets=None if targets == "all" else "pred", acc=acc)
+    return acc

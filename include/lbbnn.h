@@ -1852,6 +1852,86 @@ int lbbnn_gate_structure(const lbbnn_structure_desc_t* layers, int n, int sample
                          int32_t* kept, int32_t* needed, int32_t* active, int32_t* feature_count, int32_t* unit_count,
                          uint8_t* need_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Local explanations of a frozen posterior-mean forward (evaluate.explain).  That forward is a ReLU chain on fixed operands
+ * W_1 .. W_L, b_1 .. b_L, so for every row b its pre-head output is EXACTLY linear in the input:
+ *   logits[b, c] = sum_i J[b, c, i] x[b, i] + k[b, c],   J(b) = W_L D_{L-1}(b) W_{L-1} .. D_1(b) W_1,   D_l(b) = diag(h_l[b] > 0)
+ * The sweep keeps G_l = rows t(b, c) of W_L D_{L-1} .. W_{l+1} D_l as a (B * C', width of h_l) fp32 matrix, row b * C' + c.  Its
+ * matrix products G_l W_l are lbbnn_lrt_gemm calls (LBBNN_F_MEAN_ONLY) on transposed fp32 operands; lbbnn_explain_step is
+ * everything between two of them.  C' <= LBBNN_EXPLAIN_MAX_OUTPUTS rows of G share an input row; t(b, c) = c without targets,
+ * targets[b] (C' == 1; values outside [0, w_rows) are clamped: the caller checks them) with.
+ *
+ * lbbnn_explain_step, by mode (h: the (B, width) activations of the forward that produced the logits, rows ldh apart):
+ *   LBBNN_EXPLAIN_SEED    g[r][j] = w[t][j] * [h[b][j] > 0];  intercept[r] = bias_out[t] + <g[r], bias>;  active[b * ld_active] =
+ *                         #{j : h[b][j] > 0};  mask_out (nullable): [h[b][j] > 0] as bytes, rows ldm apart.  w: the LAST layer's
+ *                         operand as fp32 rows [w_rows][ldw], so that layer needs no product.
+ *   LBBNN_EXPLAIN_MASK    g[r][j] *= [h[b][j] > 0] in place;  intercept[r] += <g[r], bias>;  active and mask_out as above.
+ *   LBBNN_EXPLAIN_FINISH  h = the input rows x.  contributions[r][map[i]] = g[r][i] * x[b][i] (map NULL: the identity, and
+ *                         full_width == width; with a map the caller zeroes contributions: columns no map entry names are not
+ *                         written);  residual[r] = logits[b * ldl + t] - (sum_i g[r][i] x[b][i] + intercept[r]), the sum taken over
+ *                         the stored fp32 products.  g == NULL (a network of ONE layer): g[r] = w[t] and intercept[r] = bias_out[t]
+ *                         is written here.
+ * One wave per input row; every dot product and row sum is a per-lane sum in column order followed by a fixed-order wave
+ * reduction: the same bits on every run.  Nothing is read back or allocated.
+ *
+ * Checks, before anything is launched, in this order: args, h, intercept, the pointers the mode needs (seed / mask: g, bias,
+ * active; finish: logits, contributions, residual; seed and a finish without g: w, bias_out) NULL: LBBNN_E_NULL.  An unknown
+ * mode, B < 0, width < 1, C outside 1 .. LBBNN_EXPLAIN_MAX_OUTPUTS, B * C > LBBNN_EXPLAIN_MAX_ROWS, a row stride below its
+ * width (ldh, ldg, ldw, ldm; ldl < w_rows; ldc < full_width), targets with C != 1, C > w_rows without targets, w_rows < 1 where
+ * w or logits are read, ld_active < 1, full_width < width (with map) or != width (without): LBBNN_E_SHAPE.  A pointer off its
+ * natural alignment: LBBNN_E_ALIGN.  B == 0: nothing to do, 0.  Rows are read as float4 where the width, the strides and the
+ * bases allow it, element by element otherwise.
+ *
+ * lbbnn_explain_totals: running totals of a batch of contributions (B * C' rows of I columns, rows ldc apart) by output:
+ *   sum[cls][i] += sum_r contributions[r][i],  abs_sum[cls][i] += sum_r |contributions[r][i]|,  rows[cls] += #r   over the rows r
+ *   of output cls -- r = b * C + cls without targets (C' == C), r = b with targets[b] == cls (C' == 1; clamped into [0, C)).
+ * sum / abs_sum: (C, I) doubles, rows: (C) int64, ADDED TO.  Two launches: per-workgroup fp64 column partials into `work`
+ * (lbbnn_explain_work_bytes(B, C, I) bytes, 8-B aligned; 0 for a shape the call refuses), rows in order, then one workgroup adds
+ * the partials block by block.  The order of every addition depends on the shapes alone: no float atomics, the same bits on
+ * every run.  Checks: a NULL pointer (targets may be): LBBNN_E_NULL; B < 0, C outside 1 .. LBBNN_EXPLAIN_MAX_OUTPUTS, I < 1,
+ * ldc < I, more than LBBNN_EXPLAIN_MAX_ROWS rows: LBBNN_E_SHAPE; alignment: LBBNN_E_ALIGN; B == 0: 0.
+ *
+ * lbbnn_explain_operand: out[o][k] = hi + lo (exact in fp32) of an LBBNN_F_SPLIT16 operand [O][ld], as fp32 rows [O][ld]: the
+ * value the forward's products multiply by.  NULL: LBBNN_E_NULL; O, I < 1, ld < I: LBBNN_E_SHAPE; ld % 32 or a base off 16 B:
+ * LBBNN_E_ALIGN. */
+#define LBBNN_EXPLAIN_SEED 0
+#define LBBNN_EXPLAIN_MASK 1
+#define LBBNN_EXPLAIN_FINISH 2
+#define LBBNN_EXPLAIN_MAX_OUTPUTS 16
+#define LBBNN_EXPLAIN_MAX_ROWS (1 << 24)
+typedef struct lbbnn_explain_step_args {
+    int mode;
+    int B, C, width;
+    float* g;
+    int64_t ldg;
+    const float* w;
+    int64_t ldw;
+    int w_rows;
+    const int64_t* targets;
+    const float* h;
+    int64_t ldh;
+    const float* bias;
+    const float* bias_out;
+    float* intercept;
+    int32_t* active;
+    int64_t ld_active;
+    uint8_t* mask_out;
+    int64_t ldm;
+    const float* logits;
+    int64_t ldl;
+    const int32_t* map;
+    int full_width;
+    float* contributions;
+    int64_t ldc;
+    float* residual;
+} lbbnn_explain_step_args_t;
+
+int lbbnn_explain_step(const lbbnn_explain_step_args_t* args, void* stream);
+int64_t lbbnn_explain_work_bytes(int B, int C, int I);
+int lbbnn_explain_totals(const float* contributions, int64_t ldc, const int64_t* targets, int B, int C, int I,
+                         double* sum, double* abs_sum, int64_t* rows, void* work, void* stream);
+int lbbnn_explain_operand(const void* op, int O, int I, int ld, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
