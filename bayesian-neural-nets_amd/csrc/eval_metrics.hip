@@ -7,18 +7,16 @@
 //
 // Layout: a row's classes sit on G = the power of two >= C neighbouring lanes, so a wave holds 64 / G rows and a 256-thread
 // workgroup 256 / G; every reduction over the classes is a segmented DPP butterfly (no LDS), the members are a loop of
-// independent loads issued four at a time.  The integer totals are counted per workgroup in LDS and added to the caller's
-// totals with integer atomics (exact, hence reproducible in any order); the two double sums leave each workgroup as one
-// partial in `work` and are added in a fixed order by the second launch.
-#include "lbbnn_device.h"
-#include "lbbnn_internal.h"
+// independent loads issued four at a time.  Totals: DESIGN.md, "Evaluation totals"; the integer ones go through eval_totals.h,
+// the two double sums keep a layout of their own (below): each workgroup's block sum is one partial in `work`.
+#include "eval_totals.h"
 #include "seg_reduce.h"
 
 namespace {
 
 using namespace lbbnn;
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kEvalThreads;
 constexpr int kMemberChunk = 1024;     // per-member correct counts held in LDS at a time
 
 struct EvalK {
@@ -110,19 +108,14 @@ __global__ __launch_bounds__(kThreads) void eval_metrics_kernel(const EvalK a) {
     const bool fin = __builtin_isfinite(ent);
     const bool flags[kCounts] = {leader, leader && tvalid, leader && has_t && !tvalid, leader && tvalid && pe == (int)t,
                                  leader && tvalid && a.mean_logp != nullptr && pq == (int)t, leader && !fin};
-#pragma unroll
-    for (int k = 0; k < kCounts; ++k) {
-        const unsigned long long bal = __ballot(flags[k]);
-        if (lane == 0 && bal) atomicAdd(&cnt[k], (unsigned)__popcll(bal));
-    }
+    count_flags(flags, cnt);
     if (leader && tvalid) atomicAdd(&hist[(int)t * C + pe], 1u);   // rows: the true label
     double nll = (tvalid && cok && c == (int)t) ? -(double)ens : 0.0;
     double es = (leader && fin) ? (double)ent : 0.0;
     nll = block_sum<double, kThreads / 64>(nll, scratch);          // fixed order: the wave butterfly, then the 4 waves
     es = block_sum<double, kThreads / 64>(es, scratch);
-    if (tid < kCounts && cnt[tid]) atomicAdd(&a.counts[tid], (unsigned long long)cnt[tid]);
-    for (int i = tid; i < C * C; i += kThreads)
-        if (hist[i]) atomicAdd(&a.confusion[i], (unsigned long long)hist[i]);
+    flush_counters(cnt, kCounts, a.counts);
+    flush_counters(hist, C * C, a.confusion);
     if (tid == 0) {
         a.partials[2 * (size_t)blockIdx.x] = nll;
         a.partials[2 * (size_t)blockIdx.x + 1] = es;
@@ -146,42 +139,24 @@ __global__ __launch_bounds__(kThreads) void eval_metrics_sums_kernel(const doubl
     }
 }
 
-int lanes_per_row(int C) {
-    int G = 1;
-    while (G < C) G <<= 1;
-    return G;
-}
-
-long long workgroups(long long B, int C) {
-    const long long rows = kThreads / lanes_per_row(C);
-    return (B + rows - 1) / rows;
-}
-
-template <int G>
-void launch(const EvalK& k, long long nblk, hipStream_t s) {
-    hipLaunchKernelGGL(eval_metrics_kernel<G>, dim3((unsigned)nblk), dim3(kThreads), 0, s, k);
-}
-
-bool off(const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) != 0; }
-
 }  // namespace
 
 extern "C" int64_t lbbnn_eval_metrics_work_bytes(int S, int B, int C) {
     (void)S;
     if (C < 1 || C > 64 || B < 0) return 0;
-    const long long nblk = workgroups(B, C);
+    const long long nblk = row_workgroups(B, C);
     return (int64_t)(2 * sizeof(double)) * (nblk > 0 ? nblk : 1);
 }
 
 extern "C" int lbbnn_eval_metrics(const lbbnn_eval_metrics_args_t* a, void* stream) {
     if (!a || !a->logp) return LBBNN_E_NULL;
-    const bool any = a->counts || a->correct_member || a->confusion || a->sums;
-    if (any && !(a->counts && a->correct_member && a->confusion && a->sums && a->work)) return LBBNN_E_NULL;
+    const int given = totals_given({a->counts, a->correct_member, a->confusion, a->sums}, a->work);
+    if (given < 0) return LBBNN_E_NULL;
+    const bool any = given > 0;
     if (a->pred_mean && !a->mean_logp) return LBBNN_E_NULL;
-    if (a->S < 1 || a->S > 65535 || a->C < 1 || a->C > 64 || a->B < 0) return LBBNN_E_SHAPE;
-    if (a->ldp < a->C || (a->mean_logp && a->ldm < a->C)) return LBBNN_E_SHAPE;
-    if (a->S > 1 && a->B > 0 && a->m_stride < (int64_t)(a->B - 1) * a->ldp + a->C) return LBBNN_E_SHAPE;
-    if (workgroups(a->B, a->C) > 0x7FFFFFFFll) return LBBNN_E_SHAPE;
+    if (check_member_block(a->S, 65535, a->B, a->C, 64, a->ldp, a->m_stride)) return LBBNN_E_SHAPE;
+    if (a->mean_logp && a->ldm < a->C) return LBBNN_E_SHAPE;
+    if (row_workgroups(a->B, a->C) > 0x7FFFFFFFll) return LBBNN_E_SHAPE;
     if (off(a->logp, 4) || off(a->mean_logp, 4) || off(a->ens_logp, 4) || off(a->entropy, 4) || off(a->target, 8) ||
         off(a->pred_ensemble, 8) || off(a->pred_mean, 8) || off(a->counts, 8) || off(a->correct_member, 8) ||
         off(a->confusion, 8) || off(a->sums, 8) || off(a->work, 8))
@@ -196,17 +171,11 @@ extern "C" int lbbnn_eval_metrics(const lbbnn_eval_metrics_args_t* a, void* stre
     k.confusion = (unsigned long long*)a->confusion;
     k.partials = (double*)a->work;
     k.S = a->S; k.B = a->B; k.C = a->C;
-    const long long nblk = workgroups(a->B, a->C);
+    const long long nblk = row_workgroups(a->B, a->C);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (lanes_per_row(a->C)) {
-        case 1: launch<1>(k, nblk, s); break;
-        case 2: launch<2>(k, nblk, s); break;
-        case 4: launch<4>(k, nblk, s); break;
-        case 8: launch<8>(k, nblk, s); break;
-        case 16: launch<16>(k, nblk, s); break;
-        case 32: launch<32>(k, nblk, s); break;
-        default: launch<64>(k, nblk, s); break;
-    }
+    with_lanes_per_row(a->C, [&](auto G) {
+        hipLaunchKernelGGL(eval_metrics_kernel<decltype(G)::value>, dim3((unsigned)nblk), dim3(kThreads), 0, s, k);
+    });
     int rc = (int)hipGetLastError();
     if (rc || !any) return rc;
     hipLaunchKernelGGL(eval_metrics_sums_kernel, dim3(1), dim3(kThreads), 0, s, (const double*)a->work, nblk, a->sums);

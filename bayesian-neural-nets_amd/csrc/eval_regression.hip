@@ -5,23 +5,20 @@
 // double sums.
 //
 // Layout: one thread per element (b, o), 256 elements per workgroup in element order e = b * O + o; the members are two loops of
-// independent loads (the second needs the first's mean).  The integer totals are counted per workgroup in LDS (the counts and
-// the PIT bins: dynamic LDS, sized from the arguments) and added to the caller's totals with integer atomics, zeros skipped;
-// thread j < 8 then adds column j of the workgroup's elements in element order, in double, and leaves the partial in `work`,
-// which the second launch adds in a fixed order.  The per-member values are single fp32 operations: no contraction.
-#include "lbbnn_device.h"
-#include "lbbnn_internal.h"
+// independent loads (the second needs the first's mean): eval_member_pass.h, with one log-variance for all members.  Totals:
+// DESIGN.md, "Evaluation totals", through eval_totals.h; the LDS counters are the K PIT bins (dynamic LDS, sized from the
+// arguments), a slot is an element, the columns are the 8 sums.  The per-member values are single fp32 operations: no contraction.
+#include "eval_totals.h"
 
 #pragma clang fp contract(off)
+#include "eval_member_pass.h"
 
 namespace {
 
 using namespace lbbnn;
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kEvalThreads;
 constexpr int kMaxPitBins = 1024;
-constexpr float kLog2Pi = 1.8378770664093453f;
-constexpr float kRsqrt2 = 0.70710678118654752f;
 
 enum { kElements = 0, kWithTarget, kBadTargets, kNonfinite, kScored, kCounts };
 static_assert(kCounts == LBBNN_REG_COUNTS, "the header's count list");
@@ -41,19 +38,12 @@ struct RegK {
     int S, O, K;
 };
 
-// clamp((int)(v * scale), 0, n - 1): the product is clamped to [0, n] as a float first (a NaN or an overflowed product cannot
-// reach the conversion: fmaxf returns its other operand for a NaN), the integer afterwards -- eval_uncertainty.hip's rule.
-__device__ __forceinline__ int bin_of(float v, float scale, int n) {
-    const float p = fminf(fmaxf(v * scale, 0.f), (float)n);
-    return min(max((int)p, 0), n - 1);
-}
-
 __global__ __launch_bounds__(kThreads) void eval_regression_kernel(const RegK a) {
     extern __shared__ __attribute__((aligned(16))) unsigned bins[];   // K PIT counters
     __shared__ unsigned cnt[kCounts];
     __shared__ float colv[kSums][kThreads];
     __shared__ int flagv[kThreads];
-    const int tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x;
     const int S = a.S, O = a.O, K = a.K;
     const long long e = (long long)blockIdx.x * kThreads + tid;
     const bool in = e < a.n;
@@ -70,58 +60,18 @@ __global__ __launch_bounds__(kThreads) void eval_regression_kernel(const RegK a)
     if (in) {
         const long long b = e / O;
         const int o = (int)(e - b * O);
-        const float* p = a.out + b * a.ldp + o;
-        const float lv = a.log_var[o];
         y = has_t ? a.target[b * a.ldt + o] : nanv;
         tvalid = has_t && isfinite(y);
-        const float iv = expf(-lv), hs = expf(-0.5f * lv);
-        av = expf(lv);
-        fin = isfinite(lv);
-        float acc = 0.f, pacc = 0.f;
-        float mx = -INFINITY, ssum = 0.f;                          // streaming logsumexp over the members
-        for (int m = 0; m < S; m += 4) {
-            float v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = p[(long long)min(m + k, S - 1) * a.m_stride];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (m + k >= S) break;
-                const float x = v[k];
-                fin = fin && isfinite(x);
-                acc = (m + k == 0) ? x : acc + x;                  // the stated order: m_0, then += m_s
-                const float r = y - x;
-                const float t = -0.5f * ((kLog2Pi + lv) + (r * r) * iv);
-                if (t > mx) {
-                    ssum = ssum * expf(mx - t) + 1.f;
-                    mx = t;
-                } else if (t != -INFINITY) {
-                    ssum += expf(t - mx);                          // (a NaN term arrives here and stays)
-                }
-                const float ph = 0.5f * erfcf(-((r * hs) * kRsqrt2));
-                pacc = (m + k == 0) ? ph : pacc + ph;
-            }
-        }
-        pm = acc / (float)S;                                       // IEEE division (hipcc's default)
-        float acc2 = 0.f;
-        for (int m = 0; m < S; m += 4) {
-            float v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = p[(long long)min(m + k, S - 1) * a.m_stride];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (m + k >= S) break;
-                const float d = v[k] - pm;
-                acc2 = (m + k == 0) ? d * d : acc2 + d * d;
-            }
-        }
-        ev = acc2 / (float)S;
+        const MemberPass r = member_pass<false, false>(a.out + b * a.ldp + o, a.m_stride, a.log_var + o, 0, S, y);
+        fin = isfinite(a.log_var[o]) && r.finite;
+        pm = r.pm; ev = r.ev; av = r.av;
         tv = ev + av;
         if (tvalid) {
             const float err = y - pm;
             sq = err * err;
             ab = fabsf(err);
-            ld = (mx + logf(ssum)) - logf((float)S);
-            pit = pacc / (float)S;
+            ld = r.ld;
+            pit = r.pit;
             if (a.mean_out) {
                 const float f = y - a.mean_out[b * a.ldm + o];
                 pmsq = f * f;
@@ -139,47 +89,20 @@ __global__ __launch_bounds__(kThreads) void eval_regression_kernel(const RegK a)
 
     const bool scored = in && fin && tvalid;
     const bool flags[kCounts] = {in, in && tvalid, in && has_t && !tvalid, in && !fin, scored};
-#pragma unroll
-    for (int k = 0; k < kCounts; ++k) {
-        const unsigned long long bal = __ballot(flags[k]);
-        if (lane == 0 && bal) atomicAdd(&cnt[k], (unsigned)__popcll(bal));
-    }
+    count_flags(flags, cnt);
     if (scored) atomicAdd(&bins[bin_of(pit, (float)K, K)], 1u);
     flagv[tid] = (in && fin ? kInFinite : 0) | (scored ? kInScored : 0);
     colv[kSumSq][tid] = sq; colv[kSumAbs][tid] = ab; colv[kSumLogDensity][tid] = ld; colv[kSumEpistemic][tid] = ev;
     colv[kSumTotalVar][tid] = tv; colv[kSumY][tid] = y; colv[kSumY2][tid] = y * y; colv[kSumPmSq][tid] = pmsq;
     __syncthreads();
-    if (tid < kCounts && cnt[tid]) atomicAdd(&a.counts[tid], (unsigned long long)cnt[tid]);
-    for (int i = tid; i < K; i += kThreads) {
-        const unsigned c = bins[i];
-        if (c) atomicAdd(&a.hist[i], (unsigned long long)c);
-    }
-    // column j of the workgroup's elements, added in element order
-    if (tid < kSums) {
-        const int need = (tid == kSumEpistemic || tid == kSumTotalVar) ? kInFinite : kInScored;
-        double s = 0.0;
-        for (int i = 0; i < kThreads; ++i)
-            if ((flagv[i] & need) == need) s += (double)colv[tid][i];
-        a.partials[(size_t)tid * (size_t)a.nblk + blockIdx.x] = s;
-    }
-}
-
-// sums[j] += the workgroups' partials of column j.  Wave w takes the columns j = w, w + 4; lane l adds partials l, l + 64, ... in
-// ascending order, then the fixed wave butterfly.
-__global__ __launch_bounds__(kThreads) void eval_regression_sums_kernel(const double* __restrict__ partials, long long nblk,
-                                                                         double* sums) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (int j = w; j < kSums; j += kThreads / 64) {
-        double s = 0.0;
-        for (long long i = lane; i < nblk; i += 64) s += partials[(size_t)j * (size_t)nblk + i];
-        s = wave_sum(s);
-        if (lane == 0) sums[j] += s;
-    }
+    flush_counters(cnt, kCounts, a.counts);
+    flush_counters(bins, K, a.hist);
+    if (tid < kSums)
+        column_partial<kThreads>(tid, colv[tid], flagv, (tid == kSumEpistemic || tid == kSumTotalVar) ? kInFinite : kInScored,
+                                 a.partials, a.nblk);
 }
 
 long long workgroups(long long n) { return (n + kThreads - 1) / kThreads; }
-
-bool off(const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) != 0; }
 
 }  // namespace
 
@@ -192,11 +115,11 @@ extern "C" int64_t lbbnn_eval_regression_work_bytes(int S, int B, int O) {
 
 extern "C" int lbbnn_eval_regression(const lbbnn_eval_regression_args_t* a, void* stream) {
     if (!a || !a->out || !a->log_var) return LBBNN_E_NULL;
-    const bool any = a->counts || a->sums || a->pit_hist;
-    if (any && !(a->counts && a->sums && a->pit_hist && a->work)) return LBBNN_E_NULL;
-    if (a->S < 1 || a->S > 65535 || a->O < 1 || a->O > 16 || a->B < 0) return LBBNN_E_SHAPE;
-    if (a->ldp < a->O || (a->mean_out && a->ldm < a->O) || (a->target && a->ldt < a->O)) return LBBNN_E_SHAPE;
-    if (a->S > 1 && a->B > 0 && a->m_stride < (int64_t)(a->B - 1) * a->ldp + a->O) return LBBNN_E_SHAPE;
+    const int given = totals_given({a->counts, a->sums, a->pit_hist}, a->work);
+    if (given < 0) return LBBNN_E_NULL;
+    const bool any = given > 0;
+    if (check_member_block(a->S, 65535, a->B, a->O, 16, a->ldp, a->m_stride)) return LBBNN_E_SHAPE;
+    if ((a->mean_out && a->ldm < a->O) || (a->target && a->ldt < a->O)) return LBBNN_E_SHAPE;
     if ((long long)a->B * a->O > 0x7FFFFFFFll) return LBBNN_E_SHAPE;
     // the LDS counters are sized from pit_bins: 4 * 1024 B at most
     if (any && (a->pit_bins < 1 || a->pit_bins > kMaxPitBins)) return LBBNN_E_SHAPE;
@@ -221,6 +144,5 @@ extern "C" int lbbnn_eval_regression(const lbbnn_eval_regression_args_t* a, void
     hipLaunchKernelGGL(eval_regression_kernel, dim3((unsigned)k.nblk), dim3(kThreads), sizeof(unsigned) * (size_t)k.K, s, k);
     int rc = (int)hipGetLastError();
     if (rc || !any) return rc;
-    hipLaunchKernelGGL(eval_regression_sums_kernel, dim3(1), dim3(kThreads), 0, s, (const double*)a->work, k.nblk, a->sums);
-    return (int)hipGetLastError();
+    return launch_column_sums(a->work, k.nblk, kSums, a->sums, s);
 }

@@ -12,20 +12,19 @@
 // LDS to wave 0, which finishes the element and writes it.  Every wave rescans its element's members for the finite flag and the
 // bracket with the same expressions, so no wave waits before its share.  A member's (mean, log-variance) pair is re-read from
 // L1 / L2 wherever it is needed (the block is tens of KB at evaluation sizes, a member row a coalesced load across the wave).
-// The CRPS sums are kept in double: non-negative terms whose difference cancels.  Totals as in eval_regression.hip: integer counts
-// by ballot, PIT bins in LDS, then integer atomics; thread j < kSums adds column j of the workgroup's 64 elements in element order,
-// in double, and leaves the partial in `work`, which the second launch adds in a fixed order.  The per-member values are single
-// fp32 operations: no contraction.
-#include "lbbnn_device.h"
-#include "lbbnn_internal.h"
+// The CRPS sums are kept in double: non-negative terms whose difference cancels.  Totals: DESIGN.md, "Evaluation totals", through
+// eval_totals.h; wave 0 holds all 64 slots, so its ballots go straight to the caller's counts, the LDS counters are the K PIT
+// bins, the columns are the kSums sums.  The per-member values are single fp32 operations: no contraction.
+#include "eval_totals.h"
 
 #pragma clang fp contract(off)
+#include "eval_member_pass.h"
 
 namespace {
 
 using namespace lbbnn;
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kEvalThreads;
 constexpr int kElems = 64;                  // elements per workgroup: one per lane, shared by the workgroup's four waves
 constexpr int kWaves = kThreads / 64;
 constexpr int kMaxPitBins = 1024;
@@ -33,9 +32,6 @@ constexpr int kMaxLevels = LBBNN_SCORE_MAX_LEVELS;
 constexpr int kQuantiles = 2 * kMaxLevels;
 static_assert(kQuantiles == 2 * kWaves, "wave w takes quantiles w and w + kWaves");
 constexpr int kBisect = 26;                 // the bracket halves 26 times: (hi - lo) * 2^-27 about the returned midpoint
-constexpr float kLog2Pi = 1.8378770664093453f;
-constexpr float kRsqrt2 = 0.70710678118654752f;
-constexpr float kRsqrt2Pi = 0.39894228040143268f;
 constexpr float kMaxAbsLv = 80.f;
 constexpr float kMinLevel = 0.01f, kMaxLevel = 0.999f;
 
@@ -61,19 +57,6 @@ struct ScoreK {
     int S, O, K, L;
     float levels[kMaxLevels];
 };
-
-// eval_regression.hip's rule: the product is clamped to [0, n] as a float first, the integer afterwards
-__device__ __forceinline__ int bin_of(float v, float scale, int n) {
-    const float p = fminf(fmaxf(v * scale, 0.f), (float)n);
-    return min(max((int)p, 0), n - 1);
-}
-
-// A(m, v) = 2 sqrt(v) phi(m / sqrt v) + m (2 Phi(m / sqrt v) - 1) = E|N(m, v)|, as 2 sd phi(z) + |m| erf(z / sqrt 2) with
-// z = |m| / sd: both terms non-negative, and no 0 * inf (z * z may overflow: expf(-inf) = 0).  v >= exp(-80) here: sd > 0.
-__device__ __forceinline__ float a_term(float m, float v) {
-    const float sd = sqrtf(v), am = fabsf(m), z = am / sd;
-    return (2.f * sd) * (kRsqrt2Pi * expf(-0.5f * (z * z))) + am * erff(z * kRsqrt2);
-}
 
 __global__ __launch_bounds__(kThreads) void eval_scores_kernel(const ScoreK a) {
     extern __shared__ __attribute__((aligned(16))) unsigned bins[];   // K PIT counters
@@ -174,62 +157,19 @@ __global__ __launch_bounds__(kThreads) void eval_scores_kernel(const ScoreK a) {
         c2s[lane] = c2;
     }
 
-    // wave 0: the member pass of eval_regression.hip with a log-variance per member, and the CRPS's first sum
+    // wave 0: the member pass with a log-variance per member, and the CRPS's first sum
     float pm = nanv, ev = nanv, av = nanv, tv = nanv, sq = nanv, ab = 0.f, ld = nanv, pit = nanv, pmsq = 0.f;
     double c1 = 0.0;
     if (w == 0 && fin) {
-        float acc = 0.f, pacc = 0.f, vacc = 0.f;
-        float mx = -INFINITY, ssum = 0.f;                          // streaming logsumexp over the members
-        for (int m = 0; m < S; m += 4) {
-            float v[4], u[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const long long s = min(m + k, S - 1);
-                v[k] = p[s * ms];
-                u[k] = q[s * ls];
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (m + k >= S) break;
-                const float x = v[k], lv = u[k];
-                acc = (m + k == 0) ? x : acc + x;                  // the stated order: m_0, then += m_s
-                const float var = expf(lv), iv = expf(-lv), hs = expf(-0.5f * lv);
-                vacc = (m + k == 0) ? var : vacc + var;
-                const float r = y - x;
-                const float t = -0.5f * ((kLog2Pi + lv) + (r * r) * iv);
-                if (t > mx) {
-                    ssum = ssum * expf(mx - t) + 1.f;
-                    mx = t;
-                } else if (t != -INFINITY) {
-                    ssum += expf(t - mx);                          // (a NaN term arrives here and stays)
-                }
-                const float ph = 0.5f * erfcf(-((r * hs) * kRsqrt2));
-                pacc = (m + k == 0) ? ph : pacc + ph;
-                c1 += (double)a_term(r, var);
-            }
-        }
-        pm = acc / (float)S;                                       // IEEE division (hipcc's default)
-        float acc2 = 0.f;
-        for (int m = 0; m < S; m += 4) {
-            float v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = p[(long long)min(m + k, S - 1) * ms];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (m + k >= S) break;
-                const float d = v[k] - pm;
-                acc2 = (m + k == 0) ? d * d : acc2 + d * d;
-            }
-        }
-        ev = acc2 / (float)S;
-        av = vacc / (float)S;
+        const MemberPass r = member_pass<true, true>(p, ms, q, ls, S, y);
+        pm = r.pm; ev = r.ev; av = r.av; c1 = r.c1;
         tv = ev + av;
         if (tvalid) {
             const float err = y - pm;
             sq = err * err;
             ab = fabsf(err);
-            ld = (mx + logf(ssum)) - logf((float)S);
-            pit = pacc / (float)S;
+            ld = r.ld;
+            pit = r.pit;
             if (a.mean_out) {
                 const float f = y - a.mean_out[b * a.ldm + o];
                 pmsq = f * f;
@@ -285,11 +225,7 @@ __global__ __launch_bounds__(kThreads) void eval_scores_kernel(const ScoreK a) {
             bool flags[kCounts] = {in, tvalid, in && has_t && !tvalid, in && !fin, scored};
 #pragma unroll
             for (int l = 0; l < kMaxLevels; ++l) flags[kInside + l] = scored && inside[l];
-#pragma unroll
-            for (int k = 0; k < kCounts; ++k) {                     // one wave holds the whole workgroup's elements: no LDS stage
-                const unsigned long long bal = __ballot(flags[k]);
-                if (lane == 0 && bal) atomicAdd(&a.counts[k], (unsigned long long)__popcll(bal));
-            }
+            count_flags(flags, a.counts);                           // one wave holds the whole workgroup's elements: no LDS stage
             if (scored) atomicAdd(&bins[bin_of(pit, (float)K, K)], 1u);
             flagv[lane] = (fin ? kInFinite : 0) | (scored ? kInScored : 0);
             colv[kSumSq][lane] = sq; colv[kSumAbs][lane] = ab; colv[kSumLogDensity][lane] = ld; colv[kSumEpistemic][lane] = ev;
@@ -304,36 +240,14 @@ __global__ __launch_bounds__(kThreads) void eval_scores_kernel(const ScoreK a) {
     }
     if (!totals) return;                                           // (uniform over the grid)
     __syncthreads();
-    for (int i = tid; i < K; i += kThreads) {
-        const unsigned c = bins[i];
-        if (c) atomicAdd(&a.hist[i], (unsigned long long)c);
-    }
-    // column j of the workgroup's elements, added in element order
-    if (tid < kSums) {
-        const int need = (tid == kSumEpistemic || tid == kSumTotalVar || tid == kSumAleatoric) ? kInFinite : kInScored;
-        double s = 0.0;
-        for (int i = 0; i < kElems; ++i)
-            if ((flagv[i] & need) == need) s += (double)colv[tid][i];
-        a.partials[(size_t)tid * (size_t)a.nblk + blockIdx.x] = s;
-    }
-}
-
-// sums[j] += the workgroups' partials of column j.  Wave w takes the columns j = w, w + 4, ...; lane l adds partials l, l + 64,
-// ... in ascending order, then the fixed wave butterfly.
-__global__ __launch_bounds__(kThreads) void eval_scores_sums_kernel(const double* __restrict__ partials, long long nblk,
-                                                                     double* sums) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (int j = w; j < kSums; j += kThreads / 64) {
-        double s = 0.0;
-        for (long long i = lane; i < nblk; i += 64) s += partials[(size_t)j * (size_t)nblk + i];
-        s = wave_sum(s);
-        if (lane == 0) sums[j] += s;
-    }
+    flush_counters(bins, K, a.hist);
+    if (tid < kSums)
+        column_partial<kElems>(tid, colv[tid], flagv,
+                               (tid == kSumEpistemic || tid == kSumTotalVar || tid == kSumAleatoric) ? kInFinite : kInScored,
+                               a.partials, a.nblk);
 }
 
 long long workgroups(long long n) { return (n + kElems - 1) / kElems; }
-
-bool off(const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) != 0; }
 
 }  // namespace
 
@@ -345,11 +259,11 @@ extern "C" int64_t lbbnn_eval_regression_scores_work_bytes(int S, int B, int O, 
 
 extern "C" int lbbnn_eval_regression_scores(const lbbnn_eval_scores_args_t* a, void* stream) {
     if (!a || !a->out || !a->log_var) return LBBNN_E_NULL;
-    const bool any = a->counts || a->sums || a->pit_hist;
-    if (any && !(a->counts && a->sums && a->pit_hist && a->work)) return LBBNN_E_NULL;
-    if (a->S < 1 || a->S > LBBNN_SCORE_MAX_MEMBERS || a->O < 1 || a->O > 16 || a->B < 0) return LBBNN_E_SHAPE;
-    if (a->ldp < a->O || (a->mean_out && a->ldm < a->O) || (a->target && a->ldt < a->O)) return LBBNN_E_SHAPE;
-    if (a->S > 1 && a->B > 0 && a->m_stride < (int64_t)(a->B - 1) * a->ldp + a->O) return LBBNN_E_SHAPE;
+    const int given = totals_given({a->counts, a->sums, a->pit_hist}, a->work);
+    if (given < 0) return LBBNN_E_NULL;
+    const bool any = given > 0;
+    if (check_member_block(a->S, LBBNN_SCORE_MAX_MEMBERS, a->B, a->O, 16, a->ldp, a->m_stride)) return LBBNN_E_SHAPE;
+    if ((a->mean_out && a->ldm < a->O) || (a->target && a->ldt < a->O)) return LBBNN_E_SHAPE;
     if ((long long)a->B * a->O > 0x7FFFFFFFll) return LBBNN_E_SHAPE;
     // the log-variance operand: (0, 0) per unit, (0, ld) per element, (ms, ld) per member and element
     if (a->lv_ld != 0 && a->lv_ld < a->O) return LBBNN_E_SHAPE;
@@ -384,6 +298,5 @@ extern "C" int lbbnn_eval_regression_scores(const lbbnn_eval_scores_args_t* a, v
     hipLaunchKernelGGL(eval_scores_kernel, dim3((unsigned)k.nblk), dim3(kThreads), sizeof(unsigned) * (size_t)k.K, s, k);
     int rc = (int)hipGetLastError();
     if (rc || !any) return rc;
-    hipLaunchKernelGGL(eval_scores_sums_kernel, dim3(1), dim3(kThreads), 0, s, (const double*)a->work, k.nblk, a->sums);
-    return (int)hipGetLastError();
+    return launch_column_sums(a->work, k.nblk, kSums, a->sums, s);
 }

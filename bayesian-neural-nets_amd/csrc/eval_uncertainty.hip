@@ -5,19 +5,17 @@
 //
 // Layout: eval_metrics_kernel's.  A row's classes sit on G = the power of two >= C neighbouring lanes (256 / G rows per 256-thread
 // workgroup), every reduction over the classes is a segmented DPP butterfly, the members are a loop of independent loads issued
-// four at a time.  Each row's leader lane leaves the row's numbers in LDS; the integer totals are counted per workgroup in LDS
-// (3 * M reliability counters and 3 * K histogram counters: dynamic LDS, sized from the arguments) and added to the caller's totals
-// with integer atomics, zeros skipped; thread j < 6 + M then adds column j of the rows in row order, in double, and leaves the
-// partial in `work`, which the second launch adds in a fixed order.
-#include "lbbnn_device.h"
-#include "lbbnn_internal.h"
+// four at a time.  Totals: DESIGN.md, "Evaluation totals", through eval_totals.h.  Particular here: the LDS counters are 3 * M
+// reliability and 3 * K histogram ones (dynamic LDS, sized from the arguments); a slot is a row, whose leader lane leaves the
+// row's numbers in LDS; the columns are the 6 sums and, 6 + m, the confidence of bin m's rows with a target.
+#include "eval_totals.h"
 #include "seg_reduce.h"
 
 namespace {
 
 using namespace lbbnn;
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kEvalThreads;
 constexpr int kMaxConfBins = 100, kMaxHistBins = 4096;
 
 enum { kRows = 0, kRowsWithTarget, kBadTargets, kCorrectBma, kNonfiniteRows, kLogScoreNonfinite, kCounts };
@@ -39,13 +37,6 @@ struct UncK {
     int S, B, C, M, K;
     float ent_scale;
 };
-
-// clamp((int)(v * scale), 0, n - 1) of a FINITE v: the product is clamped to [0, n] as a float first (a NaN scale or an
-// overflowed product cannot reach the conversion: fmaxf returns its other operand for a NaN), the integer afterwards.
-__device__ __forceinline__ int bin_of(float v, float scale, int n) {
-    const float p = fminf(fmaxf(v * scale, 0.f), (float)n);
-    return min(max((int)p, 0), n - 1);
-}
 
 template <int G>
 __global__ __launch_bounds__(kThreads) void eval_uncertainty_kernel(const UncK a) {
@@ -128,11 +119,7 @@ __global__ __launch_bounds__(kThreads) void eval_uncertainty_kernel(const UncK a
     const bool hit = tvalid && pe == (int)t;
     const bool flags[kCounts] = {leader, leader && tvalid, leader && has_t && !tvalid, leader && hit, leader && !fin,
                                  leader && fin && tvalid && !ls_fin};
-#pragma unroll
-    for (int k = 0; k < kCounts; ++k) {
-        const unsigned long long bal = __ballot(flags[k]);
-        if (lane == 0 && bal) atomicAdd(&cnt[k], (unsigned)__popcll(bal));
-    }
+    count_flags(flags, cnt);
     const int r = w * RPW + g;                                     // this row's slot in the workgroup, < R
     if (c == 0) {                                                  // one lane per slot, rows past the end included (flag 0)
         int mb = 0, flag = 0;
@@ -152,81 +139,36 @@ __global__ __launch_bounds__(kThreads) void eval_uncertainty_kernel(const UncK a
         rowv[kSumBrier][r] = br; rowv[kSumLogScore][r] = ls;
     }
     __syncthreads();
-    if (tid < kCounts && cnt[tid]) atomicAdd(&a.counts[tid], (unsigned long long)cnt[tid]);
-    for (int i = tid; i < nbins; i += kThreads) {
-        const unsigned n = bins[i];
-        if (!n) continue;
-        unsigned long long* dst = i < M ? a.bin_rows + i : i < 2 * M ? a.bin_rows_t + (i - M)
-                                : i < 3 * M ? a.bin_correct + (i - 2 * M) : a.hist + (i - 3 * M);
-        atomicAdd(dst, (unsigned long long)n);
-    }
-    // column j of the rows, added in row order: j < 6 the sums, 6 + m the confidence of bin m's rows with a target
+    flush_counters(cnt, kCounts, a.counts);
+    flush_counters(bins, M, a.bin_rows);
+    flush_counters(bins + M, M, a.bin_rows_t);
+    flush_counters(bins + 2 * M, M, a.bin_correct);
+    flush_counters(bins + 3 * M, 3 * K, a.hist);
+    // column j < 6: a sum; 6 + m: the confidence of bin m's rows with a target
     if (tid < kSums + M) {
         const int need = tid < kSumBrier ? kInFinite : tid == kSumBrier ? (kInFinite | kInTarget)
                        : tid == kSumLogScore ? (kInFinite | kInLogScore) : (kInFinite | kInTarget);
-        const int col = tid < kSums ? tid : kSumConf, mb = tid - kSums;
-        double s = 0.0;
-        for (int i = 0; i < R; ++i) {
-            const bool in = (rowflag[i] & need) == need && (tid < kSums || rowbin[i] == mb);
-            if (in) s += (double)rowv[col][i];
-        }
-        a.partials[(size_t)tid * (size_t)a.nblk + blockIdx.x] = s;
+        column_partial<R>(tid, rowv[tid < kSums ? tid : kSumConf], rowflag, need, a.partials, a.nblk, rowbin, tid - kSums);
     }
 }
-
-// dst[j] += the workgroups' partials of column j (j < 6: sums, else bin_conf_sum[j - 6]).  Wave w takes the columns j = w, w + 4,
-// ...; lane l adds partials l, l + 64, ... in ascending order, then the fixed wave butterfly.
-__global__ __launch_bounds__(kThreads) void eval_uncertainty_sums_kernel(const double* __restrict__ partials, long long nblk, int M,
-                                                                          double* sums, double* bin_conf_sum) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (int j = w; j < kSums + M; j += kThreads / 64) {
-        double s = 0.0;
-        for (long long i = lane; i < nblk; i += 64) s += partials[(size_t)j * (size_t)nblk + i];
-        s = wave_sum(s);
-        if (lane == 0) {
-            double* dst = j < kSums ? sums + j : bin_conf_sum + (j - kSums);
-            *dst += s;
-        }
-    }
-}
-
-int lanes_per_row(int C) {
-    int G = 1;
-    while (G < C) G <<= 1;
-    return G;
-}
-
-long long workgroups(long long B, int C) {
-    const long long rows = kThreads / lanes_per_row(C);
-    return (B + rows - 1) / rows;
-}
-
-template <int G>
-void launch(const UncK& k, size_t lds, hipStream_t s) {
-    hipLaunchKernelGGL(eval_uncertainty_kernel<G>, dim3((unsigned)k.nblk), dim3(kThreads), lds, s, k);
-}
-
-bool off(const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) != 0; }
 
 }  // namespace
 
 extern "C" int64_t lbbnn_eval_uncertainty_work_bytes(int S, int B, int C, int conf_bins) {
     (void)S;
     if (C < 1 || C > 64 || B < 0 || conf_bins < 1 || conf_bins > kMaxConfBins) return 0;
-    const long long nblk = workgroups(B, C);
+    const long long nblk = row_workgroups(B, C);
     return (int64_t)sizeof(double) * (kSums + conf_bins) * (nblk > 0 ? nblk : 1);
 }
 
 extern "C" int lbbnn_eval_uncertainty(const lbbnn_eval_uncertainty_args_t* a, void* stream) {
     if (!a || !a->logp) return LBBNN_E_NULL;
-    const bool any = a->counts || a->sums || a->bin_rows || a->bin_rows_with_target || a->bin_correct || a->bin_conf_sum || a->hist;
-    if (any && !(a->counts && a->sums && a->bin_rows && a->bin_rows_with_target && a->bin_correct && a->bin_conf_sum && a->hist &&
-                 a->work))
-        return LBBNN_E_NULL;
-    if (a->S < 1 || a->S > 65535 || a->C < 1 || a->C > 64 || a->B < 0) return LBBNN_E_SHAPE;
-    if (a->ldp < a->C) return LBBNN_E_SHAPE;
-    if (a->S > 1 && a->B > 0 && a->m_stride < (int64_t)(a->B - 1) * a->ldp + a->C) return LBBNN_E_SHAPE;
-    if (workgroups(a->B, a->C) > 0x7FFFFFFFll) return LBBNN_E_SHAPE;
+    const int given = totals_given({a->counts, a->sums, a->bin_rows, a->bin_rows_with_target, a->bin_correct, a->bin_conf_sum, a->hist},
+                                   a->work);
+    if (given < 0) return LBBNN_E_NULL;
+    const bool any = given > 0;
+    if (check_member_block(a->S, 65535, a->B, a->C, 64, a->ldp, a->m_stride)) return LBBNN_E_SHAPE;
+    if (row_workgroups(a->B, a->C) > 0x7FFFFFFFll) return LBBNN_E_SHAPE;
     if (any) {
         // the LDS counters are sized from these two: 4 * (3 * 100 + 3 * 4096) B at most, inside the 64 KiB a workgroup may ask for
         if (a->conf_bins < 1 || a->conf_bins > kMaxConfBins || a->hist_bins < 1 || a->hist_bins > kMaxHistBins) return LBBNN_E_SHAPE;
@@ -247,24 +189,16 @@ extern "C" int lbbnn_eval_uncertainty(const lbbnn_eval_uncertainty_args_t* a, vo
     k.bin_rows_t = (unsigned long long*)a->bin_rows_with_target; k.bin_correct = (unsigned long long*)a->bin_correct;
     k.hist = (unsigned long long*)a->hist;
     k.partials = (double*)a->work;
-    k.nblk = workgroups(a->B, a->C);
+    k.nblk = row_workgroups(a->B, a->C);
     k.S = a->S; k.B = a->B; k.C = a->C;
     k.M = any ? a->conf_bins : 0; k.K = any ? a->hist_bins : 0;
     k.ent_scale = a->ent_scale;
     const size_t lds = sizeof(unsigned) * (size_t)(3 * k.M + 3 * k.K);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (lanes_per_row(a->C)) {
-        case 1: launch<1>(k, lds, s); break;
-        case 2: launch<2>(k, lds, s); break;
-        case 4: launch<4>(k, lds, s); break;
-        case 8: launch<8>(k, lds, s); break;
-        case 16: launch<16>(k, lds, s); break;
-        case 32: launch<32>(k, lds, s); break;
-        default: launch<64>(k, lds, s); break;
-    }
+    with_lanes_per_row(a->C, [&](auto G) {
+        hipLaunchKernelGGL(eval_uncertainty_kernel<decltype(G)::value>, dim3((unsigned)k.nblk), dim3(kThreads), lds, s, k);
+    });
     int rc = (int)hipGetLastError();
     if (rc || !any) return rc;
-    hipLaunchKernelGGL(eval_uncertainty_sums_kernel, dim3(1), dim3(kThreads), 0, s, (const double*)a->work, k.nblk, k.M, a->sums,
-                       a->bin_conf_sum);
-    return (int)hipGetLastError();
+    return launch_column_sums(a->work, k.nblk, kSums + k.M, a->sums, s, kSums, a->bin_conf_sum);
 }

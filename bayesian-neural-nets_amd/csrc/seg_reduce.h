@@ -1,6 +1,7 @@
 // Reductions over the G neighbouring lanes that hold one row's classes (eval_metrics.hip, eval_uncertainty.hip): G a power of
 // two <= 64, rows aligned to G, every lane of the row ends with the result.
 #pragma once
+#include <type_traits>
 #include "lbbnn_device.h"
 
 namespace lbbnn {
@@ -45,6 +46,31 @@ __device__ __forceinline__ int seg_argmax(float x, int c, bool cok) {
     const uint32_t key = (x != x) ? 0xFFFFFFFFu : ((bits & 0x80000000u) ? ~bits : (bits | 0x80000000u));
     const uint64_t packed = cok ? (((uint64_t)key << 32) | (uint32_t)(63 - c)) : 0ull;
     return 63 - (int)(uint32_t)seg_max<G>(packed);
+}
+
+// Host side of the layout: G for C classes, the 256-thread workgroups B rows take, and the call of f with G as a constant.
+inline int lanes_per_row(int C) {
+    int G = 1;
+    while (G < C) G <<= 1;
+    return G;
+}
+
+inline long long row_workgroups(long long B, int C) {
+    const long long rows = 256 / lanes_per_row(C);
+    return (B + rows - 1) / rows;
+}
+
+template <class F>
+void with_lanes_per_row(int C, F&& f) {
+    switch (lanes_per_row(C)) {
+        case 1: f(std::integral_constant<int, 1>()); break;
+        case 2: f(std::integral_constant<int, 2>()); break;
+        case 4: f(std::integral_constant<int, 4>()); break;
+        case 8: f(std::integral_constant<int, 8>()); break;
+        case 16: f(std::integral_constant<int, 16>()); break;
+        case 32: f(std::integral_constant<int, 32>()); break;
+        default: f(std::integral_constant<int, 64>()); break;
+    }
 }
 
 }  // namespace lbbnn

@@ -546,6 +546,78 @@ def _target_rows(target: torch.Tensor, B: int, dev) -> torch.Tensor:
     return t if (B < 2 or t.stride(0) == 1) else t.contiguous()
 
 
+def _mean_rows(mean_outputs: torch.Tensor, B: int, C: int, dev):
+    """(tensor, row stride) of the (B, C) posterior-mean outputs as the metrics kernels read them."""
+    if tuple(mean_outputs.shape) != (B, C) or mean_outputs.device != dev:
+        raise ValueError("bnn_amd: mean_outputs must be (%d, %d) on %s, got %s on %s"
+                         % (B, C, dev, tuple(mean_outputs.shape), mean_outputs.device))
+    return _dense_rows(mean_outputs if mean_outputs.dtype == torch.float32 else mean_outputs.float(), B, C)
+
+
+def _launch(dev, name: str, *args):
+    """One library call on ``dev``'s current stream (its last argument), checked."""
+    from . import _lib
+    with torch.cuda.device(dev):
+        _lib.check(getattr(_lib.lib(), name)(*args, torch.cuda.current_stream(dev).cuda_stream), name)
+
+
+class _DeviceTotals:
+    """What the accumulators share: ``_totals``, one int64 device buffer read in one copy (doubles as bit patterns); ``_work``,
+    the kernels' partials, grown to the largest batch; ``updates``; and the refusals every update and result repeat."""
+    _width = "classes"                       # the attribute that, with ``samples``, is fixed for the accumulator's life
+
+    def _start(self, words: int, device):
+        self.device = torch.device(device)
+        self._totals = torch.zeros(words, dtype=torch.int64, device=self.device)
+        self._work = None
+        self.reset()
+
+    def reset(self):
+        self._totals.zero_()
+        self.updates = 0
+
+    def _note(self, with_mean: bool = False):
+        self.updates += 1
+
+    def _read(self):
+        """The totals as a host int64 array (the one device-to-host copy)."""
+        return self._totals.cpu().numpy()
+
+    def _host(self):
+        import numpy as np
+        return np.ascontiguousarray(self._read(), dtype=np.int64)
+
+    def _check_batch(self, S: int, W: int, dev):
+        if (S, W) != (self.samples, getattr(self, self._width)):
+            raise ValueError("bnn_amd: this %s was built for %d members and %d %s, the outputs have %d and %d"
+                             % (type(self).__name__, self.samples, getattr(self, self._width), self._width, S, W))
+        if dev != self._totals.device:
+            raise ValueError("bnn_amd: the outputs are on %s, the accumulator on %s" % (dev, self._totals.device))
+
+    def _work_ptr(self, need: int) -> int:
+        """The address of at least ``need`` bytes of work memory."""
+        if self._work is None or self._work.numel() * 8 < need:
+            self._work = torch.empty(int(need) // 8, dtype=torch.float64, device=self._totals.device)
+        return self._work.data_ptr()
+
+    @staticmethod
+    def _refuse_bad_targets(res, strict: bool, what: str):
+        if strict and res["bad_targets"]:
+            raise IndexError("bnn_amd: %d target(s) %s in this evaluation pass" % (res["bad_targets"], what))
+
+
+class _MeanTotals(_DeviceTotals):
+    """Totals whose updates may carry posterior-mean outputs: ``posterior_mean_updates`` counts those that did."""
+
+    def reset(self):
+        super().reset()
+        self.posterior_mean_updates = 0
+
+    def _note(self, with_mean: bool = False):
+        self.updates += 1
+        self.posterior_mean_updates += int(with_mean)
+
+
 @torch.no_grad()
 def ensemble_metrics(outputs: torch.Tensor, target: Optional[torch.Tensor] = None,
                      mean_outputs: Optional[torch.Tensor] = None, *, acc: Optional["EvalAccumulator"] = None) -> Dict[str, object]:
@@ -570,11 +642,8 @@ def ensemble_metrics(outputs: torch.Tensor, target: Optional[torch.Tensor] = Non
     a.logp, a.m_stride, a.ldp, a.S, a.B, a.C = o.data_ptr(), ms, ldp, S, B, C
     keep = [o]
     if mean_outputs is not None:
-        if tuple(mean_outputs.shape) != (B, C) or mean_outputs.device != dev:
-            raise ValueError("bnn_amd: mean_outputs must be (%d, %d) on %s, got %s on %s"
-                             % (B, C, dev, tuple(mean_outputs.shape), mean_outputs.device))
-        mo, ldm = _dense_rows(mean_outputs if mean_outputs.dtype == torch.float32 else mean_outputs.float(), B, C)
-        a.mean_logp, a.ldm = mo.data_ptr(), ldm
+        mo, a.ldm = _mean_rows(mean_outputs, B, C, dev)
+        a.mean_logp = mo.data_ptr()
         keep.append(mo)
     if target is not None:
         t = _target_rows(target, B, dev)
@@ -591,16 +660,14 @@ def ensemble_metrics(outputs: torch.Tensor, target: Optional[torch.Tensor] = Non
     if acc is not None:
         acc._fill(a, S, B, C, dev)
     if B > 0:                                                # (an empty batch has no storage to point at, and nothing to add)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(_lib.lib().lbbnn_eval_metrics(ctypes.byref(a), stream), "lbbnn_eval_metrics")
+        _launch(dev, "lbbnn_eval_metrics", ctypes.byref(a))
     if acc is not None:
         acc._note(mean_outputs is not None)
     del keep
     return res
 
 
-class EvalAccumulator:
+class EvalAccumulator(_MeanTotals):
     """Running totals of an evaluation pass, kept on the device: ``update`` adds a batch (no host read), ``result`` reads them
     -- the ONLY synchronisation of a pass.  What the reference's loops accumulate on the host with an ``.item()`` per batch:
     test_ensemble's two correct counts (LBBNN-GP-MF-MNF.py:316-323), outofsample's per-member ``corrects``, ensemble correct
@@ -614,43 +681,21 @@ class EvalAccumulator:
             raise ValueError("bnn_amd: EvalAccumulator takes 1 to 64 classes, got %d" % C)
         if not 1 <= S <= 65535:
             raise ValueError("bnn_amd: EvalAccumulator takes 1 to 65535 members, got %d" % S)
-        self.classes, self.samples, self.device = C, S, torch.device(device)
-        n = _lib.EVAL_COUNTS
+        self.classes, self.samples = C, S
         # one buffer, one read: counts | correct_member | confusion | the two double sums (bit patterns)
-        self._totals = torch.zeros(n + S + C * C + 2, dtype=torch.int64, device=self.device)
-        self._work = None
-        self.updates = self.posterior_mean_updates = 0
+        self._start(_lib.EVAL_COUNTS + S + C * C + 2, device)
 
     def _fill(self, a, S, B, C, dev):
         """Point the totals of an lbbnn_eval_metrics_args_t at this accumulator (work memory grows to the largest batch)."""
         from . import _lib
-        if (S, C) != (self.samples, self.classes):
-            raise ValueError("bnn_amd: this EvalAccumulator was built for %d members and %d classes, the outputs have %d and %d"
-                             % (self.samples, self.classes, S, C))
-        if dev != self._totals.device:
-            raise ValueError("bnn_amd: the outputs are on %s, the accumulator on %s" % (dev, self._totals.device))
-        need = int(_lib.lib().lbbnn_eval_metrics_work_bytes(S, B, C))
-        if self._work is None or self._work.numel() * 8 < need:
-            self._work = torch.empty(need // 8, dtype=torch.float64, device=dev)
+        self._check_batch(S, C, dev)
+        a.work = self._work_ptr(_lib.lib().lbbnn_eval_metrics_work_bytes(S, B, C))
         n, base = _lib.EVAL_COUNTS, self._totals.data_ptr()
-        a.counts, a.correct_member, a.confusion = base, base + 8 * n, base + 8 * (n + S)
-        a.sums, a.work = base + 8 * (n + S + C * C), self._work.data_ptr()
-
-    def _note(self, with_mean: bool):
-        self.updates += 1
-        self.posterior_mean_updates += int(with_mean)
+        a.counts, a.correct_member, a.confusion, a.sums = base, base + 8 * n, base + 8 * (n + S), base + 8 * (n + S + C * C)
 
     def update(self, outputs: torch.Tensor, target: Optional[torch.Tensor], mean_outputs: Optional[torch.Tensor] = None):
         """``ensemble_metrics(outputs, target, mean_outputs)`` of one batch, its numbers added to the totals."""
         return ensemble_metrics(outputs, target, mean_outputs, acc=self)
-
-    def reset(self):
-        self._totals.zero_()
-        self.updates = self.posterior_mean_updates = 0
-
-    def _read(self):
-        """The totals as a host int64 array (the one device-to-host copy)."""
-        return self._totals.cpu().numpy()
 
     def result(self, strict: bool = True) -> Dict[str, object]:
         """Python numbers: ``rows``, ``rows_with_target``, ``bad_targets``, ``correct_ensemble``, ``correct_posterior_mean``,
@@ -662,11 +707,10 @@ class EvalAccumulator:
         ``F.nll_loss`` would have; with ``strict=False`` they are reported in ``bad_targets`` and left out of the totals."""
         import numpy as np
         from . import _lib
-        h = np.ascontiguousarray(self._read(), dtype=np.int64)
+        h = self._host()
         n, S, C = _lib.EVAL_COUNTS, self.samples, self.classes
         res = {k: int(h[i]) for i, k in enumerate(_lib.EVAL_COUNT_NAMES)}
-        if strict and res["bad_targets"]:
-            raise IndexError("bnn_amd: %d target(s) outside [0, %d) in this evaluation pass" % (res["bad_targets"], C))
+        self._refuse_bad_targets(res, strict, "outside [0, %d)" % C)
         sums = h[n + S + C * C:].view(np.float64)
         res["correct_member"] = h[n:n + S].copy()
         res["confusion"] = h[n + S:n + S + C * C].reshape(C, C).copy()
@@ -730,16 +774,14 @@ def ensemble_uncertainty(outputs: torch.Tensor, target: Optional[torch.Tensor] =
     if acc is not None:
         acc._fill(a, S, B, C, dev)
     if B > 0:                                                # (an empty batch has no storage to point at, and nothing to add)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(_lib.lib().lbbnn_eval_uncertainty(ctypes.byref(a), stream), "lbbnn_eval_uncertainty")
+        _launch(dev, "lbbnn_eval_uncertainty", ctypes.byref(a))
     if acc is not None:
-        acc.updates += 1
+        acc._note()
     del keep
     return res
 
 
-class UncertaintyAccumulator:
+class UncertaintyAccumulator(_DeviceTotals):
     """Running uncertainty and calibration totals of an evaluation pass, kept on the device: ``update`` adds a batch (no host
     read), ``result`` reads them -- one buffer, one copy.  Counts, the sums of the per-row numbers of ``ensemble_uncertainty``,
     a reliability table over ``conf_bins`` equal-width confidence bins and ``hist_bins``-bin histograms of the three
@@ -757,13 +799,11 @@ class UncertaintyAccumulator:
             raise ValueError("bnn_amd: UncertaintyAccumulator takes 1 to 100 confidence bins, got %d" % M)
         if not 1 <= K <= 4096:
             raise ValueError("bnn_amd: UncertaintyAccumulator takes 1 to 4096 histogram bins, got %d" % K)
-        self.classes, self.samples, self.conf_bins, self.hist_bins, self.device = C, S, M, K, torch.device(device)
+        self.classes, self.samples, self.conf_bins, self.hist_bins = C, S, M, K
         self.ent_scale = _ent_scale(C, K)
         # one buffer, one read: counts | sums | bin_rows | bin_rows_with_target | bin_correct | bin_conf_sum | hist (the doubles
         # as bit patterns)
-        self._totals = torch.zeros(self._offsets()["end"], dtype=torch.int64, device=self.device)
-        self._work = None
-        self.updates = 0
+        self._start(self._offsets()["end"], device)
 
     def _offsets(self) -> Dict[str, int]:
         """Where each total starts in the buffer, in 8-byte words."""
@@ -780,32 +820,17 @@ class UncertaintyAccumulator:
     def _fill(self, a, S, B, C, dev):
         """Point the totals of an lbbnn_eval_uncertainty_args_t at this accumulator (work memory grows to the largest batch)."""
         from . import _lib
-        if (S, C) != (self.samples, self.classes):
-            raise ValueError("bnn_amd: this UncertaintyAccumulator was built for %d members and %d classes, the outputs have "
-                             "%d and %d" % (self.samples, self.classes, S, C))
-        if dev != self._totals.device:
-            raise ValueError("bnn_amd: the outputs are on %s, the accumulator on %s" % (dev, self._totals.device))
-        need = int(_lib.lib().lbbnn_eval_uncertainty_work_bytes(S, B, C, self.conf_bins))
-        if self._work is None or self._work.numel() * 8 < need:
-            self._work = torch.empty(need // 8, dtype=torch.float64, device=dev)
+        self._check_batch(S, C, dev)
+        a.work = self._work_ptr(_lib.lib().lbbnn_eval_uncertainty_work_bytes(S, B, C, self.conf_bins))
         base = self._totals.data_ptr()
         for name, at in self._offsets().items():
             if name != "end":
                 setattr(a, name, base + 8 * at)
-        a.work = self._work.data_ptr()
         a.conf_bins, a.hist_bins, a.ent_scale = self.conf_bins, self.hist_bins, float(self.ent_scale)
 
     def update(self, outputs: torch.Tensor, target: Optional[torch.Tensor] = None):
         """``ensemble_uncertainty(outputs, target)`` of one batch, its numbers added to the totals."""
         return ensemble_uncertainty(outputs, target, acc=self)
-
-    def reset(self):
-        self._totals.zero_()
-        self.updates = 0
-
-    def _read(self):
-        """The totals as a host int64 array (the one device-to-host copy)."""
-        return self._totals.cpu().numpy()
 
     def result(self, strict: bool = True) -> Dict[str, object]:
         """Python numbers and numpy arrays.  The raw totals: the counts ``rows``, ``rows_with_target``, ``bad_targets``,
@@ -821,11 +846,10 @@ class UncertaintyAccumulator:
         means less certain in all three).  NaN where a denominator is 0.  ``strict``: as ``EvalAccumulator.result``."""
         import numpy as np
         from . import _lib
-        h = np.ascontiguousarray(self._read(), dtype=np.int64)
+        h = self._host()
         off, M, K, C = self._offsets(), self.conf_bins, self.hist_bins, self.classes
         res = {k: int(h[off["counts"] + i]) for i, k in enumerate(_lib.UNC_COUNT_NAMES)}
-        if strict and res["bad_targets"]:
-            raise IndexError("bnn_amd: %d target(s) outside [0, %d) in this evaluation pass" % (res["bad_targets"], C))
+        self._refuse_bad_targets(res, strict, "outside [0, %d)" % C)
         res.update(classes=C, samples=self.samples, conf_bins=M, hist_bins=K)
         part = lambda name, n: h[off[name]:off[name] + n]
         sums = part("sums", _lib.UNC_SUMS).view(np.float64)
@@ -954,11 +978,8 @@ def ensemble_regression(outputs: torch.Tensor, target: Optional[torch.Tensor] = 
     a.out, a.m_stride, a.ldp, a.S, a.B, a.O, a.log_var = o.data_ptr(), ms, ldp, S, B, O, lv.data_ptr()
     keep = [o, lv]
     if mean_outputs is not None:
-        if tuple(mean_outputs.shape) != (B, O) or mean_outputs.device != dev:
-            raise ValueError("bnn_amd: mean_outputs must be (%d, %d) on %s, got %s on %s"
-                             % (B, O, dev, tuple(mean_outputs.shape), mean_outputs.device))
-        mo, ldm = _dense_rows(mean_outputs if mean_outputs.dtype == torch.float32 else mean_outputs.float(), B, O)
-        a.mean_out, a.ldm = mo.data_ptr(), ldm
+        mo, a.ldm = _mean_rows(mean_outputs, B, O, dev)
+        a.mean_out = mo.data_ptr()
         keep.append(mo)
     if target is not None:
         t = _regression_target(target, B, O, dev)
@@ -973,16 +994,14 @@ def ensemble_regression(outputs: torch.Tensor, target: Optional[torch.Tensor] = 
     if acc is not None:
         acc._fill(a, S, B, O, dev)
     if B > 0:                                                # (an empty batch has no storage to point at, and nothing to add)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(_lib.lib().lbbnn_eval_regression(ctypes.byref(a), stream), "lbbnn_eval_regression")
+        _launch(dev, "lbbnn_eval_regression", ctypes.byref(a))
     if acc is not None:
         acc._note(mean_outputs is not None)
     del keep
     return res
 
 
-class RegressionAccumulator:
+class RegressionAccumulator(_MeanTotals):
     """Running regression totals of an evaluation pass, kept on the device: ``update`` adds a batch (no host read), ``result``
     reads them -- one buffer, one copy, the ONLY synchronisation of a pass.  The counterpart of ``EvalAccumulator`` /
     ``UncertaintyAccumulator`` for a network with ``head="identity"``: error sums, the log density of the members' mixture,
@@ -991,6 +1010,9 @@ class RegressionAccumulator:
     ``units`` (1 to 16), ``samples`` and ``pit_bins`` (1 to 1024) are fixed for the accumulator's life.  ``log_var``: the
     log-variance of the normal likelihood per output unit -- a number, or a live float32 (units,) device tensor (e.g. the
     ``nn.Parameter`` that ``elbo_gaussian_loss`` trained), which the kernel reads through its pointer at every update."""
+
+    _width = "units"
+    _layout = ("REG_COUNTS", "REG_SUMS")       # the _lib names of the sizes of counts | sums; pit_hist follows them
 
     def __init__(self, units: int, samples: int, device, log_var, pit_bins: int = 20):
         from . import _lib
@@ -1001,43 +1023,26 @@ class RegressionAccumulator:
             raise ValueError("bnn_amd: RegressionAccumulator takes 1 to 65535 members, got %d" % S)
         if not 1 <= K <= 1024:
             raise ValueError("bnn_amd: RegressionAccumulator takes 1 to 1024 PIT bins, got %d" % K)
-        self.units, self.samples, self.pit_bins, self.device = O, S, K, torch.device(device)
+        self.units, self.samples, self.pit_bins = O, S, K
         # one buffer, one read: counts | sums (bit patterns) | pit_hist
-        self._totals = torch.zeros(_lib.REG_COUNTS + _lib.REG_SUMS + K, dtype=torch.int64, device=self.device)
+        self._start(getattr(_lib, self._layout[0]) + getattr(_lib, self._layout[1]) + K, device)
         self._log_var = _regression_log_var(log_var, O, self._totals.device)
-        self._work = None
-        self.updates = self.posterior_mean_updates = 0
+
+    def _work_bytes(self, S, B, O):
+        from . import _lib
+        return _lib.lib().lbbnn_eval_regression_work_bytes(S, B, O)
 
     def _fill(self, a, S, B, O, dev):
-        """Point the totals of an lbbnn_eval_regression_args_t at this accumulator (work memory grows to the largest batch)."""
+        """Point the totals of the call's arguments at this accumulator (work memory grows to the largest batch)."""
         from . import _lib
-        if (S, O) != (self.samples, self.units):
-            raise ValueError("bnn_amd: this RegressionAccumulator was built for %d members and %d units, the outputs have %d and %d"
-                             % (self.samples, self.units, S, O))
-        if dev != self._totals.device:
-            raise ValueError("bnn_amd: the outputs are on %s, the accumulator on %s" % (dev, self._totals.device))
-        need = int(_lib.lib().lbbnn_eval_regression_work_bytes(S, B, O))
-        if self._work is None or self._work.numel() * 8 < need:
-            self._work = torch.empty(need // 8, dtype=torch.float64, device=dev)
-        base = self._totals.data_ptr()
-        a.counts, a.sums, a.pit_hist = base, base + 8 * _lib.REG_COUNTS, base + 8 * (_lib.REG_COUNTS + _lib.REG_SUMS)
-        a.work, a.pit_bins = self._work.data_ptr(), self.pit_bins
-
-    def _note(self, with_mean: bool):
-        self.updates += 1
-        self.posterior_mean_updates += int(with_mean)
+        self._check_batch(S, O, dev)
+        a.work, a.pit_bins = self._work_ptr(self._work_bytes(S, B, O)), self.pit_bins
+        nc, ns, base = getattr(_lib, self._layout[0]), getattr(_lib, self._layout[1]), self._totals.data_ptr()
+        a.counts, a.sums, a.pit_hist = base, base + 8 * nc, base + 8 * (nc + ns)
 
     def update(self, outputs: torch.Tensor, target: Optional[torch.Tensor] = None, mean_outputs: Optional[torch.Tensor] = None):
         """``ensemble_regression(outputs, target, self's log_var, mean_outputs)`` of one batch, its numbers added to the totals."""
         return ensemble_regression(outputs, target, None, mean_outputs, acc=self)
-
-    def reset(self):
-        self._totals.zero_()
-        self.updates = self.posterior_mean_updates = 0
-
-    def _read(self):
-        """The totals as a host int64 array (the one device-to-host copy)."""
-        return self._totals.cpu().numpy()
 
     def result(self, strict: bool = True) -> Dict[str, object]:
         """Python numbers.  Counts: ``elements``, ``elements_with_target``, ``bad_targets`` (NaN or infinite targets),
@@ -1050,8 +1055,7 @@ class RegressionAccumulator:
         ``coverage(level)`` = ``pit_coverage(pit_hist, level)``, the share of PIT values in the central ``level`` interval
         (ValueError when its edges are not bin edges).  ``strict``: as ``EvalAccumulator.result`` -- bad targets raise
         IndexError; with ``strict=False`` they are reported in ``bad_targets`` and left out of the totals."""
-        import numpy as np
-        return self._result_of(np.ascontiguousarray(self._read(), dtype=np.int64), strict)
+        return self._result_of(self._host(), strict)
 
     def _result_of(self, h, strict: bool) -> Dict[str, object]:
         """``result`` from the host copy ``h`` of totals laid out counts | sums | pit_hist."""
@@ -1060,8 +1064,7 @@ class RegressionAccumulator:
         from . import _lib
         nc, ns = _lib.REG_COUNTS, _lib.REG_SUMS
         res = {k: int(h[i]) for i, k in enumerate(_lib.REG_COUNT_NAMES)}
-        if strict and res["bad_targets"]:
-            raise IndexError("bnn_amd: %d target(s) that are NaN or infinite in this evaluation pass" % res["bad_targets"])
+        self._refuse_bad_targets(res, strict, "that are NaN or infinite")
         res.update(units=self.units, samples=self.samples, pit_bins=self.pit_bins)
         sums = h[nc:nc + ns].view(np.float64)
         for i, k in enumerate(_lib.REG_SUM_NAMES):
@@ -1174,11 +1177,8 @@ def ensemble_scores(outputs: torch.Tensor, target: Optional[torch.Tensor] = None
         a.log_var = lv.data_ptr()
     keep = [o, lv]
     if mean_outputs is not None:
-        if tuple(mean_outputs.shape) != (B, C) or mean_outputs.device != dev:
-            raise ValueError("bnn_amd: mean_outputs must be (%d, %d) on %s, got %s on %s"
-                             % (B, C, dev, tuple(mean_outputs.shape), mean_outputs.device))
-        mo, ldm = _dense_rows(mean_outputs if mean_outputs.dtype == torch.float32 else mean_outputs.float(), B, C)
-        a.mean_out, a.ldm = mo.data_ptr(), ldm
+        mo, a.ldm = _mean_rows(mean_outputs, B, C, dev)
+        a.mean_out = mo.data_ptr()
         keep.append(mo)
     if target is not None:
         t = _regression_target(target, B, O, dev)
@@ -1201,9 +1201,7 @@ def ensemble_scores(outputs: torch.Tensor, target: Optional[torch.Tensor] = None
     if acc is not None:
         acc._fill(a, S, B, O, dev)
     if B > 0:                                                # (an empty batch has no storage to point at, and nothing to add)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(_lib.lib().lbbnn_eval_regression_scores(ctypes.byref(a), stream), "lbbnn_eval_regression_scores")
+        _launch(dev, "lbbnn_eval_regression_scores", ctypes.byref(a))
     if acc is not None:
         acc._note(mean_outputs is not None)
     del keep
@@ -1221,6 +1219,8 @@ class RegressionScoreAccumulator(RegressionAccumulator):
     device tensor, or ``"output"`` -- the model then has ``dims[-1] == 2 * units`` and every member's outputs carry the
     log-variances in their upper ``units`` columns.  A per-batch (B, units) or (samples, B, units) tensor goes to ``update``."""
 
+    _layout = ("SCORE_COUNTS", "SCORE_SUMS")
+
     def __init__(self, units: int, samples: int, device, log_var, pit_bins: int = 20, levels=(0.5, 0.9)):
         from . import _lib
         self.in_output = isinstance(log_var, str)
@@ -1230,24 +1230,10 @@ class RegressionScoreAccumulator(RegressionAccumulator):
         if self.samples > _lib.SCORE_MAX_MEMBERS:
             raise ValueError("bnn_amd: RegressionScoreAccumulator takes 1 to %d members, got %d" % (_lib.SCORE_MAX_MEMBERS, self.samples))
         self.levels = _score_levels(levels)
-        # one buffer, one read: counts | sums (bit patterns) | pit_hist
-        self._totals = torch.zeros(_lib.SCORE_COUNTS + _lib.SCORE_SUMS + self.pit_bins, dtype=torch.int64, device=self.device)
 
-    def _fill(self, a, S, B, O, dev):
-        """Point the totals of an lbbnn_eval_scores_args_t at this accumulator (work memory grows to the largest batch)."""
+    def _work_bytes(self, S, B, O):
         from . import _lib
-        if (S, O) != (self.samples, self.units):
-            raise ValueError("bnn_amd: this RegressionScoreAccumulator was built for %d members and %d units, the outputs have %d and %d"
-                             % (self.samples, self.units, S, O))
-        if dev != self._totals.device:
-            raise ValueError("bnn_amd: the outputs are on %s, the accumulator on %s" % (dev, self._totals.device))
-        need = int(_lib.lib().lbbnn_eval_regression_scores_work_bytes(S, B, O, len(self.levels)))
-        if self._work is None or self._work.numel() * 8 < need:
-            self._work = torch.empty(need // 8, dtype=torch.float64, device=dev)
-        base = self._totals.data_ptr()
-        a.counts, a.sums = base, base + 8 * _lib.SCORE_COUNTS
-        a.pit_hist = base + 8 * (_lib.SCORE_COUNTS + _lib.SCORE_SUMS)
-        a.work, a.pit_bins = self._work.data_ptr(), self.pit_bins
+        return _lib.lib().lbbnn_eval_regression_scores_work_bytes(S, B, O, len(self.levels))
 
     def update(self, outputs: torch.Tensor, target: Optional[torch.Tensor] = None, mean_outputs: Optional[torch.Tensor] = None,
                *, log_var=None):
@@ -1274,7 +1260,7 @@ class RegressionScoreAccumulator(RegressionAccumulator):
         is 0.  ``strict``: as ``RegressionAccumulator.result``."""
         import numpy as np
         from . import _lib
-        h = np.ascontiguousarray(self._read(), dtype=np.int64)
+        h = self._host()
         nc, ns, rc, rs, ml = _lib.SCORE_COUNTS, _lib.SCORE_SUMS, _lib.REG_COUNTS, _lib.REG_SUMS, _lib.SCORE_MAX_LEVELS
         res = self._result_of(np.concatenate([h[:rc], h[nc:nc + rs], h[nc + ns:]]), strict)
         sums = h[nc:nc + ns].view(np.float64)
@@ -2802,7 +2788,7 @@ def _explanation_means(rows, total, abs_total):
     return np.asarray(total, dtype=np.float64) / den + nan, np.asarray(abs_total, dtype=np.float64) / den + nan
 
 
-class ExplanationAccumulator:
+class ExplanationAccumulator(_DeviceTotals):
     """Running totals of ``explain`` over an evaluation pass, kept on the device: per output the number of explained rows and
     the fp64 sums of the contributions and of their absolute values per input feature.  ``update`` adds a batch with no host
     read (lbbnn_explain_totals: per-workgroup fp64 partials, then a fixed-order add -- the same bits on every run, no float
@@ -2816,11 +2802,9 @@ class ExplanationAccumulator:
             raise ValueError("bnn_amd: ExplanationAccumulator takes 1 to %d outputs, got %d" % (_lib.EXPLAIN_MAX_OUTPUTS, C))
         if F < 1:
             raise ValueError("bnn_amd: ExplanationAccumulator takes at least one feature, got %d" % F)
-        self.outputs, self.features, self.device = C, F, torch.device(device)
+        self.outputs, self.features = C, F
         # one buffer, one read: rows | the sums (bit patterns of doubles) | the sums of absolute values
-        self._totals = torch.zeros(C + 2 * C * F, dtype=torch.int64, device=self.device)
-        self._work = None
-        self.updates = 0
+        self._start(C + 2 * C * F, device)
 
     def update(self, result: Dict[str, object]):
         """Add the batch an ``explain`` call returned."""
@@ -2840,23 +2824,10 @@ class ExplanationAccumulator:
         self.updates += 1
         if B == 0:
             return self
-        need = int(_lib.lib().lbbnn_explain_work_bytes(B, C, F))
-        if self._work is None or self._work.numel() * 8 < need:
-            self._work = torch.empty(need // 8, dtype=torch.float64, device=dev)
-        base = self._totals.data_ptr()
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().lbbnn_explain_totals(contributions.data_ptr(), F, targets.data_ptr() if targets is not None else None,
-                                                       B, C, F, base + 8 * C, base + 8 * (C + C * F), base, self._work.data_ptr(),
-                                                       torch.cuda.current_stream(dev).cuda_stream), "lbbnn_explain_totals")
+        work, base = self._work_ptr(_lib.lib().lbbnn_explain_work_bytes(B, C, F)), self._totals.data_ptr()
+        _launch(dev, "lbbnn_explain_totals", contributions.data_ptr(), F, targets.data_ptr() if targets is not None else None,
+                B, C, F, base + 8 * C, base + 8 * (C + C * F), base, work)
         return self
-
-    def reset(self):
-        self._totals.zero_()
-        self.updates = 0
-
-    def _read(self):
-        """The totals as a host int64 array (the one device-to-host copy)."""
-        return self._totals.cpu().numpy()
 
     def result(self) -> Dict[str, object]:
         """``rows`` (outputs,) int64: explained rows per output; ``mean_contribution`` and ``mean_abs_contribution`` (outputs,
@@ -2864,7 +2835,7 @@ class ExplanationAccumulator:
         ``mean_abs_contribution`` is the global importance that sits beside ``structure_posterior``'s ``feature_prob``; and the
         raw ``sum_contribution`` / ``sum_abs_contribution``."""
         import numpy as np
-        h = np.ascontiguousarray(self._read(), dtype=np.int64)
+        h = self._host()
         C, F = self.outputs, self.features
         rows = h[:C].copy()
         total = h[C:C + C * F].view(np.float64).reshape(C, F).copy()
