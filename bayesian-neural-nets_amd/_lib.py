@@ -553,3 +553,9 @@ def check(rc, what):
     if rc != 0:
         msg = lib().lbbnn_error_string(rc)
         raise RuntimeError("bnn_amd: %s failed (%d): %s" % (what, rc, msg.decode() if msg else "?"))
+
+
+def launch(dev, name: str, *args):
+    """One library call on ``dev``'s current stream (its last argument), checked."""
+    import torch
+    check(getattr(lib(), name)(*args, torch.cuda.current_stream(dev).cuda_stream), name)

@@ -168,11 +168,8 @@ class _BaseDrawFn(torch.autograd.Function):
             g_out = torch.zeros_like(out)
         if act == "log_softmax":
             from . import losses
-            ent = losses._LOGITS_GRAD.pop(out.data_ptr(), None)
-            if ent is not None and ent[0] == g_out.data_ptr():
-                g_out = ent[1]                                 # formed by the loss's own backward launch
-            else:
-                g_out = ops.log_softmax_backward(g_out, out)
+            left = losses._HEAD_GRAD.take(out, g_out)          # formed by the loss's own backward launch (losses._Handover)
+            g_out = left if left is not None else ops.log_softmax_backward(g_out, out)
         relu = act == "relu"
         want_gx = bool(ctx.needs_input_grad[1])
         gm, _, gmT, _, g_sum, _ = ops.output_grad(g_out.contiguous(), out=out if relu else None, relu=relu, want_g=want_gx)

@@ -12,6 +12,7 @@
 // lbbnn_sigmoid_backward applied to g_probs are the same bits.
 #include "lbbnn_device.h"
 #include "lbbnn_internal.h"
+#include "train_totals.h"
 
 #pragma clang fp contract(off)
 
@@ -36,9 +37,9 @@ __global__ __launch_bounds__(256) void binary_head_kernel(const float* logits, i
     }
 }
 
-// The one pass of the BCE loss, shared by the plain and the monitored kernel so that both add the same terms in the same order:
-// element i of the (B, O) block goes to thread i % 1024, a thread adds its elements in rising i, block_sum<double, 16> adds the
-// threads.  Every thread returns the four block totals (the counts are whole numbers < 2^53: exact in fp64).
+// The one pass of the BCE loss: element i of the (B, O) block goes to thread i % 1024, a thread adds its elements in rising i,
+// block_sum<double, 16> adds the threads.  Every thread returns the four block totals (the counts are whole numbers < 2^53:
+// exact in fp64).
 struct BceSums { double s, n_ok, n_bad, n_nonfinite; };
 
 __device__ __forceinline__ BceSums bce_sums(const float* __restrict__ probs, int ldp, const float* __restrict__ target, int ldt,
@@ -70,57 +71,23 @@ __device__ __forceinline__ void bce_stats(int* stats, int accumulate, const BceS
     for (int k = 0; k < 4; ++k) stats[k] = (accumulate ? stats[k] : 0) + c[k];
 }
 
-__global__ __launch_bounds__(1024) void elbo_bce_loss_kernel(const float* __restrict__ probs, int ldp, const float* __restrict__ target,
-                                                             int ldt, long long n, int O, const float* kl, float kl_scale,
-                                                             float* loss, int* stats, int accumulate) {
+// MONITOR: plus the training monitor (train_totals.h): the same pass, so *loss and stats are the plain kernel's
+// bits.  The unit of account of the totals is one element (b, o): the four block totals of the pass are the counts of the step.
+// The totals are loaded in the tail.
+template <bool MONITOR>
+__global__ __launch_bounds__(1024) void elbo_bce_loss_kernel(const float* __restrict__ probs, int ldp,
+                                                             const float* __restrict__ target, int ldt, long long n, int O,
+                                                             const float* kl, float kl_scale, float* loss, int* stats,
+                                                             int accumulate, int64_t* totals, int32_t* guard) {
     __shared__ double scratch[16];
     const BceSums r = bce_sums(probs, ldp, target, ldt, n, O, scratch);
     if (threadIdx.x == 0) {
-        *loss = (float)(r.s + (kl ? (double)(*kl) * (double)kl_scale : 0.0));
+        [[maybe_unused]] MonitorWords pre;
+        if constexpr (MONITOR) pre = monitor_preload(totals);
+        const TrainStep st = {r.s, kl_term_of(kl, kl_scale), n, (int64_t)r.n_ok, (int64_t)r.n_bad, (int64_t)r.n_nonfinite};
+        *loss = loss_of(st.nll, st.kl_term);
         if (stats) bce_stats(stats, accumulate, r, n);
-    }
-}
-
-// elbo_bce_loss_kernel plus the training monitor: the same pass, so *loss and stats are its bits.  The unit of
-// account of the totals is one element (b, o): the four block totals of the pass are the counts of the step.  One workgroup,
-// launches of one stream ordered: thread 0 adds to the totals with plain loads and stores -- no atomics, the same bits from run
-// to run.
-__global__ __launch_bounds__(1024) void elbo_bce_loss_monitor_kernel(const float* __restrict__ probs, int ldp,
-                                                                     const float* __restrict__ target, int ldt, long long n, int O,
-                                                                     const float* kl, float kl_scale, float* loss, int* stats,
-                                                                     int accumulate, int64_t* totals, int32_t* guard) {
-    __shared__ double scratch[16];
-    const BceSums r = bce_sums(probs, ldp, target, ldt, n, O, scratch);
-    if (threadIdx.x == 0) {
-        int64_t cnt[LBBNN_MONITOR_COUNTS];
-        double sum[LBBNN_MONITOR_SUMS];
-        double* sums = reinterpret_cast<double*>(totals + LBBNN_MONITOR_COUNTS);
-#pragma unroll
-        for (int q = 0; q < LBBNN_MONITOR_COUNTS; ++q) cnt[q] = totals[q];      // every load ahead of the first store
-#pragma unroll
-        for (int q = 0; q < LBBNN_MONITOR_SUMS; ++q) sum[q] = sums[q];
-        const double kl_term = kl ? (double)(*kl) * (double)kl_scale : 0.0;
-        const float lf = (float)(r.s + kl_term);
-        const bool ok = isfinite(lf);
-        const int64_t bad = (int64_t)r.n_bad;
-        *loss = lf;
-        if (stats) bce_stats(stats, accumulate, r, n);
-        if (guard) *guard = ok ? 0 : 1;
-        totals[LBBNN_MONITOR_STEPS] = cnt[LBBNN_MONITOR_STEPS] + 1;
-        totals[LBBNN_MONITOR_ROWS] = cnt[LBBNN_MONITOR_ROWS] + n;
-        totals[LBBNN_MONITOR_CORRECT] = cnt[LBBNN_MONITOR_CORRECT] + (int64_t)r.n_ok;
-        totals[LBBNN_MONITOR_BAD_TARGETS] = cnt[LBBNN_MONITOR_BAD_TARGETS] + bad;
-        totals[LBBNN_MONITOR_NONFINITE_ROWS] = cnt[LBBNN_MONITOR_NONFINITE_ROWS] + (int64_t)r.n_nonfinite;
-        if (ok) {                                                 // (LBBNN_MONITOR_SKIPPED_STEPS is the optimizer's word: not written)
-            totals[LBBNN_MONITOR_NLL_ROWS] = cnt[LBBNN_MONITOR_NLL_ROWS] + (n - bad);
-            sums[LBBNN_MONITOR_NLL_SUM] = sum[LBBNN_MONITOR_NLL_SUM] + r.s;
-            sums[LBBNN_MONITOR_KL_TERM_SUM] = sum[LBBNN_MONITOR_KL_TERM_SUM] + kl_term;
-            sums[LBBNN_MONITOR_LOSS_SUM] = sum[LBBNN_MONITOR_LOSS_SUM] + (r.s + kl_term);
-        } else {
-            totals[LBBNN_MONITOR_NONFINITE_STEPS] = cnt[LBBNN_MONITOR_NONFINITE_STEPS] + 1;
-        }
-        sums[LBBNN_MONITOR_LAST_NLL] = r.s;
-        sums[LBBNN_MONITOR_LAST_LOSS] = (double)lf;
+        if constexpr (MONITOR) monitor_commit(totals, guard, pre, st);
     }
 }
 
@@ -137,7 +104,7 @@ __global__ __launch_bounds__(256) void elbo_bce_loss_backward_kernel(const float
         g_probs[i] = gp;
         if (g_logits) g_logits[i] = target_ok(y) ? gp * d : 0.f;
     }
-    if (g_kl && blockIdx.x == 0 && threadIdx.x == 0) *g_kl = gv * kl_scale;
+    store_g_kl(g_kl, gv, kl_scale);
 }
 
 __global__ __launch_bounds__(256) void sigmoid_backward_kernel(const float* g, int ldg, const float* probs, int ldp, float* out,
@@ -150,10 +117,6 @@ __global__ __launch_bounds__(256) void sigmoid_backward_kernel(const float* g, i
     }
 }
 
-inline bool off4(const void* p) { return ((uintptr_t)p & 3) != 0; }
-inline int grid_for(long long n) { const long long b = (n + 255) / 256; return (int)(b < 1024 ? b : 1024); }
-inline bool bad_shape(int B, int O) { return B < 0 || O < 1 || O > 16 || (long long)B * O > 0x7FFFFFFFLL; }
-
 }  // namespace
 
 extern "C" int lbbnn_binary_head(const float* logits, int ldi, int B, int O, float* probs, int ldp, float* logp2, int ld2,
@@ -161,7 +124,7 @@ extern "C" int lbbnn_binary_head(const float* logits, int ldi, int B, int O, flo
     if (!logits || (!probs && !logp2)) return LBBNN_E_NULL;
     if (bad_shape(B, O) || ldi < O || (probs && ldp < O)) return LBBNN_E_SHAPE;
     if (logp2 && (O != 1 || ld2 < 2)) return LBBNN_E_SHAPE;
-    if (off4(logits) || off4(probs) || off4(logp2)) return LBBNN_E_ALIGN;
+    if (off(logits, 4) || off(probs, 4) || off(logp2, 4)) return LBBNN_E_ALIGN;
     if (B == 0) return 0;
     const long long n = (long long)B * O;
     hipLaunchKernelGGL(binary_head_kernel, dim3(grid_for(n)), dim3(256), 0, static_cast<hipStream_t>(stream), logits, ldi, n, O,
@@ -173,9 +136,9 @@ extern "C" int lbbnn_elbo_bce_loss(const float* probs, int ldp, const float* tar
                                    float kl_scale, float* loss, int* stats, int accumulate, void* stream) {
     if (!probs || !target || !loss) return LBBNN_E_NULL;
     if (bad_shape(B, O) || ldp < O || ldt < O) return LBBNN_E_SHAPE;
-    if (off4(probs) || off4(target) || off4(kl) || off4(loss) || off4(stats)) return LBBNN_E_ALIGN;
-    hipLaunchKernelGGL(elbo_bce_loss_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), probs, ldp, target, ldt,
-                       (long long)B * O, O, kl, kl_scale, loss, stats, accumulate);
+    if (off(probs, 4) || off(target, 4) || off(kl, 4) || off(loss, 4) || off(stats, 4)) return LBBNN_E_ALIGN;
+    hipLaunchKernelGGL(elbo_bce_loss_kernel<false>, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), probs, ldp, target,
+                       ldt, (long long)B * O, O, kl, kl_scale, loss, stats, accumulate, (int64_t*)nullptr, (int32_t*)nullptr);
     return (int)hipGetLastError();
 }
 
@@ -184,9 +147,9 @@ extern "C" int lbbnn_elbo_bce_loss_monitor(const float* probs, int ldp, const fl
                                            int32_t* guard, void* stream) {
     if (!probs || !target || !loss || !totals) return LBBNN_E_NULL;
     if (bad_shape(B, O) || B < 1 || ldp < O || ldt < O) return LBBNN_E_SHAPE;
-    if (off4(probs) || off4(target) || off4(kl) || off4(loss) || off4(stats) || off4(guard) || ((uintptr_t)totals & 7))
+    if (off(probs, 4) || off(target, 4) || off(kl, 4) || off(loss, 4) || off(stats, 4) || off(guard, 4) || off(totals, 8))
         return LBBNN_E_ALIGN;
-    hipLaunchKernelGGL(elbo_bce_loss_monitor_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), probs, ldp, target,
+    hipLaunchKernelGGL(elbo_bce_loss_kernel<true>, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), probs, ldp, target,
                        ldt, (long long)B * O, O, kl, kl_scale, loss, stats, accumulate, totals, guard);
     return (int)hipGetLastError();
 }
@@ -195,7 +158,7 @@ extern "C" int lbbnn_elbo_bce_loss_backward(const float* g, const float* probs, 
                                             float kl_scale, float* g_probs, float* g_logits, float* g_kl, void* stream) {
     if (!g || !probs || !target || !g_probs) return LBBNN_E_NULL;
     if (bad_shape(B, O) || ldp < O || ldt < O) return LBBNN_E_SHAPE;
-    if (off4(g) || off4(probs) || off4(target) || off4(g_probs) || off4(g_logits) || off4(g_kl)) return LBBNN_E_ALIGN;
+    if (off(g, 4) || off(probs, 4) || off(target, 4) || off(g_probs, 4) || off(g_logits, 4) || off(g_kl, 4)) return LBBNN_E_ALIGN;
     const long long n = (long long)B * O;
     // (an empty batch still writes g_kl: one workgroup whose loop runs zero times)
     hipLaunchKernelGGL(elbo_bce_loss_backward_kernel, dim3(n ? grid_for(n) : 1), dim3(256), 0, static_cast<hipStream_t>(stream), g,
@@ -207,7 +170,7 @@ extern "C" int lbbnn_sigmoid_backward(const float* g, int ldg, const float* prob
                                       void* stream) {
     if (!g || !probs || !out) return LBBNN_E_NULL;
     if (bad_shape(B, O) || ldg < O || ldp < O || ldo < O) return LBBNN_E_SHAPE;
-    if (off4(g) || off4(probs) || off4(out)) return LBBNN_E_ALIGN;
+    if (off(g, 4) || off(probs, 4) || off(out, 4)) return LBBNN_E_ALIGN;
     if (B == 0) return 0;
     const long long n = (long long)B * O;
     hipLaunchKernelGGL(sigmoid_backward_kernel, dim3(grid_for(n)), dim3(256), 0, static_cast<hipStream_t>(stream), g, ldg, probs,

@@ -72,8 +72,6 @@ inline int launch_column_sums(const void* work, long long nblk, int ncols, doubl
     return (int)hipGetLastError();
 }
 
-inline bool off(const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) != 0; }
-
 // The running totals come all (with `work`) or none: 1, 0, or -1 when only some are there.
 inline int totals_given(std::initializer_list<const void*> totals, const void* work) {
     bool any = false, all = work != nullptr;

@@ -14,6 +14,7 @@
 // (deterministic), no atomics.
 #include "lbbnn_device.h"
 #include "lbbnn_internal.h"
+#include "train_totals.h"
 
 #pragma clang fp contract(off)
 
@@ -25,10 +26,9 @@ constexpr float kLog2Pi = 1.8378770664093453f;
 
 __device__ __forceinline__ bool target_ok(float y) { return isfinite(y); }                // false for NaN, +inf, -inf
 
-// The one pass of the loss, shared by the plain and the monitored kernel so that both add the same terms in the same order.
-// The first T = (1024 / O) * O threads work, thread t on the elements t, t + T, t + 2 T, ... in rising order: all of them lie
-// in column t % O, so a thread's sum of dlv belongs to one column.  Every sum is reduced the same way: the fixed wave butterfly
-// (wave_sum), the 16 wave totals through LDS, added in wave order by ONE thread after the workgroup's single barrier -- thread 0
+// The one pass of the loss.  The first T = (1024 / O) * O threads work, thread t on the elements t, t + T, t + 2 T, ... in
+// rising order: all of them lie in column t % O, so a thread's sum of dlv belongs to one column.  Every sum is reduced the
+// same way: the fixed wave butterfly (wave_sum), the 16 wave totals through LDS, added in wave order by ONE thread after the workgroup's single barrier -- thread 0
 // for the six totals (the counts are whole numbers < 2^53: exact in fp64), thread o < O for column o, whose wave totals are the
 // wave sums of the threads with t % O == o (the others add 0.0).  The totals are valid on thread 0, `col` on thread o < O.
 struct GaussSums { double s, se, ae, n_in, n_bad, n_nonfinite, col; };
@@ -94,7 +94,7 @@ struct GaussPre { double kl_term, st[4]; };
 
 __device__ __forceinline__ GaussPre gauss_preload(const float* kl, float kl_scale, const double* stats) {
     GaussPre p = {0.0, {0.0, 0.0, 0.0, 0.0}};
-    if (kl) p.kl_term = (double)(*kl) * (double)kl_scale;
+    p.kl_term = kl_term_of(kl, kl_scale);
     if (stats) { p.st[0] = stats[0]; p.st[1] = stats[1]; p.st[2] = stats[2]; p.st[3] = stats[3]; }
     return p;
 }
@@ -106,69 +106,29 @@ __device__ __forceinline__ void gauss_stats(double* stats, const GaussPre& p, co
     stats[3] = p.st[3] + r.n_bad;
 }
 
+// MONITOR: plus the training monitor (train_totals.h): the same pass, so *loss, stats and lv_cols are the plain kernel's bits.
+// The unit of account of the totals is one element (b, o), as for the BCE loss; `correct` counts the elements inside one
+// standard deviation.  The totals are loaded with gauss_preload's words, at the start of the kernel.
+template <bool MONITOR>
 __global__ __launch_bounds__(1024) void elbo_gaussian_loss_kernel(const float* __restrict__ mean, int ldm,
                                                                   const float* __restrict__ target, int ldt,
                                                                   const float* __restrict__ log_var, int ldv, long long n, int O,
                                                                   const float* kl, float kl_scale, float* loss, double* stats,
-                                                                  float* lv_cols) {
+                                                                  float* lv_cols, int64_t* totals, int32_t* guard) {
     __shared__ double red[kRed][16];
     GaussPre pre = {0.0, {0.0, 0.0, 0.0, 0.0}};
-    if (threadIdx.x == 0) pre = gauss_preload(kl, kl_scale, stats);
-    const GaussSums r = gauss_sums(mean, ldm, target, ldt, log_var, ldv, n, O, lv_cols != nullptr, red);
-    if (lv_cols && threadIdx.x < O) lv_cols[threadIdx.x] = (float)r.col;
-    if (threadIdx.x == 0) {
-        *loss = (float)(r.s + pre.kl_term);
-        if (stats) gauss_stats(stats, pre, r, n);
-    }
-}
-
-// elbo_gaussian_loss_kernel plus the training monitor: the same pass, so *loss, stats and lv_cols are its bits.  The unit of
-// account of the totals is one element (b, o), as for the BCE loss; `correct` counts the elements inside one standard deviation.
-// One workgroup, launches of one stream ordered: thread 0 adds to the totals with plain loads (every one of them at the start of
-// the kernel, ahead of the first store) and stores -- no atomics.
-__global__ __launch_bounds__(1024) void elbo_gaussian_loss_monitor_kernel(const float* __restrict__ mean, int ldm,
-                                                                          const float* __restrict__ target, int ldt,
-                                                                          const float* __restrict__ log_var, int ldv, long long n,
-                                                                          int O, const float* kl, float kl_scale, float* loss,
-                                                                          double* stats, float* lv_cols, int64_t* totals,
-                                                                          int32_t* guard) {
-    __shared__ double red[kRed][16];
-    GaussPre pre = {0.0, {0.0, 0.0, 0.0, 0.0}};
-    int64_t cnt[LBBNN_MONITOR_COUNTS] = {0, 0, 0, 0, 0, 0, 0, 0};
-    double sum[LBBNN_MONITOR_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    double* sums = reinterpret_cast<double*>(totals + LBBNN_MONITOR_COUNTS);
+    [[maybe_unused]] MonitorWords words = {{0, 0, 0, 0, 0, 0, 0, 0}, {0.0, 0.0, 0.0, 0.0, 0.0}};
     if (threadIdx.x == 0) {
         pre = gauss_preload(kl, kl_scale, stats);
-#pragma unroll
-        for (int q = 0; q < LBBNN_MONITOR_COUNTS; ++q) cnt[q] = totals[q];
-#pragma unroll
-        for (int q = 0; q < LBBNN_MONITOR_SUMS; ++q) sum[q] = sums[q];
+        if constexpr (MONITOR) words = monitor_preload(totals);
     }
     const GaussSums r = gauss_sums(mean, ldm, target, ldt, log_var, ldv, n, O, lv_cols != nullptr, red);
     if (lv_cols && threadIdx.x < O) lv_cols[threadIdx.x] = (float)r.col;
     if (threadIdx.x == 0) {
-        const double kl_term = pre.kl_term;
-        const float lf = (float)(r.s + kl_term);
-        const bool ok = isfinite(lf);
-        const int64_t bad = (int64_t)r.n_bad;
-        *loss = lf;
+        const TrainStep st = {r.s, pre.kl_term, n, (int64_t)r.n_in, (int64_t)r.n_bad, (int64_t)r.n_nonfinite};
+        *loss = loss_of(st.nll, st.kl_term);
         if (stats) gauss_stats(stats, pre, r, n);
-        if (guard) *guard = ok ? 0 : 1;
-        totals[LBBNN_MONITOR_STEPS] = cnt[LBBNN_MONITOR_STEPS] + 1;
-        totals[LBBNN_MONITOR_ROWS] = cnt[LBBNN_MONITOR_ROWS] + n;
-        totals[LBBNN_MONITOR_CORRECT] = cnt[LBBNN_MONITOR_CORRECT] + (int64_t)r.n_in;
-        totals[LBBNN_MONITOR_BAD_TARGETS] = cnt[LBBNN_MONITOR_BAD_TARGETS] + bad;
-        totals[LBBNN_MONITOR_NONFINITE_ROWS] = cnt[LBBNN_MONITOR_NONFINITE_ROWS] + (int64_t)r.n_nonfinite;
-        if (ok) {                                                 // (LBBNN_MONITOR_SKIPPED_STEPS is the optimizer's word: not written)
-            totals[LBBNN_MONITOR_NLL_ROWS] = cnt[LBBNN_MONITOR_NLL_ROWS] + (n - bad);
-            sums[LBBNN_MONITOR_NLL_SUM] = sum[LBBNN_MONITOR_NLL_SUM] + r.s;
-            sums[LBBNN_MONITOR_KL_TERM_SUM] = sum[LBBNN_MONITOR_KL_TERM_SUM] + kl_term;
-            sums[LBBNN_MONITOR_LOSS_SUM] = sum[LBBNN_MONITOR_LOSS_SUM] + (r.s + kl_term);
-        } else {
-            totals[LBBNN_MONITOR_NONFINITE_STEPS] = cnt[LBBNN_MONITOR_NONFINITE_STEPS] + 1;
-        }
-        sums[LBBNN_MONITOR_LAST_NLL] = r.s;
-        sums[LBBNN_MONITOR_LAST_LOSS] = (double)lf;
+        if constexpr (MONITOR) monitor_commit(totals, guard, words, st);
     }
 }
 
@@ -191,16 +151,9 @@ __global__ __launch_bounds__(256) void elbo_gaussian_loss_backward_kernel(const 
             g_lv[i] = ok ? (gv * 0.5f) * (1.f - (d * d) * iv) : 0.f;
         }
     }
-    if (blockIdx.x == 0) {
-        if (g_lv && !ldv && threadIdx.x < O) g_lv[threadIdx.x] = gv * lv_cols[threadIdx.x];
-        if (g_kl && threadIdx.x == 0) *g_kl = gv * kl_scale;
-    }
+    if (g_lv && !ldv && blockIdx.x == 0 && threadIdx.x < O) g_lv[threadIdx.x] = gv * lv_cols[threadIdx.x];
+    store_g_kl(g_kl, gv, kl_scale);
 }
-
-inline bool off4(const void* p) { return ((uintptr_t)p & 3) != 0; }
-inline bool off8(const void* p) { return ((uintptr_t)p & 7) != 0; }
-inline int grid_for(long long n) { const long long b = (n + 255) / 256; return (int)(b < 1024 ? b : 1024); }
-inline bool bad_shape(int B, int O) { return B < 0 || O < 1 || O > 16 || (long long)B * O > 0x7FFFFFFFLL; }
 
 }  // namespace
 
@@ -210,9 +163,11 @@ extern "C" int lbbnn_elbo_gaussian_loss(const float* mean, int ldm, const float*
     if (!mean || !target || !log_var || !loss) return LBBNN_E_NULL;
     if (bad_shape(B, O) || ldm < O || ldt < O || (ldv != 0 && ldv < O)) return LBBNN_E_SHAPE;
     if (lv_cols && ldv != 0) return LBBNN_E_SHAPE;
-    if (off4(mean) || off4(target) || off4(log_var) || off4(kl) || off4(loss) || off4(lv_cols) || off8(stats)) return LBBNN_E_ALIGN;
-    hipLaunchKernelGGL(elbo_gaussian_loss_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), mean, ldm, target, ldt,
-                       log_var, ldv, (long long)B * O, O, kl, kl_scale, loss, stats, lv_cols);
+    if (off(mean, 4) || off(target, 4) || off(log_var, 4) || off(kl, 4) || off(loss, 4) || off(lv_cols, 4) || off(stats, 8))
+        return LBBNN_E_ALIGN;
+    hipLaunchKernelGGL(elbo_gaussian_loss_kernel<false>, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), mean, ldm,
+                       target, ldt, log_var, ldv, (long long)B * O, O, kl, kl_scale, loss, stats, lv_cols, (int64_t*)nullptr,
+                       (int32_t*)nullptr);
     return (int)hipGetLastError();
 }
 
@@ -222,10 +177,10 @@ extern "C" int lbbnn_elbo_gaussian_loss_monitor(const float* mean, int ldm, cons
     if (!mean || !target || !log_var || !loss || !totals) return LBBNN_E_NULL;
     if (bad_shape(B, O) || B < 1 || ldm < O || ldt < O || (ldv != 0 && ldv < O)) return LBBNN_E_SHAPE;
     if (lv_cols && ldv != 0) return LBBNN_E_SHAPE;
-    if (off4(mean) || off4(target) || off4(log_var) || off4(kl) || off4(loss) || off4(lv_cols) || off8(stats) || off4(guard) ||
-        off8(totals))
+    if (off(mean, 4) || off(target, 4) || off(log_var, 4) || off(kl, 4) || off(loss, 4) || off(lv_cols, 4) || off(stats, 8) ||
+        off(guard, 4) || off(totals, 8))
         return LBBNN_E_ALIGN;
-    hipLaunchKernelGGL(elbo_gaussian_loss_monitor_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), mean, ldm,
+    hipLaunchKernelGGL(elbo_gaussian_loss_kernel<true>, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), mean, ldm,
                        target, ldt, log_var, ldv, (long long)B * O, O, kl, kl_scale, loss, stats, lv_cols, totals, guard);
     return (int)hipGetLastError();
 }
@@ -236,7 +191,8 @@ extern "C" int lbbnn_elbo_gaussian_loss_backward(const float* g, const float* me
     if (!g || !mean || !target || !log_var || !g_mean) return LBBNN_E_NULL;
     if (g_lv && ldv == 0 && !lv_cols) return LBBNN_E_NULL;
     if (bad_shape(B, O) || ldm < O || ldt < O || (ldv != 0 && ldv < O)) return LBBNN_E_SHAPE;
-    if (off4(g) || off4(mean) || off4(target) || off4(log_var) || off4(lv_cols) || off4(g_mean) || off4(g_lv) || off4(g_kl))
+    if (off(g, 4) || off(mean, 4) || off(target, 4) || off(log_var, 4) || off(lv_cols, 4) || off(g_mean, 4) || off(g_lv, 4) ||
+        off(g_kl, 4))
         return LBBNN_E_ALIGN;
     const long long n = (long long)B * O;
     // (an empty batch still writes g_kl and a shared g_lv: one workgroup whose loop runs zero times)

@@ -70,9 +70,11 @@ struct FinalizePiggy { FinalizeArgs l[LBBNN_MAX_LAYERS]; int active[LBBNN_MAX_LA
     } while (0)
 static_assert(LBBNN_MAX_LAYERS == 4, "LBBNN_SELECT_LAYER enumerates 4 layers");
 
-// the alignment the entry points ask of a pointer: 16 B for what a kernel reads or writes as float4 / uint4, 4 B otherwise
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+// THE alignment test of the entry points: p is off an n-byte boundary (n a power of two; a null pointer never is).  16 B for
+// what a kernel reads or writes as float4 / uint4, 8 B for int64 / double words, 4 B otherwise.
+inline bool off(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) != 0; }
+inline bool aligned16(const void* p) { return !off(p, 16); }
+inline bool aligned4(const void* p) { return !off(p, 4); }
 
 // Fill / validate helpers (return LBBNN_E_* or 0); launchers return hipGetLastError().
 LBBNN_HIDDEN int make_weight_pass_args(WeightPassArgs& a, const float* mu, const float* rho, const float* lambdal,

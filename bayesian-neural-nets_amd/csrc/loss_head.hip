@@ -10,6 +10,7 @@
 // One workgroup / one pass each; sums in a fixed order (deterministic).
 #include "lbbnn_device.h"
 #include "lbbnn_internal.h"
+#include "train_totals.h"
 
 namespace {
 
@@ -24,15 +25,15 @@ __global__ __launch_bounds__(1024) void elbo_loss_kernel(const float* __restrict
         if (t >= 0 && t < C) s -= (double)logp[(size_t)b * ldp + t];
     }
     s = block_sum<double, 16>(s, scratch);
-    if (threadIdx.x == 0) *loss = (float)(s + (kl ? (double)(*kl) * (double)kl_scale : 0.0));
+    if (threadIdx.x == 0) *loss = loss_of(s, kl_term_of(kl, kl_scale));
 }
 
 // elbo_loss_kernel plus the training monitor.  The nll sum is elbo_loss_kernel's, term for term (same rows per thread, same
 // order, same block_sum), so *loss has its bits.  A thread reads its row's C log-probabilities in batches of 16 independent
 // loads (the target's term is picked out of the registers instead of being loaded behind the target), finds the arg-max by
 // numpy.argmax's rule (a NaN is the maximum, the lowest index wins a tie) and whether all C values are finite.  The three row
-// counts are wave sums left in LDS ahead of block_sum's barriers.  One workgroup, launches of one stream ordered: thread 0 adds
-// to the totals with plain loads and stores -- no atomics, the same bits from run to run.
+// counts are wave sums left in LDS ahead of block_sum's barriers.  The unit of account of the totals is one row; they are
+// loaded in the tail (train_totals.h).
 __global__ __launch_bounds__(1024) void elbo_loss_monitor_kernel(const float* __restrict__ logp, int ldp,
                                                                  const int64_t* __restrict__ target, int B, int C, const float* kl,
                                                                  float kl_scale, float* loss, int64_t* totals, int32_t* guard) {
@@ -82,33 +83,10 @@ __global__ __launch_bounds__(1024) void elbo_loss_monitor_kernel(const float* __
         int tot[3] = {0, 0, 0};
         for (int q = 0; q < 3; ++q)
             for (int w = 0; w < 16; ++w) tot[q] += counts[q][w];
-        int64_t cnt[LBBNN_MONITOR_COUNTS];
-        double sum[LBBNN_MONITOR_SUMS];
-        double* sums = reinterpret_cast<double*>(totals + LBBNN_MONITOR_COUNTS);
-#pragma unroll
-        for (int q = 0; q < LBBNN_MONITOR_COUNTS; ++q) cnt[q] = totals[q];      // every load ahead of the first store
-#pragma unroll
-        for (int q = 0; q < LBBNN_MONITOR_SUMS; ++q) sum[q] = sums[q];
-        const double kl_term = kl ? (double)(*kl) * (double)kl_scale : 0.0;
-        const float lf = (float)(s + kl_term);
-        const bool ok = isfinite(lf);
-        *loss = lf;
-        if (guard) *guard = ok ? 0 : 1;
-        totals[LBBNN_MONITOR_STEPS] = cnt[LBBNN_MONITOR_STEPS] + 1;
-        totals[LBBNN_MONITOR_ROWS] = cnt[LBBNN_MONITOR_ROWS] + B;
-        totals[LBBNN_MONITOR_CORRECT] = cnt[LBBNN_MONITOR_CORRECT] + tot[0];
-        totals[LBBNN_MONITOR_BAD_TARGETS] = cnt[LBBNN_MONITOR_BAD_TARGETS] + tot[1];
-        totals[LBBNN_MONITOR_NONFINITE_ROWS] = cnt[LBBNN_MONITOR_NONFINITE_ROWS] + tot[2];
-        if (ok) {                                                 // (LBBNN_MONITOR_SKIPPED_STEPS is the optimizer's word: not written)
-            totals[LBBNN_MONITOR_NLL_ROWS] = cnt[LBBNN_MONITOR_NLL_ROWS] + (B - tot[1]);
-            sums[LBBNN_MONITOR_NLL_SUM] = sum[LBBNN_MONITOR_NLL_SUM] + s;
-            sums[LBBNN_MONITOR_KL_TERM_SUM] = sum[LBBNN_MONITOR_KL_TERM_SUM] + kl_term;
-            sums[LBBNN_MONITOR_LOSS_SUM] = sum[LBBNN_MONITOR_LOSS_SUM] + (s + kl_term);
-        } else {
-            totals[LBBNN_MONITOR_NONFINITE_STEPS] = cnt[LBBNN_MONITOR_NONFINITE_STEPS] + 1;
-        }
-        sums[LBBNN_MONITOR_LAST_NLL] = s;
-        sums[LBBNN_MONITOR_LAST_LOSS] = (double)lf;
+        const MonitorWords pre = monitor_preload(totals);
+        const TrainStep st = {s, kl_term_of(kl, kl_scale), B, tot[0], tot[1], tot[2]};
+        *loss = loss_of(st.nll, st.kl_term);
+        monitor_commit(totals, guard, pre, st);
     }
 }
 
@@ -120,7 +98,7 @@ __global__ __launch_bounds__(256) void elbo_loss_backward_kernel(const float* g,
         const int b = i / C, c = i - b * C;
         g_logp[i] = (target[b] == c) ? -gv : 0.f;
     }
-    if (g_kl && blockIdx.x == 0 && threadIdx.x == 0) *g_kl = gv * kl_scale;
+    store_g_kl(g_kl, gv, kl_scale);
 }
 
 // ... and, in the same launch, what lbbnn_log_softmax_backward makes of that gradient when the log-probabilities are the
@@ -138,7 +116,7 @@ __global__ __launch_bounds__(256) void elbo_loss_backward_logits_kernel(const fl
         g_logp[i] = gl;
         g_logits[i] = gl - expf(logp[(size_t)b * ldp + c]) * s;
     }
-    if (g_kl && blockIdx.x == 0 && threadIdx.x == 0) *g_kl = gv * kl_scale;
+    store_g_kl(g_kl, gv, kl_scale);
 }
 
 // thread per row (C <= 64)

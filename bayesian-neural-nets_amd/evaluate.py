@@ -555,10 +555,10 @@ def _mean_rows(mean_outputs: torch.Tensor, B: int, C: int, dev):
 
 
 def _launch(dev, name: str, *args):
-    """One library call on ``dev``'s current stream (its last argument), checked."""
+    """``_lib.launch`` with ``dev`` the current device for the call."""
     from . import _lib
     with torch.cuda.device(dev):
-        _lib.check(getattr(_lib.lib(), name)(*args, torch.cuda.current_stream(dev).cuda_stream), name)
+        _lib.launch(dev, name, *args)
 
 
 class _DeviceTotals:

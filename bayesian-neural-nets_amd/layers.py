@@ -252,11 +252,9 @@ class _BayesLinearFn(torch.autograd.Function):
         explicit = ctx.saved.get("noise") or {}
         if ctx.saved.get("lsm"):
             from . import losses
-            ent = losses._LOGITS_GRAD.pop(out.data_ptr(), None)
-            if ent is not None and ent[0] == g_out.data_ptr():
-                g_out = ent[1]                                        # formed by the loss's own backward launch (losses._LOGITS_GRAD)
-            else:
-                g_out = ops.log_softmax_backward(g_out, out)          # grad wrt log-probabilities -> grad wrt the logits
+            # grad wrt log-probabilities -> grad wrt the logits: as the loss's own backward launch left it (losses._Handover), or here
+            left = losses._HEAD_GRAD.take(out, g_out)
+            g_out = left if left is not None else ops.log_softmax_backward(g_out, out)
         planar = layer._mnf and layer._check_flows() == "planar"
         dense = layer._mnf and ctx.saved.get("dense_save") is not None
         # With the vector chains deferred (they are the only readers of the column sums Sum_b G_m / G_v, dz_k, dz_2, dr0_c)
@@ -474,7 +472,7 @@ def _x_operand_pair(x, gT, g_vT, module=None):
 
 class _SigmoidHeadFn(torch.autograd.Function):
     """The binary head of a ``head="sigmoid"`` network in the training forward: lbbnn_binary_head on the last layer's logits.
-    Backward: the gradient with respect to the logits as the fused loss left it (losses._BCE_LOGITS_GRAD) when the gradient it
+    Backward: the gradient with respect to the logits as the fused loss left it (losses._Handover) when the gradient it
     receives is the very tensor ``elbo_bce_loss`` returned for these probabilities, else lbbnn_sigmoid_backward."""
 
     @staticmethod
@@ -487,12 +485,9 @@ class _SigmoidHeadFn(torch.autograd.Function):
     def backward(ctx, g):
         from . import losses
         (probs,) = ctx.saved_tensors
-        ent = losses._BCE_LOGITS_GRAD.pop(probs.data_ptr(), None)
-        if ent is not None and ent[0] == g.data_ptr():
-            losses.HANDOVER["taken"] += 1
-            return ent[1]
-        losses.HANDOVER["sigmoid_backward"] += 1
-        return ops.sigmoid_backward(g, probs)
+        left = losses._HEAD_GRAD.take(probs, g)
+        losses.HANDOVER["sigmoid_backward" if left is None else "taken"] += 1
+        return left if left is not None else ops.sigmoid_backward(g, probs)
 
 
 HEADS = ("log_softmax", "sigmoid", "identity")

@@ -23,11 +23,53 @@ from . import _lib
 _FUSE_LSM_BWD = _os.environ.get("LBBNN_FUSE_LSM_BWD", "1") != "0"     # A/B knob
 
 
-# Hand-over from the loss's backward to the head layer's backward: when the log-probabilities came out of a layer's fused
-# log_softmax, the loss backward forms the gradient with respect to the LOGITS in its own launch
-# (lbbnn_elbo_loss_backward_logits) and leaves it here under the log-probabilities' address; the layer's backward takes it if
-# the gradient it receives is the very tensor the loss returned, instead of launching lbbnn_log_softmax_backward.
-_LOGITS_GRAD = {}
+class _Handover:
+    """Hand-over from a loss's backward to the backward of the head that produced the loss's input.  When the log-probabilities
+    came out of a layer's fused log_softmax, or the probabilities out of ``layers._SigmoidHeadFn``, the loss backward forms the
+    gradient with respect to the LOGITS in its own launch (lbbnn_elbo_loss_backward_logits, lbbnn_elbo_bce_loss_backward) and
+    leaves it here; the head's backward takes it instead of launching lbbnn_log_softmax_backward / lbbnn_sigmoid_backward.
+
+    ``leave(out, g_out, g_logits)``: ``g_logits`` is for the node that produced ``out``, valid only against ``g_out``, the
+    gradient the loss returns for ``out``.  ``take(out, g)``: ``g_logits`` if ``g``, the gradient that node received, is that
+    very tensor, else None (something stood between the head and the loss: the caller runs its own backward kernel).
+
+    Why the addresses are enough: the entry HOLDS ``out`` and ``g_out``.  While it exists their storage cannot be freed and
+    handed to another tensor, so "same address" means "same tensor" (an address alone could be a reused block).  Entries live
+    for one backward pass: ``take`` removes the entry whether it matches or not, and the forward of the next fused loss
+    clears what no head asked for."""
+
+    def __init__(self):
+        self._held = {}
+
+    def __len__(self):
+        return len(self._held)
+
+    def clear(self):
+        self._held.clear()
+
+    def leave(self, out, g_out, g_logits):
+        self._held[out.data_ptr()] = (g_out.data_ptr(), g_logits, out, g_out)
+
+    def take(self, out, g):
+        ent = self._held.pop(out.data_ptr(), None)
+        return ent[1] if ent is not None and ent[0] == g.data_ptr() else None
+
+
+_HEAD_GRAD = _Handover()
+HANDOVER = {"taken": 0, "sigmoid_backward": 0}     # which way each sigmoid head's backward went
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _launch_loss(dev, name, head, monitor):
+    """The forward launch of a loss: ``name(*head)``, or with a monitor ``name``_monitor with the same head arguments plus the
+    monitor's two pointers."""
+    if monitor is None:
+        _lib.launch(dev, name, *head)
+    else:
+        _lib.launch(dev, name + "_monitor", *head, monitor._totals.data_ptr(), monitor._guard.data_ptr())
 
 
 class TrainMonitor:
@@ -123,19 +165,11 @@ class _ElboLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, log_probs, target, kl, scale, monitor):
         B, C = log_probs.shape
-        _LOGITS_GRAD.clear()                       # entries live for one backward pass only
+        _HEAD_GRAD.clear()                         # entries live for one backward pass only
         lp = log_probs if log_probs.stride(1) == 1 else log_probs.contiguous()
         loss = torch.empty((), dtype=torch.float32, device=lp.device)
-        stream = torch.cuda.current_stream(lp.device).cuda_stream
-        if monitor is not None:
-            _lib.check(_lib.lib().lbbnn_elbo_loss_monitor(lp.data_ptr(), lp.stride(0), target.data_ptr(), B, C,
-                                                          kl.data_ptr() if kl is not None else None, float(scale), loss.data_ptr(),
-                                                          monitor._totals.data_ptr(), monitor._guard.data_ptr(), stream),
-                       "lbbnn_elbo_loss_monitor")
-        else:
-            _lib.check(_lib.lib().lbbnn_elbo_loss(lp.data_ptr(), lp.stride(0), target.data_ptr(), B, C,
-                                                  kl.data_ptr() if kl is not None else None, float(scale), loss.data_ptr(), stream),
-                       "lbbnn_elbo_loss")
+        head = (lp.data_ptr(), lp.stride(0), target.data_ptr(), B, C, _ptr(kl), float(scale), loss.data_ptr())
+        _launch_loss(lp.device, "lbbnn_elbo_loss", head, monitor)
         ctx.save_for_backward(target, lp)
         ctx.meta = (B, C, float(scale), kl is not None)
         return loss
@@ -147,19 +181,14 @@ class _ElboLossFn(torch.autograd.Function):
         g = g.contiguous()
         g_logp = torch.empty((B, C), dtype=torch.float32, device=g.device)
         g_kl = torch.empty((), dtype=torch.float32, device=g.device) if has_kl else None
-        stream = torch.cuda.current_stream(g.device).cuda_stream
         if _FUSE_LSM_BWD and C <= 64:
             g_logits = torch.empty((B, C), dtype=torch.float32, device=g.device)
-            _lib.check(_lib.lib().lbbnn_elbo_loss_backward_logits(g.data_ptr(), target.data_ptr(), lp.data_ptr(), lp.stride(0), B, C,
-                                                                  scale, g_logp.data_ptr(), g_logits.data_ptr(),
-                                                                  g_kl.data_ptr() if has_kl else None, stream),
-                       "lbbnn_elbo_loss_backward_logits")
-            # the entry HOLDS lp and g_logp: while it exists their storage cannot be freed and handed to another tensor, so
-            # "same address" in the head's backward means "same tensor" (an address alone could be a reused block)
-            _LOGITS_GRAD[lp.data_ptr()] = (g_logp.data_ptr(), g_logits, lp, g_logp)
+            _lib.launch(g.device, "lbbnn_elbo_loss_backward_logits", g.data_ptr(), target.data_ptr(), lp.data_ptr(), lp.stride(0),
+                        B, C, scale, g_logp.data_ptr(), g_logits.data_ptr(), _ptr(g_kl))
+            _HEAD_GRAD.leave(lp, g_logp, g_logits)
         else:
-            _lib.check(_lib.lib().lbbnn_elbo_loss_backward(g.data_ptr(), target.data_ptr(), B, C, scale, g_logp.data_ptr(),
-                                                           g_kl.data_ptr() if has_kl else None, stream), "lbbnn_elbo_loss_backward")
+            _lib.launch(g.device, "lbbnn_elbo_loss_backward", g.data_ptr(), target.data_ptr(), B, C, scale, g_logp.data_ptr(),
+                        _ptr(g_kl))
         return g_logp, None, g_kl, None, None
 
 
@@ -167,26 +196,36 @@ def _fused_kl(kl) -> bool:
     return kl is None or (torch.is_tensor(kl) and kl.is_cuda and kl.dtype == torch.float32 and kl.numel() == 1)
 
 
-def _check_monitored(log_probs, target, kl, monitor):
-    """A monitor rides in the fused forward launch: ValueError naming what keeps this call off that path."""
-    who = "bnn_amd: elbo_loss(monitor=...): "
+_BAD_KL = "kl must be None or a one-element float32 HIP tensor"
+
+
+def _check_monitored(loss, noun, units, x, kl, monitor, target=None):
+    """A monitor rides in the fused forward launch: ValueError naming what keeps this call of ``loss`` off that path.  ``x`` is
+    the loss's (B, ``units``) input, called ``noun``.  The order of the refusals is each loss's own and stays: with class-id
+    targets (``elbo_loss``) the device comes before the target and ``kl``, the element-wise losses refuse ``kl`` before the
+    device."""
+    def refuse(msg):
+        raise ValueError("bnn_amd: %s(monitor=...): %s" % (loss, msg))
+
     if not isinstance(monitor, TrainMonitor):
-        raise ValueError(who + "monitor must be a bnn_amd.TrainMonitor, got %s" % type(monitor).__name__)
-    if log_probs.dtype != torch.float32 or log_probs.dim() != 2:
-        raise ValueError(who + "log_probs must be float32 (B, classes), got %s %s" % (log_probs.dtype, tuple(log_probs.shape)))
-    if log_probs.shape[1] != monitor.classes:
-        raise ValueError(who + "log_probs has %d classes, the monitor was built for %d" % (log_probs.shape[1], monitor.classes))
-    if log_probs.shape[0] < 1:
-        raise ValueError(who + "an empty batch has no step to record")
-    if not log_probs.is_cuda:
-        raise ValueError(who + "the monitor lives in the fused HIP loss; log_probs is on %s" % log_probs.device)
-    if log_probs.device != monitor.device:
-        raise ValueError(who + "log_probs is on %s, the monitor on %s" % (log_probs.device, monitor.device))
-    if target.dtype != torch.int64 or not target.is_contiguous():
-        raise ValueError(who + "target must be contiguous int64 class ids, got %s with strides %s"
-                         % (target.dtype, tuple(target.stride())))
-    if not _fused_kl(kl):
-        raise ValueError(who + "kl must be None or a one-element float32 HIP tensor")
+        refuse("monitor must be a bnn_amd.TrainMonitor, got %s" % type(monitor).__name__)
+    if x.dtype != torch.float32 or x.dim() != 2:
+        refuse("%s must be float32 (B, %s), got %s %s" % (noun, units, x.dtype, tuple(x.shape)))
+    if x.shape[1] != monitor.classes:
+        refuse("%s has %d %s, the monitor was built for %d" % (noun, x.shape[1], units, monitor.classes))
+    if x.shape[0] < 1:
+        refuse("an empty batch has no step to record")
+    if target is None and not _fused_kl(kl):
+        refuse(_BAD_KL)
+    if not x.is_cuda:
+        refuse("the monitor lives in the fused HIP loss; %s is on %s" % (noun, x.device))
+    if x.device != monitor.device:
+        refuse("%s is on %s, the monitor on %s" % (noun, x.device, monitor.device))
+    if target is not None:
+        if target.dtype != torch.int64 or not target.is_contiguous():
+            refuse("target must be contiguous int64 class ids, got %s with strides %s" % (target.dtype, tuple(target.stride())))
+        if not _fused_kl(kl):
+            refuse(_BAD_KL)
 
 
 def elbo_loss(log_probs, target, kl=None, num_batches=1.0, *, monitor=None):
@@ -205,42 +244,25 @@ def elbo_loss(log_probs, target, kl=None, num_batches=1.0, *, monitor=None):
             raise ValueError("bnn_amd: elbo_loss: target has %d element(s), log_probs %d row(s)"
                              % (target.numel(), log_probs.shape[0]))
     if monitor is not None:
-        _check_monitored(log_probs, target, kl, monitor)
+        _check_monitored("elbo_loss", "log_probs", "classes", log_probs, kl, monitor, target)
         return _ElboLossFn.apply(log_probs, target, kl if kl is None else kl.reshape(()), 1.0 / float(num_batches), monitor)
     if (log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.dim() == 2 and target.dtype == torch.int64
-            and target.is_contiguous() and (kl is None or (torch.is_tensor(kl) and kl.is_cuda and kl.dtype == torch.float32
-                                                           and kl.numel() == 1))):
+            and target.is_contiguous() and _fused_kl(kl)):
         return _ElboLossFn.apply(log_probs, target, kl if kl is None else kl.reshape(()), 1.0 / float(num_batches), None)
     nll = F.nll_loss(log_probs, target, reduction="sum")
     return nll if kl is None else nll + kl / num_batches
-
-
-# The same hand-over for the binary head: the BCE loss backward forms the gradient with respect to the LOGITS in its own launch
-# when the probabilities are the very tensor a sigmoid head returned (layers._SigmoidHeadFn), and leaves it here under the
-# probabilities' address.  HANDOVER counts which way each head backward went.
-_BCE_LOGITS_GRAD = {}
-HANDOVER = {"taken": 0, "sigmoid_backward": 0}
 
 
 class _ElboBceLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, probs, target, kl, scale, stats, from_head, monitor=None):
         B, O = probs.shape
-        _BCE_LOGITS_GRAD.clear()                   # entries live for one backward pass only
+        _HEAD_GRAD.clear()                         # entries live for one backward pass only
         p = probs if (probs.stride(1) == 1 or O == 1) else probs.contiguous()
         loss = torch.empty((), dtype=torch.float32, device=p.device)
-        stream = torch.cuda.current_stream(p.device).cuda_stream
-        if monitor is not None:
-            _lib.check(_lib.lib().lbbnn_elbo_bce_loss_monitor(p.data_ptr(), p.stride(0) if B > 1 else O, target.data_ptr(), O, B, O,
-                                                              kl.data_ptr() if kl is not None else None, float(scale),
-                                                              loss.data_ptr(), stats.data_ptr() if stats is not None else None, 1,
-                                                              monitor._totals.data_ptr(), monitor._guard.data_ptr(), stream),
-                       "lbbnn_elbo_bce_loss_monitor")
-        else:
-            _lib.check(_lib.lib().lbbnn_elbo_bce_loss(p.data_ptr(), p.stride(0) if B > 1 else O, target.data_ptr(), O, B, O,
-                                                      kl.data_ptr() if kl is not None else None, float(scale), loss.data_ptr(),
-                                                      stats.data_ptr() if stats is not None else None, 1, stream),
-                       "lbbnn_elbo_bce_loss")
+        head = (p.data_ptr(), p.stride(0) if B > 1 else O, target.data_ptr(), O, B, O, _ptr(kl), float(scale), loss.data_ptr(),
+                _ptr(stats), 1)
+        _launch_loss(p.device, "lbbnn_elbo_bce_loss", head, monitor)
         ctx.save_for_backward(target, p)
         ctx.meta = (B, O, float(scale), kl is not None, bool(from_head) and p is probs)
         return loss
@@ -253,15 +275,10 @@ class _ElboBceLossFn(torch.autograd.Function):
         g_probs = torch.empty((B, O), dtype=torch.float32, device=g.device)
         g_logits = torch.empty((B, O), dtype=torch.float32, device=g.device) if from_head else None
         g_kl = torch.empty((), dtype=torch.float32, device=g.device) if has_kl else None
-        stream = torch.cuda.current_stream(g.device).cuda_stream
-        _lib.check(_lib.lib().lbbnn_elbo_bce_loss_backward(g.data_ptr(), p.data_ptr(), p.stride(0) if B > 1 else O,
-                                                           target.data_ptr(), O, B, O, scale, g_probs.data_ptr(),
-                                                           g_logits.data_ptr() if from_head else None,
-                                                           g_kl.data_ptr() if has_kl else None, stream),
-                   "lbbnn_elbo_bce_loss_backward")
+        _lib.launch(g.device, "lbbnn_elbo_bce_loss_backward", g.data_ptr(), p.data_ptr(), p.stride(0) if B > 1 else O,
+                    target.data_ptr(), O, B, O, scale, g_probs.data_ptr(), _ptr(g_logits), _ptr(g_kl))
         if from_head:
-            # the entry HOLDS p and g_probs, as _LOGITS_GRAD does: "same address" in the head's backward means "same tensor"
-            _BCE_LOGITS_GRAD[p.data_ptr()] = (g_probs.data_ptr(), g_logits, p, g_probs)
+            _HEAD_GRAD.leave(p, g_probs, g_logits)
         return g_probs, None, g_kl, None, None, None, None
 
 
@@ -281,25 +298,6 @@ def _bce_target(probs, target):
     if not target.is_contiguous():
         raise ValueError("bnn_amd: elbo_bce_loss: target must be contiguous (strides %s)" % (tuple(target.stride()),))
     return target.view(probs.shape)
-
-
-def _check_monitored_bce(probs, kl, monitor):
-    """``_check_monitored`` for the BCE loss: ValueError naming what keeps this call off the fused, monitored launch."""
-    who = "bnn_amd: elbo_bce_loss(monitor=...): "
-    if not isinstance(monitor, TrainMonitor):
-        raise ValueError(who + "monitor must be a bnn_amd.TrainMonitor, got %s" % type(monitor).__name__)
-    if probs.dtype != torch.float32 or probs.dim() != 2:
-        raise ValueError(who + "probs must be float32 (B, units), got %s %s" % (probs.dtype, tuple(probs.shape)))
-    if probs.shape[1] != monitor.classes:
-        raise ValueError(who + "probs has %d units, the monitor was built for %d" % (probs.shape[1], monitor.classes))
-    if probs.shape[0] < 1:
-        raise ValueError(who + "an empty batch has no step to record")
-    if not _fused_kl(kl):
-        raise ValueError(who + "kl must be None or a one-element float32 HIP tensor")
-    if not probs.is_cuda:
-        raise ValueError(who + "the monitor lives in the fused HIP loss; probs is on %s" % probs.device)
-    if probs.device != monitor.device:
-        raise ValueError(who + "probs is on %s, the monitor on %s" % (probs.device, monitor.device))
 
 
 def elbo_bce_loss(probs, target, kl=None, num_batches=1.0, *, stats=None, monitor=None):
@@ -322,14 +320,13 @@ def elbo_bce_loss(probs, target, kl=None, num_batches=1.0, *, stats=None, monito
     else is a ValueError naming the mismatch."""
     t = _bce_target(probs, target)
     if monitor is not None:
-        _check_monitored_bce(probs, kl, monitor)
+        _check_monitored("elbo_bce_loss", "probs", "units", probs, kl, monitor)
     if stats is not None and not (torch.is_tensor(stats) and stats.dtype == torch.int32 and stats.numel() == 4
                                   and stats.is_contiguous() and stats.device == probs.device):
         raise ValueError("bnn_amd: elbo_bce_loss: stats must be a contiguous int32[4] tensor on %s" % probs.device)
     if not 1 <= probs.shape[1] <= 16 and probs.is_cuda:
         raise ValueError("bnn_amd: elbo_bce_loss: the fused loss takes 1 to 16 output units, got %d" % probs.shape[1])
-    if (probs.is_cuda and probs.dtype == torch.float32
-            and (kl is None or (torch.is_tensor(kl) and kl.is_cuda and kl.dtype == torch.float32 and kl.numel() == 1))):
+    if probs.is_cuda and probs.dtype == torch.float32 and _fused_kl(kl):
         from . import layers
         from_head = isinstance(probs.grad_fn, layers._SigmoidHeadFn._backward_cls)
         return _ElboBceLossFn.apply(probs, t, kl if kl is None else kl.reshape(()), 1.0 / float(num_batches), stats, from_head,
@@ -362,15 +359,9 @@ class _ElboGaussianLossFn(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=m.device)
         # d loss / d log_var[o] of a shared noise level, up to the factor g: column sums the forward pass leaves as a by-product
         cols = torch.empty(O, dtype=torch.float32, device=m.device) if shared else None
-        stream = torch.cuda.current_stream(m.device).cuda_stream
-        head = (m.data_ptr(), ldm, target.data_ptr(), O, lv.data_ptr(), ldv, B, O, kl.data_ptr() if kl is not None else None,
-                float(scale), loss.data_ptr(), stats.data_ptr() if stats is not None else None,
-                cols.data_ptr() if shared else None)
-        if monitor is not None:
-            _lib.check(_lib.lib().lbbnn_elbo_gaussian_loss_monitor(*head, monitor._totals.data_ptr(), monitor._guard.data_ptr(),
-                                                                   stream), "lbbnn_elbo_gaussian_loss_monitor")
-        else:
-            _lib.check(_lib.lib().lbbnn_elbo_gaussian_loss(*head, stream), "lbbnn_elbo_gaussian_loss")
+        head = (m.data_ptr(), ldm, target.data_ptr(), O, lv.data_ptr(), ldv, B, O, _ptr(kl), float(scale), loss.data_ptr(),
+                _ptr(stats), _ptr(cols))
+        _launch_loss(m.device, "lbbnn_elbo_gaussian_loss", head, monitor)
         ctx.save_for_backward(target, m, lv, cols)
         ctx.meta = (B, O, ldm, ldv, float(scale), kl is not None, tuple(log_var.shape))
         return loss
@@ -383,12 +374,8 @@ class _ElboGaussianLossFn(torch.autograd.Function):
         g_mean = torch.empty((B, O), dtype=torch.float32, device=g.device)
         g_lv = torch.empty(lv_shape, dtype=torch.float32, device=g.device) if ctx.needs_input_grad[2] else None
         g_kl = torch.empty((), dtype=torch.float32, device=g.device) if has_kl else None
-        stream = torch.cuda.current_stream(g.device).cuda_stream
-        _lib.check(_lib.lib().lbbnn_elbo_gaussian_loss_backward(g.data_ptr(), m.data_ptr(), ldm, target.data_ptr(), O, lv.data_ptr(),
-                                                                ldv, B, O, scale, cols.data_ptr() if cols is not None else None,
-                                                                g_mean.data_ptr(), g_lv.data_ptr() if g_lv is not None else None,
-                                                                g_kl.data_ptr() if has_kl else None, stream),
-                   "lbbnn_elbo_gaussian_loss_backward")
+        _lib.launch(g.device, "lbbnn_elbo_gaussian_loss_backward", g.data_ptr(), m.data_ptr(), ldm, target.data_ptr(), O,
+                    lv.data_ptr(), ldv, B, O, scale, _ptr(cols), g_mean.data_ptr(), _ptr(g_lv), _ptr(g_kl))
         return g_mean, None, g_lv, g_kl, None, None, None
 
 
@@ -426,23 +413,6 @@ def _gaussian_args(mean, target, log_var):
     return target.view(B, O)
 
 
-def _check_monitored_gaussian(mean, kl, monitor):
-    """``_check_monitored_bce`` for the Gaussian loss: ValueError naming what keeps this call off the fused, monitored launch."""
-    who = "bnn_amd: elbo_gaussian_loss(monitor=...): "
-    if not isinstance(monitor, TrainMonitor):
-        raise ValueError(who + "monitor must be a bnn_amd.TrainMonitor, got %s" % type(monitor).__name__)
-    if mean.shape[1] != monitor.classes:
-        raise ValueError(who + "mean has %d units, the monitor was built for %d" % (mean.shape[1], monitor.classes))
-    if mean.shape[0] < 1:
-        raise ValueError(who + "an empty batch has no step to record")
-    if not _fused_kl(kl):
-        raise ValueError(who + "kl must be None or a one-element float32 HIP tensor")
-    if not mean.is_cuda:
-        raise ValueError(who + "the monitor lives in the fused HIP loss; mean is on %s" % mean.device)
-    if mean.device != monitor.device:
-        raise ValueError(who + "mean is on %s, the monitor on %s" % (mean.device, monitor.device))
-
-
 def elbo_gaussian_loss(mean, target, log_var, kl=None, num_batches=1.0, *, stats=None, monitor=None):
     """sum_{b,o} 0.5 (log(2 pi) + lv + (y - m)^2 exp(-lv)) + kl / num_batches -- ``F.gaussian_nll_loss(mean, target, exp(log_var),
     full=True, reduction="sum") + kl / num_batches``: the ELBO loss of a regression network (``head="identity"``).
@@ -471,7 +441,7 @@ def elbo_gaussian_loss(mean, target, log_var, kl=None, num_batches=1.0, *, stats
     non-empty batch, ``kl`` None or a one-element float32 HIP tensor -- and anything else is a ValueError."""
     t = _gaussian_args(mean, target, log_var)
     if monitor is not None:
-        _check_monitored_gaussian(mean, kl, monitor)
+        _check_monitored("elbo_gaussian_loss", "mean", "units", mean, kl, monitor)     # (_gaussian_args: float32 (B, O) already)
     if stats is not None and not (torch.is_tensor(stats) and stats.dtype == torch.float64 and stats.numel() == 4
                                   and stats.is_contiguous() and stats.device == mean.device):
         raise ValueError("bnn_amd: elbo_gaussian_loss: stats must be a contiguous float64[4] tensor on %s" % mean.device)

@@ -347,7 +347,7 @@ def test_loss_hand_over_equals_sigmoid_backward_bitwise(bnn, dev, name, B):
         assert (took, ran) == ((1, 0) if path == "A" else (0, 1)), (path, took, ran)
         grads.append(({k: p.grad.clone() for k, p in net.named_parameters()}, loss.detach().clone()))
         del out, loss
-    assert not losses._BCE_LOGITS_GRAD                                           # the entry was taken, nothing is held
+    assert len(losses._HEAD_GRAD) == 0                                           # the entry was taken, nothing is held
     for k in grads[0][0]:
         assert _same(grads[0][0][k].reshape(-1), grads[1][0][k].reshape(-1)), k
         assert bool(torch.isfinite(grads[0][0][k]).all()), k

@@ -15,9 +15,9 @@ identical."""
 import argparse
 import os
 import pickle
-import subprocess
 import sys
-import tempfile
+
+import ab_trees
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ap = argparse.ArgumentParser()
@@ -186,35 +186,7 @@ def worker(tree, dump):
 def main():
     if args.parent is None:
         sys.exit("eval_totals_ab: --parent DIR (a built checkout of the parent commit) is required")
-    lines = []
-    say = lambda s: (lines.append(s), print(s, flush=True))
-    dumps = {}
-    with tempfile.TemporaryDirectory() as tmp:
-        for name, tree in (("parent", os.path.abspath(args.parent)), ("this tree", HERE)):
-            path = os.path.join(tmp, name.replace(" ", "_") + ".pkl")
-            env = {k: v for k, v in os.environ.items() if k != "LBBNN_LIB_PATH"}      # each tree loads its own library
-            rc = subprocess.run(["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__),
-                                 "--worker", tree, "--dump", path], env=env, cwd=tree).returncode
-            if rc != 0 or not os.path.exists(path):
-                sys.exit("eval_totals_ab: the child of %s (%s) ended with status %d; stopped" % (name, tree, rc))
-            with open(path, "rb") as fh:
-                dumps[name] = pickle.load(fh)
-    a, b = dumps["parent"], dumps["this tree"]
-    cases = {}
-    for k in list(a) + [k for k in b if k not in a]:
-        cases.setdefault(k.split("/")[0].rsplit(" #", 1)[0], []).append(k)
-    bad = 0
-    say("tools/eval_totals_ab.py: %d cases, %d dumped arrays (%d bytes); parent %s" % (len(cases), len(a), sum(map(len, a.values())),
-                                                                                      args.parent))
-    for case, keys in cases.items():
-        diff = next((k for k in keys if a.get(k) != b.get(k)), None)
-        bad += diff is not None
-        say("%-78s %s" % (case, "identical" if diff is None else "DIFFERENT at %s" % diff))
-    say("every case identical" if not bad else "%d case(s) DIFFERENT" % bad)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
-        fh.write("\n".join(lines) + "\n")
-    sys.exit(1 if bad else 0)
+    sys.exit(ab_trees.report(__file__, ab_trees.child_dumps(__file__, args.parent, args.timeout), args.parent, args.out))
 
 
 if __name__ == "__main__":
