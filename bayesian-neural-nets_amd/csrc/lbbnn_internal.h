@@ -82,15 +82,16 @@ LBBNN_HIDDEN int make_weight_pass_args(WeightPassArgs& a, const float* mu, const
                                        const lbbnn_priors_t* priors, void* e_w, void* var_w, int ld,
                                        float* kl_rows, float* act_mu, float* act_var, float* bias_var, int O, int I,
                                        int split = 0, float* e_scale = nullptr, float* v_scale = nullptr);
+// fmt (optional): an lbbnn_format_x job for the launch to carry in workgroups behind its rows; *fmt_done says whether it did
+// (the two-wave row kernel does: launches without in-kernel flows and without a member dimension)
 LBBNN_HIDDEN int launch_weight_pass(const WeightPassArgs* a, int n, hipStream_t s, uint64_t* rng = nullptr,
                                     uint64_t* rng_snap = nullptr, uint64_t advance = 0, const InFlow* flows = nullptr,
-                                    int members = 1);
+                                    int members = 1, const struct FormatJob* fmt = nullptr, bool* fmt_done = nullptr);
 // planar flows of a layer computed inside the weight pass's workgroups instead of by launch_flow_planar (advance must be 0)
 LBBNN_HIDDEN bool in_flow_eligible(const FlowArgs& f, const WeightPassArgs& w);
 LBBNN_HIDDEN void make_in_flow(InFlow& o, const FlowArgs& f);
-// fmt (optional): an lbbnn_format_x job for the launch to carry on otherwise idle CUs; *fmt_done says whether it did
 LBBNN_HIDDEN int launch_flow_planar(const FlowArgs* a, int n, hipStream_t s, int members = 1, unsigned long long m_adv = 0,
-                                    long long z_ms = 0, const struct FormatJob* fmt = nullptr, bool* fmt_done = nullptr);
+                                    long long z_ms = 0);
 LBBNN_HIDDEN int launch_kl_finalize_all(const FinalizeArgs* a, const int* active, int n, uint64_t* rng, uint64_t advance,
                                         float* kl_total, hipStream_t s);
 LBBNN_HIDDEN int launch_kl_finalize(const FinalizeArgs* a, int n, hipStream_t s);

@@ -626,7 +626,7 @@ int launch16(G16Args& a, int npv, bool xpl, hipStream_t s, bool* hosted) {
 }
 
 // fp32 rows -> planes as a launch of its own (lbbnn_device.h: format_x_items; a fused forward lets the same job ride in the
-// launch of the planar flows instead: lbbnn_layers_operands_x)
+// weight-pass launch instead: lbbnn_layers_operands_x)
 __global__ __launch_bounds__(256) void format_x_kernel(const FormatJob j) {
     format_x_items(j, (size_t)blockIdx.x * 256 + threadIdx.x, (size_t)gridDim.x * 256);
 }

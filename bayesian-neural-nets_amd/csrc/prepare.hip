@@ -76,14 +76,15 @@ static int layers_prepare_impl(const lbbnn_layer_desc_t* L, int n, const uint64_
     if (in_kernel) {
         for (int i = 0; i < n; ++i) if (flow_of[i] >= 0) make_in_flow(inf[i], fa[flow_of[i]]);
     } else if (nf) {
-        bool fmt_done = false;
-        rc = launch_flow_planar(fa, nf, s, 1, 0, 0, fmt, &fmt_done); if (rc) return rc;
-        if (fmt_done) fmt = nullptr;
+        rc = launch_flow_planar(fa, nf, s); if (rc) return rc;
     }
-    if (fmt) {          // no flow launch to ride in (LRT layers, in-kernel flows, shapes the register kernel does not take)
+    // the x-format job rides behind the rows of the weight-pass launch; a launch that cannot carry it (in-kernel flows, rows
+    // the generic kernel takes) leaves it to a launch of its own
+    bool fmt_done = false;
+    rc = launch_weight_pass(wa, n, s, rng_live, rng_snap, advance, in_kernel ? inf : nullptr, 1, fmt, &fmt_done); if (rc) return rc;
+    if (fmt && !fmt_done) {
         rc = lbbnn_format_x(fmt->x, fmt->ldx, fmt->planes, fmt->ldp, fmt->B, fmt->I, stream); if (rc) return rc;
     }
-    rc = launch_weight_pass(wa, n, s, rng_live, rng_snap, advance, in_kernel ? inf : nullptr); if (rc) return rc;
     if (nk && with_k5) { rc = launch_kl_finalize(ka, nk, s); if (rc) return rc; }
     return 0;
 }

@@ -7,9 +7,11 @@
 //
 // Roofline: HBM.  Algorithmic bytes per weight: 12 read + 8 written (fp32 operands).
 //
-// Two kernels:
-//   weight_rows_kernel (rows whose length is a multiple of 4, 16-B aligned, ld <= 2048: every layer of the BASELINE
-//     configurations)  -- round 2.  ONE WAVE PER ROW, four rows per 256-thread workgroup: a lane owns the float4 column
+// Three kernels:
+//   weight_row_tasks_kernel (rows whose length is a multiple of 4, 16-B aligned, ld <= 2048: every layer of the BASELINE
+//     configurations): one row per two-wave workgroup, the row's float4 groups split between the waves; see the kernel.
+//   weight_rows_kernel (the same rows, for launches that compute planar flows inside their workgroups: LBBNN_K1_INFLOW=1)
+//     -- round 2.  ONE WAVE PER ROW, four rows per 256-thread workgroup: a lane owns the float4 column
 //     groups lane, lane + 64, ... so a wave reads 1 KiB contiguous per instruction, has all of its row's loads in flight
 //     at once (15 x 16 B per lane at I = 1200) and reduces its row sums with DPP moves alone -- no barrier, no LDS
 //     round trip per row.  603 workgroups cover the headline net, all resident at once (<= 3 per CU).
@@ -299,22 +301,12 @@ constexpr int kInT = 4;                                  // in-kernel planar flo
 constexpr int kInNV = 3 * kInT + kInT * (kInT - 1) / 2 + kInT + 1;      // A_k | UW | X | A_f | LQ0 = 23 sums (19 used at T = 2 + 2)
 constexpr int kRowG = 8;                                 // float4 groups per lane: ld <= 64 * 4 * 8 = 2048
 constexpr int kRowB = 5;                                 // ... of which this many are loaded together
-#ifndef LBBNN_K1_ROWS_PER_WG
-#define LBBNN_K1_ROWS_PER_WG 1
-#endif
-// Rows (= waves) per workgroup of the row kernel.  Measured on the headline forward, round 3, alternating processes on one box
-// (profiles/r03_ab_k1_rows.txt).  With the layer's per-column vectors (z_fwd, z_kl, r0_c: 14.4 KB at I = 1200) staged in LDS
-// once per workgroup: 4 rows 0.1251 ms, 2 rows 0.1249, 1 row 0.1259, 8 rows 0.1285 -- the launch is a single wave of
-// workgroups (2410 rows on 3072 wave slots) and a SIMD holds 2 or 3 of them whatever the grouping; fewer rows per workgroup
-// balance the CUs better (603 four-row workgroups: 3 on 91 CUs, 2 on the rest) but stage the vectors once per row, which
-// costs what the balance gains.  ONE row per workgroup with the vectors taken straight into registers, a float4 group at a
-// time beside the row's parameters (no LDS, no barrier; kDirectZ below): 0.1220 against 0.1226 for the 4-row form -- kept.
-// (A first run of this experiment staged only the first 2 x 64 x rows float4s of the vectors -- the loop was written for 4
-// rows -- and "won" 3 us at 1 row with wrong operands: the staging loop now covers any workgroup size.)  In-kernel flows
-// (INFLOW) are computed by four waves together.
+// Rows (= waves) per workgroup of the in-kernel-flow row kernel: four waves compute a layer's flows together and share its
+// per-column vectors through LDS.  Measured history of the flow-less launches, round 3 (profiles/r03_ab_k1_rows.txt, headline
+// forward): with the vectors staged in LDS 4 rows per workgroup 0.1251 ms, 2 rows 0.1249, 1 row 0.1259, 8 rows 0.1285; one
+// one-wave row per workgroup with the vectors taken straight into registers 0.1220 against 0.1226 for the 4-row form.  That
+// form is replaced by the two-wave row tasks below (weight_row_tasks_kernel).
 constexpr int kRowsWGFlow = 4;
-constexpr int kRowsWG = LBBNN_K1_ROWS_PER_WG;
-template <bool INFLOW> struct RowsCfg { static constexpr int RW = INFLOW ? kRowsWGFlow : kRowsWG, NT = 64 * RW; };
 
 struct WeightRowsBatch {
     WeightPassArgs l[LBBNN_MAX_LAYERS];
@@ -324,6 +316,8 @@ struct WeightRowsBatch {
     uint64_t* rng; uint64_t* rng_snap; uint64_t advance;
     int members;                 // ensemble (lbbnn_ensemble_operands): gridDim.y members; member m reads z_fwd + m*ld and writes
                                  // e_w + m*O*ld; var_w / bias_var are written by member 0 only; no KL outputs
+    FormatJob fmt; int fmt_blocks;      // two-wave row kernel only: fmt_blocks workgroups behind the rows (blockIdx.x >= wg_end[n - 1])
+                                        // turn the network input into fp16 planes (format_x_items)
 };
 
 __device__ __forceinline__ float4 ld4(const float* p, int j) { return reinterpret_cast<const float4*>(p)[j]; }
@@ -332,14 +326,14 @@ __device__ __forceinline__ float4 fma4(const float4 u, float s, const float4 z) 
     return make_float4(z.x + u.x * s, z.y + u.y * s, z.z + u.z * s, z.w + u.w * s);
 }
 
-// INFLOW: some layer of the launch computes its planar flows inside its workgroups (f.on); the fused forwards since K3v have
-// none, and their instantiation carries neither that code nor its register pressure.
-template <bool F16S, bool INFLOW>
-__global__ __launch_bounds__(RowsCfg<INFLOW>::NT, 3) void weight_rows_kernel(const WeightRowsBatch bt_) {
-    constexpr int kRowsWG = RowsCfg<INFLOW>::RW, kRowNT = RowsCfg<INFLOW>::NT;
+// Launches in which some layer computes its planar flows inside its workgroups (f.on).  The fused forwards since K3v have
+// none: they take weight_row_tasks_kernel, which carries neither this code nor its register pressure.
+template <bool F16S>
+__global__ __launch_bounds__(64 * kRowsWGFlow, 3) void weight_rows_kernel(const WeightRowsBatch bt_) {
+    constexpr int kRowsWG = kRowsWGFlow, kRowNT = 64 * kRowsWGFlow;
     const LBBNN_CONST_AS WeightRowsBatch* bt = kernarg_as<WeightRowsBatch>();
     extern __shared__ __attribute__((aligned(16))) float sm[];          // zf[P] | zk[P] | rc[P]
-    __shared__ double red[INFLOW ? kInNV : 1][kRowsWG];
+    __shared__ double red[kInNV][kRowsWG];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     if (bt->rng_snap && blockIdx.x == 0 && tid == 0) {                   // see weight_pass_kernel
         const uint64_t sd = bt->rng[0], of = bt->rng[1];
@@ -365,38 +359,10 @@ __global__ __launch_bounds__(RowsCfg<INFLOW>::NT, 3) void weight_rows_kernel(con
     const size_t rowoff = (size_t)o * I;
     // (Measured and dropped, round 2: requesting the row AHEAD of the prologue -- held in registers: 98 spilled VGPRs at the
     // 168-register budget three workgroups per CU need; touched line by line with unused asm loads: 35.7 us against 33.6.)
-
-    // Round 3: with the flows computed by their own launch (f.on == 0: the fused forwards since K3v) the row's first batch of
-    // parameter loads is requested HERE, ahead of the staging of the per-column vectors -- 15 x 16 B per lane in flight while
-    // the z vectors make their round trip to LDS, instead of after the barrier behind it.  (With the in-kernel flows the same
-    // hoist spilled: see above; that path keeps the loads below.)
     float4 mu[kRowB], rho[kRowB], lam[kRowB];
-    // one-row workgroups: no sharing to stage for -- every lane takes its own float4s of the per-column vectors straight
-    // into registers, with the row's parameters (no LDS round trip, no barrier)
-    constexpr bool kDirectZ = !INFLOW && kRowsWG == 1;
-    float4 zfr[1], zkr[1], rcr[1];
-    if (!INFLOW && has_row) {
-#pragma unroll
-        for (int g = 0; g < kRowB; ++g) {
-            const int j = lane + 64 * g;
-            if (g < G && j < iq) { mu[g] = ld4(a.mu + rowoff, j); rho[g] = ld4(a.rho + rowoff, j); lam[g] = ld4(a.lambdal + rowoff, j); }
-        }
-    }
-    // (all five groups of the three vectors up front, beside the 15 parameter registers and the operands kept for the row
-    // maximum: 115 spilled VGPRs at the 168 three waves per SIMD leave -- so one group ahead of its use, two register sets)
-    auto load_z = [&](int gg, float4& zf, float4& zk, float4& rc) {
-        const int j = lane + 64 * gg;
-        zf = one4; zk = one4; rc = one4;
-        if (gg < G && j < iq) {
-            if (a.z_fwd) zf = ld4(a.z_fwd + (size_t)mem * P, j);
-            if (a.z_kl) zk = ld4(a.z_kl, j);
-            if (a.r0_c) rc = ld4(a.r0_c, j);
-        }
-    };
-    if constexpr (kDirectZ) { if (has_row) load_z(0, zfr[0], zkr[0], rcr[0]); }
 
     // ---------------------------------------------------------------- per-column vectors of this layer -> LDS
-    if (INFLOW && f.on) {
+    if (f.on) {
         const int Tz = f.Tz, NT = f.Tz + f.Tr;
         const bool klb = f.want_kl != 0;
         uint64_t seed = 0, offs = 0;
@@ -528,7 +494,7 @@ __global__ __launch_bounds__(RowsCfg<INFLOW>::NT, 3) void weight_rows_kernel(con
             f.scal[4] = ldf;                                                          // logdet of sample_z(B) (:187)
             if (klb) { f.scal[0] = ldq; f.scal[1] = (float)acc[kInNV - 1]; f.scal[2] = ldr; }
         }
-    } else if constexpr (!kDirectZ) {
+    } else {
 #pragma unroll
         for (int h = 0; h < (64 * kRowG + kRowNT - 1) / kRowNT; ++h) {
             const int j = tid + kRowNT * h;
@@ -544,7 +510,7 @@ __global__ __launch_bounds__(RowsCfg<INFLOW>::NT, 3) void weight_rows_kernel(con
             }
         }
     }
-    if constexpr (!kDirectZ) __syncthreads();
+    __syncthreads();
 
     // ---------------------------------------------------------------- one row per wave
     if (!has_row) return;
@@ -563,26 +529,19 @@ __global__ __launch_bounds__(RowsCfg<INFLOW>::NT, 3) void weight_rows_kernel(con
     const bool vhi_only = a.split == 3;               // LBBNN_F_VAR1 operands: var_w = plain fp16 rows (the hi part alone)
     float4 ew_keep[F16S ? kRowB : 1], vw_keep[F16S ? kRowB : 1];
     for (int g0 = 0; g0 < G; g0 += kRowB) {
-        if (INFLOW || g0 > 0) {                                  // (the first batch of a flow-less launch is in flight already)
 #pragma unroll
-            for (int g = 0; g < kRowB; ++g) {
-                const int j = lane + 64 * (g0 + g);
-                if (g0 + g < G && j < iq) { mu[g] = ld4(a.mu + rowoff, j); rho[g] = ld4(a.rho + rowoff, j); lam[g] = ld4(a.lambdal + rowoff, j); }
-            }
+        for (int g = 0; g < kRowB; ++g) {
+            const int j = lane + 64 * (g0 + g);
+            if (g0 + g < G && j < iq) { mu[g] = ld4(a.mu + rowoff, j); rho[g] = ld4(a.rho + rowoff, j); lam[g] = ld4(a.lambdal + rowoff, j); }
         }
 #pragma unroll
         for (int g = 0; g < kRowB; ++g) {
             if (g0 + g >= G) break;
             const int j = lane + 64 * (g0 + g);
             float4 ew = zero4, vw = zero4;
-            if constexpr (kDirectZ) { if (g0 + g > 0) load_z(g0 + g, zfr[0], zkr[0], rcr[0]); }
             if (j < iq) {
-                float4 zf, zk, rc;
-                if constexpr (kDirectZ) { zf = zfr[0]; zk = zkr[0]; rc = rcr[0]; }
-                else {
-                    zf = reinterpret_cast<const float4*>(zf_s)[j]; zk = reinterpret_cast<const float4*>(zk_s)[j];
-                    rc = reinterpret_cast<const float4*>(rc_s)[j];
-                }
+                const float4 zf = reinterpret_cast<const float4*>(zf_s)[j], zk = reinterpret_cast<const float4*>(zk_s)[j],
+                             rc = reinterpret_cast<const float4*>(rc_s)[j];
                 const Elem2 ea = weight_elem_p2(k1_f2{mu[g].x, mu[g].y}, k1_f2{rho[g].x, rho[g].y}, k1_f2{lam[g].x, lam[g].y},
                                                 k1_f2{zf.x, zf.y}, k1_f2{zk.x, zk.y}, k1_f2{rc.x, rc.y}, want_kl, want_act, ec);
                 const Elem2 eb = weight_elem_p2(k1_f2{mu[g].z, mu[g].w}, k1_f2{rho[g].z, rho[g].w}, k1_f2{lam[g].z, lam[g].w},
@@ -690,6 +649,208 @@ __global__ __launch_bounds__(RowsCfg<INFLOW>::NT, 3) void weight_rows_kernel(con
     }
 }
 
+// ------------------------------------------------------------------------------------------------ two-wave row tasks
+// Launches without in-kernel flows (every fused forward since K3v): ONE ROW PER WORKGROUP, TWO WAVES.  The row's G float4
+// groups are split by whole groups, contiguously: wave 0 takes groups 0 .. ceil(G/2)-1, wave 1 the rest (G = 5: {0,1,2} and
+// {3,4}; G = 1: wave 1 has none and only takes part in the exchange).  Column halves would idle 22 % of the lanes at
+// I = 1200; whole groups idle none that the one-wave row did not.  A wave requests and keeps its own groups alone, so the
+// kernel fits the next occupancy step and the launch is ~2x as many, half as long tasks for the dispatcher to balance.
+//   Row scales (F16S): each wave's maxima meet in LDS; a maximum is order-free, so pow2_scale sees the same value.
+//   Row sums: lane l of the one-wave row added its groups' terms in group order, then wave_sum.  Wave 0 runs the chain over
+//   its groups and hands the per-lane partials to wave 1 in the same exchange; wave 1 keeps its groups' terms apart until
+//   then and continues the chain ((a + t3) + t4) -- the same association, the same bits.  (A group past the row's end
+//   contributes +0 terms: x + 0 == x bit for bit, and a chain that starts at +0 never holds -0.)
+// One barrier per row.  Format workgroups (fmt_blocks of them, behind the rows: blockIdx.x >= wg_end[n - 1]) turn the network
+// input into fp16 planes for the first GEMM (format_x_items) while the rows compute.
+constexpr int kTaskW = 2;                                // waves per row
+// Waves per SIMD the register budget is set for.  4: 103 VGPRs (F16S) / 128 (fp32 and bf16 stores), no spills -- and the
+// compiler needs no more at a bound of 3 (the same code); 5 (96 VGPRs) spills 18 / 66 registers, so it was not run.
+constexpr int kTaskWavesEU = 4;
+// Format workgroups: 8-float items per thread, up to kFmtMaxBlocks workgroups (grid-stride beyond).  Measured on the headline
+// forward (B = 4096, I = 784: 409 600 items), ms per replay: 1 item per thread (3 200 workgroups) 0.1120, 2: 0.1121, 4: 0.1122,
+// 8: 0.1134 -- against 0.1161 with fp32 x.
+constexpr int kFmtItemsPerThread = 1;
+constexpr size_t kFmtMaxBlocks = 4096;
+template <bool F16S> struct TaskCfg { static constexpr int NG = ((F16S ? kRowB : kRowG) + kTaskW - 1) / kTaskW; };   // groups per wave
+
+template <bool F16S>
+__global__ __launch_bounds__(64 * kTaskW, kTaskWavesEU) void weight_row_tasks_kernel(const WeightRowsBatch bt_) {
+    constexpr int NG = TaskCfg<F16S>::NG;
+    const LBBNN_CONST_AS WeightRowsBatch* bt = kernarg_as<WeightRowsBatch>();
+    __shared__ float mx_s[kTaskW][2];                                    // row maxima of |e_w|, var_w per wave
+    __shared__ k1_f2 part_s[3][64];                                      // wave 0's per-lane partial row sums
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (bt->rng_snap && blockIdx.x == 0 && tid == 0) {                   // see weight_pass_kernel
+        const uint64_t sd = bt->rng[0], of = bt->rng[1];
+        bt->rng_snap[0] = sd; bt->rng_snap[1] = of;
+        if (bt->advance) bt->rng[1] = of + bt->advance;
+    }
+    if ((int)blockIdx.x >= bt->wg_end[LBBNN_MAX_LAYERS - 1]) {           // format workgroups (member 0 only: the host checks)
+        const FormatJob fj = {bt->fmt.x, bt->fmt.planes, bt->fmt.ldx, bt->fmt.ldp, bt->fmt.B, bt->fmt.I};
+        format_x_items(fj, (size_t)((int)blockIdx.x - bt->wg_end[LBBNN_MAX_LAYERS - 1]) * (64 * kTaskW) + tid,
+                       (size_t)bt->fmt_blocks * (64 * kTaskW));
+        return;
+    }
+    int li = 0;
+#pragma unroll
+    for (int t = 0; t < LBBNN_MAX_LAYERS - 1; ++t) if (t + 1 < bt->n && (int)blockIdx.x >= bt->wg_end[t]) li = t + 1;
+    const LBBNN_CONST_AS WeightPassArgs& a = bt->l[li];
+    const int o = (int)blockIdx.x - (li ? bt->wg_end[li - 1] : 0);
+    const int I = a.I, P = a.ld, nq = P >> 2, iq = I >> 2;
+    const int mem = blockIdx.y;                                          // 0 unless an ensemble launch
+    const bool want_kl = a.kl_rows != nullptr, want_act = a.act_mu != nullptr;
+    const float4 one4 = make_float4(1.f, 1.f, 1.f, 1.f), zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int G = (nq + 63) >> 6;                                        // <= kRowG (F16S launches: <= kRowB), host-checked
+    const int g_lo = wv ? (G + 1) >> 1 : 0, ng = wv ? G >> 1 : (G + 1) >> 1;      // this wave's groups: g_lo .. g_lo + ng - 1
+    const size_t rowoff = (size_t)o * I;
+
+    // every load of the wave's share is requested here: parameters and the per-column vectors of its own groups
+    float4 mu[NG], rho[NG], lam[NG], zf[NG], zk[NG], rc[NG];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        const int j = lane + 64 * (g_lo + g);
+        zf[g] = one4; zk[g] = one4; rc[g] = one4;
+        if (g < ng && j < iq) {
+            mu[g] = ld4(a.mu + rowoff, j); rho[g] = ld4(a.rho + rowoff, j); lam[g] = ld4(a.lambdal + rowoff, j);
+            if (a.z_fwd) zf[g] = ld4(a.z_fwd + (size_t)mem * P, j);
+            if (a.z_kl) zk[g] = ld4(a.z_kl, j);
+            if (a.r0_c) rc[g] = ld4(a.r0_c, j);
+        }
+    }
+    const ElemConst ec = {a.mu_prior, a.log_sp, a.log_ap, a.log_1map, a.inv_2sp2};
+    const k1_f2 zero2 = {0.f, 0.f};
+    k1_f2 kl2 = zero2, amu2 = zero2, avar2 = zero2;          // wave 0: the chain over its groups
+    k1_f2 tkl[NG], tamu[NG], tavar[NG];                       // wave 1: its groups' terms, added after wave 0's partials
+    float* const ewp = a.e_w ? a.e_w + (size_t)mem * a.O * P : nullptr;
+    float* const vwp = mem == 0 ? a.var_w : nullptr;
+    // F16S instantiation: launches in which SOME layer takes row-scaled fp16 operands (split >= 2); every row keeps its operands
+    // in registers until the row maxima are known, and the other layers of the launch (the fp32 10-class head) store theirs
+    // from the same place
+    const bool f16s = F16S && a.split >= 2;
+    const bool vhi_only = a.split == 3;               // LBBNN_F_VAR1 operands: var_w = plain fp16 rows (the hi part alone)
+    const bool odd = lane & 1;
+    float4 ew_keep[F16S ? NG : 1], vw_keep[F16S ? NG : 1];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        tkl[g] = zero2; tamu[g] = zero2; tavar[g] = zero2;
+        if (g >= ng) continue;
+        const int j = lane + 64 * (g_lo + g);
+        float4 ew = zero4, vw = zero4;
+        if (j < iq) {
+            const Elem2 ea = weight_elem_p2(k1_f2{mu[g].x, mu[g].y}, k1_f2{rho[g].x, rho[g].y}, k1_f2{lam[g].x, lam[g].y},
+                                            k1_f2{zf[g].x, zf[g].y}, k1_f2{zk[g].x, zk[g].y}, k1_f2{rc[g].x, rc[g].y}, want_kl, want_act, ec);
+            const Elem2 eb = weight_elem_p2(k1_f2{mu[g].z, mu[g].w}, k1_f2{rho[g].z, rho[g].w}, k1_f2{lam[g].z, lam[g].w},
+                                            k1_f2{zf[g].z, zf[g].w}, k1_f2{zk[g].z, zk[g].w}, k1_f2{rc[g].z, rc[g].w}, want_kl, want_act, ec);
+            ew = make_float4(ea.ew.x, ea.ew.y, eb.ew.x, eb.ew.y);
+            vw = make_float4(ea.vw.x, ea.vw.y, eb.vw.x, eb.vw.y);
+            tkl[g] = ea.kl + eb.kl; tamu[g] = ea.amu + eb.amu; tavar[g] = ea.avar + eb.avar;
+        }
+        if (wv == 0) { kl2 = kl2 + tkl[g]; amu2 = amu2 + tamu[g]; avar2 = avar2 + tavar[g]; }
+        if constexpr (F16S) {
+            ew_keep[g] = ew; vw_keep[g] = vw;               // stored below, once the row maxima are known
+        } else if (a.split != 1) {
+            if (j < nq) {
+                if (ewp) reinterpret_cast<float4*>(ewp + (size_t)o * P)[j] = ew;
+                if (vwp) reinterpret_cast<float4*>(vwp + (size_t)o * P)[j] = vw;
+            }
+        } else {
+            // whole 16-B units through the lane-pair exchange (pair_unit: every lane takes part; vwp is wave-uniform)
+            const size_t at = split_hi_index((size_t)o, 4 * (j & ~1), P) + (odd ? kSplitLoOffset : 0);
+            uint2 hi, lo;
+            split4(ew, hi, lo);
+            {
+                const uint4 unit = pair_unit(odd, hi, lo);
+                if (ewp && j < nq) *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(ewp) + at) = unit;
+            }
+            if (vwp) {
+                split4(vw, hi, lo);
+                const uint4 unit = pair_unit(odd, hi, lo);
+                if (j < nq) *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(vwp) + at) = unit;
+            }
+        }
+    }
+    // ---------------------------------------------------------------- the exchange: one barrier per row
+    const bool sums = want_kl || want_act;
+    float me = 0.f, mv = 0.f;
+    if constexpr (F16S) {
+        if (f16s) {
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                if (g >= ng) break;
+                me = fmaxf(fmaxf(fmaxf(fmaxf(me, fabsf(ew_keep[g].x)), fabsf(ew_keep[g].y)), fabsf(ew_keep[g].z)), fabsf(ew_keep[g].w));
+                mv = fmaxf(fmaxf(fmaxf(fmaxf(mv, vw_keep[g].x), vw_keep[g].y), vw_keep[g].z), vw_keep[g].w);   // chains: v_max3_f32
+            }
+            me = wave_max(me); mv = wave_max(mv);
+            if (lane == 0) { mx_s[wv][0] = me; mx_s[wv][1] = mv; }
+        }
+    }
+    if (sums && wv == 0) { part_s[0][lane] = kl2; part_s[1][lane] = amu2; part_s[2][lane] = avar2; }
+    if (f16s || sums) __syncthreads();                                   // (workgroup-uniform condition)
+    if constexpr (F16S) {
+        // LBBNN_F_F16S: one exact power-of-two scale per row and operand, then hi | lo fp16 units exactly as the bf16 form
+        // lays them out (even lane of a pair: the hi unit, odd lane: the lo unit).  Layers of the launch in another format
+        // (split 0 / 1) store the operands they kept, unscaled, in their own format.
+        float se = 1.f, ie = 1.f, sv = 1.f, iv = 1.f;
+        if (f16s) {
+            me = fmaxf(mx_s[0][0], mx_s[1][0]); mv = fmaxf(mx_s[0][1], mx_s[1][1]);
+            pow2_scale(me, se, ie);
+            pow2_scale(mv, sv, iv);
+        }
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            if (g >= ng) break;
+            const int j = lane + 64 * (g_lo + g);
+            if (a.split == 0) {
+                if (j < nq) {
+                    if (ewp) reinterpret_cast<float4*>(ewp + (size_t)o * P)[j] = ew_keep[g];
+                    if (vwp) reinterpret_cast<float4*>(vwp + (size_t)o * P)[j] = vw_keep[g];
+                }
+                continue;
+            }
+            const size_t at = split_hi_index((size_t)o, 4 * (j & ~1), P) + (odd ? kSplitLoOffset : 0);
+            uint2 hi, lo;
+            {
+                const float4 w = ew_keep[g];
+                if (f16s) split4_hs(w, se, hi, lo);
+                else split4(w, hi, lo);
+                const uint4 unit = pair_unit(odd, hi, lo);
+                if (ewp && j < nq) *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(ewp) + at) = unit;
+            }
+            if (vwp && vhi_only) {
+                // one RNE fp16 value per weight, row-major with a row stride of P halves: 8 B per lane, a wave-store covers
+                // 512 B contiguous (32 k x 2 B = the 64-B row of one K step in the GEMM's LDS image)
+                const float4 w = vw_keep[g];
+                if (j < nq) *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(vwp) + (size_t)o * P + 4 * j) =
+                    make_uint2(cvt_pk_h(w.x * sv, w.y * sv), cvt_pk_h(w.z * sv, w.w * sv));
+            } else if (vwp) {
+                const float4 w = vw_keep[g];
+                if (f16s) split4_hs(w, sv, hi, lo);
+                else split4(w, hi, lo);
+                const uint4 unit = pair_unit(odd, hi, lo);
+                if (j < nq) *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(vwp) + at) = unit;
+            }
+        }
+        if (f16s && tid == 0) {
+            if (a.e_scale) a.e_scale[o] = ie;
+            if (a.v_scale && vwp) a.v_scale[o] = iv;
+        }
+    }
+    if (sums && wv == kTaskW - 1) {
+        kl2 = part_s[0][lane]; amu2 = part_s[1][lane]; avar2 = part_s[2][lane];
+#pragma unroll
+        for (int g = 0; g < NG; ++g) { kl2 = kl2 + tkl[g]; amu2 = amu2 + tamu[g]; avar2 = avar2 + tavar[g]; }
+        const float kl = wave_sum(kl2.x + kl2.y), amu = wave_sum(amu2.x + amu2.y), avar = wave_sum(avar2.x + avar2.y);
+        if (lane == 0) {
+            if (want_kl) a.kl_rows[o] = kl;
+            if (want_act) { a.act_mu[o] = amu; a.act_var[o] = avar; }
+        }
+    }
+    if (tid == 0 && mem == 0 && a.bias_var && a.bias_rho) {
+        const float sb = softplus_ref(a.bias_rho[o]);
+        a.bias_var[o] = sb * sb;                      // bias.sigma**2, LBBNN-GP-MF-LRT.py:173
+    }
+}
+
 }  // namespace
 
 namespace lbbnn {
@@ -748,7 +909,8 @@ void make_in_flow(InFlow& o, const FlowArgs& f) {
 }
 
 int launch_weight_pass(const WeightPassArgs* a, int n, hipStream_t s, uint64_t* rng, uint64_t* rng_snap, uint64_t advance,
-                       const InFlow* flows, int members) {
+                       const InFlow* flows, int members, const FormatJob* fmt, bool* fmt_done) {
+    if (fmt_done) *fmt_done = false;
     bool rows_ok = true;
     for (int i = 0; i < n; ++i) rows_ok = rows_ok && a[i].vec && a[i].ld <= 64 * 4 * kRowG;
     // LBBNN_K1_ROWS=0 (environment, read once): A/B switch for measurements -- the one-row-per-workgroup kernel of round 1
@@ -767,7 +929,7 @@ int launch_weight_pass(const WeightPassArgs* a, int n, hipStream_t s, uint64_t* 
         int wgs = 0, maxld = 0;
         bool flow_on = false;
         for (int i = 0; i < n && flows; ++i) flow_on = flow_on || flows[i].on;
-        const int rw = flow_on ? RowsCfg<true>::RW : RowsCfg<false>::RW;      // rows per workgroup of the instantiation launched
+        const int rw = flow_on ? kRowsWGFlow : 1;                // rows per workgroup of the kernel launched
         for (int i = 0; i < n; ++i) {
             bt.l[i] = a[i];
             if (flows) bt.f[i] = flows[i];
@@ -781,13 +943,24 @@ int launch_weight_pass(const WeightPassArgs* a, int n, hipStream_t s, uint64_t* 
         if (members > 1) for (int i = 0; i < n; ++i) if (bt.f[i].on || a[i].kl_rows || a[i].act_mu) return LBBNN_E_FLAGS;
         bool any_flow = false;
         for (int i = 0; i < n; ++i) any_flow = any_flow || bt.f[i].on;
-        const dim3 grid(wgs, any_f16 ? 1 : (members > 1 ? members : 1));
-        // (one-row workgroups hold the per-column vectors in registers: no LDS, nothing for the dispatcher to count)
-        const size_t lds = (!flow_on && RowsCfg<false>::RW == 1) ? 0 : (size_t)3 * maxld * sizeof(float);
-        if (any_f16 && any_flow)  hipLaunchKernelGGL((weight_rows_kernel<true, true>), grid, dim3(RowsCfg<true>::NT), lds, s, bt);
-        else if (any_f16)         hipLaunchKernelGGL((weight_rows_kernel<true, false>), grid, dim3(RowsCfg<false>::NT), lds, s, bt);
-        else if (any_flow)        hipLaunchKernelGGL((weight_rows_kernel<false, true>), grid, dim3(RowsCfg<true>::NT), lds, s, bt);
-        else                      hipLaunchKernelGGL((weight_rows_kernel<false, false>), grid, dim3(RowsCfg<false>::NT), lds, s, bt);
+        const int ny = any_f16 ? 1 : (members > 1 ? members : 1);
+        if (any_flow) {
+            const dim3 grid(wgs, ny);
+            const size_t lds = (size_t)3 * maxld * sizeof(float);
+            if (any_f16) hipLaunchKernelGGL((weight_rows_kernel<true>), grid, dim3(64 * kRowsWGFlow), lds, s, bt);
+            else         hipLaunchKernelGGL((weight_rows_kernel<false>), grid, dim3(64 * kRowsWGFlow), lds, s, bt);
+            return (int)hipGetLastError();
+        }
+        // two-wave row tasks; a format job rides behind the rows.  fmt_blocks: see kFmtItemsPerThread
+        if (fmt && ny == 1) {
+            const size_t items = (size_t)fmt->B * (fmt->ldp >> 3), per = (size_t)64 * kTaskW * kFmtItemsPerThread;
+            const size_t nb = (items + per - 1) / per;
+            bt.fmt = *fmt; bt.fmt_blocks = (int)(nb < 1 ? 1 : (nb > kFmtMaxBlocks ? kFmtMaxBlocks : nb));
+            if (fmt_done) *fmt_done = true;
+        }
+        const dim3 grid(wgs + bt.fmt_blocks, ny);
+        if (any_f16) hipLaunchKernelGGL((weight_row_tasks_kernel<true>), grid, dim3(64 * kTaskW), 0, s, bt);
+        else         hipLaunchKernelGGL((weight_row_tasks_kernel<false>), grid, dim3(64 * kTaskW), 0, s, bt);
         return (int)hipGetLastError();
     }
     if (members > 1) return LBBNN_E_ALIGN;                  // the member dimension exists in the row kernel only

@@ -42,12 +42,14 @@ _MASKS_IN_KERNEL = _os.environ.get("LBBNN_TORCH_MASKS", "0") != "1"
 # pass (default: while a HIP graph is being captured they go on a side stream beside the weight pass and the first GEMM -- only
 # the KL finalize needs them; "always": in eager launches too)
 _DENSE_DEFER = {"0": False, "always": "always"}.get(_os.environ.get("LBBNN_DENSE_DEFER", "1"), True)
-# LBBNN_F16_FIRST=planes: the first row-scaled-fp16 layer of a fused forward reads the network input as fp16 hi | lo planes,
-# made by extra workgroups of the flow launch (lbbnn_layers_operands_x).  Default (f32): it takes the fp32 input as it is and
-# splits it in registers.  Measured on the headline net (tools/precision_time.py, one process, interleaved): the in-register
-# split costs the first GEMM's K loop 1.33 us per step instead of 1.08 (~6 us); the format pass costs 6.9 us as a launch of its
-# own (0.1543 against 0.1487 ms per forward) and as much as it saves when it rides in the flow launch (0.1401 against
-# 0.1392 ms): no form of the pre-pass beats the in-register split, so the simpler one is the default.
+# LBBNN_F16_FIRST: how the first row-scaled-fp16 layer of a fused forward reads the network input.  As fp16 hi | lo planes,
+# made by workgroups behind the rows of the weight-pass launch (lbbnn_layers_operands_x), or (f32) as the fp32 input it is,
+# split in the GEMM's registers.  Default: planes where both forms give the same bits -- the single-variance-product layers
+# of "fp16x3f" (format 3: the GEMM forms x^2 from the halves either way); a three-product layer (format 2) squares the fp32
+# value itself when it has it, so it keeps fp32 x.  f32 / planes: the A/B overrides (never / wherever the format job applies).
+# Measured on the headline net: the in-register split costs the first GEMM's K loop 1.33 us per step instead of 1.08; the
+# format pass costs 6.9 us as a launch of its own and as much as it saves inside the 6 us flow launch (both dropped, DESIGN
+# 7.8); inside the 16 us weight-pass launch it costs less than it saves (profiles/weight_launch_ab.txt).
 # LBBNN_HEAD_FOLD=0: keep the 10-class head a GEMM launch of its own (the skinny kernel) in the fused fp16 forward
 _HEAD_FOLD = _os.environ.get("LBBNN_HEAD_FOLD", "1") != "0"
 _ADV_RIDE = _os.environ.get("LBBNN_ADV_RIDE", "1") != "0"          # training forward: the RNG advance rides in the first GEMM's launch
@@ -55,7 +57,7 @@ _V1_BATCH = _os.environ.get("LBBNN_V1_BATCH", "1") != "0"          # all layers'
 _DEFER_SUMS = _os.environ.get("LBBNN_DEFER_SUMS", "1") != "0"      # column sums finished with the deferred vector chains (A/B knob)
 _LRT_BIAS_HIP = _os.environ.get("LBBNN_LRT_BIAS_HIP", "1") != "0"   # the LRT layer's bias gradients through lbbnn_bias_backward (A/B knob)
 _HEAD_DW = _os.environ.get("LBBNN_HEAD_DW", "1") != "0"           # the head's weight gradients through lbbnn_head_dw (A/B knob)
-_F16_FIRST_PLANES = _os.environ.get("LBBNN_F16_FIRST", "f32") != "f32"
+_F16_FIRST_PLANES = {"f32": False, "planes": True}.get(_os.environ.get("LBBNN_F16_FIRST", ""))      # None: the default rule
 _SIDE = {}
 
 
@@ -1408,11 +1410,13 @@ class _NetworkBase(nn.Module):
         n0 = lgroups[0][1]
         d0 = _lib.group_slice(descs, 0, n0)
         # A first layer in the row-scaled fp16 format reads its x as fp16 hi | lo planes: the format pass over the network
-        # input rides in the SAME launch as the planar flows (lbbnn_layers_operands_x: extra workgroups on the CUs the two
-        # flow workgroups per layer leave idle), so the first GEMM spends no VALU on the split and no launch is added.
+        # input rides in the weight-pass launch (lbbnn_layers_operands_x: workgroups behind the rows, whose memory system idles
+        # through their compute phase), so the first GEMM spends no VALU on the split and no launch is added.  An input the
+        # format job does not take (I % 8, alignment) stays fp32 and is split in the GEMM's registers.
         B, x_planes = x.shape[0], False
-        if (layers[0]._split_now >= 2 and _F16_FIRST_PLANES and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
-                and B > 0):
+        first_planes = layers[0]._split_now == 3 if _F16_FIRST_PLANES is None else _F16_FIRST_PLANES
+        if (layers[0]._split_now >= 2 and first_planes and layers[0].in_features % 8 == 0 and x.stride(1) == 1
+                and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0 and B > 0):
             xp = self._planes("in", B, layers[0].in_features, dev, plan)
             _lib.check(_lib.lib().lbbnn_layers_operands_x(d0, n0, rng.data_ptr() if rng is not None else None,
                                                           snap.data_ptr() if snap is not None else None, 0,

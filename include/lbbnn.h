@@ -1424,10 +1424,10 @@ int lbbnn_elbo_bce_loss_monitor(const float* probs, int ldp, const float* target
                                 float kl_scale, float* loss, int* stats, int accumulate, int64_t* totals, int32_t* guard,
                                 void* stream);
 
-/* lbbnn_layers_operands_snap + lbbnn_format_x of the network input in the SAME launches: the planar flows of a network are two
- * latency-bound workgroups per layer, and the format job (one pass over x) runs as extra workgroups of that launch on the CUs
- * it leaves idle -- no launch of its own, nothing added to the critical path.  Falls back to a separate lbbnn_format_x launch
- * when the flow launch cannot carry it (no planar flows, shapes outside the register form of the flow kernel). */
+/* lbbnn_layers_operands_snap + lbbnn_format_x of the network input in the SAME launches: the format job (one pass over x) runs
+ * as workgroups behind the rows of the weight-pass launch, whose memory system idles through the rows' compute phase -- no
+ * launch of its own.  Falls back to a separate lbbnn_format_x launch when the weight-pass launch cannot carry it (in-kernel
+ * flows, rows that take the generic kernel). */
 int lbbnn_layers_operands_x(const lbbnn_layer_desc_t* layers, int n, uint64_t* rng, uint64_t* rng_snap, uint64_t advance,
                             const float* x, int ldx, void* planes, int ldp, int B, int I, void* stream);
 

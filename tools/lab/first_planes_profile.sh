@@ -1,6 +1,6 @@
 #!/bin/bash
-# Kernel durations of the headline forward with the first layer on fp32 x (default) and on planes formatted by extra
-# workgroups of the flow launch (LBBNN_F16_FIRST=planes), under rocprofv3 --kernel-trace --stats.
+# Kernel durations of the headline forward with the first layer on fp32 x (LBBNN_F16_FIRST=f32) and on planes formatted by
+# workgroups behind the rows of the weight-pass launch (planes: the default under fp16x3f), under rocprofv3 --kernel-trace --stats.
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 export TMPDIR=/tmp
 mkdir -p $R/gpurun_out/r03f
