@@ -215,6 +215,12 @@ class CompactMap(ctypes.Structure):
     _fields_ = [("rows", c_p), ("cols", c_p), ("O_full", c_i), ("I_full", c_i)]
 
 
+class SparseDesc(ctypes.Structure):
+    """lbbnn_sparse_desc_t"""
+    _fields_ = [(n, c_p) for n in ("weight_mu", "weight_rho", "lambdal", "bias_rho", "row_ptr", "col", "mean", "var", "bias_var",
+                                   "kept_rows")] + [("O", c_i), ("I", c_i), ("nnz", c_i), ("cut", ctypes.c_float)]
+
+
 class BaseFrozenDesc(ctypes.Structure):
     """lbbnn_base_frozen_desc_t"""
     _fields_ = [(n, c_p) for n in ("mu", "rho", "lambdal", "bias_mu", "bias_rho", "w_mu", "w_sigma", "alpha", "e_w", "b_mu",
@@ -481,6 +487,11 @@ SIGNATURES = {
     "lbbnn_frozen_operands_compact": (c_i, [ctypes.POINTER(FrozenDesc), ctypes.POINTER(CompactMap), c_i, c_p]),
     "lbbnn_frozen_members_compact": (c_i, [ctypes.POINTER(FrozenDesc), ctypes.POINTER(CompactMap), c_i, c_i, c_p, c_u64, c_p]),
     "lbbnn_gather_columns": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_p]),
+    "lbbnn_sparse_count": (c_i, [ctypes.POINTER(SparseDesc), c_i, c_p]),
+    "lbbnn_sparse_pack": (c_i, [ctypes.POINTER(SparseDesc), c_i, c_p]),
+    "lbbnn_frozen_members_z": (c_i, [ctypes.POINTER(FrozenDesc), c_i, c_i, c_p, c_u64, c_p]),
+    "lbbnn_sparse_layer_members": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_i64, c_p, c_i64, c_p, c_u32, c_i64, c_u64,
+                                         c_p, c_i, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     "lbbnn_base_frozen_operands": (c_i, [ctypes.POINTER(BaseFrozenDesc), ctypes.POINTER(CompactMap), c_i, c_i, ctypes.c_float, c_p]),
     "lbbnn_base_frozen_members": (c_i, [ctypes.POINTER(BaseFrozenDesc), ctypes.POINTER(CompactMap), c_i, c_i, c_i, ctypes.c_float,
                                         ctypes.POINTER(c_p), ctypes.POINTER(c_p), ctypes.POINTER(c_p), c_p, c_u64, c_p]),

@@ -20,7 +20,8 @@
 //     and MNF layer in one launch: 4 B read (e0, L2-resident across members) and 4 B written per weight and member.  Compact:
 //     E0'[o'][j'] * z_m[cols[j']], the gather of the full-width z fused in: no compact z is ever stored.
 //     lbbnn_frozen_members_dense is the same launch behind lbbnn_flow_dense_members (flow_dense_members.hip) instead of the
-//     planar-flow launch: the z of RNVP / MNF-type z flows.
+//     planar-flow launch: the z of RNVP / MNF-type z flows.  lbbnn_frozen_members_z is the planar-flow launch WITHOUT this
+//     kernel: the z of a sparse model (sparse_members.hip), which scales inside its layer kernel.
 //   gather_columns_kernel -- lbbnn_gather_columns: out[b][j] = x[b][idx[j]], one thread per float4 of the output.
 #include <cstdlib>
 #include "lbbnn_device.h"
@@ -281,9 +282,10 @@ int frozen_operands_impl(const lbbnn_frozen_desc_t* L, const lbbnn_compact_map_t
 
 // the per-member part of a frozen model: the z flows of the MNF layers (planar: d.z_flow; dense: F, lbbnn_flow_dense_members),
 // then frozen_scale_kernel.  M (optional): the layers are compact; the flow runs, and z lies, at the FULL width, so member m's
-// z is the full model's, bit for bit.
+// z is the full model's, bit for bit.  z_only (lbbnn_frozen_members_z): the flow launch alone -- e0, e_w_members, ld and flags
+// are neither checked nor read, and nothing is scaled.
 int frozen_members_impl(const lbbnn_frozen_desc_t* L, const lbbnn_dense_members_t* F, bool dense, const lbbnn_compact_map_t* M,
-                        int n, int members, const uint64_t* rng, uint64_t member_advance, void* stream) {
+                        int n, int members, const uint64_t* rng, uint64_t member_advance, void* stream, bool z_only = false) {
     if (!L || (dense && !F)) return LBBNN_E_NULL;
     if (n <= 0 || n > LBBNN_MAX_LAYERS || members < 1 || members > 65535) return LBBNN_E_SHAPE;
     FlowArgs fa[LBBNN_MAX_LAYERS];
@@ -294,14 +296,14 @@ int frozen_members_impl(const lbbnn_frozen_desc_t* L, const lbbnn_dense_members_
     for (int i = 0; i < n; ++i) {
         const lbbnn_frozen_desc_t& d = L[i];
         if (!d.q0_mean) continue;                           // an LRT layer: its e_w is shared by every member
-        if (!d.q0_log_var || !d.z_fwd || !d.e0 || !d.e_w_members) return LBBNN_E_NULL;
+        if (!d.q0_log_var || !d.z_fwd || (!z_only && (!d.e0 || !d.e_w_members))) return LBBNN_E_NULL;
         if (!dense) {
             if (d.z_flow.T < 0 || d.z_flow.T > LBBNN_MAX_FLOW_T) return LBBNN_E_SHAPE;
             for (int t = 0; t < d.z_flow.T; ++t)
                 if (!d.z_flow.u[t] || !d.z_flow.w[t] || !d.z_flow.b[t]) return LBBNN_E_NULL;
         }
         if (!rng) return LBBNN_E_NOISE;
-        if (d.O <= 0 || d.I <= 0 || d.ld < d.I || (!M && d.I > LBBNN_MAX_FLOW_DIM)) return LBBNN_E_SHAPE;
+        if (d.O <= 0 || d.I <= 0 || (!z_only && d.ld < d.I) || (!M && d.I > LBBNN_MAX_FLOW_DIM)) return LBBNN_E_SHAPE;
         int If = d.I;                                       // the width of the flow and of z
         if (M) {
             const int rc = check_map(M[i], d.O, d.I);
@@ -310,9 +312,9 @@ int frozen_members_impl(const lbbnn_frozen_desc_t* L, const lbbnn_dense_members_
             if (If > LBBNN_MAX_FLOW_DIM) return LBBNN_E_SHAPE;
         }
         if (d.z_mstride < If) return LBBNN_E_SHAPE;
-        if ((d.ld & 31) || (d.I & 3) || (If & 3) || (d.z_mstride & 3)) return LBBNN_E_ALIGN;
-        if (!aligned16(d.e0) || !aligned16(d.e_w_members) || !aligned16(d.z_fwd)) return LBBNN_E_ALIGN;
-        if (d.flags & ~LBBNN_F_SPLIT16) return LBBNN_E_FLAGS;
+        if ((!z_only && (d.ld & 31)) || (d.I & 3) || (If & 3) || (d.z_mstride & 3)) return LBBNN_E_ALIGN;
+        if ((!z_only && (!aligned16(d.e0) || !aligned16(d.e_w_members))) || !aligned16(d.z_fwd)) return LBBNN_E_ALIGN;
+        if (!z_only && (d.flags & ~LBBNN_F_SPLIT16)) return LBBNN_E_FLAGS;
         if (M && (d.flags & LBBNN_F_SPLIT16) && (d.I & 7)) return LBBNN_E_ALIGN;
         if (dense) {
             fd[nf] = F[i];
@@ -349,6 +351,7 @@ int frozen_members_impl(const lbbnn_frozen_desc_t* L, const lbbnn_dense_members_
             if (rc) return rc;
         }
     }
+    if (z_only) return 0;
     if (M) hipLaunchKernelGGL(frozen_scale_kernel<true>, dim3(wgs, members), dim3(kFzNT), 0, s, bt);
     else hipLaunchKernelGGL(frozen_scale_kernel<false>, dim3(wgs, members), dim3(kFzNT), 0, s, bt);
     return (int)hipGetLastError();
@@ -368,6 +371,11 @@ extern "C" int lbbnn_frozen_operands_compact(const lbbnn_frozen_desc_t* L, const
 extern "C" int lbbnn_frozen_members(const lbbnn_frozen_desc_t* L, int n, int members, const uint64_t* rng,
                                     uint64_t member_advance, void* stream) {
     return frozen_members_impl(L, nullptr, false, nullptr, n, members, rng, member_advance, stream);
+}
+
+extern "C" int lbbnn_frozen_members_z(const lbbnn_frozen_desc_t* L, int n, int members, const uint64_t* rng,
+                                      uint64_t member_advance, void* stream) {
+    return frozen_members_impl(L, nullptr, false, nullptr, n, members, rng, member_advance, stream, true);
 }
 
 extern "C" int lbbnn_frozen_members_dense(const lbbnn_frozen_desc_t* L, const lbbnn_dense_members_t* F, int n, int members,

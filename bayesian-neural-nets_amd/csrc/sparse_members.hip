@@ -1,0 +1,348 @@
+// Sparse median-probability model (gfx950): the kept weights of a frozen LRT / MNF network in CSR, and the member layers
+// evaluated on the vector ALU from that format alone, see include/lbbnn.h.
+//
+//   sparse_rows_kernel -- lbbnn_sparse_count / lbbnn_sparse_pack: one launch over the rows of up to LBBNN_MAX_LAYERS layers,
+//     ONE WAVE PER ROW (four rows per 256-thread workgroup).  The wave walks its row 64 columns at a time: a lane loads one
+//     lambdal (a 256-B line per wave), the ballot of `lambdal > cut` is the kept set of the 64 columns, and a kept lane's
+//     place is the running count of the row plus the number of kept lanes below it (mbcnt of the ballot) -- ascending
+//     columns without a sort, an atomic or LDS.  Pack: kept lanes load mu / rho and store col / mean / var there; lane 0
+//     stores bias_var.  Count: lane 0 stores the row's total.  The arithmetic of var / bias_var is frozen_operands_kernel's
+//     (k1_sigma, softplus_ref of lbbnn_device.h), so the values are its bits.
+//   sparse_layer_kernel -- lbbnn_sparse_layer_members: ONE LANE PER BATCH ROW, WEIGHTS WAVE-UNIFORM.  A wave owns 64 rows of
+//     one member (blockIdx.y: the row tile, blockIdx.z: the member, so z_m[col] is uniform) and four consecutive output
+//     units, one philox_normal4 call per lane as in the dense epilogue.  It walks the CSR row of each unit once: col / mean /
+//     var (and z[col]) are the same for all lanes -- scalar loads, eight nonzeros a batch -- and a lane does two FMAs per
+//     nonzero on its own row's activation, which it loads from the transposed buffer a[col][b]: one contiguous 256-B line
+//     per wave and nonzero.  The four waves of a workgroup take the same row tile and neighbouring unit groups, so they
+//     read the same activation lines.  No cross-lane step: the sums are sequential in CSR order by construction.  The only
+//     LDS is the <= 16-unit head's: its four waves exchange the tile's logits for the log_softmax.  Two batch rows per lane
+//     (tiles of 128 rows, 8-B loads, packed fp32 FMAs) halve the scalar work per row, which is what bounds the loop.
+#include <cstdlib>
+#include "lbbnn_device.h"
+#include "lbbnn_internal.h"
+#include "operand_store.h"
+
+namespace {
+
+using namespace lbbnn;
+
+constexpr int kSpRows = 4;                 // weight rows (= waves) per workgroup of the count / pack kernel
+constexpr int kSpNT = 64 * kSpRows;
+constexpr int kSpChunk = 8;                // nonzeros whose activation loads are in flight together
+
+struct SparseLayer {
+    const float* mu; const float* rho; const float* lambdal; const float* bias_rho;
+    const int32_t* row_ptr; int32_t* col; float* mean; float* var; float* bias_var; int32_t* kept_rows;
+    int O, I, nnz;
+    float cut;
+};
+struct SparseBatch { SparseLayer l[LBBNN_MAX_LAYERS]; int wg_end[LBBNN_MAX_LAYERS]; int n; };
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+template <bool kPack>
+__global__ __launch_bounds__(kSpNT) void sparse_rows_kernel(const SparseBatch bt_) {
+    const LBBNN_CONST_AS SparseBatch* bt = kernarg_as<SparseBatch>();
+    int wg0;
+    const int li = layer_of(bt, wg0);
+    const LBBNN_CONST_AS SparseLayer& a = bt->l[li];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int o = kSpRows * ((int)blockIdx.x - wg0) + wv;
+    if (o >= a.O) return;                                                 // (whole waves leave: no barrier below)
+    const int I = a.I;
+    const size_t rowoff = (size_t)o * I;
+    const float cut = a.cut;
+    int base = 0, end = 0;
+    if constexpr (kPack) {
+        // the row's slots, inside [0, nnz] whatever row_ptr holds
+        base = clampi(a.row_ptr[o], 0, a.nnz);
+        end = clampi(a.row_ptr[o + 1], base, a.nnz);
+    }
+    int run = 0;                                                          // kept so far in this row (wave-uniform)
+    for (int c0 = 0; c0 < I; c0 += 64) {
+        const int c = c0 + lane;
+        const bool kept = c < I && a.lambdal[rowoff + c] > cut;           // fp32 compare: NaN is never kept
+        const unsigned long long m = __ballot(kept);
+        if constexpr (kPack) {
+            const int below = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+            const int pos = base + run + below;
+            if (kept && pos < end) {
+                const float sigma = k1_sigma(a.rho[rowoff + c]);
+                a.col[pos] = c;
+                a.mean[pos] = a.mu[rowoff + c];
+                a.var[pos] = sigma * sigma;
+            }
+        }
+        run += __popcll(m);
+    }
+    if (lane == 0) {
+        if constexpr (kPack) {
+            const float sb = softplus_ref(a.bias_rho[o]);
+            a.bias_var[o] = sb * sb;                  // bias.sigma**2, LBBNN-GP-MF-LRT.py:173 (never gated)
+        } else {
+            a.kept_rows[o] = run;
+        }
+    }
+}
+
+int sparse_rows_impl(const lbbnn_sparse_desc_t* L, int n, bool pack, void* stream) {
+    if (!L) return LBBNN_E_NULL;
+    if (n <= 0 || n > LBBNN_MAX_LAYERS) return LBBNN_E_SHAPE;
+    SparseBatch bt = {};
+    int wgs = 0;
+    for (int i = 0; i < n; ++i) {
+        const lbbnn_sparse_desc_t& d = L[i];
+        if (!d.lambdal) return LBBNN_E_NULL;
+        if (pack) {
+            if (!d.weight_mu || !d.weight_rho || !d.bias_rho || !d.row_ptr || !d.bias_var) return LBBNN_E_NULL;
+            if (d.nnz > 0 && (!d.col || !d.mean || !d.var)) return LBBNN_E_NULL;
+        } else if (!d.kept_rows) return LBBNN_E_NULL;
+        if (d.O <= 0 || d.I <= 0 || (pack && d.nnz < 0)) return LBBNN_E_SHAPE;
+        if (!aligned4(d.lambdal)) return LBBNN_E_ALIGN;
+        if (pack) {
+            if (!aligned4(d.weight_mu) || !aligned4(d.weight_rho) || !aligned4(d.bias_rho) || !aligned4(d.row_ptr) ||
+                !aligned4(d.col) || !aligned4(d.mean) || !aligned4(d.var) || !aligned4(d.bias_var)) return LBBNN_E_ALIGN;
+        } else if (!aligned4(d.kept_rows)) return LBBNN_E_ALIGN;
+        SparseLayer& a = bt.l[i];
+        a.mu = d.weight_mu; a.rho = d.weight_rho; a.lambdal = d.lambdal; a.bias_rho = d.bias_rho;
+        a.row_ptr = d.row_ptr; a.col = d.col; a.mean = d.mean; a.var = d.var; a.bias_var = d.bias_var; a.kept_rows = d.kept_rows;
+        a.O = d.O; a.I = d.I; a.nnz = pack ? d.nnz : 0; a.cut = d.cut;
+        wgs += (d.O + kSpRows - 1) / kSpRows;
+        bt.wg_end[i] = wgs;
+    }
+    bt.n = n;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (pack) hipLaunchKernelGGL(sparse_rows_kernel<true>, dim3(wgs), dim3(kSpNT), 0, s, bt);
+    else hipLaunchKernelGGL(sparse_rows_kernel<false>, dim3(wgs), dim3(kSpNT), 0, s, bt);
+    return (int)hipGetLastError();
+}
+
+struct SpArgs {
+    const int32_t* row_ptr; const int32_t* col; const float* mean; const float* var;
+    const float* bias_mu; const float* bias_var;
+    const float* a; long long a_ms; int lda; int a_bytes;     // a_bytes: what a member's block of `a` spans
+    const float* z; long long z_ms;
+    const uint64_t* rng; uint32_t rng_stream; long long row_offset; unsigned long long m_adv;
+    float* out; long long o_ms; int ldo;
+    int B, I, O, nnz, relu, lsm, out_rows;
+};
+
+__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// kR batch rows of a lane as one value: the two-row form loads them as one 8-B word and does its FMAs as packed fp32
+// (v_pk_fma_f32: IEEE per component, so a row's bits are those of the one-row form)
+typedef float sp_f2 __attribute__((ext_vector_type(2)));
+template <int kR> struct SpRows;
+template <> struct SpRows<1> {
+    typedef float T;
+    static __device__ __forceinline__ T load(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
+        return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
+    }
+    static __device__ __forceinline__ T splat(float v) { return v; }
+    static __device__ __forceinline__ T fma(float w, T x, T acc) { return __builtin_fmaf(w, x, acc); }
+    static __device__ __forceinline__ float get(T v, int) { return v; }
+};
+template <> struct SpRows<2> {
+    typedef sp_f2 T;
+    static __device__ __forceinline__ T load(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
+        return __builtin_bit_cast(sp_f2, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
+    }
+    static __device__ __forceinline__ T splat(float v) { return sp_f2{v, v}; }
+    static __device__ __forceinline__ T fma(float w, T x, T acc) { return __builtin_elementwise_fma(sp_f2{w, w}, x, acc); }
+    static __device__ __forceinline__ float get(T v, int i) { return i ? v.y : v.x; }
+};
+
+// One nonzero of a unit's CSR row for the lane's rows: the column index is taken inside [0, I) whatever the array holds
+// (one unsigned minimum), the weights are wave-uniform, the activation line is a buffer load at a scalar offset
+#define LBBNN_SP_LOAD(t, k)                                                         \
+    do {                                                                            \
+        const unsigned c = min((unsigned)a.col[k], imax);                           \
+        w[t] = a.mean[k];                                                           \
+        v[t] = kMeanOnly ? 0.f : a.var[k];                                          \
+        if (kZ) w[t] *= z[c];               /* (mu * a) * z_k, K1's order of products */ \
+        x[t] = R::load(act, boff, c * lda4);                                        \
+    } while (0)
+#define LBBNN_SP_FMA(t)                                                             \
+    do {                                                                            \
+        am[r] = R::fma(w[t], x[t], am[r]);                                          \
+        if (!kMeanOnly) av[r] = R::fma(v[t], x[t] * x[t], av[r]);                   \
+    } while (0)
+
+// kR: batch rows per lane (1: tiles of 64 rows; 2: tiles of 128, lane l owns rows 2l and 2l + 1 of the tile).  The four waves
+// of a workgroup take the same row tile and four neighbouring unit groups; a <= 16-unit head with log_softmax is one
+// workgroup per tile, and its waves hand each other the tile's logits through LDS.
+template <bool kMeanOnly, bool kZ, int kR>
+__global__ __launch_bounds__(256) void sparse_layer_kernel(const SpArgs a) {
+#pragma clang fp contract(off)
+    typedef SpRows<kR> R;
+    typedef typename R::T rows_t;
+    __shared__ float logits[16][64 * kR];
+    const int lane = threadIdx.x & 63, wv = uniform(threadIdx.x >> 6);
+    const int mem = blockIdx.z;
+    const int b = ((int)blockIdx.y * 64 + lane) * kR;                     // the lane's first row
+    const bool live = b < a.B;
+    // a lane past the batch computes rows 0 .. kR - 1 again (in bounds, never stored): no lane-dependent branch in the loop.
+    // A load is a buffer load of the member's block: the lane's byte offset in a register that never changes, the line
+    // (col * lda * 4) as the scalar offset -- no vector instruction for an address, and a range check in hardware
+    const __amdgpu_buffer_rsrc_t act = __builtin_amdgcn_make_buffer_rsrc((void*)(a.a + (size_t)mem * a.a_ms), 0, a.a_bytes, 0x00020000);
+    const unsigned lda4 = 4u * (unsigned)a.lda, imax = (unsigned)a.I - 1u;
+    const unsigned boff = live ? 4u * (unsigned)b : 0u;
+    const float* z = kZ ? a.z + (size_t)mem * a.z_ms : nullptr;
+    uint64_t seed = 0, offs = 0;
+    if (!kMeanOnly) { seed = a.rng[0]; offs = a.rng[1] + (uint64_t)mem * a.m_adv; }
+    const int o0 = 4 * ((int)blockIdx.x * 4 + wv);
+    const bool any = o0 < a.O;                                            // wave-uniform
+    float res[kR][4];
+#pragma unroll
+    for (int i = 0; i < kR; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) res[i][r] = 0.f;
+    if (any) {
+        rows_t am[4], av[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            am[r] = R::splat(0.f); av[r] = R::splat(0.f);
+            const int o = o0 + r;
+            if (o >= a.O) continue;                                       // wave-uniform
+            const int k0 = uniform(clampi(a.row_ptr[o], 0, a.nnz));
+            const int k1 = uniform(clampi(a.row_ptr[o + 1], k0, a.nnz));
+            int k = k0;
+            rows_t x[kSpChunk];
+            float w[kSpChunk], v[kSpChunk];
+            for (; k + kSpChunk <= k1; k += kSpChunk) {
+#pragma unroll
+                for (int t = 0; t < kSpChunk; ++t) LBBNN_SP_LOAD(t, k + t);
+#pragma unroll
+                for (int t = 0; t < kSpChunk; ++t) LBBNN_SP_FMA(t);
+            }
+            const int rem = k1 - k;                                       // the last, partial batch: its loads in flight together too
+            if (rem > 0) {
+#pragma unroll
+                for (int t = 0; t < kSpChunk - 1; ++t) if (t < rem) LBBNN_SP_LOAD(t, k + t);
+#pragma unroll
+                for (int t = 0; t < kSpChunk - 1; ++t) if (t < rem) LBBNN_SP_FMA(t);
+            }
+        }
+        // the local-reparameterisation epilogue of the dense GEMMs (LBBNN-GP-MF-LRT.py:172-175) at the same counters
+#pragma unroll
+        for (int i = 0; i < kR; ++i) {
+            float e[4] = {0.f, 0.f, 0.f, 0.f};
+            if (!kMeanOnly) philox_normal4(seed, offs, a.rng_stream, (uint64_t)(a.row_offset + b + i), (uint32_t)(o0 >> 2), e);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int o = o0 + r;
+                if (o >= a.O) continue;
+                float mean = R::get(am[r], i) + a.bias_mu[o];
+                if (!kMeanOnly) mean = __builtin_fmaf(sqrt_hw(R::get(av[r], i) + a.bias_var[o]), e[r], mean);
+                res[i][r] = a.relu ? fmaxf(mean, 0.f) : mean;
+            }
+        }
+    }
+    if (a.lsm) {                                                          // (every wave of the one workgroup of the tile gets here)
+        // log_softmax over the row (LBBNN-GP-MF-LRT.py:210): the tile's logits through LDS, every lane sums its rows in unit order
+#pragma unroll
+        for (int i = 0; i < kR; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) logits[4 * wv + r][kR * lane + i] = res[i][r];
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < kR; ++i) {
+            float mx = -INFINITY;
+            for (int j = 0; j < a.O; ++j) mx = fmaxf(mx, logits[j][kR * lane + i]);
+            float se = 0.f;
+            for (int j = 0; j < a.O; ++j) se += expf(logits[j][kR * lane + i] - mx);
+            const float lse = mx + logf(se);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) res[i][r] -= lse;
+        }
+    }
+    if (!live || !any) return;
+    float* out = a.out + (size_t)mem * a.o_ms;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int o = o0 + r;
+        if (o >= a.O) continue;
+        if (kR == 2 && !a.out_rows && b + 1 < a.B) {                      // both rows of the lane: one 8-B store
+            *reinterpret_cast<sp_f2*>(out + (size_t)o * a.ldo + b) = sp_f2{res[0][r], res[kR - 1][r]};
+            continue;
+        }
+#pragma unroll
+        for (int i = 0; i < kR; ++i) {
+            if (b + i >= a.B) continue;
+            if (a.out_rows) out[(size_t)(b + i) * a.ldo + o] = res[i][r];
+            else out[(size_t)o * a.ldo + b + i] = res[i][r];
+        }
+    }
+}
+#undef LBBNN_SP_LOAD
+#undef LBBNN_SP_FMA
+
+// rows per lane: LBBNN_SPARSE_ROWS = 1 | 2 overrides the choice (a knob for A/B timing; both forms give the same bits)
+int sparse_rows_per_lane(const SpArgs& a) {
+    static const char* env = getenv("LBBNN_SPARSE_ROWS");
+    // the two-row form reads and writes 8-B words: even strides on 8-B boundaries, and a row B (odd B) that exists
+    const bool can2 = !off(a.a, 8) && !(a.lda & 1) && !(a.a_ms & 1) && a.lda >= a.B + (a.B & 1) &&
+                      (a.out_rows || (!off(a.out, 8) && !(a.ldo & 1) && !(a.o_ms & 1)));
+    if (!can2) return 1;
+    if (env && env[0] == '1') return 1;
+    if (env && env[0] == '2') return 2;
+    return a.B > 64 ? 2 : 1;
+}
+
+template <bool kMeanOnly, bool kZ>
+void launch_sparse_layer(const SpArgs& a, int members, hipStream_t s) {
+    const dim3 block(256);
+    const unsigned groups = (unsigned)((a.O + 15) / 16);                  // (1 with log_softmax: O <= 16)
+    if (sparse_rows_per_lane(a) == 2)
+        hipLaunchKernelGGL((sparse_layer_kernel<kMeanOnly, kZ, 2>), dim3(groups, (unsigned)((a.B + 127) / 128), members), block, 0, s, a);
+    else
+        hipLaunchKernelGGL((sparse_layer_kernel<kMeanOnly, kZ, 1>), dim3(groups, (unsigned)((a.B + 63) / 64), members), block, 0, s, a);
+}
+
+}  // namespace
+
+extern "C" int lbbnn_sparse_count(const lbbnn_sparse_desc_t* L, int n, void* stream) {
+    return sparse_rows_impl(L, n, false, stream);
+}
+
+extern "C" int lbbnn_sparse_pack(const lbbnn_sparse_desc_t* L, int n, void* stream) {
+    return sparse_rows_impl(L, n, true, stream);
+}
+
+extern "C" int lbbnn_sparse_layer_members(const int32_t* row_ptr, const int32_t* col, const float* mean, const float* var,
+                                          int nnz, const float* bias_mu, const float* bias_var, const float* a, int lda,
+                                          int64_t a_mstride, const float* z, int64_t z_mstride, const uint64_t* rng,
+                                          uint32_t rng_stream, int64_t row_offset, uint64_t member_advance, float* out,
+                                          int ldo, int64_t o_mstride, int out_rows, int B, int I, int O, int flags,
+                                          int members, void* stream) {
+    if (B == 0) return 0;
+    if (!row_ptr || !bias_mu || !bias_var || !a || !out) return LBBNN_E_NULL;
+    if (nnz > 0 && (!col || !mean || !var)) return LBBNN_E_NULL;
+    if (B < 0 || (long long)B > 65535LL * 64 || I <= 0 || O <= 0 || nnz < 0 || members < 1 || members > 65535) return LBBNN_E_SHAPE;
+    if (lda < B || ldo < (out_rows ? O : B) || a_mstride < 0 || z_mstride < 0 || o_mstride < 0) return LBBNN_E_SHAPE;
+    // the kernel addresses a member's input as a buffer: I lines of B rows -- of B + 1 where lda has room for the pair of an
+    // odd last row (the two-row form reads it and drops it)
+    const long long a_bytes = 4 * ((long long)(I - 1) * lda + B + ((B & 1) && lda > B ? 1 : 0));
+    if (a_bytes > 0x7FFFFFF0LL) return LBBNN_E_SHAPE;
+    if (members > 1) {
+        // members may share an input (a_mstride == 0: the first layer's x^T), never an output
+        const long long need = out_rows ? (long long)(B - 1) * ldo + O : (long long)(O - 1) * ldo + B;
+        if (o_mstride < need || (a_mstride && a_mstride < (long long)(I - 1) * lda + B) || (z && z_mstride < I)) return LBBNN_E_SHAPE;
+    }
+    const bool mean_only = (flags & LBBNN_F_MEAN_ONLY) != 0, lsm = (flags & LBBNN_F_LOG_SOFTMAX) != 0;
+    if (flags & ~(LBBNN_F_RELU | LBBNN_F_MEAN_ONLY | LBBNN_F_LOG_SOFTMAX)) return LBBNN_E_FLAGS;
+    if (lsm && (O > 16 || (flags & LBBNN_F_RELU) || !out_rows)) return LBBNN_E_FLAGS;
+    if (!mean_only && !rng) return LBBNN_E_NOISE;
+    if (!aligned4(row_ptr) || !aligned4(col) || !aligned4(mean) || !aligned4(var) || !aligned4(bias_mu) || !aligned4(bias_var) ||
+        !aligned4(a) || !aligned4(z) || !aligned4(out) || off(rng, 8)) return LBBNN_E_ALIGN;
+    SpArgs k = {};
+    k.row_ptr = row_ptr; k.col = col; k.mean = mean; k.var = var; k.bias_mu = bias_mu; k.bias_var = bias_var;
+    k.a = a; k.a_ms = a_mstride; k.lda = lda; k.a_bytes = (int)a_bytes; k.z = z; k.z_ms = z_mstride;
+    k.rng = rng; k.rng_stream = rng_stream; k.row_offset = row_offset; k.m_adv = member_advance;
+    k.out = out; k.o_ms = o_mstride; k.ldo = ldo;
+    k.B = B; k.I = I; k.O = O; k.nnz = nnz; k.relu = (flags & LBBNN_F_RELU) ? 1 : 0; k.lsm = lsm ? 1 : 0; k.out_rows = out_rows ? 1 : 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (mean_only) { if (z) launch_sparse_layer<true, true>(k, members, s); else launch_sparse_layer<true, false>(k, members, s); }
+    else { if (z) launch_sparse_layer<false, true>(k, members, s); else launch_sparse_layer<false, false>(k, members, s); }
+    return (int)hipGetLastError();
+}

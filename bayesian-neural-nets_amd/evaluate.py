@@ -2242,7 +2242,194 @@ def _freeze_compact(net, layers, family, threshold) -> CompactFrozenNetwork:
     return fz._bind(net, need, masks)
 
 
-def freeze(net, gates: str = "alpha", *, threshold: float = 0.5, dense: bool = False, compact: bool = False) -> FrozenNetwork:
+class SparseFrozenNetwork(FrozenNetwork):
+    """The median probability model as its kept weights alone (``freeze(net, "mpm", sparse=True)``): per layer a CSR of the
+    weights with ``lambdal > logit(threshold)`` -- buffers ``row_ptr_<i>`` (O + 1) int32, ``col_<i>`` (nnz) int32 ascending
+    within a row, ``mean_<i>`` (nnz) = weight_mu, ``var_<i>`` (nnz) = sigma^2 -- plus the dense ``bias_mu``, ``bias_var`` and
+    ``kept_rows``.  There is no dense e0 / e_w / var_w operand and no per-member operand: a layer is ONE
+    lbbnn_sparse_layer_members launch for all members, on the vector ALU, over the kept weights only, whatever the network's
+    precision setting (the model is fp32).  ``csr(i)``: the four tensors of layer i; ``nnz`` / ``operand_bytes``: plain ints.
+
+    Draws: member m draws at Philox offset live + m; eps_out of layer i from stream STREAM_EPS_OUT * 64 + layer id at counter
+    (row_offset + b, o / 4) with o the network's own output index, z of an MNF layer from the flow launch of
+    ``freeze(net, "mpm")`` (lbbnn_frozen_members_z) -- the draws of the dense median model bit for bit, so a member equals
+    that model's member to fp32 rounding (the sums run over the kept weights in column order, sequentially).  The bits of an
+    output depend on its member, row and unit alone.  No ``refresh()`` and no ``evaluate.explain``: freeze again, or use
+    ``freeze(net, "mpm")``."""
+
+    def __init__(self, dims, family: str = "lrt", threshold: float = 0.5, device=None, head: str = "log_softmax"):
+        _FrozenModel.__init__(self, dims, "mpm", threshold, device, head)
+        self._init_family(family, None)
+        self._nnz = []
+
+    def extra_repr(self) -> str:
+        return "%s, sparse, nnz=%d" % (super().extra_repr(), self.nnz)
+
+    def _device(self):
+        return self._buf("kept_rows", 0).device
+
+    @property
+    def nnz(self) -> int:
+        """Kept weights over every layer."""
+        return sum(self._nnz)
+
+    @property
+    def operand_bytes(self) -> int:
+        """Bytes of everything the layer launches read of this model: row_ptr, col, mean, var, bias_mu and bias_var."""
+        return sum(4 * (self.dims[i + 1] + 1) + 12 * n + 8 * self.dims[i + 1] for i, n in enumerate(self._nnz))
+
+    def csr(self, i: int):
+        """(row_ptr, col, mean, var) of layer i."""
+        return tuple(self._buf(k, i) for k in ("row_ptr", "col", "mean", "var"))
+
+    @torch.no_grad()
+    def _bind(self, net, need=None, masks=None):
+        """Count, scan, size (the ONE host read), pack: two batched launches per layer group and torch's cumsum between."""
+        from . import _lib
+        layers = net._layers()
+        dev = layers[0].weight_mu.device
+        f = dict(dtype=torch.float32, device=dev)
+        n = self.n_layers
+        self._src = [net]
+        self._layer_ids = [int(l._layer_id) for l in layers]
+        self._row_offsets = [int(l.row_offset) for l in layers]
+        self._split = [False] * n
+        descs = (_lib.SparseDesc * n)()
+        for i, l in enumerate(layers):
+            O, If = self.dims[i + 1], self.dims[i]
+            for name in ("weight_mu", "weight_rho", "lambdal"):
+                if not getattr(l, name).is_contiguous():
+                    raise RuntimeError("bnn_amd: %s of layer %d is not contiguous" % (name, i + 1))
+            for name in ("bias_var", "bias_mu"):
+                self.register_buffer("%s_%d" % (name, i), _empty((O,), **f))
+            if l._mnf:
+                T = len(l.z_flow.transforms)
+                self._T.append(T)
+                for name, shape in (("q0_mean", (If,)), ("q0_log_var", (If,)), ("flow_u", (T, If)), ("flow_w", (T, If)),
+                                    ("flow_b", (T, 1))):
+                    self.register_buffer("%s_%d" % (name, i), _empty(shape, **f))
+            else:
+                self._T.append(0)
+            d = descs[i]
+            d.weight_mu, d.weight_rho, d.lambdal = l.weight_mu.data_ptr(), l.weight_rho.data_ptr(), l.lambdal.data_ptr()
+            d.bias_rho = l.bias_rho.data_ptr()
+            d.bias_var, d.kept_rows = self._buf("bias_var", i).data_ptr(), self._buf("kept_rows", i).data_ptr()
+            d.O, d.I, d.cut = O, If, self.cut
+        dst, src = self._z_copies(layers)
+        dst += [self._buf("bias_mu", i) for i in range(n)]
+        src += [l.bias_mu.detach() for l in layers]
+        torch._foreach_copy_(dst, src)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            for k, cnt in _lib.layer_groups(n):
+                _lib.check(_lib.lib().lbbnn_sparse_count(_lib.group_slice(descs, k, cnt), cnt, stream), "lbbnn_sparse_count")
+            for i in range(n):
+                self.register_buffer("row_ptr_%d" % i, ops.sparse_row_ptr(self._buf("kept_rows", i)))
+            self._nnz = [int(v) for v in torch.stack([self._buf("row_ptr", i)[-1] for i in range(n)]).tolist()]   # the host read
+            for i, nz in enumerate(self._nnz):
+                # (col comes from _empty too, as fp32 words: a NaN-filled slot that was never packed is an index out of range)
+                self.register_buffer("col_%d" % i, _empty((nz,), **f).view(torch.int32))
+                self.register_buffer("mean_%d" % i, _empty((nz,), **f))
+                self.register_buffer("var_%d" % i, _empty((nz,), **f))
+                d = descs[i]
+                d.row_ptr, d.nnz = self._buf("row_ptr", i).data_ptr(), nz
+                d.col, d.mean, d.var = (self._buf(k, i).data_ptr() for k in ("col", "mean", "var"))
+            for k, cnt in _lib.layer_groups(n):
+                _lib.check(_lib.lib().lbbnn_sparse_pack(_lib.group_slice(descs, k, cnt), cnt, stream), "lbbnn_sparse_pack")
+        self._point()
+        return self
+
+    def refresh(self):
+        raise NotImplementedError("bnn_amd: a sparse model does not refresh: the structure, and with it the size of every CSR "
+                                  "buffer, may have changed with the parameters -- freeze again (evaluate.freeze(net, \"mpm\", "
+                                  "sparse=True))")
+
+    def _member_buffers(self, c: int):
+        """z [c][sum of ld], every MNF layer's block side by side (one member stride, one flow launch); no member operands."""
+        if c > self._mcap:
+            self._zbuf = _empty((c, sum(ops.operand_ld(d) for d in self.dims[:-1])), dtype=torch.float32, device=self._device())
+            self._mcap = c
+        return self._zbuf, []
+
+    def _draw_members(self, c: int, rng, stream, masks=None):
+        """MNF: member m's z at Philox offset rng[1] + m -- the flow launch of the dense model alone (lbbnn_frozen_members_z)."""
+        from . import _lib
+        zbuf, _ = self._member_buffers(c)
+        n = self.n_layers
+        descs = (_lib.FrozenDesc * n)()
+        off = 0
+        for i in range(n):
+            d = descs[i]
+            d.O, d.I, d.layer_id = self.dims[i + 1], self.dims[i], self._layer_ids[i]
+            d.q0_mean, d.q0_log_var = self._buf("q0_mean", i).data_ptr(), self._buf("q0_log_var", i).data_ptr()
+            u, w, b = self._buf("flow_u", i), self._buf("flow_w", i), self._buf("flow_b", i)
+            d.z_flow.T = self._T[i]
+            for t in range(self._T[i]):
+                d.z_flow.u[t], d.z_flow.w[t], d.z_flow.b[t] = u[t].data_ptr(), w[t].data_ptr(), b[t].data_ptr()
+            d.z_fwd, d.z_mstride = zbuf.data_ptr() + 4 * off, zbuf.stride(0)
+            off += ops.operand_ld(self.dims[i])
+        for k, cnt in _lib.layer_groups(n):
+            _lib.check(_lib.lib().lbbnn_frozen_members_z(_lib.group_slice(descs, k, cnt), cnt, c, rng.data_ptr(), 1, stream),
+                       "lbbnn_frozen_members_z")
+        return zbuf, []
+
+    def _layers_of(self, zbuf, c: int):
+        """The per-layer tuples ops.sparse_member_chain takes; zbuf None: an LRT model."""
+        out, off = [], 0
+        for i in range(self.n_layers):
+            z = None if zbuf is None else zbuf[:c, off:off + self.dims[i]]
+            off += ops.operand_ld(self.dims[i])
+            out.append(self.csr(i) + (self._buf("bias_mu", i), self._buf("bias_var", i), z,
+                                      ops.STREAM_EPS_OUT * 64 + self._layer_ids[i], self._row_offsets[i]))
+        return out
+
+    def _chunk(self, x, c: int, st, head, zs, ms=None):
+        """Members live .. live + c - 1 of the ensemble into head (c, pad4(B * classes)): MNF one flow launch for z, then the
+        input transpose and one lbbnn_sparse_layer_members launch per layer."""
+        dev = x.device
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        zbuf = None
+        if self.family == "mnf":
+            zbuf, _ = self._draw_members(c, st.t, stream)
+            if zs is not None:
+                zs.append(self._z_of(zbuf, c))
+        ops.sparse_member_chain(x, c, self._layers_of(zbuf, c), head=self.head, out=head, empty=_empty, rng=st.t, stream=stream)
+        st.advance(c)                                        # as c single forwards would have
+
+    @torch.no_grad()
+    def forward(self, data: torch.Tensor, sample: bool = False, *, log_probs: bool = False) -> torch.Tensor:
+        """(B, classes) of one member, as ``FrozenNetwork.forward``: ``sample=True`` is member 0 of ``ensemble(data, 1)``;
+        ``sample=False`` the posterior-mean branch, for which an MNF model still draws its z and advances the live offset by
+        1 and an LRT model draws nothing."""
+        _check_log_probs(self, log_probs)
+        if sample:
+            return self.ensemble(data, 1, log_probs=log_probs)[0]
+        x = self._input(data)
+        B, C, dev = x.shape[0], self.dims[-1], x.device
+        st = ops.RngState.get(dev)
+        with torch.cuda.device(dev):
+            if B == 0:
+                if self.family == "mnf":
+                    st.advance(1)
+                return torch.zeros((0, 2 if log_probs else C), dtype=torch.float32, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            zbuf = self._draw_members(1, st.t, stream)[0] if self.family == "mnf" else None
+            head = _empty((1, ops.pad4(B * C)), dtype=torch.float32, device=dev)
+            ops.sparse_member_chain(x, 1, self._layers_of(zbuf, 1), head=self.head, out=head, empty=_empty, stochastic=False,
+                                    stream=stream)
+            if zbuf is not None:
+                st.advance(1)
+        return self._finish(head, 1, B, log_probs)[0]
+
+
+def _freeze_sparse(net, layers, family, threshold) -> SparseFrozenNetwork:
+    fz = SparseFrozenNetwork(net.dims, family, threshold, device=layers[0].weight_mu.device, head=net.head)
+    fz.eval()
+    return fz._bind(net)
+
+
+def freeze(net, gates: str = "alpha", *, threshold: float = 0.5, dense: bool = False, compact: bool = False,
+           sparse: bool = False) -> FrozenNetwork:
     """Frozen evaluation model of an LRT / MNF network (``lrt.BayesianNetwork``, ``mnf.BayesianNetwork``) on a HIP device.
 
     ``gates="alpha"``: the gates as trained, a = sigmoid(lambdal) -- ``frozen.ensemble(x, S)`` computes what
@@ -2271,7 +2458,15 @@ def freeze(net, gates: str = "alpha", *, threshold: float = 0.5, dense: bool = F
     the same kernels at the smaller shapes.  Its posterior-mean forward equals the full model's to fp32 rounding; its
     stochastic members equal the full model's in distribution (z is the same bits, eps_out is indexed by the compact column).
     The one device read that sizes its buffers happens here.  Refused, each with a ValueError that says what to use instead:
-    ``gates="alpha"``, ``dense=True``, and a network with dense coupling z flows."""
+    ``gates="alpha"``, ``dense=True``, and a network with dense coupling z flows.
+
+    ``sparse=True`` (with ``gates="mpm"``; LRT and planar MNF networks, every head, 1 to 16 layers) returns a
+    ``SparseFrozenNetwork``: the median probability model as a CSR of its kept weights, evaluated by a vector-ALU kernel that
+    touches no pruned weight and writes no per-member operand.  Its members have the draws of ``freeze(net, "mpm")`` bit for bit
+    (z and eps_out at the network's own indices) and equal that model's members to fp32 rounding; it is fp32 whatever the
+    precision setting, and it takes any ``in_features`` of an LRT network.  Opt-in: nothing chooses it by density.  The one
+    device read that sizes its buffers happens here.  Refused, each with a ValueError that says what to use instead:
+    ``gates="alpha"``, ``compact=True``, ``dense=True``, and a network with dense coupling z flows."""
     from . import layers as L
     FrozenNetwork._check_gates(gates)
     _cut(threshold)
@@ -2294,6 +2489,19 @@ def freeze(net, gates: str = "alpha", *, threshold: float = 0.5, dense: bool = F
         if any(l._mnf and l._check_flows() == "dense" for l in layers):
             raise ValueError("bnn_amd: compact=True is not built for dense coupling z flows (the member kernel keeps z in LDS at "
                              "full width) -- use freeze(net, \"mpm\", dense=True) for the full median probability model")
+    if sparse:
+        if gates != "mpm":
+            raise ValueError("bnn_amd: sparse=True needs gates=\"mpm\": alpha gates are never exactly zero, so there is no zero "
+                             "to skip -- use freeze(net, \"mpm\", sparse=True), or freeze(net) for the gates as trained")
+        if compact:
+            raise ValueError("bnn_amd: sparse=True does not take compact=True (a dropped unit already costs a sparse model only "
+                             "its epilogue) -- use freeze(net, \"mpm\", sparse=True) or freeze(net, \"mpm\", compact=True)")
+        if dense:
+            raise ValueError("bnn_amd: sparse=True does not take dense=True (the sparse model draws z through the planar flow "
+                             "launch only) -- use freeze(net, \"mpm\", dense=True) for the dense median probability model")
+        if any(l._mnf and l._check_flows() == "dense" for l in layers):
+            raise ValueError("bnn_amd: sparse=True is not built for dense coupling z flows -- use freeze(net, \"mpm\", "
+                             "dense=True) for the dense median probability model")
     _check_freezable_layers(layers, dense=bool(dense))
     if not layers[0].weight_mu.is_cuda:
         raise RuntimeError("bnn_amd: freeze needs the network on a HIP device (it is on %s); there is no CPU path"
@@ -2301,6 +2509,8 @@ def freeze(net, gates: str = "alpha", *, threshold: float = 0.5, dense: bool = F
     family = "mnf" if layers[0]._mnf else "lrt"
     if compact:
         return _freeze_compact(net, layers, family, float(threshold))
+    if sparse:
+        return _freeze_sparse(net, layers, family, float(threshold))
     flows = layers[0]._check_flows() if family == "mnf" else None          # "planar" | "dense" (checked above)
     fz = FrozenNetwork(net.dims, family, gates, threshold, device=layers[0].weight_mu.device, flows=flows, head=net.head)
     fz.eval()
@@ -2625,6 +2835,10 @@ def _check_explainable(fz):
     if not isinstance(fz, FrozenNetwork):
         raise TypeError("bnn_amd: explain takes a FrozenNetwork (evaluate.freeze(net, \"alpha\" | \"mpm\")), got %s"
                         % type(fz).__name__)
+    if isinstance(fz, SparseFrozenNetwork):
+        raise ValueError("bnn_amd: explain is not built for sparse=True models (its sweep multiplies by dense operands, which a "
+                         "sparse model does not hold); explain the dense median probability model: "
+                         "evaluate.explain(evaluate.freeze(net, \"mpm\"), data)")
     if fz.flows == "dense":
         raise ValueError("bnn_amd: explain is not built for dense=True models (RNVP / MNF-type z flows); use planar z flows "
                          "(mnf.BayesianNetwork(..., z_flow_type=\"Planar\")) or an LRT network")

@@ -696,6 +696,75 @@ int lbbnn_frozen_members_compact(const lbbnn_frozen_desc_t* layers, const lbbnn_
 int lbbnn_gather_columns(const float* x, int ldx, const int32_t* idx, int n_idx, float* out, int ldo, int B, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Sparse median-probability model: the kept weights of LBBNN_FROZEN_MPM alone, in CSR, evaluated by a vector-ALU kernel that
+ * touches no pruned weight.  Per layer, with the keep rule of lbbnn_frozen_operands (lambdal > cut compared in fp32, NaN is
+ * never kept) and columns ascending within a row:
+ *     row_ptr (O + 1) int32, the exclusive scan of kept_rows;   col (nnz) int32;
+ *     mean (nnz) fp32 = weight_mu;   var (nnz) fp32 = sigma^2, sigma = log1p(exp(weight_rho)) through the device functions of
+ *     lbbnn_frozen_operands, so var is bit for bit its fp32 var_w at the kept places;   bias_var (O) = softplus(bias_rho)^2.
+ *
+ * lbbnn_sparse_count: ONE launch for all n <= LBBNN_MAX_LAYERS layers, one wave per weight row: kept_rows[o] = the number
+ *   of weights of row o with lambdal > cut.  Reads lambdal only; the caller scans kept_rows into row_ptr.
+ *   NULL layers / lambdal / kept_rows: LBBNN_E_NULL; n outside [1, LBBNN_MAX_LAYERS], O <= 0, I <= 0: LBBNN_E_SHAPE; a
+ *   pointer off a 4-B boundary: LBBNN_E_ALIGN.
+ * lbbnn_sparse_pack: ONE launch for all n layers, one wave per weight row: 64 columns at a time the kept ones are compacted
+ *   in ascending order (a ballot of the lanes and the count of the lower kept lanes give each its place) and col / mean /
+ *   var are written from row_ptr[o] on, bias_var[o] once per row.  Plain vector stores, no atomics.  Nothing is written at
+ *   or past `nnz` (the capacity of col / mean / var) or past row_ptr[o + 1], whatever row_ptr holds.
+ *   NULL layers / weight_mu / weight_rho / lambdal / bias_rho / row_ptr / bias_var, or col / mean / var with nnz > 0:
+ *   LBBNN_E_NULL; the shapes above or nnz < 0: LBBNN_E_SHAPE; a pointer off a 4-B boundary: LBBNN_E_ALIGN.
+ *
+ * lbbnn_frozen_members_z: the flow launch of lbbnn_frozen_members alone -- member m's z of every MNF layer among the n
+ *   descriptors (q0_mean != NULL) into z_fwd + m * z_mstride, same Philox stream, offsets and counters, so z is bit for bit
+ *   the z of lbbnn_frozen_members.  e0, e_w_members, ld and flags are not read; nothing is scaled.  The checks of
+ *   lbbnn_frozen_members that concern the flow: NULL layers / q0_log_var / z_fwd / a transform: LBBNN_E_NULL; rng == NULL with
+ *   an MNF layer present: LBBNN_E_NOISE; n, members, O, I, z_mstride < I, z_flow.T: LBBNN_E_SHAPE; I % 4, z_mstride % 4, z_fwd
+ *   off a 16-B boundary: LBBNN_E_ALIGN.  No MNF layer: a successful no-op.
+ *
+ * lbbnn_sparse_layer_members: one layer of the sparse model for every member in ONE launch.  Activations between layers are
+ *   TRANSPOSED, [member][unit][ld] with ld >= B floats, so that the 64 lanes of a wave are 64 batch rows and every load of
+ *   a[col][.] and every store of a finished unit is one contiguous line; the first layer reads x^T as lbbnn_transpose_operand
+ *   writes it, with a_mstride = 0.  Per (member m, row b, unit o), k running over row_ptr[o] .. row_ptr[o + 1] - 1 in order:
+ *     mean = bias_mu[o] + sum_k (mean[k] * z_m[col[k]]) * a_m[col[k]][b]       (z == NULL: no z factor -- an LRT layer)
+ *     var  = bias_var[o] + sum_k var[k] * a_m[col[k]][b]^2
+ *     out  = mean + v_sqrt_f32(var) * eps,   or out = mean with LBBNN_F_MEAN_ONLY;   then ReLU (LBBNN_F_RELU) or, with
+ *     LBBNN_F_LOG_SOFTMAX (O <= 16, row-major output), log_softmax over the row.
+ *   Both sums are sequential fp32 FMAs from 0 in CSR order, the bias added last, so an output's bits depend on its member,
+ *   row and unit alone -- not on B, members, chunking or the grid.  An empty row gives relu(bias_mu + sqrt(bias_var) * eps).
+ *   eps = philox_normal4 at {rng[0], rng[1] + m * member_advance}, stream rng_stream, counter (row_offset + b, o / 4), word
+ *   o % 4: the draw of lbbnn_lrt_gemm_members at the same (row, unit).
+ *   out_rows == 0: out[m * o_mstride + o * ldo + b] (transposed, ldo >= B: the next layer's input);
+ *   out_rows != 0: out[m * o_mstride + b * ldo + o] (row-major, ldo >= O: what the heads and the metrics read).
+ *   B == 0: a successful no-op.  NULL row_ptr / bias_mu / bias_var / a / out, or col / mean / var with nnz > 0: LBBNN_E_NULL;
+ *   B < 0, more than 65535 * 64 rows, a member's input block of 2 GiB or more, I <= 0, O <= 0, nnz < 0, members outside [1, 65535], lda < B, ldo below what the layout
+ *   needs, a negative stride, z_mstride < I with more than one member: LBBNN_E_SHAPE; flags other than LBBNN_F_RELU |
+ *   LBBNN_F_MEAN_ONLY | LBBNN_F_LOG_SOFTMAX, or LBBNN_F_LOG_SOFTMAX with O > 16, with LBBNN_F_RELU or with out_rows == 0:
+ *   LBBNN_E_FLAGS; rng == NULL without LBBNN_F_MEAN_ONLY: LBBNN_E_NOISE; a pointer off a 4-B boundary (rng: 8 B):
+ *   LBBNN_E_ALIGN.  Column indices outside [0, I) and row pointers outside [0, nnz] are clamped, never followed. */
+typedef struct lbbnn_sparse_desc {
+    const float *weight_mu, *weight_rho, *lambdal;   /* (O,I)                                   */
+    const float *bias_rho;                           /* (O)                                     */
+    const int32_t* row_ptr;                          /* (O + 1); lbbnn_sparse_pack              */
+    int32_t* col;                                    /* (nnz);   lbbnn_sparse_pack              */
+    float *mean, *var;                               /* (nnz);   lbbnn_sparse_pack              */
+    float* bias_var;                                 /* (O);     lbbnn_sparse_pack              */
+    int32_t* kept_rows;                              /* (O);     lbbnn_sparse_count             */
+    int O, I;
+    int nnz;                                         /* capacity of col / mean / var            */
+    float cut;                                       /* logit(threshold)                        */
+} lbbnn_sparse_desc_t;
+
+int lbbnn_sparse_count(const lbbnn_sparse_desc_t* layers, int n, void* stream);
+int lbbnn_sparse_pack(const lbbnn_sparse_desc_t* layers, int n, void* stream);
+int lbbnn_frozen_members_z(const lbbnn_frozen_desc_t* layers, int n, int members, const uint64_t* rng,
+                           uint64_t member_advance, void* stream);
+int lbbnn_sparse_layer_members(const int32_t* row_ptr, const int32_t* col, const float* mean, const float* var, int nnz,
+                               const float* bias_mu, const float* bias_var, const float* a, int lda, int64_t a_mstride,
+                               const float* z, int64_t z_mstride, const uint64_t* rng, uint32_t rng_stream,
+                               int64_t row_offset, uint64_t member_advance, float* out, int ldo, int64_t o_mstride,
+                               int out_rows, int B, int I, int O, int flags, int members, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Frozen evaluation model of a baseline LBBNN network (LBBNN-GP-MF.py:345-502: test_ensemble and outofsample): a snapshot of
  * sigma = softplus(rho), alpha = sigmoid(lambdal) and the gated mean taken ONCE, from which every member is then drawn
  * without reading the parameters, without drawing for weights the median probability model has pruned, and -- with a map --
