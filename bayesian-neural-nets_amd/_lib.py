@@ -79,6 +79,15 @@ class GemmDesc(ctypes.Structure):
                 ("head_out", c_p), ("head_ldo", c_i), ("head_slab", c_p), ("head_flags", c_i)]
 
 
+class GemmPlan(ctypes.Structure):
+    """lbbnn_gemm_plan_t"""
+    _fields_ = [("family", c_i), ("large_tile", c_i), ("xvec", c_i), ("mean_only", c_i), ("products", c_i), ("half", c_i),
+                ("fan", c_i), ("kernel_id", c_i)]
+
+
+GEMM_FAMILIES = {-1: "none", 0: "skinny", 1: "staged", 2: "dma", 3: "split"}      # LBBNN_GEMM_*
+
+
 class DenseTransform(ctypes.Structure):
     """lbbnn_dense_transform_t"""
     _fields_ = [("kind", c_i), ("hidden", c_i), ("w_in", c_p), ("b_in", c_p),
@@ -383,6 +392,7 @@ SIGNATURES = {
     "lbbnn_format_x": (c_i, [c_p, c_i, c_p, c_i, c_i, c_i, c_p]),
     "lbbnn_lrt_gemm": (c_i, [c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_u32, c_i64,
                              c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "lbbnn_lrt_gemm_plan": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(GemmPlan)]),
     "lbbnn_lrt_gemm_train": (c_i, [c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_u32, c_i64,
                                    c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p]),
     "lbbnn_transpose_operand": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_p]),

@@ -58,7 +58,7 @@ struct GemmArgs {
     // (var_w shared), out + m*o_ms, its noise drawn at Philox offset rng[1] + m*m_adv -- an ensemble of forwards
     // (test_ensemble, LBBNN-GP-MF-MNF.py:286-294) in one launch, every member bit-identical to its own launch
     // (lbbnn_gemm_members_mean: bias_mean + m*b_ms as well -- each member its own bias; 0 = shared)
-    int single16;                // LBBNN_F_SINGLE16 (host-side dispatch only)
+    int single16;                // LBBNN_F_SINGLE16 / _HALF16 as 1 / 2 (host side; the launch goes by the plan's products / half)
     int members;
     long long x_ms, w_ms, o_ms, b_ms;
     unsigned long long m_adv, m_off;     // m_off: filled in by member_view()
@@ -87,7 +87,8 @@ template <bool MEAN_ONLY>
 __device__ __forceinline__ EpiCtx make_epi_ctx(const GemmArgs& a) {
     EpiCtx c;
     c.ovec = ((a.O & 3) == 0) && ((a.ldo & 3) == 0) && ((reinterpret_cast<uintptr_t>(a.out) & 15u) == 0) &&
-             (!a.eps || (reinterpret_cast<uintptr_t>(a.eps) & 15u) == 0);
+             (!a.eps || (reinterpret_cast<uintptr_t>(a.eps) & 15u) == 0) &&
+             (!a.std_out || (reinterpret_cast<uintptr_t>(a.std_out) & 15u) == 0);    // std_out is stored with the same flag
     c.seed = 0; c.offs = 0;
     if (!MEAN_ONLY && !a.eps) { c.seed = a.rng[0]; c.offs = a.rng[1] + a.m_off; }
     return c;
@@ -919,46 +920,118 @@ __global__ __launch_bounds__(SK_WAVES * 64) void lrt_gemm_skinny_kernel(const Ge
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Kernel selection.  ONE pure host function decides which instantiation a call takes -- family (skinny / register-staged /
+// LDS-DMA / 16-bit split), tile, x loads, mean-only, product count, fp16, fan-out -- from the call's sizes, x's layout and the
+// flags.  lrt_gemm_dispatch launches from its answer (launch_plan), and lbbnn_lrt_gemm_plan returns the same answer to the
+// host, so tests can name the instantiation a shape reaches without a GPU.
+struct PlanIn {
+    int B, I, O, ldx;
+    bool x_aligned;          // x on a 16-B boundary
+    int flags, members, fan, kchunk;
+    int ld;                  // operand row stride; 0 = not known (the host query): the two checks that need it are skipped
+    bool solo;               // the call carries eps / std_out / combine operands / a finalize: forms no member launch carries
+};
+
+// shape and flag rules, in the order the dispatcher reports them (its pointer checks come between these and plan_select)
+int plan_check(const PlanIn& p) {
+    if (p.B <= 0 || p.I <= 0 || p.O <= 0 || p.ldx < p.I) return LBBNN_E_SHAPE;
+    const int flags = p.flags;
+    if (flags & ~(LBBNN_F_RELU | LBBNN_F_MEAN_ONLY | LBBNN_F_SPLIT16 | LBBNN_F_LOG_SOFTMAX | LBBNN_F_SINGLE16 | LBBNN_F_HALF16))
+        return LBBNN_E_FLAGS;
+    if ((flags & LBBNN_F_HALF16) && (!(flags & LBBNN_F_SINGLE16) || (flags & LBBNN_F_MEAN_ONLY))) return LBBNN_E_FLAGS;
+    if ((flags & LBBNN_F_LOG_SOFTMAX) && (p.O > 16 || (flags & LBBNN_F_RELU))) return LBBNN_E_FLAGS;
+    if ((flags & LBBNN_F_SINGLE16) && !(flags & LBBNN_F_SPLIT16)) return LBBNN_E_FLAGS;
+    return 0;
+}
+
+constexpr int kPlanLarge = 1 << 2, kPlanXvec = 1 << 3, kPlanMean = 1 << 4, kPlanFan = 1 << 5, kPlanSingle = 1 << 6,
+              kPlanHalf = 1 << 7;                         // kernel_id = family | these bits
+
+int plan_select(const PlanIn& p, lbbnn_gemm_plan_t& out) {
+    const int B = p.B, I = p.I, O = p.O;
+    const bool split = (p.flags & LBBNN_F_SPLIT16) != 0;
+    const bool mean_only = (p.flags & LBBNN_F_MEAN_ONLY) != 0;
+    const bool solo = p.solo || p.kchunk;
+    if (p.kchunk && !(split && mean_only)) return LBBNN_E_FLAGS;          // (split-K exists as lbbnn_matmul_splitk only)
+    if (p.members > 1 && solo) return LBBNN_E_FLAGS;
+    if (p.fan && (p.members != 1 || mean_only || solo || (p.flags & LBBNN_F_LOG_SOFTMAX))) return LBBNN_E_FLAGS;
+
+    const bool xvec = ((I & 3) == 0) && ((p.ldx & 3) == 0) && p.x_aligned;
+    lbbnn_gemm_plan_t pl{};
+    pl.mean_only = mean_only; pl.fan = p.fan > 0; pl.products = 1;
+    // Tile choice: 80(o) x 128(b) fills the chip for the headline shapes (B=4096, O=1200 -> 15x32 = 480
+    // workgroups, 2 resident per CU); small problems take a 80x32 tile for more workgroups; a skinny
+    // output (O <= 16, the 10-class head) takes the split-K kernel above.
+    if (split) {
+        // split-precision operands: aligned x, I % 8 == 0, >= 16 B of zero tail when there is a K tail, O > 16
+        const bool tail = (I % BKS) != 0;
+        if (!xvec || (I & 7) || O <= 16 || (p.ld && tail && (p.ld - I) < 8)) return LBBNN_E_ALIGN;
+        // the split kernel addresses x and the operands through 32-bit buffer offsets
+        if (((size_t)(B - 1) * p.ldx + I) * 4 >= 0x7FFFFFF0u || (p.ld && (size_t)O * p.ld * 4 >= 0x7FFFFFF0u)) return LBBNN_E_SHAPE;
+        // 128x80 tile, 2 workgroups/CU, 2 LDS stages.  Variants measured and dropped: 256x80 3-stage ring
+        // (one workgroup/CU), 128x160 with 4 or 8 waves, x split once per tile through LDS, x delivered pre-split.
+        const long nz = p.kchunk ? (I + p.kchunk - 1) / p.kchunk : 1;
+        const long blocks_big = (long)((O + 79) / 80) * ((B + 127) / 128) * nz;
+        pl.family = LBBNN_GEMM_SPLIT; pl.xvec = 1;
+        pl.large_tile = blocks_big >= 256 && B >= 96;
+        if ((p.flags & LBBNN_F_SINGLE16) && !mean_only) { pl.products = 1; pl.half = (p.flags & LBBNN_F_HALF16) != 0; }
+        else pl.products = 3;
+    } else if (O <= 16) {
+        pl.family = LBBNN_GEMM_SKINNY; pl.xvec = xvec;
+    } else {
+        static const bool no_dma = getenv("LBBNN_GEMM_NO_DMA") != nullptr;     // A/B knob for bench sweeps
+        const long blocks_big = (long)((O + 79) / 80) * ((B + 127) / 128);
+        pl.large_tile = blocks_big >= 256;
+        const bool dma = xvec && (I % BK) == 0 && !no_dma;
+        pl.family = dma ? LBBNN_GEMM_DMA : LBBNN_GEMM_STAGED; pl.xvec = xvec;
+    }
+    pl.kernel_id = pl.family | (pl.large_tile ? kPlanLarge : 0) | (pl.xvec ? kPlanXvec : 0) | (pl.mean_only ? kPlanMean : 0) |
+                   (pl.fan ? kPlanFan : 0) | ((pl.family == LBBNN_GEMM_SPLIT && pl.products == 1) ? kPlanSingle : 0) |
+                   (pl.half ? kPlanHalf : 0);
+    out = pl;
+    return 0;
+}
+
 // *hosted (if non-NULL, and a.fin.n > 0): set to true when the launch carries the finalize row; otherwise the caller
 // runs the finalize as a launch of its own
-// FAN: the fan-out kernels (GemmArgs::fan; never mean-only, no finalize): same tile, same grid, same kernel choice
-template <int TO, int TB, int WB, bool FAN = false>
-int launch_cfg(GemmArgs& a, bool mean_only, bool xvec, hipStream_t s, bool* hosted) {
+// p.fan: the fan-out kernels (GemmArgs::fan; never mean-only, no finalize): same tile, same grid, same kernel choice
+template <int TO, int TB, int WB>
+int launch_f32(GemmArgs& a, const lbbnn_gemm_plan_t& p, hipStream_t s, bool* hosted) {
     constexpr int BN = TO * 16, BM = TB * WB * 16;
     dim3 grid((a.O + BN - 1) / BN, (a.B + BM - 1) / BM, a.members > 1 ? a.members : 1);
     dim3 block(WB * 64);
     const long nblocks = (long)grid.x * grid.y * grid.z;
-    static const bool no_dma = getenv("LBBNN_GEMM_NO_DMA") != nullptr;     // A/B knob for bench sweeps
     const int fin_n = a.fin.n;
     a.fin.n = 0;
-    if (xvec && (a.I % BK) == 0 && !no_dma) {
+    if (p.family == LBBNN_GEMM_DMA) {
         const size_t l_full = lds_request(2u * (BM + 2 * BN) * DROW * sizeof(float), nblocks);
         const size_t l_mean = lds_request(2u * (BM + BN) * DROW * sizeof(float), nblocks);
         if (fin_n > 0 && hosted) {
             a.fin.n = fin_n;
-            if (piggy_lds_bytes(a.fin) <= (mean_only ? l_mean : l_full)) { grid.y += 1; *hosted = true; }
+            if (piggy_lds_bytes(a.fin) <= (p.mean_only ? l_mean : l_full)) { grid.y += 1; *hosted = true; }
             else a.fin.n = 0;
         }
-        if constexpr (FAN) return launch_one(lrt_gemm_f32_dma_kernel<TO, TB, WB, false, true>, grid, block, l_full, s, a);
-        if (mean_only) return launch_one(lrt_gemm_f32_dma_kernel<TO, TB, WB, true>, grid, block, l_mean, s, a);
+        if (p.fan) return launch_one(lrt_gemm_f32_dma_kernel<TO, TB, WB, false, true>, grid, block, l_full, s, a);
+        if (p.mean_only) return launch_one(lrt_gemm_f32_dma_kernel<TO, TB, WB, true>, grid, block, l_mean, s, a);
         return launch_one(lrt_gemm_f32_dma_kernel<TO, TB, WB, false>, grid, block, l_full, s, a);
     }
     const size_t lds_full = lds_request(2u * (BM + 2 * BN) * LDS_LD * sizeof(float), nblocks);
     const size_t lds_mean = lds_request(2u * (BM + BN) * LDS_LD * sizeof(float), nblocks);
-    if constexpr (FAN) {
-        if (xvec) return launch_one(lrt_gemm_f32_kernel<TO, TB, WB, false, true, true>, grid, block, lds_full, s, a);
+    if (p.fan) {
+        if (p.xvec) return launch_one(lrt_gemm_f32_kernel<TO, TB, WB, false, true, true>, grid, block, lds_full, s, a);
         return launch_one(lrt_gemm_f32_kernel<TO, TB, WB, false, false, true>, grid, block, lds_full, s, a);
     }
-    if (mean_only) {
-        if (xvec) return launch_one(lrt_gemm_f32_kernel<TO, TB, WB, true, true>, grid, block, lds_mean, s, a);
+    if (p.mean_only) {
+        if (p.xvec) return launch_one(lrt_gemm_f32_kernel<TO, TB, WB, true, true>, grid, block, lds_mean, s, a);
         return launch_one(lrt_gemm_f32_kernel<TO, TB, WB, true, false>, grid, block, lds_mean, s, a);
     }
-    if (xvec) return launch_one(lrt_gemm_f32_kernel<TO, TB, WB, false, true>, grid, block, lds_full, s, a);
+    if (p.xvec) return launch_one(lrt_gemm_f32_kernel<TO, TB, WB, false, true>, grid, block, lds_full, s, a);
     return launch_one(lrt_gemm_f32_kernel<TO, TB, WB, false, false>, grid, block, lds_full, s, a);
 }
 
-template <int TO, int TB, int WB, bool FAN = false>
-int launch_split_cfg(GemmArgs& a, bool mean_only, hipStream_t s, bool* hosted) {
+template <int TO, int TB, int WB>
+int launch_split(GemmArgs& a, const lbbnn_gemm_plan_t& p, hipStream_t s, bool* hosted) {
     constexpr int BN = TO * 16, BM = TB * WB * 16;
     dim3 grid((a.O + BN - 1) / BN, (a.B + BM - 1) / BM,
               a.kchunk ? (a.I + a.kchunk - 1) / a.kchunk : (a.members > 1 ? a.members : 1));
@@ -970,28 +1043,45 @@ int launch_split_cfg(GemmArgs& a, bool mean_only, hipStream_t s, bool* hosted) {
     a.fin.n = 0;
     if (fin_n > 0 && hosted && !a.kchunk) {
         a.fin.n = fin_n;
-        if (piggy_lds_bytes(a.fin) <= (mean_only ? l_mean : l_full)) { grid.y += 1; *hosted = true; }
+        if (piggy_lds_bytes(a.fin) <= (p.mean_only ? l_mean : l_full)) { grid.y += 1; *hosted = true; }
         else a.fin.n = 0;
     }
-    if constexpr (FAN) {
-        if (a.single16 == 2) return launch_one(lrt_gemm_bf16x3_kernel<TO, TB, WB, false, 1, true, true>, grid, block, l_full, s, a);
-        if (a.single16) return launch_one(lrt_gemm_bf16x3_kernel<TO, TB, WB, false, 1, false, true>, grid, block, l_full, s, a);
+    if (p.fan) {
+        if (p.half) return launch_one(lrt_gemm_bf16x3_kernel<TO, TB, WB, false, 1, true, true>, grid, block, l_full, s, a);
+        if (p.products == 1) return launch_one(lrt_gemm_bf16x3_kernel<TO, TB, WB, false, 1, false, true>, grid, block, l_full, s, a);
         return launch_one(lrt_gemm_bf16x3_kernel<TO, TB, WB, false, 3, false, true>, grid, block, l_full, s, a);
     }
-    if (a.single16 == 2 && !mean_only) return launch_one(lrt_gemm_bf16x3_kernel<TO, TB, WB, false, 1, true>, grid, block, l_full, s, a);
-    if (a.single16 && !mean_only) return launch_one(lrt_gemm_bf16x3_kernel<TO, TB, WB, false, 1>, grid, block, l_full, s, a);
-    if (mean_only) return launch_one(lrt_gemm_bf16x3_kernel<TO, TB, WB, true>, grid, block, l_mean, s, a);
+    if (p.half) return launch_one(lrt_gemm_bf16x3_kernel<TO, TB, WB, false, 1, true>, grid, block, l_full, s, a);
+    if (p.products == 1) return launch_one(lrt_gemm_bf16x3_kernel<TO, TB, WB, false, 1>, grid, block, l_full, s, a);
+    if (p.mean_only) return launch_one(lrt_gemm_bf16x3_kernel<TO, TB, WB, true>, grid, block, l_mean, s, a);
     return launch_one(lrt_gemm_bf16x3_kernel<TO, TB, WB, false>, grid, block, l_full, s, a);
 }
 
-template <bool FAN = false>
-int launch_split(GemmArgs& a, bool mean_only, hipStream_t s, bool* hosted) {
-    // 128x80 tile, 2 workgroups/CU, 2 LDS stages.  Variants measured and dropped: 256x80 3-stage ring
-    // (one workgroup/CU), 128x160 with 4 or 8 waves, x split once per tile through LDS, x delivered pre-split.
-    const long nz = a.kchunk ? (a.I + a.kchunk - 1) / a.kchunk : 1;
-    const long blocks_big = (long)((a.O + 79) / 80) * ((a.B + 127) / 128) * nz;
-    if (blocks_big >= 256 && a.B >= 96) return launch_split_cfg<5, 2, 4, FAN>(a, mean_only, s, hosted);
-    return launch_split_cfg<5, 1, 2, FAN>(a, mean_only, s, hosted);
+int launch_skinny(GemmArgs& a, const lbbnn_gemm_plan_t& p, hipStream_t s) {
+    a.fin.n = 0;
+    dim3 grid((a.B + 15) / 16, 1, a.members > 1 ? a.members : 1), block(SK_WAVES * 64);
+    if (p.fan) {
+        if (p.xvec) hipLaunchKernelGGL((lrt_gemm_skinny_kernel<false, true, true>), grid, block, 0, s, a);
+        else        hipLaunchKernelGGL((lrt_gemm_skinny_kernel<false, false, true>), grid, block, 0, s, a);
+    } else if (p.mean_only) {
+        if (p.xvec) hipLaunchKernelGGL((lrt_gemm_skinny_kernel<true, true>), grid, block, 0, s, a);
+        else        hipLaunchKernelGGL((lrt_gemm_skinny_kernel<true, false>), grid, block, 0, s, a);
+    } else {
+        if (p.xvec) hipLaunchKernelGGL((lrt_gemm_skinny_kernel<false, true>), grid, block, 0, s, a);
+        else        hipLaunchKernelGGL((lrt_gemm_skinny_kernel<false, false>), grid, block, 0, s, a);
+    }
+    return (int)hipGetLastError();
+}
+
+// the one place a plan becomes a launch
+int launch_plan(GemmArgs& a, const lbbnn_gemm_plan_t& p, hipStream_t s, bool* hosted) {
+    switch (p.family) {
+        case LBBNN_GEMM_SKINNY: return launch_skinny(a, p, s);
+        case LBBNN_GEMM_SPLIT:
+            return p.large_tile ? launch_split<5, 2, 4>(a, p, s, hosted) : launch_split<5, 1, 2>(a, p, s, hosted);
+        default:
+            return p.large_tile ? launch_f32<5, 2, 4>(a, p, s, hosted) : launch_f32<5, 1, 2>(a, p, s, hosted);
+    }
 }
 
 }  // namespace
@@ -1008,16 +1098,13 @@ static GemmArgs gemm_args(const float* x, int ldx, const void* e_w, const void* 
 }
 
 static int lrt_gemm_dispatch(GemmArgs& a, int flags, void* stream, bool* hosted = nullptr) {
-    const int B = a.B, I = a.I, O = a.O, ldx = a.ldx, ld = a.ld, ldo = a.ldo, fan = a.fan;
+    const int B = a.B, I = a.I, O = a.O, ld = a.ld;
     if (B == 0 && I > 0 && O > 0) return 0;        // empty batch (torch.mm of 0 rows, LBBNN-GP-MF-LRT.py:172): nothing to do
     if (!a.x || !a.e_w || !a.out) return LBBNN_E_NULL;
-    if (B <= 0 || I <= 0 || O <= 0 || ldx < I || ldo < O) return LBBNN_E_SHAPE;
-    if (flags & ~(LBBNN_F_RELU | LBBNN_F_MEAN_ONLY | LBBNN_F_SPLIT16 | LBBNN_F_LOG_SOFTMAX | LBBNN_F_SINGLE16 | LBBNN_F_HALF16))
-        return LBBNN_E_FLAGS;
-    if ((flags & LBBNN_F_HALF16) && (!(flags & LBBNN_F_SINGLE16) || (flags & LBBNN_F_MEAN_ONLY))) return LBBNN_E_FLAGS;
-    if ((flags & LBBNN_F_LOG_SOFTMAX) && (O > 16 || (flags & LBBNN_F_RELU))) return LBBNN_E_FLAGS;
-    if ((flags & LBBNN_F_SINGLE16) && !(flags & LBBNN_F_SPLIT16)) return LBBNN_E_FLAGS;
-    const bool split = (flags & LBBNN_F_SPLIT16) != 0;
+    if (a.ldo < O) return LBBNN_E_SHAPE;
+    PlanIn pin{B, I, O, a.ldx, (reinterpret_cast<uintptr_t>(a.x) & 15u) == 0, flags, a.members, a.fan, a.kchunk, ld,
+               a.fin.n > 0 || a.eps || a.std_out || a.comb_x};
+    if (const int rc = plan_check(pin)) return rc;
     const bool mean_only = (flags & LBBNN_F_MEAN_ONLY) != 0;
     if (!mean_only && !a.var_w) return LBBNN_E_NULL;
     if (!mean_only && !a.eps && !a.rng) return LBBNN_E_NOISE;
@@ -1026,46 +1113,23 @@ static int lrt_gemm_dispatch(GemmArgs& a, int flags, void* stream, bool* hosted 
 
     a.relu = (flags & LBBNN_F_RELU) ? 1 : 0; a.log_softmax = (flags & LBBNN_F_LOG_SOFTMAX) ? 1 : 0;
     a.single16 = (flags & LBBNN_F_HALF16) ? 2 : ((flags & LBBNN_F_SINGLE16) ? 1 : 0);
-    a.split_stride = (long long)B * ldo; a.m_off = 0;
-    const bool solo = a.kchunk || a.fin.n > 0 || a.eps || a.std_out || a.comb_x;      // forms that no member launch carries
-    if (a.members > 1 && solo) return LBBNN_E_FLAGS;
-    if (fan && (a.members != 1 || mean_only || solo || a.log_softmax)) return LBBNN_E_FLAGS;
+    a.split_stride = (long long)B * a.ldo; a.m_off = 0;
+    lbbnn_gemm_plan_t plan;
+    if (const int rc = plan_select(pin, plan)) return rc;
+    return launch_plan(a, plan, static_cast<hipStream_t>(stream), hosted);
+}
 
-    const bool xvec = ((I & 3) == 0) && ((ldx & 3) == 0) && ((reinterpret_cast<uintptr_t>(a.x) & 15u) == 0);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // Tile choice: 80(o) x 128(b) fills the chip for the headline shapes (B=4096, O=1200 -> 15x32 = 480
-    // workgroups, 2 resident per CU); small problems take a 80x32 tile for more workgroups; a skinny
-    // output (O <= 16, the 10-class head) takes the split-K kernel above.
-    if (split) {
-        // split-precision operands: aligned x, I % 8 == 0, >= 16 B of zero tail when there is a K tail, O > 16
-        const bool tail = (I % BKS) != 0;
-        if (!xvec || (I & 7) || O <= 16 || (tail && (ld - I) < 8)) return LBBNN_E_ALIGN;
-        // the split kernel addresses x and the operands through 32-bit buffer offsets
-        if (((size_t)(B - 1) * ldx + I) * 4 >= 0x7FFFFFF0u || (size_t)O * ld * 4 >= 0x7FFFFFF0u) return LBBNN_E_SHAPE;
-        return fan ? launch_split<true>(a, mean_only, s, hosted) : launch_split(a, mean_only, s, hosted);
-    }
-    if (O <= 16) {
-        a.fin.n = 0;
-        dim3 grid((B + 15) / 16, 1, a.members > 1 ? a.members : 1), block(SK_WAVES * 64);
-        if (fan) {
-            if (xvec) hipLaunchKernelGGL((lrt_gemm_skinny_kernel<false, true, true>), grid, block, 0, s, a);
-            else      hipLaunchKernelGGL((lrt_gemm_skinny_kernel<false, false, true>), grid, block, 0, s, a);
-        } else if (mean_only) {
-            if (xvec) hipLaunchKernelGGL((lrt_gemm_skinny_kernel<true, true>), grid, block, 0, s, a);
-            else      hipLaunchKernelGGL((lrt_gemm_skinny_kernel<true, false>), grid, block, 0, s, a);
-        } else {
-            if (xvec) hipLaunchKernelGGL((lrt_gemm_skinny_kernel<false, true>), grid, block, 0, s, a);
-            else      hipLaunchKernelGGL((lrt_gemm_skinny_kernel<false, false>), grid, block, 0, s, a);
-        }
-        return (int)hipGetLastError();
-    }
-    const long blocks_big = (long)((O + 79) / 80) * ((B + 127) / 128);
-    if (fan) {
-        if (blocks_big >= 256) return launch_cfg<5, 2, 4, true>(a, mean_only, xvec, s, hosted);
-        return launch_cfg<5, 1, 2, true>(a, mean_only, xvec, s, hosted);
-    }
-    if (blocks_big >= 256) return launch_cfg<5, 2, 4>(a, mean_only, xvec, s, hosted);
-    return launch_cfg<5, 1, 2>(a, mean_only, xvec, s, hosted);
+extern "C" int lbbnn_lrt_gemm_plan(int B, int I, int O, int ldx, int x_aligned, int flags, int members, int fan, int kchunk,
+                                   lbbnn_gemm_plan_t* plan) {
+    if (!plan) return LBBNN_E_NULL;
+    *plan = lbbnn_gemm_plan_t{};
+    plan->family = LBBNN_GEMM_NONE; plan->kernel_id = -1;
+    if (members < 1 || members > 65535 || fan < 0 || fan > 65535) return LBBNN_E_SHAPE;    // (the member entry points' range)
+    if (kchunk < 0 || (kchunk & 31)) return LBBNN_E_ALIGN;                                 // (lbbnn_matmul_splitk's rule)
+    if (B == 0 && I > 0 && O > 0) return 0;                                                // nothing is launched
+    const PlanIn pin{B, I, O, ldx, x_aligned != 0, flags, members, fan, kchunk, 0, false};
+    if (const int rc = plan_check(pin)) return rc;
+    return plan_select(pin, *plan);
 }
 
 extern "C" int lbbnn_lrt_gemm(const float* x, int ldx, const void* e_w, const void* var_w, int ld,

@@ -5,7 +5,7 @@ enqueues on torch's current stream and returns without synchronising.  Nothing h
 on the host; a CPU tensor or a missing library raises.
 """
 import ctypes
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 
@@ -474,6 +474,40 @@ def lrt_gemm(x, e_w, var_w, *, I: int, O: int, bias_mean=None, bias_var=None, va
         ev[1].record()
         GEMM_EVENTS.append((B, I, O, ev[0], ev[1]))
     return out
+
+
+class GemmPlan(NamedTuple):
+    """lbbnn_gemm_plan_t: the kernel instantiation a dual-moment GEMM call takes."""
+    family: str              # "skinny" | "staged" | "dma" | "split" ("none": B == 0, nothing is launched)
+    large_tile: bool
+    xvec: bool
+    mean_only: bool
+    products: int
+    half: bool
+    fan: bool
+    kernel_id: int
+
+
+def lrt_gemm_plan_code(B: int, I: int, O: int, *, ldx: Optional[int] = None, x_aligned: bool = True, flags: int = 0,
+                       members: int = 1, fan: int = 0, kchunk: int = 0):
+    """lbbnn_lrt_gemm_plan as (return code, GemmPlan or None): a rejected input gives the launch's LBBNN_E_* code."""
+    p = _lib.GemmPlan()
+    rc = _lib.lib().lbbnn_lrt_gemm_plan(B, I, O, I if ldx is None else ldx, 1 if x_aligned else 0, flags, members, fan, kchunk,
+                                        ctypes.byref(p))
+    if rc != 0:
+        return rc, None
+    return 0, GemmPlan(_lib.GEMM_FAMILIES[p.family], bool(p.large_tile), bool(p.xvec), bool(p.mean_only), p.products,
+                       bool(p.half), bool(p.fan), p.kernel_id)
+
+
+def lrt_gemm_plan(B: int, I: int, O: int, **kw) -> GemmPlan:
+    """The kernel ``lrt_gemm`` / ``vd_gemm_members`` / ``lrt_gemm_combine`` / ``matmul_splitk`` launch for these sizes, x layout
+    (row stride ``ldx``, default I; ``x_aligned``: base on a 16-B boundary) and ``flags`` (the F_* bits), ``members`` > 1 for
+    the member forms, ``fan`` > 0 for the fan-out, ``kchunk`` for split-K.  A host-side query: no tensor, no GPU.  Rejected
+    inputs raise as the launch would."""
+    rc, plan = lrt_gemm_plan_code(B, I, O, **kw)
+    _lib.check(rc, "lbbnn_lrt_gemm_plan")
+    return plan
 
 
 def vd_gemm_members(x, e_w, var_w, var_scale, rng: torch.Tensor, *, I: int, O: int, members: int, fanout: bool = False,

@@ -124,6 +124,34 @@ int lbbnn_lrt_gemm(const float* x, int ldx, const void* e_w, const void* var_w, 
                    const float* eps, const uint64_t* rng, uint32_t rng_stream, int64_t row_offset,
                    float* out, int ldo, int B, int I, int O, int flags, void* stream);
 
+/* lbbnn_lrt_gemm_plan -- which kernel instantiation lbbnn_lrt_gemm and its member / fan-out / combine / split-K forms launch
+ * for a call, answered on the host: no pointer is taken, no GPU is touched.  It is the selection function the dispatcher
+ * itself launches from, so the answer cannot drift from what runs.
+ *   family      LBBNN_GEMM_SKINNY (O <= 16) | LBBNN_GEMM_STAGED (fp32, register-staged) | LBBNN_GEMM_DMA (fp32, LDS-DMA)
+ *               | LBBNN_GEMM_SPLIT (16-bit operands, LBBNN_F_SPLIT16); LBBNN_GEMM_NONE for B == 0 (nothing is launched)
+ *   large_tile  1: the 80 x 128 tile (four waves), 0: 80 x 32 (two waves); 0 for the skinny kernel
+ *   xvec        x rows are read as 16-B vectors (always 1 for the DMA and split families)
+ *   mean_only   the mean product alone, no noise
+ *   products    matrix products per moment: 3 or 1 for the split family (LBBNN_F_SINGLE16 on a dual launch), else 1
+ *   half        the single product in fp16 (LBBNN_F_HALF16)
+ *   fan         the fan-out form of lbbnn_vd_gemm_members (one tile product, every member's epilogue)
+ *   kernel_id   one integer per instantiation: equal ids, same kernel
+ * Inputs: the call's B, I, O, ldx; x_aligned: x sits on a 16-B boundary; flags as for lbbnn_lrt_gemm; members (>= 1, > 1: the
+ * member forms); fan (> 0: fan-out over that many members); kchunk (> 0: lbbnn_matmul_splitk's chunk).  Returns 0, or the
+ * code the launch would return for these inputs (LBBNN_E_SHAPE / _FLAGS / _ALIGN); checks that need a pointer or the operand
+ * stride ld stay with the launch.  Whether the KL finalize rides in the launch depends on LDS and is not part of the plan.
+ * The environment knob LBBNN_GEMM_NO_DMA (read once) turns the DMA family into the staged one here as in the launch. */
+#define LBBNN_GEMM_NONE (-1)
+#define LBBNN_GEMM_SKINNY 0
+#define LBBNN_GEMM_STAGED 1
+#define LBBNN_GEMM_DMA 2
+#define LBBNN_GEMM_SPLIT 3
+typedef struct lbbnn_gemm_plan {
+    int family, large_tile, xvec, mean_only, products, half, fan, kernel_id;
+} lbbnn_gemm_plan_t;
+int lbbnn_lrt_gemm_plan(int B, int I, int O, int ldx, int x_aligned, int flags, int members, int fan, int kchunk,
+                        lbbnn_gemm_plan_t* plan);
+
 /* ---------------------------------------------------------------------------------------------
  * K3  lbbnn_mnf_flow_planar -- z sampling + planar flows of one MNF layer, one launch.
  *

@@ -7,6 +7,7 @@ import torch
 
 import philox_ref
 from conftest import rel_err
+from gemm_variant_cases import FAMILIES
 from oracle import lbbnn_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -136,21 +137,8 @@ def test_against_fp64_oracle(bnn, dev, prec, p, dims, B, S):
     assert int(st.t[1]) == live + L * S
 
 
-# kernel families of the dispatch (lrt_gemm_dispatch): (B, I, O, flags-name, relu)
-FAMILIES = [
-    ("fp32 register-staged", 33, 50, 37, "fp32", True),           # x rows not float4-aligned
-    ("fp32 register-staged, I % 16 != 0", 70, 36, 120, "fp32", False),
-    ("fp32 LDS-DMA", 100, 784, 120, "fp32", True),
-    ("fp32 LDS-DMA, large tile", 2048, 64, 1280, "fp32", False),
-    ("bf16x3", 100, 256, 200, "bf16x3", True),
-    ("bf16x3, K tail", 45, 200, 120, "bf16x3", False),
-    ("bf16x3, large tile", 2048, 64, 1280, "bf16x3", True),
-    ("bf16 single", 100, 256, 200, "bf16", True),
-    ("fp16 single", 100, 256, 200, "fp16", False),
-    ("fp16 single, large tile", 2048, 64, 1280, "fp16", True),
-    ("skinny O <= 16", 40, 64, 8, "fp32", False),
-    ("skinny O <= 16, unaligned rows", 33, 50, 3, "fp32", True),
-]
+# kernel families of the dispatch (lrt_gemm_dispatch): (name, B, I, O, flags-name, relu), one or more rows per fan-out
+# instantiation; the table and the host-side check that it is complete live in tests/gemm_variant_cases.py
 
 
 @pytest.mark.parametrize("name,B,I,O,mode,relu", FAMILIES, ids=[f[0] for f in FAMILIES])
