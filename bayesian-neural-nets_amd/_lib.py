@@ -230,6 +230,27 @@ class SparseDesc(ctypes.Structure):
                                    "kept_rows")] + [("O", c_i), ("I", c_i), ("nnz", c_i), ("cut", ctypes.c_float)]
 
 
+class SparseDrawDesc(ctypes.Structure):
+    """lbbnn_sparse_draw_desc_t"""
+    _fields_ = [(n, c_p) for n in ("col", "mean", "var", "bias_mu", "bias_var", "z")] + [("z_mstride", c_i64), ("tpos", c_p), ("wt", c_p), ("w", c_p),
+               ("w_mstride", c_i64), ("b", c_p), ("b_mstride", c_i64), ("O", c_i), ("I", c_i), ("nnz", c_i), ("layer_id", c_u32)]
+
+
+class SparseGatherArgs(ctypes.Structure):
+    """lbbnn_sparse_gather_args_t"""
+    _fields_ = [("ptr", c_p), ("idx", c_p), ("slot", c_p), ("w", c_p), ("w_mstride", c_i64), ("bias", c_p), ("b_mstride", c_i64),
+                ("a", c_p), ("a_mstride", c_i64), ("h", c_p), ("h_mstride", c_i64), ("out", c_p), ("o_mstride", c_i64)] + \
+               [(n, c_i) for n in ("lda", "ldh", "ldo", "B", "K", "N", "nnz", "mode", "relu", "out_rows", "a_shared", "blocks",
+                                   "per_member")] + [("dot_bias", c_p), ("dot_b_mstride", c_i64), ("dot_acc", c_p)]
+
+
+class MemberStatsArgs(ctypes.Structure):
+    """lbbnn_member_stats_args_t"""
+    _fields_ = [("t", c_p), ("t_mstride", c_i64)] + [(n, c_i) for n in ("ldt", "S", "C", "F", "B")] + \
+               [(n, c_p) for n in ("mean", "std", "prob_pos", "prob_neg", "members", "logits")] + \
+               [("ldl", c_i), ("n_logits", c_i), ("targets", c_p), ("intercept", c_p), ("residual", c_p)]
+
+
 class BaseFrozenDesc(ctypes.Structure):
     """lbbnn_base_frozen_desc_t"""
     _fields_ = [(n, c_p) for n in ("mu", "rho", "lambdal", "bias_mu", "bias_rho", "w_mu", "w_sigma", "alpha", "e_w", "b_mu",
@@ -365,6 +386,8 @@ class StructureDesc(ctypes.Structure):
 
 
 EXPLAIN_SEED, EXPLAIN_MASK, EXPLAIN_FINISH = 0, 1, 2    # LBBNN_EXPLAIN_*: the modes of lbbnn_explain_step
+GATHER_FORWARD, GATHER_SWEEP, GATHER_FINISH = 0, 1, 2   # LBBNN_GATHER_*: the post-ops of lbbnn_sparse_gather_members
+MEMBER_BLOCKS_MAX = 65535              # members x explained outputs of one explain_ensemble call (gridDim.z)
 EXPLAIN_MAX_OUTPUTS = 16               # LBBNN_EXPLAIN_MAX_OUTPUTS: rows of G per input row
 EXPLAIN_MAX_ROWS = 1 << 24             # LBBNN_EXPLAIN_MAX_ROWS: B * C'
 
@@ -524,6 +547,10 @@ SIGNATURES = {
     "lbbnn_explain_work_bytes": (c_i64, [c_i, c_i, c_i]),
     "lbbnn_explain_totals": (c_i, [c_p, c_i64, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "lbbnn_explain_operand": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),
+    "lbbnn_sparse_draw_members": (c_i, [ctypes.POINTER(SparseDrawDesc), c_i, c_i, c_p, c_i, c_p]),
+    "lbbnn_sparse_gather_members": (c_i, [ctypes.POINTER(SparseGatherArgs), c_p]),
+    "lbbnn_explain_seed": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i64, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_u64, c_p]),
+    "lbbnn_explain_member_stats": (c_i, [ctypes.POINTER(MemberStatsArgs), c_p]),
 }
 
 _lib = None

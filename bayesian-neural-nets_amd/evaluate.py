@@ -45,6 +45,8 @@ needed units, and how often each input feature and hidden unit lies on an active
 posterior-mean forward is a ReLU chain on fixed operands, so per row the pre-head output is exactly linear in the input, and the
 call returns every input's contribution ``J[b, c, i] * x[b, i]``, the bias path and a residual that ties them to the logits;
 ``ExplanationAccumulator`` / ``explain_batches`` (lbbnn_explain_totals) average them over a pass on the device.
+``explain_ensemble`` (lbbnn_sparse_draw_members / _gather_members, lbbnn_explain_seed / _member_stats) explains sampled-weight
+members of the sparse median probability model and returns the mean, spread and sign probability of every contribution over them.
 """
 import math
 from typing import Dict, List, Optional, Tuple
@@ -2255,7 +2257,8 @@ class SparseFrozenNetwork(FrozenNetwork):
     ``freeze(net, "mpm")`` (lbbnn_frozen_members_z) -- the draws of the dense median model bit for bit, so a member equals
     that model's member to fp32 rounding (the sums run over the kept weights in column order, sequentially).  The bits of an
     output depend on its member, row and unit alone.  No ``refresh()`` and no ``evaluate.explain``: freeze again, or use
-    ``freeze(net, "mpm")``."""
+    ``freeze(net, "mpm")``.  ``evaluate.explain_ensemble`` explains this model's sampled-weight members; its first call adds the
+    buffers ``col_ptr_<i>`` (I + 1), ``trow_<i>``, ``tslot_<i>``, ``tpos_<i>`` (nnz): the pattern column by column."""
 
     def __init__(self, dims, family: str = "lrt", threshold: float = 0.5, device=None, head: str = "log_softmax"):
         _FrozenModel.__init__(self, dims, "mpm", threshold, device, head)
@@ -2350,6 +2353,16 @@ class SparseFrozenNetwork(FrozenNetwork):
             self._zbuf = _empty((c, sum(ops.operand_ld(d) for d in self.dims[:-1])), dtype=torch.float32, device=self._device())
             self._mcap = c
         return self._zbuf, []
+
+    def _take_z(self, c: int):
+        """The z of the c members just drawn, [c][sum of ld], for a caller that hands it on with its result: the buffer itself
+        where it holds exactly those members (the model lets go of it; the next draw allocates anew), a copy where the model
+        holds a larger one (which it keeps)."""
+        zbuf = self._zbuf
+        if zbuf.shape[0] > c:
+            return zbuf[:c].clone()
+        self._zbuf, self._mcap = None, 0
+        return zbuf
 
     def _draw_members(self, c: int, rng, stream, masks=None):
         """MNF: member m's z at Philox offset rng[1] + m -- the flow launch of the dense model alone (lbbnn_frozen_members_z)."""
@@ -3074,3 +3087,244 @@ def explain_batches(fz, batches, acc: Optional[ExplanationAccumulator] = None, t
         x = batch[0] if isinstance(batch, (tuple, list)) else batch
         explain(fz, x, targets=None if targets == "all" else "pred", acc=acc)
     return acc
+
+
+# ----------------------------------------------------------------------------------------- explanations of sampled-weight members
+def _check_ensemble_explainable(fz):
+    """``explain_ensemble`` takes a SparseFrozenNetwork; everything else is refused with what to use instead."""
+    from . import layers as L
+    if isinstance(fz, SparseFrozenNetwork):
+        return
+    if isinstance(fz, FrozenNetwork):
+        raise TypeError("bnn_amd: explain_ensemble explains sampled-weight members of the sparse median probability model (it "
+                        "keeps every member's weights, which only the kept weights of a sparse model make small); build it with "
+                        "evaluate.freeze(net, \"mpm\", sparse=True).  For a point explanation of this dense model: "
+                        "evaluate.explain(fz, data)")
+    if isinstance(fz, FrozenBaseNetwork) or _is_base(fz) or _is_vd(fz):
+        raise TypeError("bnn_amd: explain_ensemble is built for LRT and planar MNF networks: "
+                        "evaluate.explain_ensemble(evaluate.freeze(net, \"mpm\", sparse=True), data) of an lrt / mnf "
+                        "BayesianNetwork, got %s" % type(fz).__name__)
+    if isinstance(fz, L._NetworkBase):
+        raise TypeError("bnn_amd: explain_ensemble takes a sparse frozen model, not the network itself: "
+                        "evaluate.explain_ensemble(evaluate.freeze(net, \"mpm\", sparse=True), data)")
+    raise TypeError("bnn_amd: explain_ensemble takes a SparseFrozenNetwork (evaluate.freeze(net, \"mpm\", sparse=True)), got %s"
+                    % type(fz).__name__)
+
+
+def _transposed_pattern(fz, i: int):
+    """(col_ptr, trow, tslot, tpos) of layer i of a sparse model, built at the first use and kept as buffers ``col_ptr_<i>``
+    (I + 1), ``trow_<i>``, ``tslot_<i>`` (nnz): ops.sparse_transposed_pattern, and ``tpos_<i>`` (nnz), the inverse of tslot (the
+    place of CSR slot k in the column-by-column order); no host read."""
+    if not hasattr(fz, "col_ptr_%d" % i):
+        row_ptr, col, _, _ = fz.csr(i)
+        pat = ops.sparse_transposed_pattern(row_ptr, col, fz.dims[i])
+        tpos = torch.empty_like(pat[2])
+        tpos[pat[2].long()] = torch.arange(pat[2].numel(), dtype=torch.int32, device=tpos.device)
+        for name, t in zip(("col_ptr", "trow", "tslot", "tpos"), pat + (tpos,)):
+            fz.register_buffer("%s_%d" % (name, i), t)
+    return tuple(fz._buf(k, i) for k in ("col_ptr", "trow", "tslot", "tpos"))
+
+
+def explain_ensemble_work_bytes(dims, B: int, samples: int, outputs: int) -> int:
+    """Bytes of the work buffers of one ``explain_ensemble`` call: per member the kept hidden activations, per (member,
+    explained output) two G buffers of the widest hidden layer and the transposed contributions, each line
+    ops.sparse_row_pad(B) floats."""
+    hidden = list(dims[1:-1])
+    per_member = sum(hidden) + outputs * (2 * max(hidden, default=0) + dims[0])
+    return 4 * ops.sparse_row_pad(B) * int(samples) * per_member
+
+
+@torch.no_grad()
+def explain_ensemble(fz, data: torch.Tensor, samples: int = 10, *, targets=None, weight_noise: bool = True,
+                     keep_members: bool = False, keep_weights: bool = False, levels=None,
+                     max_bytes: int = 2 << 30, keep_masks: bool = False) -> Dict[str, object]:
+    """Which inputs drove which output, row by row, WITH the posterior's uncertainty: the explanation of ``samples``
+    sampled-weight members of the sparse median probability model ``fz`` (``freeze(net, "mpm", sparse=True)``; LRT or planar
+    MNF, any head, 1 to 16 layers), and its mean, spread and sign probability over the members.
+
+    A member draws explicit weights on the kept pattern: per CSR slot ``w = mean * z[col] + sqrt(var) * eps`` (an LRT layer has
+    no z factor), per unit ``b = bias_mu + sqrt(bias_var) * eps``.  It is then an ordinary ReLU network, so its pre-head output
+    is exactly ``logits_m[b, c] = sum_i J_m[b, c, i] x[b, i] + k_m[b, c]``; the member of ``fz.ensemble`` draws per activation
+    (local reparameterisation, the row-wise marginal of this draw), is not linear in x and has no such sum.  Member m draws at
+    Philox offset live + m: z of an MNF layer from the flow launch of ``fz.ensemble`` (the same z, bit for bit), eps of the
+    weights from stream STREAM_EPS_W * 64 + layer id (slot k: counter (k / 4, 0), word k % 4), of the biases from STREAM_EPS_B *
+    64 + layer id (unit o: counter (o / 4, 0), word o % 4).  The live offset advances by ``samples`` (not at all when nothing is
+    drawn: an LRT model with ``weight_noise=False``).  ``weight_noise=False``: eps = 0, every member is the mean network under
+    its own z; an LRT model then has one member (``samples`` must be 1): the sparse counterpart of
+    ``explain(freeze(net, "mpm"), data)``.
+
+    ``targets`` as for ``explain``: None -- every output (C' = C <= 16); a (B,) int64 device tensor -- one output per row
+    (C' = 1; a value outside [0, C) raises IndexError, found by one host read); ``"pred"`` -- the largest member-mean logit of
+    the row, taken on the device.  Returns device tensors: ``mean``, ``std`` (B, C', F) over the members of J_m(b) * x (fp64 sum
+    in member order; the unbiased deviation, 0.0 for one member); ``prob_positive``, ``prob_negative`` (B, C', F), the share of
+    members with a contribution > 0 / < 0; ``logits`` (S, B, C); ``intercept`` (S, B, C') = b_L + sum_l <G_l D_l, b_l>, summed on
+    its own; ``residual`` (S, B, C') = logits - (sum_i contributions + intercept) in fp64 from the fp32 terms, the caller's
+    self-check; ``targets``; an MNF model: ``z``, per layer (S, in_features) (views of one buffer); ``keep_members``: ``members`` (S, B, C', F);
+    ``keep_weights``: ``weights`` / ``biases``, per layer (S, nnz) / (S, O); ``levels=(0.9, ...)``: ``lower`` / ``upper``, per
+    level the (B, C', F) bounds of the central interval, ``torch.quantile`` over ``members`` (which are then kept);
+    ``keep_masks`` (as for ``explain``): ``masks``, per hidden layer the (S, B, O_l) bool pattern h_l > 0 of the members' own
+    forward.  A feature without a kept path to the output contributes exactly 0.0 in every member.
+
+    The statistics are over one chunk of members.  Refused before any launch: a model that is not a SparseFrozenNetwork, CPU
+    data, ``samples`` < 1 or ``samples * C'`` > 65535, work buffers (``explain_ensemble_work_bytes``) above ``max_bytes``."""
+    import ctypes
+    from . import _lib
+    _check_ensemble_explainable(fz)
+    if not isinstance(data, torch.Tensor):
+        raise TypeError("bnn_amd: explain_ensemble takes a device tensor of input rows, got %s" % type(data).__name__)
+    if not data.is_cuda:
+        raise ValueError("bnn_amd: explain_ensemble runs on the HIP device (data is on %s); there is no CPU path -- move it with "
+                         "data.to(device)" % data.device)
+    S = int(samples)
+    if S < 1:
+        raise ValueError("bnn_amd: explain_ensemble takes samples >= 1, got %r" % (samples,))
+    mnf = fz.family == "mnf"
+    if not weight_noise and not mnf and S != 1:
+        raise ValueError("bnn_amd: an LRT model with weight_noise=False has ONE member (the mean network), got samples=%d; pass "
+                         "samples=1, or weight_noise=True for members that differ" % S)
+    if levels is not None:
+        levels = tuple(float(v) for v in levels)
+        if not levels or any(not 0.0 < v < 1.0 for v in levels):
+            raise ValueError("bnn_amd: levels must be coverages inside (0, 1), e.g. levels=(0.9,), got %r" % (levels,))
+        keep_members = True
+    n, dims = fz.n_layers, tuple(fz.dims)
+    C, F = dims[-1], dims[0]
+    x = fz._input(data)
+    B, dev = x.shape[0], x.device
+    pred = isinstance(targets, str)
+    if pred and targets != "pred":
+        raise ValueError("bnn_amd: targets must be None, \"pred\" or a (B,) int64 device tensor, got %r" % (targets,))
+    if targets is None:
+        if C > _lib.EXPLAIN_MAX_OUTPUTS:
+            raise ValueError("bnn_amd: explaining every output takes at most %d outputs, this model has %d; pass targets= (one "
+                             "output per row, e.g. targets=\"pred\")" % (_lib.EXPLAIN_MAX_OUTPUTS, C))
+        Cp = C
+    else:
+        Cp = 1
+        if not pred:
+            if not isinstance(targets, torch.Tensor) or targets.dtype != torch.int64 or tuple(targets.shape) != (B,):
+                raise ValueError("bnn_amd: targets must be a (%d,) int64 tensor (one output per row)" % B)
+            if targets.device != dev:
+                raise ValueError("bnn_amd: targets is on %s, the model on %s; move it with targets.to(device)" % (targets.device, dev))
+    if S * Cp > _lib.MEMBER_BLOCKS_MAX:
+        raise ValueError("bnn_amd: explain_ensemble takes at most %d (members x explained outputs) per call, got %d x %d; lower "
+                         "samples or pass targets=" % (_lib.MEMBER_BLOCKS_MAX, S, Cp))
+    work = explain_ensemble_work_bytes(dims, B, S, Cp)
+    if work > max_bytes:
+        raise ValueError("bnn_amd: explain_ensemble needs %d bytes of work buffers for %d rows x %d members x %d explained "
+                         "outputs, max_bytes is %d; split the batch or lower samples" % (work, B, S, Cp, max_bytes))
+    if targets is not None and not pred:
+        targets = targets.contiguous()
+        if B and bool(((targets < 0) | (targets >= C)).any()):
+            raise IndexError("bnn_amd: a target lies outside [0, %d)" % C)
+    f = dict(dtype=torch.float32, device=dev)
+    st = ops.RngState.get(dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        pats = [_transposed_pattern(fz, i) for i in range(n)]
+        csrs = [fz.csr(i) for i in range(n)]
+        zbuf = None
+        if mnf:
+            fz._draw_members(S, st.t, stream)
+            zbuf = fz._take_z(S)                              # the members' z go out with the result
+        zs = [] if mnf else None
+        layers, off = [], 0
+        for i in range(n):
+            z = None if zbuf is None else zbuf[:, off:off + dims[i]]
+            off += ops.operand_ld(dims[i])
+            if mnf:
+                zs.append(z)
+            _, col, mean, var = csrs[i]
+            layers.append((col, mean, var, fz._buf("bias_mu", i), fz._buf("bias_var", i), z, fz._layer_ids[i], dims[i],
+                           pats[i][3]))
+        wb = ops.sparse_draw_members(layers, S, st.t, weight_noise=weight_noise, empty=_empty, stream=stream)
+        # the live offset moves on in the seed launch, behind the launches that drew (with no rows: a launch of its own)
+        advance = S if (mnf or weight_noise) else 0
+        if advance and B == 0:
+            st.advance(S)
+        res = dict(targets=targets)
+        if zs is not None:
+            res["z"] = zs
+        if keep_weights:
+            res["weights"] = [t[0][:, :layers[i][0].numel()] for i, t in enumerate(wb)]
+            res["biases"] = [t[1][:, :dims[i + 1]] for i, t in enumerate(wb)]
+        if B == 0:
+            res.update(logits=torch.zeros((S, 0, C), **f), intercept=torch.zeros((S, 0, Cp), **f),
+                       residual=torch.zeros((S, 0, Cp), **f))
+            for k in ("mean", "std", "prob_positive", "prob_negative"):
+                res[k] = torch.zeros((0, Cp, F), **f)
+            if pred:
+                res["targets"] = torch.zeros(0, dtype=torch.int64, device=dev)
+            if keep_members:
+                res["members"] = torch.zeros((S, 0, Cp, F), **f)
+            if keep_masks:
+                res["masks"] = [torch.zeros((S, 0, dims[l + 1]), dtype=torch.bool, device=dev) for l in range(n - 1)]
+            if levels is not None:
+                res["lower"] = [torch.zeros((0, Cp, F), **f) for _ in levels]
+                res["upper"] = [torch.zeros((0, Cp, F), **f) for _ in levels]
+            return res
+        # the members' forward: every hidden layer kept, transposed [member][unit][ldb]
+        ldb = ops.sparse_row_pad(B)
+        xT = _empty((F, ldb), **f)
+        _lib.check(_lib.lib().lbbnn_transpose_operand(ops._ptr_rows(x, "x"), B, F, x.stride(0), xT.data_ptr(), ldb, 0, 0, stream),
+                   "lbbnn_transpose_operand")
+        logits = _empty((S, B, C), **f)
+        hs, a, a_ms = [], xT, 0
+        for i in range(n):
+            row_ptr, col, _, _ = csrs[i]
+            O, last = dims[i + 1], i == n - 1
+            o = logits if last else _empty((S, O * ldb), **f)
+            ops.sparse_gather_members(_lib.GATHER_FORWARD, row_ptr, col, None, wb[i][0], a, o, B=B, K=dims[i], N=O, lda=ldb,
+                                      a_mstride=a_ms, ldo=C if last else ldb, o_mstride=B * C if last else O * ldb, blocks=S,
+                                      bias=wb[i][1], relu=not last, out_rows=last, stream=stream)
+            if not last:
+                hs.append(o)
+                a, a_ms = o, O * ldb
+        if keep_masks:
+            res["masks"] = [(h.view(S, dims[l + 1], ldb)[:, :, :B] > 0).transpose(1, 2).contiguous() for l, h in enumerate(hs)]
+        # where the sweep starts, one launch: the explained output ("pred": the largest member-mean logit), the one-hot seed
+        # G_L [c'][c][b] the members share, and the intercept's first term b_L
+        if pred:
+            targets = res["targets"] = _empty((B,), dtype=torch.int64, device=dev)
+        R = S * Cp
+        seed, intercept = _empty((Cp, C, ldb), **f), _empty((S, B, Cp), **f)
+        _lib.check(_lib.lib().lbbnn_explain_seed(logits.data_ptr(), None if pred or targets is None else targets.data_ptr(),
+                                                 int(pred), targets.data_ptr() if pred else None, wb[n - 1][1].data_ptr(),
+                                                 wb[n - 1][1].stride(0), seed.data_ptr(), ldb, intercept.data_ptr(), S, B, C, Cp,
+                                                 st.t.data_ptr() if advance else None, advance, stream), "lbbnn_explain_seed")
+        # the sweep: the member layer on the transposed pattern, G_l = D_l W_{l+1}^T G_{l+1}, then J * x = (W_1^T G_1) * x^T; a
+        # launch whose input is a hidden layer's G also adds that layer's bias path <G, b> to the intercept
+        wmax = max(dims[1:-1], default=0)
+        gbufs = [_empty((R, wmax * ldb), **f) for _ in range(min(2, n - 1))]
+        g, g_ms, shared = seed, C * ldb, True
+        for l in range(n - 1, 0, -1):                        # hidden layer l: hs[l - 1], width dims[l]; the pattern of layer l + 1
+            width = dims[l]
+            col_ptr, trow = pats[l][:2]
+            o = gbufs[(n - 1 - l) % 2]
+            ops.sparse_gather_members(_lib.GATHER_SWEEP, col_ptr, trow, None, wb[l][2], g, o, B=B, K=dims[l + 1], N=width,
+                                      lda=ldb, a_mstride=g_ms, ldo=ldb, o_mstride=width * ldb, blocks=R, per_member=Cp,
+                                      h=hs[l - 1], ldh=ldb, h_mstride=width * ldb, a_shared=shared,
+                                      dot_bias=None if shared else wb[l][1], dot_acc=None if shared else intercept, stream=stream)
+            g, g_ms, shared = o, width * ldb, False
+        col_ptr, trow = pats[0][:2]
+        contrib = _empty((R, F * ldb), **f)
+        ops.sparse_gather_members(_lib.GATHER_FINISH, col_ptr, trow, None, wb[0][2], g, contrib, B=B, K=dims[1], N=F, lda=ldb,
+                                  a_mstride=g_ms, ldo=ldb, o_mstride=F * ldb, blocks=R, per_member=Cp, h=xT, ldh=ldb,
+                                  a_shared=shared, dot_bias=None if shared else wb[0][1], dot_acc=None if shared else intercept,
+                                  stream=stream)
+        # the statistics over the members, row-major
+        out = dict((k, _empty((B, Cp, F), **f)) for k in ("mean", "std", "prob_positive", "prob_negative"))
+        members = _empty((S, B, Cp, F), **f) if keep_members else None
+        residual = _empty((S, B, Cp), **f)
+        sa = _lib.MemberStatsArgs(contrib.data_ptr(), F * ldb, ldb, S, Cp, F, B, out["mean"].data_ptr(), out["std"].data_ptr(),
+                                  out["prob_positive"].data_ptr(), out["prob_negative"].data_ptr(),
+                                  members.data_ptr() if keep_members else None, logits.data_ptr(), C, C,
+                                  targets.data_ptr() if targets is not None else None, intercept.data_ptr(), residual.data_ptr())
+        _lib.check(_lib.lib().lbbnn_explain_member_stats(ctypes.byref(sa), stream), "lbbnn_explain_member_stats")
+        res.update(out, logits=logits, intercept=intercept, residual=residual)
+        if keep_members:
+            res["members"] = members
+        if levels is not None:
+            res["lower"] = [torch.quantile(members, (1.0 - v) / 2.0, dim=0) for v in levels]
+            res["upper"] = [torch.quantile(members, (1.0 + v) / 2.0, dim=0) for v in levels]
+    return res

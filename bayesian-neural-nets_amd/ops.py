@@ -632,6 +632,72 @@ def sparse_member_chain(x, members: int, layers, *, head: str, out, empty=torch.
     return out
 
 
+def sparse_transposed_pattern(row_ptr: torch.Tensor, col: torch.Tensor, I: int):
+    """(col_ptr (I + 1) int32, trow (nnz) int32, tslot (nnz) int32) of a CSR layer: the same entries column by column, rows
+    ascending within a column; tslot[k] is the CSR slot of transposed entry k.  Torch ops on the tensors' own device, no host
+    read: CSR slots are row-major, so a STABLE sort of the slots by column keeps the rows of a column in ascending order; the
+    row of a slot is repeat_interleave of the row lengths (its output size is known: nnz); the column lengths are an integer
+    scatter-add of ones (bincount would read its largest value back to size its result)."""
+    nnz, O, dev = col.numel(), row_ptr.numel() - 1, col.device
+    c = col.long()
+    tslot = torch.argsort(c, stable=True)
+    rows = torch.repeat_interleave(torch.arange(O, device=dev), (row_ptr[1:] - row_ptr[:-1]).long(), output_size=nnz)
+    counts = torch.zeros(I, dtype=torch.int64, device=dev).index_add_(0, c, torch.ones(nnz, dtype=torch.int64, device=dev))
+    col_ptr = torch.zeros(I + 1, dtype=torch.int32, device=dev)
+    torch.cumsum(counts, 0, dtype=torch.int32, out=col_ptr[1:])
+    return col_ptr, rows[tslot].to(torch.int32), tslot.to(torch.int32)
+
+
+def sparse_draw_members(layers, members: int, rng, *, weight_noise: bool = True, empty=torch.empty, stream=None):
+    """The explicit weights of ``members`` sampled-weight members of a sparse model (lbbnn_sparse_draw_members, one launch per
+    group of up to LBBNN_MAX_LAYERS layers).  ``layers``: per layer (col, mean, var, bias_mu, bias_var, z, layer_id, I, tpos)
+    with z None (LRT) or a (members, >= I) view whose row stride is its member stride, and tpos None or the (nnz,) int32 place
+    of every slot in the column-by-column order.  Member m draws at Philox offset rng[1] + m; ``weight_noise`` False: eps = 0,
+    nothing is drawn.  Returns per layer (w (members, pad4(nnz)), b (members, pad4(O)), wt): wt the values once more at
+    wt[m][tpos[k]] (None without tpos)."""
+    stream = _stream() if stream is None else stream
+    n = len(layers)
+    descs = (_lib.SparseDrawDesc * n)()
+    out = []
+    for i, (col, mean, var, bias_mu, bias_var, z, layer_id, I, tpos) in enumerate(layers):
+        nnz, O, dev = col.numel(), bias_mu.numel(), bias_mu.device
+        ldw, ldb = pad4(nnz), pad4(O)
+        w = empty((members, ldw), dtype=torch.float32, device=dev)
+        b = empty((members, ldb), dtype=torch.float32, device=dev)
+        wt = None if tpos is None else empty((members, ldw), dtype=torch.float32, device=dev)
+        # (one constructor call in the struct's field order)
+        descs[i] = _lib.SparseDrawDesc(col.data_ptr(), mean.data_ptr(), var.data_ptr(), bias_mu.data_ptr(), bias_var.data_ptr(),
+                                       None if z is None else z.data_ptr(), 0 if z is None else z.stride(0),
+                                       None if tpos is None else tpos.data_ptr(), None if wt is None else wt.data_ptr(),
+                                       w.data_ptr(), ldw, b.data_ptr(), ldb, O, I, nnz, layer_id)
+        out.append((w, b, wt))
+    for k, cnt in _lib.layer_groups(n):
+        rc = _lib.lib().lbbnn_sparse_draw_members(_lib.group_slice(descs, k, cnt), cnt, members,
+                                                  rng.data_ptr() if weight_noise else None, 0 if weight_noise else F_MEAN_ONLY,
+                                                  stream)
+        _lib.check(rc, "lbbnn_sparse_draw_members")
+    return out
+
+
+def sparse_gather_members(mode: int, ptr, idx, slot, w, a, out, *, B: int, K: int, N: int, lda: int, a_mstride: int, ldo: int,
+                          o_mstride: int, blocks: int, per_member: int = 1, bias=None, h=None, ldh: int = 0, h_mstride: int = 0,
+                          relu: bool = False, out_rows: bool = False, a_shared: bool = False, dot_bias=None, dot_acc=None, stream=None):
+    """One lbbnn_sparse_gather_members launch: the member layer on stored values ``w`` (members, >= nnz), pattern ptr / idx
+    (values through ``slot`` when given), input lines ``a``, post-op ``mode`` (_lib.GATHER_*).  ``dot_bias`` (members, >= K) with
+    ``dot_acc``: the same launch adds <a[block][.][b], dot_bias[m]> to dot_acc[(m * B + b) * per_member + c]."""
+    # (one constructor call in the struct's field order: this runs six times per explanation)
+    g = _lib.SparseGatherArgs(ptr.data_ptr(), idx.data_ptr(), None if slot is None else slot.data_ptr(), w.data_ptr(), w.stride(0),
+                              None if bias is None else bias.data_ptr(), 0 if bias is None else bias.stride(0), a.data_ptr(),
+                              a_mstride, None if h is None else h.data_ptr(), h_mstride, out.data_ptr(), o_mstride, lda, ldh, ldo,
+                              B, K, N, idx.numel(), mode, int(relu), int(out_rows), int(a_shared), blocks, per_member,
+                              None if dot_bias is None else dot_bias.data_ptr(), 0 if dot_bias is None else dot_bias.stride(0),
+                              None if dot_acc is None else dot_acc.data_ptr())
+    import ctypes
+    _lib.check(_lib.lib().lbbnn_sparse_gather_members(ctypes.byref(g), _stream() if stream is None else stream),
+               "lbbnn_sparse_gather_members")
+    return out
+
+
 def plane_ld(n: int) -> int:
     return operand_ld(n)
 

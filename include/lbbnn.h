@@ -2029,6 +2029,133 @@ int lbbnn_explain_totals(const float* contributions, int64_t ldc, const int64_t*
                          double* sum, double* abs_sum, int64_t* rows, void* work, void* stream);
 int lbbnn_explain_operand(const void* op, int O, int I, int ld, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Explanations of sampled-weight members of the sparse median-probability model (evaluate.explain_ensemble).  A member draws
+ * explicit weights on the kept pattern -- w[m][k] = mean[k] * z_m[col[k]] + sqrt(var[k]) * eps, b[m][o] = bias_mu[o] +
+ * sqrt(bias_var[o]) * eps -- and is then an ordinary ReLU network, so its pre-head output is exactly linear in the input and
+ * J_m(b) * x is well defined (the local-reparameterisation member of lbbnn_sparse_layer_members draws per activation and is
+ * not).  All buffers between the launches are TRANSPOSED, [block][unit][ld] with the batch row fastest, as in
+ * lbbnn_sparse_layer_members.  Every store is a plain vector store; no atomics; sums are sequential or added in a fixed order.
+ *
+ * lbbnn_sparse_draw_members: ONE launch for all n <= LBBNN_MAX_LAYERS layers and all members.  One thread draws four
+ *   consecutive CSR slots (or four units' biases) from one philox_normal4 call at {rng[0], rng[1] + m}:
+ *     w[m * w_mstride + k] = fmaf(v_sqrt_f32(var[k]), eps, mean[k] * z[m * z_mstride + col[k]])    stream LBBNN_STREAM_EPS_W * 64 +
+ *                            layer_id, counter (k / 4, 0), word k % 4;  z == NULL: no z factor
+ *     b[m * b_mstride + o] = fmaf(v_sqrt_f32(bias_var[o]), eps, bias_mu[o])                          stream LBBNN_STREAM_EPS_B * 64 +
+ *                            layer_id, counter (o / 4, 0), word o % 4
+ *   With tpos / wt (both or neither, else LBBNN_E_NULL) the same value is also stored at wt[m * w_mstride + tpos[k]] (tpos
+ *   clamped into [0, nnz)): with tpos the inverse of tslot, wt holds the member's values column by column, the order in which
+ *   the sweep walks them.
+ *   LBBNN_F_MEAN_ONLY: eps = 0 and nothing is drawn (rng may be NULL).  A member's w / b block is written in whole 16-B quads:
+ *   w_mstride >= pad4(nnz), b_mstride >= pad4(O), the tail of the last quad is 0.  col is clamped into [0, I).
+ *   NULL layers, bias_mu / bias_var / b, or col / mean / var / w with nnz > 0: LBBNN_E_NULL; n outside [1, LBBNN_MAX_LAYERS],
+ *   members outside [1, 65535], O < 1, I < 1, nnz < 0, a member stride below its padded row, z_mstride < I: LBBNN_E_SHAPE; flags
+ *   other than 0 | LBBNN_F_MEAN_ONLY: LBBNN_E_FLAGS; rng == NULL without LBBNN_F_MEAN_ONLY: LBBNN_E_NOISE; w / b off a 16-B
+ *   boundary or a stride of theirs not a multiple of 4, any other pointer off 4 B (rng: 8 B): LBBNN_E_ALIGN.
+ *
+ * lbbnn_sparse_gather_members: the member layer on stored values, for `blocks` grid blocks (gridDim.z) of which every
+ *   `per_member` consecutive ones belong to one member (m = block / per_member).  With ptr (N + 1) / idx (nnz) a CSR-shaped
+ *   pattern over N output units whose entries name input lines in [0, K) (clamped), k running over ptr[u] .. ptr[u + 1] - 1:
+ *     s[u][b] = sum_k w[m * w_mstride + (slot ? slot[k] : k)] * a[ablock * a_mstride + idx[k] * lda + b]
+ *   sequential fp32 FMAs from 0 in pattern order.  ablock = block, or block % per_member with a_shared (the one-hot seed every
+ *   member shares).  Then, by mode:
+ *     LBBNN_GATHER_FORWARD  out = s + bias[m * b_mstride + u], then ReLU with `relu`                    (pattern: row_ptr / col)
+ *     LBBNN_GATHER_SWEEP    out = h[m * h_mstride + u * ldh + b] > 0 ? s : 0                            (pattern: col_ptr / trow,
+ *                           G_l = D_l W_{l+1}^T G_{l+1}; values column by column -- wt of the draw -- or w with slot = tslot)
+ *     LBBNN_GATHER_FINISH   out = s * h[u * ldh + b]   with h = x^T, shared by all blocks: the contributions J * x, transposed
+ *   out[block * o_mstride + u * ldo + b] (out_rows == 0) or out[block * o_mstride + b * ldo + u] (out_rows != 0).
+ *   With dot_bias / dot_acc (both or neither, else LBBNN_E_NULL; not with a_shared: LBBNN_E_FLAGS) extra workgroups of the same
+ *   launch add the bias path of the layer whose G is the input: dot_acc[(m * B + b) * per_member + c] += sum_u a[block * a_mstride
+ *   + u * lda + b] * dot_bias[m * dot_b_mstride + u] -- four sequential FMA chains over the quarters ceil(K / 4) of u = 0 .. K - 1,
+ *   added in order (block = m * per_member + c).  This is how the intercept gathers its hidden layers' terms without a launch.
+ *   One lane per batch row (two when B > 64 and the strides allow 8-B words), four units per wave; pattern and values are
+ *   wave-uniform scalar loads.  The bits of a number depend on its block, row and unit alone.
+ *   B == 0: 0.  args, ptr, w / idx with nnz > 0, a, out, bias (forward) or h (sweep, finish) NULL (slot is nullable):
+ *   LBBNN_E_NULL; B < 0 or more than 65535 * 64 rows, K, N < 1, nnz < 0, blocks outside
+ *   [1, 65535], per_member < 1 or not dividing blocks, lda / ldh < B, ldo below the layout's need, a negative stride, an
+ *   output block stride that does not hold a block, an input block of 2 GiB or more: LBBNN_E_SHAPE; an unknown mode:
+ *   LBBNN_E_FLAGS; a pointer off 4 B: LBBNN_E_ALIGN.
+ *
+ * lbbnn_explain_seed: where the sweep starts, one lane per line position b < ld.  t(b, c') = c' (no targets, Cp == C), targets[b]
+ *   (Cp == 1, clamped into [0, C)) or, with pred (Cp == 1), the first largest of mean_m logits[(m * B + b) * C + c] (fp32 sum in
+ *   member order, / S), which is also written to targets_out[b].  seed[(c' * C + c) * ld + b] = (b < B && c == t) -- the one-hot
+ *   G_L shared by the members -- and intercept[(m * B + b) * Cp + c'] = bias[m * b_mstride + t], the last layer's bias.
+ *   rng_live (nullable): rng_live[1] += advance by one lane -- the live Philox offset moves on behind the launches that drew.
+ *   B == 0: 0.  bias / seed / intercept, or logits / targets_out with pred NULL: LBBNN_E_NULL; S outside [1, 65535], B < 0, C < 1,
+ *   ld < B, Cp != 1 with targets or pred, Cp != C without, b_mstride < C with S > 1: LBBNN_E_SHAPE; pred with targets:
+ *   LBBNN_E_FLAGS; alignment (rng_live: 8 B): LBBNN_E_ALIGN.
+ *
+ * lbbnn_explain_member_stats: statistics over the S members of contributions t[(m * C + c) * t_mstride + i * ldt + b] (what
+ *   LBBNN_GATHER_FINISH wrote), as row-major (B, C, F) tensors: mean = (sum_m v) / S with the sum in fp64 in member order; std
+ *   = sqrt(sum_m (v - mean)^2 / (S - 1)) in fp64, as (sum d^2 - (sum d)^2 / S) with d = v - v_0 shifted by the first member (one pass; 0 for S == 1); prob_pos / prob_neg = #{m : v > 0} / S and
+ *   #{m : v < 0} / S from integer counts; members (nullable) [m][b][c][i] = v.  A 64 x 64 (feature x row) tile goes through
+ *   LDS so that both the loads and the stores are coalesced.  With residual (nullable; needs logits and intercept):
+ *   residual[(m * B + b) * C + c] = logits[(m * B + b) * ldl + t] - (sum_i v + intercept[(m * B + b) * C + c]) in fp64 with the
+ *   sum over i in index order; t = c without targets, targets[b] (C == 1, clamped into [0, n_logits)) with.
+ *   B == 0: 0.  args / t / mean / std / prob_pos / prob_neg NULL, residual without logits / intercept: LBBNN_E_NULL; S outside
+ *   [1, 65535], C < 1, S * C > 65535, F < 1, B < 0, ldt < B, t_mstride < (F - 1) * ldt + B, targets with C != 1, ldl < n_logits,
+ *   C > n_logits without targets: LBBNN_E_SHAPE; a pointer off its natural alignment: LBBNN_E_ALIGN. */
+#define LBBNN_GATHER_FORWARD 0
+#define LBBNN_GATHER_SWEEP 1
+#define LBBNN_GATHER_FINISH 2
+typedef struct lbbnn_sparse_draw_desc {
+    const int32_t* col;                              /* (nnz)                                   */
+    const float *mean, *var;                         /* (nnz)                                   */
+    const float *bias_mu, *bias_var;                 /* (O)                                     */
+    const float* z;                                  /* [members][z_mstride] or NULL            */
+    int64_t z_mstride;
+    const int32_t* tpos;                             /* (nnz) or NULL: place of slot k in wt    */
+    float* wt;                                       /* [members][w_mstride] or NULL, with tpos */
+    float* w;                                        /* [members][w_mstride]                    */
+    int64_t w_mstride;
+    float* b;                                        /* [members][b_mstride]                    */
+    int64_t b_mstride;
+    int O, I, nnz;
+    uint32_t layer_id;
+} lbbnn_sparse_draw_desc_t;
+
+typedef struct lbbnn_sparse_gather_args {
+    const int32_t *ptr, *idx, *slot;
+    const float* w;
+    int64_t w_mstride;
+    const float* bias;
+    int64_t b_mstride;
+    const float* a;
+    int64_t a_mstride;
+    const float* h;
+    int64_t h_mstride;
+    float* out;
+    int64_t o_mstride;
+    int lda, ldh, ldo;
+    int B, K, N, nnz;
+    int mode, relu, out_rows, a_shared;
+    int blocks, per_member;
+    const float* dot_bias;                           /* nullable, with dot_acc: the bias path of the INPUT's layer */
+    int64_t dot_b_mstride;
+    float* dot_acc;
+} lbbnn_sparse_gather_args_t;
+
+typedef struct lbbnn_member_stats_args {
+    const float* t;
+    int64_t t_mstride;
+    int ldt;
+    int S, C, F, B;
+    float *mean, *std, *prob_pos, *prob_neg, *members;
+    const float* logits;
+    int ldl, n_logits;
+    const int64_t* targets;
+    const float* intercept;
+    float* residual;
+} lbbnn_member_stats_args_t;
+
+int lbbnn_sparse_draw_members(const lbbnn_sparse_draw_desc_t* layers, int n, int members, const uint64_t* rng, int flags,
+                              void* stream);
+int lbbnn_sparse_gather_members(const lbbnn_sparse_gather_args_t* args, void* stream);
+int lbbnn_explain_seed(const float* logits, const int64_t* targets, int pred, int64_t* targets_out, const float* bias,
+                       int64_t b_mstride, float* seed, int ld, float* intercept, int S, int B, int C, int Cp, uint64_t* rng_live,
+                       uint64_t advance, void* stream);
+int lbbnn_explain_member_stats(const lbbnn_member_stats_args_t* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
