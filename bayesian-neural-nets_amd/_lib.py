@@ -251,6 +251,18 @@ class MemberStatsArgs(ctypes.Structure):
                [("ldl", c_i), ("n_logits", c_i), ("targets", c_p), ("intercept", c_p), ("residual", c_p)]
 
 
+class BaseSparseDesc(ctypes.Structure):
+    """lbbnn_base_sparse_desc_t"""
+    _fields_ = [(n, c_p) for n in ("mu", "rho", "lambdal", "bias_mu", "bias_rho", "row_ptr", "col", "mean", "sigma", "b_mu",
+                                   "b_sigma", "kept_rows")] + [("O", c_i), ("I", c_i), ("nnz", c_i)]
+
+
+class BaseSparseDrawDesc(ctypes.Structure):
+    """lbbnn_base_sparse_draw_desc_t"""
+    _fields_ = [(n, c_p) for n in ("row_ptr", "col", "mean", "sigma", "b_mu", "b_sigma", "tpos", "wt", "w")] + \
+               [("w_mstride", c_i64), ("b", c_p), ("b_mstride", c_i64), ("O", c_i), ("I", c_i), ("nnz", c_i), ("layer_id", c_u32)]
+
+
 class BaseFrozenDesc(ctypes.Structure):
     """lbbnn_base_frozen_desc_t"""
     _fields_ = [(n, c_p) for n in ("mu", "rho", "lambdal", "bias_mu", "bias_rho", "w_mu", "w_sigma", "alpha", "e_w", "b_mu",
@@ -551,6 +563,9 @@ SIGNATURES = {
     "lbbnn_sparse_gather_members": (c_i, [ctypes.POINTER(SparseGatherArgs), c_p]),
     "lbbnn_explain_seed": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i64, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_u64, c_p]),
     "lbbnn_explain_member_stats": (c_i, [ctypes.POINTER(MemberStatsArgs), c_p]),
+    "lbbnn_base_sparse_count": (c_i, [ctypes.POINTER(BaseSparseDesc), c_i, ctypes.c_float, c_p]),
+    "lbbnn_base_sparse_pack": (c_i, [ctypes.POINTER(BaseSparseDesc), c_i, ctypes.c_float, c_p]),
+    "lbbnn_base_sparse_draw_members": (c_i, [ctypes.POINTER(BaseSparseDrawDesc), c_i, c_i, c_p, c_u64, c_i, c_p]),
 }
 
 _lib = None

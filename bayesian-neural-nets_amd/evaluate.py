@@ -30,6 +30,10 @@ Baseline networks have a frozen model of their own, ``freeze_base(net, gates="sa
 ``FrozenBaseNetwork``: sigma, alpha and the gated means taken once (lbbnn_base_frozen_operands), every member then drawn from
 that snapshot (lbbnn_base_frozen_members) at the streams, offsets and counters of ``base_ensemble`` -- a full model's members are
 ``base_ensemble``'s bit for bit, a compact model's weights the full model's at the rows and columns that stay.
+``freeze_base(net, "mpm", sparse=True)`` -> ``SparseFrozenBaseNetwork``: the kept weights alone in CSR, every member's (nnz,)
+values drawn at the full network's counters (lbbnn_base_sparse_draw_members: the dense model's member weights bit for bit at
+the kept positions) and run by the member layer on stored values (lbbnn_sparse_gather_members); the baseline member has explicit
+weights, so ``explain_ensemble`` explains exactly the members this model's ``ensemble`` evaluates.
 
 An LRT / MNF network with ``head="identity"`` (regression) returns raw outputs from every ensemble form above and from its frozen
 models; ``ensemble_regression`` / ``RegressionAccumulator`` (lbbnn_eval_regression) are its metrics -- predictive mean, epistemic
@@ -2759,12 +2763,13 @@ def _base_sources(d, l, i: int):
     d.bias_mu, d.bias_rho = l.bias_mu.data_ptr(), l.bias_rho.data_ptr()
 
 
-def _check_base_freezable(layers):
+def _check_base_freezable(layers, dense: bool = True):
+    """``dense`` False: a sparse model, which holds no operand rows and so has no widest row."""
     for i, l in enumerate(layers):
         if l.noise:
             raise ValueError("bnn_amd: layer %d has injected noise (layer.noise); a frozen model draws in-kernel noise only -- "
                              "clear layer.noise first" % (i + 1))
-        if ops.operand_ld(l.in_features) > ops.GATE_MEMBERS_MAX_LD:
+        if dense and ops.operand_ld(l.in_features) > ops.GATE_MEMBERS_MAX_LD:
             raise ValueError("bnn_amd: layer %d: in_features = %d gives operand rows wider than the member kernels take "
                              "(operand_ld(in_features) <= %d); evaluate this network with base_ensemble(net, data, samples)"
                              % (i + 1, l.in_features, ops.GATE_MEMBERS_MAX_LD))
@@ -2793,7 +2798,7 @@ def _base_keep_masks(layers, threshold: float):
     return [p.bool() for p in planes]
 
 
-def freeze_base(net, gates: str = "sample", *, threshold: float = 0.5, compact: bool = False) -> FrozenBaseNetwork:
+def freeze_base(net, gates: str = "sample", *, threshold: float = 0.5, compact: bool = False, sparse: bool = False):
     """Frozen evaluation model of a baseline LBBNN network (``base.BayesianNetwork``) on a HIP device.
 
     ``gates="sample"``: every member draws its gates as trained (the hard draw when ``gamma.exact`` is set, else the relaxed
@@ -2806,9 +2811,17 @@ def freeze_base(net, gates: str = "sample", *, threshold: float = 0.5, compact: 
     ``compact=True`` (with ``gates="mpm"``): the model without the hidden units and input features no output depends on
     (``live_structure`` of the kernel's own keep masks); its members' weights are the full model's, bit for bit, at the rows
     and columns that stay, its outputs equal the full model's to fp32 rounding.  The one device read that sizes its buffers
-    happens here.  Refused, each with a ValueError / TypeError that names the cause: a network that is not a
-    ``base.BayesianNetwork``, unknown ``gates``, a threshold outside (0, 1), ``compact=True`` with ``gates="sample"``, a layer
-    with injected ``noise``, a layer wider than ``ops.GATE_MEMBERS_MAX_LD`` operand columns, a network on the CPU."""
+    happens here.
+
+    ``sparse=True`` (with ``gates="mpm"``): a ``SparseFrozenBaseNetwork`` -- the kept weights alone, in CSR, whose members are
+    drawn on that pattern (the dense model's members, bit for bit, at the kept positions) and evaluated on the vector ALU
+    without touching a pruned weight; fp32 whatever the precision setting.  It is also what ``explain_ensemble`` explains for
+    this family.  The one device read (nnz per layer, to size the buffers) happens here.
+
+    Refused, each with a ValueError / TypeError that names the cause: a network that is not a
+    ``base.BayesianNetwork``, unknown ``gates``, a threshold outside (0, 1), ``compact=True`` or ``sparse=True`` with
+    ``gates="sample"``, ``sparse=True`` with ``compact=True``, a layer with injected ``noise``, a layer wider than
+    ``ops.GATE_MEMBERS_MAX_LD`` operand columns (dense models), a network on the CPU."""
     if not _is_base(net):
         raise TypeError("bnn_amd: freeze_base takes a baseline LBBNN network (bnn_amd.base.BayesianNetwork), got %s; an LRT / "
                         "MNF network has evaluate.freeze" % type(net).__name__)
@@ -2818,11 +2831,22 @@ def freeze_base(net, gates: str = "sample", *, threshold: float = 0.5, compact: 
     if compact and gates != "mpm":
         raise ValueError("bnn_amd: compact=True needs gates=\"mpm\": sampled gates are never fixed at zero, so no unit can be "
                          "dropped -- use freeze_base(net, \"mpm\", compact=True), or freeze_base(net) for the gates as trained")
+    if sparse and gates != "mpm":
+        raise ValueError("bnn_amd: sparse=True needs gates=\"mpm\": sampled gates are never fixed at zero, so every weight "
+                         "stays -- use freeze_base(net, \"mpm\", sparse=True), or freeze_base(net) for the gates as trained")
+    if sparse and compact:
+        raise ValueError("bnn_amd: sparse=True with compact=True is not built: the sparse model already touches no pruned "
+                         "weight (pruning it further to the active paths is out of scope) -- use freeze_base(net, \"mpm\", "
+                         "sparse=True) or freeze_base(net, \"mpm\", compact=True)")
     layers = net._layers()
-    _check_base_freezable(layers)
+    _check_base_freezable(layers, dense=not sparse)
     dev = layers[0].weight_mu.device
     if not layers[0].weight_mu.is_cuda:
         raise ValueError("bnn_amd: freeze_base needs the network on a HIP device (it is on %s); there is no CPU path" % dev)
+    if sparse:
+        fz = SparseFrozenBaseNetwork(net.dims, threshold, device=dev, head=net.head)
+        fz.eval()
+        return fz._bind(net)
     live = needed = need = masks = None
     if compact:
         masks = _base_keep_masks(layers, threshold)
@@ -2832,10 +2856,243 @@ def freeze_base(net, gates: str = "sample", *, threshold: float = 0.5, compact: 
     return fz._bind(net, need, masks)
 
 
+
+class SparseFrozenBaseNetwork(_FrozenModel):
+    """The median probability model of a baseline LBBNN network as its kept weights alone (``freeze_base(net, "mpm",
+    sparse=True)``): per layer a CSR of the weights with sigmoid(lambdal) > threshold (the comparison of the dense frozen
+    model, made by the kernel in fp32) -- buffers ``row_ptr_<i>`` (O + 1) int32, ``col_<i>`` (nnz) int32 ascending within a row,
+    ``mean_<i>`` (nnz) = weight_mu, ``sigma_<i>`` (nnz) = softplus(weight_rho) -- plus the dense ``b_mu``, ``b_sigma`` and
+    ``kept_rows``.  It holds no dense plane and no dense member operand: the members' weights are (members, nnz) values, and a
+    layer is ONE lbbnn_sparse_gather_members launch for all members, on the vector ALU, over the kept weights only.  The model
+    is fp32 whatever the precision setting.  ``csr(i)``: the four tensors of layer i; ``nnz`` / ``operand_bytes``: plain ints.
+
+    Draws: member m draws at Philox offset live + m, every kept weight at its counter in the FULL network -- the weights and
+    biases of ``freeze_base(net, "mpm", threshold=t)``'s member m at the kept positions, bit for bit (the pruned ones are that
+    model's zeros), so a member equals the dense model's to fp32 rounding (the sums run over the kept weights in column order,
+    sequentially).  The bits of an output depend on its member, row and unit alone.  The baseline member is an explicit-weight
+    member, so ``evaluate.explain_ensemble`` explains exactly the members ``ensemble`` evaluates; its first call adds the buffers
+    ``col_ptr_<i>`` (I + 1), ``trow_<i>``, ``tslot_<i>``, ``tpos_<i>`` (nnz): the pattern column by column.  No ``refresh()``:
+    freeze again."""
+
+    GATES, FREEZE = ("mpm",), "freeze_base"
+    GATES_DOC = "'mpm' (a sparse model is the median probability model)"
+    _POINTER_STATE = ("_draw_descs",)
+
+    def __init__(self, dims, threshold: float = 0.5, device=None, head: str = "log_softmax"):
+        super().__init__(dims, "mpm", threshold, device, head)
+        self.family = "base"
+        self._nnz = []
+        self._draw_descs = None
+        self.last_weights = self.last_biases = None
+
+    def extra_repr(self) -> str:
+        head = ", head=%s" % self.head if self.head != "log_softmax" else ""
+        return "dims=%s, family=base, gates=mpm, threshold=%g%s, sparse, nnz=%d" % (self.dims, self.threshold, head, self.nnz)
+
+    def _device(self):
+        return self._buf("kept_rows", 0).device
+
+    @property
+    def nnz(self) -> int:
+        """Kept weights over every layer."""
+        return sum(self._nnz)
+
+    @property
+    def operand_bytes(self) -> int:
+        """Bytes of everything the draw reads of this model: row_ptr, col, mean, sigma, b_mu and b_sigma."""
+        return sum(4 * (self.dims[i + 1] + 1) + 12 * n + 8 * self.dims[i + 1] for i, n in enumerate(self._nnz))
+
+    def csr(self, i: int):
+        """(row_ptr, col, mean, sigma) of layer i."""
+        return tuple(self._buf(k, i) for k in ("row_ptr", "col", "mean", "sigma"))
+
+    @torch.no_grad()
+    def _bind(self, net):
+        """Count, scan, size (the ONE host read), pack: two batched launches per layer group and torch's cumsum between."""
+        from . import _lib
+        layers = net._layers()
+        dev = layers[0].weight_mu.device
+        f = dict(dtype=torch.float32, device=dev)
+        n = self.n_layers
+        self._src = [net]
+        self._layer_ids = [int(l._layer_id) for l in layers]
+        self._split = [False] * n
+        descs = (_lib.BaseSparseDesc * n)()
+        for i, l in enumerate(layers):
+            O = self.dims[i + 1]
+            d = descs[i]
+            _base_sources(d, l, i)
+            for name in ("b_mu", "b_sigma"):
+                self.register_buffer("%s_%d" % (name, i), _empty((O,), **f))
+            d.b_mu, d.b_sigma = self._buf("b_mu", i).data_ptr(), self._buf("b_sigma", i).data_ptr()
+            d.kept_rows = self._buf("kept_rows", i).data_ptr()
+            d.O, d.I = O, self.dims[i]
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            for k, cnt in _lib.layer_groups(n):
+                _lib.check(_lib.lib().lbbnn_base_sparse_count(_lib.group_slice(descs, k, cnt), cnt, self.threshold, stream),
+                           "lbbnn_base_sparse_count")
+            for i in range(n):
+                self.register_buffer("row_ptr_%d" % i, ops.sparse_row_ptr(self._buf("kept_rows", i)))
+            self._nnz = [int(v) for v in torch.stack([self._buf("row_ptr", i)[-1] for i in range(n)]).tolist()]   # the host read
+            for i, nz in enumerate(self._nnz):
+                # (col comes from _empty too, as fp32 words: a NaN-filled slot that was never packed is an index out of range)
+                self.register_buffer("col_%d" % i, _empty((nz,), **f).view(torch.int32))
+                self.register_buffer("mean_%d" % i, _empty((nz,), **f))
+                self.register_buffer("sigma_%d" % i, _empty((nz,), **f))
+                d = descs[i]
+                d.row_ptr, d.nnz = self._buf("row_ptr", i).data_ptr(), nz
+                d.col, d.mean, d.sigma = (self._buf(k, i).data_ptr() for k in ("col", "mean", "sigma"))
+            for k, cnt in _lib.layer_groups(n):
+                _lib.check(_lib.lib().lbbnn_base_sparse_pack(_lib.group_slice(descs, k, cnt), cnt, self.threshold, stream),
+                           "lbbnn_base_sparse_pack")
+        self._point()
+        return self
+
+    def _point(self):
+        """The draw descriptors of every layer, pointing at this model's buffers as they are now (a call fills in its own
+        member buffers)."""
+        from . import _lib
+        n = self.n_layers
+        self._draw_descs = (_lib.BaseSparseDrawDesc * n)()
+        for i in range(n):
+            d = self._draw_descs[i]
+            d.row_ptr, d.col, d.mean, d.sigma = (t.data_ptr() for t in self.csr(i))
+            d.b_mu, d.b_sigma = self._buf("b_mu", i).data_ptr(), self._buf("b_sigma", i).data_ptr()
+            d.O, d.I, d.nnz, d.layer_id = self.dims[i + 1], self.dims[i], self._nnz[i], self._layer_ids[i]
+
+    def refresh(self):
+        raise NotImplementedError("bnn_amd: a sparse model does not refresh: the structure, and with it the size of every CSR "
+                                  "buffer, may have changed with the parameters -- freeze again (evaluate.freeze_base(net, "
+                                  "\"mpm\", sparse=True))")
+
+    # ------------------------------------------------------------------------------------- evaluation
+    def _draw(self, c: int, rng, stream, tpos=None, weight_noise: bool = True):
+        """Members live .. live + c - 1: per layer (w (c, pad4(nnz)), b (c, pad4(O)), wt) from ceil(n / 4)
+        lbbnn_base_sparse_draw_members launches; ``tpos`` (per layer the place of every slot in the column-by-column order):
+        wt holds the values once more in that order (None without).  Every group reads the same offset; the caller advances it."""
+        from . import _lib
+        n, descs, out = self.n_layers, self._draw_descs, []
+        f = dict(dtype=torch.float32, device=self._device())
+        for i in range(n):
+            ldw, ldo = ops.pad4(self._nnz[i]), ops.pad4(self.dims[i + 1])
+            w, b = _empty((c, ldw), **f), _empty((c, ldo), **f)
+            wt = None if tpos is None else _empty((c, ldw), **f)
+            d = descs[i]
+            d.w, d.w_mstride, d.b, d.b_mstride = w.data_ptr(), ldw, b.data_ptr(), ldo
+            d.tpos, d.wt = (None, None) if tpos is None else (tpos[i].data_ptr(), wt.data_ptr())
+            out.append((w, b, wt))
+        for k, cnt in _lib.layer_groups(n):
+            rc = _lib.lib().lbbnn_base_sparse_draw_members(_lib.group_slice(descs, k, cnt), cnt, c,
+                                                           rng.data_ptr() if weight_noise else None, 1,
+                                                           0 if weight_noise else ops.F_MEAN_ONLY, stream)
+            _lib.check(rc, "lbbnn_base_sparse_draw_members")
+        return out
+
+    def _transpose(self, x, stream):
+        """x^T [I0][sparse_row_pad(B)], what every member's first layer reads: one launch."""
+        from . import _lib
+        B, I = x.shape
+        ldb = ops.sparse_row_pad(B)
+        xT = _empty((I, ldb), dtype=torch.float32, device=x.device)
+        _lib.check(_lib.lib().lbbnn_transpose_operand(ops._ptr_rows(x, "x"), B, I, x.stride(0), xT.data_ptr(), ldb, 0, 0, stream),
+                   "lbbnn_transpose_operand")
+        return xT
+
+    def _layers_forward(self, xT, B: int, c: int, wb, out, stream):
+        """One lbbnn_sparse_gather_members FORWARD launch per layer on the stored values ``wb`` (per layer (w, b, ...), rows =
+        members): hidden layers transposed [member][unit][sparse_row_pad(B)] with ReLU, the last written row-major into ``out``
+        (c, B * classes)."""
+        from . import _lib
+        n, dims, ldb = self.n_layers, self.dims, xT.shape[1]
+        a, a_ms = xT, 0
+        for i in range(n):
+            O, last = dims[i + 1], i == n - 1
+            o = out if last else _empty((c, O * ldb), dtype=torch.float32, device=xT.device)
+            ops.sparse_gather_members(_lib.GATHER_FORWARD, self._buf("row_ptr", i), self._buf("col", i), None, wb[i][0], a, o,
+                                      B=B, K=dims[i], N=O, lda=ldb, a_mstride=a_ms, ldo=O if last else ldb,
+                                      o_mstride=out.stride(0) if last else O * ldb, blocks=c, bias=wb[i][1], relu=not last,
+                                      out_rows=last, stream=stream)
+            a, a_ms = o, O * ldb                             # (a keeps the buffer alive until the launch that reads it is queued)
+        return out
+
+    def _head(self, buf, S: int, B: int, log_probs: bool):
+        """The (S, B, C) result from the (S, B * C) logits: at most one launch, whatever S."""
+        C = self.dims[-1]
+        if self.head == "sigmoid":
+            return _binary_members(buf, S, B, C, log_probs)
+        out = buf.view(S, B, C)
+        if self.head == "identity":
+            return out
+        if C <= 64:
+            rows = buf.view(S * B, C)
+            ops.log_softmax_rows(rows, out=rows)             # in place: one thread per row
+            return out
+        return torch.log_softmax(out, dim=-1)
+
+    @torch.no_grad()
+    def ensemble(self, data: torch.Tensor, samples: int = 10, *, max_members: Optional[int] = None, log_probs: bool = False,
+                 keep_weights: bool = False) -> torch.Tensor:
+        """(samples, B, classes) log-probabilities of ``samples`` members, as ``FrozenBaseNetwork.ensemble``.  Member m draws at
+        Philox offset live + m; the live offset advances by ``samples``.  Per chunk of ``max_members`` members (default: all):
+        one draw launch per group of 4 layers and one layer launch per layer, after ONE input transpose per call; then the head,
+        at most one launch.  Chunked and unchunked results are the same bits, and nothing here reads the device.
+        ``keep_weights``: ``self.last_weights`` / ``self.last_biases`` = per layer the (samples, nnz) values in CSR order and the
+        (samples, O) biases."""
+        _check_log_probs(self, log_probs)
+        S, chunk = _member_counts(samples, max_members)
+        x = self._input(data)
+        B, C, dev = x.shape[0], self.dims[-1], x.device
+        st = ops.RngState.get(dev)
+        self.last_weights = self.last_biases = None
+        kept = [] if keep_weights else None
+        with torch.cuda.device(dev):
+            if B == 0:
+                st.advance(S)
+                return torch.zeros((S, 0, 2 if log_probs else C), dtype=torch.float32, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            xT = self._transpose(x, stream)
+            buf = _empty((S, B * C), dtype=torch.float32, device=dev)
+            for m0 in range(0, S, chunk):
+                c = min(chunk, S - m0)
+                wb = self._draw(c, st.t, stream)
+                if kept is not None:
+                    kept.append(wb)
+                self._layers_forward(xT, B, c, wb, buf[m0:m0 + c], stream)
+                st.advance(c)                                # as c single forwards would have
+            if kept is not None:
+                self.last_weights = [torch.cat([k[i][0] for k in kept])[:, :nz] for i, nz in enumerate(self._nnz)]
+                self.last_biases = [torch.cat([k[i][1] for k in kept])[:, :self.dims[i + 1]] for i in range(self.n_layers)]
+            return self._head(buf, S, B, log_probs)
+
+    @torch.no_grad()
+    def forward(self, data: torch.Tensor, sample: bool = False, *, log_probs: bool = False) -> torch.Tensor:
+        """(B, classes) of one member.  ``sample=True``: member 0 of ``ensemble(data, 1)``.  ``sample=False``: the medimean
+        forward (LBBNN-GP-MF.py:236-238) -- the layer launches on ``mean_<i>`` / ``b_mu_<i>`` as a one-member value vector; no
+        draw launch, nothing is drawn and the live offset stays."""
+        _check_log_probs(self, log_probs)
+        if sample:
+            return self.ensemble(data, 1, log_probs=log_probs)[0]
+        x = self._input(data)
+        B, C, dev = x.shape[0], self.dims[-1], x.device
+        if B == 0:
+            return torch.zeros((0, 2 if log_probs else C), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            buf = _empty((1, B * C), dtype=torch.float32, device=dev)
+            wb = [(self._buf("mean", i).view(1, -1), self._buf("b_mu", i).view(1, -1)) for i in range(self.n_layers)]
+            self._layers_forward(self._transpose(x, stream), B, 1, wb, buf, stream)
+            return self._head(buf, 1, B, log_probs)[0]
+
+
 # ----------------------------------------------------------------------------------------- local explanations
 def _check_explainable(fz):
     """``explain`` takes a FrozenNetwork of family LRT or planar MNF; everything else is refused with what to use instead."""
     from . import layers as L
+    if isinstance(fz, SparseFrozenBaseNetwork):
+        raise ValueError("bnn_amd: explain is not built for sparse=True models (its sweep multiplies by dense operands, which a "
+                         "sparse model does not hold); the point explanation of this model, its medimean network: "
+                         "evaluate.explain_ensemble(fz, data, samples=1, weight_noise=False)")
     if isinstance(fz, FrozenBaseNetwork) or _is_base(fz):
         raise TypeError("bnn_amd: explain is not built for the baseline family (its frozen model draws its weights per member); "
                         "explain an LRT / MNF network: evaluate.explain(evaluate.freeze(net, \"mpm\"), data)")
@@ -3091,17 +3348,22 @@ def explain_batches(fz, batches, acc: Optional[ExplanationAccumulator] = None, t
 
 # ----------------------------------------------------------------------------------------- explanations of sampled-weight members
 def _check_ensemble_explainable(fz):
-    """``explain_ensemble`` takes a SparseFrozenNetwork; everything else is refused with what to use instead."""
+    """``explain_ensemble`` takes a SparseFrozenNetwork or a SparseFrozenBaseNetwork; everything else is refused with what to
+    use instead."""
     from . import layers as L
-    if isinstance(fz, SparseFrozenNetwork):
+    if isinstance(fz, (SparseFrozenNetwork, SparseFrozenBaseNetwork)):
         return
     if isinstance(fz, FrozenNetwork):
         raise TypeError("bnn_amd: explain_ensemble explains sampled-weight members of the sparse median probability model (it "
                         "keeps every member's weights, which only the kept weights of a sparse model make small); build it with "
                         "evaluate.freeze(net, \"mpm\", sparse=True).  For a point explanation of this dense model: "
                         "evaluate.explain(fz, data)")
-    if isinstance(fz, FrozenBaseNetwork) or _is_base(fz) or _is_vd(fz):
-        raise TypeError("bnn_amd: explain_ensemble is built for LRT and planar MNF networks: "
+    if isinstance(fz, FrozenBaseNetwork) or _is_base(fz):
+        raise TypeError("bnn_amd: explain_ensemble explains the members of the SPARSE median probability model of a baseline "
+                        "network, got %s; build it with evaluate.freeze_base(net, \"mpm\", sparse=True): "
+                        "evaluate.explain_ensemble(evaluate.freeze_base(net, \"mpm\", sparse=True), data)" % type(fz).__name__)
+    if _is_vd(fz):
+        raise TypeError("bnn_amd: explain_ensemble is built for LRT, planar MNF and baseline networks: "
                         "evaluate.explain_ensemble(evaluate.freeze(net, \"mpm\", sparse=True), data) of an lrt / mnf "
                         "BayesianNetwork, got %s" % type(fz).__name__)
     if isinstance(fz, L._NetworkBase):
@@ -3165,7 +3427,14 @@ def explain_ensemble(fz, data: torch.Tensor, samples: int = 10, *, targets=None,
     ``keep_masks`` (as for ``explain``): ``masks``, per hidden layer the (S, B, O_l) bool pattern h_l > 0 of the members' own
     forward.  A feature without a kept path to the output contributes exactly 0.0 in every member.
 
-    The statistics are over one chunk of members.  Refused before any launch: a model that is not a SparseFrozenNetwork, CPU
+    A baseline model (``freeze_base(net, "mpm", sparse=True)``, a ``SparseFrozenBaseNetwork``): its member is an explicit-weight
+    member already -- per CSR slot ``w = mean + sigma * eps`` with eps at the weight's counter in the FULL network, per unit ``b =
+    b_mu + b_sigma * eps`` (lbbnn_base_sparse_draw_members) -- so from the same Philox offset the members explained are the
+    members ``fz.ensemble`` evaluates: ``weights`` / ``biases`` are its ``last_weights`` / ``last_biases`` and, with an identity
+    head, ``logits`` its result, bit for bit.  There is no z.  ``weight_noise=False`` (``samples`` must be 1) is the medimean
+    network: the family's point explanation.
+
+    The statistics are over one chunk of members.  Refused before any launch: a model that is not a sparse frozen model, CPU
     data, ``samples`` < 1 or ``samples * C'`` > 65535, work buffers (``explain_ensemble_work_bytes``) above ``max_bytes``."""
     import ctypes
     from . import _lib
@@ -3178,10 +3447,11 @@ def explain_ensemble(fz, data: torch.Tensor, samples: int = 10, *, targets=None,
     S = int(samples)
     if S < 1:
         raise ValueError("bnn_amd: explain_ensemble takes samples >= 1, got %r" % (samples,))
+    base = isinstance(fz, SparseFrozenBaseNetwork)
     mnf = fz.family == "mnf"
     if not weight_noise and not mnf and S != 1:
-        raise ValueError("bnn_amd: an LRT model with weight_noise=False has ONE member (the mean network), got samples=%d; pass "
-                         "samples=1, or weight_noise=True for members that differ" % S)
+        raise ValueError("bnn_amd: %s model with weight_noise=False has ONE member (the mean network), got samples=%d; pass "
+                         "samples=1, or weight_noise=True for members that differ" % ("a baseline" if base else "an LRT", S))
     if levels is not None:
         levels = tuple(float(v) for v in levels)
         if not levels or any(not 0.0 < v < 1.0 for v in levels):
@@ -3234,10 +3504,16 @@ def explain_ensemble(fz, data: torch.Tensor, samples: int = 10, *, targets=None,
             off += ops.operand_ld(dims[i])
             if mnf:
                 zs.append(z)
+            if base:
+                continue
             _, col, mean, var = csrs[i]
             layers.append((col, mean, var, fz._buf("bias_mu", i), fz._buf("bias_var", i), z, fz._layer_ids[i], dims[i],
                            pats[i][3]))
-        wb = ops.sparse_draw_members(layers, S, st.t, weight_noise=weight_noise, empty=_empty, stream=stream)
+        if base:
+            # the baseline member IS an explicit-weight member: the draw of fz.ensemble, with the column-by-column copy
+            wb = fz._draw(S, st.t, stream, tpos=[p[3] for p in pats], weight_noise=weight_noise)
+        else:
+            wb = ops.sparse_draw_members(layers, S, st.t, weight_noise=weight_noise, empty=_empty, stream=stream)
         # the live offset moves on in the seed launch, behind the launches that drew (with no rows: a launch of its own)
         advance = S if (mnf or weight_noise) else 0
         if advance and B == 0:
@@ -3246,7 +3522,7 @@ def explain_ensemble(fz, data: torch.Tensor, samples: int = 10, *, targets=None,
         if zs is not None:
             res["z"] = zs
         if keep_weights:
-            res["weights"] = [t[0][:, :layers[i][0].numel()] for i, t in enumerate(wb)]
+            res["weights"] = [t[0][:, :csrs[i][1].numel()] for i, t in enumerate(wb)]
             res["biases"] = [t[1][:, :dims[i + 1]] for i, t in enumerate(wb)]
         if B == 0:
             res.update(logits=torch.zeros((S, 0, C), **f), intercept=torch.zeros((S, 0, Cp), **f),

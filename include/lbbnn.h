@@ -2156,6 +2156,79 @@ int lbbnn_explain_seed(const float* logits, const int64_t* targets, int pred, in
                        uint64_t advance, void* stream);
 int lbbnn_explain_member_stats(const lbbnn_member_stats_args_t* args, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Sparse median-probability model of a baseline LBBNN network (evaluate.freeze_base(net, "mpm", sparse=True)): the kept weights
+ * of lbbnn_base_frozen_operands' LBBNN_GATES_MPM planes alone, in CSR, and every member's explicit weights drawn on that
+ * pattern.  The baseline member IS an explicit-weight member (w = gate * (mu + sigma * eps), per weight), so one draw of
+ * (members, nnz) values serves both the ensemble (lbbnn_sparse_gather_members, LBBNN_GATHER_FORWARD) and its explanation.
+ * Per layer, columns ascending within a row:
+ *     row_ptr (O + 1) int32, the exclusive scan of kept_rows;   col (nnz) int32;   mean (nnz) fp32 = weight_mu;
+ *     sigma (nnz) fp32 = softplus(weight_rho);   b_mu (O) = bias_mu;   b_sigma (O) = softplus(bias_rho).
+ * The keep rule is lbbnn_base_frozen_operands': sigmoid(lambdal) > threshold through its device functions, compared in fp32 (NaN
+ * is never kept) -- NOT lambdal > logit(threshold), the rule of lbbnn_sparse_count, which can differ at the boundary: the pattern
+ * is the dense frozen model's at every threshold.  sigma and not sigma^2 is stored (lbbnn_sparse_pack keeps var for the
+ * local-reparameterisation sums): the draw multiplies by sigma, and sqrt(sigma^2) is not sigma to the bit.
+ *
+ * lbbnn_base_sparse_count: ONE launch for all n <= LBBNN_MAX_LAYERS layers, one wave per weight row: kept_rows[o] = the number of
+ *   kept weights of row o.  Reads lambdal only; the caller scans kept_rows into row_ptr.
+ *   NULL layers / lambdal / kept_rows: LBBNN_E_NULL; n outside [1, LBBNN_MAX_LAYERS], O <= 0, I <= 0: LBBNN_E_SHAPE; a threshold
+ *   outside (0, 1): LBBNN_E_FLAGS; a pointer off a 4-B boundary: LBBNN_E_ALIGN.
+ * lbbnn_base_sparse_pack: ONE launch for all n layers, one wave per weight row: 64 columns at a time the kept ones are compacted in
+ *   ascending order (a ballot of the lanes and the count of the lower kept lanes give each its place) and col / mean / sigma are
+ *   written from row_ptr[o] on, b_mu[o] and b_sigma[o] once per row.  Plain vector stores, no atomics.  Nothing is written at or
+ *   past `nnz` (the capacity of col / mean / sigma) or past row_ptr[o + 1], whatever row_ptr holds.
+ *   NULL layers / mu / rho / lambdal / bias_mu / bias_rho / row_ptr / b_mu / b_sigma, or col / mean / sigma with nnz > 0:
+ *   LBBNN_E_NULL; the shapes above or nnz < 0: LBBNN_E_SHAPE; the threshold: LBBNN_E_FLAGS; a pointer off a 4-B boundary:
+ *   LBBNN_E_ALIGN.
+ *
+ * lbbnn_base_sparse_draw_members: ONE launch for all n <= LBBNN_MAX_LAYERS layers and all members, one wave per CSR row (the
+ *   members on gridDim.y with a stride inside).  Member m draws from {rng[0], rng[1] + m * member_advance}; with r the row of slot k
+ *     w[m * w_mstride + k] = fmaf(sigma[k], eps, mean[k])     eps: stream LBBNN_STREAM_EPS_W * 64 + layer_id, counter
+ *                            (r, col[k] / 4), word col[k] % 4 -- the weight's counter in the FULL network
+ *     b[m * b_mstride + o] = fmaf(b_sigma[o], eps, b_mu[o])   eps: stream LBBNN_STREAM_EPS_B * 64 + layer_id, counter (o / 4, 0),
+ *                            word o % 4
+ *   which are, bit for bit, the weight (r, col[k]) and the bias o of member m of lbbnn_base_frozen_members in LBBNN_GATES_MPM mode
+ *   from the same state (its mu + sigma * eps compiles to this one fused operation).  With tpos / wt (both or neither, else
+ *   LBBNN_E_NULL) the value is stored once more at wt[m * w_mstride + tpos[k]], as lbbnn_sparse_draw_members does.
+ *   LBBNN_F_MEAN_ONLY: w = mean, b = b_mu, nothing is drawn (rng may be NULL).  Every float of a member's block is written:
+ *   w_mstride >= pad4(nnz), b_mstride >= pad4(O), the tail of the last 16-B quad is 0.  col is clamped into [0, I), tpos into
+ *   [0, nnz), row_ptr into [0, nnz]: never followed outside.  A layer with nnz == 0 is legal (col / mean / sigma / w may be NULL).
+ *   NULL layers, row_ptr / b_mu / b_sigma / b, or col / mean / sigma / w with nnz > 0: LBBNN_E_NULL; n outside [1,
+ *   LBBNN_MAX_LAYERS], members outside [1, 65535], O < 1, I < 1, nnz < 0, a member stride below its padded row: LBBNN_E_SHAPE;
+ *   flags other than 0 | LBBNN_F_MEAN_ONLY: LBBNN_E_FLAGS; rng == NULL without LBBNN_F_MEAN_ONLY: LBBNN_E_NOISE; w / wt / b off a
+ *   16-B boundary or a stride of theirs not a multiple of 4, any other pointer off 4 B (rng: 8 B): LBBNN_E_ALIGN.  The caller
+ *   advances rng afterwards. */
+typedef struct lbbnn_base_sparse_desc {
+    const float *mu, *rho, *lambdal;                 /* (O, I)                                  */
+    const float *bias_mu, *bias_rho;                 /* (O)                                     */
+    const int32_t* row_ptr;                          /* (O + 1); lbbnn_base_sparse_pack         */
+    int32_t* col;                                    /* (nnz);   lbbnn_base_sparse_pack         */
+    float *mean, *sigma;                             /* (nnz);   lbbnn_base_sparse_pack         */
+    float *b_mu, *b_sigma;                           /* (O);     lbbnn_base_sparse_pack         */
+    int32_t* kept_rows;                              /* (O);     lbbnn_base_sparse_count        */
+    int O, I;
+    int nnz;                                         /* capacity of col / mean / sigma          */
+} lbbnn_base_sparse_desc_t;
+
+typedef struct lbbnn_base_sparse_draw_desc {
+    const int32_t *row_ptr, *col;                    /* (O + 1), (nnz)                          */
+    const float *mean, *sigma;                       /* (nnz)                                   */
+    const float *b_mu, *b_sigma;                     /* (O)                                     */
+    const int32_t* tpos;                             /* (nnz) or NULL: place of slot k in wt    */
+    float* wt;                                       /* [members][w_mstride] or NULL, with tpos */
+    float* w;                                        /* [members][w_mstride]                    */
+    int64_t w_mstride;
+    float* b;                                        /* [members][b_mstride]                    */
+    int64_t b_mstride;
+    int O, I, nnz;
+    uint32_t layer_id;
+} lbbnn_base_sparse_draw_desc_t;
+
+int lbbnn_base_sparse_count(const lbbnn_base_sparse_desc_t* layers, int n, float threshold, void* stream);
+int lbbnn_base_sparse_pack(const lbbnn_base_sparse_desc_t* layers, int n, float threshold, void* stream);
+int lbbnn_base_sparse_draw_members(const lbbnn_base_sparse_draw_desc_t* layers, int n, int members, const uint64_t* rng,
+                                   uint64_t member_advance, int flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
