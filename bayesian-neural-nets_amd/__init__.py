@@ -12,5 +12,6 @@ from . import base, evaluate, flows, graphs, losses, lrt, mnf, optim, parallel, 
 from .losses import TrainMonitor, elbo_bce_loss, elbo_gaussian_loss, elbo_loss  # noqa: F401
 from .evaluate import FrozenNetwork, freeze  # noqa: F401
 from .evaluate import FrozenBaseNetwork, SparseFrozenBaseNetwork, freeze_base  # noqa: F401
+from .evaluate import ThresholdSweep, sweep_batches, threshold_sweep  # noqa: F401
 
 __version__ = "0.1.0"

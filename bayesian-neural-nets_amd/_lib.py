@@ -230,6 +230,16 @@ class SparseDesc(ctypes.Structure):
                                    "kept_rows")] + [("O", c_i), ("I", c_i), ("nnz", c_i), ("cut", ctypes.c_float)]
 
 
+MAX_LEVELS = 16           # LBBNN_MAX_LEVELS: thresholds of one sweep
+
+
+class SparseLevelsDesc(ctypes.Structure):
+    """lbbnn_sparse_levels_desc_t"""
+    _fields_ = [(n, c_p) for n in ("weight_mu", "weight_rho", "lambdal", "bias_rho", "row_ptr", "col", "mean", "var", "bias_var",
+                                   "kept_rows")] + [("O", c_i), ("I", c_i), ("nnz", c_i), ("levels", c_i),
+                                                    ("cut", ctypes.c_float * MAX_LEVELS)]
+
+
 class SparseDrawDesc(ctypes.Structure):
     """lbbnn_sparse_draw_desc_t"""
     _fields_ = [(n, c_p) for n in ("col", "mean", "var", "bias_mu", "bias_var", "z")] + [("z_mstride", c_i64), ("tpos", c_p), ("wt", c_p), ("w", c_p),
@@ -537,6 +547,10 @@ SIGNATURES = {
     "lbbnn_frozen_members_z": (c_i, [ctypes.POINTER(FrozenDesc), c_i, c_i, c_p, c_u64, c_p]),
     "lbbnn_sparse_layer_members": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_i64, c_p, c_i64, c_p, c_u32, c_i64, c_u64,
                                          c_p, c_i, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "lbbnn_sparse_count_levels": (c_i, [ctypes.POINTER(SparseLevelsDesc), c_i, c_p]),
+    "lbbnn_sparse_pack_levels": (c_i, [ctypes.POINTER(SparseLevelsDesc), c_i, c_p]),
+    "lbbnn_sparse_layer_levels": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_i64, c_p, c_i64, c_p, c_u32, c_i64, c_u64,
+                                        c_p, c_i, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     "lbbnn_base_frozen_operands": (c_i, [ctypes.POINTER(BaseFrozenDesc), ctypes.POINTER(CompactMap), c_i, c_i, ctypes.c_float, c_p]),
     "lbbnn_base_frozen_members": (c_i, [ctypes.POINTER(BaseFrozenDesc), ctypes.POINTER(CompactMap), c_i, c_i, c_i, ctypes.c_float,
                                         ctypes.POINTER(c_p), ctypes.POINTER(c_p), ctypes.POINTER(c_p), c_p, c_u64, c_p]),

@@ -116,6 +116,117 @@ int sparse_rows_impl(const lbbnn_sparse_desc_t* L, int n, bool pack, void* strea
     return (int)hipGetLastError();
 }
 
+// The threshold sweep's count / pack (lbbnn_sparse_count_levels / _pack_levels): sparse_rows_kernel for K ascending cuts at
+// once.  A lane loads its lambdal ONCE per 64 columns and compares it with every cut (kernel arguments: scalar registers); the
+// ballot of level j is that level's kept set, and the running count of (level, row) is wave-uniform.  Pack: a lane kept at level 0
+// (the loosest cut: every other level's kept set lies inside it) loads mu / rho once and computes sigma^2 once, then stores the
+// same three words into the segment of every level that keeps it, at base_j + run_j + (kept lanes below it at level j).  The
+// unrolled level loop keeps run / base / end in registers (constant indices); levels past K do nothing.
+struct SparseLevelsLayer {
+    const float* mu; const float* rho; const float* lambdal; const float* bias_rho;
+    const int32_t* row_ptr; int32_t* col; float* mean; float* var; float* bias_var; int32_t* kept_rows;
+    int O, I, nnz, K;
+    float cut[LBBNN_MAX_LEVELS];
+};
+struct SparseLevelsBatch { SparseLevelsLayer l[LBBNN_MAX_LAYERS]; int wg_end[LBBNN_MAX_LAYERS]; int n; };
+
+template <bool kPack>
+__global__ __launch_bounds__(kSpNT) void sparse_levels_kernel(const SparseLevelsBatch bt_) {
+    const LBBNN_CONST_AS SparseLevelsBatch* bt = kernarg_as<SparseLevelsBatch>();
+    int wg0;
+    const int li = layer_of(bt, wg0);
+    const LBBNN_CONST_AS SparseLevelsLayer& a = bt->l[li];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int o = kSpRows * ((int)blockIdx.x - wg0) + wv;
+    if (o >= a.O) return;                                                 // (whole waves leave: no barrier below)
+    const int I = a.I, K = a.K;
+    const size_t rowoff = (size_t)o * I;
+    int run[LBBNN_MAX_LEVELS], base[LBBNN_MAX_LEVELS], end[LBBNN_MAX_LEVELS];
+#pragma unroll
+    for (int j = 0; j < LBBNN_MAX_LEVELS; ++j) {
+        run[j] = base[j] = end[j] = 0;
+        if (kPack && j < K) {
+            // the slots of (level j, row o), inside [0, nnz] whatever row_ptr holds
+            base[j] = clampi(a.row_ptr[(size_t)j * a.O + o], 0, a.nnz);
+            end[j] = clampi(a.row_ptr[(size_t)j * a.O + o + 1], base[j], a.nnz);
+        }
+    }
+    for (int c0 = 0; c0 < I; c0 += 64) {
+        const int c = c0 + lane;
+        const bool in = c < I;
+        const float lam = in ? a.lambdal[rowoff + c] : 0.f;
+        float mu = 0.f, var = 0.f;
+        if constexpr (kPack) {
+            if (in && lam > a.cut[0]) {                                    // fp32 compare: NaN is never kept
+                const float sigma = k1_sigma(a.rho[rowoff + c]);
+                mu = a.mu[rowoff + c];
+                var = sigma * sigma;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < LBBNN_MAX_LEVELS; ++j) {
+            if (j >= K) continue;                                         // wave-uniform
+            const bool kept = in && lam > a.cut[j];
+            const unsigned long long m = __ballot(kept);
+            if constexpr (kPack) {
+                const int below = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                const int pos = base[j] + run[j] + below;
+                if (kept && pos < end[j]) {
+                    a.col[pos] = c;
+                    a.mean[pos] = mu;
+                    a.var[pos] = var;
+                }
+            }
+            run[j] += __popcll(m);
+        }
+    }
+    if (lane == 0) {
+        if constexpr (kPack) {
+            const float sb = softplus_ref(a.bias_rho[o]);
+            a.bias_var[o] = sb * sb;                  // bias.sigma**2, LBBNN-GP-MF-LRT.py:173 (never gated)
+        } else {
+#pragma unroll
+            for (int j = 0; j < LBBNN_MAX_LEVELS; ++j) if (j < K) a.kept_rows[(size_t)j * a.O + o] = run[j];
+        }
+    }
+}
+
+int sparse_levels_impl(const lbbnn_sparse_levels_desc_t* L, int n, bool pack, void* stream) {
+    if (!L) return LBBNN_E_NULL;
+    if (n <= 0 || n > LBBNN_MAX_LAYERS) return LBBNN_E_SHAPE;
+    SparseLevelsBatch bt = {};
+    int wgs = 0;
+    for (int i = 0; i < n; ++i) {
+        const lbbnn_sparse_levels_desc_t& d = L[i];
+        if (!d.lambdal) return LBBNN_E_NULL;
+        if (pack) {
+            if (!d.weight_mu || !d.weight_rho || !d.bias_rho || !d.row_ptr || !d.bias_var) return LBBNN_E_NULL;
+            if (d.nnz > 0 && (!d.col || !d.mean || !d.var)) return LBBNN_E_NULL;
+        } else if (!d.kept_rows) return LBBNN_E_NULL;
+        if (d.O <= 0 || d.I <= 0 || (pack && d.nnz < 0)) return LBBNN_E_SHAPE;
+        if (d.levels < 1 || d.levels > LBBNN_MAX_LEVELS) return LBBNN_E_SHAPE;
+        for (int j = 0; j < d.levels; ++j)            // finite and strictly ascending (a NaN fails `< INFINITY`)
+            if (!(fabsf(d.cut[j]) < INFINITY) || (j && !(d.cut[j - 1] < d.cut[j]))) return LBBNN_E_SHAPE;
+        if (!aligned4(d.lambdal)) return LBBNN_E_ALIGN;
+        if (pack) {
+            if (!aligned4(d.weight_mu) || !aligned4(d.weight_rho) || !aligned4(d.bias_rho) || !aligned4(d.row_ptr) ||
+                !aligned4(d.col) || !aligned4(d.mean) || !aligned4(d.var) || !aligned4(d.bias_var)) return LBBNN_E_ALIGN;
+        } else if (!aligned4(d.kept_rows)) return LBBNN_E_ALIGN;
+        SparseLevelsLayer& a = bt.l[i];
+        a.mu = d.weight_mu; a.rho = d.weight_rho; a.lambdal = d.lambdal; a.bias_rho = d.bias_rho;
+        a.row_ptr = d.row_ptr; a.col = d.col; a.mean = d.mean; a.var = d.var; a.bias_var = d.bias_var; a.kept_rows = d.kept_rows;
+        a.O = d.O; a.I = d.I; a.nnz = pack ? d.nnz : 0; a.K = d.levels;
+        for (int j = 0; j < d.levels; ++j) a.cut[j] = d.cut[j];
+        wgs += (d.O + kSpRows - 1) / kSpRows;
+        bt.wg_end[i] = wgs;
+    }
+    bt.n = n;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (pack) hipLaunchKernelGGL(sparse_levels_kernel<true>, dim3(wgs), dim3(kSpNT), 0, s, bt);
+    else hipLaunchKernelGGL(sparse_levels_kernel<false>, dim3(wgs), dim3(kSpNT), 0, s, bt);
+    return (int)hipGetLastError();
+}
+
 struct SpArgs {
     const int32_t* row_ptr; const int32_t* col; const float* mean; const float* var;
     const float* bias_mu; const float* bias_var;
@@ -124,6 +235,7 @@ struct SpArgs {
     const uint64_t* rng; uint32_t rng_stream; long long row_offset; unsigned long long m_adv;
     float* out; long long o_ms; int ldo;
     int B, I, O, nnz, relu, lsm, out_rows;
+    int S;                                                    // kLv: members (draws) per level
 };
 
 // One nonzero of a unit's CSR row for the lane's rows: the column index is taken inside [0, I) whatever the array holds
@@ -145,7 +257,11 @@ struct SpArgs {
 // kR: batch rows per lane (1: tiles of 64 rows; 2: tiles of 128, lane l owns rows 2l and 2l + 1 of the tile).  The four waves
 // of a workgroup take the same row tile and four neighbouring unit groups; a <= 16-unit head with log_softmax is one
 // workgroup per tile, and its waves hand each other the tile's logits through LDS.
-template <bool kMeanOnly, bool kZ, int kR>
+// kLv: a threshold sweep's launch (lbbnn_sparse_layer_levels) -- member blockIdx.z is level lv = z / S under draw dr = z % S:
+// the level picks the row pointers (row_ptr + lv * O), the draw picks z and the Philox offset; both come from blockIdx.z and a
+// kernel argument alone, so they live in scalar registers and everything indexed by them stays a scalar load.  !kLv: lv = 0,
+// dr = the member -- the plain kernel, instruction for instruction.
+template <bool kMeanOnly, bool kZ, int kR, bool kLv>
 __global__ __launch_bounds__(256) void sparse_layer_kernel(const SpArgs a) {
 #pragma clang fp contract(off)
     typedef SpRows<kR> R;
@@ -153,6 +269,8 @@ __global__ __launch_bounds__(256) void sparse_layer_kernel(const SpArgs a) {
     __shared__ float logits[16][64 * kR];
     const int lane = threadIdx.x & 63, wv = uniform(threadIdx.x >> 6);
     const int mem = blockIdx.z;
+    const int lv = kLv ? mem / a.S : 0, dr = kLv ? mem - lv * a.S : mem;
+    const int32_t* row_ptr = a.row_ptr + (size_t)lv * a.O;
     const int b = ((int)blockIdx.y * 64 + lane) * kR;                     // the lane's first row
     const bool live = b < a.B;
     // a lane past the batch computes rows 0 .. kR - 1 again (in bounds, never stored): no lane-dependent branch in the loop.
@@ -161,9 +279,9 @@ __global__ __launch_bounds__(256) void sparse_layer_kernel(const SpArgs a) {
     const __amdgpu_buffer_rsrc_t act = __builtin_amdgcn_make_buffer_rsrc((void*)(a.a + (size_t)mem * a.a_ms), 0, a.a_bytes, 0x00020000);
     const unsigned lda4 = 4u * (unsigned)a.lda, imax = (unsigned)a.I - 1u;
     const unsigned boff = live ? 4u * (unsigned)b : 0u;
-    const float* z = kZ ? a.z + (size_t)mem * a.z_ms : nullptr;
+    const float* z = kZ ? a.z + (size_t)dr * a.z_ms : nullptr;
     uint64_t seed = 0, offs = 0;
-    if (!kMeanOnly) { seed = a.rng[0]; offs = a.rng[1] + (uint64_t)mem * a.m_adv; }
+    if (!kMeanOnly) { seed = a.rng[0]; offs = a.rng[1] + (uint64_t)dr * a.m_adv; }
     const int o0 = 4 * ((int)blockIdx.x * 4 + wv);
     const bool any = o0 < a.O;                                            // wave-uniform
     float res[kR][4];
@@ -178,8 +296,8 @@ __global__ __launch_bounds__(256) void sparse_layer_kernel(const SpArgs a) {
             am[r] = R::splat(0.f); av[r] = R::splat(0.f);
             const int o = o0 + r;
             if (o >= a.O) continue;                                       // wave-uniform
-            const int k0 = uniform(clampi(a.row_ptr[o], 0, a.nnz));
-            const int k1 = uniform(clampi(a.row_ptr[o + 1], k0, a.nnz));
+            const int k0 = uniform(clampi(row_ptr[o], 0, a.nnz));
+            const int k1 = uniform(clampi(row_ptr[o + 1], k0, a.nnz));
             int k = k0;
             rows_t x[kSpChunk];
             float w[kSpChunk], v[kSpChunk];
@@ -263,36 +381,30 @@ int sparse_rows_per_lane(const SpArgs& a) {
     return a.B > 64 ? 2 : 1;
 }
 
-template <bool kMeanOnly, bool kZ>
+template <bool kMeanOnly, bool kZ, bool kLv>
 void launch_sparse_layer(const SpArgs& a, int members, hipStream_t s) {
     const dim3 block(256);
     const unsigned groups = (unsigned)((a.O + 15) / 16);                  // (1 with log_softmax: O <= 16)
     if (sparse_rows_per_lane(a) == 2)
-        hipLaunchKernelGGL((sparse_layer_kernel<kMeanOnly, kZ, 2>), dim3(groups, (unsigned)((a.B + 127) / 128), members), block, 0, s, a);
+        hipLaunchKernelGGL((sparse_layer_kernel<kMeanOnly, kZ, 2, kLv>), dim3(groups, (unsigned)((a.B + 127) / 128), members), block, 0, s, a);
     else
-        hipLaunchKernelGGL((sparse_layer_kernel<kMeanOnly, kZ, 1>), dim3(groups, (unsigned)((a.B + 63) / 64), members), block, 0, s, a);
+        hipLaunchKernelGGL((sparse_layer_kernel<kMeanOnly, kZ, 1, kLv>), dim3(groups, (unsigned)((a.B + 63) / 64), members), block, 0, s, a);
 }
 
-}  // namespace
-
-extern "C" int lbbnn_sparse_count(const lbbnn_sparse_desc_t* L, int n, void* stream) {
-    return sparse_rows_impl(L, n, false, stream);
-}
-
-extern "C" int lbbnn_sparse_pack(const lbbnn_sparse_desc_t* L, int n, void* stream) {
-    return sparse_rows_impl(L, n, true, stream);
-}
-
-extern "C" int lbbnn_sparse_layer_members(const int32_t* row_ptr, const int32_t* col, const float* mean, const float* var,
-                                          int nnz, const float* bias_mu, const float* bias_var, const float* a, int lda,
-                                          int64_t a_mstride, const float* z, int64_t z_mstride, const uint64_t* rng,
-                                          uint32_t rng_stream, int64_t row_offset, uint64_t member_advance, float* out,
-                                          int ldo, int64_t o_mstride, int out_rows, int B, int I, int O, int flags,
-                                          int members, void* stream) {
+// Both layer entry points.  !lv: lbbnn_sparse_layer_members, `per_level` members of the one model (levels = 1); lv:
+// lbbnn_sparse_layer_levels, levels * per_level members of which `per_level` differ in their draws.
+int sparse_layer_impl(const int32_t* row_ptr, const int32_t* col, const float* mean, const float* var, int nnz,
+                      const float* bias_mu, const float* bias_var, const float* a, int lda, int64_t a_mstride, const float* z,
+                      int64_t z_mstride, const uint64_t* rng, uint32_t rng_stream, int64_t row_offset, uint64_t member_advance,
+                      float* out, int ldo, int64_t o_mstride, int out_rows, int B, int I, int O, int flags, bool lv,
+                      int levels, int per_level, void* stream) {
     if (B == 0) return 0;
     if (!row_ptr || !bias_mu || !bias_var || !a || !out) return LBBNN_E_NULL;
     if (nnz > 0 && (!col || !mean || !var)) return LBBNN_E_NULL;
-    if (B < 0 || (long long)B > 65535LL * 64 || I <= 0 || O <= 0 || nnz < 0 || members < 1 || members > 65535) return LBBNN_E_SHAPE;
+    if (levels < 1 || levels > LBBNN_MAX_LEVELS) return LBBNN_E_SHAPE;
+    if (per_level < 1 || per_level > 65535) return LBBNN_E_SHAPE;
+    const int members = levels * per_level;                    // (at most 16 * 65535: no overflow)
+    if (B < 0 || (long long)B > 65535LL * 64 || I <= 0 || O <= 0 || nnz < 0 || members > 65535) return LBBNN_E_SHAPE;
     if (lda < B || ldo < (out_rows ? O : B) || a_mstride < 0 || z_mstride < 0 || o_mstride < 0) return LBBNN_E_SHAPE;
     // the kernel addresses a member's input as a buffer: I lines of B rows -- of B + 1 where lda has room for the pair of an
     // odd last row (the two-row form reads it and drops it)
@@ -301,8 +413,9 @@ extern "C" int lbbnn_sparse_layer_members(const int32_t* row_ptr, const int32_t*
     if (members > 1) {
         // members may share an input (a_mstride == 0: the first layer's x^T), never an output
         const long long need = out_rows ? (long long)(B - 1) * ldo + O : (long long)(O - 1) * ldo + B;
-        if (o_mstride < need || (a_mstride && a_mstride < (long long)(I - 1) * lda + B) || (z && z_mstride < I)) return LBBNN_E_SHAPE;
+        if (o_mstride < need || (a_mstride && a_mstride < (long long)(I - 1) * lda + B)) return LBBNN_E_SHAPE;
     }
+    if (per_level > 1 && z && z_mstride < I) return LBBNN_E_SHAPE;         // (the levels of one draw share its z)
     const bool mean_only = (flags & LBBNN_F_MEAN_ONLY) != 0, lsm = (flags & LBBNN_F_LOG_SOFTMAX) != 0;
     if (flags & ~(LBBNN_F_RELU | LBBNN_F_MEAN_ONLY | LBBNN_F_LOG_SOFTMAX)) return LBBNN_E_FLAGS;
     if (lsm && (O > 16 || (flags & LBBNN_F_RELU) || !out_rows)) return LBBNN_E_FLAGS;
@@ -315,8 +428,58 @@ extern "C" int lbbnn_sparse_layer_members(const int32_t* row_ptr, const int32_t*
     k.rng = rng; k.rng_stream = rng_stream; k.row_offset = row_offset; k.m_adv = member_advance;
     k.out = out; k.o_ms = o_mstride; k.ldo = ldo;
     k.B = B; k.I = I; k.O = O; k.nnz = nnz; k.relu = (flags & LBBNN_F_RELU) ? 1 : 0; k.lsm = lsm ? 1 : 0; k.out_rows = out_rows ? 1 : 0;
+    k.S = per_level;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (mean_only) { if (z) launch_sparse_layer<true, true>(k, members, s); else launch_sparse_layer<true, false>(k, members, s); }
-    else { if (z) launch_sparse_layer<false, true>(k, members, s); else launch_sparse_layer<false, false>(k, members, s); }
+    const int form = (mean_only ? 4 : 0) | (z ? 2 : 0) | (lv ? 1 : 0);
+    switch (form) {
+        case 0: launch_sparse_layer<false, false, false>(k, members, s); break;
+        case 1: launch_sparse_layer<false, false, true>(k, members, s); break;
+        case 2: launch_sparse_layer<false, true, false>(k, members, s); break;
+        case 3: launch_sparse_layer<false, true, true>(k, members, s); break;
+        case 4: launch_sparse_layer<true, false, false>(k, members, s); break;
+        case 5: launch_sparse_layer<true, false, true>(k, members, s); break;
+        case 6: launch_sparse_layer<true, true, false>(k, members, s); break;
+        default: launch_sparse_layer<true, true, true>(k, members, s); break;
+    }
     return (int)hipGetLastError();
 }
+
+}  // namespace
+
+extern "C" int lbbnn_sparse_count(const lbbnn_sparse_desc_t* L, int n, void* stream) {
+    return sparse_rows_impl(L, n, false, stream);
+}
+
+extern "C" int lbbnn_sparse_pack(const lbbnn_sparse_desc_t* L, int n, void* stream) {
+    return sparse_rows_impl(L, n, true, stream);
+}
+
+extern "C" int lbbnn_sparse_count_levels(const lbbnn_sparse_levels_desc_t* L, int n, void* stream) {
+    return sparse_levels_impl(L, n, false, stream);
+}
+
+extern "C" int lbbnn_sparse_pack_levels(const lbbnn_sparse_levels_desc_t* L, int n, void* stream) {
+    return sparse_levels_impl(L, n, true, stream);
+}
+
+extern "C" int lbbnn_sparse_layer_members(const int32_t* row_ptr, const int32_t* col, const float* mean, const float* var,
+                                          int nnz, const float* bias_mu, const float* bias_var, const float* a, int lda,
+                                          int64_t a_mstride, const float* z, int64_t z_mstride, const uint64_t* rng,
+                                          uint32_t rng_stream, int64_t row_offset, uint64_t member_advance, float* out,
+                                          int ldo, int64_t o_mstride, int out_rows, int B, int I, int O, int flags,
+                                          int members, void* stream) {
+    return sparse_layer_impl(row_ptr, col, mean, var, nnz, bias_mu, bias_var, a, lda, a_mstride, z, z_mstride, rng, rng_stream,
+                             row_offset, member_advance, out, ldo, o_mstride, out_rows, B, I, O, flags, false, 1, members, stream);
+}
+
+extern "C" int lbbnn_sparse_layer_levels(const int32_t* row_ptr, const int32_t* col, const float* mean, const float* var,
+                                         int nnz, const float* bias_mu, const float* bias_var, const float* a, int lda,
+                                         int64_t a_mstride, const float* z, int64_t z_mstride, const uint64_t* rng,
+                                         uint32_t rng_stream, int64_t row_offset, uint64_t member_advance, float* out,
+                                         int ldo, int64_t o_mstride, int out_rows, int B, int I, int O, int flags, int levels,
+                                         int members_per_level, void* stream) {
+    return sparse_layer_impl(row_ptr, col, mean, var, nnz, bias_mu, bias_var, a, lda, a_mstride, z, z_mstride, rng, rng_stream,
+                             row_offset, member_advance, out, ldo, o_mstride, out_rows, B, I, O, flags, true, levels,
+                             members_per_level, stream);
+}
+

@@ -51,6 +51,11 @@ call returns every input's contribution ``J[b, c, i] * x[b, i]``, the bias path 
 ``ExplanationAccumulator`` / ``explain_batches`` (lbbnn_explain_totals) average them over a pass on the device.
 ``explain_ensemble`` (lbbnn_sparse_draw_members / _gather_members, lbbnn_explain_seed / _member_stats) explains sampled-weight
 members of the sparse median probability model and returns the mean, spread and sign probability of every contribution over them.
+
+``threshold_sweep(net, thresholds)`` -> ``ThresholdSweep`` answers where to prune: the sparse models of up to 16 ascending
+thresholds from one count and one pack launch (lbbnn_sparse_count_levels / _pack_levels), evaluated K x S members a layer launch
+(lbbnn_sparse_layer_levels) under draws common to the levels; ``sweep_batches`` is the evaluation pass over all of them, and
+``sw.model(j)`` hands the chosen level on as a ``SparseFrozenNetwork``.
 """
 import math
 from typing import Dict, List, Optional, Tuple
@@ -2443,6 +2448,324 @@ def _freeze_sparse(net, layers, family, threshold) -> SparseFrozenNetwork:
     fz = SparseFrozenNetwork(net.dims, family, threshold, device=layers[0].weight_mu.device, head=net.head)
     fz.eval()
     return fz._bind(net)
+
+
+# ----------------------------------------------------------------------------------------- threshold sweep
+class ThresholdSweep(nn.Module):
+    """The sparse median probability models of K ascending thresholds in one set of buffers (``threshold_sweep(net,
+    thresholds)``; LRT and planar MNF networks, every head, 1 to 16 layers; buffers only, fp32 whatever the precision setting).
+
+    Per layer i with O rows: ``kept_rows_<i>`` (K, O) int32, ``row_ptr_<i>`` (K * O + 1) int32 -- the exclusive scan of
+    kept_rows level after level -- and ``col_<i>`` / ``mean_<i>`` / ``var_<i>``, in which level j, row o owns the slots
+    [row_ptr[j * O + o], row_ptr[j * O + o + 1]); ``bias_mu_<i>``, ``bias_var_<i>`` and the q0 / planar-flow copies of an MNF
+    layer are shared by the levels.  Level j's segment holds the bits ``freeze(net, "mpm", threshold=thresholds[j],
+    sparse=True)`` packs (lbbnn_sparse_count_levels / _pack_levels: every parameter read once, ONE host read of the
+    (layers, K) level totals).
+
+    ``ensemble(x, S)`` -> (K, S, B, classes): one lbbnn_frozen_members_z launch for S draws (MNF), one input transpose, and one
+    lbbnn_sparse_layer_levels launch per layer for all K * S members.  Member (j, s) is bit for bit member s of level j's own
+    model from the same Philox offset: draw s is common to the levels (common random numbers), and the live offset advances by
+    S, as ONE model's ensemble advances it.  ``sw(x)`` -> (K, B, classes): the posterior-mean forward of every level; an MNF
+    network draws one z, shared by the levels, and advances the offset by 1; an LRT network draws nothing.
+    ``model(j)``: level j as a ``SparseFrozenNetwork`` on this sweep's value buffers.
+
+    ``thresholds`` / ``cuts``: the K thresholds and their fp32 logits; ``nnz``: K host ints, the kept weights of each level;
+    ``kept``: (K, layers) int64 on the device; ``density``: (K,) float64 on the device, kept / all weights -- the thesis'
+    density per level; ``operand_bytes``: what the layer launches read of the sweep."""
+
+    def __init__(self, dims, thresholds, family: str = "lrt", device=None, head: str = "log_softmax"):
+        super().__init__()
+        from . import _lib
+        if head not in ("log_softmax", "sigmoid", "identity"):
+            raise ValueError("bnn_amd: head must be 'log_softmax', 'sigmoid' or 'identity', got %r" % (head,))
+        if family not in ("lrt", "mnf"):
+            raise ValueError("bnn_amd: family must be 'lrt' or 'mnf', got %r" % (family,))
+        self.thresholds = tuple(float(t) for t in thresholds)
+        if not 1 <= len(self.thresholds) <= _lib.MAX_LEVELS:
+            raise ValueError("bnn_amd: a threshold sweep takes 1 to %d thresholds, got %d" % (_lib.MAX_LEVELS, len(self.thresholds)))
+        self.cuts = tuple(_cut(t) for t in self.thresholds)
+        for j in range(1, len(self.cuts)):
+            if not self.thresholds[j - 1] < self.thresholds[j]:
+                raise ValueError("bnn_amd: the thresholds of a sweep ascend strictly, got %r" % (self.thresholds,))
+            if not self.cuts[j - 1] < self.cuts[j]:
+                raise ValueError("bnn_amd: thresholds %r and %r have the same fp32 cut logit(threshold) = %r: they are one level"
+                                 % (self.thresholds[j - 1], self.thresholds[j], self.cuts[j]))
+        self.dims = self.full_dims = tuple(int(d) for d in dims)
+        if head in ("sigmoid", "identity") and self.dims[-1] > 16:
+            raise ValueError("bnn_amd: %s head takes at most 16 output units, got dims[-1] = %d"
+                             % ("a sigmoid" if head == "sigmoid" else "an identity", self.dims[-1]))
+        self.family, self.head = family, head
+        self._src = [None]              # the source network, in a list so that it is not registered as a submodule
+        self._layer_ids, self._row_offsets, self._T = [], [], []
+        self._tot = []                  # [layer][level] kept weights, host ints: the sizes and bases of the segments
+        self._level0 = [None]           # model(0), which draws z and lays out x for every level (dropped when the buffers move)
+        K = len(self.cuts)
+        for i in range(len(self.dims) - 1):
+            self.register_buffer("kept_rows_%d" % i, torch.zeros((K, self.dims[i + 1]), dtype=torch.int32, device=device))
+        self.register_buffer("kept", torch.zeros((K, len(self.dims) - 1), dtype=torch.int64, device=device))
+
+    def extra_repr(self) -> str:
+        head = ", head=%s" % self.head if self.head != "log_softmax" else ""
+        return "dims=%s, family=%s, thresholds=%s%s, sparse, nnz=%s" % (self.dims, self.family, self.thresholds, head, self.nnz)
+
+    @property
+    def n_layers(self) -> int:
+        return len(self.dims) - 1
+
+    def _buf(self, name: str, i: int) -> torch.Tensor:
+        return getattr(self, "%s_%d" % (name, i))
+
+    @property
+    def nnz(self) -> List[int]:
+        """Kept weights of each level, over every layer."""
+        return [sum(t[j] for t in self._tot) for j in range(len(self.cuts))]
+
+    @property
+    def density(self) -> torch.Tensor:
+        """(K,) float64 on the device: kept weights / all weights of each level."""
+        kept = self.kept.sum(1).double()
+        # (a tensor divisor: dividing by a Python number multiplies by its rounded reciprocal on the device)
+        return kept / torch.full_like(kept, sum(self.dims[i] * self.dims[i + 1] for i in range(self.n_layers)))
+
+    @property
+    def operand_bytes(self) -> int:
+        """Bytes of everything the layer launches read of this sweep: row_ptr, col, mean, var, bias_mu and bias_var."""
+        K = len(self.cuts)
+        return sum(4 * (K * self.dims[i + 1] + 1) + 12 * sum(t) + 8 * self.dims[i + 1] for i, t in enumerate(self._tot))
+
+    @torch.no_grad()
+    def _bind(self, net):
+        """Count, scan, size (the ONE host read), pack: two batched launches per layer group and one cumsum per layer."""
+        from . import _lib
+        layers = net._layers()
+        dev = layers[0].weight_mu.device
+        f = dict(dtype=torch.float32, device=dev)
+        n, K = self.n_layers, len(self.cuts)
+        self._src = [net]
+        self._layer_ids = [int(l._layer_id) for l in layers]
+        self._row_offsets = [int(l.row_offset) for l in layers]
+        descs = (_lib.SparseLevelsDesc * n)()
+        dst, src = [], []
+        for i, l in enumerate(layers):
+            O, If = self.dims[i + 1], self.dims[i]
+            for name in ("weight_mu", "weight_rho", "lambdal"):
+                if not getattr(l, name).is_contiguous():
+                    raise RuntimeError("bnn_amd: %s of layer %d is not contiguous" % (name, i + 1))
+            for name in ("bias_var", "bias_mu"):
+                self.register_buffer("%s_%d" % (name, i), _empty((O,), **f))
+            dst.append(self._buf("bias_mu", i)); src.append(l.bias_mu.detach())
+            T = len(l.z_flow.transforms) if l._mnf else 0
+            self._T.append(T)
+            if l._mnf:
+                for name, shape in (("q0_mean", (If,)), ("q0_log_var", (If,)), ("flow_u", (T, If)), ("flow_w", (T, If)),
+                                    ("flow_b", (T, 1))):
+                    self.register_buffer("%s_%d" % (name, i), _empty(shape, **f))
+                dst += [self._buf("q0_mean", i), self._buf("q0_log_var", i)]
+                src += [l.q0_mean.detach(), l.q0_log_var.detach()]
+                for t, tr in enumerate(l.z_flow.transforms):
+                    dst += [self._buf("flow_u", i)[t], self._buf("flow_w", i)[t], self._buf("flow_b", i)[t]]
+                    src += [tr.u.detach().reshape(-1), tr.w.detach().reshape(-1), tr.bias.detach().reshape(-1)]
+            d = descs[i]
+            d.weight_mu, d.weight_rho, d.lambdal = l.weight_mu.data_ptr(), l.weight_rho.data_ptr(), l.lambdal.data_ptr()
+            d.bias_rho = l.bias_rho.data_ptr()
+            d.bias_var, d.kept_rows = self._buf("bias_var", i).data_ptr(), self._buf("kept_rows", i).data_ptr()
+            d.O, d.I, d.levels = O, If, K
+            for j, c in enumerate(self.cuts):
+                d.cut[j] = c
+        torch._foreach_copy_(dst, src)                       # the small vectors of every layer in one fused copy
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            for k, cnt in _lib.layer_groups(n):
+                _lib.check(_lib.lib().lbbnn_sparse_count_levels(_lib.group_slice(descs, k, cnt), cnt, stream),
+                           "lbbnn_sparse_count_levels")
+            for i in range(n):
+                self.register_buffer("row_ptr_%d" % i, ops.sparse_row_ptr(self._buf("kept_rows", i).view(-1)))
+            kept = torch.stack([self._buf("kept_rows", i).sum(1) for i in range(n)])         # (layers, K) int64
+            self.kept.copy_(kept.t())
+            self._tot = [[int(v) for v in row] for row in kept.tolist()]                     # the host read
+            for i, tot in enumerate(self._tot):
+                cap = sum(tot)
+                # (col comes from _empty too, as fp32 words: a NaN-filled slot that was never packed is an index out of range)
+                self.register_buffer("col_%d" % i, _empty((cap,), **f).view(torch.int32))
+                self.register_buffer("mean_%d" % i, _empty((cap,), **f))
+                self.register_buffer("var_%d" % i, _empty((cap,), **f))
+                d = descs[i]
+                d.row_ptr, d.nnz = self._buf("row_ptr", i).data_ptr(), cap
+                d.col, d.mean, d.var = (self._buf(k, i).data_ptr() for k in ("col", "mean", "var"))
+            for k, cnt in _lib.layer_groups(n):
+                _lib.check(_lib.lib().lbbnn_sparse_pack_levels(_lib.group_slice(descs, k, cnt), cnt, stream),
+                           "lbbnn_sparse_pack_levels")
+        return self
+
+    # ------------------------------------------------------------------------------------- the buffers move
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        self._level0 = [None]                                # its views addressed the buffers that were replaced
+        return out
+
+    def load_state_dict(self, *args, **kwargs):
+        out = super().load_state_dict(*args, **kwargs)
+        self._level0 = [None]
+        return out
+
+    def __deepcopy__(self, memo):
+        """A copy owns its buffers and builds its own level models."""
+        import copy
+        held = self.__dict__.pop("_level0")
+        try:
+            new = type(self).__new__(type(self))
+            memo[id(self)] = new
+            new.__dict__ = copy.deepcopy(self.__dict__, memo)
+        finally:
+            self._level0 = held
+        new._level0 = [None]
+        return new
+
+    # ------------------------------------------------------------------------------------- levels
+    def model(self, j: int) -> SparseFrozenNetwork:
+        """Level j as a ``SparseFrozenNetwork`` that shares this sweep's buffers: ``col`` / ``mean`` / ``var`` / ``kept_rows``
+        are views of level j's segment, ``row_ptr`` is the level's slice minus its base (a small tensor of its own), the bias
+        and flow vectors are the sweep's.  ``ensemble_eval``, ``make_graphed_eval_step`` and ``explain_ensemble`` take it
+        without another freeze; nothing is read from the host."""
+        import operator
+        j = operator.index(j)
+        if not 0 <= j < len(self.cuts):
+            raise IndexError("bnn_amd: a sweep of %d thresholds has no level %d" % (len(self.cuts), j))
+        if self._src[0] is None:
+            raise RuntimeError("bnn_amd: this ThresholdSweep is not bound to a network; build it with evaluate.threshold_sweep(net)")
+        n = self.n_layers
+        fz = SparseFrozenNetwork(self.dims, self.family, self.thresholds[j], device=self.kept.device, head=self.head)
+        fz.eval()
+        fz._src = [self._src[0]]
+        fz._layer_ids, fz._row_offsets, fz._T = list(self._layer_ids), list(self._row_offsets), list(self._T)
+        fz._split = [False] * n
+        shared = ("bias_mu", "bias_var") + (("q0_mean", "q0_log_var", "flow_u", "flow_w", "flow_b") if self.family == "mnf" else ())
+        for i, tot in enumerate(self._tot):
+            O, base, nz = self.dims[i + 1], sum(tot[:j]), tot[j]
+            fz.register_buffer("kept_rows_%d" % i, self._buf("kept_rows", i)[j])
+            fz.register_buffer("row_ptr_%d" % i, self._buf("row_ptr", i)[j * O:(j + 1) * O + 1] - base)
+            for name in ("col", "mean", "var"):
+                fz.register_buffer("%s_%d" % (name, i), self._buf(name, i)[base:base + nz])
+            for name in shared:
+                fz.register_buffer("%s_%d" % (name, i), self._buf(name, i))
+        fz._nnz = [tot[j] for tot in self._tot]
+        fz._point()
+        return fz
+
+    def _first(self) -> SparseFrozenNetwork:
+        if self._level0[0] is None:
+            self._level0 = [self.model(0)]
+        return self._level0[0]
+
+    def _run(self, data, S: int, stochastic: bool, log_probs: bool):
+        """(K * S, B, classes) of every level under S draws (``stochastic`` False: S = 1, the posterior-mean branch)."""
+        _check_log_probs(self, log_probs)
+        K = len(self.cuts)
+        m0 = self._first()
+        x = m0._input(data)
+        B, C, dev = x.shape[0], self.dims[-1], x.device
+        st = ops.RngState.get(dev)
+        mnf = self.family == "mnf"
+        with torch.cuda.device(dev):
+            if B == 0:
+                if stochastic or mnf:
+                    st.advance(S)
+                return torch.zeros((K * S, 0, 2 if log_probs else C), dtype=torch.float32, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            zbuf = m0._draw_members(S, st.t, stream)[0] if mnf else None
+            layers = [tuple(self._buf(k, i) for k in ("row_ptr", "col", "mean", "var")) + t[4:]
+                      for i, t in enumerate(m0._layers_of(zbuf, S))]
+            head = _empty((K * S, ops.pad4(B * C)), dtype=torch.float32, device=dev)
+            ops.sparse_member_chain(x, S, layers, head=self.head, out=head, empty=_empty, rng=st.t if stochastic else None,
+                                    stochastic=stochastic, stream=stream, levels=K)
+            if stochastic or mnf:
+                st.advance(S)                                # as ONE model's call would have
+        return _members_result(head, K * S, B, C, self.head, log_probs)
+
+    @torch.no_grad()
+    def ensemble(self, data: torch.Tensor, samples: int = 10, *, log_probs: bool = False) -> torch.Tensor:
+        """(K, samples, B, classes): ``[j, s]`` is member s of ``model(j).ensemble(data, samples)`` from the same Philox offset,
+        bit for bit; the live offset advances by ``samples``.  ``log_probs``: as ``FrozenNetwork.ensemble``."""
+        S, K = int(samples), len(self.cuts)
+        if S < 1:
+            raise ValueError("bnn_amd: samples must be >= 1")
+        if K * S > 65535:
+            raise ValueError("bnn_amd: a sweep evaluates thresholds * samples members in one launch, at most 65535; got %d * %d"
+                             % (K, S))
+        return self._run(data, S, True, log_probs).unflatten(0, (K, S))
+
+    @torch.no_grad()
+    def forward(self, data: torch.Tensor, *, log_probs: bool = False) -> torch.Tensor:
+        """(K, B, classes): ``[j]`` is ``model(j)(data, sample=False)`` from the same Philox offset, bit for bit."""
+        return self._run(data, 1, False, log_probs)
+
+
+def threshold_sweep(net, thresholds=(0.5, 0.9, 0.99)) -> ThresholdSweep:
+    """The sparse median probability models of an LRT / planar MNF network at every one of ``thresholds`` (1 to 16 numbers in
+    (0, 1), strictly ascending, no two with the same fp32 logit) from ONE pass over the parameters: see ``ThresholdSweep``.
+    Refused, each naming what to use: baseline and variational-dropout networks (TypeError), dense coupling z flows and layers
+    with ``noise`` / ``as_written`` (ValueError), a network on the CPU (RuntimeError)."""
+    from . import layers as L
+    if _is_base(net):
+        raise TypeError("bnn_amd: threshold_sweep takes an LRT / MNF network; the sparse model of a baseline LBBNN network draws "
+                        "explicit weights -- freeze it per threshold: freeze_base(net, \"mpm\", threshold=t, sparse=True)")
+    if _is_vd(net):
+        raise TypeError("bnn_amd: threshold_sweep takes an LRT / MNF network; a variational-dropout network has no gates -- use "
+                        "vd_ensemble(net, data, samples)")
+    if not isinstance(net, L._NetworkBase):
+        raise TypeError("bnn_amd: threshold_sweep takes an lrt.BayesianNetwork or mnf.BayesianNetwork, got %s" % type(net).__name__)
+    layers = net._layers()
+    family = "mnf" if layers[0]._mnf else "lrt"
+    sw = ThresholdSweep(net.dims, thresholds, family, device=layers[0].weight_mu.device, head=net.head)
+    if any(l._mnf and l._check_flows() == "dense" for l in layers):
+        raise ValueError("bnn_amd: threshold_sweep is not built for dense coupling z flows -- freeze the dense median probability "
+                         "model per threshold: freeze(net, \"mpm\", threshold=t, dense=True)")
+    _check_freezable_layers(layers)
+    if not layers[0].weight_mu.is_cuda:
+        raise RuntimeError("bnn_amd: threshold_sweep needs the network on a HIP device (it is on %s); there is no CPU path"
+                           % layers[0].weight_mu.device)
+    sw.eval()
+    return sw._bind(net)
+
+
+@torch.no_grad()
+def sweep_batches(sw: ThresholdSweep, batches, samples: int = 10, posterior_mean: bool = True, accs=None) -> Dict[str, object]:
+    """A whole evaluation pass of every level of a ``ThresholdSweep`` with no host read until the last batch is done: per
+    ``(x, y)`` of ``batches`` ONE ``sw.ensemble``, ONE ``sw(x)`` (``posterior_mean``) and one accumulator update per level --
+    ``evaluate_batches`` of every ``sw.model(j)`` from the same Philox offset, under common draws.  ``accs``: K accumulators to
+    add to; default K fresh ``EvalAccumulator``s (a one-unit sigmoid head counts as two classes); a ``head="identity"`` sweep
+    requires K ``RegressionAccumulator``s; any other pairing is a ValueError naming the mismatch.
+    Returns ``{"thresholds", "density", "kept", "results"}`` with ``results[j]`` = ``accs[j].result()``."""
+    if not isinstance(sw, ThresholdSweep):
+        raise TypeError("bnn_amd: sweep_batches takes a ThresholdSweep (evaluate.threshold_sweep(net, thresholds)), got %s"
+                        % type(sw).__name__)
+    S, K = int(samples), len(sw.thresholds)
+    reg = sw.head == "identity"
+    if accs is not None:
+        accs = list(accs)
+        if len(accs) != K:
+            raise ValueError("bnn_amd: sweep_batches: accs must hold one accumulator per threshold (%d), got %d" % (K, len(accs)))
+    if reg:
+        if accs is None or not all(isinstance(a, RegressionAccumulator) for a in accs):
+            raise ValueError("bnn_amd: sweep_batches: this sweep has head=\"identity\" (regression): accs must be %d "
+                             "evaluate.RegressionAccumulator, got %s"
+                             % (K, "None" if accs is None else sorted(set(type(a).__name__ for a in accs))))
+    elif accs is not None and not all(isinstance(a, EvalAccumulator) for a in accs):
+        raise ValueError("bnn_amd: sweep_batches: a head=%r sweep takes EvalAccumulators, got %s (a RegressionAccumulator takes a "
+                         "head=\"identity\" sweep)" % (sw.head, sorted(set(type(a).__name__ for a in accs))))
+    binary = False if reg else _binary_eval(sw)
+    for x, y in batches:
+        outputs = sw.ensemble(x, S, log_probs=binary)
+        mean = sw(x, log_probs=binary) if posterior_mean else None
+        if binary and y is not None:
+            y = _binary_target(y)                 # float 0 / 1 targets: converted on the device, no host read
+        if accs is None:
+            accs = [EvalAccumulator(outputs.shape[-1], S, outputs.device) for _ in range(K)]
+        for j, acc in enumerate(accs):
+            acc.update(outputs[j], y, None if mean is None else mean[j])
+    if accs is None:
+        raise ValueError("bnn_amd: sweep_batches got no batches and no accumulators")
+    return {"thresholds": sw.thresholds, "density": sw.density, "kept": sw.kept, "results": [a.result() for a in accs]}
 
 
 def freeze(net, gates: str = "alpha", *, threshold: float = 0.5, dense: bool = False, compact: bool = False,

@@ -598,15 +598,19 @@ def sparse_row_pad(B: int) -> int:
 
 
 def sparse_member_chain(x, members: int, layers, *, head: str, out, empty=torch.empty, rng=None, stochastic: bool = True,
-                        stream=None):
+                        stream=None, levels: int = 0):
     """A sparse model's layers for ``members`` members: ONE lbbnn_transpose_operand launch lays the (B, I0) rows ``x`` out as
     x^T [I0][sparse_row_pad(B)], then one lbbnn_sparse_layer_members launch per layer.  The rules are member_gemm_chain's,
     with the activations between the layers transposed ([member][unit][sparse_row_pad(B)]): every layer but the last gets
     ReLU; the last writes ``out`` (members, >= pad4(B * O)) row-major and applies log_softmax exactly when O <= 16 and
     ``head`` is "log_softmax".  ``layers``: per layer (row_ptr, col, mean, var, bias_mu, bias_var, z, rng_stream, row_offset)
     with z None (LRT) or a (members, >= I) view of the members' z whose row stride is its member stride.  ``stochastic``
-    False: the posterior-mean branch (no eps_out is drawn)."""
+    False: the posterior-mean branch (no eps_out is drawn).
+    ``levels`` = K >= 1: a threshold sweep's layers (row_ptr (K * O + 1), the K CSRs level after level) -- the same launches
+    through lbbnn_sparse_layer_levels for K * ``members`` members, member j * members + s being level j under draw s; ``out``
+    has K * members rows and z still ``members``."""
     (B, I), last, dev = x.shape, len(layers) - 1, x.device
+    total = max(levels, 1) * members
     stream = _stream() if stream is None else stream
     ldb = sparse_row_pad(B)
     h = empty((I, ldb), dtype=torch.float32, device=dev)
@@ -617,17 +621,18 @@ def sparse_member_chain(x, members: int, layers, *, head: str, out, empty=torch.
         O = bias_mu.numel()
         flags = 0 if stochastic else F_MEAN_ONLY
         if i < last:
-            o, ldo, o_ms, rows, flags = empty((members, O * ldb), dtype=torch.float32, device=dev), ldb, O * ldb, 0, flags | F_RELU
+            o, ldo, o_ms, rows, flags = empty((total, O * ldb), dtype=torch.float32, device=dev), ldb, O * ldb, 0, flags | F_RELU
         else:
             o, ldo, o_ms, rows = out, O, out.stride(0), 1
             if O <= 16 and head == "log_softmax":
                 flags |= F_LOG_SOFTMAX
-        rc = _lib.lib().lbbnn_sparse_layer_members(
-            row_ptr.data_ptr(), col.data_ptr(), mean.data_ptr(), var.data_ptr(), col.numel(), bias_mu.data_ptr(),
-            bias_var.data_ptr(), h.data_ptr(), ldb, h_ms, None if z is None else z.data_ptr(), 0 if z is None else z.stride(0),
-            None if rng is None else rng.data_ptr(), rng_stream, row_offset, 1, o.data_ptr(), ldo, o_ms, rows, B, I, O, flags,
-            members, stream)
-        _lib.check(rc, "lbbnn_sparse_layer_members")
+        args = (row_ptr.data_ptr(), col.data_ptr(), mean.data_ptr(), var.data_ptr(), col.numel(), bias_mu.data_ptr(),
+                bias_var.data_ptr(), h.data_ptr(), ldb, h_ms, None if z is None else z.data_ptr(), 0 if z is None else z.stride(0),
+                None if rng is None else rng.data_ptr(), rng_stream, row_offset, 1, o.data_ptr(), ldo, o_ms, rows, B, I, O, flags)
+        if levels:
+            _lib.check(_lib.lib().lbbnn_sparse_layer_levels(*args, levels, members, stream), "lbbnn_sparse_layer_levels")
+        else:
+            _lib.check(_lib.lib().lbbnn_sparse_layer_members(*args, members, stream), "lbbnn_sparse_layer_members")
         h, h_ms, I = o, o_ms, O                       # (h keeps the buffer alive until the launch that reads it is queued)
     return out
 

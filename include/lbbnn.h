@@ -793,6 +793,59 @@ int lbbnn_sparse_layer_members(const int32_t* row_ptr, const int32_t* col, const
                                int out_rows, int B, int I, int O, int flags, int members, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Threshold sweep of the sparse median-probability model (evaluate.threshold_sweep): the sparse models of K ascending cuts
+ * c_0 < ... < c_{K-1} packed by ONE count and ONE pack launch, and evaluated by one layer launch for K x S members -- level j
+ * under draw s.  Per layer with O rows the K CSRs lie level after level in one set of arrays:
+ *     kept_rows (K, O) int32: kept_rows[j][o] = #{c : lambdal[o][c] > c_j}, compared in fp32 (NaN is never kept);
+ *     row_ptr (K * O + 1) int32: the exclusive scan of kept_rows flattened level-major (the caller scans); level j, row o owns
+ *     the slots [row_ptr[j * O + o], row_ptr[j * O + o + 1]) of the shared col / mean / var, columns ascending;
+ *     mean / var / bias_var: the bits lbbnn_sparse_pack writes, so level j's segment is the model of cut c_j bit for bit.
+ * The patterns are nested (a weight kept at level j is kept at every lower level) but every level has a segment of its own: a
+ * member walks the kept weights of its level and nothing else.
+ *
+ * lbbnn_sparse_count_levels: ONE launch for all n <= LBBNN_MAX_LAYERS layers, one wave per weight row.  Each lambdal is loaded
+ *   once; per 64 columns K compares against cuts in scalar registers and K ballots; kept_rows[j][o] is stored for every j.
+ * lbbnn_sparse_pack_levels: ONE launch, one wave per row.  Per 64 columns lambdal is loaded once, mu / rho once for the lanes
+ *   kept at level 0 (sigma computed once), and for every level the ballot and the count of the lower kept lanes give a kept
+ *   lane its slot in that level's segment.  Plain vector stores, no atomics, no LDS.  Nothing is written at or past `nnz` (the
+ *   capacity of col / mean / var) or past the end of a (level, row), whatever row_ptr holds.  bias_var[o] is stored once.
+ *   Both: the checks and codes of lbbnn_sparse_count / lbbnn_sparse_pack; and levels outside [1, LBBNN_MAX_LEVELS], a cut that
+ *   is not finite, or cuts that do not ascend strictly: LBBNN_E_SHAPE.
+ *
+ * lbbnn_sparse_layer_levels: lbbnn_sparse_layer_members for levels * members_per_level members in ONE launch.  Member m is
+ *   level j = m / members_per_level under draw s = m % members_per_level: it reads its row pointers at row_ptr[j * O + o], its
+ *   z at z + s * z_mstride, draws eps at Philox offset rng[1] + s * member_advance, reads its input at a + m * a_mstride and
+ *   writes at out + m * o_mstride.  Everything else is lbbnn_sparse_layer_members (the same kernel): the sums, the counters,
+ *   the heads, the clamps -- so member (j, s) has the bits of member s of the model packed for cut c_j alone, and the draws
+ *   are common to the levels.  `nnz` is the capacity of col / mean / var over all levels; row_ptr holds levels * O + 1 entries.
+ *   The work is proportional to the sum of the levels' kept weights.  The checks and codes of lbbnn_sparse_layer_members
+ *   with members = levels * members_per_level (z_mstride < I is refused with more than one draw); and levels outside
+ *   [1, LBBNN_MAX_LEVELS], members_per_level < 1 or levels * members_per_level > 65535: LBBNN_E_SHAPE. */
+#define LBBNN_MAX_LEVELS 16
+
+typedef struct lbbnn_sparse_levels_desc {
+    const float *weight_mu, *weight_rho, *lambdal;   /* (O,I)                                          */
+    const float *bias_rho;                           /* (O)                                            */
+    const int32_t* row_ptr;                          /* (levels * O + 1); lbbnn_sparse_pack_levels     */
+    int32_t* col;                                    /* (nnz);            lbbnn_sparse_pack_levels     */
+    float *mean, *var;                               /* (nnz);            lbbnn_sparse_pack_levels     */
+    float* bias_var;                                 /* (O);              lbbnn_sparse_pack_levels     */
+    int32_t* kept_rows;                              /* (levels, O);      lbbnn_sparse_count_levels    */
+    int O, I;
+    int nnz;                                         /* capacity of col / mean / var, all levels       */
+    int levels;                                      /* K, 1 .. LBBNN_MAX_LEVELS                       */
+    float cut[LBBNN_MAX_LEVELS];                     /* logit(threshold_j), strictly ascending         */
+} lbbnn_sparse_levels_desc_t;
+
+int lbbnn_sparse_count_levels(const lbbnn_sparse_levels_desc_t* layers, int n, void* stream);
+int lbbnn_sparse_pack_levels(const lbbnn_sparse_levels_desc_t* layers, int n, void* stream);
+int lbbnn_sparse_layer_levels(const int32_t* row_ptr, const int32_t* col, const float* mean, const float* var, int nnz,
+                              const float* bias_mu, const float* bias_var, const float* a, int lda, int64_t a_mstride,
+                              const float* z, int64_t z_mstride, const uint64_t* rng, uint32_t rng_stream,
+                              int64_t row_offset, uint64_t member_advance, float* out, int ldo, int64_t o_mstride,
+                              int out_rows, int B, int I, int O, int flags, int levels, int members_per_level, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Frozen evaluation model of a baseline LBBNN network (LBBNN-GP-MF.py:345-502: test_ensemble and outofsample): a snapshot of
  * sigma = softplus(rho), alpha = sigmoid(lambdal) and the gated mean taken ONCE, from which every member is then drawn
  * without reading the parameters, without drawing for weights the median probability model has pruned, and -- with a map --
