@@ -1,113 +1,32 @@
 // Sparse median-probability model of a baseline LBBNN network (gfx950), see include/lbbnn.h: the kept weights of
 // freeze_base(net, "mpm") in CSR, and every member's explicit weights drawn on that pattern alone.
 //
-//   base_sparse_rows_kernel -- lbbnn_base_sparse_count / lbbnn_base_sparse_pack: sparse_rows_kernel's work split (one launch over
-//     the rows of up to LBBNN_MAX_LAYERS layers, ONE WAVE PER ROW, 64 columns at a time, the ballot of the kept lanes and the
-//     count of the kept lanes below give each its slot) with the keep rule of base_frozen_operands_kernel: sigmoid_ref(lambdal) >
-//     threshold in fp32 -- not lambdal > logit(threshold), which can differ at the boundary.  Pack stores sigma = softplus_ref(rho)
-//     itself (the draw multiplies by sigma: sqrt(sigma^2) is not sigma to the bit), and per row b_mu / b_sigma.
+//   csr_rows_kernel<BaseRule> (csr_pack.h) -- lbbnn_base_sparse_count / lbbnn_base_sparse_pack: the count / pack of the LRT / MNF
+//     sparse model with the keep rule of base_frozen_operands_kernel, sigma itself as the third value, b_mu / b_sigma per row.
 //   base_sparse_draw_kernel -- lbbnn_base_sparse_draw_members: ONE WAVE PER CSR ROW, the rows of all layers on gridDim.x, the
 //     members on gridDim.y with a stride inside (base_frozen_members_kernel's split: pattern and planes are read once per
 //     member stride).  A lane owns slot row_ptr[o] + 64 j + lane: the row o is the wave's, so the Philox counter of the weight is
 //     the FULL network's (o, col / 4) without a row array, and the value is base_frozen_members_kernel's fused mu + sigma * eps.
 //     One Philox evaluation per lane and member: at the densities this model is for, most quads hold one kept weight.
 // No LDS, no atomics, plain vector stores; every index read from device memory is clamped before it is followed.
-#include "lbbnn_device.h"
-#include "lbbnn_internal.h"
-#include "operand_store.h"
-#include "sparse_lanes.h"
+#include "csr_pack.h"
 
 namespace {
 
 using namespace lbbnn;
 
-constexpr int kBsRows = 4;                 // weight rows (= waves) per workgroup of both kernels
+constexpr int kBsRows = 4;                 // weight rows (= waves) per workgroup of the draw kernel
 constexpr int kBsNT = 64 * kBsRows;
 
-struct BsLayer {
-    const float* mu; const float* rho; const float* lambdal; const float* bias_mu; const float* bias_rho;
-    const int32_t* row_ptr; int32_t* col; float* mean; float* sigma; float* b_mu; float* b_sigma; int32_t* kept_rows;
-    int O, I, nnz;
-};
-struct BsBatch { BsLayer l[LBBNN_MAX_LAYERS]; int wg_end[LBBNN_MAX_LAYERS]; int n; float threshold; };
-
-template <bool kPack>
-__global__ __launch_bounds__(kBsNT) void base_sparse_rows_kernel(const BsBatch bt_) {
-    const LBBNN_CONST_AS BsBatch* bt = kernarg_as<BsBatch>();
-    int wg0;
-    const int li = layer_of(bt, wg0);
-    const LBBNN_CONST_AS BsLayer& a = bt->l[li];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int o = kBsRows * ((int)blockIdx.x - wg0) + wv;
-    if (o >= a.O) return;                                                 // (whole waves leave: no barrier below)
-    const int I = a.I;
-    const size_t rowoff = (size_t)o * I;
-    const float thr = bt->threshold;
-    int base = 0, end = 0;
-    if constexpr (kPack) {
-        // the row's slots, inside [0, nnz] whatever row_ptr holds
-        base = clampi(a.row_ptr[o], 0, a.nnz);
-        end = clampi(a.row_ptr[o + 1], base, a.nnz);
-    }
-    int run = 0;                                                          // kept so far in this row (wave-uniform)
-    for (int c0 = 0; c0 < I; c0 += 64) {
-        const int c = c0 + lane;
-        const bool kept = c < I && sigmoid_ref(a.lambdal[rowoff + c]) > thr;   // fp32; NaN is never kept
-        const unsigned long long m = __ballot(kept);
-        if constexpr (kPack) {
-            const int below = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-            const int pos = base + run + below;
-            if (kept && pos < end) {
-                a.col[pos] = c;
-                a.mean[pos] = a.mu[rowoff + c];
-                a.sigma[pos] = softplus_ref(a.rho[rowoff + c]);
-            }
-        }
-        run += __popcll(m);
-    }
-    if (lane == 0) {
-        if constexpr (kPack) {
-            a.b_mu[o] = a.bias_mu[o];
-            a.b_sigma[o] = softplus_ref(a.bias_rho[o]);                   // (never gated)
-        } else {
-            a.kept_rows[o] = run;
-        }
-    }
-}
-
-int base_sparse_rows_impl(const lbbnn_base_sparse_desc_t* L, int n, float threshold, bool pack, void* stream) {
-    if (!L) return LBBNN_E_NULL;
-    if (n <= 0 || n > LBBNN_MAX_LAYERS) return LBBNN_E_SHAPE;
-    if (!(threshold > 0.f && threshold < 1.f)) return LBBNN_E_FLAGS;
-    BsBatch bt = {};
-    int wgs = 0;
-    for (int i = 0; i < n; ++i) {
-        const lbbnn_base_sparse_desc_t& d = L[i];
-        if (!d.lambdal) return LBBNN_E_NULL;
-        if (pack) {
-            if (!d.mu || !d.rho || !d.bias_mu || !d.bias_rho || !d.row_ptr || !d.b_mu || !d.b_sigma) return LBBNN_E_NULL;
-            if (d.nnz > 0 && (!d.col || !d.mean || !d.sigma)) return LBBNN_E_NULL;
-        } else if (!d.kept_rows) return LBBNN_E_NULL;
-        if (d.O <= 0 || d.I <= 0 || (pack && d.nnz < 0)) return LBBNN_E_SHAPE;
-        if (!aligned4(d.lambdal)) return LBBNN_E_ALIGN;
-        if (pack) {
-            if (!aligned4(d.mu) || !aligned4(d.rho) || !aligned4(d.bias_mu) || !aligned4(d.bias_rho) || !aligned4(d.row_ptr) ||
-                !aligned4(d.col) || !aligned4(d.mean) || !aligned4(d.sigma) || !aligned4(d.b_mu) || !aligned4(d.b_sigma))
-                return LBBNN_E_ALIGN;
-        } else if (!aligned4(d.kept_rows)) return LBBNN_E_ALIGN;
-        BsLayer& a = bt.l[i];
+// lbbnn_base_sparse_count / _pack: csr_pack.h's single-level kernel under BaseRule, the threshold as every layer's one cut
+int base_sparse_rows(const lbbnn_base_sparse_desc_t* L, int n, float threshold, bool pack, void* stream) {
+    const int args = threshold > 0.f && threshold < 1.f ? 0 : LBBNN_E_FLAGS;
+    return csr_rows<BaseRule, 1>(L, n, pack, args, stream, [threshold](const lbbnn_base_sparse_desc_t& d, CsrLayer<1>& a) {
         a.mu = d.mu; a.rho = d.rho; a.lambdal = d.lambdal; a.bias_mu = d.bias_mu; a.bias_rho = d.bias_rho;
-        a.row_ptr = d.row_ptr; a.col = d.col; a.mean = d.mean; a.sigma = d.sigma; a.b_mu = d.b_mu; a.b_sigma = d.b_sigma;
+        a.row_ptr = d.row_ptr; a.col = d.col; a.mean = d.mean; a.val = d.sigma; a.row0 = d.b_mu; a.row1 = d.b_sigma;
         a.kept_rows = d.kept_rows;
-        a.O = d.O; a.I = d.I; a.nnz = pack ? d.nnz : 0;
-        wgs += (d.O + kBsRows - 1) / kBsRows;
-        bt.wg_end[i] = wgs;
-    }
-    bt.n = n; bt.threshold = threshold;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (pack) hipLaunchKernelGGL(base_sparse_rows_kernel<true>, dim3(wgs), dim3(kBsNT), 0, s, bt);
-    else hipLaunchKernelGGL(base_sparse_rows_kernel<false>, dim3(wgs), dim3(kBsNT), 0, s, bt);
-    return (int)hipGetLastError();
+        a.O = d.O; a.I = d.I; a.nnz = d.nnz; a.K = 1; a.cut[0] = threshold;
+    });
 }
 
 struct BdLayer {
@@ -197,11 +116,11 @@ __global__ __launch_bounds__(kBsNT) void base_sparse_draw_kernel(const BdBatch b
 }  // namespace
 
 extern "C" int lbbnn_base_sparse_count(const lbbnn_base_sparse_desc_t* L, int n, float threshold, void* stream) {
-    return base_sparse_rows_impl(L, n, threshold, false, stream);
+    return base_sparse_rows(L, n, threshold, false, stream);
 }
 
 extern "C" int lbbnn_base_sparse_pack(const lbbnn_base_sparse_desc_t* L, int n, float threshold, void* stream) {
-    return base_sparse_rows_impl(L, n, threshold, true, stream);
+    return base_sparse_rows(L, n, threshold, true, stream);
 }
 
 extern "C" int lbbnn_base_sparse_draw_members(const lbbnn_base_sparse_draw_desc_t* L, int n, int members, const uint64_t* rng,

@@ -1,13 +1,8 @@
 // Sparse median-probability model (gfx950): the kept weights of a frozen LRT / MNF network in CSR, and the member layers
 // evaluated on the vector ALU from that format alone, see include/lbbnn.h.
 //
-//   sparse_rows_kernel -- lbbnn_sparse_count / lbbnn_sparse_pack: one launch over the rows of up to LBBNN_MAX_LAYERS layers,
-//     ONE WAVE PER ROW (four rows per 256-thread workgroup).  The wave walks its row 64 columns at a time: a lane loads one
-//     lambdal (a 256-B line per wave), the ballot of `lambdal > cut` is the kept set of the 64 columns, and a kept lane's
-//     place is the running count of the row plus the number of kept lanes below it (mbcnt of the ballot) -- ascending
-//     columns without a sort, an atomic or LDS.  Pack: kept lanes load mu / rho and store col / mean / var there; lane 0
-//     stores bias_var.  Count: lane 0 stores the row's total.  The arithmetic of var / bias_var is frozen_operands_kernel's
-//     (k1_sigma, softplus_ref of lbbnn_device.h), so the values are its bits.
+//   csr_rows_kernel<LrtRule> (csr_pack.h) -- lbbnn_sparse_count / _pack and lbbnn_sparse_count_levels / _pack_levels: one wave per
+//     weight row, the ballot of `lambdal > cut` and the count of the kept lanes below give each kept weight its slot.
 //   sparse_layer_kernel -- lbbnn_sparse_layer_members: ONE LANE PER BATCH ROW, WEIGHTS WAVE-UNIFORM.  A wave owns 64 rows of
 //     one member (blockIdx.y: the row tile, blockIdx.z: the member, so z_m[col] is uniform) and four consecutive output
 //     units, one philox_normal4 call per lane as in the dense epilogue.  It walks the CSR row of each unit once: col / mean /
@@ -18,213 +13,39 @@
 //     LDS is the <= 16-unit head's: its four waves exchange the tile's logits for the log_softmax.  Two batch rows per lane
 //     (tiles of 128 rows, 8-B loads, packed fp32 FMAs) halve the scalar work per row, which is what bounds the loop.
 #include <cstdlib>
-#include "lbbnn_device.h"
-#include "lbbnn_internal.h"
-#include "operand_store.h"
-#include "sparse_lanes.h"
+#include "csr_pack.h"
 
 namespace {
 
 using namespace lbbnn;
 
-constexpr int kSpRows = 4;                 // weight rows (= waves) per workgroup of the count / pack kernel
-constexpr int kSpNT = 64 * kSpRows;
 constexpr int kSpChunk = 8;                // nonzeros whose activation loads are in flight together
 
-struct SparseLayer {
-    const float* mu; const float* rho; const float* lambdal; const float* bias_rho;
-    const int32_t* row_ptr; int32_t* col; float* mean; float* var; float* bias_var; int32_t* kept_rows;
-    int O, I, nnz;
-    float cut;
-};
-struct SparseBatch { SparseLayer l[LBBNN_MAX_LAYERS]; int wg_end[LBBNN_MAX_LAYERS]; int n; };
-
-template <bool kPack>
-__global__ __launch_bounds__(kSpNT) void sparse_rows_kernel(const SparseBatch bt_) {
-    const LBBNN_CONST_AS SparseBatch* bt = kernarg_as<SparseBatch>();
-    int wg0;
-    const int li = layer_of(bt, wg0);
-    const LBBNN_CONST_AS SparseLayer& a = bt->l[li];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int o = kSpRows * ((int)blockIdx.x - wg0) + wv;
-    if (o >= a.O) return;                                                 // (whole waves leave: no barrier below)
-    const int I = a.I;
-    const size_t rowoff = (size_t)o * I;
-    const float cut = a.cut;
-    int base = 0, end = 0;
-    if constexpr (kPack) {
-        // the row's slots, inside [0, nnz] whatever row_ptr holds
-        base = clampi(a.row_ptr[o], 0, a.nnz);
-        end = clampi(a.row_ptr[o + 1], base, a.nnz);
-    }
-    int run = 0;                                                          // kept so far in this row (wave-uniform)
-    for (int c0 = 0; c0 < I; c0 += 64) {
-        const int c = c0 + lane;
-        const bool kept = c < I && a.lambdal[rowoff + c] > cut;           // fp32 compare: NaN is never kept
-        const unsigned long long m = __ballot(kept);
-        if constexpr (kPack) {
-            const int below = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-            const int pos = base + run + below;
-            if (kept && pos < end) {
-                const float sigma = k1_sigma(a.rho[rowoff + c]);
-                a.col[pos] = c;
-                a.mean[pos] = a.mu[rowoff + c];
-                a.var[pos] = sigma * sigma;
-            }
-        }
-        run += __popcll(m);
-    }
-    if (lane == 0) {
-        if constexpr (kPack) {
-            const float sb = softplus_ref(a.bias_rho[o]);
-            a.bias_var[o] = sb * sb;                  // bias.sigma**2, LBBNN-GP-MF-LRT.py:173 (never gated)
-        } else {
-            a.kept_rows[o] = run;
-        }
-    }
+// lbbnn_sparse_count / _pack (K = 1, the single-level kernel) and the threshold sweep's lbbnn_sparse_count_levels / _pack_levels:
+// csr_pack.h's kernel under LrtRule.  K = 0 tells csr_rows that the levels or the cuts are out of range.
+template <int kMaxLevels, typename Desc>
+void sparse_copy(const Desc& d, CsrLayer<kMaxLevels>& a, int K) {
+    a.mu = d.weight_mu; a.rho = d.weight_rho; a.lambdal = d.lambdal; a.bias_rho = d.bias_rho;
+    a.row_ptr = d.row_ptr; a.col = d.col; a.mean = d.mean; a.val = d.var; a.row0 = d.bias_var; a.kept_rows = d.kept_rows;
+    a.O = d.O; a.I = d.I; a.nnz = d.nnz; a.K = K;
 }
 
-int sparse_rows_impl(const lbbnn_sparse_desc_t* L, int n, bool pack, void* stream) {
-    if (!L) return LBBNN_E_NULL;
-    if (n <= 0 || n > LBBNN_MAX_LAYERS) return LBBNN_E_SHAPE;
-    SparseBatch bt = {};
-    int wgs = 0;
-    for (int i = 0; i < n; ++i) {
-        const lbbnn_sparse_desc_t& d = L[i];
-        if (!d.lambdal) return LBBNN_E_NULL;
-        if (pack) {
-            if (!d.weight_mu || !d.weight_rho || !d.bias_rho || !d.row_ptr || !d.bias_var) return LBBNN_E_NULL;
-            if (d.nnz > 0 && (!d.col || !d.mean || !d.var)) return LBBNN_E_NULL;
-        } else if (!d.kept_rows) return LBBNN_E_NULL;
-        if (d.O <= 0 || d.I <= 0 || (pack && d.nnz < 0)) return LBBNN_E_SHAPE;
-        if (!aligned4(d.lambdal)) return LBBNN_E_ALIGN;
-        if (pack) {
-            if (!aligned4(d.weight_mu) || !aligned4(d.weight_rho) || !aligned4(d.bias_rho) || !aligned4(d.row_ptr) ||
-                !aligned4(d.col) || !aligned4(d.mean) || !aligned4(d.var) || !aligned4(d.bias_var)) return LBBNN_E_ALIGN;
-        } else if (!aligned4(d.kept_rows)) return LBBNN_E_ALIGN;
-        SparseLayer& a = bt.l[i];
-        a.mu = d.weight_mu; a.rho = d.weight_rho; a.lambdal = d.lambdal; a.bias_rho = d.bias_rho;
-        a.row_ptr = d.row_ptr; a.col = d.col; a.mean = d.mean; a.var = d.var; a.bias_var = d.bias_var; a.kept_rows = d.kept_rows;
-        a.O = d.O; a.I = d.I; a.nnz = pack ? d.nnz : 0; a.cut = d.cut;
-        wgs += (d.O + kSpRows - 1) / kSpRows;
-        bt.wg_end[i] = wgs;
-    }
-    bt.n = n;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (pack) hipLaunchKernelGGL(sparse_rows_kernel<true>, dim3(wgs), dim3(kSpNT), 0, s, bt);
-    else hipLaunchKernelGGL(sparse_rows_kernel<false>, dim3(wgs), dim3(kSpNT), 0, s, bt);
-    return (int)hipGetLastError();
+int sparse_rows(const lbbnn_sparse_desc_t* L, int n, bool pack, void* stream) {
+    return csr_rows<LrtRule, 1>(L, n, pack, 0, stream, [](const lbbnn_sparse_desc_t& d, CsrLayer<1>& a) {
+        sparse_copy(d, a, 1);
+        a.cut[0] = d.cut;
+    });
 }
 
-// The threshold sweep's count / pack (lbbnn_sparse_count_levels / _pack_levels): sparse_rows_kernel for K ascending cuts at
-// once.  A lane loads its lambdal ONCE per 64 columns and compares it with every cut (kernel arguments: scalar registers); the
-// ballot of level j is that level's kept set, and the running count of (level, row) is wave-uniform.  Pack: a lane kept at level 0
-// (the loosest cut: every other level's kept set lies inside it) loads mu / rho once and computes sigma^2 once, then stores the
-// same three words into the segment of every level that keeps it, at base_j + run_j + (kept lanes below it at level j).  The
-// unrolled level loop keeps run / base / end in registers (constant indices); levels past K do nothing.
-struct SparseLevelsLayer {
-    const float* mu; const float* rho; const float* lambdal; const float* bias_rho;
-    const int32_t* row_ptr; int32_t* col; float* mean; float* var; float* bias_var; int32_t* kept_rows;
-    int O, I, nnz, K;
-    float cut[LBBNN_MAX_LEVELS];
-};
-struct SparseLevelsBatch { SparseLevelsLayer l[LBBNN_MAX_LAYERS]; int wg_end[LBBNN_MAX_LAYERS]; int n; };
-
-template <bool kPack>
-__global__ __launch_bounds__(kSpNT) void sparse_levels_kernel(const SparseLevelsBatch bt_) {
-    const LBBNN_CONST_AS SparseLevelsBatch* bt = kernarg_as<SparseLevelsBatch>();
-    int wg0;
-    const int li = layer_of(bt, wg0);
-    const LBBNN_CONST_AS SparseLevelsLayer& a = bt->l[li];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int o = kSpRows * ((int)blockIdx.x - wg0) + wv;
-    if (o >= a.O) return;                                                 // (whole waves leave: no barrier below)
-    const int I = a.I, K = a.K;
-    const size_t rowoff = (size_t)o * I;
-    int run[LBBNN_MAX_LEVELS], base[LBBNN_MAX_LEVELS], end[LBBNN_MAX_LEVELS];
-#pragma unroll
-    for (int j = 0; j < LBBNN_MAX_LEVELS; ++j) {
-        run[j] = base[j] = end[j] = 0;
-        if (kPack && j < K) {
-            // the slots of (level j, row o), inside [0, nnz] whatever row_ptr holds
-            base[j] = clampi(a.row_ptr[(size_t)j * a.O + o], 0, a.nnz);
-            end[j] = clampi(a.row_ptr[(size_t)j * a.O + o + 1], base[j], a.nnz);
+int sparse_levels(const lbbnn_sparse_levels_desc_t* L, int n, bool pack, void* stream) {
+    return csr_rows<LrtRule, LBBNN_MAX_LEVELS>(L, n, pack, 0, stream, [](const lbbnn_sparse_levels_desc_t& d, CsrLayer<LBBNN_MAX_LEVELS>& a) {
+        bool ok = d.levels >= 1 && d.levels <= LBBNN_MAX_LEVELS;
+        for (int j = 0; ok && j < d.levels; ++j) {    // finite and strictly ascending (a NaN fails `< INFINITY`)
+            ok = fabsf(d.cut[j]) < INFINITY && (!j || d.cut[j - 1] < d.cut[j]);
+            a.cut[j] = d.cut[j];
         }
-    }
-    for (int c0 = 0; c0 < I; c0 += 64) {
-        const int c = c0 + lane;
-        const bool in = c < I;
-        const float lam = in ? a.lambdal[rowoff + c] : 0.f;
-        float mu = 0.f, var = 0.f;
-        if constexpr (kPack) {
-            if (in && lam > a.cut[0]) {                                    // fp32 compare: NaN is never kept
-                const float sigma = k1_sigma(a.rho[rowoff + c]);
-                mu = a.mu[rowoff + c];
-                var = sigma * sigma;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < LBBNN_MAX_LEVELS; ++j) {
-            if (j >= K) continue;                                         // wave-uniform
-            const bool kept = in && lam > a.cut[j];
-            const unsigned long long m = __ballot(kept);
-            if constexpr (kPack) {
-                const int below = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                const int pos = base[j] + run[j] + below;
-                if (kept && pos < end[j]) {
-                    a.col[pos] = c;
-                    a.mean[pos] = mu;
-                    a.var[pos] = var;
-                }
-            }
-            run[j] += __popcll(m);
-        }
-    }
-    if (lane == 0) {
-        if constexpr (kPack) {
-            const float sb = softplus_ref(a.bias_rho[o]);
-            a.bias_var[o] = sb * sb;                  // bias.sigma**2, LBBNN-GP-MF-LRT.py:173 (never gated)
-        } else {
-#pragma unroll
-            for (int j = 0; j < LBBNN_MAX_LEVELS; ++j) if (j < K) a.kept_rows[(size_t)j * a.O + o] = run[j];
-        }
-    }
-}
-
-int sparse_levels_impl(const lbbnn_sparse_levels_desc_t* L, int n, bool pack, void* stream) {
-    if (!L) return LBBNN_E_NULL;
-    if (n <= 0 || n > LBBNN_MAX_LAYERS) return LBBNN_E_SHAPE;
-    SparseLevelsBatch bt = {};
-    int wgs = 0;
-    for (int i = 0; i < n; ++i) {
-        const lbbnn_sparse_levels_desc_t& d = L[i];
-        if (!d.lambdal) return LBBNN_E_NULL;
-        if (pack) {
-            if (!d.weight_mu || !d.weight_rho || !d.bias_rho || !d.row_ptr || !d.bias_var) return LBBNN_E_NULL;
-            if (d.nnz > 0 && (!d.col || !d.mean || !d.var)) return LBBNN_E_NULL;
-        } else if (!d.kept_rows) return LBBNN_E_NULL;
-        if (d.O <= 0 || d.I <= 0 || (pack && d.nnz < 0)) return LBBNN_E_SHAPE;
-        if (d.levels < 1 || d.levels > LBBNN_MAX_LEVELS) return LBBNN_E_SHAPE;
-        for (int j = 0; j < d.levels; ++j)            // finite and strictly ascending (a NaN fails `< INFINITY`)
-            if (!(fabsf(d.cut[j]) < INFINITY) || (j && !(d.cut[j - 1] < d.cut[j]))) return LBBNN_E_SHAPE;
-        if (!aligned4(d.lambdal)) return LBBNN_E_ALIGN;
-        if (pack) {
-            if (!aligned4(d.weight_mu) || !aligned4(d.weight_rho) || !aligned4(d.bias_rho) || !aligned4(d.row_ptr) ||
-                !aligned4(d.col) || !aligned4(d.mean) || !aligned4(d.var) || !aligned4(d.bias_var)) return LBBNN_E_ALIGN;
-        } else if (!aligned4(d.kept_rows)) return LBBNN_E_ALIGN;
-        SparseLevelsLayer& a = bt.l[i];
-        a.mu = d.weight_mu; a.rho = d.weight_rho; a.lambdal = d.lambdal; a.bias_rho = d.bias_rho;
-        a.row_ptr = d.row_ptr; a.col = d.col; a.mean = d.mean; a.var = d.var; a.bias_var = d.bias_var; a.kept_rows = d.kept_rows;
-        a.O = d.O; a.I = d.I; a.nnz = pack ? d.nnz : 0; a.K = d.levels;
-        for (int j = 0; j < d.levels; ++j) a.cut[j] = d.cut[j];
-        wgs += (d.O + kSpRows - 1) / kSpRows;
-        bt.wg_end[i] = wgs;
-    }
-    bt.n = n;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (pack) hipLaunchKernelGGL(sparse_levels_kernel<true>, dim3(wgs), dim3(kSpNT), 0, s, bt);
-    else hipLaunchKernelGGL(sparse_levels_kernel<false>, dim3(wgs), dim3(kSpNT), 0, s, bt);
-    return (int)hipGetLastError();
+        sparse_copy(d, a, ok ? d.levels : 0);
+    });
 }
 
 struct SpArgs {
@@ -447,19 +268,19 @@ int sparse_layer_impl(const int32_t* row_ptr, const int32_t* col, const float* m
 }  // namespace
 
 extern "C" int lbbnn_sparse_count(const lbbnn_sparse_desc_t* L, int n, void* stream) {
-    return sparse_rows_impl(L, n, false, stream);
+    return sparse_rows(L, n, false, stream);
 }
 
 extern "C" int lbbnn_sparse_pack(const lbbnn_sparse_desc_t* L, int n, void* stream) {
-    return sparse_rows_impl(L, n, true, stream);
+    return sparse_rows(L, n, true, stream);
 }
 
 extern "C" int lbbnn_sparse_count_levels(const lbbnn_sparse_levels_desc_t* L, int n, void* stream) {
-    return sparse_levels_impl(L, n, false, stream);
+    return sparse_levels(L, n, false, stream);
 }
 
 extern "C" int lbbnn_sparse_pack_levels(const lbbnn_sparse_levels_desc_t* L, int n, void* stream) {
-    return sparse_levels_impl(L, n, true, stream);
+    return sparse_levels(L, n, true, stream);
 }
 
 extern "C" int lbbnn_sparse_layer_members(const int32_t* row_ptr, const int32_t* col, const float* mean, const float* var,

@@ -1598,6 +1598,26 @@ class _FrozenModel(nn.Module):
         return _members_result(buf, S, B, self.dims[-1], self.head, log_probs)
 
 
+def _z_copies(fz, layers):
+    """(dst, src) of the copies that snapshot q0 and the z flow of every MNF layer into the buffers of ``fz`` (a frozen model
+    or a threshold sweep)."""
+    dst, src = [], []
+    for i, l in enumerate(layers):
+        if not l._mnf:
+            continue
+        dst += [fz._buf("q0_mean", i), fz._buf("q0_log_var", i)]
+        src += [l.q0_mean.detach(), l.q0_log_var.detach()]
+        for t, tr in enumerate(l.z_flow.transforms):
+            if getattr(fz, "flows", None) == "dense":
+                ps = dict(tr.named_parameters())
+                for k in fz._zflow_names[i][t]:
+                    dst.append(getattr(fz, fz._zflow_buf(i, t, k))); src.append(ps[k].detach())
+            else:
+                dst += [fz._buf("flow_u", i)[t], fz._buf("flow_w", i)[t], fz._buf("flow_b", i)[t]]
+                src += [tr.u.detach().reshape(-1), tr.w.detach().reshape(-1), tr.bias.detach().reshape(-1)]
+    return dst, src
+
+
 class FrozenNetwork(_FrozenModel):
     """A trained LRT / MNF network frozen for evaluation (built by ``freeze``; no parameters, buffers only).
 
@@ -1758,24 +1778,6 @@ class FrozenNetwork(_FrozenModel):
                         d.z_flow.u[t], d.z_flow.w[t], d.z_flow.b[t] = u[t].data_ptr(), w[t].data_ptr(), b[t].data_ptr()
         return descs
 
-    def _z_copies(self, layers):
-        """(dst, src) of the copies that snapshot q0 and the z flow of every MNF layer."""
-        dst, src = [], []
-        for i, l in enumerate(layers):
-            if not l._mnf:
-                continue
-            dst += [self._buf("q0_mean", i), self._buf("q0_log_var", i)]
-            src += [l.q0_mean.detach(), l.q0_log_var.detach()]
-            for t, tr in enumerate(l.z_flow.transforms):
-                if self.flows == "dense":
-                    ps = dict(tr.named_parameters())
-                    for k in self._zflow_names[i][t]:
-                        dst.append(getattr(self, self._zflow_buf(i, t, k))); src.append(ps[k].detach())
-                else:
-                    dst += [self._buf("flow_u", i)[t], self._buf("flow_w", i)[t], self._buf("flow_b", i)[t]]
-                    src += [tr.u.detach().reshape(-1), tr.w.detach().reshape(-1), tr.bias.detach().reshape(-1)]
-        return dst, src
-
     @torch.no_grad()
     def refresh(self):
         """Take the snapshot again from the source network's current parameters, into the same buffers: ONE
@@ -1796,7 +1798,7 @@ class FrozenNetwork(_FrozenModel):
         self._layer_ids = [int(l._layer_id) for l in layers]
         self._row_offsets = [int(l.row_offset) for l in layers]
         self._xops = None                                    # explain's operands belong to the old snapshot
-        dst, src = self._z_copies(layers)
+        dst, src = _z_copies(self, layers)
         dst += [self._buf("bias_mu", i) for i in range(self.n_layers)]
         src += [l.bias_mu.detach() for l in layers]
         torch._foreach_copy_(dst, src)                       # the small vectors of every layer in one fused copy
@@ -2225,7 +2227,7 @@ class CompactFrozenNetwork(FrozenNetwork):
         self._row_offsets = [int(l.row_offset) for l in layers]
         for i, l in enumerate(layers):
             torch.index_select(l.bias_mu.detach(), 0, self._buf("live", i + 1).long(), out=self._buf("bias_mu", i))
-        dst, src = self._z_copies(layers)
+        dst, src = _z_copies(self, layers)
         if dst:
             torch._foreach_copy_(dst, src)
         descs = self._descs(layers)
@@ -2253,7 +2255,107 @@ def _freeze_compact(net, layers, family, threshold) -> CompactFrozenNetwork:
     return fz._bind(net, need, masks)
 
 
-class SparseFrozenNetwork(FrozenNetwork):
+class _SparseModel:
+    """What the sparse median probability models share (mixed in before the frozen base): per layer a CSR ``row_ptr_<i>`` /
+    ``col_<i>`` / the two value arrays named by ``VALUES``, two dense bias vectors, and ``_nnz``, the kept weights per layer."""
+
+    VALUES = ("mean", "var")
+
+    def _device(self):
+        return self._buf("kept_rows", 0).device
+
+    @property
+    def nnz(self) -> int:
+        """Kept weights over every layer."""
+        return sum(self._nnz)
+
+    @property
+    def operand_bytes(self) -> int:
+        """Bytes of everything the launches read of this model: row_ptr, col, the two value arrays and the two bias vectors."""
+        return sum(4 * (self.dims[i + 1] + 1) + 12 * n + 8 * self.dims[i + 1] for i, n in enumerate(self._nnz))
+
+    def csr(self, i: int):
+        """(row_ptr, col) and the two value arrays (``VALUES``) of layer i."""
+        return tuple(self._buf(k, i) for k in ("row_ptr", "col") + self.VALUES)
+
+    def refresh(self):
+        raise NotImplementedError("bnn_amd: a sparse model does not refresh: the structure, and with it the size of every CSR "
+                                  "buffer, may have changed with the parameters -- freeze again (evaluate.%s(net, \"mpm\", "
+                                  "sparse=True))" % self.FREEZE)
+
+
+def _pack_csr(mod, descs, count: str, pack: str, extra=(), third: str = "var", kept_out=None):
+    """Count, scan, size (the ONE host read), pack -- two batched launches per layer group and one cumsum per layer -- for the
+    layers described by ``descs`` (sources, ``kept_rows`` and the per-row destinations filled in): registers ``row_ptr_<i>``,
+    ``col_<i>``, ``mean_<i>`` and ``<third>_<i>`` on ``mod`` and returns the kept weights as host ints, [layer][level].
+    ``count`` / ``pack``: the C entry points, called with ``extra`` before the stream.  ``kept_rows_<i>`` is (O,), or a sweep's
+    (K, O): the scan then runs level after level, and ``kept_out`` (K, layers) takes the level totals on the device."""
+    from . import _lib
+    n = mod.n_layers
+    dev = mod._buf("kept_rows", 0).device
+    f = dict(dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        for k, cnt in _lib.layer_groups(n):
+            _lib.check(getattr(_lib.lib(), count)(_lib.group_slice(descs, k, cnt), cnt, *extra, stream), count)
+        rows = [mod._buf("kept_rows", i) for i in range(n)]
+        levels = rows[0].dim() == 2                          # a sweep's (K, O)
+        for i, r in enumerate(rows):
+            mod.register_buffer("row_ptr_%d" % i, ops.sparse_row_ptr(r.view(-1) if levels else r))
+        # the totals (layers,), the scans' last entries -- a sweep's (layers, K), level by level
+        kept = torch.stack([r.sum(1) for r in rows] if levels else [mod._buf("row_ptr", i)[-1] for i in range(n)])
+        if kept_out is not None:
+            kept_out.copy_(kept.t())
+        tot = kept.tolist() if levels else [[t] for t in kept.tolist()]                      # the host read
+        for i, t in enumerate(tot):
+            cap = sum(t)
+            # (col comes from _empty too, as fp32 words: a NaN-filled slot that was never packed is an index out of range)
+            mod.register_buffer("col_%d" % i, _empty((cap,), **f).view(torch.int32))
+            mod.register_buffer("mean_%d" % i, _empty((cap,), **f))
+            mod.register_buffer("%s_%d" % (third, i), _empty((cap,), **f))
+            d = descs[i]
+            d.row_ptr, d.nnz = mod._buf("row_ptr", i).data_ptr(), cap
+            d.col, d.mean = mod._buf("col", i).data_ptr(), mod._buf("mean", i).data_ptr()
+            setattr(d, third, mod._buf(third, i).data_ptr())
+        for k, cnt in _lib.layer_groups(n):
+            _lib.check(getattr(_lib.lib(), pack)(_lib.group_slice(descs, k, cnt), cnt, *extra, stream), pack)
+    return tot
+
+
+def _sparse_sources(mod, net, descs):
+    """The LRT / MNF source side of a sparse bind (a model's or a sweep's): the contiguity refusals, the ``bias_mu`` /
+    ``bias_var`` buffers and an MNF layer's ``q0_*`` / ``flow_*`` buffers with ONE fused copy of the small vectors into them,
+    and every field of ``descs`` but the cuts and what ``_pack_csr`` fills in."""
+    layers = net._layers()
+    f = dict(dtype=torch.float32, device=layers[0].weight_mu.device)
+    mod._src = [net]
+    mod._layer_ids = [int(l._layer_id) for l in layers]
+    mod._row_offsets = [int(l.row_offset) for l in layers]
+    for i, l in enumerate(layers):
+        O, If = mod.dims[i + 1], mod.dims[i]
+        for name in ("weight_mu", "weight_rho", "lambdal"):
+            if not getattr(l, name).is_contiguous():
+                raise RuntimeError("bnn_amd: %s of layer %d is not contiguous" % (name, i + 1))
+        for name in ("bias_var", "bias_mu"):
+            mod.register_buffer("%s_%d" % (name, i), _empty((O,), **f))
+        T = len(l.z_flow.transforms) if l._mnf else 0
+        mod._T.append(T)
+        if l._mnf:
+            for name, shape in (("q0_mean", (If,)), ("q0_log_var", (If,)), ("flow_u", (T, If)), ("flow_w", (T, If)),
+                                ("flow_b", (T, 1))):
+                mod.register_buffer("%s_%d" % (name, i), _empty(shape, **f))
+        d = descs[i]
+        d.weight_mu, d.weight_rho, d.lambdal = l.weight_mu.data_ptr(), l.weight_rho.data_ptr(), l.lambdal.data_ptr()
+        d.bias_rho = l.bias_rho.data_ptr()
+        d.bias_var, d.kept_rows = mod._buf("bias_var", i).data_ptr(), mod._buf("kept_rows", i).data_ptr()
+        d.O, d.I = O, If
+    dst, src = _z_copies(mod, layers)
+    dst += [mod._buf("bias_mu", i) for i in range(len(layers))]
+    src += [l.bias_mu.detach() for l in layers]
+    torch._foreach_copy_(dst, src)                           # the small vectors of every layer in one fused copy
+
+
+class SparseFrozenNetwork(_SparseModel, FrozenNetwork):
     """The median probability model as its kept weights alone (``freeze(net, "mpm", sparse=True)``): per layer a CSR of the
     weights with ``lambdal > logit(threshold)`` -- buffers ``row_ptr_<i>`` (O + 1) int32, ``col_<i>`` (nnz) int32 ascending
     within a row, ``mean_<i>`` (nnz) = weight_mu, ``var_<i>`` (nnz) = sigma^2 -- plus the dense ``bias_mu``, ``bias_var`` and
@@ -2277,84 +2379,18 @@ class SparseFrozenNetwork(FrozenNetwork):
     def extra_repr(self) -> str:
         return "%s, sparse, nnz=%d" % (super().extra_repr(), self.nnz)
 
-    def _device(self):
-        return self._buf("kept_rows", 0).device
-
-    @property
-    def nnz(self) -> int:
-        """Kept weights over every layer."""
-        return sum(self._nnz)
-
-    @property
-    def operand_bytes(self) -> int:
-        """Bytes of everything the layer launches read of this model: row_ptr, col, mean, var, bias_mu and bias_var."""
-        return sum(4 * (self.dims[i + 1] + 1) + 12 * n + 8 * self.dims[i + 1] for i, n in enumerate(self._nnz))
-
-    def csr(self, i: int):
-        """(row_ptr, col, mean, var) of layer i."""
-        return tuple(self._buf(k, i) for k in ("row_ptr", "col", "mean", "var"))
-
     @torch.no_grad()
     def _bind(self, net, need=None, masks=None):
-        """Count, scan, size (the ONE host read), pack: two batched launches per layer group and torch's cumsum between."""
         from . import _lib
-        layers = net._layers()
-        dev = layers[0].weight_mu.device
-        f = dict(dtype=torch.float32, device=dev)
         n = self.n_layers
-        self._src = [net]
-        self._layer_ids = [int(l._layer_id) for l in layers]
-        self._row_offsets = [int(l.row_offset) for l in layers]
         self._split = [False] * n
         descs = (_lib.SparseDesc * n)()
-        for i, l in enumerate(layers):
-            O, If = self.dims[i + 1], self.dims[i]
-            for name in ("weight_mu", "weight_rho", "lambdal"):
-                if not getattr(l, name).is_contiguous():
-                    raise RuntimeError("bnn_amd: %s of layer %d is not contiguous" % (name, i + 1))
-            for name in ("bias_var", "bias_mu"):
-                self.register_buffer("%s_%d" % (name, i), _empty((O,), **f))
-            if l._mnf:
-                T = len(l.z_flow.transforms)
-                self._T.append(T)
-                for name, shape in (("q0_mean", (If,)), ("q0_log_var", (If,)), ("flow_u", (T, If)), ("flow_w", (T, If)),
-                                    ("flow_b", (T, 1))):
-                    self.register_buffer("%s_%d" % (name, i), _empty(shape, **f))
-            else:
-                self._T.append(0)
-            d = descs[i]
-            d.weight_mu, d.weight_rho, d.lambdal = l.weight_mu.data_ptr(), l.weight_rho.data_ptr(), l.lambdal.data_ptr()
-            d.bias_rho = l.bias_rho.data_ptr()
-            d.bias_var, d.kept_rows = self._buf("bias_var", i).data_ptr(), self._buf("kept_rows", i).data_ptr()
-            d.O, d.I, d.cut = O, If, self.cut
-        dst, src = self._z_copies(layers)
-        dst += [self._buf("bias_mu", i) for i in range(n)]
-        src += [l.bias_mu.detach() for l in layers]
-        torch._foreach_copy_(dst, src)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            for k, cnt in _lib.layer_groups(n):
-                _lib.check(_lib.lib().lbbnn_sparse_count(_lib.group_slice(descs, k, cnt), cnt, stream), "lbbnn_sparse_count")
-            for i in range(n):
-                self.register_buffer("row_ptr_%d" % i, ops.sparse_row_ptr(self._buf("kept_rows", i)))
-            self._nnz = [int(v) for v in torch.stack([self._buf("row_ptr", i)[-1] for i in range(n)]).tolist()]   # the host read
-            for i, nz in enumerate(self._nnz):
-                # (col comes from _empty too, as fp32 words: a NaN-filled slot that was never packed is an index out of range)
-                self.register_buffer("col_%d" % i, _empty((nz,), **f).view(torch.int32))
-                self.register_buffer("mean_%d" % i, _empty((nz,), **f))
-                self.register_buffer("var_%d" % i, _empty((nz,), **f))
-                d = descs[i]
-                d.row_ptr, d.nnz = self._buf("row_ptr", i).data_ptr(), nz
-                d.col, d.mean, d.var = (self._buf(k, i).data_ptr() for k in ("col", "mean", "var"))
-            for k, cnt in _lib.layer_groups(n):
-                _lib.check(_lib.lib().lbbnn_sparse_pack(_lib.group_slice(descs, k, cnt), cnt, stream), "lbbnn_sparse_pack")
+        _sparse_sources(self, net, descs)
+        for d in descs:
+            d.cut = self.cut
+        self._nnz = [t[0] for t in _pack_csr(self, descs, "lbbnn_sparse_count", "lbbnn_sparse_pack")]
         self._point()
         return self
-
-    def refresh(self):
-        raise NotImplementedError("bnn_amd: a sparse model does not refresh: the structure, and with it the size of every CSR "
-                                  "buffer, may have changed with the parameters -- freeze again (evaluate.freeze(net, \"mpm\", "
-                                  "sparse=True))")
 
     def _member_buffers(self, c: int):
         """z [c][sum of ld], every MNF layer's block side by side (one member stride, one flow launch); no member operands."""
@@ -2535,66 +2571,14 @@ class ThresholdSweep(nn.Module):
 
     @torch.no_grad()
     def _bind(self, net):
-        """Count, scan, size (the ONE host read), pack: two batched launches per layer group and one cumsum per layer."""
         from . import _lib
-        layers = net._layers()
-        dev = layers[0].weight_mu.device
-        f = dict(dtype=torch.float32, device=dev)
-        n, K = self.n_layers, len(self.cuts)
-        self._src = [net]
-        self._layer_ids = [int(l._layer_id) for l in layers]
-        self._row_offsets = [int(l.row_offset) for l in layers]
-        descs = (_lib.SparseLevelsDesc * n)()
-        dst, src = [], []
-        for i, l in enumerate(layers):
-            O, If = self.dims[i + 1], self.dims[i]
-            for name in ("weight_mu", "weight_rho", "lambdal"):
-                if not getattr(l, name).is_contiguous():
-                    raise RuntimeError("bnn_amd: %s of layer %d is not contiguous" % (name, i + 1))
-            for name in ("bias_var", "bias_mu"):
-                self.register_buffer("%s_%d" % (name, i), _empty((O,), **f))
-            dst.append(self._buf("bias_mu", i)); src.append(l.bias_mu.detach())
-            T = len(l.z_flow.transforms) if l._mnf else 0
-            self._T.append(T)
-            if l._mnf:
-                for name, shape in (("q0_mean", (If,)), ("q0_log_var", (If,)), ("flow_u", (T, If)), ("flow_w", (T, If)),
-                                    ("flow_b", (T, 1))):
-                    self.register_buffer("%s_%d" % (name, i), _empty(shape, **f))
-                dst += [self._buf("q0_mean", i), self._buf("q0_log_var", i)]
-                src += [l.q0_mean.detach(), l.q0_log_var.detach()]
-                for t, tr in enumerate(l.z_flow.transforms):
-                    dst += [self._buf("flow_u", i)[t], self._buf("flow_w", i)[t], self._buf("flow_b", i)[t]]
-                    src += [tr.u.detach().reshape(-1), tr.w.detach().reshape(-1), tr.bias.detach().reshape(-1)]
-            d = descs[i]
-            d.weight_mu, d.weight_rho, d.lambdal = l.weight_mu.data_ptr(), l.weight_rho.data_ptr(), l.lambdal.data_ptr()
-            d.bias_rho = l.bias_rho.data_ptr()
-            d.bias_var, d.kept_rows = self._buf("bias_var", i).data_ptr(), self._buf("kept_rows", i).data_ptr()
-            d.O, d.I, d.levels = O, If, K
+        descs = (_lib.SparseLevelsDesc * self.n_layers)()
+        _sparse_sources(self, net, descs)
+        for d in descs:
+            d.levels = len(self.cuts)
             for j, c in enumerate(self.cuts):
                 d.cut[j] = c
-        torch._foreach_copy_(dst, src)                       # the small vectors of every layer in one fused copy
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            for k, cnt in _lib.layer_groups(n):
-                _lib.check(_lib.lib().lbbnn_sparse_count_levels(_lib.group_slice(descs, k, cnt), cnt, stream),
-                           "lbbnn_sparse_count_levels")
-            for i in range(n):
-                self.register_buffer("row_ptr_%d" % i, ops.sparse_row_ptr(self._buf("kept_rows", i).view(-1)))
-            kept = torch.stack([self._buf("kept_rows", i).sum(1) for i in range(n)])         # (layers, K) int64
-            self.kept.copy_(kept.t())
-            self._tot = [[int(v) for v in row] for row in kept.tolist()]                     # the host read
-            for i, tot in enumerate(self._tot):
-                cap = sum(tot)
-                # (col comes from _empty too, as fp32 words: a NaN-filled slot that was never packed is an index out of range)
-                self.register_buffer("col_%d" % i, _empty((cap,), **f).view(torch.int32))
-                self.register_buffer("mean_%d" % i, _empty((cap,), **f))
-                self.register_buffer("var_%d" % i, _empty((cap,), **f))
-                d = descs[i]
-                d.row_ptr, d.nnz = self._buf("row_ptr", i).data_ptr(), cap
-                d.col, d.mean, d.var = (self._buf(k, i).data_ptr() for k in ("col", "mean", "var"))
-            for k, cnt in _lib.layer_groups(n):
-                _lib.check(_lib.lib().lbbnn_sparse_pack_levels(_lib.group_slice(descs, k, cnt), cnt, stream),
-                           "lbbnn_sparse_pack_levels")
+        self._tot = _pack_csr(self, descs, "lbbnn_sparse_count_levels", "lbbnn_sparse_pack_levels", kept_out=self.kept)
         return self
 
     # ------------------------------------------------------------------------------------- the buffers move
@@ -3180,7 +3164,38 @@ def freeze_base(net, gates: str = "sample", *, threshold: float = 0.5, compact: 
 
 
 
-class SparseFrozenBaseNetwork(_FrozenModel):
+def _transposed_input(x, stream):
+    """x^T [I0][sparse_row_pad(B)], what the first layer of every explicit-weight member reads: one launch."""
+    from . import _lib
+    B, I = x.shape
+    ldb = ops.sparse_row_pad(B)
+    xT = _empty((I, ldb), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().lbbnn_transpose_operand(ops._ptr_rows(x, "x"), B, I, x.stride(0), xT.data_ptr(), ldb, 0, 0, stream),
+               "lbbnn_transpose_operand")
+    return xT
+
+
+def _stored_forward(fz, xT, B: int, wb, out, stream, hidden=None):
+    """The forward of explicit-weight members of a sparse model on their stored values ``wb`` (per layer (w, b, ...), rows =
+    members), from ``_transposed_input``: one lbbnn_sparse_gather_members FORWARD launch per layer -- hidden layers transposed
+    [member][unit][sparse_row_pad(B)] with ReLU (appended to ``hidden`` where the caller keeps them), the last written
+    row-major into ``out`` (members, B * classes)."""
+    from . import _lib
+    n, dims, ldb, c = fz.n_layers, fz.dims, xT.shape[1], out.shape[0]
+    a, a_ms = xT, 0
+    for i in range(n):
+        O, last = dims[i + 1], i == n - 1
+        o = out if last else _empty((c, O * ldb), dtype=torch.float32, device=xT.device)
+        ops.sparse_gather_members(_lib.GATHER_FORWARD, fz._buf("row_ptr", i), fz._buf("col", i), None, wb[i][0], a, o,
+                                  B=B, K=dims[i], N=O, lda=ldb, a_mstride=a_ms, ldo=O if last else ldb,
+                                  o_mstride=out.stride(0) if last else O * ldb, blocks=c, bias=wb[i][1], relu=not last,
+                                  out_rows=last, stream=stream)
+        if hidden is not None and not last:
+            hidden.append(o)
+        a, a_ms = o, O * ldb                                 # (a keeps the buffer alive until the launch that reads it is queued)
+
+
+class SparseFrozenBaseNetwork(_SparseModel, _FrozenModel):
     """The median probability model of a baseline LBBNN network as its kept weights alone (``freeze_base(net, "mpm",
     sparse=True)``): per layer a CSR of the weights with sigmoid(lambdal) > threshold (the comparison of the dense frozen
     model, made by the kernel in fp32) -- buffers ``row_ptr_<i>`` (O + 1) int32, ``col_<i>`` (nnz) int32 ascending within a row,
@@ -3197,7 +3212,7 @@ class SparseFrozenBaseNetwork(_FrozenModel):
     ``col_ptr_<i>`` (I + 1), ``trow_<i>``, ``tslot_<i>``, ``tpos_<i>`` (nnz): the pattern column by column.  No ``refresh()``:
     freeze again."""
 
-    GATES, FREEZE = ("mpm",), "freeze_base"
+    GATES, FREEZE, VALUES = ("mpm",), "freeze_base", ("mean", "sigma")
     GATES_DOC = "'mpm' (a sparse model is the median probability model)"
     _POINTER_STATE = ("_draw_descs",)
 
@@ -3212,30 +3227,11 @@ class SparseFrozenBaseNetwork(_FrozenModel):
         head = ", head=%s" % self.head if self.head != "log_softmax" else ""
         return "dims=%s, family=base, gates=mpm, threshold=%g%s, sparse, nnz=%d" % (self.dims, self.threshold, head, self.nnz)
 
-    def _device(self):
-        return self._buf("kept_rows", 0).device
-
-    @property
-    def nnz(self) -> int:
-        """Kept weights over every layer."""
-        return sum(self._nnz)
-
-    @property
-    def operand_bytes(self) -> int:
-        """Bytes of everything the draw reads of this model: row_ptr, col, mean, sigma, b_mu and b_sigma."""
-        return sum(4 * (self.dims[i + 1] + 1) + 12 * n + 8 * self.dims[i + 1] for i, n in enumerate(self._nnz))
-
-    def csr(self, i: int):
-        """(row_ptr, col, mean, sigma) of layer i."""
-        return tuple(self._buf(k, i) for k in ("row_ptr", "col", "mean", "sigma"))
-
     @torch.no_grad()
     def _bind(self, net):
-        """Count, scan, size (the ONE host read), pack: two batched launches per layer group and torch's cumsum between."""
         from . import _lib
         layers = net._layers()
-        dev = layers[0].weight_mu.device
-        f = dict(dtype=torch.float32, device=dev)
+        f = dict(dtype=torch.float32, device=layers[0].weight_mu.device)
         n = self.n_layers
         self._src = [net]
         self._layer_ids = [int(l._layer_id) for l in layers]
@@ -3250,25 +3246,8 @@ class SparseFrozenBaseNetwork(_FrozenModel):
             d.b_mu, d.b_sigma = self._buf("b_mu", i).data_ptr(), self._buf("b_sigma", i).data_ptr()
             d.kept_rows = self._buf("kept_rows", i).data_ptr()
             d.O, d.I = O, self.dims[i]
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            for k, cnt in _lib.layer_groups(n):
-                _lib.check(_lib.lib().lbbnn_base_sparse_count(_lib.group_slice(descs, k, cnt), cnt, self.threshold, stream),
-                           "lbbnn_base_sparse_count")
-            for i in range(n):
-                self.register_buffer("row_ptr_%d" % i, ops.sparse_row_ptr(self._buf("kept_rows", i)))
-            self._nnz = [int(v) for v in torch.stack([self._buf("row_ptr", i)[-1] for i in range(n)]).tolist()]   # the host read
-            for i, nz in enumerate(self._nnz):
-                # (col comes from _empty too, as fp32 words: a NaN-filled slot that was never packed is an index out of range)
-                self.register_buffer("col_%d" % i, _empty((nz,), **f).view(torch.int32))
-                self.register_buffer("mean_%d" % i, _empty((nz,), **f))
-                self.register_buffer("sigma_%d" % i, _empty((nz,), **f))
-                d = descs[i]
-                d.row_ptr, d.nnz = self._buf("row_ptr", i).data_ptr(), nz
-                d.col, d.mean, d.sigma = (self._buf(k, i).data_ptr() for k in ("col", "mean", "sigma"))
-            for k, cnt in _lib.layer_groups(n):
-                _lib.check(_lib.lib().lbbnn_base_sparse_pack(_lib.group_slice(descs, k, cnt), cnt, self.threshold, stream),
-                           "lbbnn_base_sparse_pack")
+        self._nnz = [t[0] for t in _pack_csr(self, descs, "lbbnn_base_sparse_count", "lbbnn_base_sparse_pack", (self.threshold,),
+                                             "sigma")]
         self._point()
         return self
 
@@ -3283,11 +3262,6 @@ class SparseFrozenBaseNetwork(_FrozenModel):
             d.row_ptr, d.col, d.mean, d.sigma = (t.data_ptr() for t in self.csr(i))
             d.b_mu, d.b_sigma = self._buf("b_mu", i).data_ptr(), self._buf("b_sigma", i).data_ptr()
             d.O, d.I, d.nnz, d.layer_id = self.dims[i + 1], self.dims[i], self._nnz[i], self._layer_ids[i]
-
-    def refresh(self):
-        raise NotImplementedError("bnn_amd: a sparse model does not refresh: the structure, and with it the size of every CSR "
-                                  "buffer, may have changed with the parameters -- freeze again (evaluate.freeze_base(net, "
-                                  "\"mpm\", sparse=True))")
 
     # ------------------------------------------------------------------------------------- evaluation
     def _draw(self, c: int, rng, stream, tpos=None, weight_noise: bool = True):
@@ -3310,33 +3284,6 @@ class SparseFrozenBaseNetwork(_FrozenModel):
                                                            rng.data_ptr() if weight_noise else None, 1,
                                                            0 if weight_noise else ops.F_MEAN_ONLY, stream)
             _lib.check(rc, "lbbnn_base_sparse_draw_members")
-        return out
-
-    def _transpose(self, x, stream):
-        """x^T [I0][sparse_row_pad(B)], what every member's first layer reads: one launch."""
-        from . import _lib
-        B, I = x.shape
-        ldb = ops.sparse_row_pad(B)
-        xT = _empty((I, ldb), dtype=torch.float32, device=x.device)
-        _lib.check(_lib.lib().lbbnn_transpose_operand(ops._ptr_rows(x, "x"), B, I, x.stride(0), xT.data_ptr(), ldb, 0, 0, stream),
-                   "lbbnn_transpose_operand")
-        return xT
-
-    def _layers_forward(self, xT, B: int, c: int, wb, out, stream):
-        """One lbbnn_sparse_gather_members FORWARD launch per layer on the stored values ``wb`` (per layer (w, b, ...), rows =
-        members): hidden layers transposed [member][unit][sparse_row_pad(B)] with ReLU, the last written row-major into ``out``
-        (c, B * classes)."""
-        from . import _lib
-        n, dims, ldb = self.n_layers, self.dims, xT.shape[1]
-        a, a_ms = xT, 0
-        for i in range(n):
-            O, last = dims[i + 1], i == n - 1
-            o = out if last else _empty((c, O * ldb), dtype=torch.float32, device=xT.device)
-            ops.sparse_gather_members(_lib.GATHER_FORWARD, self._buf("row_ptr", i), self._buf("col", i), None, wb[i][0], a, o,
-                                      B=B, K=dims[i], N=O, lda=ldb, a_mstride=a_ms, ldo=O if last else ldb,
-                                      o_mstride=out.stride(0) if last else O * ldb, blocks=c, bias=wb[i][1], relu=not last,
-                                      out_rows=last, stream=stream)
-            a, a_ms = o, O * ldb                             # (a keeps the buffer alive until the launch that reads it is queued)
         return out
 
     def _head(self, buf, S: int, B: int, log_probs: bool):
@@ -3374,14 +3321,14 @@ class SparseFrozenBaseNetwork(_FrozenModel):
                 st.advance(S)
                 return torch.zeros((S, 0, 2 if log_probs else C), dtype=torch.float32, device=dev)
             stream = torch.cuda.current_stream(dev).cuda_stream
-            xT = self._transpose(x, stream)
+            xT = _transposed_input(x, stream)
             buf = _empty((S, B * C), dtype=torch.float32, device=dev)
             for m0 in range(0, S, chunk):
                 c = min(chunk, S - m0)
                 wb = self._draw(c, st.t, stream)
                 if kept is not None:
                     kept.append(wb)
-                self._layers_forward(xT, B, c, wb, buf[m0:m0 + c], stream)
+                _stored_forward(self, xT, B, wb, buf[m0:m0 + c], stream)
                 st.advance(c)                                # as c single forwards would have
             if kept is not None:
                 self.last_weights = [torch.cat([k[i][0] for k in kept])[:, :nz] for i, nz in enumerate(self._nnz)]
@@ -3404,7 +3351,7 @@ class SparseFrozenBaseNetwork(_FrozenModel):
             stream = torch.cuda.current_stream(dev).cuda_stream
             buf = _empty((1, B * C), dtype=torch.float32, device=dev)
             wb = [(self._buf("mean", i).view(1, -1), self._buf("b_mu", i).view(1, -1)) for i in range(self.n_layers)]
-            self._layers_forward(self._transpose(x, stream), B, 1, wb, buf, stream)
+            _stored_forward(self, _transposed_input(x, stream), B, wb, buf, stream)
             return self._head(buf, 1, B, log_probs)[0]
 
 
@@ -3864,21 +3811,9 @@ def explain_ensemble(fz, data: torch.Tensor, samples: int = 10, *, targets=None,
             return res
         # the members' forward: every hidden layer kept, transposed [member][unit][ldb]
         ldb = ops.sparse_row_pad(B)
-        xT = _empty((F, ldb), **f)
-        _lib.check(_lib.lib().lbbnn_transpose_operand(ops._ptr_rows(x, "x"), B, F, x.stride(0), xT.data_ptr(), ldb, 0, 0, stream),
-                   "lbbnn_transpose_operand")
+        xT, hs = _transposed_input(x, stream), []
         logits = _empty((S, B, C), **f)
-        hs, a, a_ms = [], xT, 0
-        for i in range(n):
-            row_ptr, col, _, _ = csrs[i]
-            O, last = dims[i + 1], i == n - 1
-            o = logits if last else _empty((S, O * ldb), **f)
-            ops.sparse_gather_members(_lib.GATHER_FORWARD, row_ptr, col, None, wb[i][0], a, o, B=B, K=dims[i], N=O, lda=ldb,
-                                      a_mstride=a_ms, ldo=C if last else ldb, o_mstride=B * C if last else O * ldb, blocks=S,
-                                      bias=wb[i][1], relu=not last, out_rows=last, stream=stream)
-            if not last:
-                hs.append(o)
-                a, a_ms = o, O * ldb
+        _stored_forward(fz, xT, B, wb, logits.view(S, B * C), stream, hidden=hs)
         if keep_masks:
             res["masks"] = [(h.view(S, dims[l + 1], ldb)[:, :, :B] > 0).transpose(1, 2).contiguous() for l, h in enumerate(hs)]
         # where the sweep starts, one launch: the explained output ("pred": the largest member-mean logit), the one-hot seed
