@@ -8,7 +8,7 @@ from ._lib import LIB_PATH, Priors  # noqa: F401
 from .layers import (LRTBayesianLinear, LRTBayesianNetwork, MNFBayesianLinear,  # noqa: F401
                      MNFBayesianNetwork)
 from .ops import get_precision, manual_seed, set_precision  # noqa: F401
-from . import base, evaluate, flows, graphs, losses, lrt, mnf, optim, parallel, vd  # noqa: F401
+from . import base, evaluate, flows, graphs, losses, lrt, mnf, optim, parallel, study, vd  # noqa: F401
 from .losses import TrainMonitor, elbo_bce_loss, elbo_gaussian_loss, elbo_loss  # noqa: F401
 from .evaluate import FrozenNetwork, freeze  # noqa: F401
 from .evaluate import FrozenBaseNetwork, SparseFrozenBaseNetwork, freeze_base  # noqa: F401

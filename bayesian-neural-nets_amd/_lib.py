@@ -162,6 +162,18 @@ class SgdHyper(ctypes.Structure):
                 ("weight_decay", ctypes.c_float), ("flags", c_u32)]
 
 
+class StudyArgs(ctypes.Structure):
+    """lbbnn_study_args_t"""
+    _fields_ = [("params", c_p), ("exp_avg", c_p), ("exp_avg_sq", c_p), ("step", c_p), ("rng", c_p), ("skipped", c_p),
+                ("x", c_p), ("x_rstride", c_i64), ("y", c_p), ("y_rstride", c_i64), ("priors", c_p), ("priors_rstride", c_i),
+                ("hyper", c_p), ("lr", c_p), ("lr_rstride", c_i64), ("restarts", c_p), ("n_restarts", c_i), ("history", c_p),
+                ("R", c_i), ("I", c_i), ("O", c_i), ("N", c_i), ("batch", c_i),
+                ("epochs", c_i), ("first_epoch", c_i), ("n_epochs", c_i)]
+
+
+STUDY_MAX_I, STUDY_MAX_O, STUDY_MAX_WEIGHTS, STUDY_MAX_BATCH, STUDY_HISTORY_COLS = 256, 16, 1024, 4096, 6     # LBBNN_STUDY_*
+
+
 class CopyList(ctypes.Structure):
     """lbbnn_copy_list_t"""
     _fields_ = [("dst", c_p * ADAM_MAX_TENSORS), ("src", c_p * ADAM_MAX_TENSORS), ("numel", c_i64 * ADAM_MAX_TENSORS), ("n", c_i)]
@@ -466,6 +478,7 @@ SIGNATURES = {
     "lbbnn_sgd_step_groups": (c_i, [ctypes.POINTER(AdamGroupList), c_p, c_p, c_i, c_p, c_p, c_i, c_p]),
     "lbbnn_adam_step_groups_guarded": (c_i, [ctypes.POINTER(AdamGroupList), c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p]),
     "lbbnn_sgd_step_groups_guarded": (c_i, [ctypes.POINTER(AdamGroupList), c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p]),
+    "lbbnn_lrt_study_fit": (c_i, [ctypes.POINTER(StudyArgs), c_p]),
     "lbbnn_grad_sumsq_workspace": (c_i64, [c_i64]),
     "lbbnn_grad_sumsq": (c_i, [ctypes.POINTER(AdamGroupList), c_p, c_i64, c_i64, ctypes.c_float, c_p, c_p, c_p]),
     "lbbnn_matmul_splitk": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),

@@ -1277,6 +1277,48 @@ def gate_structure(descs, n: int, samples: int, rng: torch.Tensor, *, kept, need
                                                p(feature_count), p(unit_count), p(need_out), _stream()), "lbbnn_gate_structure")
 
 
+def lrt_study_fit(*, params, exp_avg, exp_avg_sq, step, rng, skipped, x, y, priors, hyper, lr, restarts, history,
+                  I: int, O: int, batch: int, first_epoch: int, n_epochs: int):
+    """lbbnn_lrt_study_fit on caller-allocated device tensors (bnn_amd.study lays them out): ``params`` / ``exp_avg`` /
+    ``exp_avg_sq`` (R, 3 O I + 2 O) and ``step`` (R) float32, ``rng`` (R, 2) and ``skipped`` (R) int64, ``x`` (N, I) or (R, N, I),
+    ``y`` (N, O) or (R, N, O), ``priors`` (1 or R, 5) and ``hyper`` (R, 6) float32 rows of lbbnn_priors_t / lbbnn_adam_hyper_t,
+    ``lr`` (epochs) or (R, epochs), ``restarts`` int32 or None, ``history`` (R, epochs, 6) float64.  One launch; everything in
+    the first row is updated in place."""
+    R, epochs = params.shape[0], history.shape[1]
+    P = 3 * O * I + 2 * O
+    checks = [("params", params, torch.float32, (R, P)), ("exp_avg", exp_avg, torch.float32, (R, P)),
+              ("exp_avg_sq", exp_avg_sq, torch.float32, (R, P)), ("step", step, torch.float32, (R,)),
+              ("rng", rng, torch.int64, (R, 2)), ("skipped", skipped, torch.int64, (R,)),
+              ("hyper", hyper, torch.float32, (R, 6)), ("history", history, torch.float64, (R, epochs, _lib.STUDY_HISTORY_COLS)),
+              ("x", x, torch.float32, None), ("y", y, torch.float32, None), ("priors", priors, torch.float32, None),
+              ("lr", lr, torch.float32, None), ("restarts", restarts, torch.int32, None)]
+    for name, t, dt, shape in checks:
+        if t is None and name == "restarts":
+            continue
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape):
+            raise RuntimeError("bnn_amd: %s must be a contiguous %s tensor%s on a HIP device (no CPU path)"
+                               % (name, dt, "" if shape is None else " of shape %s" % (shape,)))
+    N = x.shape[-2]
+    if x.shape not in ((N, I), (R, N, I)) or y.shape not in ((N, O), (R, N, O)):
+        raise ValueError("bnn_amd: x must be (N, I) or (R, N, I) and y (N, O) or (R, N, O), got %s and %s"
+                         % (tuple(x.shape), tuple(y.shape)))
+    if priors.shape not in ((1, 5), (R, 5)) or lr.shape not in ((epochs,), (R, epochs)):
+        raise ValueError("bnn_amd: priors must be (1 | R, 5) and lr (epochs) or (R, epochs)")
+    a = _lib.StudyArgs()
+    a.params, a.exp_avg, a.exp_avg_sq = params.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr()
+    a.step, a.rng, a.skipped = step.data_ptr(), rng.data_ptr(), skipped.data_ptr()
+    a.x, a.x_rstride = x.data_ptr(), (N * I if x.dim() == 3 else 0)
+    a.y, a.y_rstride = y.data_ptr(), (N * O if y.dim() == 3 else 0)
+    a.priors, a.priors_rstride = priors.data_ptr(), (1 if priors.shape[0] == R and R > 1 else 0)
+    a.hyper, a.lr, a.lr_rstride = hyper.data_ptr(), lr.data_ptr(), (epochs if lr.dim() == 2 else 0)
+    n_restarts = 0 if restarts is None else restarts.numel()
+    a.restarts, a.n_restarts = (restarts.data_ptr() if n_restarts else None), n_restarts
+    a.history = history.data_ptr()
+    a.R, a.I, a.O, a.N, a.batch = R, I, O, N, batch
+    a.epochs, a.first_epoch, a.n_epochs = epochs, first_epoch, n_epochs
+    _lib.check(_lib.lib().lbbnn_lrt_study_fit(ctypes.byref(a), _stream()), "lbbnn_lrt_study_fit")
+
+
 # ----------------------------------------------------------------------------------------- workspaces
 class LayerWorkspace:
     """Caller-owned device buffers of one layer, allocated once and reused every forward

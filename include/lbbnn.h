@@ -2282,6 +2282,64 @@ int lbbnn_base_sparse_pack(const lbbnn_base_sparse_desc_t* layers, int n, float 
 int lbbnn_base_sparse_draw_members(const lbbnn_base_sparse_draw_desc_t* layers, int n, int members, const uint64_t* rng,
                                    uint64_t member_advance, int flags, void* stream);
 
+/* ---- replicate study: R independent one-layer LRT fits in one launch (lrt_study.hip) ----
+ *
+ * lbbnn_lrt_study_fit: trains R one-layer LRT networks I -> O with a sigmoid head on BCELoss(sum) + kl * batch / N
+ *   (LBBNN-GP-MF-MNFsim_study.py:305-395 with an LRT layer) for epochs first_epoch .. first_epoch + n_epochs - 1 in ONE
+ *   launch: grid = R workgroups of 256 threads, replicate r is workgroup r.  A workgroup touches replicate r's slices only;
+ *   there is no communication between workgroups (no atomics, no flags) and every loop bound is one of the counts below.
+ *   An epoch is ceil(N / batch) steps over rows [k batch, min((k + 1) batch, N)) in order (the last batch may be short).
+ *   State, loaded once, kept on chip for all steps of the launch, stored once (plain vector stores):
+ *     params / exp_avg / exp_avg_sq  (R, 3 O I + 2 O): per replicate [weight_mu | weight_rho | lambdal | bias_mu | bias_rho]
+ *     step (R) float Adam counters; rng (R, 2) {seed, offset}; skipped (R) running count of skipped steps.
+ *   Step t of a replicate draws eps_out from philox_normal4 with state {seed, offset}, stream LBBNN_STREAM_EPS_OUT * 64 + 0,
+ *   counter (b, o / 4), word o % 4, b the row INSIDE the batch -- layer l1 of a network -- and then offset += 1, skipped steps
+ *   included.  alpha / sigma, the products, the head, the BCE term and its counts, the KL (LBBNN-GP-MF-LRT.py:185-194), the
+ *   analytic backward and Adam use the expressions of weight_pass.hip, binary_head.hip, weight_pass_bwd.hip, vector_bwd.hip
+ *   and adam.hip (hyper[r]: beta1, beta2, eps, coupled weight_decay; its lr and flags are not read).  Sums over rows have a
+ *   fixed order: a replicate's bits depend on its own inputs only, and two launches of E / 2 epochs give the bits of one of E.
+ *   lr: the rate of epoch e is lr[r * lr_rstride + e] (lr_rstride 0: one (epochs) table for all; else >= epochs).
+ *   restarts: n_restarts epoch indices at whose start the moments and the step counter are zeroed (a re-created optim.Adam).
+ *   x: (N, I) rows at x + r * x_rstride (0: shared); y: (N, O) floats at y + r * y_rstride; priors[r * priors_rstride]
+ *   (priors_rstride 0 or 1).  All of these are DEVICE memory.
+ *   Guard: a step whose fp32 loss is not finite, or whose batch has a probability that is not finite, changes no parameter,
+ *   moment or step counter and adds 1 to skipped[r].
+ *   history (R, epochs, 6) float64, row (r, e) written by workgroup r for the epochs of this launch: mean loss and mean nll
+ *   over the steps that were not skipped (NaN without one), correct elements / elements, the last step's fp32 loss and its
+ *   nll, skipped steps of the epoch.
+ *   Checks, before the launch: a NULL struct or pointer (restarts with n_restarts > 0): LBBNN_E_NULL; I outside [1,
+ *   LBBNN_STUDY_MAX_I], O outside [1, LBBNN_STUDY_MAX_O], O * I > LBBNN_STUDY_MAX_WEIGHTS, batch outside [1,
+ *   LBBNN_STUDY_MAX_BATCH], N < 1, R outside [1, 65535], n_epochs < 0, first_epoch < 0, first_epoch + n_epochs > epochs,
+ *   n_restarts < 0, a stride that is neither 0 nor at least its block: LBBNN_E_SHAPE; a pointer off 4 B (rng, skipped,
+ *   history: 8 B): LBBNN_E_ALIGN.  n_epochs == 0: a successful no-op; otherwise ONE launch. */
+#define LBBNN_STUDY_MAX_I 256
+#define LBBNN_STUDY_MAX_O 16
+#define LBBNN_STUDY_MAX_WEIGHTS 1024
+#define LBBNN_STUDY_MAX_BATCH 4096
+#define LBBNN_STUDY_HISTORY_COLS 6
+typedef struct lbbnn_study_args {
+    float *params, *exp_avg, *exp_avg_sq;            /* (R, 3 O I + 2 O)                        */
+    float* step;                                     /* (R)                                     */
+    uint64_t* rng;                                   /* (R, 2): {seed, offset}                  */
+    int64_t* skipped;                                /* (R)                                     */
+    const float* x;                                  /* (N, I) per replicate or shared          */
+    int64_t x_rstride;
+    const float* y;                                  /* (N, O) per replicate or shared          */
+    int64_t y_rstride;
+    const lbbnn_priors_t* priors;                    /* 1 or R rows                             */
+    int priors_rstride;
+    const lbbnn_adam_hyper_t* hyper;                 /* (R)                                     */
+    const float* lr;                                 /* (epochs) or (R, lr_rstride)             */
+    int64_t lr_rstride;
+    const int32_t* restarts;                         /* (n_restarts) epoch indices, or NULL     */
+    int n_restarts;
+    double* history;                                 /* (R, epochs, 6)                          */
+    int R, I, O, N, batch;
+    int epochs, first_epoch, n_epochs;
+} lbbnn_study_args_t;
+
+int lbbnn_lrt_study_fit(const lbbnn_study_args_t* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
