@@ -505,6 +505,8 @@ SIGNATURES = {
                                    c_p, c_p, c_p, c_u32, c_p, c_p, c_p, c_p, c_i, c_i, c_p]),
     "lbbnn_kl_finalize": (c_i, [c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p,
                                 ctypes.POINTER(Priors), c_p, c_u32, c_p, c_p, c_i, c_p]),
+    "lbbnn_flow_planar_form": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_i]),
+    "lbbnn_kl_finalize_form": (c_i, [c_i, c_p, c_p, c_p, c_p, c_i]),
     "lbbnn_layers_prepare": (c_i, [ctypes.POINTER(LayerDesc), c_i, c_p, c_p]),
     "lbbnn_layers_operands_snap": (c_i, [ctypes.POINTER(LayerDesc), c_i, c_p, c_p, c_u64, c_p]),
     "lbbnn_layers_operands_x": (c_i, [ctypes.POINTER(LayerDesc), c_i, c_p, c_p, c_u64, c_p, c_i, c_p, c_i, c_i, c_i, c_p]),

@@ -213,8 +213,10 @@ __global__ __launch_bounds__(256) void mnf_flow_planar_lds_kernel(const FlowBatc
 //     w_t . z_t = w_t . z_0 + sum_{s<t} th_s (w_t . u_s)
 // and every dot product the whole chain needs -- w_t.z_0, w_t.u_s (s < t), u_t.w_t -- depends on the inputs only.
 // They are accumulated in one sweep and reduced in ONE block reduction (<= 14 values + log_q0); the th_t / log-det
-// chain is then scalar arithmetic, and z is written in one more sweep (terms added in transform order, so z is
-// bit-identical to the step-by-step form; the r flow needs no sweep at all: only its log-dets and z_b[-1] are used).
+// chain is then scalar arithmetic, and z is written in one more sweep (terms added in transform order, as in the
+// step-by-step form; th_t comes from this expanded sum instead of w_t . (rounded z_t), so z agrees with that form to
+// rounding -- same bits at I = 257, 4.8e-8 of max|z| apart at I = 2049, test_fast_form_z_against_the_step_by_step_form;
+// the r flow needs no sweep at all: only its log-dets and z_b[-1] are used).
 constexpr int kFastT = 4;
 
 constexpr int kFastThreads = 512, kFastWaves = kFastThreads / 64;
@@ -333,8 +335,9 @@ __global__ __launch_bounds__(kFastThreads) void mnf_flow_planar_fast_kernel(cons
 // float4s are requested back to back straight into registers (one memory latency, no LDS round trip), ONE Philox call
 // gives its four draws, the 15 partial sums are floats over four elements, reduced per wave by DPP in float and combined
 // across the 8 waves in double in a fixed order (deterministic), tanh through one hardware exp (tanh_fast: ~1e-7
-// absolute), z written as float4.  Same draws, same z0 bits; the dot products differ from the double-accumulated form by
-// ~1e-7 relative.
+// absolute), z written as float4.  Same draws; z0 is NOT the LDS forms' bits (hardware exp2 / sqrt here, expf / sqrtf there:
+// about one element in ten differs in its last bit, 5e-8 of max|z| at most, test_register_form_z0_against_the_lds_forms);
+// the dot products differ from the double-accumulated form by ~1e-7 relative.
 constexpr int kVecThreads = 512;
 
 __global__ __launch_bounds__(kVecThreads) void mnf_flow_planar_vec_kernel(const FlowBatch bt) {
@@ -748,6 +751,51 @@ bool fill_set(PlanarSet& ps, const float* const* u, const float* const* w, const
     return true;
 }
 
+// ---- which form a launch takes.  ONE host function per kernel kind: the launchers below launch from its answer, and
+// lbbnn_flow_planar_form / lbbnn_kl_finalize_form return the same answer to the host (no pointer, no GPU).
+struct FlowShape { int I, Tz, Tr, want_kl, aligned16; };          // aligned16: every vector 16-B aligned, member stride % 4 == 0
+struct FinalizeShape { int O, I, mnf, active; };
+
+bool k3_vec_allowed() {
+    static const bool allowed = [] { const char* e = getenv("LBBNN_K3_VEC"); return !(e && e[0] == '0'); }();   // A/B knob
+    return allowed;
+}
+
+// LBBNN_K3_GENERIC .. LBBNN_K3_VEC, or LBBNN_E_SHAPE (the member dimension exists in the fast and vec forms only); *need =
+// the dynamic LDS of the lds / fast forms (also what the launcher raises the kernels' limit to)
+int flow_planar_form(const FlowShape* l, int n, int members, size_t* need_out) {
+    size_t need = 0;
+    for (int i = 0; i < n; ++i) {
+        const size_t v = (size_t)(4 + 2 * (l[i].Tz + (l[i].want_kl ? l[i].Tr : 0))) * pad64(l[i].I) * sizeof(float);
+        need = v > need ? v : need;
+    }
+    if (need_out) *need_out = need;
+    if (need > (size_t)kFlowLdsBudget) return members > 1 ? LBBNN_E_SHAPE : LBBNN_K3_GENERIC;
+    bool fast = true;
+    for (int i = 0; i < n; ++i) fast = fast && (l[i].Tz + (l[i].want_kl ? l[i].Tr : 0) <= kFastT);
+    // the register form: float4 column groups, one per thread
+    bool vec = fast && k3_vec_allowed();
+    for (int i = 0; i < n && vec; ++i) vec = (l[i].I % 4 == 0) && l[i].I <= 4 * kVecThreads && l[i].aligned16;
+    if (vec) return LBBNN_K3_VEC;
+    if (fast) return LBBNN_K3_FAST;
+    return members > 1 ? LBBNN_E_SHAPE : LBBNN_K3_LDS;
+}
+
+// per-layer launch: LBBNN_K5_GENERIC / LBBNN_K5_LDS by the largest layer; all-layers launch: LBBNN_K5_UNSTAGED /
+// LBBNN_K5_STAGED by the sum over the active layers
+int kl_finalize_form(const FinalizeShape* l, int n, bool all_layers, size_t* need_out) {
+    size_t need = 0;
+    for (int i = 0; i < n; ++i) {
+        const size_t v = (size_t)(6 * pad64(l[i].O) + 2 * pad64(l[i].mnf ? l[i].I : 1)) * sizeof(float);
+        if (all_layers) need += l[i].active ? v : 0;
+        else need = v > need ? v : need;
+    }
+    if (need_out) *need_out = need;
+    const bool fits = need <= (size_t)kFlowLdsBudget;
+    if (all_layers) return fits ? LBBNN_K5_STAGED : LBBNN_K5_UNSTAGED;
+    return fits ? LBBNN_K5_LDS : LBBNN_K5_GENERIC;
+}
+
 }  // namespace
 
 namespace lbbnn {
@@ -755,49 +803,37 @@ namespace lbbnn {
 int launch_flow_planar(const FlowArgs* a, int n, hipStream_t s, int members, unsigned long long m_adv, long long z_ms) {
     FlowBatch bt;
     bt.m_adv = m_adv; bt.z_ms = z_ms;
-    int maxI = 0; bool small_t = true, any_kl = false;
+    FlowShape sh[LBBNN_MAX_LAYERS];
+    int maxI = 0; bool any_kl = false;
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
     for (int i = 0; i < n; ++i) {
-        bt.l[i] = a[i];
-        maxI = a[i].I > maxI ? a[i].I : maxI;
-        any_kl = any_kl || a[i].want_kl;
+        const FlowArgs& f = a[i];
+        bt.l[i] = f;
+        maxI = f.I > maxI ? f.I : maxI;
+        any_kl = any_kl || f.want_kl;
+        bool al = al16(f.q0_mean) && al16(f.q0_log_var) && al16(f.z_fwd) && (!f.eps_fwd || al16(f.eps_fwd)) &&
+                  (!f.want_kl || (al16(f.z_kl) && (!f.eps_kl || al16(f.eps_kl)))) && (z_ms % 4 == 0);
+        for (int t = 0; t < f.zf.T && al; ++t) al = al16(f.zf.u[t]) && al16(f.zf.w[t]);
+        for (int t = 0; t < (f.want_kl ? f.rf.T : 0) && al; ++t) al = al16(f.rf.u[t]) && al16(f.rf.w[t]);
+        sh[i] = FlowShape{f.I, f.zf.T, f.rf.T, f.want_kl, al ? 1 : 0};
     }
     const dim3 grid(any_kl ? 2 : 1, n, members > 1 ? members : 1), block(256);
-    (void)small_t;
     size_t need = 0;
-    for (int i = 0; i < n; ++i) {
-        const size_t v = (size_t)(4 + 2 * (a[i].zf.T + (a[i].want_kl ? a[i].rf.T : 0))) * pad64(a[i].I) * sizeof(float);
-        need = v > need ? v : need;
+    const int form = flow_planar_form(sh, n, members, &need);
+    if (form < 0) return form;
+    if (form != LBBNN_K3_GENERIC && need > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mnf_flow_planar_lds_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
+        if (e != hipSuccess) return (int)e;
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(mnf_flow_planar_fast_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
+        if (e != hipSuccess) return (int)e;
     }
-    if (need <= (size_t)kFlowLdsBudget) {
-        if (need > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mnf_flow_planar_lds_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
-            if (e != hipSuccess) return (int)e;
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(mnf_flow_planar_fast_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
-            if (e != hipSuccess) return (int)e;
-        }
-        bool fast = true;
-        for (int i = 0; i < n; ++i) fast = fast && (a[i].zf.T + (a[i].want_kl ? a[i].rf.T : 0) <= kFastT);
-        // the register form: float4 column groups, one per thread
-        static const bool vec_allowed = [] { const char* e = getenv("LBBNN_K3_VEC"); return !(e && e[0] == '0'); }();   // A/B knob
-        bool vec = fast && vec_allowed;
-        auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
-        for (int i = 0; i < n && vec; ++i) {
-            const FlowArgs& f = a[i];
-            vec = (f.I % 4 == 0) && f.I <= 4 * kVecThreads && al16(f.q0_mean) && al16(f.q0_log_var) && al16(f.z_fwd) &&
-                  (!f.eps_fwd || al16(f.eps_fwd)) && (!f.want_kl || (al16(f.z_kl) && (!f.eps_kl || al16(f.eps_kl)))) &&
-                  (z_ms % 4 == 0);
-            for (int t = 0; t < f.zf.T && vec; ++t) vec = al16(f.zf.u[t]) && al16(f.zf.w[t]);
-            for (int t = 0; t < (f.want_kl ? f.rf.T : 0) && vec; ++t) vec = al16(f.rf.u[t]) && al16(f.rf.w[t]);
-        }
-        if (vec) hipLaunchKernelGGL(mnf_flow_planar_vec_kernel, grid, dim3(kVecThreads), 0, s, bt);
-        else if (fast) hipLaunchKernelGGL(mnf_flow_planar_fast_kernel, grid, dim3(kFastThreads), need, s, bt);
-        else if (members > 1) return LBBNN_E_SHAPE;                     // the member dimension exists in the fast form only
-        else      hipLaunchKernelGGL(mnf_flow_planar_lds_kernel, grid, block, need, s, bt);
-    } else {
-        if (members > 1) return LBBNN_E_SHAPE;
-        hipLaunchKernelGGL(mnf_flow_planar_kernel, grid, block, (size_t)maxI * sizeof(float), s, bt);
+    switch (form) {
+        case LBBNN_K3_VEC:  hipLaunchKernelGGL(mnf_flow_planar_vec_kernel, grid, dim3(kVecThreads), 0, s, bt); break;
+        case LBBNN_K3_FAST: hipLaunchKernelGGL(mnf_flow_planar_fast_kernel, grid, dim3(kFastThreads), need, s, bt); break;
+        case LBBNN_K3_LDS:  hipLaunchKernelGGL(mnf_flow_planar_lds_kernel, grid, block, need, s, bt); break;
+        default:            hipLaunchKernelGGL(mnf_flow_planar_kernel, grid, block, (size_t)maxI * sizeof(float), s, bt); break;
     }
     return (int)hipGetLastError();
 }
@@ -805,12 +841,12 @@ int launch_flow_planar(const FlowArgs* a, int n, hipStream_t s, int members, uns
 int launch_kl_finalize_all(const FinalizeArgs* a, const int* active, int n, uint64_t* rng, uint64_t advance, float* kl_total,
                            hipStream_t s) {
     FinalizeAllArgs fa;
+    FinalizeShape sh[LBBNN_MAX_LAYERS];
     for (int i = 0; i < LBBNN_MAX_LAYERS; ++i) { fa.l[i] = i < n ? a[i] : FinalizeArgs{}; fa.active[i] = i < n ? active[i] : 0; }
+    for (int i = 0; i < n; ++i) sh[i] = FinalizeShape{a[i].O, a[i].I, a[i].scal ? 1 : 0, active[i]};
     fa.n = n; fa.rng = rng; fa.advance = advance; fa.total = kl_total;
     size_t need = 0;
-    for (int i = 0; i < n; ++i)
-        if (active[i]) need += (size_t)(6 * pad64(a[i].O) + 2 * pad64(a[i].scal ? a[i].I : 1)) * sizeof(float);
-    const int staged = need <= (size_t)kFlowLdsBudget ? 1 : 0;
+    const int staged = kl_finalize_form(sh, n, true, &need) == LBBNN_K5_STAGED ? 1 : 0;
     static size_t raised = 0;                        // dynamic-LDS limit of the function: raise once per size
     if (staged && need > 64 * 1024 && need > raised) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kl_finalize_all_kernel),
@@ -824,13 +860,13 @@ int launch_kl_finalize_all(const FinalizeArgs* a, const int* active, int n, uint
 
 int launch_kl_finalize(const FinalizeArgs* a, int n, hipStream_t s) {
     FinalizeBatch bt;
-    size_t need = 0;
+    FinalizeShape sh[LBBNN_MAX_LAYERS];
     for (int i = 0; i < n; ++i) {
         bt.l[i] = a[i];
-        const size_t v = (size_t)(6 * pad64(a[i].O) + 2 * pad64(a[i].scal ? a[i].I : 1)) * sizeof(float);
-        need = v > need ? v : need;
+        sh[i] = FinalizeShape{a[i].O, a[i].I, a[i].scal ? 1 : 0, 1};
     }
-    if (need <= (size_t)kFlowLdsBudget) {
+    size_t need = 0;
+    if (kl_finalize_form(sh, n, false, &need) == LBBNN_K5_LDS) {
         if (need > 64 * 1024) {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kl_finalize_lds_kernel),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
@@ -885,6 +921,31 @@ extern "C" int lbbnn_kl_finalize(const float* kl_rows, const float* bias_mu, con
     a.kl_out = kl_out; a.kl_layer = kl_layer; a.O = O; a.I = I; a.accum = kl_accum; a.layer = layer_id & 63u;
     a.bias_mu_prior = priors->bias_mu_prior; a.bias_sigma_prior = priors->bias_sigma_prior;
     return launch_kl_finalize(&a, 1, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int lbbnn_flow_planar_form(int n, const int* I, const int* Tz, const int* Tr, const int* want_kl,
+                                      const int* aligned16, int members) {
+    if (!I || !Tz || !Tr || !want_kl || !aligned16) return LBBNN_E_NULL;
+    if (n <= 0 || n > LBBNN_MAX_LAYERS || members < 1 || members > 65535) return LBBNN_E_SHAPE;
+    FlowShape sh[LBBNN_MAX_LAYERS];
+    for (int i = 0; i < n; ++i) {
+        if (I[i] <= 0 || I[i] > LBBNN_MAX_FLOW_DIM || Tz[i] < 0 || Tz[i] > LBBNN_MAX_FLOW_T || Tr[i] < 0 || Tr[i] > LBBNN_MAX_FLOW_T)
+            return LBBNN_E_SHAPE;
+        sh[i] = FlowShape{I[i], Tz[i], Tr[i], want_kl[i] ? 1 : 0, aligned16[i] ? 1 : 0};
+    }
+    return flow_planar_form(sh, n, members, nullptr);
+}
+
+extern "C" int lbbnn_kl_finalize_form(int n, const int* O, const int* I, const int* mnf, const int* active, int all_layers) {
+    if (!O || !I || !mnf || (all_layers && !active)) return LBBNN_E_NULL;
+    if (n <= 0 || n > LBBNN_MAX_LAYERS) return LBBNN_E_SHAPE;
+    FinalizeShape sh[LBBNN_MAX_LAYERS];
+    for (int i = 0; i < n; ++i) {
+        const int on = all_layers ? (active[i] ? 1 : 0) : 1;
+        if (on && (O[i] <= 0 || (mnf[i] && I[i] <= 0))) return LBBNN_E_SHAPE;
+        sh[i] = FinalizeShape{O[i], I[i], mnf[i] ? 1 : 0, on};
+    }
+    return kl_finalize_form(sh, n, all_layers != 0, nullptr);
 }
 
 extern "C" int lbbnn_forward_finish(uint64_t* rng, uint64_t advance, const float* const* kl_layers, int n,

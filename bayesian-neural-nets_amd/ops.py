@@ -819,6 +819,30 @@ def mnf_flow_planar(q0_mean, q0_log_var, z_params, r_params, *, eps_fwd=None, ep
     _lib.check(rc, "lbbnn_mnf_flow_planar")
 
 
+K3_GENERIC, K3_LDS, K3_FAST, K3_VEC = 0, 1, 2, 3        # LBBNN_K3_*: the form of a K3 launch
+K5_GENERIC, K5_LDS = 0, 1                               # LBBNN_K5_*: the per-layer K5 launch
+K5_UNSTAGED, K5_STAGED = 0, 1                           # ... and the all-layers launch
+
+
+def _c_ints(values):
+    return (ctypes.c_int * len(values))(*[int(v) for v in values])
+
+
+def flow_planar_form(layers, members: int = 1) -> int:
+    """lbbnn_flow_planar_form: the kernel form ONE K3 launch over ``layers`` = [(I, Tz, Tr, want_kl, aligned16)] takes
+    (K3_*), or the LBBNN_E_* code the launch would return.  Host only: no tensor, no GPU."""
+    cols = list(zip(*layers)) if layers else [()] * 5
+    return int(_lib.lib().lbbnn_flow_planar_form(len(layers), *[_c_ints(c) for c in cols], members))
+
+
+def kl_finalize_form(layers, all_layers: bool = False) -> int:
+    """lbbnn_kl_finalize_form for ``layers`` = [(O, I, mnf, active)]: K5_GENERIC / K5_LDS of the per-layer launch, or, with
+    ``all_layers``, K5_UNSTAGED / K5_STAGED of lbbnn_layers_finalize's; a negative LBBNN_E_* code for inputs the launch
+    refuses.  Host only."""
+    cols = list(zip(*layers)) if layers else [()] * 4
+    return int(_lib.lib().lbbnn_kl_finalize_form(len(layers), *[_c_ints(c) for c in cols], 1 if all_layers else 0))
+
+
 FLOW_PLANAR, FLOW_RADIAL, FLOW_HOUSEHOLDER, FLOW_SYLVESTER = 0, 1, 2, 3
 
 

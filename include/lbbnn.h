@@ -263,6 +263,41 @@ int lbbnn_kl_finalize(const float* kl_rows, const float* bias_mu, const float* b
                       const uint64_t* rng, uint32_t layer_id,
                       float* kl_out, float* kl_layer, int kl_accum, void* stream);
 
+/* lbbnn_flow_planar_form / lbbnn_kl_finalize_form -- which kernel form a K3 / K5 launch takes, answered on the host: no
+ * device pointer is taken, no GPU is touched.  Each is the selection function the launcher itself launches from, so the answer
+ * cannot drift from what runs.  The per-layer arrays are HOST arrays of n entries, 1 <= n <= LBBNN_MAX_LAYERS.
+ *
+ * lbbnn_flow_planar_form: the form of ONE K3 launch over n layers (lbbnn_mnf_flow_planar: n = 1; lbbnn_layers_prepare /
+ *   _operands: the MNF layers of the call without flows_done; lbbnn_ensemble_operands: members > 1).  I, Tz, Tr, want_kl as
+ *   in the layer (Tr is ignored without want_kl); aligned16[i] != 0: every vector of layer i the launch touches (q0_mean,
+ *   q0_log_var, z_fwd, the explicit draws, z_kl with want_kl, u and w of every transform) sits on a 16-B boundary and the
+ *   member stride of z_fwd is a multiple of 4.  Returns
+ *     LBBNN_K3_GENERIC  vectors read from global memory, z in LDS (the largest layer is past the 144 KiB LDS budget)
+ *     LBBNN_K3_LDS      inputs staged in LDS, one reduction per transform (a layer with more than 4 transforms)
+ *     LBBNN_K3_FAST     inputs staged in LDS, one reduction for the whole chain
+ *     LBBNN_K3_VEC      the same chain in registers (every layer: I % 4 == 0, I <= 2048, aligned16)
+ *   or the code the launch would return: NULL array: LBBNN_E_NULL; n, members (1 .. 65535), I (1 .. LBBNN_MAX_FLOW_DIM), Tz
+ *   or Tr (0 .. LBBNN_MAX_FLOW_T) out of range, members > 1 where the launch is neither FAST nor VEC: LBBNN_E_SHAPE.  The
+ *   environment knob LBBNN_K3_VEC=0 (read once) turns VEC into FAST here as in the launch.
+ *
+ * lbbnn_kl_finalize_form: all_layers == 0: the per-layer launch of lbbnn_kl_finalize (n = 1) and lbbnn_layers_prepare (its
+ *   layers with want_kl; active is ignored and may be NULL): LBBNN_K5_LDS if the LARGEST layer's vectors fit the budget, else
+ *   LBBNN_K5_GENERIC.  all_layers != 0: the single-workgroup launch of lbbnn_layers_finalize: LBBNN_K5_STAGED if the vectors
+ *   of all ACTIVE layers (want_kl) fit together, else LBBNN_K5_UNSTAGED.  mnf[i] != 0: the layer has the auxiliary terms
+ *   (scal != NULL); I is read for those layers only.  NULL array: LBBNN_E_NULL; n out of range, O < 1 or I < 1 of a layer that
+ *   is read: LBBNN_E_SHAPE. */
+#define LBBNN_K3_GENERIC 0
+#define LBBNN_K3_LDS 1
+#define LBBNN_K3_FAST 2
+#define LBBNN_K3_VEC 3
+#define LBBNN_K5_GENERIC 0
+#define LBBNN_K5_LDS 1
+#define LBBNN_K5_UNSTAGED 0
+#define LBBNN_K5_STAGED 1
+int lbbnn_flow_planar_form(int n, const int* I, const int* Tz, const int* Tr, const int* want_kl, const int* aligned16,
+                           int members);
+int lbbnn_kl_finalize_form(int n, const int* O, const int* I, const int* mnf, const int* active, int all_layers);
+
 
 /* ---------------------------------------------------------------------------------------------
  * Batched "prepare": everything in a network forward that does NOT depend on the activations

@@ -63,6 +63,27 @@ def test_argument_checks_return_codes_without_launching(lib):
                                      None, 0, fake, fake, fake, 20000, 1, None) == -2
 
 
+def test_form_queries_answer_on_the_host(lib):
+    """lbbnn_flow_planar_form / lbbnn_kl_finalize_form: host arrays in, a form or the launch's LBBNN_E_* code out; no device
+    pointer, no launch (tests/test_planar_forward_forms_host.py walks the case tables through them)."""
+    ints = lambda *v: (ctypes.c_int * len(v))(*v)
+    one, two = ints(1), ints(1, 1)
+    assert lib.lbbnn_flow_planar_form(1, ints(784), ints(2), ints(2), one, one, 1) == 3          # LBBNN_K3_VEC
+    assert lib.lbbnn_flow_planar_form(1, ints(784), ints(2), ints(2), one, ints(0), 1) == 2      # off 16 bytes: LBBNN_K3_FAST
+    assert lib.lbbnn_flow_planar_form(2, ints(784, 40), ints(2, 3), ints(2, 2), two, two, 1) == 1   # a (3, 2) companion: _LDS
+    assert lib.lbbnn_flow_planar_form(1, ints(16384), ints(2), ints(2), one, one, 1) == 0        # past the LDS budget: _GENERIC
+    assert lib.lbbnn_flow_planar_form(1, ints(16384), ints(2), ints(2), one, one, 2) == -2       # no member dimension there
+    assert lib.lbbnn_flow_planar_form(1, ints(20000), ints(2), ints(2), one, one, 1) == -2
+    assert lib.lbbnn_flow_planar_form(1, None, ints(2), ints(2), one, one, 1) == -1
+    assert lib.lbbnn_flow_planar_form(5, one, one, one, one, one, 1) == -2
+    assert lib.lbbnn_kl_finalize_form(1, ints(1200), ints(784), one, None, 0) == 1               # LBBNN_K5_LDS
+    assert lib.lbbnn_kl_finalize_form(1, ints(700), ints(16384), one, None, 0) == 0              # LBBNN_K5_GENERIC
+    assert lib.lbbnn_kl_finalize_form(2, ints(3000, 3000), ints(784, 784), two, two, 1) == 0     # LBBNN_K5_UNSTAGED
+    assert lib.lbbnn_kl_finalize_form(2, ints(3000, 3000), ints(784, 784), two, ints(1, 0), 1) == 1   # ... _STAGED without layer 2
+    assert lib.lbbnn_kl_finalize_form(1, ints(0), ints(784), one, None, 0) == -2
+    assert lib.lbbnn_kl_finalize_form(1, ints(8), ints(8), one, None, 1) == -1
+
+
 def test_ctypes_struct_layouts_match_the_header(tmp_path):
     """Every struct of include/lbbnn.h that the Python side mirrors with ctypes has the same size and the same offset of
     its last member when compiled by gcc from the header itself (an ABI drift here would corrupt kernel arguments)."""
