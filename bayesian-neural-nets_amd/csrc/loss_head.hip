@@ -103,16 +103,18 @@ __global__ __launch_bounds__(256) void elbo_loss_backward_kernel(const float* g,
 
 // ... and, in the same launch, what lbbnn_log_softmax_backward makes of that gradient when the log-probabilities are the
 // log_softmax of a layer's logits (the fused head of the training forward): g_logits = g_logp - exp(logp) * sum_c g_logp, with
-// the row sum being -g exactly.  Same expression, same order: bitwise the two-launch result.
+// the row sum being -g exactly -- or zero for a row whose target lies outside [0, C), which has no one-hot entry and gets no
+// gradient.  Same expression, same order: bitwise the two-launch result.
 __global__ __launch_bounds__(256) void elbo_loss_backward_logits_kernel(const float* g, const int64_t* __restrict__ target,
                                                                         const float* __restrict__ logp, int ldp, int B, int C,
                                                                         float kl_scale, float* g_logp, float* g_logits, float* g_kl) {
     const float gv = *g;
-    const float s = -gv;
     const int n = B * C;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
         const int b = i / C, c = i - b * C;
-        const float gl = (target[b] == c) ? -gv : 0.f;
+        const int64_t t = target[b];
+        const float gl = (t == c) ? -gv : 0.f;
+        const float s = (t >= 0 && t < C) ? -gv : 0.f;
         g_logp[i] = gl;
         g_logits[i] = gl - expf(logp[(size_t)b * ldp + c]) * s;
     }

@@ -288,8 +288,11 @@ def output_grad(g_out, *, out=None, std=None, eps=None, rng=None, rng_stream: in
 def head_dx(gm, gv, wmT, wvT, x, *, C: int, I: int):
     """lbbnn_head_dx: dX (B, I) of a <= 16-class head from G_m / G_v (B, C) and the transposed fp32 operands [I][ld]."""
     B = gm.shape[0]
+    gm_ptr, gv_ptr = _ptr_rows(gm, "gm"), (_ptr_rows(gv, "gv") if gv is not None else None)
+    if gv is not None and gv.stride(0) != gm.stride(0):
+        raise ValueError("bnn_amd: gm and gv must share a row stride (got %d and %d)" % (gm.stride(0), gv.stride(0)))
     out = torch.empty((B, I), dtype=torch.float32, device=gm.device)
-    rc = _lib.lib().lbbnn_head_dx(_ptr_rows(gm, "gm"), _ptr_rows(gv, "gv") if gv is not None else None, gm.stride(0),
+    rc = _lib.lib().lbbnn_head_dx(gm_ptr, gv_ptr, gm.stride(0),
                                   _ptr(wmT), _ptr(wvT), wmT.stride(0), _ptr_rows(x, "x") if gv is not None else None,
                                   x.stride(0) if gv is not None else 0, out.data_ptr(), I, B, C, I, _stream())
     _lib.check(rc, "lbbnn_head_dx")
