@@ -450,8 +450,6 @@ SIGNATURES = {
     "lbbnn_lrt_gemm": (c_i, [c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_u32, c_i64,
                              c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     "lbbnn_lrt_gemm_plan": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(GemmPlan)]),
-    "lbbnn_lrt_gemm_train": (c_i, [c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_u32, c_i64,
-                                   c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p]),
     "lbbnn_transpose_operand": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_p]),
     "lbbnn_weight_pass_backward_workspace": (c_i64, [c_i, c_i]),
     "lbbnn_weight_pass_backward": (c_i, [ctypes.POINTER(WpbArgs), c_p]),
@@ -510,17 +508,11 @@ SIGNATURES = {
     "lbbnn_layers_prepare": (c_i, [ctypes.POINTER(LayerDesc), c_i, c_p, c_p]),
     "lbbnn_layers_operands_snap": (c_i, [ctypes.POINTER(LayerDesc), c_i, c_p, c_p, c_u64, c_p]),
     "lbbnn_layers_operands_x": (c_i, [ctypes.POINTER(LayerDesc), c_i, c_p, c_p, c_u64, c_p, c_i, c_p, c_i, c_i, c_i, c_p]),
-    "lbbnn_lrt_gemm_finalize": (c_i, [c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_u32, c_i64,
-                                      c_p, c_i, c_p, c_i, c_i, c_i, c_i, ctypes.POINTER(LayerDesc), c_i, c_p, c_p, c_p]),
-    "lbbnn_lrt_gemm_finalize_adv": (c_i, [c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_u32, c_i64,
-                                          c_p, c_i, c_p, c_i, c_i, c_i, c_i, ctypes.POINTER(LayerDesc), c_i, c_p, c_p,
-                                          c_p, c_u64, c_p]),
     "lbbnn_ensemble_operands": (c_i, [ctypes.POINTER(LayerDesc), c_i, c_i, c_p, c_u64, c_p]),
     "lbbnn_lrt_gemm_members": (c_i, [c_p, c_i, c_i64, c_p, c_i64, c_p, c_i, c_p, c_p, c_p, c_u32, c_i64, c_u64,
                                      c_p, c_i, c_i64, c_i, c_i, c_i, c_i, c_i, c_p]),
     "lbbnn_layers_operands": (c_i, [ctypes.POINTER(LayerDesc), c_i, c_p, c_p]),
     "lbbnn_layers_finalize": (c_i, [ctypes.POINTER(LayerDesc), c_i, c_p, ctypes.c_uint64, c_p, c_p]),
-    "lbbnn_forward_finish": (c_i, [c_p, c_u64, c_p, c_i, c_p, c_p]),
     "lbbnn_kl_total": (c_i, [c_p, c_i, c_p, c_p]),
     "lbbnn_fold_rows": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),
     "lbbnn_gate_sample": (c_i, [ctypes.POINTER(GateArgs), c_p, c_p]),

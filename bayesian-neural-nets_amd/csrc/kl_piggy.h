@@ -1,5 +1,5 @@
 // K5 (KL finalize) of every layer of a network + the network total as ONE 256-thread workgroup body, carried by an
-// extra workgroup of a GEMM launch (lbbnn_lrt_gemm_finalize): the KL tail depends on parameters only, so it can run
+// extra workgroup of a GEMM launch (lbbnn_lrt_gemm_ex with layers): the KL tail depends on parameters only, so it can run
 // while the first GEMM runs instead of costing a launch of its own after the last one.
 // Same arithmetic as kl_finalize_all_kernel (mnf_flow.hip), layer after layer; `sm` is the host kernel's dynamic LDS
 // (at least piggy_lds_bytes() bytes): staged input vectors of one layer, then the reduction scratch.
@@ -99,7 +99,7 @@ __device__ __forceinline__ void kl_finalize_piggy(const LBBNN_CONST_AS FinalizeP
         __syncthreads();                                         // the next layer restages sm
     }
     if (t == 0 && A.total) *A.total = total;
-    // the forward's RNG advance (lbbnn_lrt_gemm_finalize_adv): no kernel of this launch reads the LIVE offset
+    // the forward's RNG advance (lbbnn_gemm_desc_t::advance): no kernel of this launch reads the LIVE offset
     if (t == 0 && A.rng_adv) A.rng_adv[1] += A.adv;
 }
 

@@ -54,7 +54,7 @@ struct FinalizeArgs {
     float bias_mu_prior, bias_sigma_prior;
 };
 
-// K5 of up to LBBNN_MAX_LAYERS layers + their total, as carried by a GEMM launch (lbbnn_lrt_gemm_finalize)
+// K5 of up to LBBNN_MAX_LAYERS layers + their total, as carried by a GEMM launch (lbbnn_lrt_gemm_ex with layers)
 struct FinalizePiggy { FinalizeArgs l[LBBNN_MAX_LAYERS]; int active[LBBNN_MAX_LAYERS]; int n; float* total;
                        uint64_t* rng_adv; uint64_t adv; };     // rng_adv != NULL: the piggy workgroup also does rng_adv[1] += adv
 
@@ -97,5 +97,8 @@ LBBNN_HIDDEN int launch_kl_finalize_all(const FinalizeArgs* a, const int* active
 LBBNN_HIDDEN int launch_kl_finalize(const FinalizeArgs* a, int n, hipStream_t s);
 // FinalizeArgs of every layer of a network from its descriptors (validation as lbbnn_layers_finalize)
 LBBNN_HIDDEN int fill_finalize_args(const lbbnn_layer_desc_t* L, int n, const uint64_t* rng, FinalizeArgs* ka, int* active);
+// lbbnn_lrt_gemm_ex's branch for a descriptor without LBBNN_F_F16S (lrt_gemm.hip; the entry point and the fp16 branch:
+// lrt_gemm_f16.hip)
+LBBNN_HIDDEN int gemm_desc_f32(const lbbnn_gemm_desc_t& d, void* stream);
 
 }  // namespace lbbnn

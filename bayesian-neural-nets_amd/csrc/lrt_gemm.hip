@@ -51,7 +51,7 @@ struct GemmArgs {
     // dX = G_m.W_m + 2 x (.) (G_v.W_v) fused into the second product's epilogue; NULL: plain output
     const float* comb_x; const float* comb_add;
     int ld_cx, ld_ca;
-    // lbbnn_lrt_gemm_finalize: fin.n > 0 => the grid has one extra row of workgroups (blockIdx.y == gridDim.y - 1) whose
+    // lbbnn_lrt_gemm_ex with layers: fin.n > 0 => the grid has one extra row of workgroups (blockIdx.y == gridDim.y - 1) whose
     // first workgroup does the KL finalize of the network (kl_piggy.h) while the tiles are computed; the rest of the row exits
     FinalizePiggy fin;
     // lbbnn_lrt_gemm_members: gridDim.z = members; member m = blockIdx.z is the same product on x + m*x_ms, e_w + m*w_ms
@@ -1136,71 +1136,43 @@ extern "C" int lbbnn_lrt_gemm(const float* x, int ldx, const void* e_w, const vo
                               const float* bias_mean, const float* bias_var, const float* var_scale,
                               const float* eps, const uint64_t* rng, uint32_t rng_stream, int64_t row_offset,
                               float* out, int ldo, int B, int I, int O, int flags, void* stream) {
-    return lbbnn_lrt_gemm_train(x, ldx, e_w, var_w, ld, bias_mean, bias_var, var_scale, eps, rng, rng_stream, row_offset,
-                                out, ldo, nullptr, B, I, O, flags, stream);
-}
-
-extern "C" int lbbnn_lrt_gemm_train(const float* x, int ldx, const void* e_w, const void* var_w, int ld,
-                                    const float* bias_mean, const float* bias_var, const float* var_scale,
-                                    const float* eps, const uint64_t* rng, uint32_t rng_stream, int64_t row_offset,
-                                    float* out, int ldo, float* std_out, int B, int I, int O, int flags, void* stream) {
-    if ((flags & LBBNN_F_MEAN_ONLY) && std_out) return LBBNN_E_FLAGS;
-    // (log_softmax + std_out is the training forward of the 10-class head: the backward needs sqrt(var), not the logits)
     GemmArgs a = gemm_args(x, ldx, e_w, var_w, ld, out, ldo, B, I, O);
     a.bias_mean = bias_mean; a.bias_var = bias_var; a.var_scale = var_scale;
-    a.eps = eps; a.rng = rng; a.rng_stream = rng_stream; a.row_offset = row_offset; a.std_out = std_out;
+    a.eps = eps; a.rng = rng; a.rng_stream = rng_stream; a.row_offset = row_offset;
     return lrt_gemm_dispatch(a, flags, stream);
 }
 
-// lbbnn_lrt_gemm_train (record `a`) with the KL finalize of a whole network carried by one extra workgroup of the same launch
-static int gemm_finalize_impl(GemmArgs& a, int flags, const lbbnn_layer_desc_t* layers, int n, const uint64_t* fin_rng,
-                              float* kl_total, uint64_t* rng_live, uint64_t advance, void* stream) {
-    if ((flags & LBBNN_F_MEAN_ONLY) && a.std_out) return LBBNN_E_FLAGS;
+// lbbnn_lrt_gemm_ex on a descriptor without LBBNN_F_F16S (fp32 / bf16 operands): the product of lbbnn_lrt_gemm plus what a
+// forward adds to it -- std_out, and the KL finalize of a whole network (with the RNG advance) carried by one extra workgroup
+// of the same launch
+int lbbnn::gemm_desc_f32(const lbbnn_gemm_desc_t& d, void* stream) {
+    const int flags = d.flags, n = d.n_layers;
+    // what only the row-scaled fp16 format has
+    if ((flags & (LBBNN_F_VAR1 | LBBNN_F_XPLANES)) || d.mean_scale || d.wvar_scale || d.out_planes || d.head_out) return LBBNN_E_FLAGS;
+    if (n < 0 || (n > 0 && !d.layers)) return LBBNN_E_SHAPE;
+    if (d.advance && !d.rng_live) return LBBNN_E_NULL;
+    // (log_softmax + std_out is the training forward of the 10-class head: the backward needs sqrt(var), not the logits)
+    if ((flags & LBBNN_F_MEAN_ONLY) && d.std_out) return LBBNN_E_FLAGS;
+    GemmArgs a = gemm_args(static_cast<const float*>(d.x), d.ldx, d.e_w, d.var_w, d.ld, d.out, d.ldo, d.B, d.I, d.O);
+    a.bias_mean = d.bias_mean; a.bias_var = d.bias_var; a.var_scale = d.var_scale;
+    a.eps = d.eps; a.rng = d.rng; a.rng_stream = d.rng_stream; a.row_offset = d.row_offset; a.std_out = d.std_out;
     if (n == 0) {
         // nothing to finalize (a forward without KL): the plain GEMM, then the advance as the tiny launch it is
         const int rc = lrt_gemm_dispatch(a, flags, stream);
-        if (rc || !rng_live || !advance) return rc;
-        return lbbnn_rng_advance(rng_live, advance, stream);
+        if (rc || !d.advance) return rc;
+        return lbbnn_rng_advance(d.rng_live, d.advance, stream);
     }
     FinalizePiggy& fin = a.fin;
-    if (const int rc = fill_finalize_args(layers, n, fin_rng, fin.l, fin.active)) return rc;
-    if (kl_total) for (int i = 0; i < n; ++i) if (!fin.active[i]) return LBBNN_E_NULL;   // a total needs every layer's KL
-    fin.n = n; fin.total = kl_total;
-    fin.rng_adv = advance ? rng_live : nullptr; fin.adv = advance;
+    if (const int rc = fill_finalize_args(d.layers, n, d.fin_rng, fin.l, fin.active)) return rc;
+    if (d.kl_total) for (int i = 0; i < n; ++i) if (!fin.active[i]) return LBBNN_E_NULL;   // a total needs every layer's KL
+    fin.n = n; fin.total = d.kl_total;
+    fin.rng_adv = d.advance ? d.rng_live : nullptr; fin.adv = d.advance;
     bool hosted = false;
     const int rc = lrt_gemm_dispatch(a, flags, stream, &hosted);
     if (rc) return rc;
     if (hosted) return 0;
     // this GEMM's kernel cannot host the extra workgroup (small tile configuration, skinny output, LDS): same work, own launch
-    return launch_kl_finalize_all(fin.l, fin.active, n, advance ? rng_live : nullptr, advance, kl_total,
-                                  static_cast<hipStream_t>(stream));
-}
-
-extern "C" int lbbnn_lrt_gemm_finalize(const float* x, int ldx, const void* e_w, const void* var_w, int ld,
-                                       const float* bias_mean, const float* bias_var, const float* var_scale,
-                                       const float* eps, const uint64_t* rng, uint32_t rng_stream, int64_t row_offset,
-                                       float* out, int ldo, float* std_out, int B, int I, int O, int flags,
-                                       const lbbnn_layer_desc_t* layers, int n, const uint64_t* fin_rng, float* kl_total,
-                                       void* stream) {
-    if (n <= 0) return LBBNN_E_SHAPE;
-    GemmArgs a = gemm_args(x, ldx, e_w, var_w, ld, out, ldo, B, I, O);
-    a.bias_mean = bias_mean; a.bias_var = bias_var; a.var_scale = var_scale;
-    a.eps = eps; a.rng = rng; a.rng_stream = rng_stream; a.row_offset = row_offset; a.std_out = std_out;
-    return gemm_finalize_impl(a, flags, layers, n, fin_rng, kl_total, nullptr, 0, stream);
-}
-
-extern "C" int lbbnn_lrt_gemm_finalize_adv(const float* x, int ldx, const void* e_w, const void* var_w, int ld,
-                                           const float* bias_mean, const float* bias_var, const float* var_scale,
-                                           const float* eps, const uint64_t* rng, uint32_t rng_stream, int64_t row_offset,
-                                           float* out, int ldo, float* std_out, int B, int I, int O, int flags,
-                                           const lbbnn_layer_desc_t* layers, int n, const uint64_t* fin_rng, float* kl_total,
-                                           uint64_t* rng_live, uint64_t advance, void* stream) {
-    if (n < 0 || (n > 0 && !layers)) return LBBNN_E_SHAPE;
-    if (advance && !rng_live) return LBBNN_E_NULL;
-    GemmArgs a = gemm_args(x, ldx, e_w, var_w, ld, out, ldo, B, I, O);
-    a.bias_mean = bias_mean; a.bias_var = bias_var; a.var_scale = var_scale;
-    a.eps = eps; a.rng = rng; a.rng_stream = rng_stream; a.row_offset = row_offset; a.std_out = std_out;
-    return gemm_finalize_impl(a, flags, layers, n, fin_rng, kl_total, rng_live, advance, stream);
+    return launch_kl_finalize_all(fin.l, fin.active, n, fin.rng_adv, d.advance, d.kl_total, static_cast<hipStream_t>(stream));
 }
 
 // An ensemble of `members` forwards of one layer in ONE launch (include/lbbnn.h)

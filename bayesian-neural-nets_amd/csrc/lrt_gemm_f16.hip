@@ -737,8 +737,8 @@ extern "C" int lbbnn_format_x(const float* x, int ldx, void* planes, int ldp, in
 extern "C" int lbbnn_lrt_gemm_ex(const lbbnn_gemm_desc_t* d, void* stream) {
     if (!d) return LBBNN_E_NULL;
     const int B = d->B, I = d->I, O = d->O, flags = d->flags;
+    if (!(flags & LBBNN_F_F16S)) return gemm_desc_f32(*d, stream);       // fp32 / bf16 operands: lrt_gemm.hip
     if (flags & ~(LBBNN_F_RELU | LBBNN_F_F16S | LBBNN_F_VAR1 | LBBNN_F_XPLANES)) return LBBNN_E_FLAGS;
-    if (!(flags & LBBNN_F_F16S)) return LBBNN_E_FLAGS;             // the descriptor form serves the fp16 format (the others: lbbnn_lrt_gemm*)
     if (B == 0 && I > 0 && O > 0 && d->n_layers == 0 && !d->advance) return 0;
     if (!d->x || !d->e_w || !d->var_w || !d->mean_scale || !d->wvar_scale) return LBBNN_E_NULL;
     if (!d->eps && !d->rng) return LBBNN_E_NOISE;

@@ -691,18 +691,8 @@ __global__ __launch_bounds__(LBBNN_MAX_LAYERS * 256) void kl_finalize_all_kernel
 // -------------------------------------------------------------------------------------------- utilities
 __global__ void rng_advance_kernel(uint64_t* rng, uint64_t delta) { rng[1] += delta; }
 
-struct FinishArgs { const float* kl[LBBNN_MAX_LAYERS]; int n; float* total; uint64_t* rng; uint64_t delta; };
-__global__ void forward_finish_kernel(const FinishArgs a) {
-    if (a.total) {
-        float s = 0.f;
-        for (int i = 0; i < a.n; ++i) s += *a.kl[i];          // fixed order: l1 + l2 + l3
-        *a.total = s;
-    }
-    if (a.rng) a.rng[1] += a.delta;
-}
-
 // lbbnn_kl_total: the network KL of more than LBBNN_MAX_LAYERS layers, whose finalize launches (one per group of layers)
-// left the per-layer values side by side -- the same fp32 left fold, in layer order, as the two kernels above
+// left the per-layer values side by side -- the same fp32 left fold, in layer order, as the finalize kernel above
 __global__ void kl_total_kernel(const float* kl, int n, float* total) {
     float s = 0.f;
     for (int i = 0; i < n; ++i) s += kl[i];
@@ -946,18 +936,6 @@ extern "C" int lbbnn_kl_finalize_form(int n, const int* O, const int* I, const i
         sh[i] = FinalizeShape{O[i], I[i], mnf[i] ? 1 : 0, on};
     }
     return kl_finalize_form(sh, n, all_layers != 0, nullptr);
-}
-
-extern "C" int lbbnn_forward_finish(uint64_t* rng, uint64_t advance, const float* const* kl_layers, int n,
-                                    float* kl_total, void* stream) {
-    if (!rng && !kl_total) return LBBNN_E_NULL;
-    if (kl_total && (n <= 0 || n > LBBNN_MAX_LAYERS || !kl_layers)) return LBBNN_E_SHAPE;
-    FinishArgs a;
-    a.n = kl_total ? n : 0; a.total = kl_total; a.rng = rng; a.delta = advance;
-    for (int i = 0; i < LBBNN_MAX_LAYERS; ++i) a.kl[i] = (kl_total && i < n) ? kl_layers[i] : nullptr;
-    for (int i = 0; i < a.n; ++i) if (!a.kl[i]) return LBBNN_E_NULL;
-    hipLaunchKernelGGL(forward_finish_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), a);
-    return (int)hipGetLastError();
 }
 
 extern "C" int lbbnn_kl_total(const float* kl_layers, int n, float* total, void* stream) {

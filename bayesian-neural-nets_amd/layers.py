@@ -646,7 +646,7 @@ class _BayesLinearBase(nn.Module):
         self._cur_B = x.shape[0]
         self._split_now = self._split(x, cfg)
         self._last_masks = None
-        # the layer's KL tail (K5) depends on parameters only: it rides in the GEMM's launch (lbbnn_lrt_gemm_finalize)
+        # the layer's KL tail (K5) depends on parameters only: it rides in the GEMM's launch (lbbnn_lrt_gemm_ex with layers)
         # instead of a launch of its own between the weight pass and the GEMM
         fin, hosted_all = None, False
         pre = self._preprep
@@ -664,7 +664,7 @@ class _BayesLinearBase(nn.Module):
                     if _ADV_RIDE and pre.get("snap") is not None and rng is not None and sh.get("all_snap"):
                         # ... and so does the forward's RNG advance: every kernel of this forward from here on reads the
                         # SNAPSHOT the weight pass took (same {seed, offset}), so the live offset may move already
-                        fin = (fin[0], fin[1], pre["snap"].data_ptr(), fin[3], rng.data_ptr(), 1)
+                        fin = fin._replace(fin_rng=pre["snap"].data_ptr(), rng_live=rng.data_ptr(), advance=1)
                         sh["advanced"] = True
                 hosted_all = True
             if sh.get("advanced"):
@@ -675,7 +675,7 @@ class _BayesLinearBase(nn.Module):
             from . import _lib
             desc = (_lib.LayerDesc * 1)()
             saved["_keep"] = self._fill_desc(desc[0], cfg, kl)         # reshaped noise views: alive past the launch
-            fin = (desc, 1, rng.data_ptr() if rng is not None else None, None)
+            fin = ops.Finalize(layers=desc, n=1, fin_rng=rng.data_ptr() if rng is not None else None, kl_total=None)
         saved["masks"] = self._last_masks
         std = torch.empty((x.shape[0], self.out_features), dtype=torch.float32, device=x.device) if want_std else None
         out = self._gemm(x, cfg, rng, std_out=std, finalize=fin, log_softmax=bool(self._lsm_now and self._split_now == 0))
@@ -1312,8 +1312,8 @@ class _NetworkBase(nn.Module):
         shared = {"hosted": False, "keep": keep, "kl_total": kl_total, "advanced": False,
                   # every layer draws in-kernel from the shared state and the step has ONE snapshot: the advance may ride early
                   "all_snap": bool(snap is not None and rng is not None and all(l._uses_rng(c) for l, c in zip(layers, cfgs))),
-                  "fin_all": (descs, len(layers), rng.data_ptr() if rng is not None else None,
-                              kl_total.data_ptr()) if all_kl else None}
+                  "fin_all": ops.Finalize(layers=descs, n=len(layers), fin_rng=rng.data_ptr() if rng is not None else None,
+                                          kl_total=kl_total.data_ptr()) if all_kl else None}
         self._pre_shared = shared
         for i, (l, c) in enumerate(zip(layers, cfgs)):
             l._preprep = {"cfg": c, "split": l._split_now, "kl": kls[i], "first": i == 0, "shared": shared, "snap": snap}
@@ -1324,7 +1324,7 @@ class _NetworkBase(nn.Module):
         lbbnn_layers_operands_snap runs the x-independent kernels the GEMMs need for all layers (flows, weight pass: one
         launch per kind); the weight-pass launch also copies the Philox state for the rest of this forward and advances
         the live offset.  Then the three GEMMs run back to back (ReLU / log_softmax in their epilogues); the first one
-        carries every layer's KL tail + the network total as one extra workgroup (lbbnn_lrt_gemm_finalize) -- the KL
+        carries every layer's KL tail + the network total as one extra workgroup (lbbnn_gemm_desc_t::layers) -- the KL
         depends on parameters only, so it needs neither a launch of its own nor a place on the critical path.
         (A two-stream schedule was measured first: every cross-stream dependency cost 13-15 us on
         the critical path and the side-stream kernels were starved by the GEMM -- see DESIGN.md.)
@@ -1403,7 +1403,7 @@ class _NetworkBase(nn.Module):
                 l._chain_flows(rng, eps_z, eps_z2, c[1])
         # K1 of every layer, the planar flows computed inside its own workgroups (no K3 launch: weight_pass.hip); the launch
         # snapshots the Philox state for the rest of this forward.  The live offset is advanced by the extra workgroup of
-        # the first GEMM's launch (lbbnn_lrt_gemm_finalize_adv): every workgroup of THIS launch reads it.
+        # the first GEMM's launch (lbbnn_gemm_desc_t::advance): every workgroup of THIS launch reads it.
         snap = st.t[2:4] if st is not None else None
         # (a network deeper than one batched launch: the FIRST group's call takes the snapshot, the others read it)
         lgroups = _lib.layer_groups(n)
@@ -1452,13 +1452,15 @@ class _NetworkBase(nn.Module):
                 torch.cuda.current_stream(dev).wait_event(defer_ev)
             if i == fin_at and (want_kl or st is not None):
                 # (the first group's finalize, with the network total when it is the only group, and the RNG advance)
-                fin = (d0 if want_kl else None, n0 if want_kl else 0, snap.data_ptr() if snap is not None else None,
-                       kls[n:].data_ptr() if (all_kl and len(lgroups) == 1) else None, rng.data_ptr() if rng is not None else None,
-                       1 if rng is not None else 0)
+                fin = ops.Finalize(layers=d0 if want_kl else None, n=n0 if want_kl else 0,
+                                   fin_rng=snap.data_ptr() if snap is not None else None,
+                                   kl_total=kls[n:].data_ptr() if (all_kl and len(lgroups) == 1) else None,
+                                   rng_live=rng.data_ptr() if rng is not None else None, advance=1 if rng is not None else 0)
             elif want_kl and fin_at < i < fin_at + len(lgroups):
                 # group g's finalize rides in GEMM fin_at + g (every group reads the snapshot; only the first one advances)
                 k, cnt = lgroups[i - fin_at]
-                fin = (_lib.group_slice(descs, k, cnt), cnt, snap.data_ptr() if snap is not None else None, None)
+                fin = ops.Finalize(layers=_lib.group_slice(descs, k, cnt), n=cnt,
+                                   fin_rng=snap.data_ptr() if snap is not None else None, kl_total=None)
             # row-scaled fp16 layers hand their activations on as fp16 hi | lo PLANES (written by the GEMM epilogue, read by
             # the next GEMM's LDS-DMA as they lie): no fp32 copy of a hidden activation is stored in this no-grad forward
             fmt = l._split_now

@@ -423,6 +423,60 @@ class GemmEventLog(list):
 GEMM_EVENTS = None
 
 
+class Finalize(NamedTuple):
+    """What a forward's GEMM launch carries beside the product (lbbnn_gemm_desc_t::layers .. advance): the KL finalize of
+    ``n`` layers (0: none) by one extra workgroup and, with ``advance``, ``rng_live[1] += advance``."""
+    layers: object                      # _lib.LayerDesc array (or _lib.group_slice of one); None with n == 0
+    n: int
+    fin_rng: Optional[int]              # pointer of the Philox state K5 draws from
+    kl_total: Optional[int]             # pointer of the network total, or None
+    rng_live: Optional[int] = None      # pointer of the live Philox state
+    advance: int = 0
+
+
+def _gemm_input(x, cols: int, what: str, O: int, eps, finalize):
+    """What both GEMM wrappers ask of x (B, cols) and eps (B, O).  Returns x with dense rows, or None for an empty batch
+    without a finalize: (0, O) activations as torch.mm gives, no call (the KL side is unaffected by B)."""
+    if x.dim() != 2 or x.shape[1] != cols:
+        raise RuntimeError("bnn_amd: %s must be (B,%d), got %s" % (what, cols, tuple(x.shape)))
+    B = x.shape[0]
+    if eps is not None and tuple(eps.shape) != (B, O):
+        raise RuntimeError("bnn_amd: eps must be (%d,%d), got %s" % (B, O, tuple(eps.shape)))
+    if B == 0 and finalize is None:
+        return None
+    if x.stride(1) != 1 or x.stride(0) < cols:
+        x = x.contiguous()
+    return x
+
+
+def _gemm_desc(x, e_w, var_w, *, I, O, bias_mean, bias_var, var_scale, eps, rng, rng_stream, row_offset, out, std_out, flags,
+               finalize):
+    """lbbnn_gemm_desc_t of the fields every operand format has; a format's own fields (scales, planes, head) stay zero."""
+    d = _lib.GemmDesc()
+    d.x, d.ldx = _ptr_rows(x, "input"), x.stride(0)
+    d.e_w, d.var_w, d.ld = _ptr(e_w), _ptr(var_w), operand_ld(I)
+    d.bias_mean, d.bias_var, d.var_scale, d.eps = _ptr(bias_mean), _ptr(bias_var), _ptr(var_scale), _ptr(eps, "eps")
+    d.rng = rng.data_ptr() if rng is not None else None
+    d.rng_stream, d.row_offset = rng_stream, row_offset
+    d.out, d.ldo = (out.data_ptr(), out.stride(0)) if out is not None else (None, 0)
+    d.std_out = _ptr(std_out, "std_out")
+    d.B, d.I, d.O, d.flags = x.shape[0], I, O, flags
+    if finalize is not None:            # a Finalize, or its fields in order (the last two may be left out)
+        d.layers, d.n_layers, d.fin_rng, d.kl_total, d.rng_live, d.advance = finalize if len(finalize) == 6 else Finalize(*finalize)
+    return d
+
+
+def _gemm_call(name: str, args, B: int, I: int, O: int):
+    """One single-GEMM library call on the current stream, checked; between a pair of GEMM_EVENTS' events when a log is set."""
+    ev = GEMM_EVENTS.take() if GEMM_EVENTS is not None else None
+    if ev is not None:
+        ev[0].record()
+    _lib.check(getattr(_lib.lib(), name)(*args, _stream()), name)
+    if ev is not None:
+        ev[1].record()
+        GEMM_EVENTS.append((B, I, O, ev[0], ev[1]))
+
+
 def lrt_gemm(x, e_w, var_w, *, I: int, O: int, bias_mean=None, bias_var=None, var_scale=None,
              eps=None, rng: Optional[torch.Tensor] = None, rng_stream: int = 0, row_offset: int = 0,
              relu: bool = False, mean_only: bool = False, log_softmax: bool = False,
@@ -430,52 +484,29 @@ def lrt_gemm(x, e_w, var_w, *, I: int, O: int, bias_mean=None, bias_var=None, va
              finalize=None, half: bool = False, single: Optional[bool] = None):
     """lbbnn_lrt_gemm: out = x.e_w^T + b [+ sqrt(x^2.var_w^T + bv) * eps] [ReLU].
     single: ONE 16-bit product per moment (the reduced "bf16" / "fp16" modes; default: what the process-wide precision says).
-    finalize = (layer descriptors, n, rng pointer for K5, kl_total pointer[, live rng pointer, advance]):
-    lbbnn_lrt_gemm_finalize_adv -- the KL finalize of the whole network (n may be 0) and the forward's RNG advance ride in
-    this launch."""
-    if x.dim() != 2 or x.shape[1] != I:
-        raise RuntimeError("bnn_amd: input must be (B,%d), got %s" % (I, tuple(x.shape)))
-    B = x.shape[0]
+    With ``std_out`` or ``finalize`` (a Finalize: the KL finalize of the whole network, n may be 0, and the forward's RNG advance
+    ride in this launch) the call is lbbnn_lrt_gemm_ex: the descriptor carries what a forward adds to the product."""
+    dev = x.device
+    x = _gemm_input(x, I, "input", O, eps, finalize)
+    B = 0 if x is None else x.shape[0]
     if out is None:
-        out = torch.empty((B, O), dtype=torch.float32, device=x.device)
-    if eps is not None and tuple(eps.shape) != (B, O):
-        raise RuntimeError("bnn_amd: eps must be (%d,%d), got %s" % (B, O, tuple(eps.shape)))
+        out = torch.empty((B, O), dtype=torch.float32, device=dev)
+    if x is None:
+        return out
     flags = ((F_RELU if relu else 0) | (F_MEAN_ONLY if mean_only else 0) | (F_LOG_SOFTMAX if log_softmax else 0)
              | (F_SPLIT16 if split else 0)
              | (F_SINGLE16 if (split and not mean_only and (single if single is not None else _PRECISION in ("bf16", "fp16"))) else 0)
              | (F_HALF16 if (half and split and not mean_only) else 0))
-    if B == 0 and finalize is None:    # empty batch: (0,O) activations, as torch.mm gives; the KL side is unaffected
-        return out
-    if x.stride(1) != 1 or (x.stride(0) < I):
-        x = x.contiguous()
-    ev = GEMM_EVENTS.take() if GEMM_EVENTS is not None else None
-    if ev is not None:
-        ev[0].record()
-    if finalize is not None:
-        # (descs, n, fin_rng, kl_total[, rng_live, advance]): with the last two the piggy workgroup also advances the live offset
-        live, adv = (finalize[4], finalize[5]) if len(finalize) > 4 else (None, 0)
-        rc = _lib.lib().lbbnn_lrt_gemm_finalize_adv(
+    if std_out is None and finalize is None:
+        _gemm_call("lbbnn_lrt_gemm", (
             _ptr_rows(x, "input"), x.stride(0), _ptr(e_w), _ptr(var_w), operand_ld(I),
             _ptr(bias_mean), _ptr(bias_var), _ptr(var_scale), _ptr(eps, "eps"),
             rng.data_ptr() if rng is not None else None, rng_stream, row_offset,
-            out.data_ptr(), out.stride(0), _ptr(std_out, "std_out"), B, I, O, flags,
-            finalize[0], finalize[1], finalize[2], finalize[3], live, adv, _stream())
-    elif std_out is None:
-        rc = _lib.lib().lbbnn_lrt_gemm(
-            _ptr_rows(x, "input"), x.stride(0), _ptr(e_w), _ptr(var_w), operand_ld(I),
-            _ptr(bias_mean), _ptr(bias_var), _ptr(var_scale), _ptr(eps, "eps"),
-            rng.data_ptr() if rng is not None else None, rng_stream, row_offset,
-            out.data_ptr(), out.stride(0), B, I, O, flags, _stream())
+            out.data_ptr(), out.stride(0), B, I, O, flags), B, I, O)
     else:
-        rc = _lib.lib().lbbnn_lrt_gemm_train(
-            _ptr_rows(x, "input"), x.stride(0), _ptr(e_w), _ptr(var_w), operand_ld(I),
-            _ptr(bias_mean), _ptr(bias_var), _ptr(var_scale), _ptr(eps, "eps"),
-            rng.data_ptr() if rng is not None else None, rng_stream, row_offset,
-            out.data_ptr(), out.stride(0), _ptr(std_out, "std_out"), B, I, O, flags, _stream())
-    _lib.check(rc, "lbbnn_lrt_gemm")
-    if ev is not None:
-        ev[1].record()
-        GEMM_EVENTS.append((B, I, O, ev[0], ev[1]))
+        d = _gemm_desc(x, e_w, var_w, I=I, O=O, bias_mean=bias_mean, bias_var=bias_var, var_scale=var_scale, eps=eps, rng=rng,
+                       rng_stream=rng_stream, row_offset=row_offset, out=out, std_out=std_out, flags=flags, finalize=finalize)
+        _gemm_call("lbbnn_lrt_gemm_ex", (ctypes.byref(d),), B, I, O)
     return out
 
 
@@ -737,32 +768,20 @@ def lrt_gemm16(x, e_w, var_w, e_scale, v_scale, *, I: int, O: int, bias_mean=Non
     ``finalize`` as in lrt_gemm.  ``head``: dict(e_w, var_w (C, operand_ld(O)) fp32 operands of the <= 16-class layer that follows,
     bias_mean, bias_var, eps (or None), rng_stream, out (B, C), slab (head_slab_floats(B, O)), log_softmax) -- the head's GEMM
     is folded into this launch's epilogue + a small finalize launch.  Returns (out or None, out_planes or None)."""
-    B = x.shape[0]
-    if x_planes:
-        if x.dim() != 2 or x.shape[1] != plane_ld(I) or x.stride(1) != 1:
-            raise RuntimeError("bnn_amd: x planes must be (B,%d), got %s" % (plane_ld(I), tuple(x.shape)))
-    elif x.dim() != 2 or x.shape[1] != I:
-        raise RuntimeError("bnn_amd: input must be (B,%d), got %s" % (I, tuple(x.shape)))
+    if x_planes and x.dim() == 2 and x.stride(1) != 1:
+        raise RuntimeError("bnn_amd: x planes must have dense rows, got strides %s" % (tuple(x.stride()),))
+    dev = x.device
+    x = _gemm_input(x, plane_ld(I) if x_planes else I, "x planes" if x_planes else "input", O, eps, finalize)
+    B = 0 if x is None else x.shape[0]
     if out is None and want_out:
-        out = torch.empty((B, O), dtype=torch.float32, device=x.device)
-    if eps is not None and tuple(eps.shape) != (B, O):
-        raise RuntimeError("bnn_amd: eps must be (%d,%d), got %s" % (B, O, tuple(eps.shape)))
-    if B == 0 and finalize is None:
+        out = torch.empty((B, O), dtype=torch.float32, device=dev)
+    if x is None:
         return out, out_planes
-    if x.stride(1) != 1 or (x.stride(0) < x.shape[1]):
-        x = x.contiguous()
-    d = _lib.GemmDesc()
-    d.x, d.ldx = _ptr_rows(x, "input"), x.stride(0)
-    d.e_w, d.var_w, d.ld = _ptr(e_w), _ptr(var_w), operand_ld(I)
+    d = _gemm_desc(x, e_w, var_w, I=I, O=O, bias_mean=bias_mean, bias_var=bias_var, var_scale=var_scale, eps=eps, rng=rng,
+                   rng_stream=rng_stream, row_offset=row_offset, out=out, std_out=std_out, finalize=finalize,
+                   flags=F_F16S | (F_RELU if relu else 0) | (F_VAR1 if var1 else 0) | (F_XPLANES if x_planes else 0))
     d.mean_scale, d.wvar_scale = _ptr(e_scale, "e_scale"), _ptr(v_scale, "v_scale")
-    d.bias_mean, d.bias_var, d.var_scale, d.eps = _ptr(bias_mean), _ptr(bias_var), _ptr(var_scale), _ptr(eps, "eps")
-    d.rng = rng.data_ptr() if rng is not None else None
-    d.rng_stream, d.row_offset = rng_stream, row_offset
-    d.out, d.ldo = (out.data_ptr(), out.stride(0)) if out is not None else (None, 0)
     d.out_planes, d.ldp = (out_planes.data_ptr(), out_planes.stride(0)) if out_planes is not None else (None, 0)
-    d.std_out = _ptr(std_out, "std_out")
-    d.B, d.I, d.O = B, I, O
-    d.flags = F_F16S | (F_RELU if relu else 0) | (F_VAR1 if var1 else 0) | (F_XPLANES if x_planes else 0)
     if head is not None:
         C = head["out"].shape[1]
         d.head_e, d.head_v, d.head_ld, d.head_classes = _ptr(head["e_w"]), _ptr(head["var_w"]), head["e_w"].stride(0), C
@@ -770,18 +789,7 @@ def lrt_gemm16(x, e_w, var_w, e_scale, v_scale, *, I: int, O: int, bias_mean=Non
         d.head_rng_stream = head.get("rng_stream", 0)
         d.head_out, d.head_ldo, d.head_slab = head["out"].data_ptr(), head["out"].stride(0), _ptr(head["slab"])
         d.head_flags = F_LOG_SOFTMAX if head.get("log_softmax") else 0
-    if finalize is not None:
-        live, adv = (finalize[4], finalize[5]) if len(finalize) > 4 else (None, 0)
-        d.layers = finalize[0] if finalize[0] is not None else None
-        d.n_layers, d.fin_rng, d.kl_total, d.rng_live, d.advance = finalize[1], finalize[2], finalize[3], live, adv
-    ev = GEMM_EVENTS.take() if GEMM_EVENTS is not None else None
-    if ev is not None:
-        ev[0].record()
-    rc = _lib.lib().lbbnn_lrt_gemm_ex(ctypes.byref(d), _stream())
-    _lib.check(rc, "lbbnn_lrt_gemm_ex")
-    if ev is not None:
-        ev[1].record()
-        GEMM_EVENTS.append((B, I, O, ev[0], ev[1]))
+    _gemm_call("lbbnn_lrt_gemm_ex", (ctypes.byref(d),), B, I, O)
     return out, out_planes
 
 

@@ -358,35 +358,14 @@ int lbbnn_layers_finalize(const lbbnn_layer_desc_t* layers, int n, uint64_t* rng
  *   forward that reads the live state (the flow kernels), so every LATER kernel of this forward -- the GEMMs, the KL
  *   finalize -- must be given rng_snap as its `rng`.  rng == NULL: no RNG in use, nothing is copied.
  *
- * lbbnn_lrt_gemm_finalize = lbbnn_lrt_gemm_train (same arguments up to `flags`; std_out may be NULL) + the work of lbbnn_layers_finalize
- *   (every layer's KL tail from its descriptor, kl_layer outputs, *kl_total if non-NULL; no RNG advance) for the n
- *   layers, computed by ONE extra workgroup of the same launch while the tiles are computed: the KL tail depends on
- *   parameters only, so it needs no launch of its own after the last GEMM.  fin_rng: the state K5 draws eps_act from
- *   (rng_snap above).  When the GEMM kernel selected for this shape cannot host the extra workgroup (small-tile
- *   configuration, O <= 16, not enough dynamic LDS) the finalize runs as a launch of its own after the GEMM: same
- *   results either way.
+ * The first GEMM of the forward (lbbnn_lrt_gemm_ex, lbbnn_gemm_desc_t::layers .. advance below) then carries the work of
+ *   lbbnn_layers_finalize in its own launch, RNG advance included.  That is what lets lbbnn_layers_operands_snap run with
+ *   advance = 0 -- and only then do its workgroups compute the planar flows of the layers THEMSELVES from the live
+ *   {seed, offset} (no K3 launch ahead of the weight pass; weight_pass.hip): the advance has to come from a later launch of
+ *   the same forward, none of whose kernels reads the live offset (they are given rng_snap).
  */
 int lbbnn_layers_operands_snap(const lbbnn_layer_desc_t* layers, int n, uint64_t* rng, uint64_t* rng_snap,
                                uint64_t advance, void* stream);
-int lbbnn_lrt_gemm_finalize(const float* x, int ldx, const void* e_w, const void* var_w, int ld,
-                            const float* bias_mean, const float* bias_var, const float* var_scale,
-                            const float* eps, const uint64_t* rng, uint32_t rng_stream, int64_t row_offset,
-                            float* out, int ldo, float* std_out, int B, int I, int O, int flags,
-                            const lbbnn_layer_desc_t* layers, int n, const uint64_t* fin_rng, float* kl_total,
-                            void* stream);
-
-/* lbbnn_lrt_gemm_finalize_adv = lbbnn_lrt_gemm_finalize + `rng_live[1] += advance`, done by the same extra workgroup
- * (n == 0 allowed: nothing to finalize, the advance is then a tiny launch after the GEMM).  This is what lets
- * lbbnn_layers_operands_snap run with advance = 0 -- and only then do its workgroups compute the planar flows of the
- * layers THEMSELVES from the live {seed, offset} (no K3 launch ahead of the weight pass; weight_pass.hip): the advance
- * has to come from a later launch of the same forward, none of whose kernels reads the live offset (they are given
- * rng_snap). */
-int lbbnn_lrt_gemm_finalize_adv(const float* x, int ldx, const void* e_w, const void* var_w, int ld,
-                                const float* bias_mean, const float* bias_var, const float* var_scale,
-                                const float* eps, const uint64_t* rng, uint32_t rng_stream, int64_t row_offset,
-                                float* out, int ldo, float* std_out, int B, int I, int O, int flags,
-                                const lbbnn_layer_desc_t* layers, int n, const uint64_t* fin_rng, float* kl_total,
-                                uint64_t* rng_live, uint64_t advance, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Ensemble evaluation (test_ensemble, LBBNN-GP-MF-MNF.py:286-294 / ...LRT.py:241-247: TEST_SAMPLES stochastic forwards of
@@ -410,12 +389,7 @@ int lbbnn_lrt_gemm_members(const float* x, int ldx, int64_t x_mstride, const voi
                            float* out, int ldo, int64_t o_mstride, int B, int I, int O, int flags, int members,
                            void* stream);
 
-/* End of a network forward: *kl_total = sum_l *kl_layers[l] (fixed order; BayesianNetwork.kl(),
- * …LRT.py:213-214) and rng[1] += advance, one tiny launch.  kl_total may be NULL (n ignored). */
-int lbbnn_forward_finish(uint64_t* rng, uint64_t advance, const float* const* kl_layers, int n,
-                         float* kl_total, void* stream);
-
-/* Network KL of a network deeper than one batched launch holds.  A network of n layers issues its batched calls in
+/* Network KL (BayesianNetwork.kl(), …LRT.py:213-214) of a network deeper than one batched launch holds.  A network of n layers issues its batched calls in
  * ceil(n / LBBNN_MAX_LAYERS) groups of consecutive layers; each group's KL finalize writes its layers' values into ONE
  * contiguous buffer kl_layers[0..n), and this call forms *total = ((0 + kl_layers[0]) + kl_layers[1]) + ... in fp32 -- the
  * order and precision in which the finalize of a single group adds its total.  1 <= n <= LBBNN_MAX_DEPTH; one launch of one
@@ -965,8 +939,8 @@ int lbbnn_weight_operands_t(const float* weight_mu, const float* weight_rho, con
 /* ---------------------------------------------------------------------------------------------
  * Training support (the backward of loss.backward(), LBBNN-GP-MF-LRT.py:225).
  *
- * lbbnn_lrt_gemm_train = lbbnn_lrt_gemm that additionally stores std_out[b,o] = sqrt(var[b,o])
- * (pre-ReLU), which the backward needs for  dL/dvar = g * eps / (2 * std).
+ * The training forward's GEMM is lbbnn_lrt_gemm_ex with lbbnn_gemm_desc_t::std_out: it additionally stores
+ * std_out[b,o] = sqrt(var[b,o]) (pre-ReLU), which the backward needs for  dL/dvar = g * eps / (2 * std).
  *
  * lbbnn_transpose_operand: dst[c][r] = src[r][c] (squared when `square`) for src (R,C) with row stride
  * lds_src, written as a GEMM operand [C][ld] (ld = lbbnn_operand_ld(R), zero tail; fp32 or, with
@@ -975,10 +949,6 @@ int lbbnn_weight_operands_t(const float* weight_mu, const float* weight_rho, con
  *   dX  = G_m . W_m + 2 x (.) (G_v . W_v)      operands W_m^T, W_v^T          (K = O)
  *   dW_m = G_m^T . x ,  dW_v = G_v^T . x^2     operands x^T, (x^2)^T          (K = B)
  */
-int lbbnn_lrt_gemm_train(const float* x, int ldx, const void* e_w, const void* var_w, int ld,
-                         const float* bias_mean, const float* bias_var, const float* var_scale,
-                         const float* eps, const uint64_t* rng, uint32_t rng_stream, int64_t row_offset,
-                         float* out, int ldo, float* std_out, int B, int I, int O, int flags, void* stream);
 
 /* lbbnn_format_operand: dst[r][c] = src[r][c] (squared when `square`) as a GEMM operand [R][ld] (ld = lbbnn_operand_ld(C),
  * zero tail, fp32 or LBBNN_F_SPLIT16) -- no transpose: the matrix already has the contraction index contiguous.  Used by
@@ -1434,7 +1404,23 @@ int lbbnn_mnf_flow_dense_backward(const lbbnn_dense_bwd_args_t* args, void* stre
 int lbbnn_mnf_flow_dense_backward_batch(const lbbnn_dense_bwd_args_t* args, int n, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Round 3: the row-scaled FP16 operand format (LBBNN_F_F16S) and the descriptor form of the dual-moment GEMM.
+ * The descriptor form of the dual-moment GEMM (every operand format), and round 3's row-scaled FP16 operand format
+ * (LBBNN_F_F16S), which only the descriptor form takes.
+ *
+ * lbbnn_lrt_gemm is the product and nothing else.  lbbnn_lrt_gemm_ex(desc) carries everything a forward adds to it:
+ *   - std_out (refused together with LBBNN_F_MEAN_ONLY: LBBNN_E_FLAGS);
+ *   - layers / n_layers / fin_rng / kl_total: the work of lbbnn_layers_finalize for the n_layers layers (every layer's KL tail
+ *     from its descriptor, kl_layer outputs, *kl_total if non-NULL), computed by ONE extra workgroup of the same launch while
+ *     the tiles are computed: the KL tail depends on parameters only, so it needs no launch of its own.  fin_rng: the state K5
+ *     draws eps_act from (rng_snap of lbbnn_layers_operands_snap).  When the kernel selected for this shape cannot host the
+ *     extra workgroup (small-tile configuration, O <= 16, not enough dynamic LDS) the finalize runs as a launch of its own
+ *     after the GEMM: same results either way.  n_layers = 0 is the plain product;
+ *   - rng_live / advance: rng_live[1] += advance, done by the same extra workgroup (with n_layers = 0: a tiny launch after
+ *     the GEMM);
+ *   - with LBBNN_F_F16S: x as planes, planes out, the head fold.
+ * Flags by format.  Without LBBNN_F_F16S (fp32 rows, or bf16 hi | lo with LBBNN_F_SPLIT16): the flags and checks of
+ * lbbnn_lrt_gemm; LBBNN_F_VAR1, LBBNN_F_XPLANES or a non-NULL mean_scale, wvar_scale, out_planes or head_out is refused with
+ * LBBNN_E_FLAGS before anything else is looked at.  With LBBNN_F_F16S: LBBNN_F_RELU | LBBNN_F_VAR1 | LBBNN_F_XPLANES only.
  *
  * Arithmetic (replaces the same reference lines as lbbnn_lrt_gemm: LBBNN-GP-MF-LRT.py:172-175, LBBNN-GP-MF-MNF.py:197-200):
  *   every operand value w is held as hi + lo, both IEEE fp16, products on v_mfma_f32_16x16x32_f16, fp32 accumulate:
@@ -1461,9 +1447,9 @@ int lbbnn_mnf_flow_dense_backward_batch(const lbbnn_dense_bwd_args_t* args, int 
 
 typedef struct lbbnn_gemm_desc {
     const void* x; int ldx;                      /* (B, I): fp32 rows of ldx floats, or planes (ldx fp32-sized slots per row) */
-    const void* e_w; const void* var_w; int ld;  /* [O][ld] operands from lbbnn_layers_operands (split == 2) / lbbnn_weight_pass_f16 */
-    const float* mean_scale;                     /* (O) e_scale  */
-    const float* wvar_scale;                     /* (O) v_scale  */
+    const void* e_w; const void* var_w; int ld;  /* [O][ld] operands in the format `flags` names (lbbnn_layers_operands, lbbnn_weight_pass[_f16]) */
+    const float* mean_scale;                     /* (O) e_scale; NULL without LBBNN_F_F16S */
+    const float* wvar_scale;                     /* (O) v_scale; NULL without LBBNN_F_F16S */
     const float* bias_mean;                      /* (O) or NULL  */
     const float* bias_var;                       /* (O) or NULL  */
     const float* var_scale;                      /* (O) or NULL: extra per-feature factor on the variance product */
@@ -1472,8 +1458,8 @@ typedef struct lbbnn_gemm_desc {
     float* out; int ldo;                         /* (B, O) fp32 output, or NULL when only planes are wanted       */
     void* out_planes; int ldp;                   /* (B, ldp) plane rows for the next layer, or NULL; needs O % 8 == 0, ldp % 32 == 0 */
     float* std_out;                              /* (B, O) sqrt(var) for the backward pass, or NULL               */
-    int B, I, O, flags;                          /* LBBNN_F_RELU | LBBNN_F_F16S | LBBNN_F_VAR1 | LBBNN_F_XPLANES   */
-    /* optional KL finalize of a network carried by one extra workgroup (as lbbnn_lrt_gemm_finalize_adv) */
+    int B, I, O, flags;                          /* LBBNN_F_F16S with LBBNN_F_RELU | LBBNN_F_VAR1 | LBBNN_F_XPLANES, or the flags of lbbnn_lrt_gemm */
+    /* optional KL finalize of a network and RNG advance carried by one extra workgroup (above) */
     const lbbnn_layer_desc_t* layers; int n_layers; const uint64_t* fin_rng; float* kl_total;
     uint64_t* rng_live; uint64_t advance;
     /* optional HEAD FOLD (head_out != NULL; needs LBBNN_F_RELU): the layer that FOLLOWS this one has head_classes <= 16 outputs

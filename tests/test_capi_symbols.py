@@ -147,8 +147,17 @@ def test_round3_entry_points_argument_checks(lib):
     from bnn_amd import _lib
     fake = ctypes.c_void_p(4096)
     assert lib.lbbnn_lrt_gemm_ex(None, None) == -1
+    # without LBBNN_F_F16S (fp32 / bf16 operands) what only the fp16 format has is refused before anything else is looked at:
+    # every one of these descriptors is also invalid at a later check (no x: -1)
+    for flags, field in ((0x80, None), (0x100, None), (0x4 | 0x80, None), (0, "mean_scale"), (0, "wvar_scale"), (0x4, "out_planes"),
+                         (0, "head_out")):
+        d = _lib.GemmDesc()
+        d.flags = flags
+        if field:
+            setattr(d, field, 4096)
+        assert lib.lbbnn_lrt_gemm_ex(ctypes.byref(d), None) == -4, (flags, field)
     d = _lib.GemmDesc()
-    d.flags = 0x4                                           # not the fp16 format: the descriptor form refuses
+    d.flags = 0x40 | 0x4                                    # the fp16 format has no LBBNN_F_SPLIT16 (also: no operands, -1)
     assert lib.lbbnn_lrt_gemm_ex(ctypes.byref(d), None) == -4
     d.flags = 0x40
     d.B, d.I, d.O = 4, 64, 80
@@ -218,6 +227,7 @@ _F = ctypes.c_void_p(4096)            # never dereferenced
 _ODD = ctypes.c_void_p(4100)          # off 16 bytes
 _RELU, _MEAN, _SPLIT, _LSM, _SINGLE, _HALF = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
 _WIDE = 0x20000000                    # a row stride whose second row lies past the 32-bit buffer offsets
+_UNKNOWN = 0x200                      # a flag no form knows (0x100 is LBBNN_F_XPLANES: a descriptor without LBBNN_F_F16S refuses it at once)
 
 # one dual-moment product that would launch: every row below breaks it, so nothing is launched
 _GEMM = dict(x=_F, ldx=8, e_w=_F, var_w=_F, ld=32, bias_mean=None, bias_var=None, var_scale=None, eps=_F, rng=None,
@@ -237,8 +247,8 @@ _MMEAN = dict(x=_F, ldx=8, x_mstride=0, w=_F, w_mstride=0, ld=32, bias=None, b_m
 _DISPATCH = [
     (dict(B=0, x=None), 0),                                   # empty batch: nothing to do, before the NULL check
     (dict(x=None, B=-1), -1), (dict(e_w=None), -1), (dict(out=None), -1),
-    (dict(B=-1, flags=0x100), -2), (dict(I=0), -2), (dict(O=0), -2), (dict(ldx=4), -2), (dict(ldo=8), -2),
-    (dict(flags=0x100, var_w=None), -4),                      # unknown flag
+    (dict(B=-1, flags=_UNKNOWN), -2), (dict(I=0), -2), (dict(O=0), -2), (dict(ldx=4), -2), (dict(ldo=8), -2),
+    (dict(flags=_UNKNOWN, var_w=None), -4),                      # unknown flag
     (dict(flags=_HALF | _SPLIT, var_w=None), -4),             # HALF16 without SINGLE16
     (dict(flags=_HALF | _SINGLE | _SPLIT | _MEAN), -4),       # HALF16 on the mean-only form
     (dict(flags=_LSM, var_w=None), -4),                       # log_softmax with O > 16
@@ -254,22 +264,22 @@ _DISPATCH = [
     (dict(flags=_SPLIT, O=1 << 24, ldo=1 << 24), -2),         # ... and the operands
 ]
 
+_POSITIONAL = {k: v for k, v in _GEMM.items() if k != "std_out"}      # lbbnn_lrt_gemm: the product and nothing else
+
+# "lbbnn_lrt_gemm_ex ...": the dict fills an lbbnn_gemm_desc_t without LBBNN_F_F16S (n is its n_layers)
 _RETURN_CODES = {
-    "lbbnn_lrt_gemm_train": (_GEMM, [(dict(flags=_MEAN, std_out=_F, x=None), -4)] + _DISPATCH),
-    "lbbnn_lrt_gemm_finalize": (_FIN, [
-        (dict(n=0, x=None), -2), (dict(n=-1, flags=_MEAN, std_out=_F), -2),
-        (dict(flags=_MEAN, std_out=_F, layers=None), -4),
-        (dict(layers=None, x=None), -1), (dict(n=5, x=None), -2),       # more than LBBNN_MAX_LAYERS
-        (dict(layers="want_kl", x=None), -1),                           # a KL without its buffers
-        (dict(kl_total=_F, x=None), -1),                                # a total needs every layer's KL
-    ] + _DISPATCH[1:]),                                                 # (an empty batch still launches the finalize)
-    "lbbnn_lrt_gemm_finalize_adv": (_ADV, [
+    "lbbnn_lrt_gemm": (_POSITIONAL, _DISPATCH),              # it no longer forwards: the same precedence, pinned here
+    "lbbnn_lrt_gemm_ex std_out": (_GEMM, [(dict(flags=_MEAN, std_out=_F, x=None), -4)] + _DISPATCH),
+    "lbbnn_lrt_gemm_ex finalize": (_ADV, [
         (dict(n=-1, advance=1), -2), (dict(layers=None, advance=1), -2),
         (dict(advance=1, flags=_MEAN, std_out=_F), -1),                 # an advance without rng_live
         (dict(flags=_MEAN, std_out=_F, n=0, x=None), -4),
+        (dict(flags=_MEAN, std_out=_F, layers="want_kl"), -4),          # ... before the layer descriptors are looked at
         (dict(n=0, layers=None, x=None), -1), (dict(n=0, layers=None, B=0), 0),     # n = 0: the plain product
-        (dict(n=5, x=None), -2), (dict(layers="want_kl", x=None), -1), (dict(kl_total=_F, x=None), -1),
-    ] + _DISPATCH[1:]),
+        (dict(n=5, x=None), -2),                                        # more than LBBNN_MAX_LAYERS
+        (dict(layers="want_kl", x=None), -1),                           # a KL without its buffers
+        (dict(kl_total=_F, x=None), -1),                                # a total needs every layer's KL
+    ] + _DISPATCH[1:]),                                                 # (an empty batch still launches the finalize)
     "lbbnn_matmul_splitk": (_SPLITK, [
         (dict(kchunk=0, x=None), -3), (dict(kchunk=-32, x=None), -3), (dict(kchunk=48, x=None), -3),
         (dict(B=0, x=None), 0), (dict(x=None, B=-1), -1), (dict(w_op=None), -1), (dict(out=None), -1),
@@ -294,7 +304,10 @@ _RETURN_CODES = {
 @pytest.mark.parametrize("name", sorted(_RETURN_CODES))
 def test_gemm_entry_points_early_return_codes(lib, name):
     """Every early return of the dual-moment GEMM's entry points that no other host test calls, in the order the code takes
-    them (nothing is launched): a call that is invalid in two ways returns the code of the earlier check."""
+    them (nothing is launched): a call that is invalid in two ways returns the code of the earlier check.  The forms with
+    std_out and with a finalize go through the descriptor (lbbnn_lrt_gemm_ex without LBBNN_F_F16S).  The descriptor has no rule
+    "n <= 0 is refused" (the removed lbbnn_lrt_gemm_finalize had one): n = 0 is the plain product, and a missing ``layers``
+    with n > 0 is a shape error (-2) before the flags are looked at."""
     from bnn_amd import _lib
     base, rows = _RETURN_CODES[name]
     layers = {None: None, "one": (_lib.LayerDesc * 5)(), "want_kl": (_lib.LayerDesc * 5)()}
@@ -304,4 +317,10 @@ def test_gemm_entry_points_early_return_codes(lib, name):
         args = dict(base, **change)
         if "layers" in args:
             args["layers"] = layers[args["layers"]]
-        assert getattr(lib, name)(*args.values(), None) == code, (name, change)
+        if name.startswith("lbbnn_lrt_gemm_ex"):
+            d = _lib.GemmDesc()
+            for k, v in args.items():
+                setattr(d, "n_layers" if k == "n" else k, v.value if isinstance(v, ctypes.c_void_p) else v)
+            assert lib.lbbnn_lrt_gemm_ex(ctypes.byref(d), None) == code, (name, change)
+        else:
+            assert getattr(lib, name)(*args.values(), None) == code, (name, change)

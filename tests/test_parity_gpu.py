@@ -2363,7 +2363,7 @@ def test_weight_operands_t_matches_weight_pass_plus_transpose(bnn, dev, O, I, sp
 @pytest.mark.gpu
 @pytest.mark.parametrize("dims,B", [((784, 1200, 1200, 10), 4096), ((40, 48, 24, 10), 64), ((64, 16, 16, 10), 32)])
 def test_gemm_hosted_finalize_equals_standalone_finalize(bnn, dev, dims, B):
-    """lbbnn_lrt_gemm_finalize: the KL tail computed by the extra workgroup of a GEMM launch (big-tile kernel, 2-wave
+    """lbbnn_lrt_gemm_ex with layers: the KL tail computed by the extra workgroup of a GEMM launch (big-tile kernel, 2-wave
     small-tile kernel) or, where the kernel cannot host it (O <= 16: skinny kernel), by the fall-back launch, against the
     stand-alone lbbnn_layers_finalize on the same inputs: per-layer KLs and total (same arithmetic, 1e-6 relative), and
     the RNG offset advanced exactly once per forward."""
