@@ -171,7 +171,13 @@ class StudyArgs(ctypes.Structure):
                 ("epochs", c_i), ("first_epoch", c_i), ("n_epochs", c_i)]
 
 
+class MnfStudyArgs(ctypes.Structure):
+    """lbbnn_mnf_study_args_t: lbbnn_study_args_t's members, then the transform counts of the two flows"""
+    _fields_ = list(StudyArgs._fields_) + [("Tz", c_i), ("Tr", c_i)]
+
+
 STUDY_MAX_I, STUDY_MAX_O, STUDY_MAX_WEIGHTS, STUDY_MAX_BATCH, STUDY_HISTORY_COLS = 256, 16, 1024, 4096, 6     # LBBNN_STUDY_*
+STUDY_MAX_TRANSFORMS = 4
 
 
 class CopyList(ctypes.Structure):
@@ -477,6 +483,7 @@ SIGNATURES = {
     "lbbnn_adam_step_groups_guarded": (c_i, [ctypes.POINTER(AdamGroupList), c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p]),
     "lbbnn_sgd_step_groups_guarded": (c_i, [ctypes.POINTER(AdamGroupList), c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p]),
     "lbbnn_lrt_study_fit": (c_i, [ctypes.POINTER(StudyArgs), c_p]),
+    "lbbnn_mnf_study_fit": (c_i, [ctypes.POINTER(MnfStudyArgs), c_p]),
     "lbbnn_grad_sumsq_workspace": (c_i64, [c_i64]),
     "lbbnn_grad_sumsq": (c_i, [ctypes.POINTER(AdamGroupList), c_p, c_i64, c_i64, ctypes.c_float, c_p, c_p, c_p]),
     "lbbnn_matmul_splitk": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),

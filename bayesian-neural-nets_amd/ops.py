@@ -1312,15 +1312,12 @@ def gate_structure(descs, n: int, samples: int, rng: torch.Tensor, *, kept, need
                                                p(feature_count), p(unit_count), p(need_out), _stream()), "lbbnn_gate_structure")
 
 
-def lrt_study_fit(*, params, exp_avg, exp_avg_sq, step, rng, skipped, x, y, priors, hyper, lr, restarts, history,
-                  I: int, O: int, batch: int, first_epoch: int, n_epochs: int):
-    """lbbnn_lrt_study_fit on caller-allocated device tensors (bnn_amd.study lays them out): ``params`` / ``exp_avg`` /
-    ``exp_avg_sq`` (R, 3 O I + 2 O) and ``step`` (R) float32, ``rng`` (R, 2) and ``skipped`` (R) int64, ``x`` (N, I) or (R, N, I),
-    ``y`` (N, O) or (R, N, O), ``priors`` (1 or R, 5) and ``hyper`` (R, 6) float32 rows of lbbnn_priors_t / lbbnn_adam_hyper_t,
-    ``lr`` (epochs) or (R, epochs), ``restarts`` int32 or None, ``history`` (R, epochs, 6) float64.  One launch; everything in
-    the first row is updated in place."""
+def _study_fit(entry, args_type, P, lr_cols, *, params, exp_avg, exp_avg_sq, step, rng, skipped, x, y, priors, hyper, lr, restarts,
+               history, I, O, batch, first_epoch, n_epochs, **counts):
+    """What lrt_study_fit and mnf_study_fit share: the checks of the caller's device tensors, the members the two argument
+    structs have in common, the call.  ``P``: the width of a packed row; ``lr_cols``: () for one rate per epoch, (3,) for the
+    three rate groups; ``counts``: the struct's further integer members."""
     R, epochs = params.shape[0], history.shape[1]
-    P = 3 * O * I + 2 * O
     checks = [("params", params, torch.float32, (R, P)), ("exp_avg", exp_avg, torch.float32, (R, P)),
               ("exp_avg_sq", exp_avg_sq, torch.float32, (R, P)), ("step", step, torch.float32, (R,)),
               ("rng", rng, torch.int64, (R, 2)), ("skipped", skipped, torch.int64, (R,)),
@@ -1337,21 +1334,42 @@ def lrt_study_fit(*, params, exp_avg, exp_avg_sq, step, rng, skipped, x, y, prio
     if x.shape not in ((N, I), (R, N, I)) or y.shape not in ((N, O), (R, N, O)):
         raise ValueError("bnn_amd: x must be (N, I) or (R, N, I) and y (N, O) or (R, N, O), got %s and %s"
                          % (tuple(x.shape), tuple(y.shape)))
-    if priors.shape not in ((1, 5), (R, 5)) or lr.shape not in ((epochs,), (R, epochs)):
-        raise ValueError("bnn_amd: priors must be (1 | R, 5) and lr (epochs) or (R, epochs)")
-    a = _lib.StudyArgs()
+    lr_shapes = ((epochs,) + lr_cols, (R, epochs) + lr_cols)
+    if priors.shape not in ((1, 5), (R, 5)) or tuple(lr.shape) not in lr_shapes:
+        raise ValueError("bnn_amd: priors must be (1 | R, 5) and lr %s or %s" % lr_shapes)
+    a = args_type()
     a.params, a.exp_avg, a.exp_avg_sq = params.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr()
     a.step, a.rng, a.skipped = step.data_ptr(), rng.data_ptr(), skipped.data_ptr()
     a.x, a.x_rstride = x.data_ptr(), (N * I if x.dim() == 3 else 0)
     a.y, a.y_rstride = y.data_ptr(), (N * O if y.dim() == 3 else 0)
     a.priors, a.priors_rstride = priors.data_ptr(), (1 if priors.shape[0] == R and R > 1 else 0)
-    a.hyper, a.lr, a.lr_rstride = hyper.data_ptr(), lr.data_ptr(), (epochs if lr.dim() == 2 else 0)
+    a.hyper, a.lr, a.lr_rstride = hyper.data_ptr(), lr.data_ptr(), (epochs if lr.dim() == 2 + len(lr_cols) else 0)
     n_restarts = 0 if restarts is None else restarts.numel()
     a.restarts, a.n_restarts = (restarts.data_ptr() if n_restarts else None), n_restarts
     a.history = history.data_ptr()
     a.R, a.I, a.O, a.N, a.batch = R, I, O, N, batch
     a.epochs, a.first_epoch, a.n_epochs = epochs, first_epoch, n_epochs
-    _lib.check(_lib.lib().lbbnn_lrt_study_fit(ctypes.byref(a), _stream()), "lbbnn_lrt_study_fit")
+    for k, v in counts.items():
+        setattr(a, k, v)
+    _lib.check(getattr(_lib.lib(), entry)(ctypes.byref(a), _stream()), entry)
+
+
+def lrt_study_fit(*, I: int, O: int, **kw):
+    """lbbnn_lrt_study_fit on caller-allocated device tensors (bnn_amd.study lays them out), keywords: ``params`` / ``exp_avg`` /
+    ``exp_avg_sq`` (R, 3 O I + 2 O) and ``step`` (R) float32, ``rng`` (R, 2) and ``skipped`` (R) int64, ``x`` (N, I) or (R, N, I),
+    ``y`` (N, O) or (R, N, O), ``priors`` (1 or R, 5) and ``hyper`` (R, 6) float32 rows of lbbnn_priors_t / lbbnn_adam_hyper_t,
+    ``lr`` (epochs) or (R, epochs), ``restarts`` int32 or None, ``history`` (R, epochs, 6) float64, ``batch``, ``first_epoch``,
+    ``n_epochs``.  One launch; everything in the first row is updated in place."""
+    _study_fit("lbbnn_lrt_study_fit", _lib.StudyArgs, 3 * O * I + 2 * O, (), I=I, O=O, **kw)
+
+
+def mnf_study_fit(*, I: int, O: int, Tz: int, Tr: int, **kw):
+    """lbbnn_mnf_study_fit on caller-allocated device tensors, as ``lrt_study_fit`` with these differences: ``params`` /
+    ``exp_avg`` / ``exp_avg_sq`` are (R, P), P = 3 O I + 2 O + 5 I + (Tz + Tr)(2 I + 1), rows in the order of
+    ``MNFBayesianLinear._param_list()``; ``lr`` is (epochs, 3) or (R, epochs, 3): the rates of the named tensors, of z_flow and
+    of r_flow."""
+    _study_fit("lbbnn_mnf_study_fit", _lib.MnfStudyArgs, 3 * O * I + 2 * O + 5 * I + (Tz + Tr) * (2 * I + 1), (3,),
+               I=I, O=O, Tz=Tz, Tr=Tr, **kw)
 
 
 # ----------------------------------------------------------------------------------------- workspaces

@@ -1,4 +1,4 @@
-"""Replicate studies: R independent one-layer LRT networks with a sigmoid head trained in one launch.
+"""Replicate studies: R independent one-layer LRT or planar-MNF networks with a sigmoid head trained in one launch.
 
 The simulation study of the latent-binary papers (LBBNN-GP-MF-MNFsim_study.py:305-395) builds k = 100 networks from seeds
 0..99, trains each for 500 epochs of 5 batches with the Adam rates switched at epochs 50 / 100 / 450, and reduces the 100 rows of
@@ -10,8 +10,15 @@ keeps the replicate's parameters, Adam state and Philox state on chip and loops 
     res = study.fit_replicates(nets, x, y, epochs=500, batch_size=400, lr=RATES, restarts=(50, 100, 450))
     print(study.selection_summary(res.inclusion_probabilities[:, 0], support))
 
-Not built: planar-MNF and baseline replicates, hidden layers, SGD, shuffled batches, HIP-graph capture of the call, data
-parallel.  Train such networks one by one with ``graphs.make_graphed_train_step``.
+The script's own family, MNF networks, goes through the same kernel's second instantiation (``lbbnn_mnf_study_fit``; DESIGN.md
+9.6) with planar flows and three rate groups -- the named tensors, z_flow, r_flow:
+
+    nets = study.make_mnf_replicates(100, (20, 1), num_transforms=2, priors=PRIORS, device=DEVICE)
+    res = study.fit_mnf_replicates(nets, x, y, epochs=500, batch_size=400, lr=RATES, lr_z_flow=Z_RATES, lr_r_flow=R_RATES,
+                                   restarts=(50, 100, 450))
+
+Not built: baseline replicates, RNVP / MNF-type flows, hidden layers, SGD, shuffled batches, HIP-graph capture of the call,
+data parallel.  Train such networks one by one with ``graphs.make_graphed_train_step``.
 """
 from typing import NamedTuple, Optional, Sequence
 
@@ -19,16 +26,18 @@ import torch
 
 from . import _lib, ops
 from ._lib import Priors
-from .layers import LRTBayesianNetwork
+from .layers import LRTBayesianNetwork, MNFBayesianNetwork
 
 PARAM_NAMES = ("weight_mu", "weight_rho", "lambdal", "bias_mu", "bias_rho")      # the order of a replicate's packed row
+MNF_VECTOR_NAMES = ("q0_mean", "q0_log_var", "r0_c", "r0_b1", "r0_b2")          # ... then z_flow.<t>.u / .w / .b, r_flow likewise
 HISTORY_COLUMNS = ("loss_mean", "nll_mean", "accuracy", "last_loss", "last_nll", "skipped_steps")
 STEPS_PER_LAUNCH = 2048        # default bound of one launch (epochs_per_launch=None): whole epochs of at most this many steps
 
 
 class StudyState(NamedTuple):
     """What a fit leaves besides the parameters, all on the device: pass it back as ``state=`` to continue.  ``exp_avg`` /
-    ``exp_avg_sq`` are (R, 3 O I + 2 O) rows packed as ``PARAM_NAMES`` (``unpack`` gives the named views), ``step`` the (R)
+    ``exp_avg_sq`` are (R, 3 O I + 2 O) rows packed as ``PARAM_NAMES`` (``unpack`` gives the named views; MNF replicates:
+    ``mnf_row_width`` wide, ``unpack_mnf``), ``step`` the (R)
     float Adam counters, ``rng`` the (R, 2) int64 Philox states {seed, offset} -- a replicate's offset grows by one per
     step, skipped steps included -- and ``skipped_steps`` the (R) int64 running counts."""
     exp_avg: torch.Tensor
@@ -55,6 +64,32 @@ def unpack(packed: torch.Tensor, O: int, I: int) -> dict:
     return out
 
 
+def mnf_row_width(O: int, I: int, Tz: int, Tr: int) -> int:
+    """P of an MNF replicate's packed row."""
+    return 3 * O * I + 2 * O + 5 * I + (Tz + Tr) * (2 * I + 1)
+
+
+def unpack_mnf(packed: torch.Tensor, O: int, I: int, Tz: int, Tr: int) -> dict:
+    """Named views of (R, P) packed rows of MNF replicates, in the order of ``MNFBayesianLinear._param_list()``: the five names
+    of ``unpack``, then q0_mean, q0_log_var, r0_c, r0_b1, r0_b2 (R, I), then ``z_flow.<t>.u`` / ``.w`` (R, I) and ``.b`` (R, 1)
+    for t < Tz and ``r_flow.<t>...`` for t < Tr."""
+    if packed.shape[1] != mnf_row_width(O, I, Tz, Tr):
+        raise ValueError("bnn_amd.study: a packed MNF row of O = %d, I = %d, Tz = %d, Tr = %d is %d wide, got %d"
+                         % (O, I, Tz, Tr, mnf_row_width(O, I, Tz, Tr), packed.shape[1]))
+    out = unpack(packed, O, I)
+    at = 3 * O * I + 2 * O
+    for n in MNF_VECTOR_NAMES:
+        out[n] = packed[:, at:at + I]
+        at += I
+    for fl, T in (("z_flow", Tz), ("r_flow", Tr)):
+        for t in range(T):
+            out["%s.%d.u" % (fl, t)] = packed[:, at:at + I]
+            out["%s.%d.w" % (fl, t)] = packed[:, at + I:at + 2 * I]
+            out["%s.%d.b" % (fl, t)] = packed[:, at + 2 * I:at + 2 * I + 1]
+            at += 2 * I + 1
+    return out
+
+
 def check_shapes(I: int, O: int, batch_size: int, N: int, R: int):
     """The limits of lbbnn_lrt_study_fit (include/lbbnn.h), refused here with their names."""
     if not (1 <= I <= _lib.STUDY_MAX_I and 1 <= O <= _lib.STUDY_MAX_O and O * I <= _lib.STUDY_MAX_WEIGHTS):
@@ -72,8 +107,8 @@ def check_shapes(I: int, O: int, batch_size: int, N: int, R: int):
 def _check_net(net):
     if not isinstance(net, LRTBayesianNetwork):
         raise NotImplementedError("bnn_amd.study: replicates are lrt.BayesianNetwork (one LRT layer, sigmoid head), got %s; "
-                                  "train MNF, baseline and VD networks one by one with graphs.make_graphed_train_step"
-                                  % type(net).__name__)
+                                  "planar-MNF networks go through fit_mnf_replicates; train other MNF, baseline and VD networks "
+                                  "one by one with graphs.make_graphed_train_step" % type(net).__name__)
     if len(net.dims) != 2:
         raise ValueError("bnn_amd.study: a replicate has one layer, got dims=%s; train deeper networks one by one with "
                          "graphs.make_graphed_train_step" % (net.dims,))
@@ -132,30 +167,32 @@ def _lr_table(lr, R, epochs, dev):
     return torch.tensor(vals, dtype=torch.float64).to(torch.float32).to(dev)
 
 
-def fit_replicates(nets, x, y, epochs: int, batch_size: int, lr=0.01, restarts=(), betas=(0.9, 0.999), eps: float = 1e-8,
-                   weight_decay: float = 0.0, seeds=None, offset: int = 0, priors=None, epochs_per_launch: Optional[int] = None,
-                   state: Optional[StudyState] = None) -> StudyResult:
-    """Train the R networks of ``nets`` (``make_replicates``, or hand-built ``lrt.BayesianNetwork((I, O), head="sigmoid")`` of
-    equal dims) independently on BCELoss(sum) + kl * batch_size / N with Adam, unshuffled batches in order, the last one of an
-    epoch possibly short -- the loop of the sim-study scripts -- in ceil(epochs / epochs_per_launch) launches, and copy every
-    replicate's trained parameters back into ``nets[r]``.
+def _named_tensors(net):
+    """[(name, tensor)] of a replicate's layer in the order of its packed row."""
+    l1 = net.l1
+    out = [(n, getattr(l1, n)) for n in PARAM_NAMES]
+    if isinstance(net, MNFBayesianNetwork):
+        out += [(n, getattr(l1, n)) for n in MNF_VECTOR_NAMES]
+        for fl in ("z_flow", "r_flow"):
+            for t, tr in enumerate(getattr(l1, fl).transforms):
+                out += [("%s.%d.u" % (fl, t), tr.u), ("%s.%d.w" % (fl, t), tr.w), ("%s.%d.b" % (fl, t), tr.bias)]
+    return out
 
-    x: (N, I) shared or (R, N, I); y: (N, O) or (R, N, O) float targets in [0, 1].  lr: one rate, a sequence of ``epochs``
-    rates (shared), or a device tensor (epochs,) / (R, epochs).  restarts: epochs at whose start the moments and the step
-    counter start afresh (the scripts re-create ``optim.Adam`` at 50 / 100 / 450).  betas / eps / weight_decay: one value or a
-    sequence of R.  seeds / offset: replicate r draws its step t from Philox state {seeds[r], offset + t} as layer l1 of a
-    network does; seeds defaults to the device RNG state's seed + r.  priors: default each net's own.  state: the ``state`` of
-    an earlier result continues it (its Philox states replace seeds / offset; epochs, lr and restarts count from this call's
-    first epoch).  A step whose loss or one of whose probabilities is not finite changes nothing and is counted.
 
-    Everything returned is on the device; the call reads nothing back to the host."""
+def _fit(nets, check_net, x, y, epochs, batch_size, lr_table, restarts, betas, eps, weight_decay, seeds, offset, priors,
+         epochs_per_launch, state, row_width, launch, unpack_rows) -> StudyResult:
+    """What fit_replicates and fit_mnf_replicates share: the checks, the tables, the launches and the copy back.
+    ``check_net(net)`` refuses and returns what must agree between replicates; ``lr_table(R, epochs, dev)``,
+    ``row_width(key)``, ``launch(key, **tensors)`` and ``unpack_rows(key, packed)`` are the family's."""
     nets = list(nets)
     if not nets:
         raise ValueError("bnn_amd.study: no replicates")
-    for n in nets:
-        _check_net(n)
+    keys = [check_net(n) for n in nets]
     if any(n.dims != nets[0].dims for n in nets):
         raise ValueError("bnn_amd.study: the replicates differ in dims: %s" % sorted({n.dims for n in nets}))
+    if any(k != keys[0] for k in keys):
+        raise ValueError("bnn_amd.study: the replicates differ in their transform counts (z_flow, r_flow): %s" % sorted(set(keys)))
+    key = keys[0]
     I, O = nets[0].dims
     R = len(nets)
     dev = nets[0].l1.weight_mu.device
@@ -206,9 +243,9 @@ def fit_replicates(nets, x, y, epochs: int, batch_size: int, lr=0.01, restarts=(
     hyper = hyper.to(torch.float32).to(dev)                             # (column 5, the flags word, is zero)
 
     with torch.no_grad():
-        packed = torch.stack([torch.cat([getattr(n.l1, name).detach().reshape(-1) for name in PARAM_NAMES]) for n in nets])
+        packed = torch.stack([torch.cat([t.detach().reshape(-1) for _, t in _named_tensors(n)]) for n in nets])
     packed = packed.to(torch.float32).contiguous()
-    P = 3 * O * I + 2 * O
+    P = row_width(key, O, I)
     if state is None:
         if seeds is None:
             base = ops.RngState.get(dev).seed
@@ -230,20 +267,121 @@ def fit_replicates(nets, x, y, epochs: int, batch_size: int, lr=0.01, restarts=(
                 raise ValueError("bnn_amd.study: state.%s must be a device tensor of shape %s" % (name, shape))
         st = StudyState(*(t.clone().contiguous() for t in state))       # the caller's state is left as it is
     prior_tab = _priors_table(nets, priors, dev)
-    lr_tab = _lr_table(lr, R, epochs, dev)
+    lr_tab = lr_table(R, epochs, dev)
     restart_tab = torch.tensor(rs, dtype=torch.int32).to(dev) if rs else None
     history = torch.zeros(R, epochs, len(HISTORY_COLUMNS), dtype=torch.float64, device=dev)
     for first in range(0, epochs, epochs_per_launch):
-        ops.lrt_study_fit(params=packed, exp_avg=st.exp_avg, exp_avg_sq=st.exp_avg_sq, step=st.step, rng=st.rng,
-                          skipped=st.skipped_steps, x=x, y=y, priors=prior_tab, hyper=hyper, lr=lr_tab, restarts=restart_tab,
-                          history=history, I=I, O=O, batch=batch_size, first_epoch=first,
-                          n_epochs=min(epochs_per_launch, epochs - first))
-    named = unpack(packed, O, I)
+        launch(key, params=packed, exp_avg=st.exp_avg, exp_avg_sq=st.exp_avg_sq, step=st.step, rng=st.rng,
+               skipped=st.skipped_steps, x=x, y=y, priors=prior_tab, hyper=hyper, lr=lr_tab, restarts=restart_tab,
+               history=history, I=I, O=O, batch=batch_size, first_epoch=first, n_epochs=min(epochs_per_launch, epochs - first))
+    named = unpack_rows(key, packed, O, I)
     with torch.no_grad():
         for r, n in enumerate(nets):
-            for name in PARAM_NAMES:
-                getattr(n.l1, name).copy_(named[name][r])
+            for name, t in _named_tensors(n):
+                t.copy_(named[name][r].view_as(t))
     return StudyResult(torch.sigmoid(named["lambdal"]), named, st, history, st.skipped_steps)
+
+
+def fit_replicates(nets, x, y, epochs: int, batch_size: int, lr=0.01, restarts=(), betas=(0.9, 0.999), eps: float = 1e-8,
+                   weight_decay: float = 0.0, seeds=None, offset: int = 0, priors=None, epochs_per_launch: Optional[int] = None,
+                   state: Optional[StudyState] = None) -> StudyResult:
+    """Train the R networks of ``nets`` (``make_replicates``, or hand-built ``lrt.BayesianNetwork((I, O), head="sigmoid")`` of
+    equal dims) independently on BCELoss(sum) + kl * batch_size / N with Adam, unshuffled batches in order, the last one of an
+    epoch possibly short -- the loop of the sim-study scripts -- in ceil(epochs / epochs_per_launch) launches, and copy every
+    replicate's trained parameters back into ``nets[r]``.
+
+    x: (N, I) shared or (R, N, I); y: (N, O) or (R, N, O) float targets in [0, 1].  lr: one rate, a sequence of ``epochs``
+    rates (shared), or a device tensor (epochs,) / (R, epochs).  restarts: epochs at whose start the moments and the step
+    counter start afresh (the scripts re-create ``optim.Adam`` at 50 / 100 / 450).  betas / eps / weight_decay: one value or a
+    sequence of R.  seeds / offset: replicate r draws its step t from Philox state {seeds[r], offset + t} as layer l1 of a
+    network does; seeds defaults to the device RNG state's seed + r.  priors: default each net's own.  state: the ``state`` of
+    an earlier result continues it (its Philox states replace seeds / offset; epochs, lr and restarts count from this call's
+    first epoch).  A step whose loss or one of whose probabilities is not finite changes nothing and is counted.
+
+    Everything returned is on the device; the call reads nothing back to the host."""
+    def check(net):
+        _check_net(net)
+        return ()
+    return _fit(nets, check, x, y, epochs, batch_size, lambda R, E, dev: _lr_table(lr, R, E, dev), restarts, betas, eps,
+                weight_decay, seeds, offset, priors, epochs_per_launch, state,
+                row_width=lambda key, O, I: 3 * O * I + 2 * O,
+                launch=lambda key, **kw: ops.lrt_study_fit(**kw),
+                unpack_rows=lambda key, packed, O, I: unpack(packed, O, I))
+
+
+def _check_mnf_net(net):
+    if not isinstance(net, MNFBayesianNetwork):
+        raise NotImplementedError("bnn_amd.study: fit_mnf_replicates takes mnf.BayesianNetwork (one planar-MNF layer, sigmoid "
+                                  "head), got %s; LRT networks go through fit_replicates, baseline and VD networks are trained "
+                                  "one by one with graphs.make_graphed_train_step" % type(net).__name__)
+    if len(net.dims) != 2:
+        raise ValueError("bnn_amd.study: a replicate has one layer, got dims=%s; train deeper networks one by one with "
+                         "graphs.make_graphed_train_step" % (net.dims,))
+    if net.head != "sigmoid":
+        raise ValueError('bnn_amd.study: a replicate has head="sigmoid", got %r; use graphs.make_graphed_train_step' % net.head)
+    kinds = (net.l1.z_flow.kind, net.l1.r_flow.kind)
+    if kinds != ("Planar", "Planar"):
+        raise NotImplementedError("bnn_amd.study: MNF replicates have planar flows (z_flow_type = r_flow_type = \"Planar\"), got "
+                                  "%s / %s; train networks with other flows one by one with graphs.make_graphed_train_step" % kinds)
+    Tz, Tr = len(net.l1.z_flow.transforms), len(net.l1.r_flow.transforms)
+    if Tz > _lib.STUDY_MAX_TRANSFORMS or Tr > _lib.STUDY_MAX_TRANSFORMS:
+        raise ValueError("bnn_amd.study: a replicate's flows have at most %d transforms each, got %d and %d; train longer flows "
+                         "one by one with graphs.make_graphed_train_step" % (_lib.STUDY_MAX_TRANSFORMS, Tz, Tr))
+    return (Tz, Tr)
+
+
+def make_mnf_replicates(R: int, dims, num_transforms: int = 2, seeds: Optional[Sequence[int]] = None, priors=None,
+                        lambdal_init=(1.5, 2.5), device=None):
+    """R networks ``mnf.BayesianNetwork(dims, num_transforms, z_flow_type="Planar", r_flow_type="Planar", head="sigmoid",
+    priors=priors[r], lambdal_init=...)``, replicate r built after ``torch.manual_seed(seeds[r])`` (default seeds 0 .. R - 1):
+    the values of the network a user builds by hand from that seed."""
+    dims = tuple(int(d) for d in dims)
+    if len(dims) != 2:
+        raise ValueError("bnn_amd.study: a replicate has one layer (dims = (I, O)), got dims=%s; train deeper networks one by "
+                         "one with graphs.make_graphed_train_step" % (dims,))
+    num_transforms = int(num_transforms)
+    if not 0 <= num_transforms <= _lib.STUDY_MAX_TRANSFORMS:
+        raise ValueError("bnn_amd.study: a replicate's flows have 0 to %d transforms, got %d; train longer flows one by one "
+                         "with graphs.make_graphed_train_step" % (_lib.STUDY_MAX_TRANSFORMS, num_transforms))
+    seeds = list(range(R)) if seeds is None else [int(s) for s in seeds]
+    if len(seeds) != R:
+        raise ValueError("bnn_amd.study: %d seeds for %d replicates" % (len(seeds), R))
+    plist = list(priors) if isinstance(priors, (list, tuple)) else [priors] * R
+    if len(plist) != R:
+        raise ValueError("bnn_amd.study: %d priors for %d replicates" % (len(plist), R))
+    nets = []
+    for r in range(R):
+        torch.manual_seed(seeds[r])
+        net = MNFBayesianNetwork(dims, num_transforms, z_flow_type="Planar", r_flow_type="Planar", head="sigmoid",
+                                 priors=plist[r], lambdal_init=lambdal_init)
+        nets.append(net.to(device) if device is not None else net)
+    return nets
+
+
+def fit_mnf_replicates(nets, x, y, epochs: int, batch_size: int, lr=0.01, lr_z_flow=None, lr_r_flow=None, restarts=(),
+                       betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, seeds=None, offset: int = 0, priors=None,
+                       epochs_per_launch: Optional[int] = None, state: Optional[StudyState] = None) -> StudyResult:
+    """``fit_replicates`` for R planar-MNF networks (``make_mnf_replicates``, or hand-built ``mnf.BayesianNetwork((I, O), T,
+    z_flow_type="Planar", r_flow_type="Planar", head="sigmoid")`` of equal dims and transform counts, at most 4 per flow): the
+    loop of LBBNN-GP-MF-MNFsim_study.py:305-395 in one launch per ``epochs_per_launch`` epochs.
+
+    lr / lr_z_flow / lr_r_flow: the rates of the ten named tensors, of the z_flow and of the r_flow parameters (the script's
+    three Adam groups); each one rate, a sequence of ``epochs`` rates, or a device tensor (epochs,) / (R, epochs); None: ``lr``.
+    Every other argument is ``fit_replicates``'.  Replicate r draws eps_z, eps_z2, eps_act and eps_out of its step t from
+    Philox state {seeds[r], offset + t} as layer l1 of the network does.  ``params`` of the result carries every name, the flow
+    parameters as ``z_flow.<t>.u`` / ``.w`` / ``.b`` and ``r_flow.<t>...``; the rows of ``state.exp_avg`` / ``exp_avg_sq`` are as
+    wide as a packed row (``unpack_mnf`` gives the named views).  The trained values, flows included, are copied back into
+    ``nets[r]``: ``freeze``, ``evaluate_batches``, ``structure_posterior`` and ``explain`` go on from there."""
+    def table(R, E, dev):
+        cols = [_lr_table(lr if v is None else v, R, E, dev) for v in (lr, lr_z_flow, lr_r_flow)]
+        if any(c.dim() == 2 for c in cols):
+            cols = [c if c.dim() == 2 else c.unsqueeze(0).expand(R, E) for c in cols]
+        return torch.stack(cols, dim=-1).contiguous()                   # (epochs, 3) or (R, epochs, 3)
+    return _fit(nets, _check_mnf_net, x, y, epochs, batch_size, table, restarts, betas, eps, weight_decay, seeds, offset, priors,
+                epochs_per_launch, state,
+                row_width=lambda key, O, I: mnf_row_width(O, I, *key),
+                launch=lambda key, **kw: ops.mnf_study_fit(Tz=key[0], Tr=key[1], **kw),
+                unpack_rows=lambda key, packed, O, I: unpack_mnf(packed, O, I, *key))
 
 
 def selection_summary(alpha, true_support, true_alpha=None) -> dict:

@@ -2361,6 +2361,51 @@ typedef struct lbbnn_study_args {
 
 int lbbnn_lrt_study_fit(const lbbnn_study_args_t* args, void* stream);
 
+/* lbbnn_mnf_study_fit: the same launch for R one-layer planar-MNF networks I -> O with a sigmoid head (LBBNN-GP-MF-MNFsim_study.py
+ *   with planar flows; lrt_study.hip, the MNF instantiation of the same kernel).  Everything said of
+ *   lbbnn_lrt_study_fit holds -- one workgroup per replicate, no communication, fixed-order sums, the guard, the history --
+ *   with these differences:
+ *   Packed row (params / exp_avg / exp_avg_sq), the order of MNFBayesianLinear._param_list(), P = 3 O I + 2 O + 5 I +
+ *   (Tz + Tr)(2 I + 1):
+ *     [weight_mu | weight_rho | lambdal | bias_mu | bias_rho | q0_mean | q0_log_var | r0_c | r0_b1 | r0_b2 |
+ *      z_flow t = 0 .. Tz - 1: u (I), w (I), b (1) | r_flow t = 0 .. Tr - 1 likewise]
+ *   Draws of a step, Philox state {seed, offset}, layer id 0 -- the draws of layer l1 of an mnf.BayesianNetwork:
+ *     eps_z[i], eps_z2[i]: streams LBBNN_STREAM_EPS_Z * 64 and LBBNN_STREAM_EPS_Z2 * 64, counter (i / 4, 0), word i % 4;
+ *     eps_act[o]: stream LBBNN_STREAM_EPS_ACT * 64, counter (o / 4, 0), word o % 4; eps_out as lbbnn_lrt_study_fit; offset += 1.
+ *   Forward (LBBNN-GP-MF-MNF.py:190-239): z_fwd = zflow(q0_mean + exp(q0_log_var / 2) eps_z), (z_kl, ldq) = zflow(.. eps_z2),
+ *     (zb, ldr) = rflow(z_kl), the batch mean product over x * z_fwd, act_mu[o] = Sum_i r0_c z_kl mu alpha, act_var[o] =
+ *     Sum_i r0_c^2 sigma^2 alpha^2, m = mean_o tanh(act_mu + sqrt(act_var) eps_act), kl = kl_bias + Sum kl_weight(mu z_kl)
+ *     - ldq + log_q0 - ldr - log_rb (log_rb on zb's LAST element).  Tz = 0: z = z0, ldq = 0.
+ *   Backward: weight_pass_bwd.hip's element chain with z_fwd, z_kl and the r0_c terms, vector_bwd.hip's V1 and V2.
+ *   Adam over three rate groups -- 0: the ten named tensors, 1: z_flow, 2: r_flow -- with one step counter: the rate of group
+ *   g in epoch e is lr[((r * lr_rstride) + e) * 3 + g] (lr_rstride 0: one (epochs, 3) table for all; else >= epochs).
+ *   Checks as lbbnn_lrt_study_fit, in its order (NULL, shape, alignment); Tz or Tr outside [0, LBBNN_STUDY_MAX_TRANSFORMS]:
+ *   LBBNN_E_SHAPE. */
+#define LBBNN_STUDY_MAX_TRANSFORMS 4
+typedef struct lbbnn_mnf_study_args {
+    float *params, *exp_avg, *exp_avg_sq;            /* (R, P)                                  */
+    float* step;                                     /* (R)                                     */
+    uint64_t* rng;                                   /* (R, 2): {seed, offset}                  */
+    int64_t* skipped;                                /* (R)                                     */
+    const float* x;                                  /* (N, I) per replicate or shared          */
+    int64_t x_rstride;
+    const float* y;                                  /* (N, O) per replicate or shared          */
+    int64_t y_rstride;
+    const lbbnn_priors_t* priors;                    /* 1 or R rows                             */
+    int priors_rstride;
+    const lbbnn_adam_hyper_t* hyper;                 /* (R)                                     */
+    const float* lr;                                 /* (epochs, 3) or (R, lr_rstride, 3)       */
+    int64_t lr_rstride;
+    const int32_t* restarts;                         /* (n_restarts) epoch indices, or NULL     */
+    int n_restarts;
+    double* history;                                 /* (R, epochs, 6)                          */
+    int R, I, O, N, batch;
+    int epochs, first_epoch, n_epochs;
+    int Tz, Tr;                                      /* transforms of z_flow / r_flow, 0 .. 4   */
+} lbbnn_mnf_study_args_t;
+
+int lbbnn_mnf_study_fit(const lbbnn_mnf_study_args_t* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
